@@ -346,6 +346,9 @@ def main() -> None:
     ap.add_argument("--same-device", action="store_true", help="FUNCTIONAL leg, not a measurement of scaling: the N ranks all use GPU 0 and "
                     "exchange their partials through the peer-mapped buffers (HIP IPC; RCCL refuses two ranks on one device) — exercises "
                     "the self-launch, sharding, forms and watchdog logic of an N > 1 run on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "to its caller (posterior state x, covariance P, measurement passes) as DIR/<name>.npy in float64 (rank 0); the "
+                    "inputs are seeded, so two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
 
     import torch
@@ -506,6 +509,7 @@ def main() -> None:
 
     xg_buf, Pg_buf = np.zeros(26), np.zeros(23 * 23)
     xgp, Pgp = xg_buf.ctypes.data_as(C.c_void_p), Pg_buf.ctypes.data_as(C.c_void_p)
+    last_by_value = []     # (x, P, passes) of the last by-value step timed
 
     def timed_regions(n_regions, form):
         """n_regions regions of exactly K steps each, no instrumentation on the stream, every region bracketed by barrier +
@@ -521,7 +525,9 @@ def main() -> None:
             t0 = time.perf_counter()
             if form == "by_value":
                 for _ in range(args.steps):
-                    tp += upd.update(sc["x_init"], sc["P0"])[2]
+                    r = upd.update(sc["x_init"], sc["P0"])
+                    tp += r[2]
+                last_by_value[:] = r
             elif form == "sync":
                 for _ in range(args.steps):
                     if lib.lv_filter_set(h, x0p, P0p) or lib.lv_correct(h, None) or lib.lv_filter_get(h, xgp, Pgp):
@@ -553,6 +559,11 @@ def main() -> None:
     dt, total_passes = region_dt[mid], region_passes[mid]
     by_value_sync = pipelined = None
     x_res = P_res = None
+    # what the last timed step handed its caller (--dump-outputs), taken before the side legs below run further steps
+    if resident:
+        timed_out = {"x": xg_buf.copy(), "P": Pg_buf.reshape(23, 23).copy(), "passes": ctx.last_passes()}
+    else:
+        timed_out = {"x": last_by_value[0].copy(), "P": last_by_value[1].copy(), "passes": last_by_value[2]}
     if resident:
         x_res, P_res = xg_buf.copy(), Pg_buf.reshape(23, 23).copy()     # the posterior the last timed step read back
 
@@ -1015,6 +1026,10 @@ def main() -> None:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sc, int(total_passes / args.steps))
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in timed_out.items():
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.asarray(a, np.float64))
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     ctx.close()
     if dist is not None:

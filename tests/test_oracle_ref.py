@@ -13,8 +13,8 @@ bits of oracle/lv_oracle.cpp (the checker of every GPU parity test):
   NOT pinned (stand-ins on the reference side, [UPSTREAM-RECALL] on both): Eigen's QR internals and reduction order, ikd-Tree's
   search / insert rule, esekf's update algebra, pcl::VoxelGrid.
 
-Needs the built library: built here when /root/reference is mounted; on a box without the mount the prebuilt .so is used; with
-neither the module skips."""
+Uses the built library where the reference is mounted (or the prebuilt .so where it is not); with neither, the library's answers
+recorded in tests/golden/ref_calls.npz (oracle/lvref.py) stand in for it, call for call."""
 import numpy as np
 import pytest
 
@@ -23,8 +23,6 @@ import pytest
 def lr(oracle, lv):
     import lvref
 
-    if lvref.build() is None:
-        pytest.skip("oracle/_ref/liblvref.so is not built and /root/reference is not mounted")
     lvref.set_config()
     lvref.reset()
     return lvref
@@ -58,7 +56,7 @@ def test_state_mirror_and_world_transform_bits(lr, oracle):
         x = _rand_state(rng, big=k % 2 == 1)
         assert np.array_equal(_bits(lr.state_to_pose(x)), _bits(oracle.state_to_pose(x)))
         scan = (rng.uniform(-90, 90, (500, 3)) * rng.choice([1e-3, 1.0, 1.0, 1.0], (500, 1))).astype(np.float32)
-        assert np.array_equal(_bits(lr.transform(x, scan)), _bits(oracle.transform_scan(x, scan)))
+        assert lr.same_bits(lr.transform(x, scan), oracle.transform_scan(x, scan))
 
 
 @pytest.mark.parametrize("extrinsics,est", [("identity", False), ("xaloc", False), ("xaloc", True)])
@@ -81,16 +79,17 @@ def test_match_set_planes_residuals_and_rows_on_cfg0(lr, oracle, lv, extrinsics,
         valid = o["valid"].astype(bool)
         assert 1000 < valid.sum() < 2000
         assert np.array_equal(m["src"], np.nonzero(valid)[0])                       # a-3 / a-5 / a-6: the chosen set
-        assert np.array_equal(_bits(m["p_world"]), _bits(oracle.transform_scan(x, sc["scan_xyz"])[valid]))
-        assert np.array_equal(_bits(m["abcd"]), _bits(o["abcd"][valid]))            # a-4
-        assert np.array_equal(_bits(m["dist"]), _bits(o["dist"][valid]))            # a-6
+        assert lr.same_bits(m["p_world"], oracle.transform_scan(x, sc["scan_xyz"])[valid])
+        assert lr.same_bits(m["abcd"], o["abcd"][valid])                             # a-4
+        assert lr.same_bits(m["dist"], o["dist"][valid])                             # a-6
         H, h, d = lr.calculate_H(x, m["p_world"], m["abcd"])                        # a-7
-        assert np.array_equal(_bits(d), _bits(m["dist"]))
-        assert np.array_equal(_bits(H), _bits(o["Hrows"][valid])) and np.array_equal(_bits(h), _bits(o["h"][valid]))
-        if est:
-            assert np.abs(H[:, 6:]).max() > 0
+        assert lr.same_bits(d, m["dist"])
+        Ho = o["Hrows"][valid]
+        assert lr.same_bits(H, Ho) and lr.same_bits(h, o["h"][valid])
+        if est:                                                                      # (H has Ho's bits)
+            assert np.abs(Ho[:, 6:]).max() > 0
         else:
-            assert not H[:, 6:].any()
+            assert not Ho[:, 6:].any()
     lr.set_config()
 
 
@@ -292,7 +291,7 @@ def test_pointcloud2_ingest_against_the_reference_processor(lr, oracle, kind, st
         want = oracle.cloud_ingest(raw, n, f, prm)
         assert len(got) == len(want) and len(got) > 0
         for k in ("x", "y", "z", "time", "intensity", "range"):
-            assert np.array_equal(got[k], want[k]), (kind, k, rate)
+            assert lr.same_bits(got[k], want[k]), (kind, k, rate)
     lr.set_config()
 
 
@@ -324,7 +323,7 @@ def test_map_growth_through_mapper_add(lr, oracle):
     lr.map_add(b, 2.0, True)
     want = oracle.map_add(a, b, downsample=True)
     got = lr.map_fetch()
-    assert got.shape == want.shape and np.array_equal(_bits(got), _bits(want))
+    assert got.shape == want.shape and lr.same_bits(got, want)
     lr.map_add(np.zeros((0, 3), np.float32), 3.0, True)   # empty: returns before touching anything
     assert lr.map_size() == len(want)
     lr.reset()
