@@ -184,6 +184,31 @@ typedef struct lv_map_stats {
 } lv_map_stats;
 int    lv_map_get_stats(lv_ctx* ctx, lv_map_stats* out);
 
+/* ---- Map queries ------------------------------------------------------------------------------
+ * ikd-Tree's search calls on the device map, for arbitrary points (the KF update's own search stays inside lv_update /
+ * lv_iterate).  Common rules: queries are map-frame points, f32 x,y,z at offset 0 of each record (stride >= 12, as lv_map_add);
+ * results go to host pointers and are written when the call returns; a call is ordered behind every earlier map mutation (an
+ * insert still in flight on the side stream included) and, during a background rebuild, reads the active store.  Indices are
+ * ranks among the living points (the index space of lv_map_fetch / lv_fetch_knn); distances are the reference's calc_dist
+ * (f32 squared distance, summed left to right, unfused).  An empty map gives LV_OK with nothing found. */
+/* KD_TREE<Point>::Nearest_Search(point, k, Nearest_Points, Point_Distance, max_dist), batched over n queries.  k in 1..32;
+ * row i of idx / d2 (n x k) holds query i's neighbours in ascending (d2, index) order, unfilled slots idx = 0xFFFFFFFF and
+ * d2 = +inf; found[i] = the filled slots.  A point is admitted iff d2 <= max_dist * max_dist (f32 product; +inf: no limit;
+ * negative or NaN: LV_EINVAL).  A query with a non-finite coordinate finds nothing.  Exact for every query (beyond the voxel
+ * range by brute force).  d2 and found may be NULL. */
+int lv_map_knn(lv_ctx* ctx, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx, float* d2, int32_t* found);
+/* KD_TREE<Point>::Radius_Search(point, radius, Storage), batched, CSR output: query i's points are idx[offsets[i] ..
+ * offsets[i + 1]) in ascending index order, every living point with d2 <= radius * radius (f32).  offsets holds n + 1 entries,
+ * *total = offsets[n].  idx == NULL: count only (offsets and *total are written).  capacity < *total: LV_EINVAL, offsets and
+ * *total still written.  Offsets are 64-bit: the count-only call reports any total; one fill returns at most 2^31 - 1 results
+ * (a larger total is LV_EINVAL, offsets and *total still written: split the queries).  n < 2^31 - 1.  d2 may be NULL. */
+int lv_map_radius_search(lv_ctx* ctx, const void* q, size_t stride, size_t n, float radius, size_t* offsets, uint32_t* idx, float* d2,
+                         size_t capacity, size_t* total);
+/* KD_TREE<Point>::Box_Search(BoxPointType, Storage): the living points inside [lo, hi] with lv_map_evict_box's predicate (both
+ * faces inclusive) in ascending index order — exactly what lv_map_evict_box(lo, hi, keep_inside = 0) would remove.  xyz: 3
+ * floats per point, may be NULL; idx and xyz both NULL: count only.  Capacity as in lv_map_radius_search (*n_out = the count). */
+int lv_map_box_search(lv_ctx* ctx, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity, size_t* n_out);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -29,7 +29,18 @@ ABI_SYMBOLS = [
     "lv_set_capture", "lv_fetch_knn", "lv_fetch_matches", "lv_fetch_neighbors", "lv_set_record_dump", "lv_last_update_fused", "lv_last_passes", "lv_set_fused_pass", "lv_set_option", "lv_get_pass_clocks", "lv_pass_geometry", "lv_fetch_rows", "lv_calculate_H", "lv_get_timing", "lv_set_profiling", "lv_get_phase_clocks", "lv_get_solve_clocks", "lv_get_level_histogram",
     "lv_comm_unique_id", "lv_comm_init", "lv_comm_destroy", "lv_comm_world", "lv_comm_set_shard_max", "lv_set_comm_fused", "lv_comm_set_host_gather", "lv_comm_peer_export", "lv_comm_peer_init",
     "lv_cloud_format_preset", "lv_cloud_ingest", "lv_cloud_size", "lv_cloud_fetch", "lv_cloud_clear", "lv_cloud_reserve", "lv_reserve_stream", "lv_scan_deskew_window",
+    "lv_map_knn", "lv_map_radius_search", "lv_map_box_search",
 ]
+
+# ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
+QUERY_ARGTYPES = {
+    "lv_map_knn": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                   C.POINTER(C.c_int32)],
+    "lv_map_radius_search": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32),
+                             C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)],
+    "lv_map_box_search": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t,
+                          C.POINTER(C.c_size_t)],
+}
 
 
 def pseudo_measurement(sums: dict, estimate_extrinsics: bool):
@@ -165,6 +176,9 @@ def load_library() -> C.CDLL:
         lib.lv_destroy.restype = None
         lib.lv_destroy.argtypes = [C.c_void_p]
         lib.lv_default_params.restype = None
+        for name, argtypes in QUERY_ARGTYPES.items():
+            getattr(lib, name).argtypes = argtypes
+            getattr(lib, name).restype = C.c_int
         _lib = lib
     return _lib
 
@@ -280,6 +294,56 @@ class Context:
         out = np.empty((n, 3), np.float32)
         self._check(self.lib.lv_map_fetch(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(n)))
         return out
+
+    # --- map queries (ikd-Tree Nearest_Search / Radius_Search / Box_Search)
+    def map_knn(self, q, k, max_dist=np.inf):
+        """(idx [n, k] uint32, d2 [n, k] float32, found [n] int32): the k nearest living points of every query, ascending
+        (d2, index); unfilled slots 0xFFFFFFFF / +inf.  Indices are ranks among the living (map_fetch order)."""
+        a, stride, n = _points(q)
+        kk = max(int(k), 1)   # (an out-of-range k still goes to the library, which refuses it)
+        idx = np.empty((n, kk), np.uint32)
+        d2 = np.empty((n, kk), np.float32)
+        found = np.empty(n, np.int32)
+        self._check(self.lib.lv_map_knn(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n), int(k), C.c_float(max_dist),
+                                        idx.ctypes.data_as(C.POINTER(C.c_uint32)), d2.ctypes.data_as(C.POINTER(C.c_float)),
+                                        found.ctypes.data_as(C.POINTER(C.c_int32))))
+        return idx, d2, found
+
+    def map_radius_count(self, q, radius):
+        """(offsets [n + 1] uint64, total): the count-only form of lv_map_radius_search."""
+        a, stride, n = _points(q)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_size_t(0)
+        self._check(self.lib.lv_map_radius_search(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n), C.c_float(radius),
+                                                  off.ctypes.data_as(C.POINTER(C.c_size_t)), None, None, C.c_size_t(0), C.byref(total)))
+        return off, int(total.value)
+
+    def map_radius(self, q, radius):
+        """(offsets [n + 1], idx [total] uint32, d2 [total] float32), CSR: query i's points are idx[offsets[i]:offsets[i + 1]],
+        ascending index.  Counts first, then fills."""
+        a, stride, n = _points(q)
+        off, total = self.map_radius_count(a, radius)
+        idx = np.empty(total, np.uint32)
+        d2 = np.empty(total, np.float32)
+        t = C.c_size_t(0)
+        self._check(self.lib.lv_map_radius_search(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n), C.c_float(radius),
+                                                  off.ctypes.data_as(C.POINTER(C.c_size_t)), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  d2.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(total), C.byref(t)))
+        return off, idx, d2
+
+    def map_box(self, lo, hi):
+        """(idx [n] uint32, xyz [n, 3] float32): the living points inside [lo, hi] (faces inclusive), ascending index."""
+        lo = np.ascontiguousarray(lo, np.float32)
+        hi = np.ascontiguousarray(hi, np.float32)
+        fp = C.POINTER(C.c_float)
+        cnt = C.c_size_t(0)
+        self._check(self.lib.lv_map_box_search(self.h, lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), None, None, C.c_size_t(0), C.byref(cnt)))
+        n = int(cnt.value)
+        idx = np.empty(n, np.uint32)
+        xyz = np.empty((n, 3), np.float32)
+        self._check(self.lib.lv_map_box_search(self.h, lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               xyz.ctypes.data_as(fp), C.c_size_t(n), C.byref(cnt)))
+        return idx[: int(cnt.value)], xyz[: int(cnt.value)]
 
     # --- Localizator side
     def scan_set(self, pts):

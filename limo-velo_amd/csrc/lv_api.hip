@@ -40,6 +40,7 @@ struct lv_ctx {
     hipStream_t stream = nullptr;
 
     MapStore map;
+    QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
     // ---- background re-linearisation of the map (row f-1; ikd-Tree rebuilds beside its searches too: the tree is constructed with
     // delete / balance criteria 0.3 / 0.6, src/Modules/Mapper.cpp:65, and rebuilds sub-trees on a second thread).  When the
     // active map wants a compaction (MapStore::wants_relinearise: a third of its id space is dead) and holds at least
@@ -799,6 +800,7 @@ void lv_destroy(lv_ctx* c) {
     hipDeviceSynchronize();
     c->map.release();
     c->relin_shadow.release();
+    c->query.release();
     if (c->relin_arena) hipFree(c->relin_arena);
     if (c->relin_stream) hipStreamDestroy(c->relin_stream);
     if (c->relin_snapshot) hipEventDestroy(c->relin_snapshot);
@@ -1385,6 +1387,30 @@ int lv_map_fetch(lv_ctx* c, float* xyz_out, size_t capacity) {
     }
     if (o != m) { set_error("map bookkeeping: %zu living points found, %zu expected", o, m); return LV_ESTATE; }
     return LV_OK;
+}
+
+// Map queries (lv_query.hip): ordered behind every earlier map mutation — the insert in flight on the side stream (settle) and a
+// finished background rebuild (adopted by relin_poll) — and read the active store
+int lv_map_knn(lv_ctx* c, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx, float* d2, int32_t* found) {
+    LV_CHECK_CTX(c);
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return c->query.knn(c->map, c->stream, q, stride, n, k, max_dist, idx, d2, found);
+}
+
+int lv_map_radius_search(lv_ctx* c, const void* q, size_t stride, size_t n, float radius, size_t* offsets, uint32_t* idx, float* d2,
+                         size_t capacity, size_t* total) {
+    LV_CHECK_CTX(c);
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return c->query.radius(c->map, c->stream, q, stride, n, radius, offsets, idx, d2, capacity, total);
+}
+
+int lv_map_box_search(lv_ctx* c, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity, size_t* n_out) {
+    LV_CHECK_CTX(c);
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return c->query.box(c->map, c->stream, lo, hi, idx, xyz, capacity, n_out);
 }
 
 int lv_scan_set(lv_ctx* c, const void* points, size_t stride, size_t n) {

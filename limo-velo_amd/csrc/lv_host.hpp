@@ -188,6 +188,41 @@ struct MapStore {
     void refresh_view();
     void stats(MapStats* out) const;
     void release();
+    // stamp of the map as it stands: refresh_view (which every build, insert, eviction, re-linearisation and store swap ends with)
+    // draws a new one from a process-wide counter, so two states of a map — or two stores — never share one (QueryStore::ensure_rank)
+    uint64_t gen = 0;
+};
+
+// Map queries (lv_query.hip): batched k-NN / radius / box searches of arbitrary points against the active store.  Owns its staging
+// and result buffers (grown on demand, freed by release); nothing here is shared with the update or the background rebuild.
+struct QueryStore {
+    float* d_q = nullptr;          // queries, packed xyz
+    uint32_t* d_idx = nullptr;     // k-NN: n x k results; radius: the ids found; box: the ranks found
+    float* d_d2 = nullptr;         // k-NN / radius: their distances; box: their xyz
+    int32_t* d_found = nullptr;
+    uint32_t* d_idx2 = nullptr;    // radius: the segmented sort's output
+    float* d_d22 = nullptr;
+    uint32_t* d_off = nullptr;     // box: positions (n_ids + 1)
+    uint32_t* d_cnt = nullptr;     // box: flags by id
+    uint64_t* d_roff = nullptr;    // radius: per-query counts -> exclusive offsets of the queries' segments (n + 1), 64-bit
+    uint64_t* d_rcnt = nullptr;
+    void* d_tmp = nullptr;         // hipcub scratch
+    uint32_t* d_rank = nullptr;    // rank among the living by id, valid for the map whose stamp is rank_gen
+    uint32_t* d_flag = nullptr;
+    size_t q_cap = 0, idx_cap = 0, d2_cap = 0, found_cap = 0, idx2_cap = 0, d22_cap = 0, off_cap = 0, cnt_cap = 0, roff_cap = 0, rcnt_cap = 0, tmp_cap = 0, rank_cap = 0,
+           flag_cap = 0;
+    uint64_t rank_gen = 0;
+    uint32_t* h_word = nullptr;    // pinned: a total read back by the host
+    int stage_queries(hipStream_t stream, const void* q, size_t stride, size_t n);
+    // nullptr when ranks equal ids (no dead id); else d_rank, rebuilt when the map's stamp moved
+    int ensure_rank(const MapStore& map, hipStream_t stream, const uint32_t** rank);
+    int knn(const MapStore& map, hipStream_t stream, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx, float* d2,
+            int32_t* found);
+    int radius(const MapStore& map, hipStream_t stream, const void* q, size_t stride, size_t n, float radius, size_t* offsets, uint32_t* idx,
+               float* d2, size_t capacity, size_t* total);
+    int box(const MapStore& map, hipStream_t stream, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity,
+            size_t* n_out);
+    void release();
 };
 
 // lv_comm.hip — RCCL bound at run time (row e)

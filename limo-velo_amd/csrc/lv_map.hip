@@ -16,6 +16,7 @@
 #include "lv_ldssort.hpp"
 
 #include <cstddef>
+#include <atomic>
 #include <cstring>
 
 #include <hipcub/hipcub.hpp>
@@ -601,7 +602,10 @@ void MapStore::release() {
     *this = MapStore();
 }
 
+static std::atomic<uint64_t> g_map_gen{0};
+
 void MapStore::refresh_view() {
+    gen = ++g_map_gen;
     view.orig = d_orig;
     view.m = built ? m : 0u;
     view.n_ids = n_ids;

@@ -35,51 +35,10 @@
 #ifndef LV_QR_SELECT
 #define LV_QR_SELECT 1    // plane_qr_solve: selects instead of branches (tiny-tail case, norm downdate, Q^T c, back substitution)
 #endif
+#include "lv_search_dev.hpp"   // keys, calc_dist, QGeom / search_radius / block_radius (shared with lv_query.hip)
 
 namespace lv {
 
-// Candidate keys.  A key packs (f32 distance bits << 32 | position) and is handled as an IEEE f64:
-// for non-negative distances the f64 order of the bit pattern equals the unsigned order, so ONE
-// v_min_f64 / v_max_f64 pair is a compare-exchange on the (distance, position) pair.  Inside a bucket
-// the points are stored in ascending ORIGINAL index, so (distance, position) order == the reference's
-// (distance, index) order, ties included; the generic path uses (distance, index) directly.
-// NONE = largest finite f64 (its high word 0x7FEFFFFF is an f32 NaN pattern no distance produces;
-// no key is ever an f64 NaN/inf because valid distance bits are <= 0x7F800000).
-typedef double kkey;
-__device__ __forceinline__ kkey make_key(float d, uint32_t low) {
-    return __longlong_as_double((long long)(((uint64_t)__float_as_uint(d) << 32) | (uint64_t)low));
-}
-// the key of a candidate slot that may lie behind the end of its run: selects, not a branch around the distance arithmetic (the
-// compiler turns `ok ? make_key(calc_dist(...), j) : none_key()` into an exec-mask region per candidate: save / branch / wait /
-// restore around eight instructions).  Level-0 stream: search phase 13.4 -> 13.2 us per launch; level 1: see bucket_attempt
-// (the loads have to be pinned in front of the arithmetic there).
-__device__ __forceinline__ kkey make_key_if(bool ok, float d, uint32_t low) {
-    const uint32_t hi = ok ? __float_as_uint(d) : 0x7FEFFFFFu;
-    const uint32_t lo = ok ? low : 0xFFFFFFFFu;
-    return __hiloint2double((int)hi, (int)lo);
-}
-__device__ __forceinline__ uint32_t key_lo(kkey k) { return (uint32_t)(uint64_t)__double_as_longlong(k); }
-__device__ __forceinline__ uint32_t key_hi(kkey k) { return (uint32_t)((uint64_t)__double_as_longlong(k) >> 32); }
-#define LV_NONE_BITS 0x7FEFFFFFFFFFFFFFll
-__device__ __forceinline__ kkey none_key() { return __longlong_as_double(LV_NONE_BITS); }
-__device__ __forceinline__ bool is_none(kkey k) { return __double_as_longlong(k) == LV_NONE_BITS; }
-
-
-__device__ __forceinline__ kkey kmin(kkey a, kkey b) {
-    kkey r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ kkey kmax(kkey a, kkey b) {
-    kkey r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ void cswap(kkey& a, kkey& b) {
-    const kkey lo = kmin(a, b), hi = kmax(a, b);
-    a = lo;
-    b = hi;
-}
 // Batcher odd-even merge sort, 8 keys, 19 comparators (verified exhaustively with the 0-1 principle)
 __device__ __forceinline__ void sort8(kkey (&c)[8]) {
     cswap(c[0], c[1]); cswap(c[2], c[3]); cswap(c[4], c[5]); cswap(c[6], c[7]);
@@ -145,22 +104,6 @@ __device__ __forceinline__ void merge_group(kkey (&k)[K]) {
     if (S >= 4) merge_round<0x4E>(k);
     if (S >= 8) merge_round<0x141>(k);
     if (S >= 16) merge_round<0x140>(k);
-}
-// [UPSTREAM-RECALL ikd-Tree calc_dist]: (ax-bx)^2 + (ay-by)^2 + (az-bz)^2, f32, left to right, unfused
-struct __attribute__((packed, aligned(4))) Xyz {   // one bucket point as streamed: 12 bytes
-    float x, y, z;
-};
-__device__ __forceinline__ float calc_dist(float qx, float qy, float qz, Xyz m) {
-    float dx = qx - m.x, dy = qy - m.y, dz = qz - m.z;
-    float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    float s = sx + sy;
-    return s + sz;
-}
-__device__ __forceinline__ float calc_dist(float qx, float qy, float qz, float4 m) {
-    float dx = qx - m.x, dy = qy - m.y, dz = qz - m.z;
-    float sx = dx * dx, sy = dy * dy, sz = dz * dz;
-    float s = sx + sy;
-    return s + sz;
 }
 
 // Column-pivoted Householder QR least squares for the K x 3 system A n = -1 (K = NUM_MATCH_POINTS: 5 on the tuned paths), f32.  Same operation
@@ -387,41 +330,6 @@ __device__ inline void plane_qr_solve(float (&A)[K][3], float (&x)[3]) {
     }
 }
 
-// Voxel geometry of one query: continuous and integer level-0 voxel coordinates.
-struct QGeom {
-    float tx, ty, tz;
-    int c0x, c0y, c0z, amax;
-};
-__device__ __forceinline__ QGeom make_geom(const MapView& map, float qx, float qy, float qz) {
-    QGeom g;
-    g.tx = (qx - map.origin[0]) * map.inv_cell;
-    g.ty = (qy - map.origin[1]) * map.inv_cell;
-    g.tz = (qz - map.origin[2]) * map.inv_cell;
-    g.c0x = cell_coord(qx, map.origin[0], map.inv_cell);
-    g.c0y = cell_coord(qy, map.origin[1], map.inv_cell);
-    g.c0z = cell_coord(qz, map.origin[2], map.inv_cell);
-    g.amax = max(abs(g.c0x - CELL_OFFSET), max(abs(g.c0y - CELL_OFFSET), abs(g.c0z - CELL_OFFSET)));
-    return g;
-}
-// guaranteed search radius of the 27-voxel block at `lvl` for THIS query: one voxel edge plus the distance to
-// the nearest wall of its own voxel, shrunk by 1e-3 relative and by the f32 rounding bound of the voxel
-// coordinates (see file header).
-__device__ __forceinline__ float search_radius(const MapView& map, const QGeom& g, int lvl) {
-    const float scale = (float)(1 << lvl);
-    const float bx = (float)((((g.c0x >> lvl) << lvl)) - CELL_OFFSET), by = (float)((((g.c0y >> lvl) << lvl)) - CELL_OFFSET),
-                bz = (float)((((g.c0z >> lvl) << lvl)) - CELL_OFFSET);
-    const float mx = fminf(g.tx - bx, scale - (g.tx - bx)), my = fminf(g.ty - by, scale - (g.ty - by)),
-                mz = fminf(g.tz - bz, scale - (g.tz - bz));
-    const float marg = fmaxf(fminf(mx, fminf(my, mz)), 0.f);
-    return map.cell * ((scale + marg) * 0.999f - 8.f * 1.1920928955078125e-07f * ((float)g.amax + 2.f * scale));
-}
-
-__device__ __forceinline__ kkey shfl_xor_key(kkey v, int mask) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, mask);
-    hi = __shfl_xor(hi, mask);
-    return __hiloint2double(hi, lo);
-}
 // all-reduce of the sorted top-5 lists over a team of LANES consecutive lanes (LANES <= 16: merge_group over
 // DPP; 64: the whole wavefront, the two cross-row rounds go through ds_bpermute)
 template <int LANES, int K>
@@ -440,9 +348,6 @@ __device__ __forceinline__ void merge_team(kkey (&k)[K]) {
     }
 }
 
-// a candidate key stands for a real point iff its distance is finite (NONE and the +inf distance of deleted
-// entries / ids are not)
-__device__ __forceinline__ bool key_real(kkey k) { return key_hi(k) < 0x7F800000u; }
 
 // k, o sorted ascending -> k = the K smallest of the union (merge5), drop = min(drop, the distances that left)
 template <int K, typename T>
@@ -471,11 +376,6 @@ __device__ __forceinline__ void merge_team_drop(kkey (&k)[K], uint32_t& drop) { 
     if (LANES >= 4) merge_round_drop<0x4E>(k, drop);
     if (LANES >= 8) merge_round_drop<0x141>(k, drop);
     if (LANES >= 16) merge_round_drop<0x140>(k, drop);
-}
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // One bucket-level attempt by a team of LANES lanes (tl = lane in team): ONE probe of the level's bucket table
@@ -611,15 +511,6 @@ __device__ __forceinline__ bool bucket_attempt(const MapView& map, int bl, const
 // that extends it, on every axis, on the side of the voxel wall the query is nearer to (SIDE 4: covers 3 m where the 3-block
 // covers between 2 and 3 — taken by the timed launches when the 3-block cannot certify MAX_DIST_PLANE); the 216 lists that tile
 // the level-3 block (SIDE 6, capturing launches).
-// guaranteed radius of a block of `side` level-`lvl` voxels per axis whose lower corner is voxel (bx, by, bz) (level-lvl voxel
-// coordinates) for THIS query: the distance to the nearest face, shrunk like search_radius
-__device__ __forceinline__ float block_radius(const MapView& map, const QGeom& g, int lvl, int bx, int by, int bz, int side) {
-    const float lox = (float)((bx << lvl) - CELL_OFFSET), loy = (float)((by << lvl) - CELL_OFFSET), loz = (float)((bz << lvl) - CELL_OFFSET);
-    const float ext = (float)(side << lvl);
-    const float mx = fminf(g.tx - lox, lox + ext - g.tx), my = fminf(g.ty - loy, loy + ext - g.ty), mz = fminf(g.tz - loz, loz + ext - g.tz);
-    const float m = fmaxf(fminf(mx, fminf(my, mz)), 0.f);
-    return map.cell * (m * 0.999f - 8.f * 1.1920928955078125e-07f * ((float)g.amax + 2.f * ext));
-}
 template <int K>
 __device__ __forceinline__ bool cells_attempt(const MapView& map, int bx, int by, int bz, int SIDE, float r, float qx, float qy, float qz, int lane,
                                               kkey (&k)[K], uint32_t* s_pref, uint32_t* s_start, const QGeom* geo = nullptr, uint32_t bound = 0x7FFFFFFFu) {

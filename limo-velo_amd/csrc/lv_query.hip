@@ -1,0 +1,530 @@
+// lv_query.hip — map queries: batched k-NN, radius and box searches of arbitrary map-frame points against the device map
+// (ikd-Tree's Nearest_Search / Radius_Search / Box_Search, which the update's own search does not expose).
+//
+// k-NN (query_knn_kernel): ONE wavefront per query walks the ladder of the update's search (lv_match.hip) —
+//   level 0  the query voxel's neighbourhood bucket (one contiguous id-sorted run of 12-byte points),
+//   level 1  the region of its tile group while the group is in one piece (extent > 0),
+//   level 2  the 27 level-2 voxel lists around it,
+//   level 3  the 216 lists that tile the level-3 block,
+//   finally  every id,
+// with the acceptance rule generalised from 5 to k and to a caller's max_dist: level l is accepted iff
+//   (k admitted candidates and d_k < r_l^2)  or  max_dist^2 < r_l^2  (every admissible point lies inside the block),
+// otherwise the next level is searched from scratch.  Keys are (d2 bits << 32 | id) handled as f64 (lv_search_dev.hpp: one
+// v_min_f64 / v_max_f64 pair is a compare-exchange), so key order is the oracle's (distance, index) order, ties included.  The
+// running top-k is one key per lane, ascending over the lanes (k <= 32 < 64): a chunk of 64 candidates (one per lane) that holds
+// no key below the k-th is skipped by one ballot; otherwise it is sorted by a 21-step bitonic network over __shfl_xor, merged
+// by min(top[i], chunk[63 - i]) (the 64 smallest of the union, bitonic) and cleaned up by 6 bitonic steps.  No LDS except the
+// 2 x 64 words of list offsets a wavefront needs on the list levels.
+//
+// Radius: a count kernel and a fill kernel walk the same source per query — the level-0 run if the radius is inside the level-0
+// radius bound, else the level-2 lists covering [q - r, q + r] (one list of margin per side), else (more lists than ids, or
+// outside the voxel range) every id — with an exclusive scan of the counts in between; the segments are then sorted by id
+// (hipcub segmented radix sort).  Box: one pass over the ids with inc_evict_box_kernel's predicate, a scan, a scatter in id order.
+// Results carry ids until the end; the rank among the living comes from a device scan of the alive flags (QueryStore::ensure_rank),
+// rebuilt only when the map's stamp (MapStore::gen) moved and skipped when no id is dead.
+#include "lv_search_dev.hpp"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace lv {
+
+namespace {
+
+constexpr int QWAVES = 4;                          // wavefronts (queries) per workgroup
+constexpr int QTHREADS = QWAVES * 64;
+constexpr uint32_t NO_IDX = 0xFFFFFFFFu;
+// hipcub counts the items of a scan / sort in an int: the largest query batch, id range or result set handed to one
+constexpr int SCAN_MAX = 0x7FFFFFFF;
+
+__device__ __forceinline__ kkey shfl_key(kkey v, int src) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl(lo, src);
+    hi = __shfl(hi, src);
+    return __hiloint2double(hi, lo);
+}
+// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
+__device__ __forceinline__ bool q_alive(const float4& p) { return p.x < __uint_as_float(0x7F800000u) && p.x > -__uint_as_float(0x7F800000u); }
+// a candidate is admitted iff its distance is finite (tombstones and slack read x = +inf) and d2 <= max_d2
+__device__ __forceinline__ bool admitted(float d, float max_d2) { return __float_as_uint(d) < 0x7F800000u && d <= max_d2; }
+
+// ascending bitonic sort of one key per lane over the 64 lanes
+__device__ __forceinline__ kkey wave_sort64(kkey v, int lane) {
+#pragma unroll
+    for (int s = 2; s <= 64; s <<= 1) {
+#pragma unroll
+        for (int j = s >> 1; j > 0; j >>= 1) {
+            const kkey o = shfl_xor_key(v, j);
+            const bool up = (lane & s) == 0, lower = (lane & j) == 0;
+            v = (lower == up) ? kmin(v, o) : kmax(v, o);
+        }
+    }
+    return v;
+}
+
+// the running top-k of one query: top ascending over the lanes; kth = the k-th smallest so far (NONE while fewer)
+struct TopK {
+    kkey top;
+    kkey kth;
+    int k;
+    __device__ __forceinline__ void reset() {
+        top = none_key();
+        kth = none_key();
+    }
+    // one chunk: every lane offers one candidate key (NONE = nothing)
+    __device__ __forceinline__ void offer(kkey c, int lane) {
+        if (__ballot(c < kth) == 0ull) return;
+        const kkey s = wave_sort64(c, lane);
+        kkey v = kmin(top, shfl_key(s, 63 - lane));
+#pragma unroll
+        for (int j = 32; j > 0; j >>= 1) {
+            const kkey o = shfl_xor_key(v, j);
+            v = (lane & j) == 0 ? kmin(v, o) : kmax(v, o);
+        }
+        top = v;
+        kth = shfl_key(top, k - 1);
+    }
+    // the level's acceptance rule (file header)
+    __device__ __forceinline__ bool accept(float r, float max_d2) const {
+        if (!(r > 0.f)) return false;
+        const float rr = r * r;
+        return (!is_none(kth) && __uint_as_float(key_hi(kth)) < rr) || max_d2 < rr;
+    }
+};
+
+// hash probe of one grid table: {start, count} of the entry whose key is `key`, count 0 if absent
+__device__ __forceinline__ uint2 probe(const GridLevel& g, uint64_t key) {
+    if (!g.table) return make_uint2(0u, 0u);
+    uint32_t slot = hash_cell(key, g.shift) & g.mask;
+    for (;;) {
+        const uint4 e = g.table[slot];
+        const uint64_t ek = (uint64_t)e.x | ((uint64_t)e.y << 32);
+        if (ek == key) return make_uint2(e.z, e.w);
+        if (ek == EMPTY_KEY) return make_uint2(0u, 0u);
+        slot = (slot + 1) & g.mask;
+    }
+}
+
+// a run of level-0 storage (bucket or tile-group region): visit(x, y, z, id, ok) for 64 entries at a time
+template <class F>
+__device__ __forceinline__ void stream_run(const MapView& map, uint32_t start, uint32_t count, int lane, F&& visit) {
+    const Xyz* __restrict__ bp = reinterpret_cast<const Xyz*>(map.bxyz[0]) + start;
+    const uint32_t* __restrict__ ip = map.bidx[0] + start;
+    for (uint32_t base = 0; base < count; base += 64) {
+        const uint32_t j = base + (uint32_t)lane;
+        const bool ok = j < count;
+        const Xyz p = bp[ok ? j : 0];
+        const uint32_t id = ip[ok ? j : 0];
+        visit(p.x, p.y, p.z, id, ok);
+    }
+}
+
+// every id
+template <class F>
+__device__ __forceinline__ void stream_all(const MapView& map, int lane, F&& visit) {
+    for (uint32_t base = 0; base < map.n_ids; base += 64) {
+        const uint32_t j = base + (uint32_t)lane;
+        const bool ok = j < map.n_ids;
+        const float4 p = map.orig[ok ? j : 0];
+        visit(p.x, p.y, p.z, j, ok);
+    }
+}
+
+// the level-2 voxel lists of the box [b, b + s) (level-2 voxel coordinates), 64 lists per round: every lane probes one, a wave
+// scan turns the lengths into one virtual candidate array, each lane finds its list by binary search over the prefix sums
+// (s_pref / s_start: 64 words each, private to this wavefront)
+template <class F>
+__device__ __forceinline__ void stream_lists(const MapView& map, int bx, int by, int bz, int sx, int sy, int sz, int lane, uint32_t* s_pref,
+                                             uint32_t* s_start, F&& visit) {
+    const uint32_t nc = (uint32_t)sx * (uint32_t)sy * (uint32_t)sz;
+    for (uint32_t r0 = 0; r0 < nc; r0 += 64) {
+        const uint32_t ci = r0 + (uint32_t)lane;
+        uint32_t start = 0, cnt = 0;
+        if (ci < nc) {
+            const uint32_t dx = ci % (uint32_t)sx, dy = (ci / (uint32_t)sx) % (uint32_t)sy, dz = ci / ((uint32_t)sx * (uint32_t)sy);
+            const uint32_t nx = (uint32_t)bx + dx, ny = (uint32_t)by + dy, nz = (uint32_t)bz + dz;
+            if (nx < (1u << 19) && ny < (1u << 19) && nz < (1u << 19)) {
+                const uint2 e = probe(map.ct, pack_cell(nx, ny, nz));
+                start = e.x;
+                cnt = e.y;
+            }
+        }
+        uint32_t incl = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t v = __shfl_up(incl, off);
+            if (lane >= off) incl += v;
+        }
+        const uint32_t total = __shfl(incl, 63);
+        if (total == 0) continue;
+        wave_lds_fence();   // the previous round's readers are done
+        s_pref[lane] = incl - cnt;
+        s_start[lane] = start;
+        wave_lds_fence();
+        for (uint32_t base = 0; base < total; base += 64) {
+            const uint32_t v = base + (uint32_t)lane;
+            const bool ok = v < total;
+            const uint32_t vv = ok ? v : 0u;
+            int L = 0;   // the last list whose first virtual index is <= vv (empty lists share their successor's)
+#pragma unroll
+            for (int step = 32; step >= 1; step >>= 1) L += s_pref[L + step] <= vv ? step : 0;
+            const float4 p = map.cell4[s_start[L] + (vv - s_pref[L])];
+            visit(p.x, p.y, p.z, __float_as_uint(p.w), ok);
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t to_rank(const uint32_t* rank, uint32_t id) { return rank ? rank[id] : id; }
+
+__global__ __launch_bounds__(QTHREADS) void query_knn_kernel(MapView map, const float* __restrict__ q, uint32_t n, int k, float max_d2,
+                                                             const uint32_t* __restrict__ rank, uint32_t* __restrict__ idx,
+                                                             float* __restrict__ d2, int32_t* __restrict__ found) {
+    __shared__ uint32_t s_pref[QWAVES][64], s_start[QWAVES][64];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const uint32_t qi = blockIdx.x * (uint32_t)QWAVES + (uint32_t)w;
+    if (qi >= n) return;   // (wavefront-uniform)
+    const float qx = q[3 * (size_t)qi], qy = q[3 * (size_t)qi + 1], qz = q[3 * (size_t)qi + 2];
+    TopK t;
+    t.k = k;
+    t.reset();
+    const bool finite = __builtin_isfinite(qx) && __builtin_isfinite(qy) && __builtin_isfinite(qz);
+    if (map.m != 0 && finite) {
+        auto visit = [&](float x, float y, float z, uint32_t id, bool ok) {
+            const float d = calc_dist(qx, qy, qz, Xyz{x, y, z});
+            t.offer(ok && admitted(d, max_d2) ? make_key(d, id) : none_key(), lane);
+        };
+        const QGeom geo = make_geom(map, qx, qy, qz);
+        bool done = false;
+        if (geo.amax < CELL_FAR) {
+            const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
+            stream_run(map, b0.x, b0.y, lane, visit);
+            done = t.accept(search_radius(map, geo, 0), max_d2);
+            if (!done) {
+                const uint2 g1 = probe(map.gt, pack_cell((uint32_t)(geo.c0x >> 1), (uint32_t)(geo.c0y >> 1), (uint32_t)(geo.c0z >> 1)));
+                if (g1.y > 0) {   // (extent 0: the group is not in one piece)
+                    t.reset();
+                    stream_run(map, g1.x, g1.y, lane, visit);
+                    done = t.accept(search_radius(map, geo, 1), max_d2);
+                }
+            }
+            if (!done) {
+                t.reset();
+                stream_lists(map, (geo.c0x >> 2) - 1, (geo.c0y >> 2) - 1, (geo.c0z >> 2) - 1, 3, 3, 3, lane, s_pref[w], s_start[w], visit);
+                done = t.accept(search_radius(map, geo, 2), max_d2);
+            }
+            if (!done) {
+                t.reset();
+                stream_lists(map, ((geo.c0x >> 3) - 1) * 2, ((geo.c0y >> 3) - 1) * 2, ((geo.c0z >> 3) - 1) * 2, 6, 6, 6, lane, s_pref[w], s_start[w],
+                             visit);
+                done = t.accept(search_radius(map, geo, 3), max_d2);
+            }
+        }
+        if (!done) {
+            t.reset();
+            stream_all(map, lane, visit);
+        }
+    }
+    const bool real = !is_none(t.top) && lane < k;
+    if (lane < k) {
+        idx[(size_t)qi * k + lane] = real ? to_rank(rank, key_lo(t.top)) : NO_IDX;
+        if (d2) d2[(size_t)qi * k + lane] = real ? __uint_as_float(key_hi(t.top)) : __uint_as_float(0x7F800000u);
+    }
+    const int nf = __popcll(__ballot(real));
+    if (found && lane == 0) found[qi] = nf;
+}
+
+// radius search of one query (one wavefront); FILL = false: count, true: write the ids / distances from out_off on
+template <bool FILL>
+__global__ __launch_bounds__(QTHREADS) void query_radius_kernel(MapView map, const float* __restrict__ q, uint32_t n, float radius,
+                                                                uint64_t* __restrict__ counts, const uint64_t* __restrict__ off,
+                                                                uint32_t* __restrict__ out_id, float* __restrict__ out_d2) {
+    __shared__ uint32_t s_pref[QWAVES][64], s_start[QWAVES][64];
+    const int lane = (int)(threadIdx.x & 63u), w = (int)(threadIdx.x >> 6);
+    const uint32_t qi = blockIdx.x * (uint32_t)QWAVES + (uint32_t)w;
+    if (qi >= n) return;
+    const float qx = q[3 * (size_t)qi], qy = q[3 * (size_t)qi + 1], qz = q[3 * (size_t)qi + 2];
+    const float r2 = radius * radius;
+    uint32_t got = 0;
+    // (64-bit offsets: a call's total may pass 2^32 even though one query finds at most n_ids points)
+    const uint64_t base = FILL ? off[qi] : 0ull, room = FILL ? off[qi + 1] - off[qi] : 0ull;
+    const uint64_t below = (1ull << lane) - 1ull;
+    auto visit = [&](float x, float y, float z, uint32_t id, bool ok) {
+        const float d = calc_dist(qx, qy, qz, Xyz{x, y, z});
+        const bool hit = ok && admitted(d, r2);
+        const unsigned long long b = __ballot(hit);
+        if (FILL && hit) {
+            const uint32_t p = got + (uint32_t)__popcll(b & below);
+            if (p < room) {
+                out_id[base + p] = id;
+                out_d2[base + p] = d;
+            }
+        }
+        got += (uint32_t)__popcll(b);
+    };
+    const bool finite = __builtin_isfinite(qx) && __builtin_isfinite(qy) && __builtin_isfinite(qz);
+    if (map.m != 0 && finite) {
+        const QGeom geo = make_geom(map, qx, qy, qz);
+        bool lists = false;
+        int lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};
+        if (geo.amax < CELL_FAR) {
+            if (radius < search_radius(map, geo, 0)) {   // every point within the radius lies in the level-0 block
+                const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
+                stream_run(map, b0.x, b0.y, lane, visit);
+                if (!FILL && lane == 0) counts[qi] = got;
+                return;
+            }
+            // the level-2 lists covering [q - r, q + r], one list of margin per side for the rounding of the voxel coordinates
+            const float qq[3] = {qx, qy, qz};
+            uint64_t nl = 1;
+            bool fits = true;
+            for (int a = 0; a < 3; ++a) {
+                const int l = (cell_coord(qq[a] - radius, map.origin[a], map.inv_cell) >> 2) - 1;
+                const int h = (cell_coord(qq[a] + radius, map.origin[a], map.inv_cell) >> 2) + 1;
+                fits = fits && l >= 0 && h < (1 << 19) && h >= l;
+                lo[a] = l;
+                ext[a] = h - l + 1;
+                nl *= (uint64_t)(fits ? ext[a] : 1);
+            }
+            lists = fits && nl <= (uint64_t)map.n_ids;
+        }
+        if (lists) stream_lists(map, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], lane, s_pref[w], s_start[w], visit);
+        else stream_all(map, lane, visit);
+    }
+    if (!FILL && lane == 0) counts[qi] = got;
+}
+
+__global__ void query_alive_kernel(const float4* __restrict__ orig, uint32_t n_ids, uint32_t* __restrict__ flag) {
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id < n_ids) flag[id] = q_alive(orig[id]) ? 1u : 0u;
+}
+// inc_evict_box_kernel's predicate (lv_mapinc.hpp): living and inside [lo, hi], both faces inclusive
+__global__ void query_box_flag_kernel(const float4* __restrict__ orig, uint32_t n_ids, float lx, float ly, float lz, float hx, float hy, float hz,
+                                      uint32_t* __restrict__ flag) {
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= n_ids) return;
+    const float4 p = orig[id];
+    const bool inside = p.x >= lx && p.x <= hx && p.y >= ly && p.y <= hy && p.z >= lz && p.z <= hz;
+    flag[id] = (q_alive(p) && inside) ? 1u : 0u;
+}
+__global__ void query_box_scatter_kernel(const float4* __restrict__ orig, uint32_t n_ids, const uint32_t* __restrict__ flag,
+                                         const uint32_t* __restrict__ pos, const uint32_t* __restrict__ rank, uint32_t* __restrict__ out_idx,
+                                         float* __restrict__ out_xyz) {
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= n_ids || !flag[id]) return;
+    const uint32_t p = pos[id];
+    const float4 v = orig[id];
+    out_idx[p] = to_rank(rank, id);
+    out_xyz[3 * (size_t)p] = v.x;
+    out_xyz[3 * (size_t)p + 1] = v.y;
+    out_xyz[3 * (size_t)p + 2] = v.z;
+}
+// the total of an exclusive scan: last offset + last count
+template <class T>
+__global__ void query_total_kernel(const T* __restrict__ excl, const T* __restrict__ cnt, uint32_t n, T* __restrict__ out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = n ? excl[n - 1] + cnt[n - 1] : T(0);
+}
+__global__ void query_remap_kernel(uint32_t* __restrict__ v, uint32_t n, const uint32_t* __restrict__ rank) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = rank[v[i]];
+}
+
+template <class T>
+int grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap && p) return LV_OK;
+    size_t c = cap ? cap : 1024;
+    while (c < need) c *= 2;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    LV_HIP(hipMalloc((void**)&p, c * sizeof(T)));
+    cap = c;
+    return LV_OK;
+}
+int grow_bytes(void*& p, size_t& cap, size_t need) {
+    if (need <= cap && p) return LV_OK;
+    size_t c = cap ? cap : 4096;
+    while (c < need) c *= 2;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    LV_HIP(hipMalloc(&p, c));
+    cap = c;
+    return LV_OK;
+}
+uint32_t grid_of(size_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+}  // namespace
+
+int QueryStore::stage_queries(hipStream_t stream, const void* q, size_t stride, size_t n) {
+    int rc = grow(d_q, q_cap, 3 * n);
+    if (rc) return rc;
+    std::vector<float> packed(3 * n);
+    const char* b = static_cast<const char*>(q);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&packed[3 * i], b + i * stride, 3 * sizeof(float));
+    LV_HIP(hipMemcpyAsync(d_q, packed.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice, stream));
+    LV_HIP(hipStreamSynchronize(stream));   // (the pageable source dies with this frame)
+    return LV_OK;
+}
+
+int QueryStore::ensure_rank(const MapStore& map, hipStream_t stream, const uint32_t** rank) {
+    *rank = nullptr;
+    if (map.n_ids == map.m) return LV_OK;   // no dead id: ranks are ids
+    if (map.n_ids > (uint32_t)SCAN_MAX) { set_error("map of %u ids: the rank scan takes at most %d", map.n_ids, SCAN_MAX); return LV_EINVAL; }
+    if (rank_gen == map.gen && d_rank) { *rank = d_rank; return LV_OK; }
+    int rc = grow(d_rank, rank_cap, map.n_ids);
+    if (rc) return rc;
+    rc = grow(d_flag, flag_cap, map.n_ids);
+    if (rc) return rc;
+    hipLaunchKernelGGL(query_alive_kernel, dim3(grid_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_flag);
+    LV_HIP(hipGetLastError());
+    size_t bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_flag, d_rank, (int)map.n_ids, stream));
+    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    if (rc) return rc;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_flag, d_rank, (int)map.n_ids, stream));
+    rank_gen = map.gen;
+    *rank = d_rank;
+    return LV_OK;
+}
+
+int QueryStore::knn(const MapStore& map, hipStream_t stream, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx,
+                    float* d2, int32_t* found) {
+    if (k < 1 || k > 32) { set_error("k = %d: must be in 1..32", k); return LV_EINVAL; }
+    if (!(max_dist >= 0.f)) { set_error("max_dist must be >= 0 (a negative or NaN max_dist)"); return LV_EINVAL; }
+    if (n && (!q || stride < 12 || !idx)) { set_error("bad query array (stride %zu) or null result", stride); return LV_EINVAL; }
+    if (n > 0xFFFFFFF0ull / 32) { set_error("too many queries"); return LV_EINVAL; }
+    if (n == 0) return LV_OK;
+    int rc = stage_queries(stream, q, stride, n);
+    if (!rc) rc = grow(d_idx, idx_cap, n * (size_t)k);
+    if (!rc) rc = grow(d_d2, d2_cap, n * (size_t)k);
+    if (!rc) rc = grow(d_found, found_cap, n);
+    const uint32_t* rank = nullptr;
+    if (!rc) rc = ensure_rank(map, stream, &rank);
+    if (rc) return rc;
+    const float max_d2 = max_dist * max_dist;
+    hipLaunchKernelGGL(query_knn_kernel, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, map.view, d_q, (uint32_t)n, k, max_d2, rank, d_idx,
+                       d_d2, d_found);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(idx, d_idx, n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (d2) LV_HIP(hipMemcpyAsync(d2, d_d2, n * k * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (found) LV_HIP(hipMemcpyAsync(found, d_found, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int QueryStore::radius(const MapStore& map, hipStream_t stream, const void* q, size_t stride, size_t n, float radius, size_t* offsets,
+                       uint32_t* idx, float* d2, size_t capacity, size_t* total) {
+    if (!(radius >= 0.f)) { set_error("radius must be >= 0 (a negative or NaN radius)"); return LV_EINVAL; }
+    if (!offsets || !total || (n && (!q || stride < 12))) { set_error("bad query array (stride %zu) or null offsets / total", stride); return LV_EINVAL; }
+    if (n >= (size_t)SCAN_MAX) { set_error("%zu queries: a radius search takes fewer than %d", n, SCAN_MAX); return LV_EINVAL; }
+    *total = 0;
+    offsets[0] = 0;
+    if (n == 0) return LV_OK;
+    int rc = stage_queries(stream, q, stride, n);
+    if (!rc) rc = grow(d_roff, roff_cap, n + 1);
+    if (!rc) rc = grow(d_rcnt, rcnt_cap, n);
+    if (rc) return rc;
+    const MapView v = map.view;
+    hipLaunchKernelGGL(query_radius_kernel<false>, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, d_q, (uint32_t)n, radius, d_rcnt,
+                       (const uint64_t*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
+    LV_HIP(hipGetLastError());
+    size_t bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_rcnt, d_roff, (int)n, stream));
+    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    if (rc) return rc;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_rcnt, d_roff, (int)n, stream));
+    hipLaunchKernelGGL(query_total_kernel<uint64_t>, dim3(1), dim3(64), 0, stream, d_roff, d_rcnt, (uint32_t)n, d_roff + n);
+    LV_HIP(hipGetLastError());
+    static_assert(sizeof(size_t) == sizeof(uint64_t), "offsets are copied out as size_t");
+    LV_HIP(hipMemcpyAsync(offsets, d_roff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    const size_t tot = offsets[n];
+    *total = tot;
+    if (!idx) return LV_OK;   // count only: any total
+    if (capacity < tot) { set_error("capacity %zu < %zu results", capacity, tot); return LV_EINVAL; }
+    // the fill's segmented sort counts its items in an int: a larger result set is refused before anything is allocated or written
+    if (tot > (size_t)SCAN_MAX) {
+        set_error("%zu results: one radius search returns at most %d (split the queries; the count-only call has no limit)", tot, SCAN_MAX);
+        return LV_EINVAL;
+    }
+    if (tot == 0) return LV_OK;
+    rc = grow(d_idx, idx_cap, tot);
+    if (!rc) rc = grow(d_d2, d2_cap, tot);
+    if (!rc) rc = grow(d_idx2, idx2_cap, tot);
+    if (!rc) rc = grow(d_d22, d22_cap, tot);
+    const uint32_t* rank = nullptr;
+    if (!rc) rc = ensure_rank(map, stream, &rank);
+    if (rc) return rc;
+    hipLaunchKernelGGL(query_radius_kernel<true>, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, d_q, (uint32_t)n, radius,
+                       (uint64_t*)nullptr, (const uint64_t*)d_roff, d_idx, d_d2);
+    LV_HIP(hipGetLastError());
+    // the lists are unordered: every query's segment by id
+    bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, bytes, d_idx, d_idx2, d_d2, d_d22, (int)tot, (int)n, d_roff, d_roff + 1, 0,
+                                                                   32, stream));
+    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    if (rc) return rc;
+    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(d_tmp, bytes, d_idx, d_idx2, d_d2, d_d22, (int)tot, (int)n, d_roff, d_roff + 1, 0,
+                                                                   32, stream));
+    if (rank) {
+        hipLaunchKernelGGL(query_remap_kernel, dim3(grid_of(tot, 256)), dim3(256), 0, stream, d_idx2, (uint32_t)tot, rank);
+        LV_HIP(hipGetLastError());
+    }
+    LV_HIP(hipMemcpyAsync(idx, d_idx2, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (d2) LV_HIP(hipMemcpyAsync(d2, d_d22, tot * sizeof(float), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int QueryStore::box(const MapStore& map, hipStream_t stream, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity,
+                    size_t* n_out) {
+    if (!lo || !hi || !n_out) { set_error("null argument"); return LV_EINVAL; }
+    *n_out = 0;
+    if (map.view.m == 0 || map.n_ids == 0) return LV_OK;
+    if (map.n_ids > (uint32_t)SCAN_MAX) { set_error("map of %u ids: a box search scans at most %d", map.n_ids, SCAN_MAX); return LV_EINVAL; }
+    const uint32_t ids = map.n_ids;
+    int rc = grow(d_off, off_cap, (size_t)ids + 1);
+    if (!rc) rc = grow(d_cnt, cnt_cap, ids);
+    if (!rc && !h_word) LV_HIP(hipHostMalloc((void**)&h_word, 4 * sizeof(uint32_t), hipHostMallocDefault));
+    if (rc) return rc;
+    hipLaunchKernelGGL(query_box_flag_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
+                       d_cnt);
+    LV_HIP(hipGetLastError());
+    size_t bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt, d_off, (int)ids, stream));
+    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    if (rc) return rc;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_cnt, d_off, (int)ids, stream));
+    hipLaunchKernelGGL(query_total_kernel<uint32_t>, dim3(1), dim3(64), 0, stream, d_off, d_cnt, ids, d_off + ids);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(h_word, d_off + ids, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    const size_t tot = h_word[0];
+    *n_out = tot;
+    if (!idx && !xyz) return LV_OK;   // count only
+    if (capacity < tot) { set_error("capacity %zu < %zu results", capacity, tot); return LV_EINVAL; }
+    if (tot == 0) return LV_OK;
+    rc = grow(d_idx, idx_cap, tot);
+    if (!rc) rc = grow(d_d2, d2_cap, 3 * tot);
+    const uint32_t* rank = nullptr;
+    if (!rc) rc = ensure_rank(map, stream, &rank);
+    if (rc) return rc;
+    hipLaunchKernelGGL(query_box_scatter_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, d_cnt, d_off, rank, d_idx, d_d2);
+    LV_HIP(hipGetLastError());
+    if (idx) LV_HIP(hipMemcpyAsync(idx, d_idx, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (xyz) LV_HIP(hipMemcpyAsync(xyz, d_d2, 3 * tot * sizeof(float), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+void QueryStore::release() {
+    hipFree(d_q); hipFree(d_idx); hipFree(d_d2); hipFree(d_found); hipFree(d_idx2); hipFree(d_d22); hipFree(d_off); hipFree(d_cnt); hipFree(d_roff); hipFree(d_rcnt);
+    hipFree(d_tmp); hipFree(d_rank); hipFree(d_flag);
+    if (h_word) hipHostFree(h_word);
+    *this = QueryStore();
+}
+
+}  // namespace lv
