@@ -209,6 +209,23 @@ int lv_map_radius_search(lv_ctx* ctx, const void* q, size_t stride, size_t n, fl
  * floats per point, may be NULL; idx and xyz both NULL: count only.  Capacity as in lv_map_radius_search (*n_out = the count). */
 int lv_map_box_search(lv_ctx* ctx, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity, size_t* n_out);
 
+/* ---- Multi-hypothesis updates ----------------------------------------------------------------
+ * Prelocalisation in a previously saved map (the reference's work in progress, README.md:64-67, and its TODO "Saving and loading
+ * HD-Maps", README.md:117): many candidate poses evaluated or refined against the current scan in one call, in a number of launches
+ * per pass that does not depend on m.  Hypothesis i is exactly the single-pose call from xs[i] (Localizator.cpp:132 per
+ * hypothesis: same lv_params, same convergence rule, its own number of passes).  Both calls use the context's current scan, are
+ * ordered behind every earlier map mutation, read the active store during a background rebuild, and return once the host arrays
+ * are written.  m == 0 is a no-op; no map or an empty scan leaves every state unchanged (passes 0, n_valid 0); a context with a
+ * multi-GPU communicator gives LV_ESTATE.  The resident filter, the per-point capture of the last single-pose call,
+ * lv_last_passes, the degeneracy values and the timing records are left as they were.  Large batches run in chunks of
+ * hypotheses (lv_set_option "batch_chunk_hypotheses" caps a chunk); results do not depend on the chunking. */
+/* m measurement-model evaluations (lv_iterate) of the current scan, one per state, in one call. */
+int lv_iterate_batch(lv_ctx* ctx, const lv_state* xs, size_t m, lv_sums* out);
+/* m independent iterated updates (lv_update), each from prior xs[i] with the shared prior covariance P (23x23 row-major).
+ * xs is updated in place.  P_out (NULL or m x 529), passes (NULL or m) and last (NULL or m: the sums of each hypothesis'
+ * last pass, i.e. lv_update's per_pass[passes-1], the fitness a caller ranks by) are optional. */
+int lv_update_batch(lv_ctx* ctx, lv_state* xs, size_t m, const double* P, double* P_out, int* passes, lv_sums* last);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "lv_comm_unique_id", "lv_comm_init", "lv_comm_destroy", "lv_comm_world", "lv_comm_set_shard_max", "lv_set_comm_fused", "lv_comm_set_host_gather", "lv_comm_peer_export", "lv_comm_peer_init",
     "lv_cloud_format_preset", "lv_cloud_ingest", "lv_cloud_size", "lv_cloud_fetch", "lv_cloud_clear", "lv_cloud_reserve", "lv_reserve_stream", "lv_scan_deskew_window",
     "lv_map_knn", "lv_map_radius_search", "lv_map_box_search",
+    "lv_iterate_batch", "lv_update_batch",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -40,6 +41,13 @@ QUERY_ARGTYPES = {
                              C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)],
     "lv_map_box_search": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_size_t,
                           C.POINTER(C.c_size_t)],
+}
+
+# ctypes signatures of the multi-hypothesis calls (include/limovelo_hip.h "Multi-hypothesis updates"; tests/test_update_batch_abi.py)
+BATCH_ARGTYPES = {
+    "lv_iterate_batch": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+    "lv_update_batch": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
+                        C.c_void_p],
 }
 
 
@@ -176,7 +184,7 @@ def load_library() -> C.CDLL:
         lib.lv_destroy.restype = None
         lib.lv_destroy.argtypes = [C.c_void_p]
         lib.lv_default_params.restype = None
-        for name, argtypes in QUERY_ARGTYPES.items():
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -425,6 +433,28 @@ class Context:
         out = Sums()
         self._check(self.lib.lv_iterate(self.h, s.ctypes.data_as(C.c_void_p), C.byref(out)))
         return out.as_dict()
+
+    def iterate_batch(self, states) -> list:
+        """lv_iterate_batch: one measurement pass per state ([m, 26]) against the current scan -> m sums dicts."""
+        xs = np.ascontiguousarray(np.asarray(states, np.float64).reshape(-1, 26))
+        m = len(xs)
+        out = (Sums * max(m, 1))()
+        self._check(self.lib.lv_iterate_batch(self.h, xs.ctypes.data_as(C.c_void_p), C.c_size_t(m), out))
+        return [out[i].as_dict() for i in range(m)]
+
+    def update_batch(self, states, P, want_P=False):
+        """lv_update_batch: m independent iterated updates from states ([m, 26]) with the shared prior covariance P ->
+        (xs [m, 26], Ps [m, 23, 23] or None, passes [m], the sums of each hypothesis' last pass as m dicts)."""
+        xs = np.ascontiguousarray(np.asarray(states, np.float64).reshape(-1, 26)).copy()
+        m = len(xs)
+        Pm = np.ascontiguousarray(P, np.float64).reshape(NS * NS)
+        Ps = np.zeros((m, NS, NS)) if want_P else None
+        passes = np.zeros(m, np.int32)
+        last = (Sums * max(m, 1))()
+        self._check(self.lib.lv_update_batch(self.h, xs.ctypes.data_as(C.c_void_p), C.c_size_t(m), Pm.ctypes.data_as(C.POINTER(C.c_double)),
+                                             Ps.ctypes.data_as(C.POINTER(C.c_double)) if want_P else None,
+                                             passes.ctypes.data_as(C.POINTER(C.c_int)), last))
+        return xs, Ps, passes, [last[i].as_dict() for i in range(m)]
 
     def update(self, state, P, want_trace=True):
         if not want_trace:

@@ -41,6 +41,7 @@ struct lv_ctx {
 
     MapStore map;
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
+    BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     // ---- background re-linearisation of the map (row f-1; ikd-Tree rebuilds beside its searches too: the tree is constructed with
     // delete / balance criteria 0.3 / 0.6, src/Modules/Mapper.cpp:65, and rebuilds sub-trees on a second thread).  When the
     // active map wants a compaction (MapStore::wants_relinearise: a third of its id space is dead) and holds at least
@@ -801,6 +802,7 @@ void lv_destroy(lv_ctx* c) {
     c->map.release();
     c->relin_shadow.release();
     c->query.release();
+    c->batch.release();
     if (c->relin_arena) hipFree(c->relin_arena);
     if (c->relin_stream) hipStreamDestroy(c->relin_stream);
     if (c->relin_snapshot) hipEventDestroy(c->relin_snapshot);
@@ -1413,6 +1415,42 @@ int lv_map_box_search(lv_ctx* c, const float lo[3], const float hi[3], uint32_t*
     return c->query.box(c->map, c->stream, lo, hi, idx, xyz, capacity, n_out);
 }
 
+// Multi-hypothesis passes / updates (lv_batch.hip): ordered behind every earlier map mutation like the map queries, the
+// context's scan; the resident filter, the update's KfDev / mailbox / capture and the timing records are left alone
+static int batch_common(lv_ctx* c, const lv_state* xs, size_t m, const double* P, bool solve, lv_state* x_out, double* P_out, int* passes,
+                        lv_sums* out) {
+    if (multi_rank(c)) { set_error("multi-hypothesis updates run on one GPU: this context has a multi-GPU communicator"); return LV_ESTATE; }
+    if (c->in_update) { set_error("multi-hypothesis update inside lv_update_begin / lv_update_end"); return LV_ESTATE; }
+    if (passes) std::memset(passes, 0, m * sizeof(int));
+    if (out) std::memset(out, 0, m * sizeof(lv_sums));
+    if (P_out) for (size_t i = 0; i < m; ++i) std::memcpy(P_out + i * NS * NS, P, sizeof(double) * NS * NS);
+    if (c->map.view.m == 0 || c->scan.n == 0) return LV_OK;   // every state unchanged, passes 0, n_valid 0
+    std::vector<double> recs(out ? m * SUMS_LEN : 0);
+    int rc = c->batch.run(c->prm, c->max_blocks, c->map.view, c->scan.d_sorted, c->scan.n, c->stream, xs, m, P, solve, x_out, P_out, passes,
+                          out ? recs.data() : nullptr);
+    if (rc) return rc;
+    if (out) for (size_t i = 0; i < m; ++i) unpack_sums(recs.data() + i * SUMS_LEN, &out[i]);
+    return LV_OK;
+}
+
+int lv_iterate_batch(lv_ctx* c, const lv_state* xs, size_t m, lv_sums* out) {
+    LV_CHECK_CTX(c);
+    if (m == 0) return LV_OK;
+    if (!xs || !out) { set_error("null argument"); return LV_EINVAL; }
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return batch_common(c, xs, m, nullptr, false, nullptr, nullptr, nullptr, out);
+}
+
+int lv_update_batch(lv_ctx* c, lv_state* xs, size_t m, const double* P, double* P_out, int* passes, lv_sums* last) {
+    LV_CHECK_CTX(c);
+    if (m == 0) return LV_OK;
+    if (!xs || !P) { set_error("null argument"); return LV_EINVAL; }
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return batch_common(c, xs, m, P, true, xs, P_out, passes, last);
+}
+
 int lv_scan_set(lv_ctx* c, const void* points, size_t stride, size_t n) {
     LV_CHECK_CTX(c);
     if (n && (!points || stride < 12)) { set_error("bad point array (stride %zu)", stride); return LV_EINVAL; }
@@ -1763,6 +1801,7 @@ int lv_set_option(lv_ctx* c, const char* name, int value) {
     else if (!std::strcmp(name, "large_window")) c->scan.large_enabled = on;
     else if (!std::strcmp(name, "small_insert")) c->map.small_front = on;
     else if (!std::strcmp(name, "survivor_list")) c->map.surv_list = on;
+    else if (!std::strcmp(name, "batch_chunk_hypotheses")) c->batch.chunk_hyp = value > 0 ? value : 0;
     else { set_error("lv_set_option: unknown option '%s'", name); return LV_EINVAL; }
     return LV_OK;
 }

@@ -225,6 +225,30 @@ struct QueryStore {
     void release();
 };
 
+// Multi-hypothesis passes and updates of the current scan (lv_batch.hip: lv_iterate_batch / lv_update_batch).  Its own
+// buffers, grown on demand and kept: the hypothesis records (all M), the hand-over records and block partials of one chunk of
+// hypotheses, and a KfDev that only knn_search's counters write (the context's kf is never touched by a batch).
+struct BatchHyp;
+// bytes of hand-over records (qrec_slots(K) x 16 B per point and hypothesis: 128 B for K = 5) one chunk may use; a batch with
+// more is processed chunk after chunk (results do not depend on the chunking)
+constexpr size_t BATCH_RECORD_BUDGET = (size_t)256 << 20;
+struct BatchStore {
+    BatchHyp* d_hyp = nullptr;
+    BatchHyp* h_hyp = nullptr;     // pinned
+    float4* d_qrec = nullptr;
+    double* d_part = nullptr;
+    KfDev* d_sink = nullptr;
+    size_t hyp_cap = 0, h_cap = 0, qrec_cap = 0, part_cap = 0;
+    int chunk_hyp = 0;             // lv_set_option "batch_chunk_hypotheses": at most this many hypotheses per chunk (0: the budget alone)
+    size_t chunk_size(uint32_t n, int num_match) const;
+    // m hypotheses xs (prior covariance P) against the map and the scan (n sorted points): solve = false runs one pass without
+    // a solve (lv_iterate_batch).  Outputs (each optional): final states, posterior covariances (m x 529), passes, the record
+    // of each hypothesis' last pass (m x SUMS_LEN).  Returns once the host arrays are written.
+    int run(const lv_params& prm, int max_blocks, const MapView& map, const float4* scan, uint32_t n, hipStream_t stream, const lv_state* xs,
+            size_t m, const double* P, bool solve, lv_state* x_out, double* P_out, int* passes, double* recs);
+    void release();
+};
+
 // lv_comm.hip — RCCL bound at run time (row e)
 struct UniqueId128 { char internal[128]; };  // ncclUniqueId
 int comm_unique_id(const char* library, void* id128);

@@ -870,6 +870,9 @@ __device__ __forceinline__ void fit_row(const PoseConsts& pc, const MatchParams&
     }
 }
 
+// lv_batch.hip includes this file with LV_MATCH_DEVICE_ONLY defined: the device functions above (knn_search, fit_row) and
+// none of the kernels or host code below.
+#ifndef LV_MATCH_DEVICE_ONLY
 // ------------------------------------------------------------------------------------------------------
 // The pass runs as two kernels: the search and the fit have very different register needs (the search
 // wants many waves in flight to hide its dependent loads, the QR fit wants ~100 VGPRs), so each gets its own
@@ -1777,5 +1780,7 @@ int launch_pass(hipStream_t stream, const PassLaunch& pl, const BeginArg* begin)
     LV_HIP(hipGetLastError());
     return LV_OK;
 }
+
+#endif  // LV_MATCH_DEVICE_ONLY
 
 }  // namespace lv
