@@ -6,14 +6,10 @@
 #include <new>
 
 #include "lv_host.hpp"
+#include "lv_rebuild.hpp"
 
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <string>
-#include <thread>
 
 namespace lv {
 
@@ -42,55 +38,7 @@ struct lv_ctx {
     MapStore map;
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
-    // ---- background re-linearisation of the map (row f-1; ikd-Tree rebuilds beside its searches too: the tree is constructed with
-    // delete / balance criteria 0.3 / 0.6, src/Modules/Mapper.cpp:65, and rebuilds sub-trees on a second thread).  When the
-    // active map wants a compaction (MapStore::wants_relinearise: a third of its id space is dead) and holds at least
-    // relin_async_min points, a compacted copy of its living points is taken (one launch chain on the context's stream) and its
-    // search structure is rebuilt by a WORKER THREAD on a stream of its own, while searches and inserts go on against the active
-    // map; every mutation of the active map in the meantime is journaled (a device copy of the staged batch) and replayed on the
-    // copy by the worker; the stores are swapped at the next map call after the worker has caught up.  The map's point set, id
-    // order and hence every search result are the same as with the stop-the-world rebuild (tests/test_gpu_map_async.py).
-    struct RelinEntry {
-        int kind = 0;                     // 0 add (Add_Points rule), 1 add, building if empty (Mapper::add), 2 evict box, 3 evict oldest
-        float4* d_pts = nullptr;          // device copy of the staged batch (owned)
-        uint32_t n = 0;
-        int downsample = 0;
-        float box = 0.2f;
-        float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-        int keep_inside = 0;
-        uint32_t n_oldest = 0;
-        hipEvent_t ready = nullptr;       // the copy has landed (recorded on the stream that made it)
-        bool from_arena = false;
-    };
-    std::condition_variable relin_cv;
-    bool relin_cancelled = false;
-    size_t relin_want = 0;                // id slots the copy is allocated for (living points + slack)
-    void* relin_arena = nullptr;          // device memory the journal's batch copies are carved from (allocated once, by the worker)
-    size_t relin_arena_bytes = 64u << 20, relin_arena_used = 0;
-    MapStore relin_shadow;
-    std::thread relin_worker;
-    std::mutex relin_mu;
-    std::deque<RelinEntry> relin_journal;
-    std::atomic<int> relin_state{0};      // 0 idle, 4 worker allocating, 5 allocated (waiting for the snapshot), 1 rebuilding / replaying, 2 ready
-                                          // (worker caught up), 3 failed — written under relin_mu
-    std::string relin_error;
-    hipStream_t relin_stream = nullptr;
-    hipEvent_t relin_snapshot = nullptr;
-    bool relin_snap_side = false;         // the snapshot was enqueued on the side stream and the context's stream has not been ordered behind it yet (relin_order)
-    bool relin_async = true;              // lv_set_option "async_relinearise" / LV_ASYNC_RELINEARISE=0: always stop-the-world
-    size_t relin_async_min = 200000;      // smaller maps rebuild in ~2 ms: not worth a thread
-    uint64_t relin_started = 0, relin_swapped = 0;
-    std::atomic<uint64_t> relin_replayed{0};   // (written by the worker, read by lv_map_rebuild_status)
-    size_t relin_journal_max = 4096;       // journal entries beyond which a rebuild that cannot keep up is given up: the
-                                           // copy is cancelled and the active map takes the stop-the-world path when it needs one
-    uint32_t relin_pause_us = 100;        // LV_RELIN_PAUSE_US / "async_relinearise_pause_us": the worker's slices are spaced by that long (lv_map.hip launch_sliced):
-                                          // a cycle beside the rebuild 0.25 instead of 0.29 ms, p99 0.53-0.57 instead of 0.62-0.68, the rebuild ~8 x longer in wall time
-                                          // (profiles/experiments_r06/rebuild_spaced_slices_ab.txt); 0: slices back to back
-    uint32_t relin_slice_wgs = 256;       // LV_RELIN_SLICE_WGS: slice size of the worker's large launches (0: whole grids).  (Round 5's opt-in PACED form — the
-                                          // grids as at most 32 looping 1024-thread workgroups — is gone: p99 0.5 instead of 0.6 ms, but two 4.6 ms cycles in 5 of
-                                          // 17 replays that plain slices never showed, cause not found: profiles/experiments_r05/async_rebuild.txt §10-11)
-    bool relin_test_race = false;         // lv_set_option "async_relinearise_test_race": see relin_journal_add
-    int relin_test_delay_ms = 0;          // lv_set_option "async_relinearise_test_delay_ms": the worker pauses between rebuild and replay (tests)
+    MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
     ScanStore scan;
     CloudStore cloud;   // row f-4: device-resident LiDAR buffer
@@ -704,9 +652,9 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     if (const char* e = getenv("LV_FUSED_PASS")) c->fused_pass = atoi(e) != 0;
     if (const char* e = getenv("LV_FUSED_EXT")) c->fused_ext = atoi(e) != 0;
     if (const char* e = getenv("LV_FUSED_MULTI")) c->fused_multi_round = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("LV_ASYNC_RELINEARISE")) c->relin_async = atoi(e) != 0;
-    if (const char* e = getenv("LV_RELIN_SLICE_WGS")) c->relin_slice_wgs = (uint32_t)atol(e);
-    if (const char* e = getenv("LV_RELIN_PAUSE_US")) c->relin_pause_us = (uint32_t)atol(e);
+    if (const char* e = getenv("LV_ASYNC_RELINEARISE")) c->rebuild.opt.async = atoi(e) != 0;
+    if (const char* e = getenv("LV_RELIN_SLICE_WGS")) c->rebuild.opt.slice_wgs = (uint32_t)atol(e);
+    if (const char* e = getenv("LV_RELIN_PAUSE_US")) c->rebuild.opt.pause_us = (uint32_t)atol(e);
     if (const char* e = getenv("LV_MULTI_OVERLAP")) c->multi_overlap = atoi(e) != 0;   // A/B: 0 = every round's fits between two barriers
     if (const char* e = getenv("LV_KEEPER_BY_COST")) c->keeper_by_cost = atoi(e) != 0;
     if (const char* e = getenv("LV_COMM_FUSED")) c->comm_fused = atoi(e) != 0;
@@ -730,12 +678,7 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     LV_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     LV_HIP(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    {   // the background map rebuild's stream (lowest priority) and snapshot event: created here, creating a stream costs ~15 ms
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
-        if (hipStreamCreateWithPriority(&c->relin_stream, hipStreamNonBlocking, lo) != hipSuccess) { c->relin_stream = nullptr; (void)hipGetLastError(); }
-        if (hipEventCreateWithFlags(&c->relin_snapshot, hipEventDisableTiming) != hipSuccess) { c->relin_snapshot = nullptr; (void)hipGetLastError(); }
-    }
+    c->rebuild.create_streams(device, /*quiet=*/true);   // (a failure is retried by the first background rebuild)
     LV_HIP(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
     if (const char* e = getenv("LV_OVERLAP_INSERT")) c->overlap_insert = atoi(e) != 0;
     if (const char* e = getenv("LV_BATCH_PREDICT")) c->batch_predict = atoi(e) != 0;
@@ -773,39 +716,20 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     return LV_OK;
 }
 
-namespace {
-void relin_cancel(lv_ctx* c);   // (background re-linearisation: defined with the map entry points below)
-// the worker's stream and the snapshot event, created when the context is (creating a stream costs ~15 ms: not inside a cycle)
-int relin_streams(lv_ctx* c) {
-    if (!c->relin_stream) {
-        // LOWEST priority: the rebuild's kernels sort and scatter millions of points; the cycle's small launches on the context's
-        // streams must get the compute units as they free up, not queue behind them
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { lo = 0; (void)hipGetLastError(); }
-        if (hipStreamCreateWithPriority(&c->relin_stream, hipStreamNonBlocking, lo) != hipSuccess) {
-            (void)hipGetLastError();
-            LV_HIP(hipStreamCreateWithFlags(&c->relin_stream, hipStreamNonBlocking));
-        }
-    }
-    if (!c->relin_snapshot) LV_HIP(hipEventCreateWithFlags(&c->relin_snapshot, hipEventDisableTiming));
-    return LV_OK;
+// the context's streams as the background map rebuild takes them (lv_rebuild.hpp)
+static CtxStreams ctx_streams(lv_ctx* c) {
+    return {c->stream, c->side_stream, c->ev_staged, c->overlap_insert && c->side_stream && c->stream == c->own_stream};
 }
-}  // namespace
 
 void lv_destroy(lv_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     c->cloud.release();
     if (c->comm) { hipStreamSynchronize(c->stream); comm_destroy(c->comm); c->comm = nullptr; }
-    relin_cancel(c);
-    hipDeviceSynchronize();
+    c->rebuild.release(c->map, ctx_streams(c));   // (joins its worker and waits for the device before anything is freed)
     c->map.release();
-    c->relin_shadow.release();
     c->query.release();
     c->batch.release();
-    if (c->relin_arena) hipFree(c->relin_arena);
-    if (c->relin_stream) hipStreamDestroy(c->relin_stream);
-    if (c->relin_snapshot) hipEventDestroy(c->relin_snapshot);
     c->scan.release();
     free_capture(c);
     if (c->h_stage) hipHostFree(c->h_stage);
@@ -883,286 +807,18 @@ static int check_map_points(const void* points, size_t stride, size_t n) {
 // the stream an incremental insert runs on: the context's side stream, ordered behind what the context's stream holds so far
 // (the staged points), whenever the overlap applies (see lv_map_add_scan); the context's stream otherwise
 static hipStream_t insert_stream(lv_ctx* c) {
-    if (!(c->overlap_insert && c->side_stream && c->stream == c->own_stream && c->map.built && c->map.m > 0)) return c->stream;
-    if (hipEventRecord(c->ev_staged, c->stream) != hipSuccess || hipStreamWaitEvent(c->side_stream, c->ev_staged, 0) != hipSuccess) return c->stream;
-    return c->side_stream;
+    return c->map.built && c->map.m > 0 ? ctx_streams(c).side_behind() : c->stream;
 }
 
-// ---- background re-linearisation (see lv_ctx::relin_*) -------------------------------------------------------------------------
-namespace {
-void relin_free_entry(lv_ctx::RelinEntry& e) {
-    if (e.d_pts && !e.from_arena) hipFree(e.d_pts);
-    if (e.ready) hipEventDestroy(e.ready);
-    e.d_pts = nullptr;
-    e.ready = nullptr;
-}
-
-// the worker.  Phase 1 (state 4): every allocation the copy needs — the id-indexed buffers for `relin_want` points, the journal
-// arena — happens HERE, not on the caller's thread (hipMalloc of ~1 GB takes ~20 ms for a 10 M-point map); then it reports
-// "allocated" (state 5) and sleeps until the caller has enqueued the snapshot (state 1).  Phase 2: rebuild the copy's search
-// structure, then replay what the active map went through since the snapshot, until the journal is empty at a moment the lock is
-// held — from then on the two stores hold the same point set (state 2).
-void relin_worker_main(lv_ctx* c) {
-    auto fail = [&](const char* what) {
-        std::lock_guard<std::mutex> g(c->relin_mu);
-        c->relin_error = std::string(what) + ": " + lv_last_error();
-        c->relin_state = 3;
-    };
-    if (hipSetDevice(c->device) != hipSuccess) { fail("hipSetDevice"); return; }
-    MapStore& S = c->relin_shadow;
-    S.n_ids = 0;
-    S.m = 0;
-    S.built = false;
-    // the worker's big kernels leave the compute units every ~0.1 ms (launch_sliced, lv_map.hip)
-    S.slice_wgs = c->relin_slice_wgs;
-    set_slice_pause_us(c->relin_pause_us);   // (this thread's launches only)
-    if (S.reserve(c->relin_want) != LV_OK) { fail("reserve"); return; }
-    if (!c->relin_arena) {
-        if (hipMalloc(&c->relin_arena, c->relin_arena_bytes) != hipSuccess) { c->relin_arena = nullptr; (void)hipGetLastError(); }
-    }
-    {
-        std::unique_lock<std::mutex> g(c->relin_mu);
-        c->relin_state = 5;
-        c->relin_cv.wait(g, [&] { return c->relin_state != 5; });
-        if (c->relin_state != 1) return;   // cancelled
-    }
-    hipStream_t st = c->relin_stream;
-    if (hipStreamWaitEvent(st, c->relin_snapshot, 0) != hipSuccess) { fail("wait for the snapshot"); return; }
-    if (S.rebuild(st) != LV_OK) { fail("rebuild"); return; }
-    if (c->relin_test_delay_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(c->relin_test_delay_ms));   // (test hook: lets the journal fill)
-    for (;;) {
-        lv_ctx::RelinEntry e;
-        {
-            std::lock_guard<std::mutex> g(c->relin_mu);
-            if (c->relin_journal.empty()) { c->relin_state = 2; return; }
-            e = c->relin_journal.front();
-            c->relin_journal.pop_front();
-        }
-        int rc = LV_OK;
-        if (e.kind <= 1) {
-            if (hipStreamWaitEvent(st, e.ready, 0) != hipSuccess) rc = LV_EHIP;
-            if (!rc) rc = S.reserve_batch(e.n);
-            if (!rc && hipMemcpyAsync(S.d_new, e.d_pts, (size_t)e.n * sizeof(float4), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = LV_EHIP;
-            if (!rc) rc = S.add_staged(st, e.n, e.downsample, e.box, e.kind == 1);
-            if (!rc) rc = S.settle(st);
-        } else if (e.kind == 2) {
-            rc = S.evict_box(st, e.lo, e.hi, e.keep_inside, nullptr);
-        } else {
-            rc = S.evict_oldest(st, e.n_oldest, nullptr);
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) rc = rc ? rc : LV_EHIP;
-        relin_free_entry(e);
-        if (rc) { fail("replay of a journaled map operation"); return; }
-        ++c->relin_replayed;
-    }
-}
-
-// join the worker and throw its work away (lv_map_build / lv_map_relinearise / lv_destroy while a rebuild is in flight)
-void relin_cancel(lv_ctx* c) {
-    {
-        std::lock_guard<std::mutex> g(c->relin_mu);
-        if (c->relin_state == 4 || c->relin_state == 5) c->relin_cancelled = true;
-    }
-    if (c->relin_worker.joinable()) {
-        for (;;) {   // a worker that is still allocating reaches its wait first
-            {
-                std::lock_guard<std::mutex> g(c->relin_mu);
-                if (c->relin_state == 5) { c->relin_state = 0; c->relin_cv.notify_all(); }
-                if (c->relin_state != 4) break;
-            }
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-        c->relin_worker.join();
-    }
-    if (c->relin_snap_side) {   // (a snapshot may still be reading the active store on the side stream: build / relinearise rewrite it)
-        if (c->side_stream) hipStreamSynchronize(c->side_stream);
-        c->relin_snap_side = false;
-    }
-    for (auto& e : c->relin_journal) relin_free_entry(e);
-    c->relin_journal.clear();
-    c->relin_state = 0;
-    c->relin_cancelled = false;
-    c->relin_arena_used = 0;
-    c->map.defer_relinearise = false;
-}
-
-// Called at the start of every map call (the map is settled): the cycle boundary the reference's loop gives us
-// (src/main.cpp:102).  An allocated copy gets its snapshot here (a launch chain on the context's stream: no allocation, no wait);
-// a finished rebuild is adopted here; a failed one is dropped (the stop-the-world path remains).
-int relin_poll(lv_ctx* c) {
-    if (c->relin_state == 0) return LV_OK;
-    int st;
-    { std::lock_guard<std::mutex> g(c->relin_mu); st = c->relin_state; }
-    if (st == 1 || st == 4) return LV_OK;
-    if (st == 5) {
-        if ((size_t)c->map.m + 1 > c->relin_shadow.capacity) {   // (the map outgrew the slack while the worker was allocating: rare)
-            int rr = c->relin_shadow.reserve((size_t)c->map.m + 1);
-            if (rr) return rr;
-        }
-        // The snapshot only READS the active store: with the context's own stream it goes to the side stream (behind everything
-        // the context's stream holds so far), where the inserts run as well — the cycle's next prediction / window / update do not
-        // queue up behind the compaction of every id (0.3-0.4 ms at 10 M points: it was the slowest cycle of a rebuild).  What
-        // MUTATES the map afterwards is ordered behind it: inserts by running on the side stream, anything on the context's
-        // stream by relin_order().
-        hipStream_t ss = c->stream;
-        if (c->overlap_insert && c->side_stream && c->stream == c->own_stream && hipEventRecord(c->ev_staged, c->stream) == hipSuccess &&
-            hipStreamWaitEvent(c->side_stream, c->ev_staged, 0) == hipSuccess)
-            ss = c->side_stream;
-        int rc = c->map.snapshot_into(c->relin_shadow, ss);
-        if (rc) return rc;
-        LV_HIP(hipEventRecord(c->relin_snapshot, ss));
-        c->relin_snap_side = ss != c->stream;
-        std::lock_guard<std::mutex> g(c->relin_mu);
-        c->relin_state = 1;
-        c->relin_cv.notify_all();
-        return LV_OK;
-    }
-    if (c->relin_worker.joinable()) c->relin_worker.join();
-    if (st == 3) {
-        //  a failed worker — out of memory for the second store is the likely, and persistent, cause — must not be
-        // started again by the very call that found it failed: relin_cancel lifts the deferral, and with the background form
-        // switched off for this context the insert that follows takes the stop-the-world path (MapStore::needs_relinearise),
-        // which rebuilds in place and needs no second store.  lv_set_option "async_relinearise" 1 turns it back on.
-        fprintf(stderr, "[limovelo_hip] background map rebuild failed (%s); the map stays as it is, re-linearisations of this context stop the world from here on\n",
-                c->relin_error.c_str());
-        relin_cancel(c);
-        c->relin_async = false;
-        return LV_OK;
-    }
-    // ready: the worker's stream is drained (it synchronised after its last operation).  Nothing the caller enqueued against
-    // the old store is disturbed — its buffers stay allocated (it becomes the next rebuild's target, written by launches that
-    // are ordered behind everything enqueued on the context's stream so far) — so the swap needs no wait at all.
-    std::swap(c->map, c->relin_shadow);           // (relin_shadow is the OLD active store from here on: it carries the history)
-    c->map.slice_wgs = 0;
-    c->relin_snap_side = false;   // (the snapshot was complete before the worker's first launch)
-    c->map.defer_relinearise = false;
-    c->relin_shadow.defer_relinearise = false;
-    c->map.relinearisations = c->relin_shadow.relinearisations + 1;
-    c->map.incremental_adds = c->relin_shadow.incremental_adds;
-    c->map.dropped_total = c->relin_shadow.dropped_total;
-    c->map.refresh_view();
-    c->relin_state = 0;
-    c->relin_arena_used = 0;
-    ++c->relin_swapped;
-    return LV_OK;
-}
-
-// start the worker (its first phase allocates; the snapshot follows at the next map call: relin_poll)
-int relin_start(lv_ctx* c) {
-    if (c->relin_state != 0) return LV_OK;
-    { int rs = relin_streams(c); if (rs) return rs; }
-    c->relin_want = (size_t)c->map.m + (size_t)c->map.m / 8 + 262144;
-    c->map.defer_relinearise = true;
-    c->relin_error.clear();
-    c->relin_state = 4;
-    ++c->relin_started;
-    c->relin_worker = std::thread(relin_worker_main, c);
-    return LV_OK;
-}
-
-// an insert of n points is about to go to the active map: start a background rebuild if the map wants one
-int relin_maybe_start(lv_ctx* c, size_t incoming) {
-    if (c->relin_state != 0 || !c->relin_async || !c->map.built || c->map.m < c->relin_async_min) return LV_OK;
-    if ((uint64_t)c->map.n_ids + incoming > 0xFFFFFFF0ull) return LV_OK;     // id space exhausted: only the stop-the-world path helps
-    if (!c->map.wants_relinearise(incoming)) return LV_OK;
-    return relin_start(c);
-}
-
-// a mutation of the active map is about to be enqueued on `s`: it must not overtake a snapshot that is being taken on the side stream
-int relin_order(lv_ctx* c, hipStream_t s) {
-    if (!c->relin_snap_side || s == c->side_stream) return LV_OK;
-    LV_HIP(hipStreamWaitEvent(s, c->relin_snapshot, 0));
-    if (s == c->stream) c->relin_snap_side = false;   // (everything later on the context's stream is behind it as well)
-    return LV_OK;
-}
-
-// journal a batch staged in c->map.d_new (copied on the context's stream, which staged it) for the worker to replay
-int relin_journal_add(lv_ctx* c, uint32_t n, int downsample, float box, bool build_if_empty) {
-    if (n == 0) return LV_OK;
-    if (c->relin_test_race && c->relin_state == 1) {   // (test hook: let the worker report "ready" right here, between this call's poll and its journal entry)
-        const auto t0 = std::chrono::steady_clock::now();
-        while (c->relin_state == 1 && std::chrono::steady_clock::now() - t0 < std::chrono::seconds(5)) std::this_thread::sleep_for(std::chrono::microseconds(100));
-    }
-    int st = c->relin_state;
-    if (st != 1 && st != 2) return LV_OK;    // (0 idle; 4 / 5: the snapshot is still to come and will contain this batch; 3 failed)
-    lv_ctx::RelinEntry e;
-    if (st == 1) {
-        e.kind = build_if_empty ? 1 : 0;
-        e.n = n;
-        e.downsample = downsample;
-        e.box = box;
-        const size_t bytes = (((size_t)n * sizeof(float4)) + 255) & ~(size_t)255;
-        if (c->relin_arena && c->relin_arena_used + bytes <= c->relin_arena_bytes) {   // a bump arena: no hipMalloc on the caller's thread
-            e.d_pts = reinterpret_cast<float4*>(static_cast<char*>(c->relin_arena) + c->relin_arena_used);
-            e.from_arena = true;
-            c->relin_arena_used += bytes;
-        } else {
-            LV_HIP(hipMalloc(&e.d_pts, (size_t)n * sizeof(float4)));
-        }
-        // (an error below must not leak the entry: ADVICE r05)
-        hipError_t je = hipMemcpyAsync(e.d_pts, c->map.d_new, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream);
-        if (je == hipSuccess) je = hipEventCreateWithFlags(&e.ready, hipEventDisableTiming);
-        if (je == hipSuccess) je = hipEventRecord(e.ready, c->stream);
-        if (je != hipSuccess) {
-            relin_free_entry(e);
-            set_error("map rebuild journal: %s", hipGetErrorString(je));
-            return LV_EHIP;
-        }
-        {
-            std::lock_guard<std::mutex> g(c->relin_mu);
-            st = c->relin_state;
-            if (st == 1 && c->relin_journal.size() < c->relin_journal_max) { c->relin_journal.push_back(e); return LV_OK; }
-        }
-        relin_free_entry(e);
-        if (st == 1) {   // the worker does not drain the journal as fast as the caller fills it: give the copy up (bounded memory, bounded deferral)
-            fprintf(stderr, "[limovelo_hip] background map rebuild cannot keep up (%zu journaled operations): cancelled; re-linearisations of this context stop the world from here on\n",
-                    c->relin_journal_max);
-            relin_cancel(c);
-            c->relin_async = false;
-            return LV_OK;
-        }
-    }
-    if (st == 2) {
-        // The worker caught up and reported "ready" after this call's relin_poll: the copy no longer takes journal entries, so
-        // this batch must go to the copy AS THE ACTIVE MAP — adopt it now and move the staged batch over (it sits in the old
-        // store's staging buffer); the caller's add_staged then acts on the adopted store.
-        float4* staged_old = c->map.d_new;
-        int rc = relin_poll(c);
-        if (rc) return rc;
-        rc = c->map.reserve_batch(n);
-        if (rc) return rc;
-        LV_HIP(hipMemcpyAsync(c->map.d_new, staged_old, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    }
-    return LV_OK;   // (3: the worker failed meanwhile — the active map simply stays)
-}
-int relin_journal_evict(lv_ctx* c, int kind, const float* lo, const float* hi, int keep_inside, uint32_t n_oldest) {
-    if (c->relin_state != 1 && c->relin_state != 2) return LV_OK;
-    lv_ctx::RelinEntry e;
-    e.kind = kind;
-    if (lo) for (int a = 0; a < 3; ++a) { e.lo[a] = lo[a]; e.hi[a] = hi[a]; }
-    e.keep_inside = keep_inside;
-    e.n_oldest = n_oldest;
-    int st;
-    {
-        std::lock_guard<std::mutex> g(c->relin_mu);
-        st = c->relin_state;
-        if (st == 1 && c->relin_journal.size() < c->relin_journal_max) { c->relin_journal.push_back(e); return LV_OK; }
-    }
-    if (st == 1) { relin_cancel(c); c->relin_async = false; return LV_OK; }   // (journal full: see relin_journal_add)
-    if (st == 2) return relin_poll(c);   // (ready since this call's poll: adopt the copy first, the caller's eviction then acts on it)
-    return LV_OK;
-}
-}  // namespace
-
-#define LV_RELIN_POLL(c)            \
-    do {                            \
-        int _rp = relin_poll(c);    \
-        if (_rp) return _rp;        \
+#define LV_RELIN_POLL(c)                                          \
+    do {                                                          \
+        int _rp = (c)->rebuild.poll((c)->map, ctx_streams(c));    \
+        if (_rp) return _rp;                                      \
     } while (0)
 
 int lv_map_build(lv_ctx* c, const void* points, size_t stride, size_t n) {
     LV_CHECK_CTX(c);
-    relin_cancel(c);
+    c->rebuild.cancel(c->map, ctx_streams(c));
     LV_SETTLE_MAP(c);
     int rc = check_map_points(points, stride, n);   // bad input leaves the previous map untouched
     if (rc) return rc;
@@ -1189,16 +845,16 @@ int lv_map_add(lv_ctx* c, const void* points, size_t stride, size_t n, int downs
     int rc = check_map_points(points, stride, n);
     if (rc) return rc;
     if ((uint64_t)c->map.n_ids + n > 0xFFFFFFF0ull) { set_error("map too large"); return LV_EINVAL; }
-    rc = relin_maybe_start(c, n);
+    rc = c->rebuild.maybe_start(c->map, n);
     if (rc) return rc;
     rc = c->map.reserve_batch(n);
     if (rc) return rc;
     rc = stage_map_points(c, points, stride, n, c->map.d_new);
     if (rc) return rc;
-    rc = relin_journal_add(c, (uint32_t)n, downsample, 0.2f, false);
+    rc = c->rebuild.journal_add(c->map, ctx_streams(c), (uint32_t)n, downsample, 0.2f, false);
     if (rc) return rc;
     hipStream_t is = insert_stream(c);
-    rc = relin_order(c, is);
+    rc = c->rebuild.order(ctx_streams(c), is);
     if (rc) return rc;
     return c->map.add_staged(is, (uint32_t)n, downsample, 0.2f, false);  // box_length of KD_TREE(0.3, 0.6, 0.2), Mapper.cpp:65
 }
@@ -1227,7 +883,7 @@ int lv_map_add_scan(lv_ctx* c, int downsample) {
     const uint32_t n = c->scan.n;
     if (n == 0) return LV_OK;   // Mapper::add returns on an empty cloud (Mapper.cpp:20)
     LV_FLUSH_PREDICTS(c);
-    int rc = relin_maybe_start(c, n);
+    int rc = c->rebuild.maybe_start(c->map, n);
     if (rc) return rc;
     rc = c->map.reserve_batch(n);
     if (rc) return rc;
@@ -1243,10 +899,10 @@ int lv_map_add_scan(lv_ctx* c, int downsample) {
     // of ~150 us occupies a handful of CUs).  Everything that touches the map settles the insert first (LV_SETTLE_MAP: the
     // host waits for the note the chain's last kernel posts), so no other ordering is needed.  Only with the context's own
     // stream: a caller-provided stream keeps everything on that stream.
-    rc = relin_journal_add(c, n, downsample, 0.2f, true);
+    rc = c->rebuild.journal_add(c->map, ctx_streams(c), n, downsample, 0.2f, true);
     if (rc) return rc;
     hipStream_t is = insert_stream(c);
-    rc = relin_order(c, is);
+    rc = c->rebuild.order(ctx_streams(c), is);
     if (rc) return rc;
     return c->map.add_staged(is, n, downsample, 0.2f, true);   // Mapper::add: an empty map is built from the cloud
 }
@@ -1257,8 +913,8 @@ int lv_map_evict_box(lv_ctx* c, const float lo[3], const float hi[3], int keep_i
     uint32_t ne = 0;
     LV_SETTLE_MAP(c);
     LV_RELIN_POLL(c);
-    int rc = relin_journal_evict(c, 2, lo, hi, keep_inside, 0);
-    if (!rc) rc = relin_order(c, c->stream);
+    int rc = c->rebuild.journal_evict(c->map, ctx_streams(c), 2, lo, hi, keep_inside, 0);
+    if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
     if (!rc) rc = c->map.evict_box(c->stream, lo, hi, keep_inside, &ne);
     if (n_evicted) *n_evicted = ne;
     return rc;
@@ -1269,8 +925,8 @@ int lv_map_evict_oldest(lv_ctx* c, size_t n_oldest, size_t* n_evicted) {
     uint32_t ne = 0;
     LV_SETTLE_MAP(c);
     LV_RELIN_POLL(c);
-    int rc = relin_journal_evict(c, 3, nullptr, nullptr, 0, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest));
-    if (!rc) rc = relin_order(c, c->stream);
+    int rc = c->rebuild.journal_evict(c->map, ctx_streams(c), 3, nullptr, nullptr, 0, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest));
+    if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
     if (!rc) rc = c->map.evict_oldest(c->stream, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest), &ne);
     if (n_evicted) *n_evicted = ne;
     return rc;
@@ -1278,7 +934,7 @@ int lv_map_evict_oldest(lv_ctx* c, size_t n_oldest, size_t* n_evicted) {
 
 int lv_map_relinearise(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    relin_cancel(c);     // (a background rebuild in flight is superseded by this synchronous one)
+    c->rebuild.cancel(c->map, ctx_streams(c));   // (a background rebuild in flight is superseded by this synchronous one)
     LV_SETTLE_MAP(c);
     if (!c->map.built) return LV_OK;
     return c->map.relinearise(c->stream);
@@ -1289,63 +945,20 @@ int lv_map_relinearise_async(lv_ctx* c) {
     LV_SETTLE_MAP(c);
     LV_RELIN_POLL(c);
     if (!c->map.built || c->map.m == 0) return LV_OK;
-    return relin_start(c);
+    return c->rebuild.start(c->map);
 }
 
-// Every allocation a background rebuild needs, made NOW (set-up time) instead of by the first rebuild's worker: the second store is
-// allocated for the map as it stands, filled from a snapshot and rebuilt once — synchronously, in whole grids — so that its id
-// buffers, pools and tables exist at the sizes a rebuild of this map takes, have been touched, and the journal arena is there.
-// The first background rebuild of the context then behaves like every later one (which find the previous active store waiting).
+// every allocation a background rebuild needs, made at set-up time (MapRebuild::reserve)
 int lv_map_reserve_rebuild(lv_ctx* c) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
     LV_RELIN_POLL(c);
-    if (c->relin_state != 0) { set_error("lv_map_reserve_rebuild: a background rebuild is in flight"); return LV_ESTATE; }
-    if (!c->map.built || c->map.m == 0) return LV_OK;
-    { int rs = relin_streams(c); if (rs) return rs; }
-    MapStore& S = c->relin_shadow;
-    S.n_ids = 0;
-    S.m = 0;
-    S.built = false;
-    S.slice_wgs = 0;
-    int rc = S.reserve((size_t)c->map.m + (size_t)c->map.m / 8 + 262144);
-    if (rc) return rc;
-    if (!c->relin_arena && hipMalloc(&c->relin_arena, c->relin_arena_bytes) != hipSuccess) { c->relin_arena = nullptr; (void)hipGetLastError(); }
-    LV_HIP(hipStreamSynchronize(c->stream));
-    if (c->side_stream) LV_HIP(hipStreamSynchronize(c->side_stream));
-    rc = c->map.snapshot_into(S, c->stream);
-    if (!rc) rc = S.rebuild(c->stream);
-    if (!rc && c->map.batch_cap) rc = S.reserve_batch(c->map.batch_cap);
-    if (!rc) rc = S.ensure_boxes(c->stream, 0.2f);   // (the 0.2 m box table a down-sampling replay builds: Mapper.cpp:65)
-    LV_HIP(hipStreamSynchronize(c->stream));
-    S.have_boxes = false;
-    // (the copy's contents are not kept: the next rebuild takes its own snapshot)
-    S.n_ids = 0;
-    S.m = 0;
-    S.built = false;
-    return rc;
+    return c->rebuild.reserve(c->map, ctx_streams(c));
 }
 
 int lv_map_rebuild_status(lv_ctx* c, int wait, uint64_t out[4]) {
     LV_CHECK_CTX(c);
-    if (wait && c->relin_state != 0) {
-        LV_SETTLE_MAP(c);
-        for (;;) {   // allocating -> (snapshot) -> rebuilding -> ready -> adopted
-            LV_RELIN_POLL(c);
-            int st;
-            { std::lock_guard<std::mutex> g(c->relin_mu); st = c->relin_state; }
-            if (st == 0) break;
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-    }
-    if (out) {
-        int st;
-        { std::lock_guard<std::mutex> g(c->relin_mu); st = c->relin_state; out[3] = (uint64_t)c->relin_journal.size(); }
-        out[0] = (uint64_t)st;
-        out[1] = c->relin_started;
-        out[2] = c->relin_swapped;
-    }
-    return LV_OK;
+    return c->rebuild.status(c->map, ctx_streams(c), wait, out);
 }
 
 int lv_map_get_stats(lv_ctx* c, lv_map_stats* out) {
@@ -1367,7 +980,7 @@ int lv_map_get_stats(lv_ctx* c, lv_map_stats* out) {
 size_t lv_map_size(lv_ctx* c) {
     if (!c) return 0;
     c->map.settle(c->stream);
-    relin_poll(c);
+    c->rebuild.poll(c->map, ctx_streams(c));
     return c->map.m;
 }
 
@@ -1392,7 +1005,7 @@ int lv_map_fetch(lv_ctx* c, float* xyz_out, size_t capacity) {
 }
 
 // Map queries (lv_query.hip): ordered behind every earlier map mutation — the insert in flight on the side stream (settle) and a
-// finished background rebuild (adopted by relin_poll) — and read the active store
+// finished background rebuild (adopted by MapRebuild::poll) — and read the active store
 int lv_map_knn(lv_ctx* c, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx, float* d2, int32_t* found) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
@@ -1779,13 +1392,13 @@ int lv_set_option(lv_ctx* c, const char* name, int value) {
     if (!std::strcmp(name, "fused_pass")) c->fused_pass = on;
     else if (!std::strcmp(name, "fused_ext")) c->fused_ext = on;
     else if (!std::strcmp(name, "fast_fit")) c->fast_fit = on;
-    else if (!std::strcmp(name, "async_relinearise")) c->relin_async = on;
-    else if (!std::strcmp(name, "async_relinearise_min")) c->relin_async_min = value > 0 ? (size_t)value : 0;
-    else if (!std::strcmp(name, "async_relinearise_pause_us")) c->relin_pause_us = value > 0 ? (uint32_t)value : 0u;
-    else if (!std::strcmp(name, "async_relinearise_slice_wgs")) c->relin_slice_wgs = value > 0 ? (uint32_t)value : 0u;      // 0: whole grids
-    else if (!std::strcmp(name, "async_relinearise_journal_max")) c->relin_journal_max = value > 0 ? (size_t)value : 1;
-    else if (!std::strcmp(name, "async_relinearise_test_delay_ms")) c->relin_test_delay_ms = value;
-    else if (!std::strcmp(name, "async_relinearise_test_race")) c->relin_test_race = on;
+    else if (!std::strcmp(name, "async_relinearise")) c->rebuild.opt.async = on;
+    else if (!std::strcmp(name, "async_relinearise_min")) c->rebuild.opt.async_min = value > 0 ? (size_t)value : 0;
+    else if (!std::strcmp(name, "async_relinearise_pause_us")) c->rebuild.opt.pause_us = value > 0 ? (uint32_t)value : 0u;
+    else if (!std::strcmp(name, "async_relinearise_slice_wgs")) c->rebuild.opt.slice_wgs = value > 0 ? (uint32_t)value : 0u;      // 0: whole grids
+    else if (!std::strcmp(name, "async_relinearise_journal_max")) c->rebuild.opt.journal_max = value > 0 ? (size_t)value : 1;
+    else if (!std::strcmp(name, "async_relinearise_test_delay_ms")) c->rebuild.opt.test_delay_ms = value;
+    else if (!std::strcmp(name, "async_relinearise_test_race")) c->rebuild.opt.test_race = on;
     else if (!std::strcmp(name, "multi_overlap")) c->multi_overlap = on;
     else if (!std::strcmp(name, "fused_multi_round")) c->fused_multi_round = on ? 1 : 0;
     else if (!std::strcmp(name, "keeper_by_cost")) c->keeper_by_cost = on;

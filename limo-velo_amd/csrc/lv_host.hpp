@@ -8,20 +8,10 @@
 
 #include "../../include/limovelo_hip.h"
 #include "lv_device.hpp"
+#include "lv_common.hpp"
 #include "lv_mapinc.hpp"
 
 namespace lv {
-
-void set_error(const char* fmt, ...);
-
-#define LV_HIP(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) {                                                                   \
-            ::lv::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return LV_EHIP;                                                                       \
-        }                                                                                         \
-    } while (0)
 
 struct MapStats {   // == lv_map_stats (include/limovelo_hip.h)
     uint64_t living, ids, capacity;
@@ -32,7 +22,6 @@ struct MapStats {   // == lv_map_stats (include/limovelo_hip.h)
     uint64_t bytes;
 };
 
-void set_slice_pause_us(uint32_t us);   // lv_map.hip: the calling THREAD's sliced launches are spaced by that many microseconds (0: back to back)
 struct MapStore {
     // ---- points by id (insertion order; deleted ids keep their slot with x = +inf)
     float4* d_orig = nullptr;
@@ -173,7 +162,7 @@ struct MapStore {
     int ensure_boxes(hipStream_t stream, float box_length);
     int ensure_alive_scratch();
     bool needs_relinearise(size_t incoming) const;
-    // background re-linearisation (lv_api.hip, round 5): while a compacted copy of this map is being rebuilt on another stream /
+    // background re-linearisation (lv_rebuild.hpp, round 5): while a compacted copy of this map is being rebuilt on another stream /
     // thread, the stop-the-world relinearise is deferred (only id-space exhaustion still forces it)
     bool defer_relinearise = false;
     uint32_t last_new = 0;    // survivors of the previous insert batch: sizes the next batch's per-survivor launches (an estimate: add_staged)

@@ -1610,7 +1610,7 @@ int MapStore::settle(hipStream_t stream) {
     uint32_t v[5] = {0, 0, 0, 0, 0};   // n_new, n_dead, dropped, overflow, free entries left in the bucket pool
     if (!note_wait(notes, 0, 5, counters_seq, v, counters_stream)) { set_error("map insert: the counters never arrived"); return LV_EHIP; }
     // three quarters of the pool's free part are gone (runs that moved, groups laid out again, newly mapped space): ask for a
-    // re-linearisation now — in the background for a large map (lv_api.hip relin_maybe_start) — instead of meeting `overflow`
+    // re-linearisation now — in the background for a large map (lv_rebuild.hpp MapRebuild::maybe_start) — instead of meeting `overflow`
     // in the middle of a later batch, which costs that batch's work and a stop-the-world rebuild
     pool_low = (uint64_t)v[4] * 4 < (uint64_t)(pool_cap[0] > pool_base[0] ? pool_cap[0] - pool_base[0] : 0);
     uint32_t n_dead = pending_n_dead;

@@ -2,14 +2,20 @@
 //
 // It lets tests/emu/mapinc_emu.cpp compile the one-thread-per-item kernels of limo-velo_amd/csrc/lv_mapinc.hpp with
 // g++ and run them as plain loops (one "thread" after another, optionally in reverse or shuffled order), so the
-// bookkeeping of the incremental map can be checked against the oracle in the GPU-less container.  Nothing here is
-// linked into, loaded by or reachable from the product library; the product runs these kernels on the GPU only.
+// bookkeeping of the incremental map can be checked against the oracle in the GPU-less container; and it lets
+// tests/emu/rebuild_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp against the fake host API at the end of this file.
+// Nothing here is linked into, loaded by or reachable from the product library.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <mutex>
+#include <string>
+#include <vector>
 
 #define __global__
 #define __device__
@@ -39,3 +45,82 @@ template <typename T> static inline T atomicMax(T* p, T v) { T o = *p; if (v > o
 using std::abs;
 using std::max;
 using std::min;
+
+// ---- host API: streams, events and allocations.  Every call runs synchronously (a copy is done when the call returns) and is
+// logged as (call, stream, event) so a test can assert the order of its stream work; allocations, events and streams are
+// counted so leaks show.  `fail` (set by a test) makes the call it returns true for fail with hipErrorUnknown.
+enum hipError_t { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
+enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3, hipMemcpyDefault = 4 };
+typedef struct emu_stream* hipStream_t;
+typedef struct emu_event* hipEvent_t;
+#define hipStreamNonBlocking 0x01
+#define hipEventDisableTiming 0x02
+
+namespace emu_hip {
+struct Call {
+    std::string call;
+    hipStream_t stream;
+    hipEvent_t event;
+};
+struct State {
+    std::mutex mu;
+    std::vector<Call> log;
+    std::function<bool(const char* call)> fail;
+    uintptr_t next_handle = 0x1000;
+    std::atomic<long> mallocs{0}, frees{0}, events_created{0}, events_destroyed{0}, streams_created{0}, streams_destroyed{0};
+};
+inline State& state() { static State s; return s; }
+inline hipError_t call(const char* name, hipStream_t s = nullptr, hipEvent_t e = nullptr) {
+    State& st = state();
+    std::lock_guard<std::mutex> g(st.mu);
+    if (st.fail && st.fail(name)) return hipErrorUnknown;
+    st.log.push_back({name, s, e});
+    return hipSuccess;
+}
+template <typename H> H new_handle() {
+    State& st = state();
+    std::lock_guard<std::mutex> g(st.mu);
+    return reinterpret_cast<H>(st.next_handle += 16);
+}
+}  // namespace emu_hip
+
+inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess" : "emulated HIP failure"; }
+inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipSetDevice(int) { return emu_hip::call("hipSetDevice"); }
+inline hipError_t hipDeviceSynchronize() { return emu_hip::call("hipDeviceSynchronize"); }
+inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *hi = -1; return emu_hip::call("hipDeviceGetStreamPriorityRange"); }
+inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) {
+    hipError_t e = emu_hip::call("hipStreamCreateWithPriority");
+    if (e == hipSuccess) { *s = emu_hip::new_handle<hipStream_t>(); ++emu_hip::state().streams_created; }
+    return e;
+}
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+    hipError_t e = emu_hip::call("hipStreamCreateWithFlags");
+    if (e == hipSuccess) { *s = emu_hip::new_handle<hipStream_t>(); ++emu_hip::state().streams_created; }
+    return e;
+}
+inline hipError_t hipStreamDestroy(hipStream_t s) { ++emu_hip::state().streams_destroyed; return emu_hip::call("hipStreamDestroy", s); }
+inline hipError_t hipStreamSynchronize(hipStream_t s) { return emu_hip::call("hipStreamSynchronize", s); }
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { return emu_hip::call("hipStreamWaitEvent", s, e); }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* ev, unsigned) {
+    hipError_t e = emu_hip::call("hipEventCreateWithFlags");
+    if (e == hipSuccess) { *ev = emu_hip::new_handle<hipEvent_t>(); ++emu_hip::state().events_created; }
+    return e;
+}
+inline hipError_t hipEventDestroy(hipEvent_t ev) { ++emu_hip::state().events_destroyed; return emu_hip::call("hipEventDestroy", nullptr, ev); }
+inline hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) { return emu_hip::call("hipEventRecord", s, ev); }
+inline hipError_t hipMalloc(void** p, size_t bytes) {
+    hipError_t e = emu_hip::call("hipMalloc");
+    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; }
+    return e;
+}
+template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(p), bytes); }
+inline hipError_t hipFree(void* p) {
+    if (p) { std::free(p); ++emu_hip::state().frees; }
+    return emu_hip::call("hipFree");
+}
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind, hipStream_t s) {
+    hipError_t e = emu_hip::call("hipMemcpyAsync", s);
+    if (e == hipSuccess && bytes) std::memcpy(dst, src, bytes);
+    return e;
+}
