@@ -226,6 +226,44 @@ int lv_iterate_batch(lv_ctx* ctx, const lv_state* xs, size_t m, lv_sums* out);
  * last pass, i.e. lv_update's per_pass[passes-1], the fitness a caller ranks by) are optional. */
 int lv_update_batch(lv_ctx* ctx, lv_state* xs, size_t m, const double* P, double* P_out, int* passes, lv_sums* last);
 
+/* ---- Dynamic-point removal -------------------------------------------------------------------
+ * The reference's open TODO (README.md, "Fixes to investigate": "Try to add a module for removing dynamic objects such as people
+ * or vehicles", "Erase unused (potentially dangerous) points in the map"): map points that a sensor has seen THROUGH leave the map.
+ * A view is one sweep: its pose sensor -> world (R 3x3 row-major, t; the caller forms Xt2 * Xt2.I_Rt_L() as lv_map_add_scan does)
+ * and its raw returns in the sensor frame (f32 x,y,z at offset 0 of each record, stride >= 12).  Per view:
+ *   1. range image of height x width pixels: column from atan2f(y, x), width equal bins over [-pi, pi); row from
+ *      atan2f(z, sqrtf(x*x + y*y)), height equal bins over [v_min_deg, v_max_deg]; a pixel keeps the minimum range
+ *      sqrtf(x*x + y*y + z*z) of its returns.  Returns that are non-finite, at range <= min_range or outside the rows are ignored;
+ *      an empty pixel is +inf.
+ *   2. every pixel becomes the minimum over the (2 window + 1)^2 pixels around it (columns wrap at +-pi, rows are clipped); an
+ *      all-empty window stays +inf: no evidence.
+ *   3. a living map point p, in the sensor frame p_s = R^T (p - t), at range r = |p_s| inside [min_range, max_range] and inside the
+ *      rows, is SEEN THROUGH iff r_img - r > fmaxf(margin_abs, margin_rel * r), r_img the filtered pixel it falls in.
+ * A point leaves the map iff it was seen through in at least min_hits views: a pure function of its coordinates and the call's
+ * inputs.  Survivors keep their order (as with lv_map_evict_box).  The call is ordered behind every earlier map mutation, acts on
+ * the active store (a background rebuild in flight replays it on its copy) and returns once its host outputs are written. */
+typedef struct lv_view {            /* one sweep: pose sensor -> world, returns in the sensor frame */
+    float R[9]; float t[3];
+    const void* points; size_t stride; size_t n;    /* n = 0: the view gives no evidence */
+} lv_view;
+typedef struct lv_visibility_params {
+    int   width, height;            /* image columns over [-pi, pi), rows over [v_min_deg, v_max_deg]; width * height <= 2^20 */
+    float v_min_deg, v_max_deg;     /* v_min_deg < v_max_deg, both in [-90, 90] */
+    float min_range, max_range;     /* map points judged only inside; scan returns <= min_range ignored; 0 < min_range < max_range */
+    float margin_abs, margin_rel;   /* finite, > 0 */
+    int   window;                   /* half-width w of the window-min, 0..8 */
+    int   min_hits;                 /* 1..n_views */
+    int   dry_run;                  /* != 0: classify only, the map is not touched */
+} lv_visibility_params;
+/* Defaults for a 64-ring spinning LiDAR: 2048 x 64 pixels over -25..+3 deg, ranges 1..80 m, margins 0.3 m and 2 %, window 1,
+ * min_hits 1, dry_run 0. */
+void lv_default_visibility_params(lv_visibility_params* p);
+/* n_views 1..32.  hits: NULL, or lv_map_size() entries in map order (the index space of lv_map_fetch / lv_map_knn): the number of
+ * views each point was seen through in, as the map stood BEFORE the removal.  *n_removed (may be NULL): the points that left the
+ * map (0 with dry_run).  Arguments outside the limits above give LV_EINVAL and change nothing; an empty map gives LV_OK, 0 removed. */
+int  lv_map_remove_dynamic(lv_ctx* ctx, const lv_view* views, size_t n_views, const lv_visibility_params* p, uint8_t* hits,
+                           size_t* n_removed);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "lv_cloud_format_preset", "lv_cloud_ingest", "lv_cloud_size", "lv_cloud_fetch", "lv_cloud_clear", "lv_cloud_reserve", "lv_reserve_stream", "lv_scan_deskew_window",
     "lv_map_knn", "lv_map_radius_search", "lv_map_box_search",
     "lv_iterate_batch", "lv_update_batch",
+    "lv_default_visibility_params", "lv_map_remove_dynamic",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -49,6 +50,53 @@ BATCH_ARGTYPES = {
     "lv_update_batch": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int),
                         C.c_void_p],
 }
+
+
+
+class View(C.Structure):  # lv_view
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("points", C.c_void_p), ("stride", C.c_size_t), ("n", C.c_size_t)]
+
+
+class VisibilityParams(C.Structure):  # lv_visibility_params
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("v_min_deg", C.c_float), ("v_max_deg", C.c_float), ("min_range", C.c_float),
+                ("max_range", C.c_float), ("margin_abs", C.c_float), ("margin_rel", C.c_float), ("window", C.c_int), ("min_hits", C.c_int),
+                ("dry_run", C.c_int)]
+
+
+# ctypes signatures of the dynamic-point removal (include/limovelo_hip.h "Dynamic-point removal"; tests/test_map_visibility_abi.py)
+VISIBILITY_ARGTYPES = {
+    "lv_map_remove_dynamic": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(C.c_uint8),
+                              C.POINTER(C.c_size_t)],
+}
+
+
+def sensor_pose(state):
+    """(R [3, 3] f32, t [3] f32): the sensor -> world pose Xt2 * Xt2.I_Rt_L() of an lv_state (26 f64), formed as lv_map_add_scan
+    forms it on the device (lv_device.hpp compute_pose_consts: rotations from the quaternions in f64, rounded to f32, composed in
+    f32 with each sum taken as p0 + (p1 + p2))."""
+    x = np.asarray(state, np.float64).ravel()
+
+    def rot(q):
+        qx, qy, qz, qw = q
+        tx, ty, tz = 2.0 * qx, 2.0 * qy, 2.0 * qz
+        twx, twy, twz = tx * qw, ty * qw, tz * qw
+        txx, txy, txz = tx * qx, ty * qx, tz * qx
+        tyy, tyz, tzz = ty * qy, tz * qy, tz * qz
+        return np.array([1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx,
+                         txz - twy, tyz + twx, 1.0 - (txx + tyy)]).astype(np.float32)
+
+    def dot3(a0, b0, a1, b1, a2, b2):
+        return np.float32(a0 * b0) + np.float32(np.float32(a1 * b1) + np.float32(a2 * b2))
+
+    XR, LR = rot(x[3:7]), rot(x[7:11])
+    Xt, Lt = x[0:3].astype(np.float32), x[11:14].astype(np.float32)
+    R = np.empty(9, np.float32)
+    t = np.empty(3, np.float32)
+    for i in range(3):
+        for j in range(3):
+            R[i * 3 + j] = dot3(XR[i * 3], LR[j], XR[i * 3 + 1], LR[3 + j], XR[i * 3 + 2], LR[6 + j])
+        t[i] = np.float32(dot3(XR[i * 3], Lt[0], XR[i * 3 + 1], Lt[1], XR[i * 3 + 2], Lt[2]) + Xt[i])
+    return R.reshape(3, 3), t
 
 
 def pseudo_measurement(sums: dict, estimate_extrinsics: bool):
@@ -184,7 +232,9 @@ def load_library() -> C.CDLL:
         lib.lv_destroy.restype = None
         lib.lv_destroy.argtypes = [C.c_void_p]
         lib.lv_default_params.restype = None
-        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES}.items():
+        lib.lv_default_visibility_params.restype = None
+        lib.lv_default_visibility_params.argtypes = [C.POINTER(VisibilityParams)]
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -200,6 +250,14 @@ def default_params(**kw) -> Params:
                 p.LIMITS[i] = float(v[i])
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_visibility_params(**kw) -> VisibilityParams:
+    p = VisibilityParams()
+    load_library().lv_default_visibility_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -354,6 +412,28 @@ class Context:
         return idx[: int(cnt.value)], xyz[: int(cnt.value)]
 
     # --- Localizator side
+    # --- dynamic-point removal
+    def map_remove_dynamic(self, views, params: VisibilityParams | None = None, dry_run=False):
+        """(n_removed, hits [map_size] uint8): lv_map_remove_dynamic over views = [(R [3, 3], t [3], points [n, 3] sensor frame)],
+        R, t the sensor -> world pose (sensor_pose); hits in map order as the map stood before the removal."""
+        p = VisibilityParams.from_buffer_copy(params) if params is not None else default_visibility_params()
+        p.dry_run = int(bool(dry_run) or bool(p.dry_run))
+        keep = []
+        arr = (View * max(len(views), 1))()
+        for i, (R, t, pts) in enumerate(views):
+            a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3)) if len(pts) else (None, 12, 0)
+            keep.append(a)
+            arr[i].R[:] = [float(v) for v in np.asarray(R, np.float32).ravel()]
+            arr[i].t[:] = [float(v) for v in np.asarray(t, np.float32).ravel()]
+            arr[i].points = a.ctypes.data if a is not None else None
+            arr[i].stride = stride
+            arr[i].n = n
+        hits = np.zeros(self.map_size(), np.uint8)
+        nr = C.c_size_t(0)
+        self._check(self.lib.lv_map_remove_dynamic(self.h, arr, C.c_size_t(len(views)), C.byref(p),
+                                                   hits.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr)))
+        return int(nr.value), hits
+
     def scan_set(self, pts):
         a, stride, n = _points(pts)
         self._n = n

@@ -7,6 +7,7 @@
 
 #include "lv_host.hpp"
 #include "lv_rebuild.hpp"
+#include "lv_visibility.hpp"
 
 #include <atomic>
 #include <chrono>
@@ -37,6 +38,7 @@ struct lv_ctx {
 
     MapStore map;
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
+    VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -729,6 +731,7 @@ void lv_destroy(lv_ctx* c) {
     c->rebuild.release(c->map, ctx_streams(c));   // (joins its worker and waits for the device before anything is freed)
     c->map.release();
     c->query.release();
+    c->vis.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -930,6 +933,105 @@ int lv_map_evict_oldest(lv_ctx* c, size_t n_oldest, size_t* n_evicted) {
     if (!rc) rc = c->map.evict_oldest(c->stream, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest), &ne);
     if (n_evicted) *n_evicted = ne;
     return rc;
+}
+
+void lv_default_visibility_params(lv_visibility_params* p) {
+    if (!p) return;
+    p->width = 2048;
+    p->height = 64;
+    p->v_min_deg = -25.f;
+    p->v_max_deg = 3.f;
+    p->min_range = 1.f;
+    p->max_range = 80.f;
+    p->margin_abs = 0.3f;
+    p->margin_rel = 0.02f;
+    p->window = 1;
+    p->min_hits = 1;
+    p->dry_run = 0;
+}
+
+// The views and parameters of lv_map_remove_dynamic against its limits: LV_EINVAL (nothing touched) outside them
+static int visibility_rule(const lv_view* views, size_t n_views, const lv_visibility_params* p, VisRule* q) {
+    if (!views || !p) { set_error("null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)VIS_MAX_VIEWS) { set_error("n_views = %zu: must be in 1..%d", n_views, VIS_MAX_VIEWS); return LV_EINVAL; }
+    if (p->width < 1 || p->height < 1 || (size_t)p->width * (size_t)p->height > VIS_MAX_PIXELS) {
+        set_error("image of %d x %d pixels: both >= 1, at most 2^20 in all", p->width, p->height);
+        return LV_EINVAL;
+    }
+    if (!(std::isfinite(p->v_min_deg) && std::isfinite(p->v_max_deg) && p->v_min_deg < p->v_max_deg && p->v_min_deg >= -90.f && p->v_max_deg <= 90.f)) {
+        set_error("vertical field of view [%g, %g] deg: v_min_deg < v_max_deg inside [-90, 90]", p->v_min_deg, p->v_max_deg);
+        return LV_EINVAL;
+    }
+    if (!(std::isfinite(p->min_range) && std::isfinite(p->max_range) && p->min_range > 0.f && p->min_range < p->max_range)) {
+        set_error("ranges [%g, %g]: finite, 0 < min_range < max_range", p->min_range, p->max_range);
+        return LV_EINVAL;
+    }
+    if (!(std::isfinite(p->margin_abs) && std::isfinite(p->margin_rel) && p->margin_abs > 0.f && p->margin_rel > 0.f)) {
+        set_error("margins %g m, %g: finite and > 0", p->margin_abs, p->margin_rel);
+        return LV_EINVAL;
+    }
+    if (p->window < 0 || p->window > VIS_MAX_WINDOW) { set_error("window = %d: must be in 0..%d", p->window, VIS_MAX_WINDOW); return LV_EINVAL; }
+    if (p->min_hits < 1 || (size_t)p->min_hits > n_views) { set_error("min_hits = %d: must be in 1..n_views", p->min_hits); return LV_EINVAL; }
+    size_t total = 0;
+    for (size_t v = 0; v < n_views; ++v) {
+        const lv_view& w = views[v];
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(w.R[i])) { set_error("view %zu: non-finite R", v); return LV_EINVAL; }
+        for (int i = 0; i < 3; ++i) if (!std::isfinite(w.t[i])) { set_error("view %zu: non-finite t", v); return LV_EINVAL; }
+        if (w.n && (!w.points || w.stride < 12)) { set_error("view %zu: bad point array (stride %zu)", v, w.stride); return LV_EINVAL; }
+        total += w.n;
+        if (w.n > 0xFFFFFFF0ull || total > 0xFFFFFFF0ull) { set_error("too many returns"); return LV_EINVAL; }
+    }
+    const double rad = 3.14159265358979323846 / 180.0;
+    q->width = p->width;
+    q->height = p->height;
+    q->n_views = (int)n_views;
+    q->window = p->window;
+    q->min_hits = p->min_hits;
+    q->inv_col = (float)((double)p->width / (2.0 * 3.14159265358979323846));
+    q->v_min = (float)((double)p->v_min_deg * rad);
+    q->inv_row = (float)((double)p->height / (((double)p->v_max_deg - (double)p->v_min_deg) * rad));
+    q->min_range = p->min_range;
+    q->max_range = p->max_range;
+    q->margin_abs = p->margin_abs;
+    q->margin_rel = p->margin_rel;
+    return LV_OK;
+}
+
+// Free-space removal (lv_visibility.hip), ordered like lv_map_evict_box: settle the insert in flight, adopt / drop a finished
+// background rebuild, journal the operation (the window-min images and poses: the worker replays the same pure rule on its copy),
+// order behind a snapshot, act
+int lv_map_remove_dynamic(lv_ctx* c, const lv_view* views, size_t n_views, const lv_visibility_params* p, uint8_t* hits, size_t* n_removed) {
+    LV_CHECK_CTX(c);
+    if (n_removed) *n_removed = 0;
+    VisRule q{};
+    int rc = visibility_rule(views, n_views, p, &q);
+    if (rc) return rc;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    if (!c->map.built || c->map.m == 0) return LV_OK;
+    rc = c->vis.build(c->stream, views, n_views, q);
+    if (rc) return rc;
+    const bool remove = p->dry_run == 0;
+    if (remove) {
+        rc = c->rebuild.journal_replay(c->map, ctx_streams(c), c->vis.d_blob, vis_blob_bytes(q), [q](MapStore& S, hipStream_t s, const void* blob) {
+            return vis_classify(S, s, blob, q, nullptr, nullptr, true, nullptr);
+        });
+        if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
+        if (rc) return rc;
+    }
+    const size_t m = c->map.m;   // (the store that acts: a copy adopted by the journal included)
+    const uint32_t* rank = nullptr;
+    if (hits) {
+        rc = c->vis.ensure_hits(m);
+        if (!rc) rc = c->query.ensure_rank(c->map, c->stream, &rank);
+        if (rc) return rc;
+    }
+    uint32_t nr = 0;
+    rc = vis_classify(c->map, c->stream, c->vis.d_blob, q, rank, hits ? c->vis.d_hits : nullptr, remove, &nr);
+    if (rc) return rc;
+    if (hits) LV_HIP(hipMemcpy(hits, c->vis.d_hits, m, hipMemcpyDeviceToHost));
+    if (n_removed) *n_removed = nr;
+    return LV_OK;
 }
 
 int lv_map_relinearise(lv_ctx* c) {

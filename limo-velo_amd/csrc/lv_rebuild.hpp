@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -174,23 +175,7 @@ public:
             e.n = n;
             e.downsample = downsample;
             e.box = box;
-            const size_t bytes = (((size_t)n * sizeof(float4)) + 255) & ~(size_t)255;
-            if (arena_ && arena_used_ + bytes <= arena_bytes_) {   // a bump arena: no hipMalloc on the caller's thread
-                e.d_pts = reinterpret_cast<float4*>(static_cast<char*>(arena_) + arena_used_);
-                e.from_arena = true;
-                arena_used_ += bytes;
-            } else {
-                LV_HIP(hipMalloc(&e.d_pts, (size_t)n * sizeof(float4)));
-            }
-            // (an error below must not leak the entry: ADVICE r05)
-            hipError_t je = hipMemcpyAsync(e.d_pts, map.d_new, (size_t)n * sizeof(float4), hipMemcpyDeviceToDevice, cs.stream);
-            if (je == hipSuccess) je = hipEventCreateWithFlags(&e.ready, hipEventDisableTiming);
-            if (je == hipSuccess) je = hipEventRecord(e.ready, cs.stream);
-            if (je != hipSuccess) {
-                free_entry(e);
-                set_error("map rebuild journal: %s", hipGetErrorString(je));
-                return LV_EHIP;
-            }
+            { int rc = copy_in(e, map.d_new, (size_t)n * sizeof(float4), cs.stream); if (rc) return rc; }
             if (push(e, st)) return LV_OK;
             free_entry(e);
             if (st == RebuildState::Rebuilding) {   // the worker does not drain the journal as fast as the caller fills it: give the copy up
@@ -226,6 +211,30 @@ public:
         if (push(e, st)) return LV_OK;
         if (st == RebuildState::Rebuilding) give_up(map, cs);   // (journal full: see journal_add)
         if (st == RebuildState::Ready) return poll(map, cs);    // (ready since this call's poll: adopt the copy first, the caller's eviction then acts on it)
+        return LV_OK;
+    }
+
+    // The replay hook of an operation the rebuild does not know (kind 4, lv_map_remove_dynamic): called by the worker with the copy,
+    // its stream and the worker's copy of the operation's device data; it returns an LV_ code.  The rule must be a pure function of
+    // the points' coordinates and that data: ids differ between the stores.
+    using Replay = std::function<int(Store&, hipStream_t, const void*)>;
+
+    // journal such an operation: `bytes` of device data at `src` (copied on the context's stream, behind what produced them) travel
+    // with it.  As journal_evict: nothing to do unless a rebuild is in flight; a full journal gives the copy up; a copy found
+    // ready is adopted first, so the caller's own action then applies to it
+    int journal_replay(Store& map, const CtxStreams& cs, const void* src, size_t bytes, Replay replay) {
+        RebuildState st = state_;
+        if (st != RebuildState::Rebuilding && st != RebuildState::Ready) return LV_OK;
+        if (st == RebuildState::Rebuilding) {
+            Entry e;
+            e.kind = 4;
+            e.replay = std::move(replay);
+            { int rc = copy_in(e, src, bytes, cs.stream); if (rc) return rc; }
+            if (push(e, st)) return LV_OK;
+            free_entry(e);
+        }
+        if (st == RebuildState::Rebuilding) give_up(map, cs);   // (journal full: see journal_add)
+        if (st == RebuildState::Ready) return poll(map, cs);    // (ready since this call's poll: see journal_evict)
         return LV_OK;
     }
 
@@ -323,8 +332,10 @@ public:
 
 private:
     struct Entry {
-        int kind = 0;                     // 0 add (Add_Points rule), 1 add, building if empty (Mapper::add), 2 evict box, 3 evict oldest
-        float4* d_pts = nullptr;          // device copy of the staged batch (owned)
+        int kind = 0;                     // 0 add (Add_Points rule), 1 add, building if empty (Mapper::add), 2 evict box, 3 evict oldest,
+                                          // 4 the caller's replay hook (journal_replay)
+        void* d_data = nullptr;           // device copy of the staged batch (kinds 0, 1) or of the hook's data (kind 4) (owned)
+        Replay replay;
         uint32_t n = 0;
         int downsample = 0;
         float box = 0.2f;
@@ -338,10 +349,32 @@ private:
     static size_t copy_size(const Store& map) { return (size_t)map.m + (size_t)map.m / 8 + 262144; }   // living points + slack
 
     static void free_entry(Entry& e) {
-        if (e.d_pts && !e.from_arena) hipFree(e.d_pts);
+        if (e.d_data && !e.from_arena) hipFree(e.d_data);
         if (e.ready) hipEventDestroy(e.ready);
-        e.d_pts = nullptr;
+        e.d_data = nullptr;
         e.ready = nullptr;
+    }
+
+    // e.d_data = a copy of `bytes` at src, made on `s`; e.ready recorded behind it
+    int copy_in(Entry& e, const void* src, size_t bytes, hipStream_t s) {
+        const size_t rounded = (bytes + 255) & ~(size_t)255;
+        if (arena_ && arena_used_ + rounded <= arena_bytes_) {   // a bump arena: no hipMalloc on the caller's thread
+            e.d_data = static_cast<char*>(arena_) + arena_used_;
+            e.from_arena = true;
+            arena_used_ += rounded;
+        } else {
+            LV_HIP(hipMalloc(&e.d_data, bytes));
+        }
+        // (an error below must not leak the entry: ADVICE r05)
+        hipError_t je = hipMemcpyAsync(e.d_data, src, bytes, hipMemcpyDeviceToDevice, s);
+        if (je == hipSuccess) je = hipEventCreateWithFlags(&e.ready, hipEventDisableTiming);
+        if (je == hipSuccess) je = hipEventRecord(e.ready, s);
+        if (je != hipSuccess) {
+            free_entry(e);
+            set_error("map rebuild journal: %s", hipGetErrorString(je));
+            return LV_EHIP;
+        }
+        return LV_OK;
     }
 
     RebuildState locked_state() {
@@ -432,13 +465,16 @@ private:
             if (e.kind <= 1) {
                 if (hipStreamWaitEvent(st, e.ready, 0) != hipSuccess) rc = LV_EHIP;
                 if (!rc) rc = S.reserve_batch(e.n);
-                if (!rc && hipMemcpyAsync(S.d_new, e.d_pts, (size_t)e.n * sizeof(float4), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = LV_EHIP;
+                if (!rc && hipMemcpyAsync(S.d_new, e.d_data, (size_t)e.n * sizeof(float4), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = LV_EHIP;
                 if (!rc) rc = S.add_staged(st, e.n, e.downsample, e.box, e.kind == 1);
                 if (!rc) rc = S.settle(st);
             } else if (e.kind == 2) {
                 rc = S.evict_box(st, e.lo, e.hi, e.keep_inside, nullptr);
-            } else {
+            } else if (e.kind == 3) {
                 rc = S.evict_oldest(st, e.n_oldest, nullptr);
+            } else {
+                if (hipStreamWaitEvent(st, e.ready, 0) != hipSuccess) rc = LV_EHIP;
+                if (!rc) rc = e.replay(S, st, e.d_data);
             }
             if (hipStreamSynchronize(st) != hipSuccess) rc = rc ? rc : LV_EHIP;
             free_entry(e);

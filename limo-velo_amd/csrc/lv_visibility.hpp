@@ -1,0 +1,48 @@
+// lv_visibility.hpp — free-space removal of dynamic points (lv_map_remove_dynamic, include/limovelo_hip.h "Dynamic-point
+// removal"; kernels and host side in lv_visibility.hip).
+#pragma once
+#include "lv_host.hpp"
+
+namespace lv {
+
+constexpr int VIS_MAX_VIEWS = 32;
+constexpr size_t VIS_MAX_PIXELS = (size_t)1 << 20;   // width * height of one view's image
+constexpr int VIS_MAX_WINDOW = 8;
+
+// The rule of one call, as the kernels take it (angles in radians, the bin scales precomputed on the host)
+struct VisRule {
+    int width, height, n_views, window, min_hits;
+    float inv_col;      // width / (2 pi): columns per radian of azimuth
+    float v_min;        // lowest elevation (rad)
+    float inv_row;      // height / (v_max - v_min): rows per radian of elevation
+    float min_range, max_range, margin_abs, margin_rel;
+};
+
+// Bytes of the device blob a call classifies against: the views' poses (12 floats each: R row-major, t), padded to 256 B, then
+// the n_views window-min images (height x width f32 each).  The background rebuild journals exactly this blob.
+inline size_t vis_pose_bytes(int n_views) { return (((size_t)n_views * 12 * sizeof(float)) + 255) & ~(size_t)255; }
+inline size_t vis_blob_bytes(const VisRule& q) { return vis_pose_bytes(q.n_views) + (size_t)q.n_views * q.width * q.height * sizeof(float); }
+
+// Classification of every living point of `map` against the blob, on `stream`.  rank: NULL (ranks are ids) or the rank among
+// the living by id (QueryStore::ensure_rank); hits: NULL or a device array of map.m counts, written at the ranks.  remove: the
+// points seen through in >= min_hits views leave the map (its dead list, then MapStore::kill_dead_list, as evict_oldest).
+// Synchronises the stream.  Shared by lv_map_remove_dynamic and the background rebuild's replay of it.
+int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const VisRule& q, const uint32_t* rank, uint8_t* hits,
+                 bool remove, uint32_t* n_removed);
+
+// The buffers of lv_map_remove_dynamic (grown on demand, kept): staged returns, the blob and the filter's intermediate image,
+// the hit counts.
+struct VisStore {
+    float4* h_pts = nullptr;     // pinned: the returns of every view, w = the view's index
+    float4* d_pts = nullptr;
+    void* d_blob = nullptr;
+    float* d_tmp = nullptr;
+    uint8_t* d_hits = nullptr;
+    size_t h_pts_cap = 0, d_pts_cap = 0, blob_cap = 0, tmp_cap = 0, hits_cap = 0;
+    // the blob of the call (poses + window-min images) from the views, on `stream`
+    int build(hipStream_t stream, const lv_view* views, size_t n_views, const VisRule& q);
+    int ensure_hits(size_t n);
+    void release();
+};
+
+}  // namespace lv

@@ -369,3 +369,54 @@ def make_stream(m_points: int, n_revs: int, *, n_rings: int = 64, n_az: int = 10
         pl = np.einsum("nji,nj->ni", Rw[idx], pw - pos[idx])
         revs.append(dict(xyz=pl.astype(np.float32), t=tt[ok].copy(), stamp=float(t0 + (r + 1) * rev_time)))
     return dict(map_xyz=map_xyz, revs=revs, L=L)
+
+
+def scene_surfaces(m_points: int, seed_map: int = SEED_MAP):
+    """The rectangles (origin [k, 3], edge u [k, 3], edge v [k, 3]) of the scene make_scene / make_ring_scene(m_points) sample
+    their map from."""
+    o, eu, ev, _, _ = _surfaces(_Rng(seed_map), m_points)
+    return o, eu, ev
+
+
+def ray_cast(rects, origin, dirs, rmin: float = 0.0, rmax: float = np.inf) -> np.ndarray:
+    """Range of the nearest hit of every ray (origin + t dirs, dirs unit [n, 3] in the world) on the rectangles (scene_surfaces)
+    within [rmin, rmax]; +inf where a ray hits nothing."""
+    o, eu, ev = (np.asarray(a, np.float64) for a in rects)
+    origin = np.asarray(origin, np.float64)
+    dirs = np.asarray(dirs, np.float64).reshape(-1, 3)
+    nrm = np.cross(eu, ev)
+    nrm /= np.linalg.norm(nrm, axis=1)[:, None]
+    uu, vv = np.sum(eu * eu, axis=1), np.sum(ev * ev, axis=1)
+    num = np.sum((o - origin) * nrm, axis=1)[None, :]
+    best = np.full(len(dirs), np.inf)
+    for c0 in range(0, len(dirs), 16384):
+        d = dirs[c0:c0 + 16384]
+        den = d @ nrm.T
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = num / den
+            t[~np.isfinite(t) | (t < rmin) | (t > rmax)] = np.inf
+            hit = origin[None, None, :] + np.where(np.isfinite(t), t, 0.0)[:, :, None] * d[:, None, :]
+            rel = hit - o[None, :, :]
+            a = np.sum(rel * eu[None, :, :], axis=2) / uu[None, :]
+            b = np.sum(rel * ev[None, :, :], axis=2) / vv[None, :]
+        t[(a < 0) | (a > 1) | (b < 0) | (b > 1)] = np.inf
+        best[c0:c0 + 16384] = np.min(t, axis=1)
+    return best
+
+
+def ring_sweep(rects, R, t, n_rings: int, n_az: int, fov_deg=(-25.0, 3.0), *, rmin: float = 0.5, rmax: float = 120.0,
+               range_sigma: float = 0.0, seed: int = 7) -> np.ndarray:
+    """The returns [k, 3] f32 in the SENSOR frame of a spinning LiDAR at pose (R sensor -> world, t) over the rectangles: one ray
+    per cell of an n_rings x n_az grid, at the cell's centre (azimuth bins over [-pi, pi), elevation bins over fov_deg), so every
+    return lies in the middle of its range-image pixel.  Rays without a hit are dropped; range_sigma: noise along the ray."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    az = -math.pi + (np.arange(n_az) + 0.5) * (2.0 * math.pi / n_az)
+    el = math.radians(fov_deg[0]) + (np.arange(n_rings) + 0.5) * (math.radians(fov_deg[1] - fov_deg[0]) / n_rings)
+    ce, se = np.cos(el)[:, None], np.sin(el)[:, None]
+    dl = np.stack([ce * np.cos(az)[None, :], ce * np.sin(az)[None, :], se * np.ones_like(az)[None, :]], axis=-1).reshape(-1, 3)
+    r = ray_cast(rects, np.asarray(t, np.float64), dl @ R.T, rmin, rmax)
+    ok = np.isfinite(r)
+    r = r[ok]
+    if range_sigma > 0:
+        r = r + (2.0 * _Rng(seed).uniform(len(r)) - 1.0) * (range_sigma * math.sqrt(3.0))
+    return (dl[ok] * r[:, None]).astype(np.float32)
