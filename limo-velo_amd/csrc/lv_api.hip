@@ -5,11 +5,11 @@
 #include <limits>
 #include <new>
 
+#include "lv_filter.hpp"
 #include "lv_host.hpp"
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
 
-#include <atomic>
 #include <chrono>
 
 namespace lv {
@@ -51,24 +51,11 @@ struct lv_ctx {
                                             // a slot is free again long before its turn comes round)
 
     KfDev* d_kf = nullptr;
-    FilterDev* d_filter = nullptr;  // x, P resident between lv_predict / lv_correct (row f-3)
-    FilterDev* h_filter = nullptr;  // pinned staging
-    bool filter_set = false;
-    int state_src = 0;          // who produced the latest state: 0 nobody yet, 1 the resident filter (lv_filter_set / lv_predict /
-                                // lv_correct), 2 lv_update (d_kf->x) — lv_map_add_scan transforms the scan with that state
+    ResidentFilter filter;   // x, P resident between lv_filter_set / lv_predict / lv_correct / lv_filter_get (lv_filter.hpp)
     KfDev* h_kf = nullptr;  // pinned mirror (logs / trace downloads)
     KfHostIO* h_io = nullptr;  // pinned, host-mapped mailbox: update inputs and results (no copy kernels)
     KfHostIO* d_io = nullptr;  // its device address
     int update_seq = 0;        // number of the update in flight (the finishing pass echoes it into h_io->seq)
-    // lv_predict calls are queued (same Q, up to PREDICT_BATCH steps) and launched together by whatever needs the filter next
-    double pred_Q[144] = {};
-    double pred_steps[PREDICT_BATCH][7] = {};
-    int pred_n = 0;
-    bool pred_src_kf = false;         // the first queued step reads the posterior from kf (filter_in_kf at the time it was queued)
-    bool batch_predict = true;        // lv_set_option "batch_predict" / LV_BATCH_PREDICT=0: one launch per lv_predict
-    bool filter_in_kf = false;        // the resident filter has not been copied out of kf->x / kf->P_post yet (see materialise_filter)
-    bool filter_in_mailbox = false;   // the resident filter == the results in the mailbox (set by lv_correct, cleared by whatever changes the filter)
-    bool mail_filter = true;          // lv_filter_get reads them from there (lv_set_option "mail_filter" 0: always copy)
     bool spin_wait = true;     // lv_update_end polls the mailbox before falling back to hipStreamSynchronize (LV_SPIN_WAIT=0: off)
     double* d_partials = nullptr;
     double* d_groups = nullptr;    // group records (reduce stage 1)
@@ -116,10 +103,6 @@ struct lv_ctx {
     bool qrec_valid = false;       // d_qrec holds the records of a pass over the CURRENT scan (lv_fetch_neighbors)
 
     bool begin_pending = false;    // the update's state waits in h_begin for the first search launch (no begin kernel)
-    bool filter_host = false;      // lv_filter_set just wrote the filter: it lives in h_filter (pinned) until something needs it on the
-                                   // device — the next lv_correct does not: the prior rides in its first launch's arguments
-    bool filter_up_pending = false;   // an upload out of h_filter may still be in flight (ev_filter_up)
-    hipEvent_t ev_filter_up = nullptr;
     BeginArg h_begin;
     int fallback_base = 0;         // device counter value before the update in flight (the device never resets it)
     long mailbox_resyncs = 0;      // updates whose mailbox checksum did not match at first sight (stream synchronised instead)
@@ -178,10 +161,7 @@ struct SlowCall {
 // (lv_comm_destroy) and the filter re-seeded.
 static int peer_poisoned(lv_ctx* c) {
     if (!c->peer.active || !peer_failed(c->peer)) return LV_OK;
-    c->filter_set = false;
-    c->filter_in_kf = false;
-    c->filter_in_mailbox = false;
-    c->pred_n = 0;
+    c->filter.drop();
     c->in_update = false;
     set_error("peer-mapped gather: a rank of the node did not publish its partials in time (or reported a failed exchange): the update "
               "was not adopted; lv_comm_destroy, then lv_filter_set / a new exchange");
@@ -289,52 +269,10 @@ void unpack_sums(const double* rec, lv_sums* out) {
     out->sum_h2 = rec[91];
 }
 
-// from_host: x / P_prop wait in the pinned mailbox (lv_update_begin), otherwise they are in d_kf already (copied
-// from the resident filter): take them over, derive the pass constants
-// The resident filter after lv_correct IS kf->x / kf->P_post (filter_in_kf): the next lv_predict reads it from there and the
-// next lv_correct starts from there; only something that needs it in d_filter, or that is about to overwrite kf (an update
-// by value, lv_iterate), copies it out first — in the 100 Hz cycle that launch never happens.
-// The filter as lv_filter_set left it (pinned host memory) goes to d_filter: needed by whatever reads the resident filter on
-// the device other than an lv_correct that starts right from it.
-static int filter_to_device(lv_ctx* c) {
-    if (!c->filter_host) return LV_OK;
-    c->filter_host = false;
-    LV_HIP(hipMemcpyAsync(c->d_filter, c->h_filter, sizeof(FilterDev), hipMemcpyHostToDevice, c->stream));
-    if (!c->ev_filter_up) LV_HIP(hipEventCreateWithFlags(&c->ev_filter_up, hipEventDisableTiming));
-    LV_HIP(hipEventRecord(c->ev_filter_up, c->stream));
-    c->filter_up_pending = true;
-    return LV_OK;
-}
-static int flush_predicts(lv_ctx* c) {
-    if (c->pred_n == 0) return LV_OK;
-    { int ru = filter_to_device(c); if (ru) return ru; }
-    const int n = c->pred_n;
-    c->pred_n = 0;
-    const KfDev* src = c->pred_src_kf ? c->d_kf : nullptr;
-    c->pred_src_kf = false;
-    return launch_predict(c->stream, c->d_filter, src, c->pred_Q, n, c->pred_steps);
-}
-#define LV_FLUSH_PREDICTS(c)             \
-    do {                                 \
-        int _rp = flush_predicts(c);     \
-        if (_rp) return _rp;             \
-    } while (0)
-
-static int materialise_filter(lv_ctx* c) {
-    if (!c->filter_in_kf) return LV_OK;
-    c->filter_in_kf = false;
-    return launch_kf_to_filter(c->stream, c->d_kf, c->d_filter);
-}
-
-int begin_device(lv_ctx* c, const double* x_host, bool defer, bool from_filter) {
-    LV_FLUSH_PREDICTS(c);   // (a queued prediction may still have to read the posterior from kf, which this update is about to overwrite)
-    // a filter that still waits on the host goes to d_filter now: kf_begin_kernel reads it there (from_filter), and an update by
-    // value / lv_iterate / lv_calculate_H uses kf as its working copy but leaves the resident filter alone (the lv_correct that
-    // CONSUMES the host copy through its launch arguments has cleared filter_host before it calls)
-    { int ru = filter_to_device(c); if (ru) return ru; }
-    if (!from_filter) { int rm = materialise_filter(c); if (rm) return rm; }
+// x_host: x / P_prop ride in the first launch's arguments (or kf_begin_kernel's); else kf_begin_kernel installs prior.dev in kf
+int begin_device(lv_ctx* c, const double* x_host, bool defer, const ResidentFilter::Prior& prior = {}) {
+    if (int rf = c->filter.begin_update(c->stream, c->d_kf, prior.dev != nullptr)) return rf;
     c->begin_pending = false;
-    c->filter_in_mailbox = false;   // (the mailbox is about to receive this update's results)
     if (c->capture) LV_HIP(hipMemsetAsync(c->d_kf->level_hist, 0, sizeof(int) * 8, c->stream));   // instrumentation of capturing passes
     if (defer && x_host && c->scan.n > 0 && c->map.view.m > 0) {
         // the first search launch installs everything (x_host: x followed by P_prop, KfHostIO layout)
@@ -343,9 +281,8 @@ int begin_device(lv_ctx* c, const double* x_host, bool defer, bool from_filter) 
         compute_pose_consts(c->h_begin.x, &c->h_begin.pose);
         c->begin_pending = true;
     } else {
-        int rc = launch_kf_begin(c->stream, c->d_kf, c->d_io, x_host, from_filter ? c->d_filter : nullptr, (from_filter && c->filter_in_kf) ? 1 : 0);
+        int rc = launch_kf_begin(c->stream, c->d_kf, c->d_io, x_host, prior.dev, prior.dev_in_kf);
         if (rc) return rc;
-        if (from_filter) c->filter_in_kf = false;   // (kf->P_post is about to become this update's working copy: the filter proper is d_filter again ... after kf_to_filter / the next predict)
     }
     c->grid = fit_grid_size(c->scan.n, c->max_blocks);
     if ((uint32_t)c->scan.n > c->qstride) {
@@ -370,7 +307,7 @@ int begin_common(lv_ctx* c, const lv_state* x, const double* P, bool defer = tru
         for (int i = 0; i < NS * NS; ++i) io->P_in[i] = (i / NS == i % NS) ? 1.0 : 0.0;
     }
     c->update_seq = (c->update_seq + 1) & 0x3fffffff;
-    return begin_device(c, io->x_in, defer, false);   // x_in and P_in (contiguous) ride in the kernel arguments
+    return begin_device(c, io->x_in, defer);   // x_in and P_in (contiguous) ride in the kernel arguments
 }
 
 int pass_solve(lv_ctx* c, bool from_groups);
@@ -662,7 +599,7 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     if (const char* e = getenv("LV_COMM_FUSED")) c->comm_fused = atoi(e) != 0;
     if (const char* e = getenv("LV_SMALL_WINDOW")) c->scan.small_enabled = atoi(e) != 0;
     if (const char* e = getenv("LV_LARGE_WINDOW")) c->scan.large_enabled = atoi(e) != 0;
-    if (const char* e = getenv("LV_MAIL_FILTER")) c->mail_filter = atoi(e) != 0;
+    if (const char* e = getenv("LV_MAIL_FILTER")) c->filter.mail_filter = atoi(e) != 0;
     if (const char* e = getenv("LV_SMALL_INSERT")) c->map.small_front = atoi(e) != 0;
     if (const char* e = getenv("LV_SURV_LIST")) c->map.surv_list = atoi(e) != 0;
     // (the stamp buffer below is strided by pass_max_wg + 1 workgroup slots: fix the grid limit first)
@@ -683,14 +620,12 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     c->rebuild.create_streams(device, /*quiet=*/true);   // (a failure is retried by the first background rebuild)
     LV_HIP(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
     if (const char* e = getenv("LV_OVERLAP_INSERT")) c->overlap_insert = atoi(e) != 0;
-    if (const char* e = getenv("LV_BATCH_PREDICT")) c->batch_predict = atoi(e) != 0;
+    if (const char* e = getenv("LV_BATCH_PREDICT")) c->filter.batch_predict = atoi(e) != 0;
     if (const char* e = getenv("LV_MERGED_INSERT")) c->map.merged_back = atoi(e) != 0;
     if (const char* e = getenv("LV_SWEEP_EVICT")) c->map.sweep_evict = atoi(e) != 0;
     LV_HIP(hipMalloc(&c->d_kf, sizeof(KfDev)));
     LV_HIP(hipMemset(c->d_kf, 0, sizeof(KfDev)));
-    LV_HIP(hipMalloc(&c->d_filter, sizeof(FilterDev)));
-    LV_HIP(hipMemset(c->d_filter, 0, sizeof(FilterDev)));
-    LV_HIP(hipHostMalloc((void**)&c->h_filter, sizeof(FilterDev), hipHostMallocDefault));
+    if (int rf = c->filter.alloc()) return rf;
     LV_HIP(hipHostMalloc((void**)&c->h_kf, sizeof(KfDev), hipHostMallocDefault));
     std::memset(c->h_kf, 0, sizeof(KfDev));
     LV_HIP(hipHostMalloc((void**)&c->h_io, sizeof(KfHostIO), hipHostMallocMapped));
@@ -738,10 +673,8 @@ void lv_destroy(lv_ctx* c) {
     if (c->h_stage) hipHostFree(c->h_stage);
     if (c->h_kf) hipHostFree(c->h_kf);
     if (c->h_io) hipHostFree(c->h_io);
-    if (c->ev_filter_up) hipEventDestroy(c->ev_filter_up);
-    if (c->h_filter) hipHostFree(c->h_filter);
+    c->filter.release();
     if (c->h_states_ring) hipHostFree(c->h_states_ring);
-    hipFree(c->d_filter);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_cpart[0]); hipFree(c->d_cpart[1]); hipFree(c->d_pclk); hipFree(c->d_wgcost[0]); hipFree(c->d_wgcost[1]);
     if (c->h_gather) hipHostFree(c->h_gather);
@@ -763,7 +696,7 @@ void lv_destroy(lv_ctx* c) {
 
 int lv_set_stream(lv_ctx* c, void* hip_stream) {
     LV_CHECK_CTX(c);
-    LV_FLUSH_PREDICTS(c);
+    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
     // whatever is still tied to the OLD stream is settled on it: a remembered Buffer::clear (CloudStore keeps the stream it was
     // issued on: the caller may destroy that stream after this call) and the outcome of an incremental map insert
     { int rs = c->cloud.settle(); if (rs) return rs; }
@@ -776,7 +709,7 @@ int lv_set_stream(lv_ctx* c, void* hip_stream) {
 void* lv_get_stream(lv_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int lv_synchronize(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    LV_FLUSH_PREDICTS(c);
+    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
     LV_HIP(hipStreamSynchronize(c->stream));
     if (c->side_stream) LV_HIP(hipStreamSynchronize(c->side_stream));
     return LV_OK;
@@ -885,15 +818,13 @@ int lv_map_add_scan(lv_ctx* c, int downsample) {
     LV_RELIN_POLL(c);
     const uint32_t n = c->scan.n;
     if (n == 0) return LV_OK;   // Mapper::add returns on an empty cloud (Mapper.cpp:20)
-    LV_FLUSH_PREDICTS(c);
+    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
     int rc = c->rebuild.maybe_start(c->map, n);
     if (rc) return rc;
     rc = c->map.reserve_batch(n);
     if (rc) return rc;
-    // the state of whichever path ran last (main.cpp:92,102: Xt2 = the state the update just produced — or, before the first
-    // map exists, the propagated state the caller handed to lv_update)
-    { int ru = filter_to_device(c); if (ru) return ru; }
-    const double* x = (c->state_src == 2 || !c->filter_set || c->filter_in_kf) ? c->d_kf->x : c->d_filter->x;
+    if (int ru = c->filter.upload(c->stream)) return ru;
+    const double* x = c->filter.scan_x(c->d_kf);
     hipLaunchKernelGGL(scan_to_world_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, x, c->scan.d_raw, n, c->map.d_new);
     LV_HIP(hipGetLastError());
     // The insert depends on nothing but the world points just staged, and nothing depends on it until the next search: it runs
@@ -1507,9 +1438,9 @@ int lv_set_option(lv_ctx* c, const char* name, int value) {
     else if (!std::strcmp(name, "tile_lpt")) c->tile_lpt = on;
     else if (!std::strcmp(name, "spin_wait")) c->spin_wait = on;
     else if (!std::strcmp(name, "comm_fused")) c->comm_fused = on;
-    else if (!std::strcmp(name, "mail_filter")) c->mail_filter = on;
+    else if (!std::strcmp(name, "mail_filter")) c->filter.mail_filter = on;
     else if (!std::strcmp(name, "overlap_insert")) c->overlap_insert = on;
-    else if (!std::strcmp(name, "batch_predict")) { int rp = flush_predicts(c); if (rp) return rp; c->batch_predict = on; }
+    else if (!std::strcmp(name, "batch_predict")) { if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp; c->filter.batch_predict = on; }
     else if (!std::strcmp(name, "merged_insert")) c->map.merged_back = on;
     else if (!std::strcmp(name, "sweep_evict")) c->map.sweep_evict = on;
     else if (!std::strcmp(name, "small_window")) c->scan.small_enabled = on;
@@ -1723,38 +1654,8 @@ int lv_pass_solve(lv_ctx* c) {
     return pass_solve(c, false);
 }
 
-// The pass that finishes an update stores the sequence number after all results (system-scope stores): poll it for a bounded
-// time (an update takes ~0.2 ms) instead of paying the stream-synchronise wake-up; anything unusual (errors, very long updates)
-// still ends in hipStreamSynchronize (by the caller, when this returns false).
-static bool mailbox_wait(lv_ctx* c) {
-    bool seen = false;
-    if (c->spin_wait && !c->profiling && !c->phase_clocks && !c->capture) {
-        volatile const unsigned long long* sc = &c->h_io->seqcheck;
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned long long word = 0;
-        for (int it = 0;; ++it) {
-            word = *sc;
-            if ((uint32_t)word == (uint32_t)c->update_seq) { seen = true; break; }
-            if ((it & 1023) == 1023 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        if (seen) {
-            // the results were stored before the word, but only the checksum proves that they have all ARRIVED
-            const uint32_t want = (uint32_t)(word >> 32);
-            const KfHostIO* io = c->h_io;
-            uint32_t chk = 0;
-            for (int i = 0; i < NS * NS; ++i) chk ^= mailbox_mix(io->P_post[i], (uint32_t)i);
-            for (int i = 0; i < NX; ++i) chk ^= mailbox_mix(io->x[i], 1000u + (uint32_t)i);
-            chk ^= mailbox_mix((double)io->passes, 2000u);
-            if (chk == MAILBOX_UNCHECKED) chk = 0u;
-            // (MAILBOX_UNCHECKED: the update ended on a pass without matches — a legitimate path that carries no
-            // checksum: synchronise the stream without counting it)
-            if (want == MAILBOX_UNCHECKED) seen = false;
-            else if (chk != want) { seen = false; ++c->mailbox_resyncs; }
-        }
-    }
-    return seen;
-}
+// mailbox_wait's `enabled` (lv_filter.hpp): not where something else waits on the stream anyway
+static bool spin_ok(const lv_ctx* c) { return c->spin_wait && !c->profiling && !c->phase_clocks && !c->capture; }
 
 int lv_update_end(lv_ctx* c, lv_state* x, double* P, int* passes) {
     LV_CHECK_CTX(c);
@@ -1766,7 +1667,7 @@ int lv_update_end(lv_ctx* c, lv_state* x, double* P, int* passes) {
         LV_HIP(hipMemcpyAsync(c->h_kf, c->d_kf, offsetof(KfDev, pose), hipMemcpyDeviceToHost, c->stream));
         LV_HIP(hipStreamSynchronize(c->stream));
     } else {
-        const bool seen = mailbox_wait(c);
+        const bool seen = mailbox_wait(c->h_io, c->update_seq, spin_ok(c), &c->mailbox_resyncs);
         if (!seen) LV_HIP(hipStreamSynchronize(c->stream));
     }
     const KfHostIO* io = c->h_io;
@@ -1794,11 +1695,11 @@ int lv_update(lv_ctx* c, lv_state* x, double* P, int* passes, lv_sums* per_pass,
     LV_SETTLE_MAP(c);
     if (!x || !P) { set_error("null argument"); return LV_EINVAL; }
     if (passes) *passes = 0;
-    c->state_src = 2;
+    c->filter.latest = ResidentFilter::Source::ByValue;
     if (c->map.view.m == 0) {  // Localizator::correct returns without a map (Localizator.cpp:24)
         // ... but the state the caller propagated is the one the first map is built with (main.cpp:92,102 -> lv_map_add_scan)
-        LV_FLUSH_PREDICTS(c);                        // (a resident filter that still lives in kf moves out before kf->x is overwritten)
-        { int rm = materialise_filter(c); if (rm) return rm; }
+        if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;   // (a resident filter that still lives in kf moves out before kf->x is overwritten)
+        if (int rm = c->filter.materialise(c->stream, c->d_kf)) return rm;
         LV_HIP(hipStreamSynchronize(c->stream));   // (x_in of an earlier update may still be in flight)
         std::memcpy(c->h_io->x_in, x, sizeof(double) * NX);
         LV_HIP(hipMemcpyAsync(c->d_kf->x, c->h_io->x_in, sizeof(double) * NX, hipMemcpyHostToDevice, c->stream));
@@ -1887,79 +1788,27 @@ int lv_update(lv_ctx* c, lv_state* x, double* P, int* passes, lv_sums* per_pass,
 int lv_filter_set(lv_ctx* c, const lv_state* x, const double* P) {
     LV_CHECK_CTX(c);
     if (!x || !P) { set_error("null argument"); return LV_EINVAL; }
-    c->pred_n = 0;   // (queued predictions of a filter that is being replaced)
-    c->pred_src_kf = false;
-    // Nothing goes to the device here (round 4; rounds 1-3 synchronised the stream and uploaded): the filter waits in pinned host
-    // memory.  An lv_correct that follows takes it along in its first launch's kernel arguments — exactly as lv_update takes its
-    // x / P — so "set the prior, correct" enqueues without a copy, a begin kernel or a wait; anything else that needs the
-    // filter on the device (lv_predict, lv_map_add_scan, a correct on a route without the argument hand-over) uploads it first.
-    if (c->filter_up_pending) {   // (h_filter is about to be overwritten: an upload out of it must have completed)
-        LV_HIP(hipEventSynchronize(c->ev_filter_up));
-        c->filter_up_pending = false;
-    }
-    std::memcpy(c->h_filter->x, x, sizeof(double) * NX);
-    std::memcpy(c->h_filter->P, P, sizeof(double) * NS * NS);
-    c->filter_host = true;
-    c->filter_set = true;
-    c->filter_in_mailbox = false;
-    c->filter_in_kf = false;
-    c->state_src = 1;
-    return LV_OK;
+    return c->filter.set(x, P);
 }
 
 int lv_filter_get(lv_ctx* c, lv_state* x, double* P) {
     LV_CHECK_CTX(c);
-    if (!c->filter_set) { set_error("lv_filter_get before lv_filter_set"); return LV_ESTATE; }
-    LV_FLUSH_PREDICTS(c);
-    if (c->filter_host) {   // (set and never touched since: it is still where lv_filter_set put it)
-        if (x) std::memcpy(x, c->h_filter->x, sizeof(double) * NX);
-        if (P) std::memcpy(P, c->h_filter->P, sizeof(double) * NS * NS);
-        return LV_OK;
-    }
-    if (c->filter_in_mailbox && c->mail_filter) {
-        // the resident filter is the posterior of the lv_correct just enqueued: its finishing pass stores x, P (and the pass count)
-        // into the host-mapped mailbox as well — wait for THAT (a poll) instead of a copy + stream synchronise (~30 us of wake-up,
-        // once per 100 Hz cycle: the reference's main loop reads the state after every correct, src/main.cpp:96-102)
-        if (!mailbox_wait(c)) LV_HIP(hipStreamSynchronize(c->stream));
-        const KfHostIO* io = c->h_io;
-        if ((unsigned)io->fallback_queries & KF_FAULT_BIT) return report_kf_fault(c, io->fallback_queries);
-        if (x) std::memcpy(x, io->x, sizeof(double) * NX);
-        if (P) std::memcpy(P, io->P_post, sizeof(double) * NS * NS);
-        return LV_OK;
-    }
-    { int rm = materialise_filter(c); if (rm) return rm; }
-    LV_HIP(hipMemcpyAsync(c->h_filter, c->d_filter, sizeof(FilterDev), hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    if (x) std::memcpy(x, c->h_filter->x, sizeof(double) * NX);
-    if (P) std::memcpy(P, c->h_filter->P, sizeof(double) * NS * NS);
-    return LV_OK;
+    const int rc = c->filter.get(c->stream, c->d_kf, c->h_io, c->update_seq, spin_ok(c), &c->mailbox_resyncs, x, P);
+    return rc > 0 ? report_kf_fault(c, rc) : rc;
 }
 
 int lv_predict(lv_ctx* c, double dt, const double* Q, const double acc[3], const double gyro[3]) {
     LV_CHECK_CTX(c);
     if (!Q || !acc || !gyro) { set_error("null argument"); return LV_EINVAL; }
-    if (!c->filter_set) { set_error("lv_predict before lv_filter_set"); return LV_ESTATE; }
-    c->state_src = 1;
-    c->filter_in_mailbox = false;
-    if (c->pred_n > 0 && (c->pred_n >= PREDICT_BATCH || std::memcmp(c->pred_Q, Q, sizeof(c->pred_Q)) != 0)) LV_FLUSH_PREDICTS(c);
-    if (c->pred_n == 0) {
-        std::memcpy(c->pred_Q, Q, sizeof(c->pred_Q));
-        c->pred_src_kf = c->filter_in_kf;
-        c->filter_in_kf = false;
-    }
-    double* st = c->pred_steps[c->pred_n++];
-    st[0] = dt;
-    for (int i = 0; i < 3; ++i) { st[1 + i] = acc[i]; st[4 + i] = gyro[i]; }
-    if (!c->batch_predict) LV_FLUSH_PREDICTS(c);
-    return LV_OK;
+    return c->filter.predict(c->stream, c->d_kf, dt, Q, acc, gyro);
 }
 
 int lv_correct(lv_ctx* c, int* passes) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
-    if (!c->filter_set) { set_error("lv_correct before lv_filter_set"); return LV_ESTATE; }
-    LV_FLUSH_PREDICTS(c);
-    c->state_src = 1;
+    if (int rs = c->filter.need("lv_correct")) return rs;
+    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
+    c->filter.latest = ResidentFilter::Source::Filter;
     if (passes) *passes = 0;
     if (c->map.view.m == 0) return LV_OK;  // Localizator::correct returns without a map (Localizator.cpp:24)
     LV_CHECK_PEER(c);   // (a failed exchange of an EARLIER, asynchronous lv_correct surfaces here at the latest)
@@ -1968,16 +1817,8 @@ int lv_correct(lv_ctx* c, int* passes) {
         return LV_ESTATE;
     }
     c->update_seq = (c->update_seq + 1) & 0x3fffffff;   // (the finishing pass echoes it into the mailbox: lv_filter_get polls for it)
-    int rc;
-    if (c->filter_host) {
-        // the prior was just set by the host: it rides in the first launch's arguments (x followed by P: FilterDev = the layout
-        // begin_device expects), like an update by value — no upload, no begin kernel
-        static_assert(offsetof(FilterDev, P) == sizeof(double) * NX, "x followed by P");
-        c->filter_host = false;
-        rc = begin_device(c, reinterpret_cast<const double*>(c->h_filter), true, false);
-    } else {
-        rc = begin_device(c, nullptr, false, true);       // (kf_begin_kernel installs the filter in kf: no launch of its own)
-    }
+    const ResidentFilter::Prior prior = c->filter.prior();
+    int rc = begin_device(c, prior.host, prior.host != nullptr, prior);
     if (rc) return rc;
     c->in_update = true;
     const int npass = c->prm.MAX_NUM_ITERS + 1;
@@ -1988,18 +1829,8 @@ int lv_correct(lv_ctx* c, int* passes) {
         for (int i = 0; i < npass && !rc; ++i) rc = pass_full(c);
     }
     c->in_update = false;
-    if (rc) {
-        // an enqueue failed part of the way: kf_begin_kernel has installed the prior in kf->x / kf->P_post (P_post is only
-        // rewritten by the pass that ends an update), but passes that did run may have moved kf->x.  Neither "the filter is
-        // d_filter" (possibly older than the prior) nor "the filter is kf" (possibly a half-iterated state) is right:
-        // the filter is declared unset and the caller re-seeds it.
-        c->filter_set = false;
-        c->filter_in_kf = false;
-        c->filter_in_mailbox = false;
-        return rc;
-    }
-    c->filter_in_kf = true;        // (the posterior stays where the update left it: materialise_filter)
-    c->filter_in_mailbox = true;
+    if (rc) { c->filter.drop(); return rc; }   // (an enqueue failed part of the way: passes that did run may have moved kf->x)
+    c->filter.correct_done();
     if (passes) {  // optional: the only synchronisation point
         LV_HIP(hipStreamSynchronize(c->stream));
         LV_CHECK_PEER(c);

@@ -1,6 +1,6 @@
-// lv_common.hpp — host declarations shared by lv_host.hpp and lv_rebuild.hpp (which must build without lv_host.hpp: the host test
-// compiles it against a HIP stand-in).  set_error keeps the message lv_last_error returns (include/limovelo_hip.h), LV_HIP turns a
-// failed HIP call into LV_EHIP.
+// lv_common.hpp — host declarations shared by lv_host.hpp, lv_rebuild.hpp and lv_filter.hpp (the last two must build without
+// lv_host.hpp: their host tests compile them against a HIP stand-in).  set_error keeps the message lv_last_error returns
+// (include/limovelo_hip.h), LV_HIP turns a failed HIP call into LV_EHIP.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +18,12 @@ void set_error(const char* fmt, ...);
             return LV_EHIP;                                                                       \
         }                                                                                         \
     } while (0)
+
+struct KfDev; struct FilterDev;
+// lv_predict.hip: n <= PREDICT_BATCH steps {dt, acc[3], gyro[3]} with one Q in one launch, from kf->x / P_post if src != nullptr
+constexpr int PREDICT_BATCH = 8;   // (== PREDICT_BATCH_MAX of lv_predict.hip)
+int launch_predict(hipStream_t stream, FilterDev* f, const KfDev* src, const double* Q, int n, const double (*steps)[7]);
+int launch_kf_to_filter(hipStream_t stream, const KfDev* kf, FilterDev* f);
 
 void set_slice_pause_us(uint32_t us);   // lv_map.hip: the calling THREAD's sliced launches are spaced by that many microseconds (0: back to back)
 

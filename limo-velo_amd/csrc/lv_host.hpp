@@ -338,12 +338,7 @@ constexpr int PK_DEFAULT_MAX_ROUNDS = 16;   // rounds per workgroup up to which 
 int pass_clock_words();   // stamp words per workgroup (PassLaunch::clk)
 int launch_pass(hipStream_t stream, const PassLaunch& pl, const BeginArg* begin);
 // lv_predict.hip
-// src != nullptr: the state and covariance are read from kf->x / kf->P_post (the posterior of the update just run) instead of f
-constexpr int PREDICT_BATCH = 8;   // (== PREDICT_BATCH_MAX of lv_predict.hip)
-// n <= PREDICT_BATCH steps {dt, acc[3], gyro[3]} with one Q, in one launch
-int launch_predict(hipStream_t stream, FilterDev* f, const KfDev* src, const double* Q, int n, const double (*steps)[7]);
 int launch_filter_to_kf(hipStream_t stream, const FilterDev* f, KfDev* kf);
-int launch_kf_to_filter(hipStream_t stream, const KfDev* kf, FilterDev* f);
 // lv_rows.hip
 int launch_rows_from_matches(hipStream_t stream, const KfDev* kf, const float* p_world, const float* abcd, const float* dist,
                              uint32_t n, int estimate_extrinsics, double* H, double* h);

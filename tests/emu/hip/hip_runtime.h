@@ -3,7 +3,8 @@
 // It lets tests/emu/mapinc_emu.cpp compile the one-thread-per-item kernels of limo-velo_amd/csrc/lv_mapinc.hpp with
 // g++ and run them as plain loops (one "thread" after another, optionally in reverse or shuffled order), so the
 // bookkeeping of the incremental map can be checked against the oracle in the GPU-less container; and it lets
-// tests/emu/rebuild_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp against the fake host API at the end of this file.
+// tests/emu/rebuild_emu.cpp and tests/emu/filter_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp and lv_filter.hpp against the
+// fake host API at the end of this file.
 // Nothing here is linked into, loaded by or reachable from the product library.
 #pragma once
 #include <algorithm>
@@ -55,6 +56,7 @@ typedef struct emu_stream* hipStream_t;
 typedef struct emu_event* hipEvent_t;
 #define hipStreamNonBlocking 0x01
 #define hipEventDisableTiming 0x02
+#define hipHostMallocDefault 0x0
 
 namespace emu_hip {
 struct Call {
@@ -109,6 +111,7 @@ inline hipError_t hipEventCreateWithFlags(hipEvent_t* ev, unsigned) {
 }
 inline hipError_t hipEventDestroy(hipEvent_t ev) { ++emu_hip::state().events_destroyed; return emu_hip::call("hipEventDestroy", nullptr, ev); }
 inline hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) { return emu_hip::call("hipEventRecord", s, ev); }
+inline hipError_t hipEventSynchronize(hipEvent_t ev) { return emu_hip::call("hipEventSynchronize", nullptr, ev); }
 inline hipError_t hipMalloc(void** p, size_t bytes) {
     hipError_t e = emu_hip::call("hipMalloc");
     if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; }
@@ -123,4 +126,18 @@ inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMe
     hipError_t e = emu_hip::call("hipMemcpyAsync", s);
     if (e == hipSuccess && bytes) std::memcpy(dst, src, bytes);
     return e;
+}
+inline hipError_t hipMemset(void* dst, int v, size_t bytes) {
+    hipError_t e = emu_hip::call("hipMemset");
+    if (e == hipSuccess && bytes) std::memset(dst, v, bytes);
+    return e;
+}
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
+    hipError_t e = emu_hip::call("hipHostMalloc");
+    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; }
+    return e;
+}
+inline hipError_t hipHostFree(void* p) {
+    if (p) { std::free(p); ++emu_hip::state().frees; }
+    return emu_hip::call("hipHostFree");
 }
