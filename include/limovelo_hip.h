@@ -264,6 +264,53 @@ void lv_default_visibility_params(lv_visibility_params* p);
 int  lv_map_remove_dynamic(lv_ctx* ctx, const lv_view* views, size_t n_views, const lv_visibility_params* p, uint8_t* hits,
                            size_t* n_removed);
 
+/* ---- Map painting ----------------------------------------------------------------------------
+ * The reference's open TODO (README.md, "Fixes to investigate": "Add vision buffer and ability to paint the map's points"): every
+ * living map point takes the colour of the camera images that see it.  A view is one image with its pinhole camera and its pose
+ * camera -> world (R row-major, t; camera frame x right, y down, z forward).  For every living point p and every view:
+ *   1. p_c = R^T (p - t), each component summed left to right without fusing (as lv_map_remove_dynamic); z = p_c.z.  The point is
+ *      judged only if min_depth <= z <= max_depth.
+ *   2. x = X / z, y = Y / z; only if x*x + y*y <= max_norm_radius^2 (f32; outside it plumb_bob may fold over).
+ *   3. plumb_bob as OpenCV's projectPoints: r2 = x*x + y*y, c = 1 + k1 r2 + k2 r2^2 + k3 r2^3,
+ *      xd = x c + 2 p1 x y + p2 (r2 + 2 x^2), yd = y c + p1 (r2 + 2 y^2) + 2 p2 x y; u = fx xd + cx, v = fy yd + cy; only if
+ *      0 <= u <= width - 1 and 0 <= v <= height - 1 (integer pixel coordinates are pixel centres).
+ *   4. occlusion buffer of ceil(width / s) x ceil(height / s) cells, s = zbuf_scale: a point falls in cell
+ *      (floor((u + 0.5) / s), floor((v + 0.5) / s)); a cell keeps the minimum z of the map's own points that pass 1-3 (empty: +inf).
+ *      Then every cell becomes the minimum over the (2 window + 1)^2 cells around it, clipped at the buffer's edge.
+ *   5. the point is SEEN by the view iff z - zbuf(cell) <= fmaxf(margin_abs, margin_rel * z): the foremost point of a cell always is.
+ *   6. its sample: the image bilinearly at (u, v) in f32, per channel 0..255, taps clamped to the image (MONO8: r = g = b).
+ * A pure function of the living points' coordinates and the call's inputs: no float atomics, bitwise reproducible. */
+enum { LV_IMAGE_RGB8 = 0, LV_IMAGE_BGR8 = 1, LV_IMAGE_MONO8 = 2 };   /* the ROS encodings rgb8 / bgr8 / mono8 */
+typedef struct lv_camera_view {
+    float R[9]; float t[3];          /* pose camera -> world, R row-major; camera frame x right, y down, z forward (OpenCV) */
+    float fx, fy, cx, cy;            /* pinhole, pixels; integer pixel coordinates are pixel centres */
+    float dist[5];                   /* k1, k2, p1, p2, k3 (OpenCV plumb_bob); all zero: no distortion */
+    int   width, height;             /* 1..8192 each, width * height <= 2^24; all views of a call together <= 2^26 pixels */
+    int   format;                    /* LV_IMAGE_* */
+    const void* image; size_t row_stride;   /* bytes between rows, >= width * channels */
+} lv_camera_view;
+typedef struct lv_paint_params {
+    float min_depth, max_depth;      /* 0 < min_depth < max_depth: only points with z in [min_depth, max_depth] are judged */
+    float max_norm_radius;           /* > 0: points whose undistorted sqrt(x^2 + y^2) (x = X/Z, y = Y/Z) exceeds it are not projected */
+    int   zbuf_scale;                /* 1..16: one occlusion cell per zbuf_scale x zbuf_scale pixels */
+    int   window;                    /* 0..8: half-width of the occlusion window-min (clipped at the edges, no wrap) */
+    float margin_abs, margin_rel;    /* finite, > 0 */
+    int   blend;                     /* 0: mean over the views that see the point, 1: the nearest such view (ties: lower index) */
+} lv_paint_params;
+/* Defaults: depth 0.3..60 m, max_norm_radius 1.5, zbuf_scale 4, window 1, margins 0.1 m and 1 %, blend 0. */
+void lv_default_paint_params(lv_paint_params* p);
+/* n_views 1..32.  Outputs, each may be NULL, lv_map_size() entries in map order (the index space of lv_map_fetch / lv_map_knn):
+ *   n_seen[i]        the number of views that see point i;
+ *   rgb[3i .. 3i+2]  blend 0: the seeing views' samples summed in view order, then divided by n_seen[i];
+ *                    blend 1: the sample of the seeing view with the smallest z (ties: the lower view index);
+ *   depth[i]         the smallest z among the seeing views.
+ * A point no view sees: rgb 0, depth +inf, n_seen 0.  Arguments outside the limits above (a non-finite pose or intrinsic, a NULL
+ * image, a format outside LV_IMAGE_* included) give LV_EINVAL and write nothing; an empty or unbuilt map gives LV_OK.  Read-only:
+ * ordered behind every earlier map mutation like lv_map_knn, reads the active store during a background rebuild (nothing is
+ * journaled) and returns once the host outputs are written. */
+int  lv_map_paint(lv_ctx* ctx, const lv_camera_view* views, size_t n_views, const lv_paint_params* p,
+                  float* rgb, float* depth, uint8_t* n_seen);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

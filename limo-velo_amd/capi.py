@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "lv_map_knn", "lv_map_radius_search", "lv_map_box_search",
     "lv_iterate_batch", "lv_update_batch",
     "lv_default_visibility_params", "lv_map_remove_dynamic",
+    "lv_default_paint_params", "lv_map_paint",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -68,6 +69,67 @@ VISIBILITY_ARGTYPES = {
     "lv_map_remove_dynamic": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(C.c_uint8),
                               C.POINTER(C.c_size_t)],
 }
+
+
+LV_IMAGE_RGB8, LV_IMAGE_BGR8, LV_IMAGE_MONO8 = 0, 1, 2
+IMAGE_CHANNELS = {LV_IMAGE_RGB8: 3, LV_IMAGE_BGR8: 3, LV_IMAGE_MONO8: 1}
+
+
+class LvCameraView(C.Structure):  # lv_camera_view
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("dist", C.c_float * 5), ("width", C.c_int), ("height", C.c_int), ("format", C.c_int), ("image", C.c_void_p),
+                ("row_stride", C.c_size_t)]
+
+
+class LvPaintParams(C.Structure):  # lv_paint_params
+    _fields_ = [("min_depth", C.c_float), ("max_depth", C.c_float), ("max_norm_radius", C.c_float), ("zbuf_scale", C.c_int),
+                ("window", C.c_int), ("margin_abs", C.c_float), ("margin_rel", C.c_float), ("blend", C.c_int)]
+
+
+# ctypes signatures of the map painting (include/limovelo_hip.h "Map painting"; tests/test_map_paint_abi.py)
+PAINT_ARGTYPES = {
+    "lv_map_paint": [C.c_void_p, C.POINTER(LvCameraView), C.c_size_t, C.POINTER(LvPaintParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                     C.POINTER(C.c_uint8)],
+}
+
+
+def camera_view(frame):
+    """(LvCameraView, image array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, image
+    ([h, w, 3] or [h, w] uint8; rows may be strided), optional format (LV_IMAGE_*; default RGB8, MONO8 for a 2-D image) and dist
+    (k1, k2, p1, p2, k3)."""
+    img = np.asarray(frame["image"])
+    if img.dtype != np.uint8:
+        raise ValueError("image must be uint8")
+    fmt = int(frame.get("format", LV_IMAGE_MONO8 if img.ndim == 2 else LV_IMAGE_RGB8))
+    ch = IMAGE_CHANNELS.get(fmt)
+    if ch is None or img.ndim != (2 if ch == 1 else 3) or (ch == 3 and img.shape[2] != 3):
+        raise ValueError(f"image of shape {img.shape} does not match format {fmt}")
+    if not (img.strides[-1] == 1 and (ch == 1 or img.strides[1] == 3)):
+        img = np.ascontiguousarray(img)
+    v = LvCameraView()
+    v.R[:] = [float(x) for x in np.asarray(frame["R"], np.float32).ravel()]
+    v.t[:] = [float(x) for x in np.asarray(frame["t"], np.float32).ravel()]
+    v.fx, v.fy, v.cx, v.cy = (float(frame[k]) for k in ("fx", "fy", "cx", "cy"))
+    v.dist[:] = [float(x) for x in np.asarray(frame.get("dist", np.zeros(5)), np.float32).ravel()]
+    v.height, v.width = int(img.shape[0]), int(img.shape[1])
+    v.format = fmt
+    v.image = img.ctypes.data
+    v.row_stride = int(img.strides[0])
+    return v, img
+
+
+def camera_pose(state, R_IC, t_IC):
+    """(R [3, 3] f32, t [3] f32): the camera -> world pose of an lv_state (26 f64) and the camera -> IMU extrinsic (R_IC, t_IC):
+    R = R_WI R_IC, t = R_WI t_IC + p_WI, composed in f64 (the IMU rotation from the state's quaternion qx, qy, qz, qw), rounded
+    to f32 once."""
+    x = np.asarray(state, np.float64).ravel()
+    qx, qy, qz, qw = x[3:7]
+    R_WI = np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)],
+                     [2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)],
+                     [2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)]])
+    R_IC = np.asarray(R_IC, np.float64).reshape(3, 3)
+    t_IC = np.asarray(t_IC, np.float64).ravel()
+    return (R_WI @ R_IC).astype(np.float32), (R_WI @ t_IC + x[0:3]).astype(np.float32)
 
 
 def sensor_pose(state):
@@ -234,7 +296,9 @@ def load_library() -> C.CDLL:
         lib.lv_default_params.restype = None
         lib.lv_default_visibility_params.restype = None
         lib.lv_default_visibility_params.argtypes = [C.POINTER(VisibilityParams)]
-        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES}.items():
+        lib.lv_default_paint_params.restype = None
+        lib.lv_default_paint_params.argtypes = [C.POINTER(LvPaintParams)]
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -256,6 +320,14 @@ def default_params(**kw) -> Params:
 def default_visibility_params(**kw) -> VisibilityParams:
     p = VisibilityParams()
     load_library().lv_default_visibility_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_paint_params(**kw) -> LvPaintParams:
+    p = LvPaintParams()
+    load_library().lv_default_paint_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -433,6 +505,24 @@ class Context:
         self._check(self.lib.lv_map_remove_dynamic(self.h, arr, C.c_size_t(len(views)), C.byref(p),
                                                    hits.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr)))
         return int(nr.value), hits
+
+    # --- map painting
+    def map_paint(self, views, params: LvPaintParams | None = None):
+        """(rgb [m, 3] f32, depth [m] f32, n_seen [m] uint8) in map order: lv_map_paint over views = [frame dict (camera_view)]."""
+        p = params if params is not None else default_paint_params()
+        arr = (LvCameraView * max(len(views), 1))()
+        keep = []
+        for i, f in enumerate(views):
+            arr[i], img = camera_view(f)
+            keep.append(img)
+        m = self.map_size()
+        rgb = np.zeros((m, 3), np.float32)
+        depth = np.full(m, np.inf, np.float32)
+        seen = np.zeros(m, np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.lv_map_paint(self.h, arr, C.c_size_t(len(views)), C.byref(p), rgb.ctypes.data_as(fp), depth.ctypes.data_as(fp),
+                                          seen.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return rgb, depth, seen
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

@@ -9,6 +9,7 @@
 #include "lv_host.hpp"
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
+#include "lv_paint.hpp"
 
 #include <chrono>
 
@@ -39,6 +40,7 @@ struct lv_ctx {
     MapStore map;
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
     VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
+    PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -667,6 +669,7 @@ void lv_destroy(lv_ctx* c) {
     c->map.release();
     c->query.release();
     c->vis.release();
+    c->paint.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -962,6 +965,123 @@ int lv_map_remove_dynamic(lv_ctx* c, const lv_view* views, size_t n_views, const
     if (rc) return rc;
     if (hits) LV_HIP(hipMemcpy(hits, c->vis.d_hits, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;
+    return LV_OK;
+}
+
+void lv_default_paint_params(lv_paint_params* p) {
+    if (!p) return;
+    p->min_depth = 0.3f;
+    p->max_depth = 60.f;
+    p->max_norm_radius = 1.5f;
+    p->zbuf_scale = 4;
+    p->window = 1;
+    p->margin_abs = 0.1f;
+    p->margin_rel = 0.01f;
+    p->blend = 0;
+}
+
+// The views and parameters of lv_map_paint against its limits: LV_EINVAL (nothing written) outside them; inside, the rule as the
+// kernels take it and every view's place in the call's buffers
+static int paint_rule(const lv_camera_view* views, size_t n_views, const lv_paint_params* p, PaintRule* q, PaintCam* cams) {
+    if (!views || !p) { set_error("null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)PAINT_MAX_VIEWS) { set_error("n_views = %zu: must be in 1..%d", n_views, PAINT_MAX_VIEWS); return LV_EINVAL; }
+    if (!(std::isfinite(p->min_depth) && std::isfinite(p->max_depth) && p->min_depth > 0.f && p->min_depth < p->max_depth)) {
+        set_error("depths [%g, %g]: finite, 0 < min_depth < max_depth", p->min_depth, p->max_depth);
+        return LV_EINVAL;
+    }
+    if (!(std::isfinite(p->max_norm_radius) && p->max_norm_radius > 0.f)) { set_error("max_norm_radius = %g: finite and > 0", p->max_norm_radius); return LV_EINVAL; }
+    if (p->zbuf_scale < 1 || p->zbuf_scale > PAINT_MAX_SCALE) { set_error("zbuf_scale = %d: must be in 1..%d", p->zbuf_scale, PAINT_MAX_SCALE); return LV_EINVAL; }
+    if (p->window < 0 || p->window > PAINT_MAX_WINDOW) { set_error("window = %d: must be in 0..%d", p->window, PAINT_MAX_WINDOW); return LV_EINVAL; }
+    if (!(std::isfinite(p->margin_abs) && std::isfinite(p->margin_rel) && p->margin_abs > 0.f && p->margin_rel > 0.f)) {
+        set_error("margins %g m, %g: finite and > 0", p->margin_abs, p->margin_rel);
+        return LV_EINVAL;
+    }
+    if (p->blend != 0 && p->blend != 1) { set_error("blend = %d: must be 0 or 1", p->blend); return LV_EINVAL; }
+    const int s = p->zbuf_scale;
+    size_t pixels = 0, cells = 0, raw = 0;
+    uint32_t max_pixels = 0, max_cells = 0;
+    for (size_t v = 0; v < n_views; ++v) {
+        const lv_camera_view& w = views[v];
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(w.R[i])) { set_error("view %zu: non-finite R", v); return LV_EINVAL; }
+        for (int i = 0; i < 3; ++i) if (!std::isfinite(w.t[i])) { set_error("view %zu: non-finite t", v); return LV_EINVAL; }
+        if (!(std::isfinite(w.fx) && std::isfinite(w.fy) && std::isfinite(w.cx) && std::isfinite(w.cy))) { set_error("view %zu: non-finite intrinsics", v); return LV_EINVAL; }
+        for (int i = 0; i < 5; ++i) if (!std::isfinite(w.dist[i])) { set_error("view %zu: non-finite distortion", v); return LV_EINVAL; }
+        if (w.width < 1 || w.height < 1 || w.width > PAINT_MAX_SIDE || w.height > PAINT_MAX_SIDE || (size_t)w.width * (size_t)w.height > PAINT_MAX_PIXELS) {
+            set_error("view %zu: image of %d x %d pixels: each side 1..%d, at most 2^24 in all", v, w.width, w.height, PAINT_MAX_SIDE);
+            return LV_EINVAL;
+        }
+        if (w.format != LV_IMAGE_RGB8 && w.format != LV_IMAGE_BGR8 && w.format != LV_IMAGE_MONO8) { set_error("view %zu: format %d", v, w.format); return LV_EINVAL; }
+        const size_t row = (size_t)w.width * (w.format == LV_IMAGE_MONO8 ? 1 : 3);
+        if (!w.image || w.row_stride < row) { set_error("view %zu: null image or row_stride %zu < %zu", v, w.row_stride, row); return LV_EINVAL; }
+        const size_t np = (size_t)w.width * (size_t)w.height;
+        const int cw = (w.width + s - 1) / s, ch = (w.height + s - 1) / s;
+        PaintCam& c = cams[v];
+        std::memset(&c, 0, sizeof(c));
+        std::memcpy(c.R, w.R, sizeof(c.R));
+        std::memcpy(c.t, w.t, sizeof(c.t));
+        c.fx = w.fx;
+        c.fy = w.fy;
+        c.cx = w.cx;
+        c.cy = w.cy;
+        c.k1 = w.dist[0];
+        c.k2 = w.dist[1];
+        c.p1 = w.dist[2];
+        c.p2 = w.dist[3];
+        c.k3 = w.dist[4];
+        c.wm1 = (float)(w.width - 1);
+        c.hm1 = (float)(w.height - 1);
+        c.width = w.width;
+        c.height = w.height;
+        c.cw = cw;
+        c.ch = ch;
+        c.format = w.format;
+        c.tex_off = (uint32_t)pixels;
+        c.cell_off = (uint32_t)cells;
+        c.raw_off = (uint32_t)raw;
+        pixels += np;
+        cells += (size_t)cw * (size_t)ch;
+        raw += (row * (size_t)w.height + 255) & ~(size_t)255;
+        if (pixels > PAINT_MAX_TOTAL_PIXELS) { set_error("the views hold more than 2^26 pixels together"); return LV_EINVAL; }
+        if (np > max_pixels) max_pixels = (uint32_t)np;
+        if ((uint32_t)(cw * ch) > max_cells) max_cells = (uint32_t)(cw * ch);
+    }
+    q->n_views = (int)n_views;
+    q->window = p->window;
+    q->blend = p->blend;
+    q->min_depth = p->min_depth;
+    q->max_depth = p->max_depth;
+    q->r2_max = p->max_norm_radius * p->max_norm_radius;
+    q->s = (float)s;
+    q->margin_abs = p->margin_abs;
+    q->margin_rel = p->margin_rel;
+    q->max_pixels = max_pixels;
+    q->max_cells = max_cells;
+    q->total_pixels = pixels;
+    q->total_cells = cells;
+    q->raw_bytes = raw;
+    return LV_OK;
+}
+
+// Map painting (lv_paint.hip), read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished
+// background rebuild, read the active store
+int lv_map_paint(lv_ctx* c, const lv_camera_view* views, size_t n_views, const lv_paint_params* p, float* rgb, float* depth, uint8_t* n_seen) {
+    LV_CHECK_CTX(c);
+    PaintRule q{};
+    PaintCam cams[PAINT_MAX_VIEWS];
+    int rc = paint_rule(views, n_views, p, &q, cams);
+    if (rc) return rc;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    if (!c->map.built || c->map.m == 0 || !(rgb || depth || n_seen)) return LV_OK;
+    const size_t m = c->map.m;
+    const uint32_t* rank = nullptr;
+    rc = c->query.ensure_rank(c->map, c->stream, &rank);
+    if (!rc) rc = c->paint.run(c->map, c->stream, views, cams, q, rank, rgb != nullptr, depth != nullptr, n_seen != nullptr);
+    if (rc) return rc;
+    if (rgb) LV_HIP(hipMemcpyAsync(rgb, c->paint.d_rgb, 3 * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (depth) LV_HIP(hipMemcpyAsync(depth, c->paint.d_depth, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n_seen) LV_HIP(hipMemcpyAsync(n_seen, c->paint.d_seen, m, hipMemcpyDeviceToHost, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
     return LV_OK;
 }
 

@@ -420,3 +420,56 @@ def ring_sweep(rects, R, t, n_rings: int, n_az: int, fov_deg=(-25.0, 3.0), *, rm
     if range_sigma > 0:
         r = r + (2.0 * _Rng(seed).uniform(len(r)) - 1.0) * (range_sigma * math.sqrt(3.0))
     return (dl[ok] * r[:, None]).astype(np.float32)
+
+
+def texture_rgb(p) -> np.ndarray:
+    """A smooth colour [n, 3] f64 in 26..230 for world points p [n, 3]: at most ~32 levels per metre along any axis."""
+    p = np.asarray(p, np.float64).reshape(-1, 3)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([128.0 + 100.0 * np.sin(0.23 * x + 0.17 * z), 128.0 + 100.0 * np.sin(0.21 * y - 0.19 * z + 1.0),
+                     128.0 + 100.0 * np.sin(0.15 * (x + y) + 0.2 * z + 2.0)], axis=1)
+
+
+def box_rects(center, size):
+    """The six faces (origin [6, 3], edge u [6, 3], edge v [6, 3]) of an axis-aligned box."""
+    c, s = np.asarray(center, np.float64), np.asarray(size, np.float64)
+    lo = c - s / 2
+    ex, ey, ez = np.diag(s)
+    o = np.array([lo, lo + ez, lo, lo + ey, lo, lo + ex])
+    eu = np.array([ex, ex, ex, ex, ey, ey])
+    ev = np.array([ey, ey, ez, ez, ez, ez])
+    return o, eu, ev
+
+
+def sample_rects(rects, n: int, seed: int = 3) -> np.ndarray:
+    """n points [n, 3] f32 uniformly over the rectangles (by area)."""
+    o, eu, ev = (np.asarray(a, np.float64) for a in rects)
+    area = np.linalg.norm(np.cross(eu, ev), axis=1)
+    rng = _Rng(seed)
+    u = rng.uniform(n * 3).reshape(n, 3)
+    which = np.minimum(np.searchsorted(np.cumsum(area) / np.sum(area), u[:, 0], side="right"), len(area) - 1)
+    return (o[which] + u[:, 1:2] * eu[which] + u[:, 2:3] * ev[which]).astype(np.float32)
+
+
+def render_pinhole(rects, R, t, fx: float, fy: float, cx: float, cy: float, width: int, height: int, *, texture=texture_rgb,
+                   occluders=(), rmax: float = 200.0):
+    """(image [height, width, 3] uint8, range [height, width] f64) that an undistorted pinhole camera at pose (R camera -> world,
+    t; x right, y down, z forward) sees of the rectangles: one ray per pixel centre (ray_cast), coloured by texture(hit point)
+    rounded to uint8.  occluders: [(rects, (r, g, b))], solid-coloured surfaces in front of the scene's; no hit: black, +inf."""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    origin = np.asarray(t, np.float64)
+    jj, ii = np.meshgrid(np.arange(height, dtype=np.float64), np.arange(width, dtype=np.float64), indexing="ij")
+    d = np.stack([(ii.ravel() - cx) / fx, (jj.ravel() - cy) / fy, np.ones(width * height)], axis=1)
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    dw = d @ R.T
+    r = ray_cast(rects, origin, dw, 0.0, rmax)
+    hit = np.isfinite(r)
+    col = np.zeros((len(r), 3))
+    col[hit] = texture(origin + r[hit, None] * dw[hit])
+    for occ, rgb in occluders:
+        ro = ray_cast(occ, origin, dw, 0.0, rmax)
+        front = ro < r
+        col[front] = np.asarray(rgb, np.float64)
+        r = np.where(front, ro, r)
+    img = np.clip(np.rint(col), 0, 255).astype(np.uint8).reshape(height, width, 3)
+    return img, r.reshape(height, width)
