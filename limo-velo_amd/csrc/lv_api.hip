@@ -67,24 +67,13 @@ struct lv_ctx {
     double* h_sums = nullptr;  // pinned
     int max_blocks = 1024;
     int grid = 1;
-    void* comm = nullptr;          // RCCL communicator (lv_comm_init): every pass all-reduces the record
-    int comm_rank = 0, comm_world = 1;
     bool fold_direct = false;      // this pass: solve_kernel reads the block partials directly
     bool tile_lpt = true;          // dispatch the search tiles farthest-first (LV_TILE_LPT=0: plain order, A/B knob)
     float4* d_qrec = nullptr;      // search -> fit hand-over: 8 float4 planes of qstride entries (one record per scan point)
     uint32_t qstride = 0;
     // one launch per pass (pass_kernel, lv_pass_dev.hpp): compact workgroup partials, ping-pong by pass parity
     double* d_cpart[2] = {nullptr, nullptr};
-    // multi-GPU form of the one-launch-per-pass update: every rank's partials gathered on every rank (ncclAllGather, in place)
-    double* d_gather[2] = {nullptr, nullptr};
-    size_t gather_cap = 0;            // doubles per buffer
-    size_t comm_shard_max = 0;        // largest shard of the CURRENT scan over the ranks (lv_comm_set_shard_max); 0: unknown
-    bool comm_fused = true;           // lv_set_comm_fused / LV_COMM_FUSED=0: always the three-kernel pass + all-reduce with a communicator
-    PeerSet peer;                      // lv_comm_peer_export / _init: the partials pulled out of the other ranks' peer-mapped buffers (lv_peer.hip)
-    lv_gather_fn gather_cb = nullptr;  // lv_comm_set_host_gather: the partials of the ranks exchanged by the caller through host memory
-    void* gather_user = nullptr;       //   (test / bring-up transport of the one-launch-per-pass multi-rank form; no librccl involved)
-    double* h_gather = nullptr;        //   pinned staging, world x slot doubles
-    size_t h_gather_cap = 0;
+    RankExchange ranks;   // multi-GPU: how the partials of every pass reach every rank (lv_exchange.hpp)
     uint32_t* d_wgcost[2] = {nullptr, nullptr};   // per searching workgroup: how long its search + fits took (picks the next bookkeeper)
     int pass_max_wg = 256;         // search workgroups of pass_kernel: all resident at once (one 1024-thread workgroup per CU)
     bool fused_pass = true;        // LV_FUSED_PASS=0: the three-kernel pass (search / fit / solve) also where pass_kernel applies
@@ -162,18 +151,13 @@ struct SlowCall {
 // — the resident filter is declared unset — and every later call of the data path fails until the exchange is torn down
 // (lv_comm_destroy) and the filter re-seeded.
 static int peer_poisoned(lv_ctx* c) {
-    if (!c->peer.active || !peer_failed(c->peer)) return LV_OK;
+    if (!c->ranks.failed()) return LV_OK;
     c->filter.drop();
     c->in_update = false;
     set_error("peer-mapped gather: a rank of the node did not publish its partials in time (or reported a failed exchange): the update "
               "was not adopted; lv_comm_destroy, then lv_filter_set / a new exchange");
     return LV_ESTATE;
 }
-#define LV_CHECK_PEER(c)                 \
-    do {                                 \
-        int _rq = peer_poisoned(c);      \
-        if (_rq) return _rq;             \
-    } while (0)
 
 // an incremental insert leaves its outcome in flight (MapStore::settle): pick it up before the map's bookkeeping is used
 #define LV_SETTLE_MAP(c)                               \
@@ -360,17 +344,16 @@ int pass_reduce(lv_ctx* c, bool finalize) {
 // record is all-reduced in place on the stream and every rank solves from the identical record.
 int pass_full(lv_ctx* c) {
     // (a rank without points still runs the pass: its partials are zeros and solve_prep must run)
-    int rc = pass_reduce(c, c->comm != nullptr);
-    if (rc) return rc;
-    if (c->comm) {
+    const bool reduced = c->ranks.transport == RankExchange::Transport::Rccl;
+    if (int rc = pass_reduce(c, reduced)) return rc;
+    if (reduced) {
         const int i = c->pass_index;
         const bool timed = c->profiling && i >= 0 && (size_t)(2 * i + 1) < c->ev_coll.size();
         if (timed) LV_HIP(hipEventRecord(c->ev_coll[2 * i], c->stream));
-        rc = comm_allreduce_record(c->comm, c->d_sums, c->stream);
-        if (rc) return rc;
+        if (int rc = c->ranks.allreduce(c->stream, c->d_sums)) return rc;
         if (timed) { LV_HIP(hipEventRecord(c->ev_coll[2 * i + 1], c->stream)); c->coll_timed = true; }
     }
-    return pass_solve(c, c->comm == nullptr);
+    return pass_solve(c, !reduced);
 }
 
 int pass_solve(lv_ctx* c, bool from_groups) {
@@ -406,35 +389,23 @@ static int report_kf_fault(lv_ctx* c, int raw) {
 }
 static inline int fallback_count(int raw) { return raw & (int)~KF_FAULT_BIT; }
 
-static inline bool multi_rank(const lv_ctx* c) { return c->comm != nullptr || c->gather_cb != nullptr || c->peer.active; }
-// transports that only carry the one-launch form's partials (no 96-double all-reduce behind them)
-static inline bool gather_only(const lv_ctx* c) { return c->gather_cb != nullptr || c->peer.active; }
 // doubles per compact workgroup partial (PassDims<W>::OW, lv_pass_dev.hpp): 32 for the 6-column rows, 96 with extrinsics
 static inline size_t partial_width(const lv_ctx* c) { return c->prm.estimate_extrinsics ? 96u : 32u; }
-uint32_t pass_geometry_points(const lv_ctx* c) { return multi_rank(c) ? (uint32_t)c->comm_shard_max : c->scan.n; }
+uint32_t pass_geometry_points(const lv_ctx* c) { return c->ranks.multi_rank() ? (uint32_t)c->ranks.shard_max : c->scan.n; }
 
 bool pass_fused_applies(const lv_ctx* c) {
     // (multi-round scans run pass_kernel<.., MULTI>: a round's plane fits run on four wavefronts beside the next round's search
     // on the other twelve; measured r04 per update: 131 072 points 191.8 us, 196 608 249.1, 262 144 304.9 against 329.3 with
     // three kernels.  The estimate_extrinsics build keeps round 3's form — a barrier either side of every round's fits — and
     // its limit of three rounds: 262 144 points 356 vs 352 us)
-    if (multi_rank(c)) {
-        // with a communicator: the caller has told the largest shard of this scan (lv_comm_set_shard_max), librccl has
-        // ncclAllGather (or the caller exchanges the partials itself: lv_comm_set_host_gather), the gather buffers are in
-        // place; a rank without points still runs every launch
-        if (!c->comm_fused || c->comm_shard_max == 0 || c->scan.n > c->comm_shard_max || (c->comm && !comm_has_allgather()) ||
-            !c->d_gather[0])
-            return false;
-    } else if (c->scan.n == 0) {
-        return false;
-    }
+    if (c->ranks.multi_rank() ? !c->ranks.fused_ready(c->scan.n) : c->scan.n == 0) return false;   // (a rank without points still runs every launch)
     int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
     pass_grid_size(pass_geometry_points(c), c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
     // (round 5: estimate_extrinsics takes the overlapped multi-round form as well — its rows staged in two halves — so the
     // limit of three rounds it had is gone: xaloc.yaml's configuration stays on one launch per pass up to the same sixteen)
     const int max_rounds = c->fused_multi_round > 0 ? INT32_MAX : c->fused_multi_round == 0 ? 3 : PK_DEFAULT_MAX_ROUNDS;
     if (rounds > max_rounds) return false;
-    if (multi_rank(c) && (size_t)nwg * (size_t)c->comm_world * partial_width(c) > c->gather_cap) return false;
+    if (c->ranks.multi_rank() && !c->ranks.fits((size_t)nwg * partial_width(c))) return false;
     // (degeneracy_mode 1 only REPORTS eigenvalues: derived on the host from the logged sums, lv_get_degeneracy_values)
     return c->fused_pass && !c->capture && !c->phase_clocks && c->prm.degeneracy_mode <= 1 && c->prm.NUM_MATCH_POINTS == KNN &&
            c->prm.lanes_per_query == 8 && (c->prm.estimate_extrinsics == 0 || c->fused_ext) && c->map.view.m > 0;
@@ -468,7 +439,7 @@ int update_fused(lv_ctx* c) {
     pl.sp.degeneracy_threshold = c->prm.degeneracy_threshold;
     int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
     pass_grid_size(pass_geometry_points(c), c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
-    const bool gathered = multi_rank(c);                      // multi-GPU: the partials of all ranks, gathered after every launch
+    const bool gathered = c->ranks.multi_rank();              // multi-GPU: the partials of all ranks, gathered after every launch
     const size_t slot = (size_t)nwg * partial_width(c);       // doubles per rank in the gather buffers (compact records)
     pl.multi_overlap = c->multi_overlap;
     pl.qrec = c->record_dump ? c->d_qrec : nullptr;
@@ -479,9 +450,9 @@ int update_fused(lv_ctx* c) {
     for (int i = 0; i <= npass; ++i) {
         const bool closing = i == npass;
         pl.mode = i == 0 ? (c->begin_pending ? 0 : 2) : 1;
-        pl.recs_in = gathered ? c->d_gather[(i + 1) & 1] : c->d_cpart[(i + 1) & 1];
-        pl.part_out = gathered ? c->d_gather[i & 1] + (size_t)c->comm_rank * slot : c->d_cpart[i & 1];
-        pl.nrec = gathered ? nwg * c->comm_world : nwg;
+        pl.recs_in = gathered ? c->ranks.d_gather[(i + 1) & 1] : c->d_cpart[(i + 1) & 1];
+        pl.part_out = gathered ? c->ranks.part_out(i & 1, slot) : c->d_cpart[i & 1];
+        pl.nrec = c->ranks.nrec(nwg);
         pl.cost_in = (i > 0 && c->keeper_by_cost) ? c->d_wgcost[(i + 1) & 1] : nullptr;
         pl.cost_out = c->d_wgcost[i & 1];
         pl.nwg = nwg;
@@ -497,24 +468,7 @@ int update_fused(lv_ctx* c) {
         if (c->profiling && !closing) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 1], c->stream));   // (the pass kernel alone)
         if (gathered && !closing) {
             if (c->profiling) LV_HIP(hipEventRecord(c->ev_coll[2 * i], c->stream));
-            if (c->gather_cb) {
-                // the caller's transport: this rank's slot to pinned host memory, the callback fills in the other ranks' slots
-                // (it blocks until they are there), everything back — the launches of an update are no longer back to back
-                double* own = c->h_gather + (size_t)c->comm_rank * slot;
-                LV_HIP(hipMemcpyAsync(own, c->d_gather[i & 1] + (size_t)c->comm_rank * slot, slot * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-                LV_HIP(hipStreamSynchronize(c->stream));
-                if (c->gather_cb(c->gather_user, c->h_gather, slot * sizeof(double), c->comm_rank, c->comm_world) != 0) {
-                    set_error("host gather callback failed (launch %d)", i);
-                    return LV_ESTATE;
-                }
-                LV_HIP(hipMemcpyAsync(c->d_gather[i & 1], c->h_gather, slot * sizeof(double) * (size_t)c->comm_world, hipMemcpyHostToDevice, c->stream));
-                rc = LV_OK;
-            } else if (c->peer.active) {
-                rc = peer_gather(c->peer, i & 1, slot, c->stream);   // publish this rank's slot, pull the others' (one small kernel)
-            } else {
-                rc = comm_allgather_inplace(c->comm, c->d_gather[i & 1], slot, c->comm_rank, c->stream);
-            }
-            if (rc) return rc;
+            if ((rc = c->ranks.exchange(c->stream, i, slot))) return rc;
             if (c->profiling) LV_HIP(hipEventRecord(c->ev_coll[2 * i + 1], c->stream));
         }
         if (c->profiling && !closing) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 2], c->stream));
@@ -598,7 +552,7 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     if (const char* e = getenv("LV_RELIN_PAUSE_US")) c->rebuild.opt.pause_us = (uint32_t)atol(e);
     if (const char* e = getenv("LV_MULTI_OVERLAP")) c->multi_overlap = atoi(e) != 0;   // A/B: 0 = every round's fits between two barriers
     if (const char* e = getenv("LV_KEEPER_BY_COST")) c->keeper_by_cost = atoi(e) != 0;
-    if (const char* e = getenv("LV_COMM_FUSED")) c->comm_fused = atoi(e) != 0;
+    if (const char* e = getenv("LV_COMM_FUSED")) c->ranks.fused = atoi(e) != 0;
     if (const char* e = getenv("LV_SMALL_WINDOW")) c->scan.small_enabled = atoi(e) != 0;
     if (const char* e = getenv("LV_LARGE_WINDOW")) c->scan.large_enabled = atoi(e) != 0;
     if (const char* e = getenv("LV_MAIL_FILTER")) c->filter.mail_filter = atoi(e) != 0;
@@ -664,7 +618,7 @@ void lv_destroy(lv_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     c->cloud.release();
-    if (c->comm) { hipStreamSynchronize(c->stream); comm_destroy(c->comm); c->comm = nullptr; }
+    c->ranks.release_comm(c->stream);
     c->rebuild.release(c->map, ctx_streams(c));   // (joins its worker and waits for the device before anything is freed)
     c->map.release();
     c->query.release();
@@ -680,12 +634,7 @@ void lv_destroy(lv_ctx* c) {
     if (c->h_states_ring) hipHostFree(c->h_states_ring);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_cpart[0]); hipFree(c->d_cpart[1]); hipFree(c->d_pclk); hipFree(c->d_wgcost[0]); hipFree(c->d_wgcost[1]);
-    if (c->h_gather) hipHostFree(c->h_gather);
-    if (c->peer.local_alloc) {   // (once lv_comm_peer_init succeeded the gather buffers ARE the peer allocation: freed by peer_close alone)
-        if (c->peer.active) c->d_gather[0] = c->d_gather[1] = nullptr;
-        peer_close(c->peer);
-    }
-    hipFree(c->d_gather[0]); hipFree(c->d_gather[1]);
+    c->ranks.release();
     hipFree(c->d_qrec); hipFree(c->d_clk); hipFree(c->d_kf); hipFree(c->d_partials); hipFree(c->d_groups); hipFree(c->d_sums_own);
     if (c->ev_begin) hipEventDestroy(c->ev_begin);
     if (c->ev_end) hipEventDestroy(c->ev_end);
@@ -1185,7 +1134,7 @@ int lv_map_box_search(lv_ctx* c, const float lo[3], const float hi[3], uint32_t*
 // context's scan; the resident filter, the update's KfDev / mailbox / capture and the timing records are left alone
 static int batch_common(lv_ctx* c, const lv_state* xs, size_t m, const double* P, bool solve, lv_state* x_out, double* P_out, int* passes,
                         lv_sums* out) {
-    if (multi_rank(c)) { set_error("multi-hypothesis updates run on one GPU: this context has a multi-GPU communicator"); return LV_ESTATE; }
+    if (c->ranks.multi_rank()) { set_error("multi-hypothesis updates run on one GPU: this context has a multi-GPU communicator"); return LV_ESTATE; }
     if (c->in_update) { set_error("multi-hypothesis update inside lv_update_begin / lv_update_end"); return LV_ESTATE; }
     if (passes) std::memset(passes, 0, m * sizeof(int));
     if (out) std::memset(out, 0, m * sizeof(lv_sums));
@@ -1239,7 +1188,7 @@ int lv_scan_set(lv_ctx* c, const void* points, size_t stride, size_t n) {
         if (z < bmin[2]) bmin[2] = z;
     }
     c->scan.n = (uint32_t)n;
-    c->comm_shard_max = 0;   // (a new scan: the caller tells its largest shard again)
+    c->ranks.shard_max = 0;   // (a new scan: the caller tells its largest shard again)
     c->dbg_valid = false;
     c->qrec_valid = false;
     if (n == 0) return LV_OK;
@@ -1257,7 +1206,7 @@ int lv_scan_deskew(lv_ctx* c, const void* points, size_t stride, size_t time_off
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
-    c->comm_shard_max = 0;
+    c->ranks.shard_max = 0;
     if (n == 0) return LV_OK;
     int rc = ensure_stage(c, n + (n + 1) / 2);  // float4 xyz + packed doubles behind them
     if (rc) return rc;
@@ -1288,7 +1237,7 @@ int lv_scan_downsample(lv_ctx* c, const void* points, size_t stride, size_t n, f
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
-    c->comm_shard_max = 0;
+    c->ranks.shard_max = 0;
     if (n == 0) return LV_OK;
     int rc = ensure_stage(c, n);
     if (rc) return rc;
@@ -1464,7 +1413,7 @@ int lv_scan_deskew_window(lv_ctx* c, double t1, double t2, const lv_motion_state
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
-    c->comm_shard_max = 0;
+    c->ranks.shard_max = 0;
     uint32_t lo = 0, hi = 0;
     int rc = c->scan.reserve_raw(1, n_states);   // (the bounds words exist: the window kernel resets them on the way)
     if (rc) return rc;
@@ -1557,7 +1506,7 @@ int lv_set_option(lv_ctx* c, const char* name, int value) {
     else if (!std::strcmp(name, "keeper_by_cost")) c->keeper_by_cost = on;
     else if (!std::strcmp(name, "tile_lpt")) c->tile_lpt = on;
     else if (!std::strcmp(name, "spin_wait")) c->spin_wait = on;
-    else if (!std::strcmp(name, "comm_fused")) c->comm_fused = on;
+    else if (!std::strcmp(name, "comm_fused")) c->ranks.fused = on;
     else if (!std::strcmp(name, "mail_filter")) c->filter.mail_filter = on;
     else if (!std::strcmp(name, "overlap_insert")) c->overlap_insert = on;
     else if (!std::strcmp(name, "batch_predict")) { if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp; c->filter.batch_predict = on; }
@@ -1635,125 +1584,51 @@ int lv_comm_init(lv_ctx* c, const char* rccl_library, const void* id128, int ran
     LV_CHECK_CTX(c);
     if (!id128 || world < 1 || rank < 0 || rank >= world) { set_error("lv_comm_init: bad arguments (rank %d, world %d)", rank, world); return LV_EINVAL; }
     if (c->in_update) { set_error("lv_comm_init inside an update"); return LV_ESTATE; }
-    if (c->comm) { set_error("communicator already initialised"); return LV_ESTATE; }
-    if (c->gather_cb) { set_error("a host gather transport is in place (lv_comm_set_host_gather)"); return LV_ESTATE; }
-    if (c->peer.local_alloc) { set_error("a peer-mapped gather is in place (lv_comm_peer_export)"); return LV_ESTATE; }
-    void* comm = nullptr;
-    int rc = comm_init(rccl_library, id128, rank, world, &comm);   // collective: every rank calls it
-    if (rc) return rc;
-    c->comm = comm;
-    c->comm_rank = rank;
-    c->comm_world = world;
-    return LV_OK;
+    return c->ranks.init_rccl(rccl_library, id128, rank, world);
 }
 
 int lv_comm_destroy(lv_ctx* c) {
     LV_CHECK_CTX(c);
     if (c->in_update) { set_error("lv_comm_destroy inside an update"); return LV_ESTATE; }
-    if (c->peer.local_alloc) {   // the peer-mapped exchange: unmap the other ranks' buffers, free this rank's (the gather buffers WERE that allocation)
-        LV_HIP(hipStreamSynchronize(c->stream));
-        if (c->peer.active) { c->d_gather[0] = c->d_gather[1] = nullptr; c->gather_cap = 0; }
-        peer_close(c->peer);
-        c->comm_world = 1;
-        c->comm_rank = 0;
-        c->comm_shard_max = 0;
-    }
-    if (!c->comm) return LV_OK;
-    LV_HIP(hipStreamSynchronize(c->stream));
-    int rc = comm_destroy(c->comm);
-    c->comm = nullptr;
-    c->comm_world = 1;
-    c->comm_rank = 0;
-    return rc;
+    return c->ranks.destroy(c->stream);
 }
 
 int lv_comm_set_host_gather(lv_ctx* c, int rank, int world, lv_gather_fn fn, void* user) {
     LV_CHECK_CTX(c);
     if (c->in_update) { set_error("lv_comm_set_host_gather inside an update"); return LV_ESTATE; }
-    if (c->comm) { set_error("a library communicator is in place"); return LV_ESTATE; }
-    if (c->peer.local_alloc) { set_error("a peer-mapped gather is in place (lv_comm_peer_export)"); return LV_ESTATE; }
-    if (fn && (world < 1 || rank < 0 || rank >= world)) { set_error("lv_comm_set_host_gather: bad arguments (rank %d, world %d)", rank, world); return LV_EINVAL; }
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->gather_cb = fn;
-    c->gather_user = fn ? user : nullptr;
-    c->comm_rank = fn ? rank : 0;
-    c->comm_world = fn ? world : 1;
-    c->comm_shard_max = 0;
-    return LV_OK;
+    return c->ranks.set_host_gather(c->stream, rank, world, fn, user);
 }
 
 int lv_comm_peer_export(lv_ctx* c, void* handle_blob) {
     LV_CHECK_CTX(c);
     if (!handle_blob) { set_error("null argument"); return LV_EINVAL; }
     if (c->in_update) { set_error("lv_comm_peer_export inside an update"); return LV_ESTATE; }
-    if (c->comm || c->gather_cb) { set_error("another multi-rank transport is in place"); return LV_ESTATE; }
-    LV_HIP(hipStreamSynchronize(c->stream));
-    // sized once for the largest case (every CU a workgroup, 96-double partials, LV_PEER_MAX ranks): the other ranks map this
-    // allocation, so it never moves
-    const size_t cap = (size_t)(c->pass_max_wg + 8) * 96u * (size_t)LV_PEER_MAX;
-    return peer_export(c->peer, cap, handle_blob);
+    return c->ranks.peer_export(c->stream, c->pass_max_wg, handle_blob);
 }
 
 int lv_comm_peer_init(lv_ctx* c, int rank, int world, const void* handles) {
     LV_CHECK_CTX(c);
     if (!handles) { set_error("null argument"); return LV_EINVAL; }
     if (c->in_update) { set_error("lv_comm_peer_init inside an update"); return LV_ESTATE; }
-    int rc = peer_init(c->peer, rank, world, handles);
-    if (rc) return rc;
-    LV_HIP(hipStreamSynchronize(c->stream));
-    hipFree(c->d_gather[0]); hipFree(c->d_gather[1]);
-    c->d_gather[0] = c->peer.buf[0];
-    c->d_gather[1] = c->peer.buf[1];
-    c->gather_cap = c->peer.cap;
-    c->comm_rank = rank;
-    c->comm_world = world;
-    c->comm_shard_max = 0;
-    return LV_OK;
+    return c->ranks.peer_init(c->stream, rank, world, handles);
 }
 
-int lv_comm_world(lv_ctx* c) { return c ? c->comm_world : 0; }
+int lv_comm_world(lv_ctx* c) { return c ? c->ranks.world : 0; }
 
 int lv_comm_set_shard_max(lv_ctx* c, size_t n_max) {
     LV_CHECK_CTX(c);
     if (c->in_update) { set_error("lv_comm_set_shard_max inside an update"); return LV_ESTATE; }
     if (n_max > 0xFFFFFFF0ull) { set_error("shard too large"); return LV_EINVAL; }
-    c->comm_shard_max = n_max;
-    if (!multi_rank(c) || n_max == 0) return LV_OK;
+    c->ranks.shard_max = n_max;
+    if (!c->ranks.multi_rank() || n_max == 0) return LV_OK;
     int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
     pass_grid_size((uint32_t)n_max, c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
-    const size_t need = (size_t)nwg * partial_width(c) * (size_t)c->comm_world;
-    if (c->gather_cb && need > c->h_gather_cap) {
-        LV_HIP(hipStreamSynchronize(c->stream));
-        if (c->h_gather) hipHostFree(c->h_gather);
-        c->h_gather = nullptr;
-        c->h_gather_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&c->h_gather, need * sizeof(double), hipHostMallocDefault));
-        std::memset(c->h_gather, 0, need * sizeof(double));
-        c->h_gather_cap = need;
-    }
-    if (need > c->gather_cap && c->peer.active) {
-        set_error("peer-mapped gather: %zu doubles exceed the exported buffers (%zu)", need, c->gather_cap);
-        return LV_EINVAL;
-    }
-    if (need > c->gather_cap) {
-        LV_HIP(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 2; ++i) {
-            hipFree(c->d_gather[i]);
-            c->d_gather[i] = nullptr;
-        }
-        c->gather_cap = 0;
-        for (int i = 0; i < 2; ++i) {
-            LV_HIP(hipMalloc(&c->d_gather[i], need * sizeof(double)));
-            LV_HIP(hipMemset(c->d_gather[i], 0, need * sizeof(double)));
-        }
-        c->gather_cap = need;
-    }
-    return LV_OK;
+    return c->ranks.reserve(c->stream, (size_t)nwg * partial_width(c));
 }
 
 int lv_set_comm_fused(lv_ctx* c, int enabled) {
     LV_CHECK_CTX(c);
-    c->comm_fused = enabled != 0;
+    c->ranks.fused = enabled != 0;
     return LV_OK;
 }
 
@@ -1826,23 +1701,19 @@ int lv_update(lv_ctx* c, lv_state* x, double* P, int* passes, lv_sums* per_pass,
         return LV_OK;
     }
     const int npass = c->prm.MAX_NUM_ITERS + 1;
-    LV_CHECK_PEER(c);
+    if (int rq = peer_poisoned(c)) return rq;
     if (!x || !P) { set_error("lv_update: null argument"); return LV_EINVAL; }   // (before the snapshot below dereferences them)
-    lv_state x_prior;
-    std::vector<double> P_prior;
-    if (c->peer.active) {   // (a failed exchange must hand the caller's buffers back untouched: lv_update_end writes into them)
-        x_prior = *x;
-        P_prior.assign(P, P + NS * NS);
-    }
+    const bool peer = c->ranks.transport == RankExchange::Transport::PeerMapped;   // (a failed exchange must hand the caller's buffers
+    const lv_state x_prior = *x;                                                      // back untouched: lv_update_end writes into them)
+    const std::vector<double> P_prior(P, peer ? P + NS * NS : P);
     int rc = lv_update_begin(c, x, P);
     if (rc) return rc;
     if (c->profiling) LV_HIP(hipEventRecord(c->ev_begin, c->stream));
     c->last_update_fused = false;
     c->coll_timed = false;
-    if (gather_only(c) && !pass_fused_applies(c)) {
+    if (c->ranks.gather_only() && !pass_fused_applies(c)) {
         c->in_update = false;
-        set_error("host-staged / peer-mapped gather: this scan does not take the one-launch-per-pass form (largest shard told? size? options?)");
-        return LV_ESTATE;
+        return c->ranks.refuse_unfused();
     }
     if (pass_fused_applies(c)) {
         rc = update_fused(c);
@@ -1865,11 +1736,11 @@ int lv_update(lv_ctx* c, lv_state* x, double* P, int* passes, lv_sums* per_pass,
     rc = lv_update_end(c, x, P, &np);
     c->want_log = false;
     if (rc) return rc;
-    if (c->peer.active) {
+    if (peer) {
         // lv_update_end has waited for the update's last launch, so every pull of this update has run: a pull that gave up on a
         // peer (or met a poisoned flag) has set the sticky status word.  The caller gets its prior back, nothing is adopted.
         LV_HIP(hipStreamSynchronize(c->stream));
-        if (peer_failed(c->peer)) {
+        if (c->ranks.failed()) {
             *x = x_prior;
             std::memcpy(P, P_prior.data(), sizeof(double) * NS * NS);
             return peer_poisoned(c);
@@ -1931,11 +1802,9 @@ int lv_correct(lv_ctx* c, int* passes) {
     c->filter.latest = ResidentFilter::Source::Filter;
     if (passes) *passes = 0;
     if (c->map.view.m == 0) return LV_OK;  // Localizator::correct returns without a map (Localizator.cpp:24)
-    LV_CHECK_PEER(c);   // (a failed exchange of an EARLIER, asynchronous lv_correct surfaces here at the latest)
-    if (gather_only(c) && !pass_fused_applies(c)) {   // (before anything is enqueued: the filter stays exactly where it was)
-        set_error("host-staged / peer-mapped gather: this scan does not take the one-launch-per-pass form (largest shard told? size? options?)");
-        return LV_ESTATE;
-    }
+    if (int rq = peer_poisoned(c)) return rq;   // (a failed exchange of an EARLIER, asynchronous lv_correct surfaces here at the latest)
+    if (c->ranks.gather_only() && !pass_fused_applies(c))   // (before anything is enqueued: the filter stays exactly where it was)
+        return c->ranks.refuse_unfused();
     c->update_seq = (c->update_seq + 1) & 0x3fffffff;   // (the finishing pass echoes it into the mailbox: lv_filter_get polls for it)
     const ResidentFilter::Prior prior = c->filter.prior();
     int rc = begin_device(c, prior.host, prior.host != nullptr, prior);
@@ -1953,7 +1822,7 @@ int lv_correct(lv_ctx* c, int* passes) {
     c->filter.correct_done();
     if (passes) {  // optional: the only synchronisation point
         LV_HIP(hipStreamSynchronize(c->stream));
-        LV_CHECK_PEER(c);
+        if (int rq = peer_poisoned(c)) return rq;
         *passes = c->h_io->passes;   // stored by solve_kernel into the pinned mailbox
     }
     return LV_OK;

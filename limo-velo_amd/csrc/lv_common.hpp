@@ -1,5 +1,5 @@
-// lv_common.hpp — host declarations shared by lv_host.hpp, lv_rebuild.hpp and lv_filter.hpp (the last two must build without
-// lv_host.hpp: their host tests compile them against a HIP stand-in).  set_error keeps the message lv_last_error returns
+// lv_common.hpp — host declarations shared by lv_host.hpp, lv_rebuild.hpp, lv_filter.hpp and lv_exchange.hpp (the last three must
+// build without lv_host.hpp: their host tests compile them against a HIP stand-in).  set_error keeps the message lv_last_error returns
 // (include/limovelo_hip.h), LV_HIP turns a failed HIP call into LV_EHIP.
 #pragma once
 #include <hip/hip_runtime.h>
