@@ -311,6 +311,59 @@ void lv_default_paint_params(lv_paint_params* p);
 int  lv_map_paint(lv_ctx* ctx, const lv_camera_view* views, size_t n_views, const lv_paint_params* p,
                   float* rgb, float* depth, uint8_t* n_seen);
 
+/* ---- Place recognition ---------------------------------------------------------------------------
+ * Where in a saved map am I, with no pose prior (the front half of the reference's "Prelocalization with a previously saved HD
+ * map")?  A place is a Scan Context descriptor (Kim & Kim, IROS 2018) with its centre, a LiDAR origin in the world.  The context
+ * holds a database of places on the device, independent of the map (map build / insert / evict / rebuild never touch it).
+ *   frame    world axes, origin at the place's centre.  A scan at state x: q = M p for every point p of the current scan (LiDAR
+ *            frame), M = R_x R_off (rotations of x.rot and x.offset_R_L_I, quaternions taken as given, composed in f64 and
+ *            rounded to f32 once; each coordinate M0*px + M1*py + M2*pz in f32, left to right, unfused); its centre is
+ *            R_x t_off + x.pos (f64).  A map place of centre c: q = p - (float)c in f32 for every living map point p.
+ *   binning  rho = sqrtf(qx*qx + qy*qy); a point counts iff rmin <= rho < rmax and v = qz + z_offset > 0.
+ *            ring = floor((rho - rmin) / ((rmax - rmin) / n_rings)), sector = floor((atan2f(qy, qx) + pi) / (2 pi / n_sectors)),
+ *            both in f32, clamped to the last ring / sector.  A bin holds the largest v of its points, 0 when empty.
+ *            Layout ring-major: desc[ring * n_sectors + sector] (the layout of describe, fetch and load).
+ *   distance for shift s: query column j against place column (j + s) mod n_sectors; a pair is valid when both columns have a
+ *            non-zero norm; d(s) = 1 - mean over valid pairs of cos(query column, place column), 1 when no pair is valid
+ *            (f32: each dot product and norm summed over the rings in order, the cosines over j in order; a result below 0
+ *            from rounding is 0).  A place's distance is min_s d(s), its shift the smallest s reaching it.
+ *   shift    the query's frame is rotated from the world by yaw = s * 2 pi / n_sectors (wrapped to (-pi, pi]): a candidate IMU
+ *            pose for place i is rotation Rz(yaw) R_x, position centre_i - Rz(yaw) R_x t_off.  The query state only supplies
+ *            roll, pitch and the extrinsics; its position is ignored and its yaw may be anything.
+ *   retrieval  the k places of smallest distance, ordered by (distance, id); deterministic.
+ * At most 2^20 places (LV_ERANGE beyond).  Outputs are synchronised on return. */
+typedef struct lv_place_params {
+    int   n_rings;      /* 1..32 */
+    int   n_sectors;    /* 2..64 */
+    float rmin, rmax;   /* 0 <= rmin < rmax <= 1000, metres */
+    float z_offset;     /* finite: added to qz before the v > 0 test and the bin maximum */
+} lv_place_params;
+/* Defaults: 20 rings, 60 sectors, 0..80 m, z_offset 2.0. */
+void lv_default_place_params(lv_place_params* p);
+/* Sets the parameters and clears the database (LV_EINVAL outside the limits, nothing changed).  Until it is called the defaults
+ * apply. */
+int  lv_place_configure(lv_ctx* ctx, const lv_place_params* p);
+/* desc: n_rings * n_sectors floats, the descriptor of the current scan (lv_scan_set) at state x; nothing is stored.
+ * LV_ESTATE without a scan. */
+int  lv_place_describe(lv_ctx* ctx, const lv_state* x, float* desc);
+/* Appends the current scan at state x as a keyframe place; *id (may be NULL) receives its id.  LV_ESTATE without a scan. */
+int  lv_place_add_scan(lv_ctx* ctx, const lv_state* x, uint32_t* id);
+/* Appends n (1..65536) places built from the device map at centres[3i .. 3i+2]; *first_id (may be NULL) receives the first id,
+ * the others follow.  An empty or unbuilt map gives all-zero descriptors.  Read-only on the map and ordered like lv_map_knn
+ * (reads the active store during a background rebuild). */
+int  lv_place_add_map(lv_ctx* ctx, const double* centres, size_t n, uint32_t* first_id);
+/* The k (1..64, clamped to the count) places nearest to the current scan at state x: ids, shifts and distances in retrieval
+ * order, *n_out = the clamped k.  LV_ESTATE on an empty database or without a scan. */
+int  lv_place_query(lv_ctx* ctx, const lv_state* x, int k, uint32_t* ids, int32_t* shifts, float* dist, size_t* n_out);
+size_t lv_place_count(lv_ctx* ctx);
+int  lv_place_clear(lv_ctx* ctx);
+/* All places in id order: desc (count * n_rings * n_sectors floats) and centres (3 * count doubles), each may be NULL;
+ * LV_EINVAL when capacity < lv_place_count(). */
+int  lv_place_fetch(lv_ctx* ctx, float* desc, double* centres, size_t capacity);
+/* Appends n places (ids count .. count + n - 1) in the layout of lv_place_fetch.  Values must be finite and >= 0, centres finite
+ * (LV_EINVAL otherwise, nothing stored). */
+int  lv_place_load(lv_ctx* ctx, const float* desc, const double* centres, size_t n);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

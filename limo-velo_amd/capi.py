@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
     "lv_iterate_batch", "lv_update_batch",
     "lv_default_visibility_params", "lv_map_remove_dynamic",
     "lv_default_paint_params", "lv_map_paint",
+    "lv_default_place_params", "lv_place_configure", "lv_place_describe", "lv_place_add_scan", "lv_place_add_map", "lv_place_query",
+    "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -90,6 +92,24 @@ class LvPaintParams(C.Structure):  # lv_paint_params
 PAINT_ARGTYPES = {
     "lv_map_paint": [C.c_void_p, C.POINTER(LvCameraView), C.c_size_t, C.POINTER(LvPaintParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                      C.POINTER(C.c_uint8)],
+}
+
+
+class PlaceParams(C.Structure):  # lv_place_params
+    _fields_ = [("n_rings", C.c_int), ("n_sectors", C.c_int), ("rmin", C.c_float), ("rmax", C.c_float), ("z_offset", C.c_float)]
+
+
+# ctypes signatures of the place recognition (include/limovelo_hip.h "Place recognition"; tests/test_place_abi.py)
+PLACE_ARGTYPES = {
+    "lv_place_configure": [C.c_void_p, C.POINTER(PlaceParams)],
+    "lv_place_describe": [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)],
+    "lv_place_add_scan": [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)],
+    "lv_place_add_map": [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_uint32)],
+    "lv_place_query": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                       C.POINTER(C.c_size_t)],
+    "lv_place_clear": [C.c_void_p],
+    "lv_place_fetch": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
+    "lv_place_load": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
 }
 
 
@@ -298,7 +318,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_visibility_params.argtypes = [C.POINTER(VisibilityParams)]
         lib.lv_default_paint_params.restype = None
         lib.lv_default_paint_params.argtypes = [C.POINTER(LvPaintParams)]
-        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES}.items():
+        lib.lv_default_place_params.restype = None
+        lib.lv_default_place_params.argtypes = [C.POINTER(PlaceParams)]
+        lib.lv_place_count.restype = C.c_size_t
+        lib.lv_place_count.argtypes = [C.c_void_p]
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -328,6 +352,14 @@ def default_visibility_params(**kw) -> VisibilityParams:
 def default_paint_params(**kw) -> LvPaintParams:
     p = LvPaintParams()
     load_library().lv_default_paint_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_place_params(**kw) -> PlaceParams:
+    p = PlaceParams()
+    load_library().lv_default_place_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -523,6 +555,84 @@ class Context:
         self._check(self.lib.lv_map_paint(self.h, arr, C.c_size_t(len(views)), C.byref(p), rgb.ctypes.data_as(fp), depth.ctypes.data_as(fp),
                                           seen.ctypes.data_as(C.POINTER(C.c_uint8))))
         return rgb, depth, seen
+
+    # --- place recognition (include/limovelo_hip.h "Place recognition")
+    def place_configure(self, params: PlaceParams | None = None):
+        """lv_place_configure: sets the parameters (default: lv_default_place_params) and clears the database."""
+        p = params if params is not None else default_place_params()
+        self._check(self.lib.lv_place_configure(self.h, C.byref(p)))
+        self._place_prm = p
+
+    def place_params(self) -> PlaceParams:
+        """The parameters of the last place_configure (the defaults before one)."""
+        return getattr(self, "_place_prm", None) or default_place_params()
+
+    def _place_bins(self):
+        p = self.place_params()
+        return int(p.n_rings), int(p.n_sectors)
+
+    def place_describe(self, state) -> np.ndarray:
+        """[n_rings, n_sectors] f32: the descriptor of the current scan at state (26 f64), not stored."""
+        r, s = self._place_bins()
+        x = np.ascontiguousarray(state, np.float64)
+        out = np.zeros((r, s), np.float32)
+        self._check(self.lib.lv_place_describe(self.h, x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def place_add_scan(self, state) -> int:
+        x = np.ascontiguousarray(state, np.float64)
+        i = C.c_uint32(0)
+        self._check(self.lib.lv_place_add_scan(self.h, x.ctypes.data_as(C.c_void_p), C.byref(i)))
+        return int(i.value)
+
+    def place_add_map(self, centres) -> int:
+        """Places built from the device map at centres [n, 3] (f64); returns the first id."""
+        c = np.ascontiguousarray(np.asarray(centres, np.float64).reshape(-1, 3))
+        i = C.c_uint32(0)
+        self._check(self.lib.lv_place_add_map(self.h, c.ctypes.data_as(C.POINTER(C.c_double)), C.c_size_t(len(c)), C.byref(i)))
+        return int(i.value)
+
+    def place_query(self, state, k: int):
+        """(ids [n] uint32, shifts [n] int32, dist [n] f32) of the k places nearest to the current scan at state, n = min(k, count)."""
+        x = np.ascontiguousarray(state, np.float64)
+        ids = np.zeros(max(int(k), 1), np.uint32)
+        sh = np.zeros(max(int(k), 1), np.int32)
+        d = np.zeros(max(int(k), 1), np.float32)
+        n = C.c_size_t(0)
+        self._check(self.lib.lv_place_query(self.h, x.ctypes.data_as(C.c_void_p), int(k), ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            sh.ctypes.data_as(C.POINTER(C.c_int32)), d.ctypes.data_as(C.POINTER(C.c_float)), C.byref(n)))
+        m = int(n.value)
+        return ids[:m].copy(), sh[:m].copy(), d[:m].copy()
+
+    def place_count(self) -> int:
+        return int(self.lib.lv_place_count(self.h))
+
+    def place_clear(self):
+        self._check(self.lib.lv_place_clear(self.h))
+
+    def place_fetch(self):
+        """(desc [n, n_rings, n_sectors] f32, centres [n, 3] f64) of every place, in id order."""
+        r, s = self._place_bins()
+        n = self.place_count()
+        desc = np.zeros((n, r, s), np.float32)
+        cen = np.zeros((n, 3), np.float64)
+        self._check(self.lib.lv_place_fetch(self.h, desc.ctypes.data_as(C.POINTER(C.c_float)), cen.ctypes.data_as(C.POINTER(C.c_double)),
+                                            C.c_size_t(n)))
+        return desc, cen
+
+    def place_centres(self) -> np.ndarray:
+        """[n, 3] f64: every place's centre, in id order (lv_place_fetch without the descriptors)."""
+        n = self.place_count()
+        cen = np.zeros((n, 3), np.float64)
+        self._check(self.lib.lv_place_fetch(self.h, None, cen.ctypes.data_as(C.POINTER(C.c_double)), C.c_size_t(n)))
+        return cen
+
+    def place_load(self, desc, centres):
+        """Appends places: desc [n, n_rings, n_sectors] (or [n, n_rings * n_sectors]) f32, centres [n, 3] f64."""
+        c = np.ascontiguousarray(np.asarray(centres, np.float64).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(desc, np.float32).reshape(len(c), -1))
+        self._check(self.lib.lv_place_load(self.h, d.ctypes.data_as(C.POINTER(C.c_float)), c.ctypes.data_as(C.POINTER(C.c_double)),
+                                           C.c_size_t(len(c))))
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

@@ -10,6 +10,7 @@
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
 #include "lv_paint.hpp"
+#include "lv_place.hpp"
 
 #include <chrono>
 
@@ -41,6 +42,7 @@ struct lv_ctx {
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
     VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
     PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
+    PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -624,6 +626,7 @@ void lv_destroy(lv_ctx* c) {
     c->query.release();
     c->vis.release();
     c->paint.release();
+    c->place.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -1032,6 +1035,139 @@ int lv_map_paint(lv_ctx* c, const lv_camera_view* views, size_t n_views, const l
     if (n_seen) LV_HIP(hipMemcpyAsync(n_seen, c->paint.d_seen, m, hipMemcpyDeviceToHost, c->stream));
     LV_HIP(hipStreamSynchronize(c->stream));
     return LV_OK;
+}
+
+// ---- Place recognition (lv_place.hip)
+void lv_default_place_params(lv_place_params* p) {
+    if (!p) return;
+    p->n_rings = 20;
+    p->n_sectors = 60;
+    p->rmin = 0.f;
+    p->rmax = 80.f;
+    p->z_offset = 2.f;
+}
+
+static int place_params_ok(const lv_place_params* p) {
+    if (!p) { set_error("null argument"); return LV_EINVAL; }
+    if (p->n_rings < 1 || p->n_rings > PLACE_MAX_RINGS) { set_error("n_rings = %d: must be in 1..%d", p->n_rings, PLACE_MAX_RINGS); return LV_EINVAL; }
+    if (p->n_sectors < 2 || p->n_sectors > PLACE_MAX_SECTORS) { set_error("n_sectors = %d: must be in 2..%d", p->n_sectors, PLACE_MAX_SECTORS); return LV_EINVAL; }
+    if (!(std::isfinite(p->rmin) && std::isfinite(p->rmax) && p->rmin >= 0.f && p->rmin < p->rmax && p->rmax <= 1000.f)) {
+        set_error("rmin %g, rmax %g: finite, 0 <= rmin < rmax <= 1000", p->rmin, p->rmax);
+        return LV_EINVAL;
+    }
+    if (!std::isfinite(p->z_offset)) { set_error("z_offset = %g: must be finite", p->z_offset); return LV_EINVAL; }
+    return LV_OK;
+}
+
+static int place_state_ok(const lv_state* x) {
+    if (!x) { set_error("null state"); return LV_EINVAL; }
+    const double* v = reinterpret_cast<const double*>(x);
+    for (size_t i = 0; i < sizeof(lv_state) / sizeof(double); ++i)
+        if (!std::isfinite(v[i])) { set_error("non-finite state"); return LV_EINVAL; }
+    return LV_OK;
+}
+
+int lv_place_configure(lv_ctx* c, const lv_place_params* p) {
+    LV_CHECK_CTX(c);
+    int rc = place_params_ok(p);
+    if (rc) return rc;
+    c->place.prm = *p;
+    c->place.clear();
+    return LV_OK;
+}
+
+// the current scan's descriptor at state x into the store's query buffer
+static int place_describe_scan(lv_ctx* c, const lv_state* x, PlaceFrame* f, double centre[3]) {
+    int rc = place_state_ok(x);
+    if (rc) return rc;
+    if (c->scan.n == 0) { set_error("no scan: call lv_scan_set first"); return LV_ESTATE; }
+    place_frame(*x, f, centre);
+    rc = c->place.reserve(c->stream, c->place.n);
+    if (rc) return rc;
+    LV_HIP(hipMemsetAsync(c->place.d_q, 0, (size_t)c->place.bins() * sizeof(uint32_t), c->stream));
+    return c->place.describe(c->scan, c->stream, *f, c->place.d_q);
+}
+
+int lv_place_describe(lv_ctx* c, const lv_state* x, float* desc) {
+    LV_CHECK_CTX(c);
+    if (!desc) { set_error("null argument"); return LV_EINVAL; }
+    PlaceFrame f;
+    double centre[3];
+    int rc = place_describe_scan(c, x, &f, centre);
+    if (rc) return rc;
+    LV_HIP(hipMemcpyAsync(desc, c->place.d_q, (size_t)c->place.bins() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
+    return LV_OK;
+}
+
+int lv_place_add_scan(lv_ctx* c, const lv_state* x, uint32_t* id) {
+    LV_CHECK_CTX(c);
+    int rc = place_state_ok(x);
+    if (rc) return rc;
+    if (c->scan.n == 0) { set_error("no scan: call lv_scan_set first"); return LV_ESTATE; }
+    if (c->place.n + 1 > PLACE_MAX_COUNT) { set_error("the place database holds 2^20 places"); return LV_ERANGE; }
+    PlaceFrame f;
+    double centre[3];
+    place_frame(*x, &f, centre);
+    return c->place.add_scan(c->scan, c->stream, f, centre, id);
+}
+
+// read-only on the map and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the
+// active store
+int lv_place_add_map(lv_ctx* c, const double* centres, size_t n, uint32_t* first_id) {
+    LV_CHECK_CTX(c);
+    if (!centres) { set_error("null argument"); return LV_EINVAL; }
+    if (n < 1 || n > PLACE_MAX_MAP_CENTRES) { set_error("n = %zu: must be in 1..%zu", n, PLACE_MAX_MAP_CENTRES); return LV_EINVAL; }
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(centres[i])) { set_error("centre %zu is not finite", i / 3); return LV_EINVAL; }
+    if (c->place.n + n > PLACE_MAX_COUNT) { set_error("the place database holds 2^20 places"); return LV_ERANGE; }
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    return c->place.add_map(c->map, c->stream, centres, n, first_id);
+}
+
+int lv_place_query(lv_ctx* c, const lv_state* x, int k, uint32_t* ids, int32_t* shifts, float* dist, size_t* n_out) {
+    LV_CHECK_CTX(c);
+    if (k < 1 || k > PLACE_MAX_K) { set_error("k = %d: must be in 1..%d", k, PLACE_MAX_K); return LV_EINVAL; }
+    int rc = place_state_ok(x);
+    if (rc) return rc;
+    if (c->place.n == 0) { set_error("the place database is empty"); return LV_ESTATE; }
+    PlaceFrame f;
+    double centre[3];
+    rc = place_describe_scan(c, x, &f, centre);
+    if (rc) return rc;
+    const int kk = (size_t)k < c->place.n ? k : (int)c->place.n;
+    rc = c->place.query(c->stream, kk, ids, shifts, dist);
+    if (rc) return rc;
+    if (n_out) *n_out = (size_t)kk;
+    return LV_OK;
+}
+
+size_t lv_place_count(lv_ctx* c) { return c ? c->place.n : 0; }
+
+int lv_place_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    c->place.clear();
+    return LV_OK;
+}
+
+int lv_place_fetch(lv_ctx* c, float* desc, double* centres, size_t capacity) {
+    LV_CHECK_CTX(c);
+    if (capacity < c->place.n) { set_error("capacity %zu < %zu places", capacity, c->place.n); return LV_EINVAL; }
+    return c->place.fetch(c->stream, desc, centres);
+}
+
+int lv_place_load(lv_ctx* c, const float* desc, const double* centres, size_t n) {
+    LV_CHECK_CTX(c);
+    if (n == 0) return LV_OK;
+    if (!desc || !centres) { set_error("null argument"); return LV_EINVAL; }
+    const size_t nb = n * (size_t)c->place.bins();
+    for (size_t i = 0; i < nb; ++i)
+        if (!(std::isfinite(desc[i]) && desc[i] >= 0.f)) { set_error("descriptor value %zu: must be finite and >= 0", i); return LV_EINVAL; }
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(centres[i])) { set_error("centre %zu is not finite", i / 3); return LV_EINVAL; }
+    if (c->place.n + n > PLACE_MAX_COUNT) { set_error("the place database holds 2^20 places"); return LV_ERANGE; }
+    return c->place.load(c->stream, desc, centres, n);
 }
 
 int lv_map_relinearise(lv_ctx* c) {

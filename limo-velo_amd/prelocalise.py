@@ -54,17 +54,23 @@ def prelocalise(ctx, prior_state, P, rounds: int = 2, keep: int = 8, **grid):
     """Batch-update the candidate grid (candidate_grid(prior_state, **grid)) from the context's current scan against its map, keep
     the best `keep`, batch-update those again `rounds` times, and return (best state [26], table): table is a list of dicts
     {state, passes, n_valid, sum_h2} of the final round, best first."""
-    xs = candidate_grid(prior_state, **grid)
+    table, _ = refine(ctx, candidate_grid(prior_state, **grid), P, rounds, keep)
+    return table[0]["state"].copy(), table
+
+
+def refine(ctx, xs, P, rounds: int = 2, keep: int = 8):
+    """Batch-update the hypotheses xs ([m, 26]), keep the best `keep`, batch-update those again `rounds` times.  Returns (table,
+    origin): table as prelocalise's, best first; origin[i] = the row of xs that table[i] grew from."""
     xs, _, passes, last = ctx.update_batch(xs, P)
-    order = rank(passes, last)[:keep]
-    xs = xs[order]
+    origin = rank(passes, last)[:keep]
+    xs = xs[origin]
     for _ in range(rounds):
         xs, _, passes, last = ctx.update_batch(xs, P)
         order = rank(passes, last)
-        xs, passes, last = xs[order], passes[order], [last[i] for i in order]
+        xs, passes, last, origin = xs[order], passes[order], [last[i] for i in order], origin[order]
     table = [dict(state=xs[i].copy(), passes=int(passes[i]), n_valid=int(last[i]["n_valid"]), sum_h2=float(last[i]["sum_h2"]))
              for i in range(len(xs))]
-    return xs[0].copy(), table
+    return table, origin
 
 
 def save_map(ctx, path) -> None:
