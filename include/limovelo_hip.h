@@ -311,6 +311,67 @@ void lv_default_paint_params(lv_paint_params* p);
 int  lv_map_paint(lv_ctx* ctx, const lv_camera_view* views, size_t n_views, const lv_paint_params* p,
                   float* rgb, float* depth, uint8_t* n_seen);
 
+/* ---- Surface normals and outlier removal ---------------------------------------------------------
+ * The local surface of the device map: a normal and a curvature per living point, and the removal of points that have no
+ * surface around them (the reference's open TODO "Erase unused (potentially dangerous) points in the map"; PCL's
+ * NormalEstimation, StatisticalOutlierRemoval and RadiusOutlierRemoval).  Both are one computation over the map's own points.
+ *
+ * Neighbourhood of a living point p for k and max_dist: N(p) = what lv_map_knn returns for the query p with this k and
+ * max_dist: the up to k living points with the smallest (calc_dist f32, id), admitted iff d2 <= max_dist * max_dist (f32).  p is
+ * a map point, so it is in N(p) with d2 = 0 (PCL's convention for a cloud searched against itself).  n = |N(p)|.
+ *
+ * lv_map_normals, per living point (k 2..32, max_dist > 0 finite, min_neighbours 3..k, orient 0 or 1, viewpoint finite):
+ *   offsets  o_j = (double)x_j - (double)p per axis (exact in f64), in neighbour order j = 0..n-1;
+ *            mean = (sum o_j) / n;  C = (sum (o_j - mean)(o_j - mean)^T) / n; all f64, summed in neighbour order, unfused.
+ *   normal   the unit eigenvector of the smallest eigenvalue l0 <= l1 <= l2 of C (f64), rounded to f32 once at the end.
+ *            curvature = (float)(l0 / (l0 + l1 + l2)) (PCL's surface variation), 0 when the trace is 0.
+ *   sign     orient 0: the component of largest magnitude is positive (ties: the lower axis); orient 1: towards viewpoint,
+ *            normal . (viewpoint - p) >= 0 in f64, the orient-0 rule when that dot product is 0.
+ *   n < min_neighbours: normal (0, 0, 0), curvature NaN.  n_used = n always.
+ *   mean_dist = (float)((sum_j sqrt((double)d2_j)) / (n - 1)), +inf when n = 1 (the point's own 0 is in the sum).
+ *
+ * lv_map_remove_outliers:
+ *   mode 0   statistical (k 1..31, max_dist > 0 finite, std_mul finite): d(p) = the f64 mean distance above over k + 1
+ *            neighbours (p and k others).  A point with fewer than k others inside max_dist has d = +inf: it is an outlier and
+ *            takes no part in the statistics.  Over the n_f points with finite d: mu = sum d / n_f,
+ *            sigma = sqrt(sum (d - mu)^2 / (n_f - 1)) (two passes, f64; the order of the two sums is the implementation's),
+ *            threshold = mu + std_mul * sigma.  Outlier iff d > threshold.  stats = {mu, sigma, threshold}.
+ *   mode 1   radius (radius > 0 finite, min_neighbours >= 1): outlier iff the number of OTHER living points with
+ *            d2 <= radius * radius (f32, as above) is below min_neighbours.  Exact; stats = {0, 0, 0}.
+ * Outliers leave the map like the points of lv_map_remove_dynamic (survivors keep their order), unless dry_run != 0.  The call
+ * is ordered behind every earlier map mutation and acts on the active store; a background rebuild in flight replays the
+ * RESOLVED rule (mode 0: the threshold the active store computed) on its copy, so the same points go. */
+typedef struct lv_surface_params {
+    int    k;                   /* 2..32 neighbours, the point itself included */
+    float  max_dist;            /* > 0, finite */
+    int    min_neighbours;      /* 3..k */
+    int    orient;              /* 0: largest component positive, 1: towards viewpoint */
+    double viewpoint[3];        /* orient 1 only; finite */
+} lv_surface_params;
+typedef struct lv_outlier_params {
+    int    mode;                /* 0 statistical, 1 radius */
+    int    k;                   /* mode 0: 1..31 other neighbours */
+    float  max_dist;            /* mode 0: > 0, finite */
+    float  std_mul;             /* mode 0: finite */
+    float  radius;              /* mode 1: > 0, finite */
+    int    min_neighbours;      /* mode 1: >= 1 */
+    int    dry_run;             /* != 0: classify only, the map is not touched */
+} lv_outlier_params;
+/* Defaults: k 10, max_dist 2 m, min_neighbours 5, orient 0, viewpoint 0. */
+void lv_default_surface_params(lv_surface_params* p);
+/* Defaults: mode 0, k 10, max_dist 2 m, std_mul 2, radius 0.5 m, min_neighbours 5, dry_run 0. */
+void lv_default_outlier_params(lv_outlier_params* p);
+/* Outputs, each may be NULL, `capacity` entries of room, lv_map_size() written in map order (the index space of lv_map_fetch /
+ * lv_map_knn): normals[3i .. 3i+2], curvature[i], mean_dist[i], n_used[i].  Parameters outside the limits, a NULL params or
+ * capacity < lv_map_size() give LV_EINVAL and write nothing; an empty or unbuilt map gives LV_OK.  Read-only, ordered like
+ * lv_map_knn. */
+int  lv_map_normals(lv_ctx* ctx, const lv_surface_params* p, float* normals, float* curvature, float* mean_dist, int32_t* n_used,
+                    size_t capacity);
+/* flags: NULL, or lv_map_size() entries in map order as the map stood BEFORE the removal, 1 = outlier.  *n_removed (may be NULL):
+ * the points that left the map (0 with dry_run).  stats: NULL or 3 doubles.  Parameters outside the limits or a NULL params give
+ * LV_EINVAL and change nothing; an empty or unbuilt map gives LV_OK, 0 removed. */
+int  lv_map_remove_outliers(lv_ctx* ctx, const lv_outlier_params* p, uint8_t* flags, size_t* n_removed, double* stats);
+
 /* ---- Place recognition ---------------------------------------------------------------------------
  * Where in a saved map am I, with no pose prior (the front half of the reference's "Prelocalization with a previously saved HD
  * map")?  A place is a Scan Context descriptor (Kim & Kim, IROS 2018) with its centre, a LiDAR origin in the world.  The context

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "lv_iterate_batch", "lv_update_batch",
     "lv_default_visibility_params", "lv_map_remove_dynamic",
     "lv_default_paint_params", "lv_map_paint",
+    "lv_default_surface_params", "lv_default_outlier_params", "lv_map_normals", "lv_map_remove_outliers",
     "lv_default_place_params", "lv_place_configure", "lv_place_describe", "lv_place_add_scan", "lv_place_add_map", "lv_place_query",
     "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
 ]
@@ -92,6 +93,23 @@ class LvPaintParams(C.Structure):  # lv_paint_params
 PAINT_ARGTYPES = {
     "lv_map_paint": [C.c_void_p, C.POINTER(LvCameraView), C.c_size_t, C.POINTER(LvPaintParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                      C.POINTER(C.c_uint8)],
+}
+
+
+class SurfaceParams(C.Structure):  # lv_surface_params
+    _fields_ = [("k", C.c_int), ("max_dist", C.c_float), ("min_neighbours", C.c_int), ("orient", C.c_int), ("viewpoint", C.c_double * 3)]
+
+
+class OutlierParams(C.Structure):  # lv_outlier_params
+    _fields_ = [("mode", C.c_int), ("k", C.c_int), ("max_dist", C.c_float), ("std_mul", C.c_float), ("radius", C.c_float),
+                ("min_neighbours", C.c_int), ("dry_run", C.c_int)]
+
+
+# ctypes signatures of the surface calls (include/limovelo_hip.h "Surface normals and outlier removal"; tests/test_map_surface_abi.py)
+SURFACE_ARGTYPES = {
+    "lv_map_normals": [C.c_void_p, C.POINTER(SurfaceParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                       C.POINTER(C.c_int32), C.c_size_t],
+    "lv_map_remove_outliers": [C.c_void_p, C.POINTER(OutlierParams), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t), C.POINTER(C.c_double)],
 }
 
 
@@ -318,11 +336,15 @@ def load_library() -> C.CDLL:
         lib.lv_default_visibility_params.argtypes = [C.POINTER(VisibilityParams)]
         lib.lv_default_paint_params.restype = None
         lib.lv_default_paint_params.argtypes = [C.POINTER(LvPaintParams)]
+        lib.lv_default_surface_params.restype = None
+        lib.lv_default_surface_params.argtypes = [C.POINTER(SurfaceParams)]
+        lib.lv_default_outlier_params.restype = None
+        lib.lv_default_outlier_params.argtypes = [C.POINTER(OutlierParams)]
         lib.lv_default_place_params.restype = None
         lib.lv_default_place_params.argtypes = [C.POINTER(PlaceParams)]
         lib.lv_place_count.restype = C.c_size_t
         lib.lv_place_count.argtypes = [C.c_void_p]
-        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES}.items():
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -352,6 +374,25 @@ def default_visibility_params(**kw) -> VisibilityParams:
 def default_paint_params(**kw) -> LvPaintParams:
     p = LvPaintParams()
     load_library().lv_default_paint_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_surface_params(**kw) -> SurfaceParams:
+    p = SurfaceParams()
+    load_library().lv_default_surface_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "viewpoint":
+            p.viewpoint[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def default_outlier_params(**kw) -> OutlierParams:
+    p = OutlierParams()
+    load_library().lv_default_outlier_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -537,6 +578,31 @@ class Context:
         self._check(self.lib.lv_map_remove_dynamic(self.h, arr, C.c_size_t(len(views)), C.byref(p),
                                                    hits.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr)))
         return int(nr.value), hits
+
+    # --- surface normals and outlier removal
+    def map_normals(self, params: SurfaceParams | None = None):
+        """dict(normals [m, 3] f32, curvature [m] f32, mean_dist [m] f32, n_used [m] int32) in map order: lv_map_normals."""
+        p = params if params is not None else default_surface_params()
+        m = self.map_size()
+        out = dict(normals=np.zeros((m, 3), np.float32), curvature=np.zeros(m, np.float32), mean_dist=np.zeros(m, np.float32),
+                   n_used=np.zeros(m, np.int32))
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.lv_map_normals(self.h, C.byref(p), out["normals"].ctypes.data_as(fp), out["curvature"].ctypes.data_as(fp),
+                                            out["mean_dist"].ctypes.data_as(fp), out["n_used"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                            C.c_size_t(m)))
+        return out
+
+    def map_remove_outliers(self, params: OutlierParams | None = None, dry_run=False):
+        """(n_removed, flags [map_size] uint8, stats [3] = mu, sigma, threshold): lv_map_remove_outliers; flags in map order as the
+        map stood before the removal."""
+        p = OutlierParams.from_buffer_copy(params) if params is not None else default_outlier_params()
+        p.dry_run = int(bool(dry_run) or bool(p.dry_run))
+        flags = np.zeros(self.map_size(), np.uint8)
+        stats = np.zeros(3)
+        nr = C.c_size_t(0)
+        self._check(self.lib.lv_map_remove_outliers(self.h, C.byref(p), flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr),
+                                                    stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return int(nr.value), flags, stats
 
     # --- map painting
     def map_paint(self, views, params: LvPaintParams | None = None):

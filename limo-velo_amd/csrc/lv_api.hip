@@ -9,6 +9,7 @@
 #include "lv_host.hpp"
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
+#include "lv_surface.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
 
@@ -42,6 +43,7 @@ struct lv_ctx {
     QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
     VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
     PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
+    SurfaceStore surface;   // lv_map_normals / lv_map_remove_outliers: their own buffers (lv_surface.hip)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
@@ -626,6 +628,7 @@ void lv_destroy(lv_ctx* c) {
     c->query.release();
     c->vis.release();
     c->paint.release();
+    c->surface.release();
     c->place.release();
     c->batch.release();
     c->scan.release();
@@ -917,6 +920,141 @@ int lv_map_remove_dynamic(lv_ctx* c, const lv_view* views, size_t n_views, const
     if (rc) return rc;
     if (hits) LV_HIP(hipMemcpy(hits, c->vis.d_hits, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;
+    return LV_OK;
+}
+
+// ---- Surface normals and outlier removal (lv_surface.hip)
+void lv_default_surface_params(lv_surface_params* p) {
+    if (!p) return;
+    p->k = 10;
+    p->max_dist = 2.f;
+    p->min_neighbours = 5;
+    p->orient = 0;
+    p->viewpoint[0] = p->viewpoint[1] = p->viewpoint[2] = 0.0;
+}
+
+void lv_default_outlier_params(lv_outlier_params* p) {
+    if (!p) return;
+    p->mode = 0;
+    p->k = 10;
+    p->max_dist = 2.f;
+    p->std_mul = 2.f;
+    p->radius = 0.5f;
+    p->min_neighbours = 5;
+    p->dry_run = 0;
+}
+
+// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
+int lv_map_normals(lv_ctx* c, const lv_surface_params* p, float* normals, float* curvature, float* mean_dist, int32_t* n_used, size_t capacity) {
+    LV_CHECK_CTX(c);
+    if (!p) { set_error("null argument"); return LV_EINVAL; }
+    if (p->k < 2 || p->k > SURF_MAX_K) { set_error("k = %d: must be in 2..%d", p->k, SURF_MAX_K); return LV_EINVAL; }
+    if (!(std::isfinite(p->max_dist) && p->max_dist > 0.f)) { set_error("max_dist = %g: finite and > 0", p->max_dist); return LV_EINVAL; }
+    if (p->min_neighbours < 3 || p->min_neighbours > p->k) { set_error("min_neighbours = %d: must be in 3..k", p->min_neighbours); return LV_EINVAL; }
+    if (p->orient != 0 && p->orient != 1) { set_error("orient = %d: 0 or 1", p->orient); return LV_EINVAL; }
+    for (int a = 0; a < 3; ++a) if (!std::isfinite(p->viewpoint[a])) { set_error("non-finite viewpoint"); return LV_EINVAL; }
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    const size_t m = c->map.m;
+    if (capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
+    if (!c->map.built || m == 0) return LV_OK;
+    SurfRule q{};
+    q.job = 0;
+    q.k = p->k;
+    q.min_neighbours = p->min_neighbours;
+    q.orient = p->orient;
+    q.max_dist = p->max_dist;
+    for (int a = 0; a < 3; ++a) q.viewpoint[a] = p->viewpoint[a];
+    const uint32_t* rank = nullptr;
+    int rc = c->query.ensure_rank(c->map, c->stream, &rank);
+    if (!rc) rc = c->surface.ensure(c->map.n_ids, m, 0);
+    if (!rc) rc = surface_search(c->map, c->stream, c->surface, q, rank);
+    if (!rc && (normals || curvature)) rc = surface_finish(c->map, c->stream, c->surface, q, rank);
+    if (rc) return rc;
+    if (normals) LV_HIP(hipMemcpyAsync(normals, c->surface.d_normals, 3 * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (curvature) LV_HIP(hipMemcpyAsync(curvature, c->surface.d_curv, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (mean_dist) LV_HIP(hipMemcpyAsync(mean_dist, c->surface.d_mean, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (n_used) LV_HIP(hipMemcpyAsync(n_used, c->surface.d_used, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
+    return LV_OK;
+}
+
+// Ordered like lv_map_remove_dynamic: settle the insert in flight, adopt / drop a finished background rebuild, resolve the rule
+// on the active store (read-only), journal the resolved rule (the worker replays it on its copy with the threshold fixed), order
+// behind a snapshot, act (on the values of the dry pass where the store is still the same)
+int lv_map_remove_outliers(lv_ctx* c, const lv_outlier_params* p, uint8_t* flags, size_t* n_removed, double* stats) {
+    LV_CHECK_CTX(c);
+    if (!p) { set_error("null argument"); return LV_EINVAL; }
+    SurfRule q{};
+    if (p->mode == 0) {
+        if (p->k < 1 || p->k > SURF_MAX_K - 1) { set_error("k = %d: must be in 1..%d", p->k, SURF_MAX_K - 1); return LV_EINVAL; }
+        if (!(std::isfinite(p->max_dist) && p->max_dist > 0.f)) { set_error("max_dist = %g: finite and > 0", p->max_dist); return LV_EINVAL; }
+        if (!std::isfinite(p->std_mul)) { set_error("std_mul must be finite"); return LV_EINVAL; }
+        q.job = 1;
+        q.k = p->k + 1;
+        q.max_dist = p->max_dist;
+        q.std_mul = p->std_mul;
+    } else if (p->mode == 1) {
+        if (!(std::isfinite(p->radius) && p->radius > 0.f)) { set_error("radius = %g: finite and > 0", p->radius); return LV_EINVAL; }
+        if (p->min_neighbours < 1) { set_error("min_neighbours = %d: must be >= 1", p->min_neighbours); return LV_EINVAL; }
+        q.job = 2;
+        q.max_dist = p->radius;
+        q.min_neighbours = p->min_neighbours;
+        q.threshold = (double)p->min_neighbours;
+        q.fixed_threshold = 1;
+    } else {
+        set_error("mode = %d: 0 (statistical) or 1 (radius)", p->mode);
+        return LV_EINVAL;
+    }
+    // (valid from here on: the outputs are written)
+    if (n_removed) *n_removed = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    if (!c->map.built || c->map.m == 0) return LV_OK;
+    const bool remove = p->dry_run == 0;
+    const uint32_t* rank = nullptr;
+    int rc = LV_OK;
+    double st3[3] = {0.0, 0.0, 0.0};
+    bool dry_pass = false;
+    if (remove) {
+        // the rule as the active store resolves it: a dry pass (mode 1 is resolved as it stands)
+        if (q.job == 1) {
+            rc = surface_outliers(c->map, c->stream, c->surface, q, nullptr, false, false, nullptr, st3);
+            if (rc) return rc;
+            dry_pass = true;
+        }
+        rc = c->surface.ensure(c->map.n_ids, c->map.m, q.job);
+        if (rc) return rc;
+        static_assert(sizeof(SurfRule) <= 2 * 256 * sizeof(double), "the rule is journaled out of SurfaceStore::d_part");
+        LV_HIP(hipMemcpyAsync(c->surface.d_part, &q, sizeof(SurfRule), hipMemcpyHostToDevice, c->stream));
+        LV_HIP(hipStreamSynchronize(c->stream));   // (q lives on this frame)
+        rc = c->rebuild.journal_replay(c->map, ctx_streams(c), c->surface.d_part, sizeof(SurfRule), [](MapStore& S, hipStream_t s, const void* blob) {
+            // (the worker runs beside the caller: its own rule copy and buffers, nothing of the context's SurfaceStore)
+            SurfRule r{};
+            LV_HIP(hipMemcpyAsync(&r, blob, sizeof(SurfRule), hipMemcpyDeviceToHost, s));
+            LV_HIP(hipStreamSynchronize(s));
+            SurfaceStore own;
+            const int rr = surface_outliers(S, s, own, r, nullptr, false, true, nullptr, nullptr);
+            own.release();   // (on every path: surface_outliers returns its errors, it does not throw)
+            return rr;
+        });
+        if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
+        if (rc) return rc;
+    }
+    const size_t m = c->map.m;   // (the store that acts: a copy adopted by the journal included)
+    if (flags) {
+        rc = c->query.ensure_rank(c->map, c->stream, &rank);
+        if (rc) return rc;
+    }
+    uint32_t nr = 0;
+    double st_act[3];
+    // (the dry pass's values stand unless the journal call adopted a rebuilt copy: the map's stamp tells)
+    rc = surface_outliers(c->map, c->stream, c->surface, q, rank, flags != nullptr, remove, &nr, st_act, dry_pass);
+    if (rc) return rc;
+    if (flags) LV_HIP(hipMemcpy(flags, c->surface.d_flags, m, hipMemcpyDeviceToHost));
+    if (n_removed) *n_removed = nr;
+    if (stats && q.job == 1) { const double* src = remove ? st3 : st_act; stats[0] = src[0]; stats[1] = src[1]; stats[2] = src[2]; }
     return LV_OK;
 }
 
