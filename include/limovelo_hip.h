@@ -372,6 +372,57 @@ int  lv_map_normals(lv_ctx* ctx, const lv_surface_params* p, float* normals, flo
  * LV_EINVAL and change nothing; an empty or unbuilt map gives LV_OK, 0 removed. */
 int  lv_map_remove_outliers(lv_ctx* ctx, const lv_outlier_params* p, uint8_t* flags, size_t* n_removed, double* stats);
 
+/* ---- Map clustering ------------------------------------------------------------------------------
+ * Which points of the device map belong together (PCL's EuclideanClusterExtraction), and the removal of whole clusters: the
+ * complement of the two point-by-point removals above.  lv_map_remove_dynamic takes only the points of an object a later sweep
+ * saw through (the reference's open TODO "Try to add a module for removing dynamic objects such as people or vehicles"): its
+ * hits, grown to the connected object, take the shell along.  lv_map_remove_outliers keeps a small blob that supports itself:
+ * components below a size are the rule that removes it.
+ *
+ * Definition.  Two living map points a, b are ADJACENT iff calc_dist(a, b) <= radius * radius: the f32, left-to-right, unfused
+ * squared distance and the comparison of lv_map_radius_search (the product radius * radius in f32).  The rule is symmetric and
+ * duplicates are adjacent.  A CLUSTER is a connected component of that graph over the INCLUDED points: every living point when
+ * mask == NULL, otherwise the points whose mask byte is non-zero (mask: lv_map_size() bytes in map order, the order of
+ * lv_map_fetch).  An excluded point links nothing and has label -1.
+ * Components with fewer than min_size points, or with more than max_size points when max_size != 0, are not reported: their
+ * points have label -1.  The reported clusters are numbered 0 .. C-1 by size descending (the order PCL returns them in), ties to
+ * the cluster whose first member in map order comes first.  Partition and labels are exactly defined: a pure function of the
+ * living points, the mask and the parameters, bitwise reproducible.
+ *
+ * lv_map_cluster is read-only and ordered like lv_map_knn: it sees every earlier insert, eviction and rebuild, and reads the
+ * active store while a background rebuild runs.
+ * lv_map_remove_clusters removes whole components (survivors keep their order, as with lv_map_remove_outliers):
+ *   seeds == NULL  debris: every included point of a component with fewer than min_size points leaves the map; max_size is ignored.
+ *   seeds != NULL  object growth (seeds: lv_map_size() bytes in map order): every component whose size is within
+ *                  [min_size, max_size] (max_size 0: no upper limit) and that holds at least one seeded INCLUDED point leaves
+ *                  the map whole.  max_size keeps a seed on a wall from removing the wall.
+ * Excluded points are never removed.  With dry_run != 0 the map is not touched.
+ * Background rebuild: mask and seeds are per-point arrays in the active store's order, so the removal is NOT journaled.  A
+ * call that removes (dry_run == 0) instead WAITS until a background rebuild in flight (lv_map_relinearise_async) has landed and
+ * been adopted, everything journaled before it included, and then acts on that store: no removal is lost, and the map order the
+ * caller's arrays refer to is kept by the adoption.  The wait is the rest of that rebuild (lv_map_rebuild_status tells whether
+ * one is running): a caller on the 100 Hz cycle should issue the removal when none is, or expect this call to take that long.
+ * lv_map_cluster and a dry run never wait. */
+typedef struct lv_cluster_params {
+    float    radius;     /* > 0, finite */
+    uint32_t min_size;   /* >= 1 */
+    uint32_t max_size;   /* 0: no limit */
+    int      dry_run;    /* lv_map_remove_clusters: != 0: classify only, the map is not touched */
+} lv_cluster_params;
+/* Defaults: radius 0.5 m, min_size 1, max_size 0, dry_run 0. */
+void lv_default_cluster_params(lv_cluster_params* p);
+/* labels: NULL (count only), or `capacity` entries of room, lv_map_size() written in map order (capacity < lv_map_size():
+ * LV_EINVAL).  sizes: NULL, or the first min(C, sizes_capacity) cluster sizes in label order.  *n_clusters (may be NULL) = C.
+ * Parameters outside the limits or a NULL params give LV_EINVAL and write nothing; an empty or unbuilt map gives LV_OK, C = 0,
+ * nothing else written. */
+int  lv_map_cluster(lv_ctx* ctx, const lv_cluster_params* p, const uint8_t* mask, int32_t* labels, size_t capacity, uint32_t* sizes,
+                    size_t sizes_capacity, size_t* n_clusters);
+/* flags: NULL, or lv_map_size() entries in map order as the map stood BEFORE the removal, 1 = the point left (with dry_run:
+ * would leave).  *n_removed (may be NULL): the points that left the map (0 with dry_run).  Parameters outside the limits or a
+ * NULL params give LV_EINVAL and change nothing; an empty or unbuilt map gives LV_OK, 0 removed. */
+int  lv_map_remove_clusters(lv_ctx* ctx, const lv_cluster_params* p, const uint8_t* mask, const uint8_t* seeds, uint8_t* flags,
+                            size_t* n_removed);
+
 /* ---- Place recognition ---------------------------------------------------------------------------
  * Where in a saved map am I, with no pose prior (the front half of the reference's "Prelocalization with a previously saved HD
  * map")?  A place is a Scan Context descriptor (Kim & Kim, IROS 2018) with its centre, a LiDAR origin in the world.  The context

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "lv_default_visibility_params", "lv_map_remove_dynamic",
     "lv_default_paint_params", "lv_map_paint",
     "lv_default_surface_params", "lv_default_outlier_params", "lv_map_normals", "lv_map_remove_outliers",
+    "lv_default_cluster_params", "lv_map_cluster", "lv_map_remove_clusters",
     "lv_default_place_params", "lv_place_configure", "lv_place_describe", "lv_place_add_scan", "lv_place_add_map", "lv_place_query",
     "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
 ]
@@ -110,6 +111,19 @@ SURFACE_ARGTYPES = {
     "lv_map_normals": [C.c_void_p, C.POINTER(SurfaceParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                        C.POINTER(C.c_int32), C.c_size_t],
     "lv_map_remove_outliers": [C.c_void_p, C.POINTER(OutlierParams), C.POINTER(C.c_uint8), C.POINTER(C.c_size_t), C.POINTER(C.c_double)],
+}
+
+
+class ClusterParams(C.Structure):  # lv_cluster_params
+    _fields_ = [("radius", C.c_float), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("dry_run", C.c_int)]
+
+
+# ctypes signatures of the clustering calls (include/limovelo_hip.h "Map clustering"; tests/test_map_cluster_abi.py)
+CLUSTER_ARGTYPES = {
+    "lv_map_cluster": [C.c_void_p, C.POINTER(ClusterParams), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_uint32),
+                       C.c_size_t, C.POINTER(C.c_size_t)],
+    "lv_map_remove_clusters": [C.c_void_p, C.POINTER(ClusterParams), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                               C.POINTER(C.c_size_t)],
 }
 
 
@@ -340,11 +354,14 @@ def load_library() -> C.CDLL:
         lib.lv_default_surface_params.argtypes = [C.POINTER(SurfaceParams)]
         lib.lv_default_outlier_params.restype = None
         lib.lv_default_outlier_params.argtypes = [C.POINTER(OutlierParams)]
+        lib.lv_default_cluster_params.restype = None
+        lib.lv_default_cluster_params.argtypes = [C.POINTER(ClusterParams)]
         lib.lv_default_place_params.restype = None
         lib.lv_default_place_params.argtypes = [C.POINTER(PlaceParams)]
         lib.lv_place_count.restype = C.c_size_t
         lib.lv_place_count.argtypes = [C.c_void_p]
-        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES}.items():
+        for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
+                               **CLUSTER_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -393,6 +410,14 @@ def default_surface_params(**kw) -> SurfaceParams:
 def default_outlier_params(**kw) -> OutlierParams:
     p = OutlierParams()
     load_library().lv_default_outlier_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_cluster_params(**kw) -> ClusterParams:
+    p = ClusterParams()
+    load_library().lv_default_cluster_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -603,6 +628,42 @@ class Context:
         self._check(self.lib.lv_map_remove_outliers(self.h, C.byref(p), flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr),
                                                     stats.ctypes.data_as(C.POINTER(C.c_double))))
         return int(nr.value), flags, stats
+
+    # --- map clustering
+    def _point_bytes(self, a, what):
+        """mask / seeds: one byte per living point in map order (None stays None)."""
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, np.uint8)
+        if len(a) != self.map_size():
+            raise ValueError(f"{what}: {len(a)} entries for a map of {self.map_size()} points")
+        return a, a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def map_cluster(self, params: ClusterParams | None = None, mask=None) -> dict:
+        """dict(labels [m] int32 in map order (-1: in no reported cluster), sizes [C] uint32 in label order, n_clusters = C):
+        lv_map_cluster; mask: None or [m] in map order, 0 = excluded."""
+        p = params if params is not None else default_cluster_params()
+        m = self.map_size()
+        keep, mp = self._point_bytes(mask, "mask")
+        labels = np.full(m, -1, np.int32)
+        sizes = np.zeros(m, np.uint32)   # (C <= m)
+        C_ = C.c_size_t(0)
+        self._check(self.lib.lv_map_cluster(self.h, C.byref(p), mp, labels.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(m),
+                                            sizes.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(m), C.byref(C_)))
+        n = int(C_.value)
+        return dict(labels=labels, sizes=sizes[:n].copy(), n_clusters=n)
+
+    def map_remove_clusters(self, params: ClusterParams | None = None, mask=None, seeds=None, dry_run=False) -> dict:
+        """dict(flags [m] uint8 in map order as the map stood before the removal, n_removed): lv_map_remove_clusters; seeds None:
+        components below min_size leave; seeds [m]: the components within [min_size, max_size] that hold a seeded point leave."""
+        p = ClusterParams.from_buffer_copy(params) if params is not None else default_cluster_params()
+        p.dry_run = int(bool(dry_run) or bool(p.dry_run))
+        keep_m, mp = self._point_bytes(mask, "mask")
+        keep_s, sp = self._point_bytes(seeds, "seeds")
+        flags = np.zeros(self.map_size(), np.uint8)
+        nr = C.c_size_t(0)
+        self._check(self.lib.lv_map_remove_clusters(self.h, C.byref(p), mp, sp, flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr)))
+        return dict(flags=flags, n_removed=int(nr.value))
 
     # --- map painting
     def map_paint(self, views, params: LvPaintParams | None = None):

@@ -10,6 +10,7 @@
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
 #include "lv_surface.hpp"
+#include "lv_cluster.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
 
@@ -44,6 +45,7 @@ struct lv_ctx {
     VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
     PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
     SurfaceStore surface;   // lv_map_normals / lv_map_remove_outliers: their own buffers (lv_surface.hip)
+    ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
@@ -629,6 +631,7 @@ void lv_destroy(lv_ctx* c) {
     c->vis.release();
     c->paint.release();
     c->surface.release();
+    c->cluster.release();
     c->place.release();
     c->batch.release();
     c->scan.release();
@@ -1055,6 +1058,99 @@ int lv_map_remove_outliers(lv_ctx* c, const lv_outlier_params* p, uint8_t* flags
     if (flags) LV_HIP(hipMemcpy(flags, c->surface.d_flags, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;
     if (stats && q.job == 1) { const double* src = remove ? st3 : st_act; stats[0] = src[0]; stats[1] = src[1]; stats[2] = src[2]; }
+    return LV_OK;
+}
+
+// ---- Map clustering (lv_cluster.hip)
+void lv_default_cluster_params(lv_cluster_params* p) {
+    if (!p) return;
+    p->radius = 0.5f;
+    p->min_size = 1;
+    p->max_size = 0;
+    p->dry_run = 0;
+}
+
+// The parameters of lv_map_cluster / lv_map_remove_clusters against their limits: LV_EINVAL (nothing touched) outside them
+static int cluster_rule(const lv_cluster_params* p, ClusterRule* q) {
+    if (!p) { set_error("null argument"); return LV_EINVAL; }
+    if (!(std::isfinite(p->radius) && p->radius > 0.f)) { set_error("radius = %g: finite and > 0", p->radius); return LV_EINVAL; }
+    if (p->min_size < 1) { set_error("min_size = 0: must be >= 1"); return LV_EINVAL; }
+    q->radius = p->radius;
+    q->min_size = p->min_size;
+    q->max_size = p->max_size;
+    q->seeded = 0;
+    return LV_OK;
+}
+
+// m bytes of the caller's (pageable) memory at living ranks -> the device
+static int cluster_upload(lv_ctx* c, uint8_t* dst, const uint8_t* src, size_t m) {
+    LV_HIP(hipMemcpyAsync(dst, src, m, hipMemcpyHostToDevice, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
+    return LV_OK;
+}
+
+// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
+int lv_map_cluster(lv_ctx* c, const lv_cluster_params* p, const uint8_t* mask, int32_t* labels, size_t capacity, uint32_t* sizes,
+                   size_t sizes_capacity, size_t* n_clusters) {
+    LV_CHECK_CTX(c);
+    ClusterRule q{};
+    int rc = cluster_rule(p, &q);
+    if (rc) return rc;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    const size_t m = c->map.m;
+    if (labels && capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
+    if (n_clusters) *n_clusters = 0;
+    if (!c->map.built || m == 0) return LV_OK;
+    const uint32_t* rank = nullptr;
+    rc = c->query.ensure_rank(c->map, c->stream, &rank);
+    if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
+    if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
+    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask : nullptr);
+    size_t C = 0;
+    if (!rc) rc = cluster_labels(c->map, c->stream, c->cluster, q, rank, labels != nullptr, &C);
+    if (rc) return rc;
+    if (labels) LV_HIP(hipMemcpyAsync(labels, c->cluster.d_labels, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    const size_t ns = C < sizes_capacity ? C : sizes_capacity;
+    if (sizes && ns) LV_HIP(hipMemcpyAsync(sizes, c->cluster.d_sizes, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
+    if (n_clusters) *n_clusters = C;
+    return LV_OK;
+}
+
+// Ordered like lv_map_remove_outliers up to the journal: mask and seeds are per-point arrays in the ACTIVE store's map order,
+// which a replay on the worker's copy could only honour by carrying both arrays and the copy's own ranks along.  A removal
+// therefore first waits until a background rebuild in flight has landed (MapRebuild::status, wait: the copy is adopted with
+// everything journaled so far replayed) and then acts on the one store there is: nothing is lost, and the wait is stated in the
+// header.  A dry run touches nothing and reads the active store like lv_map_cluster.
+int lv_map_remove_clusters(lv_ctx* c, const lv_cluster_params* p, const uint8_t* mask, const uint8_t* seeds, uint8_t* flags, size_t* n_removed) {
+    LV_CHECK_CTX(c);
+    ClusterRule q{};
+    int rc = cluster_rule(p, &q);
+    if (rc) return rc;
+    q.seeded = seeds ? 1 : 0;
+    // (valid from here on: the outputs are written)
+    if (n_removed) *n_removed = 0;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    if (!c->map.built || c->map.m == 0) return LV_OK;
+    const bool remove = p->dry_run == 0;
+    if (remove) {
+        rc = c->rebuild.status(c->map, ctx_streams(c), 1, nullptr);
+        if (rc) return rc;
+    }
+    const size_t m = c->map.m;   // (the store that acts: an adopted copy included; adoption keeps the map order)
+    const uint32_t* rank = nullptr;
+    rc = c->query.ensure_rank(c->map, c->stream, &rank);
+    if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
+    if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
+    if (!rc && seeds) rc = cluster_upload(c, c->cluster.d_seeds, seeds, m);
+    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask : nullptr);
+    uint32_t nr = 0;
+    if (!rc) rc = cluster_remove(c->map, c->stream, c->cluster, q, rank, c->cluster.d_seeds, flags ? c->cluster.d_flags : nullptr, remove, &nr);
+    if (rc) return rc;
+    if (flags) LV_HIP(hipMemcpy(flags, c->cluster.d_flags, m, hipMemcpyDeviceToHost));
+    if (n_removed) *n_removed = nr;
     return LV_OK;
 }
 
