@@ -476,6 +476,69 @@ int  lv_place_fetch(lv_ctx* ctx, float* desc, double* centres, size_t capacity);
  * (LV_EINVAL otherwise, nothing stored). */
 int  lv_place_load(lv_ctx* ctx, const float* desc, const double* centres, size_t n);
 
+/* ---- Occupancy grid ------------------------------------------------------------------------------
+ * Where space was observed empty, occupied, or never observed: what a planner needs next to the map (OctoMap's log-odds volume
+ * and octomap_server's projected 2-D map; the reference has no counterpart).  The sweeps lv_map_remove_dynamic takes (lv_view:
+ * pose sensor -> world, raw returns in the sensor frame) are ray-cast into a dense grid of f32 log-odds held by the context.  The
+ * grid is independent of the map: it needs no built map and map build / insert / evict / rebuild never touch it.
+ * The rule is integer arithmetic after one quantisation step, so it is exactly defined: a pure function of the inputs, bitwise
+ * reproducible and independent of scheduling.
+ *   grid     origin[3] is the world position of the low corner of voxel (0, 0, 0); resolution (finite, > 0) its edge; nx, ny, nz each
+ *            1..1024 with nx * ny * nz <= 2^28.  Linear index (k * ny + j) * nx + i, x fastest.  One f32 log-odds value L per
+ *            voxel; NaN = never observed.
+ *   quantisation  Q = 256 sub-units per voxel.  Per axis q = (int32) floorf(((p - origin) / resolution) * 256.0f): f32 operations in
+ *            exactly that order (unfused; IEEE division).  The voxel of q is q >> 8 (arithmetic shift).
+ *            A view whose sensor origin t is non-finite or has any |(t - origin) / resolution| >= 8192 gives no evidence (nor does
+ *            a view with n = 0): it adds nothing to the grid and nothing to the stats.  max_range / resolution <= 4096 (LV_EINVAL
+ *            beyond): every walk then stays inside +-(8192 + 4096 + 1) voxels and every product below 2^41.
+ *   returns  r2 = x*x + y*y + z*z, summed left to right.  A return is ignored if it is non-finite or r2 < min_range * min_range.  If
+ *            r2 > max_range * max_range the return is CUT: c = max_range / sqrtf(r2), the point becomes (x*c, y*c, z*c) and it is
+ *            not a hit.  World point per component ((R0*x + R1*y) + R2*z) + t, unfused, as in lv_map_remove_dynamic.  R must be
+ *            finite (LV_EINVAL) and is meant to be a rotation; a return whose world point quantises to |q| >= 2^24 on any axis
+ *            (65536 voxels from the origin: only an R that is no rotation does that) is ignored.
+ *   walk     from qs (the quantised t) to qe (the quantised world point), in integers only.  Per axis a: d_a = qe_a - qs_a,
+ *            ad_a = |d_a|, s_a = sign(d_a); cells vs = qs >> 8 and ve = qe >> 8; steps left r_a = |ve_a - vs_a|; the numerator to the
+ *            first boundary n_a = ((vs_a + 1) << 8) - qs_a if s_a > 0, qs_a - (vs_a << 8) if s_a < 0.  While any r_a > 0: among the
+ *            axes with r_a > 0 take the one with the smallest n_a / ad_a, compared by int64 cross-multiplication
+ *            (n_a * ad_b <= n_b * ad_a), ties to x, then y, then z; step that axis by s_a, add 256 to n_a, decrement r_a.  The walk
+ *            has exactly r_x + r_y + r_z steps and ends in ve.  Every cell it stands in before ve is CROSSED; ve is HIT if the
+ *            return was not cut, otherwise crossed.  Cells outside the grid are skipped.
+ *   update   OctoMap's insertPointCloud semantics, one update per voxel per view: Hit_v and Free_v are the in-grid sets over all
+ *            rays of view v, Free_v -= Hit_v; views are applied in call order.  A voxel of Hit_v:
+ *            L = fminf(fmaxf((isnan(L) ? 0 : L) + l_hit, l_min), l_max); a voxel of Free_v the same with l_miss.
+ *   projection  octomap_server's rule: over the layers k_lo..k_hi (inclusive, clipped to the grid) a column (i, j) is 100 if any
+ *            L >= l_occ, else 0 if any L <= l_free, else -1 (also when the clipped band is empty).  int8 at j * nx + i: the `data`
+ *            layout of nav_msgs/OccupancyGrid.
+ * Every call below except lv_default_occupancy_params and lv_occ_configure gives LV_ESTATE before lv_occ_configure.  Arguments
+ * outside the limits give LV_EINVAL and change nothing.  The calls run on the context's stream and return when their host
+ * outputs are written.  The grid and its buffers are owned by the context and freed by lv_destroy; nothing is allocated before
+ * lv_occ_configure. */
+typedef struct lv_occupancy_params {
+    float origin[3]; float resolution; int nx, ny, nz;
+    float min_range, max_range;              /* 0 < min_range < max_range */
+    float l_hit, l_miss, l_min, l_max;       /* l_miss < 0 < l_hit, l_min < 0 < l_max, finite */
+    float l_occ, l_free;                     /* l_free < l_occ */
+} lv_occupancy_params;
+/* Defaults: 0.2 m voxels, 512 x 512 x 64 centred on 0 in x, y with z from -3.2 (origin -51.2, -51.2, -3.2); ranges 1..80 m;
+ * l_hit 0.85, l_miss -0.4, l_min -2.0, l_max 3.5 (OctoMap's probabilities 0.7 / 0.4 / 0.12 / 0.97); l_occ 0.4, l_free -0.4. */
+void lv_default_occupancy_params(lv_occupancy_params* p);
+/* Allocates the grid, every voxel unknown; reconfiguring discards the grid. */
+int  lv_occ_configure(lv_ctx* ctx, const lv_occupancy_params* p);
+/* n_views 1..32.  stats (may be NULL): rays used (returns not ignored, the cut ones included), rays cut, voxel updates free
+ * (the sizes of Free_v), voxel updates hit (of Hit_v), each summed over the views. */
+int  lv_occ_integrate(lv_ctx* ctx, const lv_view* views, size_t n_views, uint64_t stats[4]);
+/* L of the voxel each world point falls in (quantised as above); NaN outside the grid and for non-finite points. */
+int  lv_occ_query(lv_ctx* ctx, const void* pts, size_t stride, size_t n, float* logodds);
+/* grid2d: nx * ny values; capacity < nx * ny or k_lo > k_hi: LV_EINVAL. */
+int  lv_occ_project(lv_ctx* ctx, int k_lo, int k_hi, int8_t* grid2d, size_t capacity);
+/* logodds: nx * ny * nz values (capacity below that: LV_EINVAL). */
+int  lv_occ_fetch(lv_ctx* ctx, float* logodds, size_t capacity);
+/* Replaces the grid.  n must equal nx * ny * nz; every value NaN or inside [l_min, l_max] (LV_EINVAL otherwise, grid unchanged). */
+int  lv_occ_load(lv_ctx* ctx, const float* logodds, size_t n);
+/* Every voxel back to unknown. */
+int  lv_occ_clear(lv_ctx* ctx);
+int  lv_occ_get_params(lv_ctx* ctx, lv_occupancy_params* out);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

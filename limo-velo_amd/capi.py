@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "lv_default_cluster_params", "lv_map_cluster", "lv_map_remove_clusters",
     "lv_default_place_params", "lv_place_configure", "lv_place_describe", "lv_place_add_scan", "lv_place_add_map", "lv_place_query",
     "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
+    "lv_default_occupancy_params", "lv_occ_configure", "lv_occ_integrate", "lv_occ_query", "lv_occ_project", "lv_occ_fetch", "lv_occ_load",
+    "lv_occ_clear", "lv_occ_get_params",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -142,6 +144,25 @@ PLACE_ARGTYPES = {
     "lv_place_clear": [C.c_void_p],
     "lv_place_fetch": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
     "lv_place_load": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
+}
+
+
+class OccupancyParams(C.Structure):  # lv_occupancy_params
+    _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("l_hit", C.c_float), ("l_miss", C.c_float), ("l_min", C.c_float),
+                ("l_max", C.c_float), ("l_occ", C.c_float), ("l_free", C.c_float)]
+
+
+# ctypes signatures of the occupancy grid (include/limovelo_hip.h "Occupancy grid"; tests/test_occupancy_abi.py)
+OCCUPANCY_ARGTYPES = {
+    "lv_occ_configure": [C.c_void_p, C.POINTER(OccupancyParams)],
+    "lv_occ_integrate": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(C.c_uint64)],
+    "lv_occ_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_float)],
+    "lv_occ_project": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int8), C.c_size_t],
+    "lv_occ_fetch": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
+    "lv_occ_load": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
+    "lv_occ_clear": [C.c_void_p],
+    "lv_occ_get_params": [C.c_void_p, C.POINTER(OccupancyParams)],
 }
 
 
@@ -360,8 +381,10 @@ def load_library() -> C.CDLL:
         lib.lv_default_place_params.argtypes = [C.POINTER(PlaceParams)]
         lib.lv_place_count.restype = C.c_size_t
         lib.lv_place_count.argtypes = [C.c_void_p]
+        lib.lv_default_occupancy_params.restype = None
+        lib.lv_default_occupancy_params.argtypes = [C.POINTER(OccupancyParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES}.items():
+                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -429,6 +452,32 @@ def default_place_params(**kw) -> PlaceParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_occupancy_params(**kw) -> OccupancyParams:
+    p = OccupancyParams()
+    load_library().lv_default_occupancy_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def view_array(views):
+    """(lv_view array, the point arrays it refers to) from views = [(R [3, 3], t [3], points [n, 3] sensor frame)]."""
+    keep = []
+    arr = (View * max(len(views), 1))()
+    for i, (R, t, pts) in enumerate(views):
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3)) if len(pts) else (None, 12, 0)
+        keep.append(a)
+        arr[i].R[:] = [float(v) for v in np.asarray(R, np.float32).ravel()]
+        arr[i].t[:] = [float(v) for v in np.asarray(t, np.float32).ravel()]
+        arr[i].points = a.ctypes.data if a is not None else None
+        arr[i].stride = stride
+        arr[i].n = n
+    return arr, keep
 
 
 def _points(a):
@@ -682,6 +731,54 @@ class Context:
         self._check(self.lib.lv_map_paint(self.h, arr, C.c_size_t(len(views)), C.byref(p), rgb.ctypes.data_as(fp), depth.ctypes.data_as(fp),
                                           seen.ctypes.data_as(C.POINTER(C.c_uint8))))
         return rgb, depth, seen
+
+    # --- occupancy grid (include/limovelo_hip.h "Occupancy grid")
+    def occ_configure(self, params: OccupancyParams | None = None):
+        """lv_occ_configure: allocates the grid (default: lv_default_occupancy_params), every voxel unknown."""
+        p = params if params is not None else default_occupancy_params()
+        self._check(self.lib.lv_occ_configure(self.h, C.byref(p)))
+
+    def occ_params(self) -> OccupancyParams:
+        p = OccupancyParams()
+        self._check(self.lib.lv_occ_get_params(self.h, C.byref(p)))
+        return p
+
+    def occ_integrate(self, views) -> np.ndarray:
+        """lv_occ_integrate over views = [(R [3, 3], t [3], points [n, 3] sensor frame)] (1..32 of them, the tuples of
+        map_remove_dynamic); returns stats [4] uint64: rays used, rays cut, voxel updates free, voxel updates hit."""
+        arr, keep = view_array(views)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_integrate(self.h, arr, C.c_size_t(len(views)), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_query(self, pts) -> np.ndarray:
+        """[n] f32: the log-odds of the voxel each world point falls in, NaN outside the grid / unknown."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        out = np.full(n, np.nan, np.float32)
+        self._check(self.lib.lv_occ_query(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                          out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def occ_project(self, k_lo: int, k_hi: int) -> np.ndarray:
+        """[ny, nx] int8 (100 occupied, 0 free, -1 unknown) over the layers k_lo..k_hi: lv_occ_project."""
+        p = self.occ_params()
+        out = np.full((p.ny, p.nx), -1, np.int8)
+        self._check(self.lib.lv_occ_project(self.h, int(k_lo), int(k_hi), out.ctypes.data_as(C.POINTER(C.c_int8)), C.c_size_t(out.size)))
+        return out
+
+    def occ_fetch(self) -> np.ndarray:
+        """[nz, ny, nx] f32 log-odds, NaN = never observed."""
+        p = self.occ_params()
+        out = np.zeros((p.nz, p.ny, p.nx), np.float32)
+        self._check(self.lib.lv_occ_fetch(self.h, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size)))
+        return out
+
+    def occ_load(self, logodds):
+        a = np.ascontiguousarray(logodds, np.float32)
+        self._check(self.lib.lv_occ_load(self.h, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(a.size)))
+
+    def occ_clear(self):
+        self._check(self.lib.lv_occ_clear(self.h))
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

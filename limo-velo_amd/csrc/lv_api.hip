@@ -13,6 +13,7 @@
 #include "lv_cluster.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
+#include "lv_occupancy.hpp"
 
 #include <chrono>
 
@@ -47,6 +48,7 @@ struct lv_ctx {
     SurfaceStore surface;   // lv_map_normals / lv_map_remove_outliers: their own buffers (lv_surface.hip)
     ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
+    OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -633,6 +635,7 @@ void lv_destroy(lv_ctx* c) {
     c->surface.release();
     c->cluster.release();
     c->place.release();
+    c->occ.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -2379,6 +2382,107 @@ int lv_get_phase_clocks(lv_ctx* c, long long* out, int capacity_blocks, int* n_b
     LV_HIP(hipStreamSynchronize(c->stream));
     LV_HIP(hipMemcpy(out, c->d_clk, (size_t)nb * 8 * sizeof(long long), hipMemcpyDeviceToHost));
     if (n_blocks) *n_blocks = nb;
+    return LV_OK;
+}
+
+// ---- Occupancy grid (lv_occupancy.hip)
+void lv_default_occupancy_params(lv_occupancy_params* p) {
+    if (!p) return;
+    p->origin[0] = -51.2f;
+    p->origin[1] = -51.2f;
+    p->origin[2] = -3.2f;
+    p->resolution = 0.2f;
+    p->nx = 512;
+    p->ny = 512;
+    p->nz = 64;
+    p->min_range = 1.f;
+    p->max_range = 80.f;
+    p->l_hit = 0.85f;
+    p->l_miss = -0.4f;
+    p->l_min = -2.f;
+    p->l_max = 3.5f;
+    p->l_occ = 0.4f;
+    p->l_free = -0.4f;
+}
+
+#define LV_OCC_CONFIGURED(c)                                                         \
+    do {                                                                             \
+        if (!(c)->occ.configured) {                                                  \
+            set_error("no occupancy grid: call lv_occ_configure first");             \
+            return LV_ESTATE;                                                        \
+        }                                                                            \
+    } while (0)
+
+// (the parameters are judged before the context: what is wrong with them is reported whatever else is)
+int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
+    if (const char* why = occ_check_params(p)) { set_error("lv_occ_configure: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->occ.configure(c->stream, *p);
+}
+
+int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!views) { set_error("null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
+    size_t total = 0;
+    for (size_t v = 0; v < n_views; ++v) {
+        const lv_view& w = views[v];
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(w.R[i])) { set_error("view %zu: non-finite R", v); return LV_EINVAL; }
+        if (w.n && (!w.points || w.stride < 12)) { set_error("view %zu: bad point array (stride %zu)", v, w.stride); return LV_EINVAL; }
+        total += w.n;
+        if (w.n > 0xFFFFFFF0ull / 4 || total > 0xFFFFFFF0ull / 4) { set_error("too many returns"); return LV_EINVAL; }
+    }
+    return c->occ.integrate(c->stream, views, n_views, stats);
+}
+
+int lv_occ_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* logodds) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (n && (!pts || !logodds || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
+    if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
+    return c->occ.query(c->stream, pts, stride, n, logodds);
+}
+
+int lv_occ_project(lv_ctx* c, int k_lo, int k_hi, int8_t* grid2d, size_t capacity) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
+    if (!grid2d || capacity < plane) { set_error("grid2d: room for nx * ny = %zu values needed", plane); return LV_EINVAL; }
+    if (k_lo > k_hi) { set_error("layers %d..%d: k_lo <= k_hi", k_lo, k_hi); return LV_EINVAL; }
+    return c->occ.project(c->stream, k_lo, k_hi, grid2d);
+}
+
+int lv_occ_fetch(lv_ctx* c, float* logodds, size_t capacity) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!logodds || capacity < c->occ.n_vox) { set_error("logodds: room for nx * ny * nz = %zu values needed", c->occ.n_vox); return LV_EINVAL; }
+    return c->occ.fetch(c->stream, logodds);
+}
+
+int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!logodds || n != c->occ.n_vox) { set_error("lv_occ_load: %zu values for a grid of %zu voxels", n, c->occ.n_vox); return LV_EINVAL; }
+    const float lo = c->occ.prm.l_min, hi = c->occ.prm.l_max;
+    for (size_t i = 0; i < n; ++i) {
+        const float v = logodds[i];
+        if (!(v != v) && !(v >= lo && v <= hi)) { set_error("lv_occ_load: value %g at %zu outside [%g, %g]", v, i, lo, hi); return LV_EINVAL; }
+    }
+    return c->occ.load(c->stream, logodds);
+}
+
+int lv_occ_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    return c->occ.clear(c->stream);
+}
+
+int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    *out = c->occ.prm;
     return LV_OK;
 }
 

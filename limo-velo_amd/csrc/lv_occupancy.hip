@@ -1,0 +1,303 @@
+// lv_occupancy.hip — the ray-cast occupancy grid (include/limovelo_hip.h "Occupancy grid"; the rule's code is lv_occupancy.hpp).
+//
+// Per view two kernels, on the context's stream:
+//   occ_march_kernel  one lane per return: range rules, world transform, quantisation, then the integer walk.  The cells go into
+//                     two bitmaps, crossed and hit (one bit per voxel, 32 consecutive x per word).  A lane keeps the word it
+//                     stands in and the bits it has gathered there in registers and issues ONE no-return atomicOr when the walk
+//                     leaves the word, after a plain load that skips it when the bits are already set (the words round the
+//                     sensor are shared by every ray: most of those atomics are skipped).  OR is idempotent and commutative, so
+//                     the bitmaps do not depend on the schedule; the load can only see too few bits, never too many.
+//   occ_fold_kernel   one lane per four words of both bitmaps (uint4 loads): hit wins over crossed, the set voxels take their one
+//                     update, non-zero words are cleared for the next view, the update counts go to the stats.
+// lv_occ_project / lv_occ_query are one-lane-per-item streaming kernels; fetch / load / clear are copies and a fill.
+#include "lv_occupancy.hpp"
+
+#include <cstring>
+
+#include "lv_common.hpp"
+
+namespace lv {
+
+namespace {
+
+constexpr uint32_t OCC_NAN_BITS = 0x7FC00000u;
+constexpr uint32_t OCC_NO_WORD = 0xFFFFFFFFu;
+
+struct OccPose {
+    float R[9];
+    float t[3];
+};
+
+// OR `bits` into *word unless they are all there already
+__device__ __forceinline__ void occ_or(uint32_t* word, uint32_t bits) {
+    if ((*word & bits) != bits) atomicOr(word, bits);
+}
+
+// wave-wide sum of a small per-lane count, one 64-bit atomic per wavefront that has anything to add
+__device__ __forceinline__ void occ_count(unsigned long long* dst, uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(dst, (unsigned long long)v);
+}
+
+// pts: n returns (packed x, y, z) of one view; qs: its quantised sensor origin.  crossed / hit: the bitmaps.
+__global__ __launch_bounds__(256) void occ_march_kernel(const float* __restrict__ pts, uint32_t n, OccGrid g, OccPose pose, int32_t qsx,
+                                                        int32_t qsy, int32_t qsz, uint32_t* crossed, uint32_t* hit,
+                                                        unsigned long long* stats) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    int kind = OCC_RAY_IGNORED;
+    int32_t qe[3] = {0, 0, 0};
+    if (i < n) kind = occ_return(g, pose.R, pose.t, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2], qe);
+    if (kind != OCC_RAY_IGNORED) {
+        const int32_t qs[3] = {qsx, qsy, qsz};
+        OccWalk w;
+        occ_walk_init(w, qs, qe);
+        uint32_t cur = OCC_NO_WORD, bits = 0;
+        bool left = false;
+        while (!occ_walk_done(w)) {
+            if (occ_in_grid(g, w.vx, w.vy, w.vz)) {
+                const uint32_t word = ((uint32_t)w.vz * (uint32_t)g.ny + (uint32_t)w.vy) * (uint32_t)g.wx + ((uint32_t)w.vx >> 5);
+                if (word != cur) {
+                    if (cur != OCC_NO_WORD) occ_or(crossed + cur, bits);
+                    cur = word;
+                    bits = 0;
+                }
+                bits |= 1u << (w.vx & 31);
+            } else if (occ_walk_left(g, w)) {
+                left = true;
+                break;
+            }
+            occ_walk_step(w);
+        }
+        // ve: hit, or crossed when the return was cut
+        if (!left && occ_in_grid(g, w.vx, w.vy, w.vz)) {
+            const uint32_t word = ((uint32_t)w.vz * (uint32_t)g.ny + (uint32_t)w.vy) * (uint32_t)g.wx + ((uint32_t)w.vx >> 5);
+            const uint32_t bit = 1u << (w.vx & 31);
+            if (kind == OCC_RAY_HIT) {
+                occ_or(hit + word, bit);
+            } else {
+                if (word != cur) {
+                    if (cur != OCC_NO_WORD) occ_or(crossed + cur, bits);
+                    cur = word;
+                    bits = 0;
+                }
+                bits |= bit;
+            }
+        }
+        if (cur != OCC_NO_WORD) occ_or(crossed + cur, bits);
+    }
+    occ_count(stats + 0, kind != OCC_RAY_IGNORED ? 1u : 0u);
+    occ_count(stats + 1, kind == OCC_RAY_CUT ? 1u : 0u);
+}
+
+// the voxels of one word take their update; returns nothing, counts through nf / nh
+__device__ __forceinline__ void occ_fold_word(const OccGrid& g, float* __restrict__ L, uint32_t word, uint32_t c, uint32_t h, uint32_t& nf,
+                                              uint32_t& nh) {
+    c &= ~h;
+    nf += (uint32_t)__popc(c);
+    nh += (uint32_t)__popc(h);
+    const uint32_t row = word / (uint32_t)g.wx;
+    float* base = L + (size_t)row * (size_t)g.nx + (size_t)(word - row * (uint32_t)g.wx) * 32u;
+    uint32_t m = c | h;
+    while (m) {
+        const int b = __ffs((int)m) - 1;
+        m &= m - 1;
+        base[b] = occ_update(base[b], ((h >> b) & 1u) ? g.l_hit : g.l_miss, g.l_min, g.l_max);
+    }
+}
+
+// n4: the uint4 groups of one bitmap (the word arrays are padded to a multiple of four; the padding stays zero)
+__global__ __launch_bounds__(256) void occ_fold_kernel(float* __restrict__ L, uint4* __restrict__ crossed, uint4* __restrict__ hit, uint32_t n4,
+                                                       OccGrid g, unsigned long long* stats) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t nf = 0, nh = 0;
+    if (i < n4) {
+        const uint4 c = crossed[i], h = hit[i];
+        if (c.x | c.y | c.z | c.w | h.x | h.y | h.z | h.w) {
+            if (c.x | h.x) occ_fold_word(g, L, 4u * i, c.x, h.x, nf, nh);
+            if (c.y | h.y) occ_fold_word(g, L, 4u * i + 1u, c.y, h.y, nf, nh);
+            if (c.z | h.z) occ_fold_word(g, L, 4u * i + 2u, c.z, h.z, nf, nh);
+            if (c.w | h.w) occ_fold_word(g, L, 4u * i + 3u, c.w, h.w, nf, nh);
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            if (c.x | c.y | c.z | c.w) crossed[i] = zero;
+            if (h.x | h.y | h.z | h.w) hit[i] = zero;
+        }
+    }
+    occ_count(stats + 2, nf);
+    occ_count(stats + 3, nh);
+}
+
+// one lane per column (i, j); k0..k1 already clipped (k0 > k1: an empty band)
+__global__ __launch_bounds__(256) void occ_project_kernel(const float* __restrict__ L, OccGrid g, int k0, int k1, float l_occ, float l_free,
+                                                          int8_t* __restrict__ out) {
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t plane = (uint32_t)g.nx * (uint32_t)g.ny;
+    if (c >= plane) return;
+    bool occ = false, fre = false;
+    for (int k = k0; k <= k1; ++k) {
+        const float v = L[(size_t)k * plane + c];
+        occ |= v >= l_occ;
+        fre |= v <= l_free;
+    }
+    out[c] = occ ? (int8_t)100 : (fre ? (int8_t)0 : (int8_t)-1);
+}
+
+__global__ __launch_bounds__(256) void occ_query_kernel(const float* __restrict__ L, OccGrid g, const float* __restrict__ pts, uint32_t n,
+                                                        float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int32_t q[3];
+    bool ok = true;
+    for (int a = 0; a < 3; ++a) ok = occ_quant(pts[3 * (size_t)i + a], g.origin[a], g.resolution, q[a]) && ok;
+    float v = __uint_as_float(OCC_NAN_BITS);
+    if (ok && occ_in_grid(g, q[0] >> 8, q[1] >> 8, q[2] >> 8))
+        v = L[((size_t)(q[2] >> 8) * (size_t)g.ny + (size_t)(q[1] >> 8)) * (size_t)g.nx + (size_t)(q[0] >> 8)];
+    out[i] = v;
+}
+
+inline uint32_t grid_of(size_t n) { return (uint32_t)((n + 255) / 256); }
+
+}  // namespace
+
+void OccStore::release() {
+    if (h_pts) hipHostFree(h_pts);
+    if (h_stats) hipHostFree(h_stats);
+    hipFree(d_L);
+    hipFree(d_bits);
+    hipFree(d_stats);
+    hipFree(d_pts);
+    hipFree(d_out);
+    hipFree(d_proj);
+    *this = OccStore();
+}
+
+int OccStore::configure(hipStream_t stream, const lv_occupancy_params& p) {
+    LV_HIP(hipStreamSynchronize(stream));
+    release();
+    const OccGrid g = occ_grid_of(p);
+    const size_t nv = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
+    const size_t nw = (((size_t)g.wx * (size_t)p.ny * (size_t)p.nz) + 3) & ~(size_t)3;
+    LV_HIP(hipMalloc(&d_L, nv * sizeof(float)));
+    LV_HIP(hipMalloc(&d_bits, 2 * nw * sizeof(uint32_t)));
+    LV_HIP(hipMalloc(&d_stats, 4 * sizeof(unsigned long long)));
+    LV_HIP(hipMalloc(&d_proj, (size_t)p.nx * (size_t)p.ny));
+    LV_HIP(hipHostMalloc((void**)&h_stats, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    LV_HIP(hipMemsetAsync(d_bits, 0, 2 * nw * sizeof(uint32_t), stream));
+    prm = p;
+    grid = g;
+    n_vox = nv;
+    n_words = nw;
+    const int rc = clear(stream);
+    if (rc) return rc;
+    configured = true;
+    return LV_OK;
+}
+
+int OccStore::clear(hipStream_t stream) {
+    LV_HIP(hipMemsetD32Async((hipDeviceptr_t)d_L, (int)OCC_NAN_BITS, n_vox, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+// room for n_points packed points in the pinned and the device staging buffers
+int OccStore::stage(hipStream_t stream, size_t n_points) {
+    LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the pinned buffer may still be pending)
+    if (n_points > h_pts_cap) {
+        if (h_pts) hipHostFree(h_pts);
+        h_pts = nullptr;
+        h_pts_cap = 0;
+        LV_HIP(hipHostMalloc((void**)&h_pts, n_points * 3 * sizeof(float), hipHostMallocDefault));
+        h_pts_cap = n_points;
+    }
+    if (n_points > d_pts_cap) {
+        hipFree(d_pts);
+        d_pts = nullptr;
+        d_pts_cap = 0;
+        LV_HIP(hipMalloc(&d_pts, n_points * 3 * sizeof(float)));
+        d_pts_cap = n_points;
+    }
+    return LV_OK;
+}
+
+int OccStore::integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t stats[4]) {
+    size_t total = 0;
+    for (size_t v = 0; v < n_views; ++v) total += views[v].n;
+    if (total) {
+        const int rc = stage(stream, total);
+        if (rc) return rc;
+        size_t o = 0;
+        for (size_t v = 0; v < n_views; ++v) {
+            const char* b = static_cast<const char*>(views[v].points);
+            for (size_t i = 0; i < views[v].n; ++i, ++o) std::memcpy(h_pts + 3 * o, b + i * views[v].stride, 3 * sizeof(float));
+        }
+        LV_HIP(hipMemcpyAsync(d_pts, h_pts, total * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    LV_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), stream));
+    uint32_t* crossed = d_bits;
+    uint32_t* hit = d_bits + n_words;
+    size_t o = 0;
+    for (size_t v = 0; v < n_views; ++v) {
+        const size_t n = views[v].n;
+        int32_t qs[3];
+        if (n && occ_view_origin(grid, views[v].t, qs)) {
+            OccPose pose;
+            std::memcpy(pose.R, views[v].R, sizeof(pose.R));
+            std::memcpy(pose.t, views[v].t, sizeof(pose.t));
+            hipLaunchKernelGGL(occ_march_kernel, dim3(grid_of(n)), dim3(256), 0, stream, d_pts + 3 * o, (uint32_t)n, grid, pose, qs[0], qs[1],
+                               qs[2], crossed, hit, d_stats);
+            hipLaunchKernelGGL(occ_fold_kernel, dim3(grid_of(n_words / 4)), dim3(256), 0, stream, d_L, reinterpret_cast<uint4*>(crossed),
+                               reinterpret_cast<uint4*>(hit), (uint32_t)(n_words / 4), grid, d_stats);
+            LV_HIP(hipGetLastError());
+        }
+        o += n;
+    }
+    LV_HIP(hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = (uint64_t)h_stats[i];
+    return LV_OK;
+}
+
+int OccStore::query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* logodds) {
+    if (n == 0) return LV_OK;
+    int rc = stage(stream, n);
+    if (rc) return rc;
+    if (n > d_out_cap) {
+        hipFree(d_out);
+        d_out = nullptr;
+        d_out_cap = 0;
+        LV_HIP(hipMalloc(&d_out, n * sizeof(float)));
+        d_out_cap = n;
+    }
+    const char* b = static_cast<const char*>(pts);
+    for (size_t i = 0; i < n; ++i) std::memcpy(h_pts + 3 * i, b + i * stride, 3 * sizeof(float));
+    LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(occ_query_kernel, dim3(grid_of(n)), dim3(256), 0, stream, d_L, grid, d_pts, (uint32_t)n, d_out);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(logodds, d_out, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int OccStore::project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d) {
+    const int k0 = k_lo < 0 ? 0 : k_lo, k1 = k_hi >= grid.nz ? grid.nz - 1 : k_hi;
+    const size_t plane = (size_t)grid.nx * (size_t)grid.ny;
+    hipLaunchKernelGGL(occ_project_kernel, dim3(grid_of(plane)), dim3(256), 0, stream, d_L, grid, k0, k1, prm.l_occ, prm.l_free, d_proj);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(grid2d, d_proj, plane, hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int OccStore::fetch(hipStream_t stream, float* logodds) {
+    LV_HIP(hipMemcpyAsync(logodds, d_L, n_vox * sizeof(float), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int OccStore::load(hipStream_t stream, const float* logodds) {
+    LV_HIP(hipMemcpyAsync(d_L, logodds, n_vox * sizeof(float), hipMemcpyHostToDevice, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+}  // namespace lv

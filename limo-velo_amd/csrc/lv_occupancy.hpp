@@ -1,0 +1,204 @@
+// lv_occupancy.hpp — the ray-cast occupancy grid (lv_occ_*, include/limovelo_hip.h "Occupancy grid"; kernels and host side in
+// lv_occupancy.hip).
+//
+// The first part is the rule itself as plain __host__ __device__ code without atomics: the quantisation, the return's range
+// rules and world transform, the integer walk and the log-odds update.  The kernels of lv_occupancy.hip run exactly these
+// functions; tests/emu/occupancy_emu.cpp compiles them with g++ through tests/emu/hip/hip_runtime.h and tests/test_occupancy_host.py
+// holds them to tests/occupancy_ref.py.  After occ_quant every step is integer arithmetic, so the three agree on every voxel.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/limovelo_hip.h"
+
+#define LV_OCC_HD __host__ __device__ inline
+
+namespace lv {
+
+constexpr int OCC_MAX_VIEWS = 32;
+constexpr int OCC_MAX_DIM = 1024;
+constexpr uint64_t OCC_MAX_VOXELS = (uint64_t)1 << 28;
+constexpr float OCC_SUB = 256.0f;            // sub-units per voxel (Q)
+constexpr float OCC_T_LIMIT = 8192.0f;       // a sensor origin this many voxels from the grid's origin gives no evidence
+constexpr float OCC_RANGE_LIMIT = 4096.0f;   // max_range / resolution
+constexpr float OCC_Q_LIMIT = 16777216.0f;   // 2^24: a return quantising to this or beyond on an axis is ignored
+
+// The grid and the constants of one lv_occ_integrate / lv_occ_query as the kernels take them
+struct OccGrid {
+    float origin[3];
+    float resolution;
+    int nx, ny, nz;
+    int wx;                       // words per x row of a bitmap: (nx + 31) / 32
+    float min_range2, max_range2; // min_range * min_range, max_range * max_range (f32 products)
+    float max_range;
+    float l_hit, l_miss, l_min, l_max;
+};
+
+// The quantised coordinate as f32, before the cast: floorf(((p - origin) / resolution) * 256) in exactly that order
+LV_OCC_HD float occ_quant_f(float p, float origin, float resolution) { return floorf(((p - origin) / resolution) * OCC_SUB); }
+
+// false: non-finite, or too far to be cast (only a world point farther than 65536 voxels from the origin is)
+LV_OCC_HD bool occ_quant(float p, float origin, float resolution, int32_t& q) {
+    const float f = occ_quant_f(p, origin, resolution);
+    if (!(fabsf(f) < OCC_Q_LIMIT)) return false;
+    q = (int32_t)f;
+    return true;
+}
+
+// The view's sensor origin in sub-units; false: the view gives no evidence (t non-finite or >= 8192 voxels from the origin)
+LV_OCC_HD bool occ_view_origin(const OccGrid& g, const float t[3], int32_t qs[3]) {
+    for (int a = 0; a < 3; ++a) {
+        const float c = (t[a] - g.origin[a]) / g.resolution;
+        if (!(fabsf(c) < OCC_T_LIMIT)) return false;   // (NaN and inf fail the comparison too)
+        qs[a] = (int32_t)floorf(c * OCC_SUB);
+    }
+    return true;
+}
+
+enum : int { OCC_RAY_IGNORED = 0, OCC_RAY_HIT = 1, OCC_RAY_CUT = 2 };
+
+// One return (x, y, z) of a view at pose (R row-major, t): its quantised end point, and whether it is ignored, a hit or cut
+LV_OCC_HD int occ_return(const OccGrid& g, const float R[9], const float t[3], float x, float y, float z, int32_t qe[3]) {
+    const float inf = __builtin_huge_valf();
+    if (!(fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf)) return OCC_RAY_IGNORED;
+    const float r2 = x * x + y * y + z * z;
+    if (r2 < g.min_range2) return OCC_RAY_IGNORED;
+    int kind = OCC_RAY_HIT;
+    if (r2 > g.max_range2) {
+        const float c = g.max_range / sqrtf(r2);
+        x = x * c;
+        y = y * c;
+        z = z * c;
+        kind = OCC_RAY_CUT;
+    }
+    for (int a = 0; a < 3; ++a) {
+        const float w = ((R[3 * a] * x + R[3 * a + 1] * y) + R[3 * a + 2] * z) + t[a];
+        if (!occ_quant(w, g.origin[a], g.resolution, qe[a])) return OCC_RAY_IGNORED;
+    }
+    return kind;
+}
+
+// The walk from qs to qe.  Named scalars, no indexed arrays: the state lives in registers on the device.
+struct OccWalk {
+    int32_t vx, vy, vz;   // the cell the walk stands in
+    int32_t ex, ey, ez;   // ve, where it ends
+    int32_t sx, sy, sz;   // step per axis: sign(d)
+    int32_t rx, ry, rz;   // steps left per axis
+    int32_t nx, ny, nz;   // numerator of the distance to the next boundary (sub-units); below 2^26
+    int32_t ax, ay, az;   // |d| per axis; below 2^25 (the products need int64)
+};
+
+LV_OCC_HD void occ_walk_axis(int32_t qs, int32_t qe, int32_t& v, int32_t& e, int32_t& s, int32_t& r, int32_t& n, int32_t& ad) {
+    const int32_t d = qe - qs;
+    ad = d < 0 ? -d : d;
+    s = (d > 0) - (d < 0);
+    v = qs >> 8;
+    e = qe >> 8;
+    r = e > v ? e - v : v - e;
+    n = s > 0 ? (v + 1) * 256 - qs : (s < 0 ? qs - v * 256 : 0);   // ((v + 1) << 8, v << 8: a product, v may be negative)
+}
+
+LV_OCC_HD void occ_walk_init(OccWalk& w, const int32_t qs[3], const int32_t qe[3]) {
+    occ_walk_axis(qs[0], qe[0], w.vx, w.ex, w.sx, w.rx, w.nx, w.ax);
+    occ_walk_axis(qs[1], qe[1], w.vy, w.ey, w.sy, w.ry, w.ny, w.ay);
+    occ_walk_axis(qs[2], qe[2], w.vz, w.ez, w.sz, w.rz, w.nz, w.az);
+}
+
+LV_OCC_HD bool occ_walk_done(const OccWalk& w) { return (w.rx | w.ry | w.rz) == 0; }
+
+// a before b (a the lower axis: it wins the tie): n_a / ad_a <= n_b / ad_b by cross-multiplication
+LV_OCC_HD bool occ_first(int32_t na, int32_t ada, int32_t nb, int32_t adb) { return (int64_t)na * (int64_t)adb <= (int64_t)nb * (int64_t)ada; }
+
+// One step: among the axes with steps left the one whose boundary comes first, ties to x, then y, then z.  Returns the axis.
+LV_OCC_HD int occ_walk_step(OccWalk& w) {
+    int a = -1;
+    if (w.rx > 0) a = 0;
+    if (w.ry > 0 && !(a == 0 && occ_first(w.nx, w.ax, w.ny, w.ay))) a = 1;
+    if (w.rz > 0) {
+        if (a < 0) a = 2;
+        else if (a == 0) { if (!occ_first(w.nx, w.ax, w.nz, w.az)) a = 2; }
+        else if (!occ_first(w.ny, w.ay, w.nz, w.az)) a = 2;
+    }
+    if (a == 0) { w.vx += w.sx; w.nx += 256; --w.rx; }
+    else if (a == 1) { w.vy += w.sy; w.ny += 256; --w.ry; }
+    else { w.vz += w.sz; w.nz += 256; --w.rz; }
+    return a;
+}
+
+LV_OCC_HD bool occ_in_grid(const OccGrid& g, int32_t i, int32_t j, int32_t k) {
+    return (uint32_t)i < (uint32_t)g.nx && (uint32_t)j < (uint32_t)g.ny && (uint32_t)k < (uint32_t)g.nz;
+}
+
+// true: the walk stands outside the grid on an axis it does not move back along, so neither a later cell nor ve is in the grid
+LV_OCC_HD bool occ_walk_left(const OccGrid& g, const OccWalk& w) {
+    return (w.vx < 0 && w.sx <= 0) || (w.vx >= g.nx && w.sx >= 0) || (w.vy < 0 && w.sy <= 0) || (w.vy >= g.ny && w.sy >= 0) ||
+           (w.vz < 0 && w.sz <= 0) || (w.vz >= g.nz && w.sz >= 0);
+}
+
+// One update of a voxel: unknown (NaN) starts from 0, the sum is clamped
+LV_OCC_HD float occ_update(float L, float delta, float l_min, float l_max) { return fminf(fmaxf((L != L ? 0.0f : L) + delta, l_min), l_max); }
+
+// The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_occ_configure: LV_EINVAL)
+inline const char* occ_check_params(const lv_occupancy_params* p) {
+    if (!p) return "null params";
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(p->origin[a])) return "origin: must be finite";
+    if (!(std::isfinite(p->resolution) && p->resolution > 0.f)) return "resolution: must be finite and > 0";
+    if (p->nx < 1 || p->nx > OCC_MAX_DIM || p->ny < 1 || p->ny > OCC_MAX_DIM || p->nz < 1 || p->nz > OCC_MAX_DIM)
+        return "nx, ny, nz: each must be in 1..1024";
+    if ((uint64_t)p->nx * (uint64_t)p->ny * (uint64_t)p->nz > OCC_MAX_VOXELS) return "nx * ny * nz: at most 2^28 voxels";
+    if (!(std::isfinite(p->min_range) && std::isfinite(p->max_range) && p->min_range > 0.f && p->min_range < p->max_range))
+        return "ranges: finite, 0 < min_range < max_range";
+    if (!(p->max_range / p->resolution <= OCC_RANGE_LIMIT)) return "max_range / resolution: at most 4096";
+    if (!(std::isfinite(p->l_hit) && std::isfinite(p->l_miss) && p->l_miss < 0.f && p->l_hit > 0.f)) return "l_miss < 0 < l_hit, finite";
+    if (!(std::isfinite(p->l_min) && std::isfinite(p->l_max) && p->l_min < 0.f && p->l_max > 0.f)) return "l_min < 0 < l_max, finite";
+    if (!(std::isfinite(p->l_occ) && std::isfinite(p->l_free) && p->l_free < p->l_occ)) return "l_free < l_occ, finite";
+    return nullptr;
+}
+
+inline OccGrid occ_grid_of(const lv_occupancy_params& p) {
+    OccGrid g{};
+    for (int a = 0; a < 3; ++a) g.origin[a] = p.origin[a];
+    g.resolution = p.resolution;
+    g.nx = p.nx; g.ny = p.ny; g.nz = p.nz;
+    g.wx = (p.nx + 31) / 32;
+    g.min_range2 = p.min_range * p.min_range;
+    g.max_range2 = p.max_range * p.max_range;
+    g.max_range = p.max_range;
+    g.l_hit = p.l_hit; g.l_miss = p.l_miss; g.l_min = p.l_min; g.l_max = p.l_max;
+    return g;
+}
+
+// The grid of a context and the buffers of its calls.  Nothing is allocated before configure().
+struct OccStore {
+    bool configured = false;
+    lv_occupancy_params prm{};
+    OccGrid grid{};
+    size_t n_vox = 0;
+    size_t n_words = 0;            // words of ONE bitmap, padded to a multiple of 4 (the fold reads uint4)
+    float* d_L = nullptr;          // log-odds, (k * ny + j) * nx + i; NaN = never observed
+    uint32_t* d_bits = nullptr;    // crossed bitmap, then hit bitmap: bit (i & 31) of word (k * ny + j) * wx + (i >> 5); all zero between views
+    unsigned long long* d_stats = nullptr;   // 4 counters of the call in flight
+    unsigned long long* h_stats = nullptr;   // pinned
+    float* h_pts = nullptr;        // pinned staging: packed x, y, z of every view's returns (or of the query points)
+    float* d_pts = nullptr;
+    float* d_out = nullptr;        // lv_occ_query's results
+    int8_t* d_proj = nullptr;      // lv_occ_project's result (nx * ny)
+    size_t h_pts_cap = 0, d_pts_cap = 0, d_out_cap = 0;
+
+    int configure(hipStream_t stream, const lv_occupancy_params& p);
+    int clear(hipStream_t stream);
+    int integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t stats[4]);
+    int query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* logodds);
+    int project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d);
+    int fetch(hipStream_t stream, float* logodds);
+    int load(hipStream_t stream, const float* logodds);
+    void release();
+
+   private:
+    int stage(hipStream_t stream, size_t n_points);
+};
+
+}  // namespace lv
