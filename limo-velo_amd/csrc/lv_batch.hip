@@ -96,8 +96,8 @@ __global__ __launch_bounds__(256) void batch_search_kernel(MapView map, const fl
                     const Xyz w = s_stage[gq][pos];
                     v = make_float4(w.x, w.y, w.z, __uint_as_float(0xFFFFFFFFu));
                 } else if (src >= 0) {
-                    const Xyz w = reinterpret_cast<const Xyz*>(map.bxyz[0])[(size_t)bstart + pos];
-                    v = make_float4(w.x, w.y, w.z, __uint_as_float(map.bidx[0][(size_t)bstart + pos]));
+                    const Xyz w = reinterpret_cast<const Xyz*>(map.bxyz[src])[(size_t)bstart + pos];
+                    v = make_float4(w.x, w.y, w.z, __uint_as_float(map.bidx[src][(size_t)bstart + pos]));
                 } else {
                     v = map.orig[pos];
                     v.w = __uint_as_float(pos);

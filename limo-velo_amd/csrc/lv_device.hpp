@@ -24,21 +24,21 @@ constexpr int N_OUT = 92;           // used entries of the record
 constexpr int CELL_OFFSET = 1 << 20;
 constexpr int CELL_FAR = 1 << 19;   // |cell - offset| beyond this -> brute-force path
 constexpr int MAX_LEVELS = 3;             // voxel levels of the search: edge voxel_size * 2^l (the Morton key resolves three bits per level)
-// Round 6: ONE level of 27-fold replicated neighbourhood buckets (level 0).  The 27-voxel block of a LEVEL-1 voxel v — level-0 voxels
-// [2v - 2, 2v + 4) per axis — is tiled exactly by the EIGHT level-0 buckets centred on voxels 2v - 1 and 2v + 2 per axis (each covers
-// three voxels per axis, disjoint), and every level-0 bucket belongs to exactly one such GROUP (an odd centre c is tile 0 of
-// v = (c + 1) / 2, an even one tile 1 of v = (c - 2) / 2, per axis).  A (re)build lays the eight runs of a group out side by side
-// (slack filled with +inf), so level 1 is ONE probe of the group table + ONE contiguous stream over level-0 storage (group_attempt,
-// lv_match.hip) and stores no points of its own; a group that an insert breaks up (a run moved, a tile appeared) is marked and its
-// points go on to the lists until the next re-linearisation.  Levels 2 and 3 are searched as the 27 / 216 un-replicated level-2
-// voxel lists.  Rounds 1-5 replicated three levels: 4.1 KB per map point, 81 runs touched per inserted point, 266 DRAM lines per
-// deleted one.
-constexpr int REPL_LEVELS = 1;            // level 0: 27-fold replicated neighbourhood buckets
-constexpr int SORTED_LEVELS = 1;          // ... in ascending id, 12-byte points (== REPL_LEVELS: there is no unordered replicated level any more)
+// TWO levels of 27-fold replicated neighbourhood buckets (levels 0 and 1): for every voxel of the level whose 27-block holds a point,
+// the points of that block in one run in ascending id, so a level is ONE table probe + ONE contiguous stream whose position order is
+// the reference's index order (ties included).  Levels 2 and 3 are searched as the 27 / 216 un-replicated level-2 voxel lists.
+// Round 6 kept level 0 alone and streamed level 1 out of level-0 storage (the eight level-0 buckets that tile a level-1 block, laid
+// out side by side: a tile GROUP): a third of every such stream was slack, and the runs are not in id order between them, so every
+// chunk carried tie tracking — the k-NN search's first launches paid for it.  The groups stay: the map queries
+// and the surface pass (lv_query.hip, lv_surface.hip) stream them.  Rounds 1-5 replicated three levels (4.1 KB per map point).
+constexpr int BUCKET_LEVELS = 2;          // levels 0, 1: 27-fold replicated neighbourhood buckets in ascending id, 12-byte points
+// The incremental machinery (lv_mapinc.hpp) maintains ONE replicated level per instance; the map runs one instance per bucket level
+constexpr int REPL_LEVELS = 1;            // replicated levels of one instance of lv_mapinc.hpp
+constexpr int SORTED_LEVELS = 1;          // (== REPL_LEVELS: there is no unordered replicated level)
 constexpr int CELL_LEVEL = 2;             // level-2 voxels keep one plain point list each (level-2 block = 27 lists, level-3 block = 216)
-constexpr int N_OCC = 2;                  // occupancy tables of a (re)build: [0] level-0 voxels, [1] level-2 voxels (lives on as the voxel-list table)
-constexpr int OCC_CELL = 1;
-__host__ __device__ constexpr int occ_level(int t) { return t == 0 ? 0 : CELL_LEVEL; }
+constexpr int N_OCC = 3;                  // occupancy tables of a (re)build, by level: [0], [1] feed the buckets, [2] lives on as the voxel-list table
+constexpr int OCC_CELL = 2;
+__host__ __device__ constexpr int occ_level(int t) { return t; }
 constexpr uint64_t EMPTY_KEY = ~0ull;
 constexpr int MAX_PASSES = 16;
 
@@ -165,13 +165,13 @@ struct MapView {
     // level 0: for every voxel whose 3x3x3 block holds at least one point, the points of that block in one
     // contiguous run ("bucket") with slack behind it for appends.  bt[0].table entries are {key lo, key hi, bucket
     // start, bucket count}; ascending id (deleted entries keep their place with x = +inf), 12-byte points (what the
-    // search streams) + a parallel id array (capturing launches / deletions).  The level-1 block is eight of these
-    // buckets (see REPL_LEVELS): gt maps a level-1 voxel to the region {start, extent} its group's eight runs occupy in the
-    // pool (extent 0: the group is no longer in one piece).
-    GridLevel bt[REPL_LEVELS];
+    // search streams) + a parallel id array (capturing launches / deletions).  Level 1: the same per level-1 voxel (bt[1]).
+    // gt maps a level-1 voxel to the region {start, extent} the eight level-0 runs that tile its block (a tile group) occupy
+    // in the level-0 pool (extent 0: the group is no longer in one piece): the map queries and the surface pass stream it.
+    GridLevel bt[BUCKET_LEVELS];
     GridLevel gt;
-    const float* bxyz[SORTED_LEVELS];
-    const uint32_t* bidx[SORTED_LEVELS];
+    const float* bxyz[BUCKET_LEVELS];
+    const uint32_t* bidx[BUCKET_LEVELS];
     // one plain list of {x, y, z, id} records per level-2 voxel: the level-2 block is searched as the 27 lists around the
     // query's voxel, the level-3 block as the 216 lists that tile it (whole wavefronts, (distance, id) keys)
     GridLevel ct;

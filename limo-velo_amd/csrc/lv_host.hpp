@@ -23,6 +23,8 @@ struct MapStats {   // == lv_map_stats (include/limovelo_hip.h)
     uint64_t bytes;
 };
 
+constexpr int POOL_CELL = BUCKET_LEVELS;   // index of the voxel lists in MapStore::pool_cap / pool_base and the statistics
+
 struct MapStore {
     // ---- points by id (insertion order; deleted ids keep their slot with x = +inf)
     float4* d_orig = nullptr;
@@ -39,22 +41,22 @@ struct MapStore {
     void* d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
     uint32_t* d_counts = nullptr;
-    uint4* d_tables[N_OCC] = {};           // occupied voxels -> run in d_sorted: [0] level 0, [OCC_CELL] level 2 (lives on as the voxel-list table)
+    uint4* d_tables[N_OCC] = {};           // occupied voxels -> run in d_sorted: [0], [1] levels 0, 1; [OCC_CELL] level 2 (lives on as the voxel-list table)
     uint32_t table_size[N_OCC] = {};
     uint32_t n_cells[N_OCC] = {};
-    // ---- level 0: neighbourhood buckets with slack (built straight into their pool: no float4 staging copy since round 6)
-    uint4* d_btable[REPL_LEVELS] = {};
-    SlotAux* d_baux[REPL_LEVELS] = {};
-    uint32_t btable_size[REPL_LEVELS] = {};
-    float* d_bxyz[SORTED_LEVELS] = {};    // 12-byte points: what the search kernel streams
-    uint32_t* d_bidx[SORTED_LEVELS] = {}; // ids (ascending inside a bucket)
-    uint16_t* d_backpos = nullptr;        // [id * 27 + c]: position of a point inside the bucket of its neighbour c (BACKPOS_FAR: beyond 16 bits,
-                                          // found by binary search): a deletion is 27 probes + 27 direct writes
+    // ---- levels 0, 1: neighbourhood buckets with slack (built straight into their pools: no float4 staging copy since round 6)
+    uint4* d_btable[BUCKET_LEVELS] = {};
+    SlotAux* d_baux[BUCKET_LEVELS] = {};
+    uint32_t btable_size[BUCKET_LEVELS] = {};
+    float* d_bxyz[BUCKET_LEVELS] = {};    // 12-byte points: what the search kernel streams
+    uint32_t* d_bidx[BUCKET_LEVELS] = {}; // ids (ascending inside a bucket)
+    uint16_t* d_backpos[BUCKET_LEVELS] = {};   // [l][id * 27 + c]: position of a point inside the level-l bucket of its neighbour c
+                                          // (BACKPOS_FAR: beyond 16 bits, found by binary search): a deletion is 27 probes + 27 direct writes per level
     uint32_t* d_cellpos = nullptr;        // [id]: position of a point in its voxel's list (allocated with d_backpos)
     size_t backptr_cap = 0;               // ids they are allocated for
     uint32_t* d_biglist = nullptr;        // build scratch: buckets of more than 64 points (a workgroup each)
     size_t biglist_cap = 0;
-    // tile groups (lv_device.hpp REPL_LEVELS): level-1 voxel -> {start, extent} of the region its eight level-0 runs were laid out in
+    // tile groups (level-0 storage only; read by the map queries and the surface pass): level-1 voxel -> {start, extent} of the region its eight level-0 runs were laid out in
     uint4* d_gtable = nullptr;
     uint32_t gtable_size = 0;
     uint32_t* d_gext = nullptr;           // build scratch: a group's extent while its runs take their places, then the groups' offsets
@@ -64,13 +66,13 @@ struct MapStore {
     RegroupPlan* d_regroup = nullptr;
     uint32_t broken_cap = 0;
     uint32_t n_groups = 0;
-    uint4* d_comp = nullptr;              // runs an insert batch compacts in place (lv_mapinc.hpp inc_compact_*), their staging area
-    float4* d_cstage = nullptr;
-    uint32_t* d_cnew = nullptr;
+    uint4* d_comp[BUCKET_LEVELS] = {};     // (per instance of the insert machinery, like every work list and scratch table below) runs an insert batch compacts in place (lv_mapinc.hpp inc_compact_*), their staging area
+    float4* d_cstage[BUCKET_LEVELS] = {};
+    uint32_t* d_cnew[BUCKET_LEVELS] = {};
     uint32_t comp_cap = 0, cstage_cap = 0;
-    size_t pool_cap[INC_LEVELS] = {};     // entries per pool ([CELL_SLOT]: d_cell4)
-    uint32_t pool_base[INC_LEVELS] = {};  // entries laid out by the last (re)build; the rest is split into arenas
-    uint32_t n_bcells[REPL_LEVELS] = {};
+    size_t pool_cap[BUCKET_LEVELS + 1] = {};     // entries per pool: bucket levels 0, 1; [POOL_CELL]: d_cell4
+    uint32_t pool_base[BUCKET_LEVELS + 1] = {};  // entries laid out by the last (re)build; the rest is split into arenas
+    uint32_t n_bcells[BUCKET_LEVELS] = {};
     uint32_t* d_cell_slots = nullptr;  // scratch: table slots of the bucket voxels of the level being built
     uint32_t* d_bcount = nullptr;
     uint32_t* d_bcap = nullptr;
@@ -84,7 +86,7 @@ struct MapStore {
     uint32_t caux_size = 0;
     float4* d_cell4 = nullptr;
     // ---- incremental maintenance (lv_mapinc.hpp)
-    MapCounters* d_cnt = nullptr;
+    MapCounters* d_cnt = nullptr;      // [BUCKET_LEVELS]: one per instance of the incremental machinery; [0] also carries the batch's front half, the boxes and the lists
     MapCounters* h_cnt = nullptr;      // pinned mirror
     float4* d_new = nullptr;           // staged batch
     uint64_t* d_nkeys = nullptr;
@@ -96,19 +98,19 @@ struct MapStore {
     uint32_t* d_nsurv = nullptr;       // the batch's survivors in sorted-batch (Morton box) order, + the flags / positions that build it
     uint32_t* d_nsflag = nullptr;
     uint32_t* d_nspos = nullptr;
-    uint32_t* d_rank = nullptr;
+    uint32_t* d_rank[BUCKET_LEVELS] = {};
     void* d_ntmp = nullptr;
     size_t ntmp_bytes = 0, batch_cap = 0;
     // voxel groups of a batch (lv_mapinc.hpp GroupRW)
-    uint4* d_gtab[REPL_LEVELS] = {};
+    uint4* d_gtab[BUCKET_LEVELS] = {};    // [instance]
     uint32_t gtab_size = 0;
-    uint32_t* d_prank = nullptr;
-    uint32_t* d_pslot = nullptr;
-    uint32_t* d_gbase[REPL_LEVELS] = {};
-    uint32_t* d_gslot[REPL_LEVELS] = {};
-    uint4* d_gdst[REPL_LEVELS] = {};
-    uint32_t* d_gcnt = nullptr;        // [0] relocations of the batch
-    uint4* d_reloc = nullptr;
+    uint32_t* d_prank[BUCKET_LEVELS] = {};
+    uint32_t* d_pslot[BUCKET_LEVELS] = {};
+    uint32_t* d_gbase[BUCKET_LEVELS] = {};
+    uint32_t* d_gslot[BUCKET_LEVELS] = {};
+    uint4* d_gdst[BUCKET_LEVELS] = {};
+    uint32_t* d_gcnt = nullptr;        // [instance * 4 * LIST_SHARDS]: the sharded cursors of the batch's work lists
+    uint4* d_reloc[BUCKET_LEVELS] = {};
     uint32_t reloc_cap = 0;
     float4* d_dead = nullptr;
     size_t dead_cap = 0;
@@ -174,7 +176,7 @@ struct MapStore {
     // the living points of this map, compacted in id order, into dst.d_orig (dst: an idle store whose search structure is not
     // built yet): enqueued on `stream`, no host wait; m must be settled
     int snapshot_into(MapStore& dst, hipStream_t stream);
-    MapRW rw() const;
+    MapRW rw(int inst = 0) const;   // instance 0: level-0 buckets, voxel lists, tile groups; instance 1: level-1 buckets
     void refresh_view();
     void stats(MapStats* out) const;
     void release();

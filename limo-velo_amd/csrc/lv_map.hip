@@ -126,7 +126,7 @@ __global__ void map_insert_kernel(const uint64_t* __restrict__ keys, uint32_t m,
 // hash probe and ONE coalesced stream instead of 27 probes + 27 short dependent gathers; the
 // search region, and therefore the exactness argument of lv_match.hip, is unchanged.  Every point lands
 // in 27 buckets: HBM capacity (288 GB) is traded for latency — on ONE level since round 6 (the level-1
-// block is eight of these buckets, lv_device.hpp REPL_LEVELS).
+// block is eight of these buckets; level 1 also has buckets of its own, lv_device.hpp BUCKET_LEVELS).
 __device__ __forceinline__ bool probe_cell(const GridLevelW& g, uint64_t key, uint32_t& start, uint32_t& count) {
     uint32_t slot = hash_cell(key, g.shift) & g.mask;
     for (;;) {
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void bucket_count_kernel(GridLevelW occ, GridL
     }
 }
 
-// ---- tile groups: the eight level-0 runs that tile a level-1 block side by side (lv_device.hpp REPL_LEVELS) ----------------------
+// ---- tile groups: the eight level-0 runs that tile a level-1 block side by side (lv_device.hpp BUCKET_LEVELS) ----------------------
 // pass 2b: every bucket joins its group (a slot of the group table) and takes its place in the group's region: the running sum
 // of the capacities of the runs that came before it (the order of the runs inside a region is of no consequence: level 1 streams
 // the region as ONE candidate array).  boff[cell] = the group's slot, bcount[cell] = the run's offset inside the region.
@@ -277,6 +277,7 @@ struct BuildOut {
     SlotAux* aux;
     float origin[3];
     float inv_cell;
+    int level;
 };
 __device__ __forceinline__ void bucket_emit(const BuildOut& o, size_t at, uint32_t pos, const float4& p, uint32_t bx, uint32_t by, uint32_t bz) {
     o.bxyz[at * 3] = p.x;
@@ -284,7 +285,7 @@ __device__ __forceinline__ void bucket_emit(const BuildOut& o, size_t at, uint32
     o.bxyz[at * 3 + 2] = p.z;
     const uint32_t id = __float_as_uint(p.w);
     o.bidx[at] = id;
-    o.backpos[(size_t)id * 27 + backpos_slot(p, o.origin, o.inv_cell, bx, by, bz)] = (uint16_t)(pos < (uint32_t)BACKPOS_FAR ? pos : (uint32_t)BACKPOS_FAR);
+    o.backpos[(size_t)id * 27 + backpos_slot(p, o.origin, o.inv_cell, o.level, bx, by, bz)] = (uint16_t)(pos < (uint32_t)BACKPOS_FAR ? pos : (uint32_t)BACKPOS_FAR);
 }
 
 // pass 3 (build), buckets of up to 64 points (the bulk): one wavefront per bucket gathers the block's points from `sorted`, orders
@@ -550,12 +551,14 @@ int MapStore::reserve(size_t cap) {
         d_box_next = nn;
         box_next_cap = ncap;
     }
-    if (d_backpos) {   // positions inside the buckets are by id: keep them
-        uint16_t* nb = nullptr;
-        LV_HIP(hipMalloc(&nb, ncap * 27 * sizeof(uint16_t)));
-        if (n_ids) LV_HIP(hipMemcpy(nb, d_backpos, (size_t)n_ids * 27 * sizeof(uint16_t), hipMemcpyDeviceToDevice));
-        hipFree(d_backpos);
-        d_backpos = nb;
+    if (d_backpos[0]) {   // positions inside the buckets are by id: keep them
+        for (int l = 0; l < BUCKET_LEVELS; ++l) {
+            uint16_t* nb = nullptr;
+            LV_HIP(hipMalloc(&nb, ncap * 27 * sizeof(uint16_t)));
+            if (n_ids) LV_HIP(hipMemcpy(nb, d_backpos[l], (size_t)n_ids * 27 * sizeof(uint16_t), hipMemcpyDeviceToDevice));
+            hipFree(d_backpos[l]);
+            d_backpos[l] = nb;
+        }
         uint32_t* nc = nullptr;
         LV_HIP(hipMalloc(&nc, ncap * sizeof(uint32_t)));
         if (n_ids) LV_HIP(hipMemcpy(nc, d_cellpos, (size_t)n_ids * sizeof(uint32_t), hipMemcpyDeviceToDevice));
@@ -585,20 +588,22 @@ void MapStore::release() {
     hipFree(d_orig); hipFree(d_orig2); hipFree(d_sorted); hipFree(d_keys); hipFree(d_keys_sorted); hipFree(d_idx); hipFree(d_idx_sorted);
     hipFree(d_sort_tmp); hipFree(d_counts);
     hipFree(d_cell_slots); hipFree(d_flags); hipFree(d_bcount); hipFree(d_bcap); hipFree(d_boff); hipFree(d_scan_tmp);
-    for (int l = 0; l < REPL_LEVELS; ++l) { hipFree(d_btable[l]); hipFree(d_baux[l]); }
-    for (int l = 0; l < SORTED_LEVELS; ++l) { hipFree(d_bxyz[l]); hipFree(d_bidx[l]); }
-    hipFree(d_backpos); hipFree(d_cellpos); hipFree(d_biglist); hipFree(d_gtable); hipFree(d_gext); hipFree(d_goff);
-    hipFree(d_broken); hipFree(d_regroup); hipFree(d_comp); hipFree(d_cstage); hipFree(d_cnew);
+    for (int l = 0; l < BUCKET_LEVELS; ++l) { hipFree(d_btable[l]); hipFree(d_baux[l]); hipFree(d_bxyz[l]); hipFree(d_bidx[l]); hipFree(d_backpos[l]); }
+    hipFree(d_cellpos); hipFree(d_biglist); hipFree(d_gtable); hipFree(d_gext); hipFree(d_goff);
+    hipFree(d_broken); hipFree(d_regroup);
     hipFree(d_caux); hipFree(d_cell4);
     for (int l = 0; l < N_OCC; ++l) hipFree(d_tables[l]);
     hipFree(d_cnt);
     if (h_cnt) hipHostFree(h_cnt);
     hipFree(d_new); hipFree(d_nkeys); hipFree(d_nkeys_sorted); hipFree(d_nidx); hipFree(d_nidx_sorted); hipFree(d_nalive);
-    hipFree(d_napos); hipFree(d_nsurv); hipFree(d_nsflag); hipFree(d_nspos); hipFree(d_rank); hipFree(d_ntmp); hipFree(d_dead); hipFree(d_alive); hipFree(d_apos); hipFree(d_ascan_tmp);
+    hipFree(d_napos); hipFree(d_nsurv); hipFree(d_nsflag); hipFree(d_nspos); hipFree(d_ntmp); hipFree(d_dead); hipFree(d_alive); hipFree(d_apos); hipFree(d_ascan_tmp);
     hipFree(d_box); hipFree(d_box_next);
-    for (int l = 0; l < REPL_LEVELS; ++l) { hipFree(d_gtab[l]); hipFree(d_gbase[l]); hipFree(d_gslot[l]); hipFree(d_gdst[l]); }
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
+        hipFree(d_gtab[l]); hipFree(d_gbase[l]); hipFree(d_gslot[l]); hipFree(d_gdst[l]); hipFree(d_prank[l]); hipFree(d_pslot[l]);
+        hipFree(d_rank[l]); hipFree(d_reloc[l]); hipFree(d_comp[l]); hipFree(d_cstage[l]); hipFree(d_cnew[l]);
+    }
     note_free(notes);
-    hipFree(d_prank); hipFree(d_pslot); hipFree(d_gcnt); hipFree(d_reloc);
+    hipFree(d_gcnt);
     *this = MapStore();
 }
 
@@ -612,12 +617,12 @@ void MapStore::refresh_view() {
     view.cell = cell;
     view.inv_cell = 1.0f / cell;
     for (int a = 0; a < 3; ++a) view.origin[a] = origin[a];
-    for (int l = 0; l < REPL_LEVELS; ++l) {
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
         view.bt[l].table = d_btable[l];
         view.bt[l].mask = btable_size[l] ? btable_size[l] - 1 : 0;
         view.bt[l].shift = (uint32_t)(64 - log2u(btable_size[l] ? btable_size[l] : 1));
     }
-    for (int l = 0; l < SORTED_LEVELS; ++l) {
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
         view.bxyz[l] = d_bxyz[l];
         view.bidx[l] = d_bidx[l];
     }
@@ -630,46 +635,38 @@ void MapStore::refresh_view() {
     view.cell4 = d_cell4;
 }
 
-MapRW MapStore::rw() const {
+// One instance of the incremental machinery (lv_mapinc.hpp) per bucket level: instance 0 maintains the level-0 buckets, the voxel lists
+// and the tile groups; instance 1 the level-1 buckets alone (no list table, no group table).
+MapRW MapStore::rw(int inst) const {
     MapRW M{};
     M.orig = d_orig;
-    for (int l = 0; l < REPL_LEVELS; ++l) {
-        M.lv[l].table = d_btable[l];
-        M.lv[l].aux = d_baux[l];
-        M.lv[l].mask = btable_size[l] - 1;
-        M.lv[l].shift = (uint32_t)(64 - log2u(btable_size[l]));
-        M.lv[l].slot_limit = (uint32_t)((uint64_t)btable_size[l] * 7 / 10);
-        M.lv[l].pool_cap = (uint32_t)(pool_cap[l] > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : pool_cap[l]);
-    }
-    for (int l = 0; l < SORTED_LEVELS; ++l) {
-        M.bxyz[l] = d_bxyz[l];
-        M.bidx[l] = d_bidx[l];
-    }
-    M.backpos = d_backpos;
+    M.lv[0].table = d_btable[inst];
+    M.lv[0].aux = d_baux[inst];
+    M.lv[0].mask = btable_size[inst] - 1;
+    M.lv[0].shift = (uint32_t)(64 - log2u(btable_size[inst]));
+    M.lv[0].slot_limit = (uint32_t)((uint64_t)btable_size[inst] * 7 / 10);
+    M.lv[0].pool_cap = (uint32_t)(pool_cap[inst] > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : pool_cap[inst]);
+    M.bxyz[0] = d_bxyz[inst];
+    M.bidx[0] = d_bidx[inst];
+    M.backpos = d_backpos[inst];
+    M.level = inst;
+    M.cnt = d_cnt + inst;
+    M.front = d_cnt;
+    for (int a = 0; a < 3; ++a) M.origin[a] = origin[a];
+    M.inv_cell = 1.0f / cell;
+    if (inst != 0) return M;   // (everything else stays null / zero: the lists and the groups are instance 0's)
     M.gtable = d_gtable;
     M.gmask = gtable_size ? gtable_size - 1 : 0;
     M.gshift = (uint32_t)(64 - log2u(gtable_size ? gtable_size : 1));
     M.gslot_limit = (uint32_t)((uint64_t)gtable_size * 7 / 10);
-    M.broken = nullptr;   // (add_staged hands the batch's lists over; sweeps break groups without listing them)
-    M.broken_cap = 0;
-    M.n_broken = nullptr;
-    M.comp = nullptr;
-    M.comp_cap = 0;
-    M.n_comp = nullptr;
-    M.cstage = nullptr;
-    M.cnew = nullptr;
-    M.cstage_cap = 0;
     M.cellpos = d_cellpos;
     M.lv[CELL_SLOT].table = d_tables[OCC_CELL];
     M.lv[CELL_SLOT].aux = d_caux;
     M.lv[CELL_SLOT].mask = table_size[OCC_CELL] - 1;
     M.lv[CELL_SLOT].shift = (uint32_t)(64 - log2u(table_size[OCC_CELL]));
     M.lv[CELL_SLOT].slot_limit = (uint32_t)((uint64_t)table_size[OCC_CELL] * 6 / 10);
-    M.lv[CELL_SLOT].pool_cap = (uint32_t)(pool_cap[CELL_SLOT] > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : pool_cap[CELL_SLOT]);
+    M.lv[CELL_SLOT].pool_cap = (uint32_t)(pool_cap[POOL_CELL] > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : pool_cap[POOL_CELL]);
     M.cell4 = d_cell4;
-    for (int a = 0; a < 3; ++a) M.origin[a] = origin[a];
-    M.inv_cell = 1.0f / cell;
-    M.cnt = d_cnt;
     return M;
 }
 
@@ -679,28 +676,30 @@ void MapStore::stats(MapStats* out) const {
     out->ids = n_ids;
     out->capacity = capacity;
     if (h_cnt && built) {
-        for (int l = 0; l < INC_LEVELS; ++l) {
+        for (int l = 0; l <= BUCKET_LEVELS; ++l) {   // bucket levels 0, 1, then the voxel lists (instance 0's second table)
+            const MapCounters& hc = h_cnt[l < BUCKET_LEVELS ? l : 0];
+            const int t = l < BUCKET_LEVELS ? 0 : CELL_SLOT;
             uint64_t used = pool_base[l];
             for (int a = 0; a < N_ARENAS; ++a) {
                 const uint32_t start = pool_base[l] + (uint32_t)(((uint64_t)(pool_cap[l] - pool_base[l]) * a) / N_ARENAS);
-                const uint32_t cur = h_cnt->arena_cur[l][a] < h_cnt->arena_end[l][a] ? h_cnt->arena_cur[l][a] : h_cnt->arena_end[l][a];
+                const uint32_t cur = hc.arena_cur[t][a] < hc.arena_end[t][a] ? hc.arena_cur[t][a] : hc.arena_end[t][a];
                 used += cur - start;
             }
             out->pool_used[l] = used;
-            out->slots_used[l] = h_cnt->slots_used[l];
+            out->slots_used[l] = hc.slots_used[t];
         }
         out->tombstones = tombstones;
     }
-    for (int l = 0; l < INC_LEVELS; ++l) out->pool_cap[l] = pool_cap[l];
-    for (int l = 0; l < REPL_LEVELS; ++l) out->slots_cap[l] = btable_size[l];
-    out->slots_cap[CELL_SLOT] = table_size[OCC_CELL];
+    for (int l = 0; l <= BUCKET_LEVELS; ++l) out->pool_cap[l] = pool_cap[l];
+    for (int l = 0; l < BUCKET_LEVELS; ++l) out->slots_cap[l] = btable_size[l];
+    out->slots_cap[POOL_CELL] = table_size[OCC_CELL];
     out->dropped = dropped_total;
     out->relinearisations = relinearisations;
     out->incremental_adds = incremental_adds;
     // every device allocation that grows with the map (the per-batch scratch of an insert does not: reserve_batch)
     uint64_t b = (uint64_t)capacity * (16 + 16 + 16 + 8 + 8 + 4 + 4 + 16);                                   // orig, orig2, sorted, keys x 2, idx x 2, dead
-    for (int l = 0; l < REPL_LEVELS; ++l) b += (uint64_t)pool_cap[l] * 16 + (uint64_t)btable_size[l] * 32;   // 12-byte points + ids; table + aux
-    b += (uint64_t)pool_cap[CELL_SLOT] * 16 + (uint64_t)caux_size * 16 + (uint64_t)backptr_cap * (27 * 2 + 4);   // lists, their aux; back-positions + cellpos
+    for (int l = 0; l < BUCKET_LEVELS; ++l) b += (uint64_t)pool_cap[l] * 16 + (uint64_t)btable_size[l] * 32;   // 12-byte points + ids; table + aux
+    b += (uint64_t)pool_cap[POOL_CELL] * 16 + (uint64_t)caux_size * 16 + (uint64_t)backptr_cap * (BUCKET_LEVELS * 27 * 2 + 4);   // lists, their aux; back-positions + cellpos
     for (int l = 0; l < N_OCC; ++l) b += (uint64_t)table_size[l] * 16;
     b += (uint64_t)cells_cap * 16 + (uint64_t)biglist_cap * 4;                                                // build scratch per bucket voxel
     b += (uint64_t)gtable_size * 16 + (uint64_t)gscratch_cap * 8;                                             // tile groups: table + build scratch
@@ -721,10 +720,10 @@ int MapStore::rebuild(hipStream_t stream) {
         const int rc0 = ensure_counters();
         if (rc0) return rc0;
     }
-    std::memset(h_cnt, 0, sizeof(MapCounters));
+    std::memset(h_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters));
     m = n_ids;
     if (m == 0) {
-        LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, sizeof(MapCounters), hipMemcpyHostToDevice, stream));
+        LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipMemcpyHostToDevice, stream));
         LV_HIP(hipStreamSynchronize(stream));
         return LV_OK;   // no map: view.m stays 0
     }
@@ -784,31 +783,33 @@ int MapStore::rebuild(hipStream_t stream) {
     }
     launch_sliced(slice_wgs * 2, map_insert_kernel, grid, (uint32_t)B, stream, (const uint64_t*)d_keys_sorted, m, tp);
     LV_HIP(hipGetLastError());
-    for (int l = 0; l < REPL_LEVELS; ++l) {
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
         int rc = build_buckets(stream, l, counts[l]);
         if (rc) return rc;
     }
     int rc = build_cells(stream, counts[OCC_CELL]);
     if (rc) return rc;
-    for (int l = 0; l < INC_LEVELS; ++l) {   // the free part of every pool, split into arenas
+    for (int l = 0; l <= BUCKET_LEVELS; ++l) {   // the free part of every pool, split into arenas
+        MapCounters& hc = h_cnt[l < BUCKET_LEVELS ? l : 0];
+        const int t = l < BUCKET_LEVELS ? 0 : CELL_SLOT;
         const uint64_t cap = pool_cap[l] > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : pool_cap[l];
         const uint64_t free_entries = cap - pool_base[l];
         for (int a = 0; a < N_ARENAS; ++a) {
-            h_cnt->arena_cur[l][a] = pool_base[l] + (uint32_t)((free_entries * a) / N_ARENAS);
-            h_cnt->arena_end[l][a] = pool_base[l] + (uint32_t)((free_entries * (a + 1)) / N_ARENAS);
+            hc.arena_cur[t][a] = pool_base[l] + (uint32_t)((free_entries * a) / N_ARENAS);
+            hc.arena_end[t][a] = pool_base[l] + (uint32_t)((free_entries * (a + 1)) / N_ARENAS);
         }
     }
-    for (int l = 0; l < REPL_LEVELS; ++l) h_cnt->slots_used[l] = n_bcells[l];
+    for (int l = 0; l < BUCKET_LEVELS; ++l) h_cnt[l].slots_used[0] = n_bcells[l];
     h_cnt->gslots_used = n_groups;
     h_cnt->slots_used[CELL_SLOT] = counts[OCC_CELL];
-    LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, sizeof(MapCounters), hipMemcpyHostToDevice, stream));
+    LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipMemcpyHostToDevice, stream));
     LV_HIP(hipStreamSynchronize(stream));
     built = true;
     refresh_view();
     return LV_OK;
 }
 
-// level 0 (the one replicated level; `level` stays a parameter of the pool / table arrays)
+// one replicated level (0 or 1); level 0 is also laid out by tile groups
 int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) {
     GridLevelW occ{d_tables[level], table_size[level] - 1, (uint32_t)(64 - log2u(table_size[level]))};
     const uint32_t occ_slots = table_size[level];
@@ -816,7 +817,7 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
     const bool give_back = (uint64_t)size * 8 <= btable_size[level] && btable_size[level] > (1u << 20);   // (see the occupancy tables)
     if (size < btable_size[level] && !give_back) size = btable_size[level];
     if (backptr_cap < capacity) {   // back-positions and list positions are by id
-        LV_REALLOC(d_backpos, uint16_t, capacity * 27);
+        for (int l = 0; l < BUCKET_LEVELS; ++l) LV_REALLOC(d_backpos[l], uint16_t, capacity * 27);
         LV_REALLOC(d_cellpos, uint32_t, capacity);
         backptr_cap = capacity;
     }
@@ -866,7 +867,19 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
         uint32_t gsize = next_pow2(nb);   // (a group holds up to eight buckets; on surfaces ~4: load ~0.25; checked below)
         uint64_t total = 0;
         uint32_t n_big = 0;
-        for (;;) {
+        if (level != 0) {
+            // level 1 belongs to no group: its runs follow each other in the order the buckets registered
+            size_t stmp = scan_tmp_bytes;
+            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, stmp, d_bcap, d_boff, (int)nb, stream));
+            uint32_t last_off = 0, last_cap = 0, hf[4] = {0, 0, 0, 0};
+            LV_HIP(hipMemcpyAsync(&last_off, d_boff + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            LV_HIP(hipMemcpyAsync(&last_cap, d_bcap + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            LV_HIP(hipMemcpyAsync(hf, d_flags, sizeof(hf), hipMemcpyDeviceToHost, stream));
+            LV_HIP(hipStreamSynchronize(stream));
+            total = (uint64_t)last_off + last_cap;
+            n_big = hf[2];
+        }
+        while (level == 0) {
             if (gsize > gtable_size || ((uint64_t)gsize * 8 <= gtable_size && gtable_size > (1u << 20))) {
                 LV_REALLOC(d_gtable, uint4, gsize);
                 gtable_size = gsize;
@@ -924,10 +937,10 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
             LV_REALLOC(d_bidx[level], uint32_t, want);
             pool_cap[level] = (size_t)want;
         }
-        // the slack behind every run reads as +inf (a candidate at distance +inf, like a deleted entry): level 1 streams a group's
-        // region runs AND slack
+        // the slack behind every run reads as +inf (a candidate at distance +inf, like a deleted entry): the consumers of a tile
+        // group stream its region runs AND slack
         if (total) LV_HIP(hipMemsetD32Async((hipDeviceptr_t)d_bxyz[level], 0x7F800000, (size_t)total * 3, stream));
-        BuildOut bo{d_bxyz[level], d_bidx[level], d_backpos, d_baux[level], {origin[0], origin[1], origin[2]}, 1.0f / cell};
+        BuildOut bo{d_bxyz[level], d_bidx[level], d_backpos[level], d_baux[level], {origin[0], origin[1], origin[2]}, 1.0f / cell, level};
         launch_sliced(slice_wgs, bucket_build_kernel, (nb + 3) / 4, 256u, stream, occ, bt, (const uint32_t*)d_cell_slots, nb, (const float4*)d_sorted,
                       (const uint32_t*)d_bcap, (const uint32_t*)d_boff, bo);
         if (n_big)
@@ -970,16 +983,16 @@ int MapStore::build_cells(hipStream_t stream, uint32_t n_occupied) {
     const uint64_t total = (uint64_t)last_off + last_cap;
     const uint64_t want = total + total / 4 + (1ull << 20);
     if (want > 0xFFFFFFF0ull) { set_error("voxel-list pool exceeds 2^32 entries"); return LV_ERANGE; }
-    if (want > pool_cap[CELL_SLOT]) {
-        pool_cap[CELL_SLOT] = 0;
+    if (want > pool_cap[POOL_CELL]) {
+        pool_cap[POOL_CELL] = 0;
         LV_REALLOC(d_cell4, float4, want);
-        pool_cap[CELL_SLOT] = (size_t)want;
+        pool_cap[POOL_CELL] = (size_t)want;
     }
     GridLevelW t2{d_tables[OCC_CELL], size - 1, (uint32_t)(64 - log2u(size))};
     hipLaunchKernelGGL(cell_fill_kernel, dim3((m + B - 1) / B), dim3(B), 0, stream, d_keys_sorted, d_sorted, m, t2, d_boff, d_cell4, d_cellpos);
     hipLaunchKernelGGL(cell_commit_kernel, dim3((size + B - 1) / B), dim3(B), 0, stream, d_tables[OCC_CELL], size, d_bcap, d_boff, d_caux);
     LV_HIP(hipGetLastError());
-    pool_base[CELL_SLOT] = (uint32_t)total;
+    pool_base[POOL_CELL] = (uint32_t)total;
     return LV_OK;
 }
 
@@ -998,19 +1011,19 @@ int MapStore::reserve_batch(size_t k) {
     LV_REALLOC(d_nsurv, uint32_t, ncap);
     LV_REALLOC(d_nsflag, uint32_t, ncap);
     LV_REALLOC(d_nspos, uint32_t, ncap);
-    LV_REALLOC(d_rank, uint32_t, ncap * 27 * SORTED_LEVELS);
     gtab_size = next_pow2((uint64_t)ncap * 4);
-    for (int l = 0; l < REPL_LEVELS; ++l) {
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {   // (per instance)
+        LV_REALLOC(d_rank[l], uint32_t, ncap * 27 * SORTED_LEVELS);
+        LV_REALLOC(d_prank[l], uint32_t, ncap * REPL_LEVELS);
+        LV_REALLOC(d_pslot[l], uint32_t, ncap * REPL_LEVELS);
         LV_REALLOC(d_gtab[l], uint4, gtab_size);
         LV_REALLOC(d_gbase[l], uint32_t, (size_t)gtab_size * GROUP_TARGETS);
         LV_REALLOC(d_gslot[l], uint32_t, (size_t)gtab_size * GROUP_TARGETS);
         LV_REALLOC(d_gdst[l], uint4, (size_t)gtab_size * GROUP_TARGETS);
     }
-    LV_REALLOC(d_prank, uint32_t, ncap * REPL_LEVELS);
-    LV_REALLOC(d_pslot, uint32_t, ncap * REPL_LEVELS);
-    if (!d_gcnt) LV_HIP(hipMalloc(&d_gcnt, 4 * LIST_SHARDS * sizeof(uint32_t)));
+    if (!d_gcnt) LV_HIP(hipMalloc(&d_gcnt, BUCKET_LEVELS * 4 * LIST_SHARDS * sizeof(uint32_t)));
     reloc_cap = (uint32_t)(ncap * 27 > 0x0FFFFFF0ull ? 0x0FFFFFF0ull : ncap * 27);
-    LV_REALLOC(d_reloc, uint4, reloc_cap);
+    for (int l = 0; l < BUCKET_LEVELS; ++l) LV_REALLOC(d_reloc[l], uint4, reloc_cap);
     // a batch of k points breaks up at most 27 k groups (one per target bucket), in practice a few per cent of k: more than this
     // raises `overflow` and the map is re-linearised
     broken_cap = (uint32_t)(ncap * 2 < 16384 ? 16384 : ncap * 2);   // (sharded 64 ways by table slot: room for an uneven spread)
@@ -1020,9 +1033,11 @@ int MapStore::reserve_batch(size_t k) {
     // run that finds it full moves instead)
     comp_cap = reloc_cap < (1u << 18) ? reloc_cap : (1u << 18);
     cstage_cap = (uint32_t)(ncap * 32 < (1u << 20) ? (1u << 20) : ncap * 32);
-    LV_REALLOC(d_comp, uint4, comp_cap);
-    LV_REALLOC(d_cstage, float4, cstage_cap);
-    LV_REALLOC(d_cnew, uint32_t, cstage_cap);
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
+        LV_REALLOC(d_comp[l], uint4, comp_cap);
+        LV_REALLOC(d_cstage[l], float4, cstage_cap);
+        LV_REALLOC(d_cnew[l], uint32_t, cstage_cap);
+    }
     if (d_ntmp) hipFree(d_ntmp);
     d_ntmp = nullptr;
     size_t a = 0, b = 0;
@@ -1123,7 +1138,8 @@ int MapStore::relinearise(hipStream_t stream) {
 int MapStore::kill_dead_list(hipStream_t stream, uint32_t n_dead) {
     if (n_dead == 0) return LV_OK;
     const uint64_t threads = (uint64_t)n_dead * INC_SLOTS_PER_POINT;
-    hipLaunchKernelGGL(inc_kill_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, rw(), d_dead, n_dead);
+    for (int inst = 0; inst < BUCKET_LEVELS; ++inst)
+        hipLaunchKernelGGL(inc_kill_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, stream, rw(inst), d_dead, n_dead);
     LV_HIP(hipGetLastError());
     return LV_OK;
 }
@@ -1151,7 +1167,7 @@ __global__ __launch_bounds__(1024) void inc_sort_small_kernel(const uint64_t* __
 // scan of the survivors -> ids / orig / box chains -> voxel groups.  Seven launches (two of them library calls) of a few
 // microseconds of work each otherwise; the stages are the *_item functions of lv_mapinc.hpp, separated by workgroup barriers
 // (one workgroup: a barrier also orders its global-memory traffic).
-__global__ __launch_bounds__(1024) void inc_small_front_kernel(MapRW M, BoxRW Bx, int have_boxes, GroupRW G, const float4* __restrict__ newp,
+__global__ __launch_bounds__(1024) void inc_small_front_kernel(MapRW M, BoxRW Bx, int have_boxes, GroupRW G, MapRW M1, GroupRW G1, const float4* __restrict__ newp,
                                                                uint32_t k, float len, int downsample, uint32_t* __restrict__ alive,
                                                                uint32_t* __restrict__ apos, float4* __restrict__ dead, uint32_t dead_cap,
                                                                uint32_t id_base) {
@@ -1203,6 +1219,7 @@ __global__ __launch_bounds__(1024) void inc_small_front_kernel(MapRW M, BoxRW Bx
     __syncthreads();
     for (uint32_t j = tid; j < k; j += 1024) inc_commit_points_item(M, Bx, have_boxes, newp, s_alive, s_apos, k, id_base, j);
     for (uint32_t t = tid; t < k * (uint32_t)REPL_LEVELS; t += 1024) inc_group_item(M, G, newp, s_alive, k, t);
+    for (uint32_t t = tid; t < k * (uint32_t)REPL_LEVELS; t += 1024) inc_group_item(M1, G1, newp, s_alive, k, t);   // (the level-1 instance's voxel groups)
 }
 
 // ---- the back half of a small batch's insert in four launches instead of eight ---------------------------------------------------
@@ -1212,25 +1229,93 @@ __global__ __launch_bounds__(1024) void inc_small_front_kernel(MapRW M, BoxRW Bx
 // the listed runs move (relocate: entries [0, count) of a run) while the new entries go to the tails behind them (fill); the
 // owners close their targets (commit: table counts, pending) while the new bucket entries go to their ranked places (place:
 // coordinates and ids inside the tail).  reserve and rank need everything before them: own launches.
-__global__ __launch_bounds__(256) void inc_kill_register_kernel(MapRW M, GroupRW G, const uint32_t* __restrict__ alive, uint32_t k,
-                                                                const float4* __restrict__ dead, uint32_t dead_cap, uint32_t g_kill) {
-    if (blockIdx.x < g_kill) inc_kill_counted_item(M, dead, dead_cap, blockIdx.x * blockDim.x + threadIdx.x, g_kill * blockDim.x);
-    else LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, g_kill, gridDim.x - g_kill, inc_register_item(M, G, alive, k, t));
+// ... and BOTH instances of the machinery (level-0 buckets + lists + groups, level-1 buckets: MapStore::rw) share every one of
+// these launches: a stage's workgroups come as [instance 0 | instance 1], each instance with its own tables, work lists and scratch.
+struct IncInst {
+    MapRW M;
+    GroupRW G;
+    uint4* reloc;
+    uint32_t* gcnt;    // [0, 64) cursors of the runs that move (the other cursors: M.n_broken, M.n_comp)
+    uint32_t* rank;
+};
+struct IncBoth {
+    IncInst i[BUCKET_LEVELS];
+};
+// workgroup blockIdx.x of a stage that starts at workgroup `first` with g workgroups per instance -> its instance
+__device__ __forceinline__ uint32_t inc_inst_of(uint32_t first, uint32_t g) { return blockIdx.x - first >= g ? 1u : 0u; }
+
+__global__ __launch_bounds__(256) void inc_group_both_kernel(IncBoth Bo, const float4* __restrict__ newp, const uint32_t* __restrict__ alive, uint32_t k, uint32_t g) {
+    const uint32_t in = inc_inst_of(0u, g);
+    const IncInst& I = Bo.i[in];
+    inc_group_item(I.M, I.G, newp, alive, k, inc_block_of(blockIdx.x - in * g, g) * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void inc_kill_register_kernel(IncBoth Bo, const uint32_t* __restrict__ alive, uint32_t k,
+                                                                const float4* __restrict__ dead, uint32_t dead_cap, uint32_t g_kill, uint32_t g_grp) {
+    if (blockIdx.x < 2u * g_kill) {
+        const uint32_t in = inc_inst_of(0u, g_kill);
+        inc_kill_counted_item(Bo.i[in].M, dead, dead_cap, (blockIdx.x - in * g_kill) * blockDim.x + threadIdx.x, g_kill * blockDim.x);
+    } else {
+        const uint32_t in = inc_inst_of(2u * g_kill, g_grp);
+        const MapRW& M = Bo.i[in].M;
+        const GroupRW& G = Bo.i[in].G;
+        LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, 2u * g_kill + in * g_grp, g_grp, inc_register_item(M, G, alive, k, t));
+    }
+}
+__global__ __launch_bounds__(256) void inc_reserve_both_kernel(IncBoth Bo, const uint32_t* __restrict__ alive, uint32_t k, uint32_t reloc_cap, uint32_t g_grp) {
+    const uint32_t in = inc_inst_of(0u, g_grp);
+    const MapRW& M = Bo.i[in].M;
+    const GroupRW& G = Bo.i[in].G;
+    LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, in * g_grp, g_grp, inc_reserve_item(M, G, alive, k, Bo.i[in].reloc, reloc_cap, Bo.i[in].gcnt, t));
+}
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void inc_compact_both_kernel(IncBoth Bo, uint32_t g) {
+    const uint32_t in = inc_inst_of(0u, g);
+    const uint32_t t = (blockIdx.x - in * g) * blockDim.x + threadIdx.x;
+    if (SCATTER) inc_compact_scatter_item(Bo.i[in].M, t, g * blockDim.x);
+    else inc_compact_gather_item(Bo.i[in].M, t, g * blockDim.x);
 }
 // (round 4: the listed runs move while every (group, target) notes where its target's batch tail lies — inc_resolve — and the new
 // entries go to the tails in a launch of their own behind it)
 template <int LANES>
-__global__ __launch_bounds__(256) void inc_relocate_resolve_kernel(MapRW M, GroupRW G, const uint32_t* __restrict__ alive, uint32_t k,
-                                                                   const uint4* __restrict__ reloc, uint32_t reloc_cap,
-                                                                   const uint32_t* __restrict__ n_reloc, uint32_t g_rel) {
-    if (blockIdx.x < g_rel) inc_relocate_item<LANES>(M, reloc, reloc_cap, n_reloc, blockIdx.x * blockDim.x + threadIdx.x, g_rel * blockDim.x);
-    else LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, g_rel, gridDim.x - g_rel, inc_resolve_item(M, G, alive, k, t));
+__global__ __launch_bounds__(256) void inc_relocate_resolve_kernel(IncBoth Bo, const uint32_t* __restrict__ alive, uint32_t k, uint32_t reloc_cap,
+                                                                   uint32_t g_rel, uint32_t g_grp) {
+    if (blockIdx.x < 2u * g_rel) {
+        const uint32_t in = inc_inst_of(0u, g_rel);
+        inc_relocate_item<LANES>(Bo.i[in].M, Bo.i[in].reloc, reloc_cap, Bo.i[in].gcnt, (blockIdx.x - in * g_rel) * blockDim.x + threadIdx.x, g_rel * blockDim.x);
+    } else {
+        const uint32_t in = inc_inst_of(2u * g_rel, g_grp);
+        const MapRW& M = Bo.i[in].M;
+        const GroupRW& G = Bo.i[in].G;
+        LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, 2u * g_rel + in * g_grp, g_grp, inc_resolve_item(M, G, alive, k, t));
+    }
 }
-__global__ __launch_bounds__(256) void inc_place_commit_kernel(MapRW M, GroupRW G, const float4* __restrict__ newp,
-                                                               const uint32_t* __restrict__ alive, const uint32_t* __restrict__ apos, uint32_t k,
-                                                               uint32_t id_base, const uint32_t* __restrict__ rank, uint32_t g_place) {
-    if (blockIdx.x < g_place) LV_INC_ITEMS(27 * SORTED_LEVELS, 0u, g_place, inc_place_item(M, G, newp, alive, apos, k, id_base, rank, t))
-    else LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, g_place, gridDim.x - g_place, inc_commit_item(M, G, alive, k, t))
+__global__ __launch_bounds__(256) void inc_fill_both_kernel(IncBoth Bo, const float4* __restrict__ newp, const uint32_t* __restrict__ alive,
+                                                            const uint32_t* __restrict__ apos, uint32_t k, uint32_t id_base, uint32_t g_all) {
+    const uint32_t in = inc_inst_of(0u, g_all);
+    const MapRW& M = Bo.i[in].M;
+    const GroupRW& G = Bo.i[in].G;
+    LV_INC_ITEMS(INC_SLOTS_PER_POINT, in * g_all, g_all, inc_fill_item(M, G, newp, alive, apos, k, id_base, t));
+}
+__global__ __launch_bounds__(256) void inc_rank_both_kernel(IncBoth Bo, const uint32_t* __restrict__ alive, const uint32_t* __restrict__ apos, uint32_t k,
+                                                            uint32_t id_base, uint32_t g_rep) {
+    const uint32_t in = inc_inst_of(0u, g_rep);
+    const MapRW& M = Bo.i[in].M;
+    const GroupRW& G = Bo.i[in].G;
+    LV_INC_ITEMS(27 * SORTED_LEVELS, in * g_rep, g_rep, inc_rank_item(M, G, alive, apos, k, id_base, Bo.i[in].rank, t));
+}
+__global__ __launch_bounds__(256) void inc_place_commit_kernel(IncBoth Bo, const float4* __restrict__ newp, const uint32_t* __restrict__ alive,
+                                                               const uint32_t* __restrict__ apos, uint32_t k, uint32_t id_base, uint32_t g_place, uint32_t g_grp) {
+    if (blockIdx.x < 2u * g_place) {
+        const uint32_t in = inc_inst_of(0u, g_place);
+        const MapRW& M = Bo.i[in].M;
+        const GroupRW& G = Bo.i[in].G;
+        LV_INC_ITEMS(27 * SORTED_LEVELS, in * g_place, g_place, inc_place_item(M, G, newp, alive, apos, k, id_base, Bo.i[in].rank, t))
+    } else {
+        const uint32_t in = inc_inst_of(2u * g_place, g_grp);
+        const MapRW& M = Bo.i[in].M;
+        const GroupRW& G = Bo.i[in].G;
+        LV_INC_ITEMS(REPL_LEVELS * GROUP_TARGETS, 2u * g_place + in * g_grp, g_grp, inc_commit_item(M, G, alive, k, t))
+    }
 }
 
 // ---- lv_map_evict_box without a per-point search ---------------------------------------------------------------------------------
@@ -1265,10 +1350,11 @@ __global__ __launch_bounds__(256) void inc_evict_mark_kernel(float4* __restrict_
 __global__ __launch_bounds__(256) void inc_evict_sweep_kernel(MapRW M, int ti, float lx, float ly, float lz, float hx, float hy, float hz,
                                                               int keep_inside) {
     const LevelRW& L = M.lv[ti];
+    if (!L.table) return;
     const uint32_t n_slots = L.mask + 1u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const int lvl = ti == CELL_SLOT ? CELL_LEVEL : ti;
+    const int lvl = ti == CELL_SLOT ? CELL_LEVEL : ti + M.level;
     const int reach = ti == CELL_SLOT ? 0 : 1;
     const float cell = 1.0f / M.inv_cell;
     const float blo[3] = {lx, ly, lz}, bhi[3] = {hx, hy, hz};
@@ -1295,7 +1381,7 @@ __global__ __launch_bounds__(256) void inc_evict_sweep_kernel(MapRW M, int ti, f
         if (action == 1) {
             L.table[slot].w = 0u;
             L.aux[slot].dead = 0u;   // (an empty run carries no tombstones)
-            if (ti < REPL_LEVELS) inc_break_group(M, key);   // (the entries stay as they are: the group's region is no longer a valid candidate array)
+            if (ti < REPL_LEVELS && M.level == 0) inc_break_group(M, key);   // (instance 0: level-0 runs tile the groups; the entries stay as they are: the group's region is no longer a valid candidate array)
         }
         unsigned long long cut = __ballot(action == 2);
         while (cut) {
@@ -1332,37 +1418,43 @@ __global__ void inc_post_counters_kernel(const MapCounters* __restrict__ cnt, un
     note_post(note + 0, seq, cnt->n_new);
     note_post(note + 1, seq, cnt->n_dead);
     note_post(note + 2, seq, cnt->dropped);
-    note_post(note + 3, seq, cnt->overflow);
-    // what is left of the bucket pool's free part (entries): the host starts a re-linearisation BEFORE a batch runs out of room
-    uint32_t left = 0;
-    for (int a = 0; a < N_ARENAS; ++a) {
-        const uint32_t cur = cnt->arena_cur[0][a], end = cnt->arena_end[0][a];
-        left += cur < end ? end - cur : 0u;
+    note_post(note + 3, seq, cnt[0].overflow | cnt[1].overflow);
+    // what is left of the bucket pools' free parts (entries): the host starts a re-linearisation BEFORE a batch runs out of room
+    for (int l = 0; l < BUCKET_LEVELS; ++l) {
+        uint32_t left = 0;
+        for (int a = 0; a < N_ARENAS; ++a) {
+            const uint32_t cur = cnt[l].arena_cur[0][a], end = cnt[l].arena_end[0][a];
+            left += cur < end ? end - cur : 0u;
+        }
+        note_post(note + 4 + l, seq, left);
     }
-    note_post(note + 4, seq, left);
 }
 
 // the scratch tables of a batch back to empty (0xFF) and its group counters to zero: one launch instead of four fills
-__global__ void inc_clear_groups_kernel(GroupRW G, uint32_t* __restrict__ gcnt, MapCounters* __restrict__ cnt) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < 4u * LIST_SHARDS) gcnt[t] = 0u;   // (the sharded cursors of the batch's work lists: runs that move, groups broken up, runs compacted, their staging area)
-    if (t == 0u && cnt) { cnt->n_new = 0u; cnt->n_dead = 0u; cnt->overflow = 0u; cnt->dropped = 0u; }   // (reset_batch_counters)
+__global__ void inc_clear_groups_kernel(IncBoth Bo, int reset_counters, uint32_t g) {
+    const uint32_t in = inc_inst_of(0u, g);
+    const GroupRW& G = Bo.i[in].G;
+    const uint32_t t = (blockIdx.x - in * g) * blockDim.x + threadIdx.x;
+    if (t < 4u * LIST_SHARDS) Bo.i[in].gcnt[t] = 0u;   // (the sharded cursors of the instance's work lists: runs that move, groups broken up, runs compacted, their staging area)
+    MapCounters* cnt = Bo.i[in].M.cnt;
+    if (t == 0u && reset_counters) { cnt->n_new = 0u; cnt->n_dead = 0u; cnt->overflow = 0u; cnt->dropped = 0u; }   // (reset_batch_counters)
     const uint32_t l = t / G.size, e = t % G.size;
     if (l < (uint32_t)REPL_LEVELS) G.table[l][e] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
 }
 
 static int reset_batch_counters(MapStore& S, hipStream_t stream) {
     // n_new .. dropped are contiguous (MapCounters)
-    LV_HIP(hipMemsetAsync(&S.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
+    for (int l = 0; l < BUCKET_LEVELS; ++l)
+        LV_HIP(hipMemsetAsync(&S.d_cnt[l].n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
     return LV_OK;
 }
 
 int MapStore::ensure_counters() {
     if (d_cnt) return LV_OK;
-    LV_HIP(hipMalloc(&d_cnt, sizeof(MapCounters)));
-    LV_HIP(hipHostMalloc((void**)&h_cnt, sizeof(MapCounters), hipHostMallocDefault));
-    std::memset(h_cnt, 0, sizeof(MapCounters));
-    LV_HIP(hipMemset(d_cnt, 0, sizeof(MapCounters)));
+    LV_HIP(hipMalloc(&d_cnt, BUCKET_LEVELS * sizeof(MapCounters)));
+    LV_HIP(hipHostMalloc((void**)&h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipHostMallocDefault));
+    std::memset(h_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters));
+    LV_HIP(hipMemset(d_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters)));
     return LV_OK;
 }
 
@@ -1443,16 +1535,27 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
         rc = reset_batch_counters(*this, stream);
         if (rc) return rc;
     }
-    MapRW M = rw();
-    M.broken = d_broken;
-    M.broken_cap = broken_cap;
-    M.n_broken = d_gcnt + LIST_SHARDS;   // (zeroed with the batch's other counters: inc_clear_groups_kernel)
-    M.comp = d_comp;
-    M.comp_cap = comp_cap;
-    M.n_comp = d_gcnt + 2 * LIST_SHARDS;   // (+ the staging cursors behind them)
-    M.cstage = d_cstage;
-    M.cnew = d_cnew;
-    M.cstage_cap = cstage_cap;
+    // the two instances of the insert machinery (MapStore::rw) with their work lists and scratch
+    IncBoth Bo{};
+    for (int in = 0; in < BUCKET_LEVELS; ++in) {
+        IncInst& I = Bo.i[in];
+        I.gcnt = d_gcnt + (size_t)in * 4 * LIST_SHARDS;   // (zeroed with the batch's other counters: inc_clear_groups_kernel)
+        I.reloc = d_reloc[in];
+        I.rank = d_rank[in];
+        I.M = rw(in);
+        if (in == 0) {   // (only level-0 runs tile groups)
+            I.M.broken = d_broken;
+            I.M.broken_cap = broken_cap;
+            I.M.n_broken = I.gcnt + LIST_SHARDS;
+        }
+        I.M.comp = d_comp[in];
+        I.M.comp_cap = comp_cap;
+        I.M.n_comp = I.gcnt + 2 * LIST_SHARDS;   // (+ the staging cursors behind them)
+        I.M.cstage = d_cstage[in];
+        I.M.cnew = d_cnew[in];
+        I.M.cstage_cap = cstage_cap;
+    }
+    const MapRW& M = Bo.i[0].M;
     BoxRW Bx{};
     if (downsample) {
         rc = ensure_boxes(stream, box_length);
@@ -1463,28 +1566,31 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     const int B = 256;
     const uint32_t gk = (k + B - 1) / B;
     // voxel-group tables of the batch (cleared first: the small batch's front kernel fills them)
-    GroupRW G{};
-    for (int l = 0; l < REPL_LEVELS; ++l) {
-        G.table[l] = d_gtab[l];
-        G.gbase[l] = d_gbase[l];
-        G.gslot[l] = d_gslot[l];
-        G.gdst[l] = d_gdst[l];
-    }
-    G.mask = gtab_size - 1;
-    G.shift = (uint32_t)(64 - log2u(gtab_size));
-    G.size = gtab_size;
-    G.prank = d_prank;
-    G.pslot = d_pslot;
-    // large down-sampling batches walk their survivors in the order of the box sort (Morton): see inc_box_key
     const bool listed = downsample && !(small_front && k <= (uint32_t)SMALL_BATCH) && k > (uint32_t)SMALL_BATCH && surv_list;
-    G.surv = listed ? d_nsurv : nullptr;
-    G.n_live = &d_cnt->n_new;
-    hipLaunchKernelGGL(inc_clear_groups_kernel, dim3((uint32_t)(((uint64_t)gtab_size * REPL_LEVELS + B - 1) / B)), dim3(B), 0, stream, G,
-                       d_gcnt, reset_early ? nullptr : d_cnt);
+    for (int in = 0; in < BUCKET_LEVELS; ++in) {
+        GroupRW& Gi = Bo.i[in].G;
+        Gi.table[0] = d_gtab[in];
+        Gi.gbase[0] = d_gbase[in];
+        Gi.gslot[0] = d_gslot[in];
+        Gi.gdst[0] = d_gdst[in];
+        Gi.mask = gtab_size - 1;
+        Gi.shift = (uint32_t)(64 - log2u(gtab_size));
+        Gi.size = gtab_size;
+        Gi.prank = d_prank[in];
+        Gi.pslot = d_pslot[in];
+        // large down-sampling batches walk their survivors in the order of the box sort (Morton): see inc_box_key
+        Gi.surv = listed ? d_nsurv : nullptr;
+        Gi.n_live = &d_cnt->n_new;
+    }
+    static_assert(REPL_LEVELS == 1, "one replicated level per instance");
+    const GroupRW& G = Bo.i[0].G;
+    {
+        const uint32_t g_clr = (uint32_t)(((uint64_t)gtab_size * REPL_LEVELS + B - 1) / B);
+        hipLaunchKernelGGL(inc_clear_groups_kernel, dim3(2u * g_clr), dim3(B), 0, stream, Bo, reset_early ? 0 : 1, g_clr);
+    }
     const bool fused_front = small_front && k <= (uint32_t)SMALL_BATCH;
-    uint32_t n_dead = 0;
     if (fused_front) {
-        hipLaunchKernelGGL(inc_small_front_kernel, dim3(1), dim3(1024), 0, stream, M, Bx, have_boxes ? 1 : 0, G, d_new, k, box_length,
+        hipLaunchKernelGGL(inc_small_front_kernel, dim3(1), dim3(1024), 0, stream, M, Bx, have_boxes ? 1 : 0, G, Bo.i[1].M, Bo.i[1].G, d_new, k, box_length,
                            downsample, d_nalive, d_napos, d_dead, (uint32_t)dead_cap, n_ids);
     } else {
     hipLaunchKernelGGL(inc_box_keys_kernel, dim3(gk), dim3(B), 0, stream, M, d_new, k, box_length, d_nkeys, d_nidx, d_nalive, downsample, 1);
@@ -1511,32 +1617,17 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
         LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp, tmp, d_nsflag, d_nspos, (int)k, stream));
         hipLaunchKernelGGL(inc_surv_list_kernel, dim3(gk), dim3(B), 0, stream, d_nidx_sorted, d_nsflag, d_nspos, k, d_nsurv);
     }
-    // voxel groups of the survivors on every level
-    hipLaunchKernelGGL(inc_group_kernel, dim3((uint32_t)(((uint64_t)k * REPL_LEVELS + B - 1) / B)), dim3(B), 0, stream, M, G, d_new,
-                       d_nalive, k);
+    // voxel groups of the survivors, for both instances
+    {
+        const uint32_t g_g = (uint32_t)(((uint64_t)k * REPL_LEVELS + B - 1) / B);
+        hipLaunchKernelGGL(inc_group_both_kernel, dim3(2u * g_g), dim3(B), 0, stream, Bo, d_new, d_nalive, k, g_g);
+    }
     }   // !fused_front
     // (round 6: every batch leaves the length of its dead list on the device — the tombstone pass walks it in strides beside the
     // registration pass — instead of fetching it in the middle of the insert: one host round trip and one launch less per insert;
     // the append passes then cover every point of the batch, the ones that did not survive leaving at once)
     const bool counted_kill = downsample != 0;
-    if (!counted_kill && downsample) {
-        // the counters of the front half (survivors, occupants that lost) size the launches that follow: fetched as a NOTE (a
-        // one-thread kernel posts them into pinned memory, the host polls: lv_note.hpp) instead of a copy + stream synchronise,
-        // whose wake-up leaves the device idle for ~30 us in the middle of the insert (round 4)
-        LV_HIP(note_alloc(notes));
-        const uint32_t mid_seq = notes.next();
-        hipLaunchKernelGGL(inc_post_counters_kernel, dim3(1), dim3(64), 0, stream, d_cnt, notes.d, mid_seq);
-        LV_HIP(hipGetLastError());
-        uint32_t mv[4] = {0, 0, 0, 0};   // n_new, n_dead, dropped, overflow
-        if (!note_wait(notes, 0, 4, mid_seq, mv, stream)) { set_error("map insert: the front half's counters never arrived"); return LV_EHIP; }
-        h_cnt->n_new = mv[0];
-        h_cnt->n_dead = mv[1];
-        n_dead = h_cnt->n_dead < dead_cap ? h_cnt->n_dead : (uint32_t)dead_cap;
-        rc = kill_dead_list(stream, n_dead);
-        if (rc) return rc;
-    }
-    // work items of the append passes: with a survivor list (and the counters just read) one per SURVIVOR and slot, else one per
-    // point of the batch and slot (the dead leave at once)
+    const uint32_t n_dead = 0;
     // grids of the per-survivor passes: an ESTIMATE of the survivors — half again what the previous batch left — where the batch
     // walks a survivor list (the kernels cover whatever lies beyond their grid in strides: LV_INC_ITEMS), else every point
     uint64_t kk = (uint64_t)k;
@@ -1548,42 +1639,46 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     const uint64_t t_all = kk * INC_SLOTS_PER_POINT, t_rep = kk * 27 * SORTED_LEVELS;
     const uint32_t g_grp = (uint32_t)((t_grp + B - 1) / B), g_all = (uint32_t)((t_all + B - 1) / B), g_rep = (uint32_t)((t_rep + B - 1) / B);
     const uint64_t t_rel = (uint64_t)(reloc_cap < (1u << 18) ? reloc_cap : (1u << 18)) * RELOC_LANES;   // runs moved per batch (more: re-linearise)
+    const uint32_t rel_cap = (uint32_t)(t_rel / RELOC_LANES);
     // at most one run per (group, target) of this batch can be listed; 2048 workgroups walk longer lists in strides
     const uint64_t t_need = t_grp * RELOC_LANES < t_rel ? t_grp * RELOC_LANES : t_rel;
     const uint64_t g_need = (t_need + B - 1) / B;
     const uint32_t g_rel = ((uint32_t)(g_need < 2048 ? g_need : 2048) + 15u) & ~15u;   // (a multiple of 16 workgroups: 64 x n runs at a time, one per list shard)
     const uint32_t g_cmp = k <= (uint32_t)SMALL_BATCH ? 64u : 1024u;   // in-place compactions: how many is only known on the device (grid-stride)
-    if (merged_back) {   // (see inc_kill_register_kernel)
-        const uint32_t g_kill = counted_kill ? (k <= (uint32_t)SMALL_BATCH ? 256u : 2048u) : 0u;   // the occupants that lost: how many is only known on the device
-        hipLaunchKernelGGL(inc_kill_register_kernel, dim3(g_kill + g_grp), dim3(B), 0, stream, M, G, d_nalive, k, d_dead, (uint32_t)dead_cap, g_kill);
-        hipLaunchKernelGGL(inc_reserve_kernel, dim3(g_grp), dim3(B), 0, stream, M, G, d_nalive, k, d_reloc, (uint32_t)(t_rel / RELOC_LANES), d_gcnt);
+    const uint32_t g_kill = counted_kill ? (k <= (uint32_t)SMALL_BATCH ? 256u : 2048u) : 0u;   // the occupants that lost: how many is only known on the device
+    if (merged_back) {   // (see inc_kill_register_kernel: every launch serves both instances)
+        hipLaunchKernelGGL(inc_kill_register_kernel, dim3(2u * (g_kill + g_grp)), dim3(B), 0, stream, Bo, d_nalive, k, d_dead, (uint32_t)dead_cap, g_kill, g_grp);
+        hipLaunchKernelGGL(inc_reserve_both_kernel, dim3(2u * g_grp), dim3(B), 0, stream, Bo, d_nalive, k, rel_cap, g_grp);
         // runs that only their deleted entries made too long are compacted where they lie: staged here, written back below
-        hipLaunchKernelGGL(inc_compact_gather_kernel, dim3(g_cmp), dim3(B), 0, stream, M);
+        hipLaunchKernelGGL(inc_compact_both_kernel<false>, dim3(2u * g_cmp), dim3(B), 0, stream, Bo, g_cmp);
         if (k <= (uint32_t)SMALL_BATCH)   // few runs move: a workgroup each
-            hipLaunchKernelGGL(inc_relocate_resolve_kernel<RELOC_LANES_SMALL>, dim3(g_rel + g_grp), dim3(B), 0, stream, M, G, d_nalive, k, d_reloc,
-                               (uint32_t)(t_rel / RELOC_LANES), d_gcnt, g_rel);
+            hipLaunchKernelGGL(inc_relocate_resolve_kernel<RELOC_LANES_SMALL>, dim3(2u * (g_rel + g_grp)), dim3(B), 0, stream, Bo, d_nalive, k, rel_cap, g_rel, g_grp);
         else
-            hipLaunchKernelGGL(inc_relocate_resolve_kernel<RELOC_LANES>, dim3(g_rel + g_grp), dim3(B), 0, stream, M, G, d_nalive, k, d_reloc,
-                               (uint32_t)(t_rel / RELOC_LANES), d_gcnt, g_rel);
-        hipLaunchKernelGGL(inc_compact_scatter_kernel, dim3(g_cmp), dim3(B), 0, stream, M);
-        hipLaunchKernelGGL(inc_fill_kernel, dim3(g_all), dim3(B), 0, stream, M, G, d_new, d_nalive, d_napos, k, n_ids);
-        hipLaunchKernelGGL(inc_rank_kernel, dim3(g_rep), dim3(B), 0, stream, M, G, d_nalive, d_napos, k, n_ids, d_rank);
-        hipLaunchKernelGGL(inc_place_commit_kernel, dim3(g_rep + g_grp), dim3(B), 0, stream, M, G, d_new, d_nalive, d_napos, k, n_ids, d_rank, g_rep);
-    } else {
-    if (counted_kill) hipLaunchKernelGGL(inc_kill_counted_kernel, dim3(k <= (uint32_t)SMALL_BATCH ? 256 : 2048), dim3(B), 0, stream, M, d_dead, (uint32_t)dead_cap);
-    hipLaunchKernelGGL(inc_register_kernel, dim3(g_grp), dim3(B), 0, stream, M, G, d_nalive, k);
-    hipLaunchKernelGGL(inc_reserve_kernel, dim3(g_grp), dim3(B), 0, stream, M, G, d_nalive, k, d_reloc, (uint32_t)(t_rel / RELOC_LANES), d_gcnt);
-    hipLaunchKernelGGL(inc_compact_gather_kernel, dim3(g_cmp), dim3(B), 0, stream, M);
-    hipLaunchKernelGGL(inc_relocate_kernel, dim3(g_rel), dim3(B), 0, stream, M, d_reloc, (uint32_t)(t_rel / RELOC_LANES), d_gcnt);
-    hipLaunchKernelGGL(inc_resolve_kernel, dim3(g_grp), dim3(B), 0, stream, M, G, d_nalive, k);
-    hipLaunchKernelGGL(inc_compact_scatter_kernel, dim3(g_cmp), dim3(B), 0, stream, M);
-    hipLaunchKernelGGL(inc_fill_kernel, dim3(g_all), dim3(B), 0, stream, M, G, d_new, d_nalive, d_napos, k, n_ids);
-    hipLaunchKernelGGL(inc_rank_kernel, dim3(g_rep), dim3(B), 0, stream, M, G, d_nalive, d_napos, k, n_ids, d_rank);
-    hipLaunchKernelGGL(inc_place_kernel, dim3(g_rep), dim3(B), 0, stream, M, G, d_new, d_nalive, d_napos, k, n_ids, d_rank);
-    hipLaunchKernelGGL(inc_commit_kernel, dim3(g_grp), dim3(B), 0, stream, M, G, d_nalive, k);
+            hipLaunchKernelGGL(inc_relocate_resolve_kernel<RELOC_LANES>, dim3(2u * (g_rel + g_grp)), dim3(B), 0, stream, Bo, d_nalive, k, rel_cap, g_rel, g_grp);
+        hipLaunchKernelGGL(inc_compact_both_kernel<true>, dim3(2u * g_cmp), dim3(B), 0, stream, Bo, g_cmp);
+        hipLaunchKernelGGL(inc_fill_both_kernel, dim3(2u * g_all), dim3(B), 0, stream, Bo, d_new, d_nalive, d_napos, k, n_ids, g_all);
+        hipLaunchKernelGGL(inc_rank_both_kernel, dim3(2u * g_rep), dim3(B), 0, stream, Bo, d_nalive, d_napos, k, n_ids, g_rep);
+        hipLaunchKernelGGL(inc_place_commit_kernel, dim3(2u * (g_rep + g_grp)), dim3(B), 0, stream, Bo, d_new, d_nalive, d_napos, k, n_ids, g_rep, g_grp);
+    } else {   // (LV_MERGED_INSERT=0: the stand-alone kernels, one instance after the other)
+    for (int in = 0; in < BUCKET_LEVELS; ++in) {
+    const MapRW& Mi = Bo.i[in].M;
+    const GroupRW& Gi = Bo.i[in].G;
+    if (counted_kill) hipLaunchKernelGGL(inc_kill_counted_kernel, dim3(g_kill), dim3(B), 0, stream, Mi, d_dead, (uint32_t)dead_cap);
+    hipLaunchKernelGGL(inc_register_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k);
+    hipLaunchKernelGGL(inc_reserve_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k, Bo.i[in].reloc, rel_cap, Bo.i[in].gcnt);
+    hipLaunchKernelGGL(inc_compact_gather_kernel, dim3(g_cmp), dim3(B), 0, stream, Mi);
+    hipLaunchKernelGGL(inc_relocate_kernel, dim3(g_rel), dim3(B), 0, stream, Mi, Bo.i[in].reloc, rel_cap, Bo.i[in].gcnt);
+    hipLaunchKernelGGL(inc_resolve_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k);
+    hipLaunchKernelGGL(inc_compact_scatter_kernel, dim3(g_cmp), dim3(B), 0, stream, Mi);
+    hipLaunchKernelGGL(inc_fill_kernel, dim3(g_all), dim3(B), 0, stream, Mi, Gi, d_new, d_nalive, d_napos, k, n_ids);
+    hipLaunchKernelGGL(inc_rank_kernel, dim3(g_rep), dim3(B), 0, stream, Mi, Gi, d_nalive, d_napos, k, n_ids, Bo.i[in].rank);
+    hipLaunchKernelGGL(inc_place_kernel, dim3(g_rep), dim3(B), 0, stream, Mi, Gi, d_new, d_nalive, d_napos, k, n_ids, Bo.i[in].rank);
+    hipLaunchKernelGGL(inc_commit_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k);
     }
-    // the tile groups this batch broke up (a run outgrew its room, a bucket appeared) are laid out again: level 1 streams a group's
-    // region as one candidate array (bucket_attempt, lv_match.hip); three small launches that find nothing to do in most batches
+    }
+    // the tile groups this batch broke up (a level-0 run outgrew its room, a level-0 bucket appeared) are laid out again for the map
+    // queries and the surface pass, which stream a group's region as one candidate array; three small launches that find nothing to
+    // do in most batches
     hipLaunchKernelGGL(inc_regroup_plan_kernel, dim3(64), dim3(B), 0, stream, M, d_regroup);
     hipLaunchKernelGGL(inc_regroup_move_kernel, dim3(512), dim3(B), 0, stream, M, (const RegroupPlan*)d_regroup);
     hipLaunchKernelGGL(inc_regroup_commit_kernel, dim3(64), dim3(B), 0, stream, M, (const RegroupPlan*)d_regroup);
@@ -1607,12 +1702,14 @@ int MapStore::settle(hipStream_t stream) {
     // (the note is posted by the last kernel of the insert's chain, on the stream the chain ran on — the context's side stream
     // when the insert overlaps the next cycle's prediction and window: once it has arrived the whole insert has completed, so
     // whatever the caller enqueues next, on any stream, sees the finished map)
-    uint32_t v[5] = {0, 0, 0, 0, 0};   // n_new, n_dead, dropped, overflow, free entries left in the bucket pool
-    if (!note_wait(notes, 0, 5, counters_seq, v, counters_stream)) { set_error("map insert: the counters never arrived"); return LV_EHIP; }
+    uint32_t v[4 + BUCKET_LEVELS] = {};   // n_new, n_dead, dropped, overflow, free entries left in the bucket pools
+    if (!note_wait(notes, 0, 4 + BUCKET_LEVELS, counters_seq, v, counters_stream)) { set_error("map insert: the counters never arrived"); return LV_EHIP; }
     // three quarters of the pool's free part are gone (runs that moved, groups laid out again, newly mapped space): ask for a
     // re-linearisation now — in the background for a large map (lv_rebuild.hpp MapRebuild::maybe_start) — instead of meeting `overflow`
     // in the middle of a later batch, which costs that batch's work and a stop-the-world rebuild
-    pool_low = (uint64_t)v[4] * 4 < (uint64_t)(pool_cap[0] > pool_base[0] ? pool_cap[0] - pool_base[0] : 0);
+    pool_low = false;
+    for (int l = 0; l < BUCKET_LEVELS; ++l)
+        pool_low = pool_low || (uint64_t)v[4 + l] * 4 < (uint64_t)(pool_cap[l] > pool_base[l] ? pool_cap[l] - pool_base[l] : 0);
     uint32_t n_dead = pending_n_dead;
     if (pending_counted_kill) n_dead = v[1] < dead_cap ? v[1] : (uint32_t)dead_cap;
     n_ids += v[0];
@@ -1620,7 +1717,7 @@ int MapStore::settle(hipStream_t stream) {
     last_new = v[0];
     have_last_new = true;
     m -= n_dead;
-    tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
+    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
     dropped_total += v[2];
     ++incremental_adds;
     refresh_view();
@@ -1639,8 +1736,9 @@ int MapStore::evict_box(hipStream_t stream, const float lo[3], const float hi[3]
         const uint32_t g_mark = (n_ids + 255) / 256;
         hipLaunchKernelGGL(inc_evict_mark_kernel, dim3(g_mark < 2048u ? g_mark : 2048u), dim3(256), 0, stream, d_orig, n_ids, lo[0], lo[1], lo[2], hi[0],
                            hi[1], hi[2], keep_inside, d_cnt);
-        const MapRW M = rw();
-        for (int ti = 0; ti < INC_LEVELS; ++ti) {
+        for (int inst = 0; inst < BUCKET_LEVELS; ++inst)
+        for (int ti = 0; ti < (inst == 0 ? INC_LEVELS : REPL_LEVELS); ++ti) {
+            const MapRW M = rw(inst);
             const uint64_t slots = (uint64_t)M.lv[ti].mask + 1u;
             const uint64_t wgs = (slots + 255) / 256;   // 64 slots per wavefront step, four wavefronts per workgroup
             hipLaunchKernelGGL(inc_evict_sweep_kernel, dim3((uint32_t)(wgs < 4096 ? wgs : 4096)), dim3(256), 0, stream, M, ti, lo[0], lo[1], lo[2],
@@ -1662,7 +1760,7 @@ int MapStore::evict_box(hipStream_t stream, const float lo[3], const float hi[3]
         LV_HIP(hipStreamSynchronize(stream));
     }
     m -= n_dead;
-    tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
+    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
     if (n_evicted) *n_evicted = n_dead;
     refresh_view();
     if (m == 0) { n_ids = 0; return rebuild(stream); }
@@ -1692,7 +1790,7 @@ int MapStore::evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_ev
     LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));
     m -= n_dead;
-    tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
+    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
     if (n_evicted) *n_evicted = n_dead;
     refresh_view();
     if (m == 0) { n_ids = 0; return rebuild(stream); }

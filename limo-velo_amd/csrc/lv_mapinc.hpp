@@ -12,7 +12,11 @@
 //               remembers its position in each of its 27 buckets (backpos, 16 bits: positions are relative to the
 //               run's start, so a run that moves keeps them), so a deletion is 27 table probes + 27 direct writes
 //               (x set to +inf: tombstone); rounds 1-5 searched the bucket's ids (266 DRAM lines per deleted point
-//               over three replicated levels).  Level 1 has no storage (eight level-0 buckets tile its block).
+//               over three replicated levels).
+//   level 1     the same again per level-1 voxel.  Everything in this header maintains ONE replicated level: the map runs it as two
+//               INSTANCES (MapRW::level 0 and 1, lv_map.hip MapStore::rw) with their own tables, pools, back-positions and counters;
+//               the voxel lists, the 0.2 m boxes and the tile groups (level-0 runs side by side for the map queries and the surface
+//               pass) belong to instance 0 — instance 1 has neither a list table nor a group table.
 //   voxel lists one list per level-2 voxel, unordered: append / tombstone in the point's own voxel only.
 //   0.2 m boxes ikd-Tree's down-sampling rule needs "the points currently in this box": a hash table
 //               box -> chain of ids (box_next), built lazily by the first down-sampling insert.
@@ -34,7 +38,7 @@
 namespace lv {
 
 constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
-constexpr int INC_SLOTS_PER_POINT = 27 * REPL_LEVELS + 1;   // its 27 level-0 buckets + its level-2 voxel's list
+constexpr int INC_SLOTS_PER_POINT = 27 * REPL_LEVELS + 1;   // per instance: a point's 27 buckets + its level-2 voxel's list (instance 0 only)
 constexpr int INC_LEVELS = REPL_LEVELS + 1;                 // tables: bt[0], voxel lists
 constexpr uint16_t BACKPOS_FAR = 0xFFFFu;                   // back-position of an entry beyond 16 bits: found by binary search over the run's ids
 constexpr int CELL_SLOT = REPL_LEVELS;                      // index of the voxel-list table in the per-table arrays
@@ -93,6 +97,8 @@ struct MapRW {
     float origin[3];
     float inv_cell;
     MapCounters* cnt;
+    int level;                       // voxel level of this instance's buckets (0 or 1): their voxel coordinates are the level-0 ones >> level
+    const MapCounters* front;        // the counters the batch's front half wrote (n_dead): instance 0's; nullptr: cnt
 };
 
 struct BoxRW {
@@ -180,8 +186,8 @@ __device__ __forceinline__ uint32_t list_count(const uint32_t* cursors, uint32_t
 }
 
 // The tile group of the level-0 bucket `key` is no longer one contiguous region of up-to-date runs (one of its runs moved, a new
-// tile appeared outside the region, a run was dropped with its entries left as they were): level 1 stops streaming it
-// (bucket_attempt, lv_match.hip: extent 0 -> the point goes on to the lists).  An insert batch lists the groups it breaks
+// tile appeared outside the region, a run was dropped with its entries left as they were): the map queries and the surface pass stop streaming it
+// (lv_query.hip / lv_surface.hip: extent 0 -> the query goes on to the lists).  An insert batch lists the groups it breaks
 // (M.broken) and lays them out again, in fresh space, behind its last pass (inc_regroup_*): a group stays broken only until
 // then — or, broken by an eviction sweep (no list), until an insert touches it or the map is re-linearised.
 // Entry states: extent > 0 intact; extent 0 broken; start == ID_NONE: broken and listed by the batch in flight.
@@ -231,10 +237,12 @@ __device__ __forceinline__ bool inc_slot_key(const MapRW& M, const float4& p, in
         level = w / 27;
         const int c = w % 27;
         const int dz = c / 9 - 1, dy = (c / 3) % 3 - 1, dx = c % 3 - 1;
-        const uint32_t nx = (uint32_t)((cx >> level) + dx), ny = (uint32_t)((cy >> level) + dy), nz = (uint32_t)((cz >> level) + dz);
+        const int sh = level + M.level;
+        const uint32_t nx = (uint32_t)((cx >> sh) + dx), ny = (uint32_t)((cy >> sh) + dy), nz = (uint32_t)((cz >> sh) + dz);
         if (nx >= (1u << 21) || ny >= (1u << 21) || nz >= (1u << 21)) return false;
         key = pack_cell(nx, ny, nz);
     } else {
+        if (!M.lv[CELL_SLOT].table) return false;   // (the lists belong to instance 0)
         level = CELL_SLOT;
         key = pack_cell((uint32_t)(cx >> CELL_LEVEL), (uint32_t)(cy >> CELL_LEVEL), (uint32_t)(cz >> CELL_LEVEL));
     }
@@ -251,9 +259,9 @@ __device__ __forceinline__ bool inc_point_ok(const MapRW& M, const float4& p) {
 
 // where a point of the bucket around voxel (bx, by, bz) sits SEEN FROM THE POINT: the bucket's voxel is neighbour c of the point's
 // own voxel (target c of the insert passes) — the slot of the point's back-position
-__device__ __forceinline__ uint32_t backpos_slot(const float4& p, const float* origin, float inv_cell, uint32_t bx, uint32_t by, uint32_t bz) {
-    const int dx = (int)bx - cell_coord(p.x, origin[0], inv_cell), dy = (int)by - cell_coord(p.y, origin[1], inv_cell),
-              dz = (int)bz - cell_coord(p.z, origin[2], inv_cell);
+__device__ __forceinline__ uint32_t backpos_slot(const float4& p, const float* origin, float inv_cell, int level, uint32_t bx, uint32_t by, uint32_t bz) {
+    const int dx = (int)bx - (cell_coord(p.x, origin[0], inv_cell) >> level), dy = (int)by - (cell_coord(p.y, origin[1], inv_cell) >> level),
+              dz = (int)bz - (cell_coord(p.z, origin[2], inv_cell) >> level);
     return (uint32_t)((dz + 1) * 9 + (dy + 1) * 3 + (dx + 1));
 }
 
@@ -480,7 +488,8 @@ __global__ void inc_kill_kernel(MapRW M, const float4* __restrict__ dead, uint32
 }
 // the same with the length of the list read on the device (small batches: no host round trip for it), grid-stride
 __device__ __forceinline__ void inc_kill_counted_item(const MapRW& M, const float4* __restrict__ dead, uint32_t dead_cap, uint32_t t0, uint32_t n_threads) {
-    const uint32_t n_dead = M.cnt->n_dead < dead_cap ? M.cnt->n_dead : dead_cap;
+    const MapCounters* fc = M.front ? M.front : M.cnt;
+    const uint32_t n_dead = fc->n_dead < dead_cap ? fc->n_dead : dead_cap;
     const uint64_t total = (uint64_t)n_dead * (uint32_t)INC_SLOTS_PER_POINT;
     for (uint64_t t = t0; t < total; t += (uint64_t)n_threads)
         inc_kill_slot(M, dead, (uint32_t)(t / (uint32_t)INC_SLOTS_PER_POINT), (int)(t % (uint32_t)INC_SLOTS_PER_POINT));
@@ -583,8 +592,9 @@ __device__ __forceinline__ void inc_group_item(const MapRW& M, const GroupRW& G,
     const int l = (int)(t % (uint32_t)REPL_LEVELS);
     if (!inc_item_point(G, alive, k, t / (uint32_t)REPL_LEVELS, j)) return;
     const float4 p = newp[j];
-    const int cx = cell_coord(p.x, M.origin[0], M.inv_cell) >> l, cy = cell_coord(p.y, M.origin[1], M.inv_cell) >> l,
-              cz = cell_coord(p.z, M.origin[2], M.inv_cell) >> l;
+    const int sh = l + M.level;
+    const int cx = cell_coord(p.x, M.origin[0], M.inv_cell) >> sh, cy = cell_coord(p.y, M.origin[1], M.inv_cell) >> sh,
+              cz = cell_coord(p.z, M.origin[2], M.inv_cell) >> sh;
     const uint64_t key = pack_cell((uint32_t)cx, (uint32_t)cy, (uint32_t)cz);
     uint4* tab = G.table[l];
     uint32_t slot = hash_cell(key, G.shift) & G.mask;
@@ -668,15 +678,15 @@ __device__ __forceinline__ void inc_register_item(const MapRW& M, const GroupRW&
         tl = l;
         key = pack_cell(nx, ny, nz);
     } else {
-        if (l != REPL_LEVELS - 1) return;
+        if (l != REPL_LEVELS - 1 || !M.lv[CELL_SLOT].table) return;   // (instance 1 keeps no lists)
         tl = CELL_SLOT;   // (several voxel groups may share a list: they take their shares of its tail like the groups of a bucket)
-        key = pack_cell(vx >> (CELL_LEVEL - l), vy >> (CELL_LEVEL - l), vz >> (CELL_LEVEL - l));
+        key = pack_cell(vx >> (CELL_LEVEL - l - M.level), vy >> (CELL_LEVEL - l - M.level), vz >> (CELL_LEVEL - l - M.level));
     }
     const LevelRW& L = M.lv[tl];
     bool created = false;
     const uint32_t slot = table_get_slot(L, key, &M.cnt->slots_used[tl], &M.cnt->overflow, &created);
     if (slot == ID_NONE) return;
-    if (created && tl < REPL_LEVELS) inc_break_group(M, key);   // a new bucket lies outside its group's region
+    if (created && tl < REPL_LEVELS && M.level == 0) inc_break_group(M, key);   // a new bucket lies outside its group's region
     G.gbase[l][r] = atomicAdd(&L.aux[slot].pending, n_v);
     G.gslot[l][r] = slot;
 }
@@ -742,7 +752,7 @@ __device__ __forceinline__ void inc_reserve_item(const MapRW& M, const GroupRW& 
             }
             L.table[slot].z = ns;
             L.aux[slot].cap = ncap;
-            if (level < REPL_LEVELS) inc_break_group(M, entry_key(e));   // the run leaves its group's region
+            if (level < REPL_LEVELS && M.level == 0) inc_break_group(M, entry_key(e));   // the run leaves its group's region
         }
     }
     L.aux[slot].tail0 = tail0;
@@ -995,7 +1005,7 @@ __device__ __forceinline__ void inc_compact_scatter_item(const MapRW& M, uint32_
                 xs[(size_t)np * 3] = p.x; xs[(size_t)np * 3 + 1] = p.y; xs[(size_t)np * 3 + 2] = p.z;
                 const uint32_t id = __float_as_uint(p.w);
                 is[np] = id;
-                M.backpos[(size_t)id * 27 + backpos_slot(p, M.origin, M.inv_cell, bx, by, bz)] = (uint16_t)(np < (uint32_t)BACKPOS_FAR ? np : (uint32_t)BACKPOS_FAR);
+                M.backpos[(size_t)id * 27 + backpos_slot(p, M.origin, M.inv_cell, M.level, bx, by, bz)] = (uint16_t)(np < (uint32_t)BACKPOS_FAR ? np : (uint32_t)BACKPOS_FAR);
             }
             if (i >= tail_end) { xs[(size_t)i * 3] = pos_inf(); xs[(size_t)i * 3 + 1] = pos_inf(); xs[(size_t)i * 3 + 2] = pos_inf(); }
         }

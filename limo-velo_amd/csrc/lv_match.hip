@@ -349,52 +349,14 @@ __device__ __forceinline__ void merge_team(kkey (&k)[K]) {
 }
 
 
-// k, o sorted ascending -> k = the K smallest of the union (merge5), drop = min(drop, the distances that left)
-template <int K, typename T>
-__device__ __forceinline__ void merge5_drop(kkey (&k)[K], const T& o, uint32_t& drop) {
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        const kkey lo = kmin(o[K - 1 - i], k[i]), hi = kmax(o[K - 1 - i], k[i]);
-        k[i] = lo;
-        drop = min(drop, key_hi(hi));   // (NONE's high word is above every distance: it never lowers the minimum)
-    }
-    order_selected<K>(k);
-}
-template <int CTRL, int K>
-__device__ __forceinline__ void merge_round_drop(kkey (&k)[K], uint32_t& drop) {
-    kkey o[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) o[j] = dpp_key<CTRL>(k[j]);
-    const uint32_t od = (uint32_t)__builtin_amdgcn_update_dpp((int)drop, (int)drop, CTRL, 0xF, 0xF, true);
-    drop = min(drop, od);
-    merge5_drop(k, o, drop);
-}
-template <int LANES, int K>
-__device__ __forceinline__ void merge_team_drop(kkey (&k)[K], uint32_t& drop) {   // (the DPP rounds of merge_group)
-    static_assert(LANES <= 16, "lane groups of up to 16 lanes");
-    if (LANES >= 2) merge_round_drop<0xB1>(k, drop);
-    if (LANES >= 4) merge_round_drop<0x4E>(k, drop);
-    if (LANES >= 8) merge_round_drop<0x141>(k, drop);
-    if (LANES >= 16) merge_round_drop<0x140>(k, drop);
-}
-
 // One bucket-level attempt by a team of LANES lanes (tl = lane in team): ONE probe of the level's bucket table
 // and ONE coalesced stream over the neighbourhood bucket of the query's voxel (a miss means the whole
 // 27-voxel block is empty).  k is all-NONE on entry; returns true with the sorted result in k (low words =
 // positions inside the bucket starting at bstart) iff 5 candidates were found inside the guaranteed radius,
 // otherwise false with k reset to NONE.  Deleted entries stay in place with x = +inf: their distance is +inf,
 // which loses against every real candidate and fails the radius test.
-// bl == 1 (round 6): the level-1 block in level-0 storage.  Its 27 voxels are tiled exactly by the eight level-0 buckets of one tile
-// GROUP (lv_device.hpp REPL_LEVELS), which a (re)build lays out side by side: ONE probe of the group table and ONE stream over the
-// region {start, extent} — runs with their slack, the slack filled with +inf (distance +inf, like a deleted entry) — give the
-// candidate set a replicated level-1 bucket gave (rounds 1-5) for 27 more copies of every map point and two thirds of every
-// insert / deletion.  A group that an insert broke up has extent 0: the point is not decided here and goes on to the lists.
-// Order.  Inside ONE bucket position order is id order; across the eight runs it is not, so here the key's low word (position in
-// the region) orders equal distances differently from the reference's (distance, index).  That can only change the result when
-// two candidates at bit-equal distance compete — among the five winners, or the fifth winner with a candidate that was dropped.
-// Both are detected (the smallest dropped distance is tracked through every selection: `drop`) and such a point is NOT decided
-// here either: the lists carry ids in their keys.  Exact for every input; the detour is taken by points with an exact f32
-// distance tie among their six nearest neighbours.
+// Both replicated levels (0 and 1) keep their buckets in ascending id, so the key's low word (position in the bucket) orders equal
+// distances exactly as the reference's (distance, index) does: no tie needs a second look on either level.
 template <int LANES, int K>
 __device__ __forceinline__ bool bucket_attempt(const MapView& map, int bl, const QGeom& geo, float qx, float qy, float qz, int tl,
                                                kkey (&k)[K], uint32_t& bstart, long long* clk, Xyz* stage = nullptr, uint32_t* bound = nullptr) {
@@ -402,9 +364,8 @@ __device__ __forceinline__ bool bucket_attempt(const MapView& map, int bl, const
     // among them — K living points lie within it, so no point farther than that is among the query's K nearest (left alone otherwise)
     // stage (LDS, LANES * 8 entries of this team, or nullptr): the first chunk's candidates are kept there by
     // position, so that the caller can pick the winners up without another trip to memory
-    const GridLevel g = bl == 0 ? map.bt[0] : map.gt;
+    const GridLevel g = map.bt[bl];
     const uint64_t key = pack_cell((uint32_t)(geo.c0x >> bl), (uint32_t)(geo.c0y >> bl), (uint32_t)(geo.c0z >> bl));
-    uint32_t drop = 0x7FEFFFFFu;   // (bl == 1) smallest distance that left a selection
     uint32_t slot = hash_cell(key, g.shift) & g.mask;
     uint32_t bcount = 0;
     for (;;) {
@@ -420,14 +381,14 @@ __device__ __forceinline__ bool bucket_attempt(const MapView& map, int bl, const
     if (clk) { asm volatile("" :: "v"(bcount)); clk[2] = clock64(); }
     if (bcount < K) return false;
     constexpr int U = 8;
-    const Xyz* __restrict__ bp = reinterpret_cast<const Xyz*>(map.bxyz[0]) + bstart;
+    const Xyz* __restrict__ bp = reinterpret_cast<const Xyz*>(map.bxyz[bl]) + bstart;
     uint32_t base = 0;
     do {
         // (round 4) A bucket of the benchmark's map holds 62 candidates on average and more than the 64 of a chunk one time in four:
         // two in three of the 8-point tasks went through a second chunk for the handful of candidates beyond — at the full price of
         // eight loads, eight distances and the 19-comparator sort.  When what is left fits (at most 4 per lane for every lane group
         // of the wavefront) the tail takes HALF a chunk: four loads, four distances, a 5-comparator sort, the same merge.  Level 0
-        // only: on the level-1 stream (seven chunks) the wavefront-uniform loop it needs cost more than the half chunk saves.
+        // only: on the level-1 stream (several chunks) the wavefront-uniform loop it needs cost more than the half chunk saves.
         if constexpr (LV_HALF_CHUNK && K == KNN) {
             if (bl == 0 && base != 0 && __builtin_amdgcn_ballot_w64(base + (uint32_t)(LANES * 4) < bcount) == 0ull) {
                 Xyz mp4[4];
@@ -470,31 +431,18 @@ __device__ __forceinline__ bool bucket_attempt(const MapView& map, int bl, const
             ck[u] = make_key_if(j < bcount, calc_dist(qx, qy, qz, mpt[u]), j);
         }
         sort8(ck);
-#ifndef LV_DIAG_NODROP
-#define LV_DIAG_NODROP 0   // (diagnostic build only: level 1 without the tie tracking — NOT exact)
-#endif
-        if (bl != 0 && K < U && !LV_DIAG_NODROP) drop = min(drop, key_hi(ck[K < U ? K : 0]));
         if (base == 0) {   // k is still all-NONE: the union's five smallest are the chunk's
 #pragma unroll
             for (int i = 0; i < K; ++i) k[i] = ck[i];
-        } else if (bl != 0 && !LV_DIAG_NODROP) {
-            merge5_drop(k, ck, drop);
         } else {
             merge5(k, ck);
         }
         base += LANES * U;
     } while ((LV_HALF_CHUNK && K == KNN && bl == 0) ? __builtin_amdgcn_ballot_w64(base < bcount) != 0ull : base < bcount);
-    if (bl != 0 && !LV_DIAG_NODROP) merge_team_drop<LANES>(k, drop);
-    else merge_team<LANES>(k);
+    merge_team<LANES>(k);
     const float r = search_radius(map, geo, bl);
     const float d5 = __uint_as_float(key_hi(k[K - 1]));
-    bool ok = !is_none(k[K - 1]) && r > 0.f && d5 < r * r;
-    if (bl != 0) {   // (see "Order" above)
-        ok = ok && drop != key_hi(k[K - 1]);
-#pragma unroll
-        for (int j = 0; j + 1 < K; ++j) ok = ok && key_hi(k[j]) != key_hi(k[j + 1]);
-    }
-    if (ok) return true;
+    if (!is_none(k[K - 1]) && r > 0.f && d5 < r * r) return true;
     if (bound && key_real(k[K - 1])) *bound = min(*bound, key_hi(k[K - 1]));
 #pragma unroll
     for (int j = 0; j < K; ++j) k[j] = none_key();
@@ -733,10 +681,10 @@ __device__ __forceinline__ void knn_search(const MapView& map, KfDev* __restrict
 #ifndef LV_DIAG_LEVELS
 #define LV_DIAG_LEVELS 2
 #endif
-        for (int bl = 0; bl < LV_DIAG_LEVELS; ++bl) {   // level 0: the query's bucket; level 1: the region of its tile group (bucket_attempt)
+        for (int bl = 0; bl < LV_DIAG_LEVELS; ++bl) {   // level 0: the query's bucket; level 1: the bucket of its level-1 voxel (bucket_attempt)
             if (!decided) {
                 decided = bucket_attempt<S>(map, bl, geo, qx, qy, qz, gl, k, bstart, (DBG && bl == 0) ? clk : nullptr,
-                                            bl == 0 ? stage0 : nullptr, bl == 1 ? &bound : nullptr);   // (level 1's bound: its region holds the level-0 bucket's neighbourhood and more)
+                                            bl == 0 ? stage0 : nullptr, bl == 1 ? &bound : nullptr);   // (level 1's bound: its bucket holds the level-0 bucket's neighbourhood and more)
                 if (decided) { src = bl; hist_bin = bl; }
             }
         }
@@ -978,8 +926,8 @@ __global__ LV_SEARCH_BOUNDS void search_kernel(MapView map, const float4* __rest
                         const Xyz w = s_stage[gq][pos];
                         v = make_float4(w.x, w.y, w.z, __uint_as_float(0xFFFFFFFFu));
                     } else if (src >= 0) {
-                        const Xyz w = reinterpret_cast<const Xyz*>(map.bxyz[0])[(size_t)bstart + pos];
-                        v = make_float4(w.x, w.y, w.z, __uint_as_float(map.bidx[0][(size_t)bstart + pos]));
+                        const Xyz w = reinterpret_cast<const Xyz*>(map.bxyz[src])[(size_t)bstart + pos];
+                        v = make_float4(w.x, w.y, w.z, __uint_as_float(map.bidx[src][(size_t)bstart + pos]));
                     } else {
                         v = map.orig[pos];
                         v.w = __uint_as_float(pos);
@@ -1571,7 +1519,7 @@ __global__ __launch_bounds__(PK_THREADS, PK_THREADS / 256) void pass_kernel(Pass
                             const Xyz w = s_stage[gq][pos];   // still in LDS (same wavefront wrote it)
                             v = make_float4(w.x, w.y, w.z, __uint_as_float(0xFFFFFFFFu));
                         } else if (src >= 0) {
-                            const Xyz w = reinterpret_cast<const Xyz*>(a.map.bxyz[0])[(size_t)bstart + pos];
+                            const Xyz w = reinterpret_cast<const Xyz*>(a.map.bxyz[src])[(size_t)bstart + pos];
                             v = make_float4(w.x, w.y, w.z, __uint_as_float(0xFFFFFFFFu));
                         } else {
                             v = a.map.orig[pos];
