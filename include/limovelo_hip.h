@@ -539,6 +539,55 @@ int  lv_occ_load(lv_ctx* ctx, const float* logodds, size_t n);
 int  lv_occ_clear(lv_ctx* ctx);
 int  lv_occ_get_params(lv_ctx* ctx, lv_occupancy_params* out);
 
+/* ---- Distance field ----------------------------------------------------------------------------------
+ * How far every voxel of the occupancy grid is from the nearest obstacle, and through lv_occ_distance_query in which direction:
+ * costmap_2d's inflation layer, the ESDF of Voxblox and FIESTA, the clearance term of CHOMP and TEB (the reference has no
+ * counterpart).  An exact Euclidean distance transform of the grid, three separable passes on the device.  All distances are
+ * squared integers in voxel units, so the field is exactly defined: a pure function of the grid and the parameters.
+ *   obstacles, 3-D field (planar = 0)  voxel v is an obstacle iff L(v) >= l_occ (NaN compares false); with unknown_is_obstacle != 0
+ *            a voxel whose L is NaN is an obstacle too.  A voxel with l_free < L < l_occ is not an obstacle.
+ *   obstacles, 2-D field (planar != 0)  the cells are those of lv_occ_project(k_lo, k_hi), with the same clipping (k_lo > k_hi:
+ *            LV_EINVAL).  A cell is an obstacle iff its projected value is 100; with unknown_is_obstacle a cell whose value is -1
+ *            is one too.  The field has nx * ny cells, index j * nx + i, and behaves as a grid with nz = 1.
+ *   outside distance  d2_out(v) = min over the obstacles o of dx^2 + dy^2 + dz^2 on integer voxel offsets; 0 on obstacles.  Only
+ *            voxels inside the grid count as obstacles: the grid's border is not one.
+ *   inside distance (signed_field != 0)  d2_in(v): the same minimum over the voxels that are not obstacles.
+ *   stored value  one int32 s2 per voxel: s2 = d2_out(v) where v is not an obstacle; on obstacles s2 = 0 when unsigned and
+ *            s2 = -d2_in(v) when signed.  LV_OCC_FAR where no obstacle exists, -LV_OCC_FAR where no voxel that is not an obstacle
+ *            exists.  Every finite |s2| <= 3 * 1023^2 < 2^24.
+ *   truncation  max_cells = 0: none, otherwise 1..1024.  A value with |s2| > max_cells * max_cells is stored as +-LV_OCC_FAR;
+ *            nothing else changes.
+ *   metres   m = resolution * sqrtf((float)|s2|) with the sign of s2: f32, unfused, sqrtf correctly rounded.  s2 = 0 gives
+ *            +0.0f, +-LV_OCC_FAR gives +-inf.
+ *   query    a point is quantised per axis as lv_occ_query does it (q, then q >> 8); in a planar field z is not used and may
+ *            be anything, non-finite included.  dist is m of the voxel; NaN for a non-finite point and for one outside the grid.
+ *            grad (may be NULL) holds 3 floats per point.  Per axis a let m-, m0, m+ be the metre values at v - e_a, v, v + e_a; a
+ *            neighbour is usable iff it is in the grid and its value finite.  grad[a] = 0 if m0 is not finite (or NaN);
+ *            (m+ - m-) / (resolution + resolution) with both neighbours usable; (m+ - m0) / resolution with only +;
+ *            (m0 - m-) / resolution with only -; 0 with none.  In a planar field grad[2] = 0.
+ * The field is a SNAPSHOT of the grid at build time: lv_occ_integrate, lv_occ_load and lv_occ_clear leave it in place and set
+ * stale = 1 (a planner keeps reading the last field while sweeps arrive); lv_occ_configure frees it; a new build replaces it.
+ * Building never changes a bit of the log-odds grid.  Every call gives LV_ESTATE before lv_occ_configure, fetch and query also
+ * before a build (lv_occ_distance_info reports built = 0 instead).  Parameters outside the limits, a capacity below the field's
+ * size or both outputs NULL give LV_EINVAL and change nothing; like lv_occ_configure's, the parameters are judged before the
+ * context.  Nothing is allocated before the first build; lv_destroy frees everything.  The calls run on the context's stream and
+ * return when their host outputs are written. */
+#define LV_OCC_FAR 2147483647
+typedef struct lv_distance_params { int planar, k_lo, k_hi, unknown_is_obstacle, signed_field, max_cells; } lv_distance_params;
+typedef struct lv_distance_info   { int built, planar, nx, ny, nz, stale; lv_distance_params params; } lv_distance_info;
+/* All zero: a 3-D field, unknown = free, unsigned, untruncated. */
+void lv_default_distance_params(lv_distance_params* p);
+/* stats (may be NULL): obstacles, voxels with a finite value, the largest finite d2_out, the largest finite d2_in (0 when the
+ * field is unsigned). */
+int  lv_occ_distance_build(lv_ctx* ctx, const lv_distance_params* p, uint64_t stats[4]);
+/* s2 and / or metres: nx * ny * nz values (nx * ny of a planar field); either may be NULL, not both. */
+int  lv_occ_distance_fetch(lv_ctx* ctx, int32_t* s2, float* metres, size_t capacity);
+int  lv_occ_distance_query(lv_ctx* ctx, const void* pts, size_t stride, size_t n, float* dist, float* grad);
+/* nx, ny, nz: the field's (nz = 1 when planar); all zero with built = 0. */
+int  lv_occ_distance_info(lv_ctx* ctx, lv_distance_info* out);
+/* Frees the field. */
+int  lv_occ_distance_clear(lv_ctx* ctx);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
     "lv_default_occupancy_params", "lv_occ_configure", "lv_occ_integrate", "lv_occ_query", "lv_occ_project", "lv_occ_fetch", "lv_occ_load",
     "lv_occ_clear", "lv_occ_get_params",
+    "lv_default_distance_params", "lv_occ_distance_build", "lv_occ_distance_fetch", "lv_occ_distance_query", "lv_occ_distance_info",
+    "lv_occ_distance_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -163,6 +165,28 @@ OCCUPANCY_ARGTYPES = {
     "lv_occ_load": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t],
     "lv_occ_clear": [C.c_void_p],
     "lv_occ_get_params": [C.c_void_p, C.POINTER(OccupancyParams)],
+}
+
+LV_OCC_FAR = 2147483647
+
+
+class DistanceParams(C.Structure):  # lv_distance_params
+    _fields_ = [("planar", C.c_int), ("k_lo", C.c_int), ("k_hi", C.c_int), ("unknown_is_obstacle", C.c_int), ("signed_field", C.c_int),
+                ("max_cells", C.c_int)]
+
+
+class DistanceInfo(C.Structure):  # lv_distance_info
+    _fields_ = [("built", C.c_int), ("planar", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("stale", C.c_int),
+                ("params", DistanceParams)]
+
+
+# ctypes signatures of the distance field (include/limovelo_hip.h "Distance field"; tests/test_occ_distance_abi.py)
+DISTANCE_ARGTYPES = {
+    "lv_occ_distance_build": [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(C.c_uint64)],
+    "lv_occ_distance_fetch": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t],
+    "lv_occ_distance_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "lv_occ_distance_info": [C.c_void_p, C.POINTER(DistanceInfo)],
+    "lv_occ_distance_clear": [C.c_void_p],
 }
 
 
@@ -383,8 +407,10 @@ def load_library() -> C.CDLL:
         lib.lv_place_count.argtypes = [C.c_void_p]
         lib.lv_default_occupancy_params.restype = None
         lib.lv_default_occupancy_params.argtypes = [C.POINTER(OccupancyParams)]
+        lib.lv_default_distance_params.restype = None
+        lib.lv_default_distance_params.argtypes = [C.POINTER(DistanceParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES}.items():
+                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -462,6 +488,14 @@ def default_occupancy_params(**kw) -> OccupancyParams:
             p.origin[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_distance_params(**kw) -> DistanceParams:
+    p = DistanceParams()
+    load_library().lv_default_distance_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -779,6 +813,46 @@ class Context:
 
     def occ_clear(self):
         self._check(self.lib.lv_occ_clear(self.h))
+
+    # --- distance field (include/limovelo_hip.h "Distance field")
+    def occ_distance_build(self, params: DistanceParams | None = None) -> np.ndarray:
+        """lv_occ_distance_build (default: 3-D, unknown = free, unsigned, untruncated); returns stats [4] uint64: obstacles, voxels
+        with a finite value, the largest finite d2_out, the largest finite d2_in."""
+        p = params if params is not None else default_distance_params()
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_distance_build(self.h, C.byref(p), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_distance_info(self) -> DistanceInfo:
+        out = DistanceInfo()
+        self._check(self.lib.lv_occ_distance_info(self.h, C.byref(out)))
+        return out
+
+    def occ_distance_fetch(self, s2=True, metres=True):
+        """(s2 int32, metres f32), each [nz, ny, nx] ([ny, nx] of a planar field) or None where not asked for."""
+        i = self.occ_distance_info()
+        if not i.built:   # (the library's own refusal)
+            self._check(self.lib.lv_occ_distance_fetch(self.h, None, (C.c_float * 1)(), C.c_size_t(0)))
+        shape = (i.ny, i.nx) if i.planar else (i.nz, i.ny, i.nx)
+        a = np.zeros(shape, np.int32) if s2 else None
+        m = np.zeros(shape, np.float32) if metres else None
+        self._check(self.lib.lv_occ_distance_fetch(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)) if s2 else None,
+                                                   m.ctypes.data_as(C.POINTER(C.c_float)) if metres else None,
+                                                   C.c_size_t(int(np.prod(shape)))))
+        return a, m
+
+    def occ_distance_query(self, pts, want_grad=True):
+        """(dist [n] f32 metres, grad [n, 3] f32 or None) at the voxel of each world point; dist NaN outside the grid."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        dist = np.full(n, np.nan, np.float32)
+        grad = np.zeros((n, 3), np.float32) if want_grad else None
+        self._check(self.lib.lv_occ_distance_query(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                                   dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   grad.ctypes.data_as(C.POINTER(C.c_float)) if want_grad else None))
+        return dist, grad
+
+    def occ_distance_clear(self):
+        self._check(self.lib.lv_occ_distance_clear(self.h))
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

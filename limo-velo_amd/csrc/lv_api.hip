@@ -13,6 +13,7 @@
 #include "lv_cluster.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
+#include "lv_distance.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -49,6 +50,7 @@ struct lv_ctx {
     ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
+    DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -635,6 +637,7 @@ void lv_destroy(lv_ctx* c) {
     c->surface.release();
     c->cluster.release();
     c->place.release();
+    c->dist.release();
     c->occ.release();
     c->batch.release();
     c->scan.release();
@@ -2417,6 +2420,8 @@ void lv_default_occupancy_params(lv_occupancy_params* p) {
 int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     if (const char* why = occ_check_params(p)) { set_error("lv_occ_configure: %s", why); return LV_EINVAL; }
     LV_CHECK_CTX(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->dist.release();   // (the field belongs to the grid it was built from)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2433,6 +2438,7 @@ int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t s
         total += w.n;
         if (w.n > 0xFFFFFFF0ull / 4 || total > 0xFFFFFFF0ull / 4) { set_error("too many returns"); return LV_EINVAL; }
     }
+    if (c->dist.built) c->dist.stale = 1;
     return c->occ.integrate(c->stream, views, n_views, stats);
 }
 
@@ -2469,12 +2475,14 @@ int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) {
         const float v = logodds[i];
         if (!(v != v) && !(v >= lo && v <= hi)) { set_error("lv_occ_load: value %g at %zu outside [%g, %g]", v, i, lo, hi); return LV_EINVAL; }
     }
+    if (c->dist.built) c->dist.stale = 1;
     return c->occ.load(c->stream, logodds);
 }
 
 int lv_occ_clear(lv_ctx* c) {
     LV_CHECK_CTX(c);
     LV_OCC_CONFIGURED(c);
+    if (c->dist.built) c->dist.stale = 1;
     return c->occ.clear(c->stream);
 }
 
@@ -2483,6 +2491,63 @@ int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) {
     LV_OCC_CONFIGURED(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
     *out = c->occ.prm;
+    return LV_OK;
+}
+
+// ---- Distance field (lv_distance.hip)
+void lv_default_distance_params(lv_distance_params* p) {
+    if (!p) return;
+    *p = lv_distance_params{};
+}
+
+// (the parameters are judged before the context, as lv_occ_configure's are)
+int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats[4]) {
+    if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    return c->dist.build(c->stream, c->occ, *p, stats);
+}
+
+int lv_occ_distance_fetch(lv_ctx* c, int32_t* s2, float* metres, size_t capacity) {
+    if (!s2 && !metres) { set_error("lv_occ_distance_fetch: s2 and metres are both null"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    if (capacity < c->dist.n_vox) { set_error("lv_occ_distance_fetch: room for %zu values needed", c->dist.n_vox); return LV_EINVAL; }
+    return c->dist.fetch(c->stream, s2, metres);
+}
+
+int lv_occ_distance_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* dist, float* grad) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    if (n && (!pts || !dist || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
+    if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
+    return c->dist.query(c->stream, pts, stride, n, dist, grad);
+}
+
+int lv_occ_distance_info(lv_ctx* c, lv_distance_info* out) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    *out = lv_distance_info{};
+    if (c->dist.built) {
+        out->built = 1;
+        out->planar = c->dist.prm.planar != 0;
+        out->nx = c->dist.grid.nx;
+        out->ny = c->dist.grid.ny;
+        out->nz = c->dist.grid.nz;
+        out->stale = c->dist.stale;
+        out->params = c->dist.prm;
+    }
+    return LV_OK;
+}
+
+int lv_occ_distance_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->dist.release();
     return LV_OK;
 }
 

@@ -1,7 +1,9 @@
 """The ray-cast occupancy grid on top of the lv_occ_* calls (include/limovelo_hip.h "Occupancy grid"): what OctoMap and
 octomap_server's projected map hand to navigation.  integrate() takes any number of sweeps, occupancy_grid() gives the 2-D map in
 the shape of nav_msgs/OccupancyGrid, save_grid / load_grid keep a grid as an .npz next to prelocalise.save_map's map, and
-map_point_states() tells which points of the device map lie in space that the accumulated evidence says is free."""
+map_point_states() tells which points of the device map lie in space that the accumulated evidence says is free.
+distance_field() / clearance() give the Euclidean distance to the nearest obstacle (lv_occ_distance_*, "Distance field") and
+costmap_from_distance() costmap_2d's inflation costs from it."""
 from __future__ import annotations
 
 import math
@@ -76,3 +78,46 @@ def map_point_states(ctx) -> np.ndarray:
     if len(m) == 0:
         return np.zeros(0, np.float32)
     return ctx.occ_query(np.ascontiguousarray(m[:, :3], np.float32))
+
+
+def distance_field(ctx, max_dist=None, signed=False, unknown="free", z_band=None) -> np.ndarray:
+    """Builds the distance field of ctx's grid and returns it in metres: [nz, ny, nx] f32, or [ny, nx] over the height band
+    z_band = (z_lo, z_hi) (the layers of layers(); a band without a layer gives a field without obstacles).  max_dist (metres)
+    truncates at floor(max_dist / resolution) cells: farther values are +-inf.  signed: negative inside obstacles.  unknown:
+    "free" or "obstacle"."""
+    if unknown not in ("free", "obstacle"):
+        raise ValueError('unknown: "free" or "obstacle"')
+    p = ctx.occ_params()
+    kw = dict(signed_field=int(bool(signed)), unknown_is_obstacle=int(unknown == "obstacle"))
+    if max_dist is not None:
+        cells = int(math.floor(float(max_dist) / float(p.resolution)))
+        if cells < 1:
+            raise ValueError("max_dist: at least one voxel")
+        kw["max_cells"] = min(cells, 1024)
+    if z_band is not None:
+        k_lo, k_hi = layers(p, float(z_band[0]), float(z_band[1]))
+        if k_lo > k_hi:
+            k_lo, k_hi = p.nz, p.nz   # (clipped to nothing: every cell unknown)
+        kw.update(planar=1, k_lo=k_lo, k_hi=k_hi)
+    ctx.occ_distance_build(capi.default_distance_params(**kw))
+    return ctx.occ_distance_fetch(s2=False)[1]
+
+
+def clearance(ctx, pts):
+    """(dist [n] f32, grad [n, 3] f32): the distance in metres from each world point's voxel to the nearest obstacle in the field
+    last built, and its gradient (central differences over the neighbouring voxels; points away from the obstacles)."""
+    return ctx.occ_distance_query(pts, want_grad=True)
+
+
+def costmap_from_distance(dist_m, inscribed_radius: float, inflation_radius: float, cost_scaling_factor: float = 10.0) -> np.ndarray:
+    """costmap_2d's inflation costs (uint8) from distances in metres: 254 (lethal) at distance 0, 253 (inscribed) up to
+    inscribed_radius, (253 - 1) * exp(-cost_scaling_factor * (d - inscribed_radius)) truncated to an integer out to
+    inflation_radius, 0 beyond (and where the distance is inf or NaN).  Negative distances (inside obstacles) are lethal."""
+    d = np.asarray(dist_m, np.float64)
+    cost = np.zeros(d.shape, np.uint8)
+    with np.errstate(all="ignore"):
+        mid = (d > inscribed_radius) & (d <= inflation_radius)
+        cost[mid] = ((253 - 1) * np.exp(-cost_scaling_factor * (d[mid] - inscribed_radius))).astype(np.uint8)
+        cost[(d > 0) & (d <= inscribed_radius)] = 253
+        cost[d <= 0] = 254
+    return cost
