@@ -588,6 +588,69 @@ int  lv_occ_distance_info(lv_ctx* ctx, lv_distance_info* out);
 /* Frees the field. */
 int  lv_occ_distance_clear(lv_ctx* ctx);
 
+/* ---- Planner -----------------------------------------------------------------------------------------
+ * The cost-to-go from every traversable cell of the distance field to a set of goals, and routes from any number of starts by
+ * descent: navfn's potential array, global_planner, the global plan of move_base (the reference has no counterpart).  Edge costs
+ * are integers, so the potential is the unique fixpoint of relaxation: a pure function of the field, the table and the goals,
+ * the same bits whatever order the device relaxes in.
+ * The planner works on the cells of the distance field last built: nx * ny * nz of them, nz = 1 for a planar field, with the
+ * field's linear index (k * ny + j) * nx + i.  No float enters the rule after the goal and start points are quantised.
+ *   cell cost  let s = s2(v).  The cell is BLOCKED, c(v) = 0, iff s < min_clear_s2 (1..3 * 1023^2): obstacles, negative values and
+ *            -LV_OCC_FAR are.  Otherwise t = n_cost - 1 if s == LV_OCC_FAR, else min(isqrt(s), n_cost - 1), and c(v) = cost[t];
+ *            isqrt is the exact integer floor square root.  cost is the caller's table of n_cost (1..1025) bytes, every entry
+ *            1..255: the cost of standing isqrt(s) whole cells from the nearest obstacle.
+ *   moves    an offset (dx, dy, dz), components in {-1, 0, 1}, not all zero, m of them non-zero.  connectivity 4 or 6 allows
+ *            m = 1, 8 or 18 m <= 2, 26 m <= 3; a planar field takes 4 or 8, a 3-D field 6, 18 or 26 (LV_EINVAL otherwise).  The
+ *            move u -> v is allowed iff u and v are in the field and traversable and so is every cell u + (a proper non-empty
+ *            subset of the move's non-zero components): 2 cells for a face diagonal, 6 for a space diagonal.  No corner is cut.
+ *   edge     edge(u, v) = w(m) * (c(u) + c(v)), w = 10, 14, 17 for m = 1, 2, 3: symmetric, at most 8670.
+ *   goals    1..65536 world points, quantised per axis as lv_occ_query does it (q, then q >> 8); in a planar field z is not
+ *            used.  A goal that is non-finite, outside the field or in a blocked cell is ignored; `goals used` counts the points
+ *            that are not (two in one cell count twice).  With no usable goal the build succeeds and every cell is unreached.
+ *   potential  one uint32 P per cell.  D(v) = the least total edge cost over paths of allowed moves from any goal cell to v, 0
+ *            on goal cells.  P(v) = D(v) if D(v) < 0xFFFFFFFF, else LV_PLAN_UNREACHED; blocked and disconnected cells are
+ *            LV_PLAN_UNREACHED.  A relaxation whose 64-bit sum P(u) + edge(u, v) reaches 0xFFFFFFFF is dropped (prefixes of a
+ *            shortest path are cheaper than the path, so P stays well defined).
+ *   path     per start point.  status 2: the point is non-finite, outside the field or in a blocked cell; 1: P there is
+ *            LV_PLAN_UNREACHED; 0 otherwise.  cost[i] = P of the start cell, LV_PLAN_UNREACHED for status 1 and 2.  With status 0
+ *            the path is the sequence of cells (linear indices) from the start cell to a cell with P = 0, both included: from u
+ *            the next cell is the first v with u -> v allowed and P(v) + edge(u, v) == P(u), "first" in lexicographic order of
+ *            (dz, dy, dx), each running -1, 0, 1.  Such a v exists (the fixpoint), P strictly decreases, so the walk ends; a
+ *            start on a goal gives a path of one cell.  The row is empty for status 1 and 2.
+ * The plan is a SNAPSHOT: it keeps its own copy of the cell costs, origin and resolution, so lv_occ_plan_paths keeps answering
+ * after the distance field is rebuilt.  lv_occ_distance_build and lv_occ_distance_clear leave it in place and set stale = 1;
+ * lv_occ_configure frees it; a new build replaces it (a build that fails in the runtime, LV_EHIP, leaves no plan: built = 0;
+ * a refused one leaves the old plan).  Building never changes a bit of the log-odds grid or of the distance field
+ * (a stale field is planned on as it is).  lv_occ_plan_build judges parameters, table and counts before the context (LV_EINVAL;
+ * "null context" comes last); every call gives LV_ESTATE before lv_occ_configure, lv_occ_plan_build also before a distance build,
+ * fetch and paths also before a plan build (lv_occ_plan_info reports built = 0 instead).  A refused call writes nothing, except as
+ * stated for lv_occ_plan_paths.  Nothing is allocated before the first build; lv_destroy frees everything.  The calls run on the
+ * context's stream and return when their host outputs are written. */
+#define LV_PLAN_UNREACHED 0xFFFFFFFFu
+typedef struct lv_plan_params { int connectivity; int min_clear_s2; } lv_plan_params;
+/* rounds: the relaxation rounds the build took (how the device got there, not part of the rule). */
+typedef struct lv_plan_info   { int built, planar, nx, ny, nz, stale, rounds; lv_plan_params params; } lv_plan_info;
+/* connectivity 8 (a planar field's; a 3-D field needs 6, 18 or 26), min_clear_s2 1. */
+void lv_default_plan_params(lv_plan_params* p);
+/* goals: n_goals points of 3 floats, `stride` bytes (>= 12) apart.  stats (may be NULL): goals used, traversable cells, reached
+ * cells, the largest finite P. */
+int  lv_occ_plan_build(lv_ctx* ctx, const lv_plan_params* p, const uint8_t* cost, size_t n_cost, const void* goals, size_t stride,
+                       size_t n_goals, uint64_t stats[4]);
+/* potential and / or cell_cost: one value per cell of the plan; either may be NULL, not both.  capacity below the number of
+ * cells: LV_EINVAL. */
+int  lv_occ_plan_fetch(lv_ctx* ctx, uint32_t* potential, uint8_t* cell_cost, size_t capacity);
+/* CSR output as in lv_map_radius_search: start i's path is cells[offsets[i] .. offsets[i + 1]), offsets holds n + 1 entries,
+ * *total = offsets[n].  cells == NULL: count only (status, cost, offsets and *total are written).  capacity < *total: LV_EINVAL,
+ * with status, cost, offsets and *total still written, as lv_map_radius_search does it.  Offsets are 64-bit: the count-only call
+ * reports any total; one fill returns at most 2^31 - 1 cells (a larger total is LV_EINVAL in the same way: split the starts).
+ * n < 2^31 - 1. */
+int  lv_occ_plan_paths(lv_ctx* ctx, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets,
+                       int32_t* cells, size_t capacity, size_t* total);
+/* nx, ny, nz: the plan's (nz = 1 when planar); all zero with built = 0. */
+int  lv_occ_plan_info(lv_ctx* ctx, lv_plan_info* out);
+/* Frees the plan. */
+int  lv_occ_plan_clear(lv_ctx* ctx);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "lv_occ_clear", "lv_occ_get_params",
     "lv_default_distance_params", "lv_occ_distance_build", "lv_occ_distance_fetch", "lv_occ_distance_query", "lv_occ_distance_info",
     "lv_occ_distance_clear",
+    "lv_default_plan_params", "lv_occ_plan_build", "lv_occ_plan_fetch", "lv_occ_plan_paths", "lv_occ_plan_info", "lv_occ_plan_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -187,6 +188,29 @@ DISTANCE_ARGTYPES = {
     "lv_occ_distance_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "lv_occ_distance_info": [C.c_void_p, C.POINTER(DistanceInfo)],
     "lv_occ_distance_clear": [C.c_void_p],
+}
+
+LV_PLAN_UNREACHED = 0xFFFFFFFF
+
+
+class PlanParams(C.Structure):  # lv_plan_params
+    _fields_ = [("connectivity", C.c_int), ("min_clear_s2", C.c_int)]
+
+
+class PlanInfo(C.Structure):  # lv_plan_info
+    _fields_ = [("built", C.c_int), ("planar", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("stale", C.c_int),
+                ("rounds", C.c_int), ("params", PlanParams)]
+
+
+# ctypes signatures of the planner (include/limovelo_hip.h "Planner"; tests/test_occ_plan_abi.py)
+PLAN_ARGTYPES = {
+    "lv_occ_plan_build": [C.c_void_p, C.POINTER(PlanParams), C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                          C.POINTER(C.c_uint64)],
+    "lv_occ_plan_fetch": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t],
+    "lv_occ_plan_paths": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                          C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)],
+    "lv_occ_plan_info": [C.c_void_p, C.POINTER(PlanInfo)],
+    "lv_occ_plan_clear": [C.c_void_p],
 }
 
 
@@ -409,8 +433,10 @@ def load_library() -> C.CDLL:
         lib.lv_default_occupancy_params.argtypes = [C.POINTER(OccupancyParams)]
         lib.lv_default_distance_params.restype = None
         lib.lv_default_distance_params.argtypes = [C.POINTER(DistanceParams)]
+        lib.lv_default_plan_params.restype = None
+        lib.lv_default_plan_params.argtypes = [C.POINTER(PlanParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES}.items():
+                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -494,6 +520,14 @@ def default_occupancy_params(**kw) -> OccupancyParams:
 def default_distance_params(**kw) -> DistanceParams:
     p = DistanceParams()
     load_library().lv_default_distance_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_plan_params(**kw) -> PlanParams:
+    p = PlanParams()
+    load_library().lv_default_plan_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -853,6 +887,57 @@ class Context:
 
     def occ_distance_clear(self):
         self._check(self.lib.lv_occ_distance_clear(self.h))
+
+    # --- planner (include/limovelo_hip.h "Planner")
+    def occ_plan_build(self, goals, cost_table, params: PlanParams | None = None) -> np.ndarray:
+        """lv_occ_plan_build over the distance field last built: goals [n, 3] world points, cost_table uint8 [n_cost] (every entry
+        1..255; entry t is the cost of a cell isqrt(s2) = t cells from the nearest obstacle), params default 8-connected with
+        min_clear_s2 1.  Returns stats [4] uint64: goals used, traversable cells, reached cells, the largest finite P."""
+        p = params if params is not None else default_plan_params()
+        a, stride, n = _points(np.asarray(goals, np.float32).reshape(-1, 3))
+        table = np.ascontiguousarray(cost_table, np.uint8).reshape(-1)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_plan_build(self.h, C.byref(p), table.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(table.size),
+                                               a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                               stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_plan_info(self) -> PlanInfo:
+        out = PlanInfo()
+        self._check(self.lib.lv_occ_plan_info(self.h, C.byref(out)))
+        return out
+
+    def occ_plan_fetch(self, potential=True, cell_cost=True):
+        """(potential uint32, cell_cost uint8), each [nz, ny, nx] ([ny, nx] of a planar plan) or None where not asked for."""
+        i = self.occ_plan_info()
+        if not i.built:   # (the library's own refusal)
+            self._check(self.lib.lv_occ_plan_fetch(self.h, (C.c_uint32 * 1)(), None, C.c_size_t(0)))
+        shape = (i.ny, i.nx) if i.planar else (i.nz, i.ny, i.nx)
+        pot = np.zeros(shape, np.uint32) if potential else None
+        cc = np.zeros(shape, np.uint8) if cell_cost else None
+        self._check(self.lib.lv_occ_plan_fetch(self.h, pot.ctypes.data_as(C.POINTER(C.c_uint32)) if potential else None,
+                                               cc.ctypes.data_as(C.POINTER(C.c_uint8)) if cell_cost else None,
+                                               C.c_size_t(int(np.prod(shape)))))
+        return pot, cc
+
+    def occ_plan_paths(self, starts):
+        """(status [n] int32, cost [n] uint32, offsets [n + 1] uint64, cells [total] int32), CSR: start i's path is
+        cells[offsets[i]:offsets[i + 1]], linear cell indices from the start cell to a goal cell.  Counts first, then fills."""
+        a, stride, n = _points(np.asarray(starts, np.float32).reshape(-1, 3))
+        status = np.full(n, 2, np.int32)
+        cost = np.full(n, LV_PLAN_UNREACHED, np.uint32)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_size_t(0)
+        args = (self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n), status.ctypes.data_as(C.POINTER(C.c_int32)),
+                cost.ctypes.data_as(C.POINTER(C.c_uint32)), off.ctypes.data_as(C.POINTER(C.c_size_t)))
+        self._check(self.lib.lv_occ_plan_paths(*args, None, C.c_size_t(0), C.byref(total)))
+        cells = np.empty(int(total.value), np.int32)
+        if cells.size:
+            self._check(self.lib.lv_occ_plan_paths(*args, cells.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(cells.size), C.byref(total)))
+        return status, cost, off, cells
+
+    def occ_plan_clear(self):
+        self._check(self.lib.lv_occ_plan_clear(self.h))
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

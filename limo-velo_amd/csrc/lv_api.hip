@@ -14,6 +14,7 @@
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
 #include "lv_distance.hpp"
+#include "lv_plan.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -51,6 +52,7 @@ struct lv_ctx {
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
     DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
+    PlanStore plan;     // lv_occ_plan_*: the cost-to-go over that field (lv_plan.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -637,6 +639,7 @@ void lv_destroy(lv_ctx* c) {
     c->surface.release();
     c->cluster.release();
     c->place.release();
+    c->plan.release();
     c->dist.release();
     c->occ.release();
     c->batch.release();
@@ -2422,6 +2425,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     LV_CHECK_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->dist.release();   // (the field belongs to the grid it was built from)
+    c->plan.release();   // (and the plan to the field)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2505,6 +2509,7 @@ int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats
     if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
     LV_CHECK_CTX(c);
     LV_OCC_CONFIGURED(c);
+    if (c->plan.built) c->plan.stale = 1;
     return c->dist.build(c->stream, c->occ, *p, stats);
 }
 
@@ -2548,6 +2553,82 @@ int lv_occ_distance_clear(lv_ctx* c) {
     LV_OCC_CONFIGURED(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->dist.release();
+    if (c->plan.built) c->plan.stale = 1;
+    return LV_OK;
+}
+
+// ---- Planner (lv_plan.hip)
+void lv_default_plan_params(lv_plan_params* p) {
+    if (!p) return;
+    *p = lv_plan_params{};
+    p->connectivity = 8;
+    p->min_clear_s2 = 1;
+}
+
+#define LV_PLAN_BUILT(c)                                                       \
+    do {                                                                       \
+        if (!(c)->plan.built) {                                                \
+            set_error("no plan: call lv_occ_plan_build first");                \
+            return LV_ESTATE;                                                  \
+        }                                                                      \
+    } while (0)
+
+// (parameters, table and counts are judged before the context, as lv_occ_configure's parameters are)
+int lv_occ_plan_build(lv_ctx* c, const lv_plan_params* p, const uint8_t* cost, size_t n_cost, const void* goals, size_t stride, size_t n_goals,
+                      uint64_t stats[4]) {
+    if (const char* why = plan_check(p, cost, n_cost, goals, stride, n_goals)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    if (const char* why = plan_check_field(p->connectivity, c->dist.prm.planar != 0)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
+    return c->plan.build(c->stream, c->dist, *p, cost, n_cost, goals, stride, n_goals, stats);
+}
+
+int lv_occ_plan_fetch(lv_ctx* c, uint32_t* potential, uint8_t* cell_cost, size_t capacity) {
+    if (!potential && !cell_cost) { set_error("lv_occ_plan_fetch: potential and cell_cost are both null"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_PLAN_BUILT(c);
+    if (capacity < c->plan.n_cells) { set_error("lv_occ_plan_fetch: room for %zu values needed", c->plan.n_cells); return LV_EINVAL; }
+    return c->plan.fetch(c->stream, potential, cell_cost);
+}
+
+int lv_occ_plan_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* cells,
+                      size_t capacity, size_t* total) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_PLAN_BUILT(c);
+    if (!offsets || !total || (n && (!starts || !status || !cost || stride < 12))) {
+        set_error("bad start array (stride %zu) or null status / cost / offsets / total", stride);
+        return LV_EINVAL;
+    }
+    if (n >= (size_t)0x7FFFFFFF) { set_error("%zu starts: one call takes fewer than 2^31 - 1", n); return LV_EINVAL; }
+    return c->plan.paths(c->stream, starts, stride, n, status, cost, offsets, cells, capacity, total);
+}
+
+int lv_occ_plan_info(lv_ctx* c, lv_plan_info* out) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    *out = lv_plan_info{};
+    if (c->plan.built) {
+        out->built = 1;
+        out->planar = c->plan.grid.planar;
+        out->nx = c->plan.grid.nx;
+        out->ny = c->plan.grid.ny;
+        out->nz = c->plan.grid.nz;
+        out->stale = c->plan.stale;
+        out->rounds = c->plan.rounds;
+        out->params = c->plan.prm;
+    }
+    return LV_OK;
+}
+
+int lv_occ_plan_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->plan.release();
     return LV_OK;
 }
 

@@ -1,0 +1,447 @@
+// lv_plan.hip — the cost-to-go planner over the distance field (include/limovelo_hip.h "Planner"; the rule's code is lv_plan.hpp).
+//
+// A build is a block-based label-correcting solver (the layout of the fast iterative method) on the context's stream:
+//   plan_cost_kernel    one lane per cell: the cost byte from s2 and the table, P = unreached.
+//   plan_seed_kernel    one lane per goal: P = 0 in its cell; its tile, and each neighbouring tile that has the cell in its halo,
+//                       active for the first round.
+//   plan_round_kernel   one workgroup of 256 per tile (32 x 32 cells planar, 8 x 8 x 8 in 3-D), one launch per round over all tiles; a
+//                       tile that is not active leaves at once.  An active one loads its cells and a one-cell halo of P and cost
+//                       into LDS, works out per cell the mask of allowed moves (plan_move_allowed on the LDS tile), and relaxes
+//                       (plan_relax) inside LDS until nothing changes, at most as often as the tile has cells.  Lowered values go
+//                       back to global memory (only the owner writes a cell), and the neighbouring tiles that see a lowered border
+//                       cell in their halo are marked active for the next round.  A halo read while the neighbour writes is safe:
+//                       every stored value is the cost of a real path and values only decrease, and the neighbour marks this tile
+//                       for the next round whenever it lowers what this tile may have read too early.
+//   plan_stats_kernel   traversable cells, reached cells and the largest finite P, folded per wavefront.
+// The rounds are driven by the host: PLAN_ROUNDS_PER_READ launches, then one read of that batch's round words ("this round lowered
+// something") through pinned memory.  The build is finished after the first round that lowered nothing.  No workgroup ever waits
+// for another one.  The fixpoint is unique, so the schedule does not show in the result.
+// lv_occ_plan_paths is one lane per start walking plan_next twice: a counting pass, an exclusive scan, a filling pass.
+#include "lv_plan.hpp"
+
+#include <hipcub/hipcub.hpp>
+
+#include <cstring>
+
+#include "lv_common.hpp"
+
+namespace lv {
+
+namespace {
+
+__global__ __launch_bounds__(256) void plan_cost_kernel(const int32_t* __restrict__ s2, int min_clear_s2, const uint8_t* __restrict__ table,
+                                                        int n_cost, uint32_t n, uint8_t* __restrict__ cost, uint32_t* __restrict__ pot) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    cost[v] = (uint8_t)plan_cell_cost(s2[v], min_clear_s2, table, n_cost);
+    pot[v] = PLAN_UNREACHED;
+}
+
+template <int TX, int TY, int TZ>
+__global__ __launch_bounds__(256) void plan_seed_kernel(PlanGrid g, const float* __restrict__ pts, uint32_t n, const uint8_t* __restrict__ cost,
+                                                        uint32_t* __restrict__ pot, uint32_t* __restrict__ active,
+                                                        unsigned long long* __restrict__ stats) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const float p[3] = {pts[3 * (size_t)q], pts[3 * (size_t)q + 1], pts[3 * (size_t)q + 2]};
+    int i, j, k;
+    if (!plan_cell_of(g, p, i, j, k)) return;
+    const size_t at = ((size_t)k * (size_t)g.ny + (size_t)j) * (size_t)g.nx + (size_t)i;
+    if (!cost[at]) return;
+    pot[at] = 0u;   // (several goals in one cell store the same value)
+    // the goal's tile, and every tile that holds the goal cell in its halo: a goal is never "lowered", so no round would wake them
+    const int tiles_x = (g.nx + TX - 1) / TX, tiles_y = (g.ny + TY - 1) / TY, tiles_z = (g.nz + TZ - 1) / TZ;
+    const int tx = i / TX, ty = j / TY, tz = k / TZ;
+    const int li = i - tx * TX, lj = j - ty * TY, lk = k - tz * TZ;
+    for (int mv = 0; mv < 27; ++mv) {
+        int dx, dy, dz;
+        plan_move(mv, dx, dy, dz);
+        if ((dx < 0 && li != 0) || (dx > 0 && li != TX - 1) || (dy < 0 && lj != 0) || (dy > 0 && lj != TY - 1) || (dz < 0 && lk != 0) ||
+            (dz > 0 && lk != TZ - 1))
+            continue;
+        const int ux = tx + dx, uy = ty + dy, uz = tz + dz;
+        if ((uint32_t)ux < (uint32_t)tiles_x && (uint32_t)uy < (uint32_t)tiles_y && (uint32_t)uz < (uint32_t)tiles_z)
+            active[((size_t)uz * (size_t)tiles_y + (size_t)uy) * (size_t)tiles_x + (size_t)ux] = 1u;
+    }
+    atomicAdd(&stats[0], 1ull);
+}
+
+// A workgroup's tile with its one-cell halo in LDS; coordinates are local to the tile, -1 .. T
+template <int TX, int TY, int TZ>
+struct PlanTile {
+    static constexpr int HZ = TZ > 1 ? 1 : 0;   // a planar field has no halo in z
+    static constexpr int LX = TX + 2, LY = TY + 2, LZ = TZ + 2 * HZ;
+    static constexpr int CELLS = TX * TY * TZ, LCELLS = LX * LY * LZ;
+    const uint8_t* c;
+    const uint32_t* p;
+    __device__ __forceinline__ static int at(int i, int j, int k) { return ((k + HZ) * LY + (j + 1)) * LX + (i + 1); }
+    __device__ __forceinline__ uint32_t cost(int i, int j, int k) const { return c[at(i, j, k)]; }
+    __device__ __forceinline__ uint32_t pot(int i, int j, int k) const { return p[at(i, j, k)]; }
+};
+
+enum : uint32_t { PLAN_F_AGAIN = 1u << 6, PLAN_F_LOWERED = 1u << 7 };   // above the six face bits
+
+template <int TX, int TY, int TZ>
+__global__ __launch_bounds__(256) void plan_round_kernel(PlanGrid g, const uint8_t* __restrict__ cost, uint32_t* pot, uint32_t* cur, uint32_t* nxt,
+                                                         uint32_t* round_word) {
+    using T = PlanTile<TX, TY, TZ>;
+    constexpr int NPT = T::CELLS / 256;   // cells per lane
+    static_assert(T::CELLS % 256 == 0, "a tile is a whole number of cells per lane");
+    __shared__ uint32_t sp[T::LCELLS];
+    __shared__ uint8_t sc[T::LCELLS];
+    __shared__ uint32_t s_flag, s_faces;
+    const uint32_t t = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) {
+        s_flag = cur[t];
+        cur[t] = 0u;   // (this buffer is `nxt` in the next round: clean by then)
+        s_faces = 0u;
+    }
+    __syncthreads();
+    if (!s_flag) return;   // (the whole workgroup)
+    const int tiles_x = (g.nx + TX - 1) / TX, tiles_y = (g.ny + TY - 1) / TY, tiles_z = (g.nz + TZ - 1) / TZ;
+    const int tx = (int)(t % (uint32_t)tiles_x), ty = (int)((t / (uint32_t)tiles_x) % (uint32_t)tiles_y), tz = (int)(t / (uint32_t)(tiles_x * tiles_y));
+    const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
+    for (int l = (int)tid; l < T::LCELLS; l += 256) {
+        const int gi = x0 + l % T::LX - 1, gj = y0 + (l / T::LX) % T::LY - 1, gk = z0 + l / (T::LX * T::LY) - T::HZ;
+        const bool in = (uint32_t)gi < (uint32_t)g.nx && (uint32_t)gj < (uint32_t)g.ny && (uint32_t)gk < (uint32_t)g.nz;
+        const size_t at = ((size_t)gk * (size_t)g.ny + (size_t)gj) * (size_t)g.nx + (size_t)gi;
+        sc[l] = in ? cost[at] : (uint8_t)0;
+        sp[l] = in ? pot[at] : PLAN_UNREACHED;
+    }
+    __syncthreads();
+    const T tile{sc, sp};
+    const int mv0 = TZ > 1 ? 0 : 9, mv1 = TZ > 1 ? 27 : 18;
+    uint32_t mask[NPT], first[NPT];
+    int at[NPT];
+#pragma unroll
+    for (int q = 0; q < NPT; ++q) {
+        const int c = (int)tid + q * 256;
+        const int i = c % TX, j = (c / TX) % TY, k = c / (TX * TY);
+        at[q] = T::at(i, j, k);
+        first[q] = sp[at[q]];
+        uint32_t m = 0;
+        for (int mv = mv0; mv < mv1; ++mv) {
+            int dx, dy, dz;
+            const int nz = plan_move(mv, dx, dy, dz);
+            if (nz != 0 && nz <= g.max_m && plan_move_allowed(tile, i, j, k, dx, dy, dz)) m |= 1u << mv;
+        }
+        mask[q] = m;   // (0 for a blocked cell and for one past the field's edge: its cost is 0)
+    }
+    int it = 0;
+    bool more = true;
+    for (; it < T::CELLS && more; ++it) {
+        bool changed = false;
+#pragma unroll
+        for (int q = 0; q < NPT; ++q) {
+            const uint32_t cv = sc[at[q]];
+            uint32_t best = sp[at[q]];
+            const uint32_t had = best;
+            for (uint32_t mm = mask[q]; mm; mm &= mm - 1u) {
+                int dx, dy, dz;
+                const int nz = plan_move(__builtin_ctz(mm), dx, dy, dz);
+                const int u = at[q] + (dz * T::LY + dy) * T::LX + dx;
+                const uint32_t cand = plan_relax(sp[u], sc[u], cv, plan_weight(nz));
+                best = cand < best ? cand : best;
+            }
+            if (best < had) {
+                sp[at[q]] = best;   // (a neighbour's lane may read the old or the new value: both are costs of real paths)
+                changed = true;
+            }
+        }
+        more = __syncthreads_or(changed) != 0;
+    }
+    uint32_t faces = more ? (uint32_t)PLAN_F_AGAIN : 0u;   // (the cap: not reachable; the tile would go on next round)
+#pragma unroll
+    for (int q = 0; q < NPT; ++q) {
+        const uint32_t now = sp[at[q]];
+        if (now < first[q]) {
+            const int c = (int)tid + q * 256;
+            const int i = c % TX, j = (c / TX) % TY, k = c / (TX * TY);
+            pot[((size_t)(z0 + k) * (size_t)g.ny + (size_t)(y0 + j)) * (size_t)g.nx + (size_t)(x0 + i)] = now;
+            faces |= PLAN_F_LOWERED | (i == 0 ? 1u : 0u) | (i == TX - 1 ? 2u : 0u) | (j == 0 ? 4u : 0u) | (j == TY - 1 ? 8u : 0u);
+            if (TZ > 1) faces |= (k == 0 ? 16u : 0u) | (k == TZ - 1 ? 32u : 0u);
+        }
+    }
+    if (faces) atomicOr(&s_faces, faces);
+    __syncthreads();
+    const uint32_t f = s_faces;
+    if (!f) return;
+    if (tid == 0 && (f & PLAN_F_LOWERED)) *round_word = 1u;
+    if (tid < 27) {
+        int dx, dy, dz;
+        const int nz = plan_move((int)tid, dx, dy, dz);
+        if (nz == 0) {
+            if (f & PLAN_F_AGAIN) nxt[t] = 1u;
+        } else {
+            const uint32_t need = (dx < 0 ? 1u : 0u) | (dx > 0 ? 2u : 0u) | (dy < 0 ? 4u : 0u) | (dy > 0 ? 8u : 0u) | (dz < 0 ? 16u : 0u) | (dz > 0 ? 32u : 0u);
+            const int ux = tx + dx, uy = ty + dy, uz = tz + dz;
+            if ((f & need) == need && (uint32_t)ux < (uint32_t)tiles_x && (uint32_t)uy < (uint32_t)tiles_y && (uint32_t)uz < (uint32_t)tiles_z)
+                nxt[((size_t)uz * (size_t)tiles_y + (size_t)uy) * (size_t)tiles_x + (size_t)ux] = 1u;
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long plan_wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long plan_wave_max(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// stats[1..3]: traversable cells, reached cells, the largest finite P (grid-stride: one atomic per counter and wavefront)
+__global__ __launch_bounds__(256) void plan_stats_kernel(const uint8_t* __restrict__ cost, const uint32_t* __restrict__ pot, uint32_t n,
+                                                         unsigned long long* __restrict__ stats) {
+    unsigned long long trav = 0, reached = 0, top = 0;
+    for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
+        trav += cost[v] != 0;
+        const uint32_t p = pot[v];
+        if (p != PLAN_UNREACHED) {
+            ++reached;
+            top = p > top ? p : top;
+        }
+    }
+    trav = plan_wave_sum(trav);
+    reached = plan_wave_sum(reached);
+    top = plan_wave_max(top);
+    if ((threadIdx.x & 63u) == 0) {
+        if (trav) atomicAdd(&stats[1], trav);
+        if (reached) atomicAdd(&stats[2], reached);
+        if (top) atomicMax(&stats[3], top);
+    }
+}
+
+// cnt[n] = 0 makes the exclusive scan's entry n the total
+template <bool FILL>
+__global__ __launch_bounds__(256) void plan_paths_kernel(PlanGrid g, const uint8_t* __restrict__ cost, const uint32_t* __restrict__ pot,
+                                                         const float* __restrict__ pts, uint32_t n, int32_t* __restrict__ status,
+                                                         uint32_t* __restrict__ pcost, unsigned long long* __restrict__ cnt,
+                                                         const unsigned long long* __restrict__ off, int32_t* __restrict__ cells) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q > n) return;
+    if (q == n) {
+        if (!FILL) cnt[n] = 0ull;
+        return;
+    }
+    const float p[3] = {pts[3 * (size_t)q], pts[3 * (size_t)q + 1], pts[3 * (size_t)q + 2]};
+    const PlanView f{cost, pot, g.nx, g.ny, g.nz};
+    int32_t st;
+    uint32_t pc;
+    const uint64_t len = plan_walk(g, f, p, &st, &pc, FILL ? cells + off[q] : nullptr);
+    if (!FILL) {
+        status[q] = st;
+        pcost[q] = pc;
+        cnt[q] = len;
+    }
+}
+
+inline uint32_t blocks_of(size_t n) { return (uint32_t)((n + 255) / 256); }
+
+}  // namespace
+
+void PlanStore::release() {
+    if (h_round) hipHostFree(h_round);
+    if (h_stats) hipHostFree(h_stats);
+    if (h_pts) hipHostFree(h_pts);
+    hipFree(d_cost);
+    hipFree(d_pot);
+    hipFree(d_active);
+    hipFree(d_table);
+    hipFree(d_round);
+    hipFree(d_stats);
+    hipFree(d_pts);
+    hipFree(d_status);
+    hipFree(d_pcost);
+    hipFree(d_cnt);
+    hipFree(d_off);
+    hipFree(d_cells);
+    hipFree(d_tmp);
+    *this = PlanStore();
+}
+
+// n points (goals or starts) of 3 floats into d_pts
+int PlanStore::stage(hipStream_t stream, const void* pts, size_t stride, size_t n) {
+    LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the pinned buffer may still be pending)
+    if (n > pts_cap) {
+        if (h_pts) hipHostFree(h_pts);
+        hipFree(d_pts);
+        h_pts = d_pts = nullptr;
+        pts_cap = 0;
+        LV_HIP(hipHostMalloc((void**)&h_pts, n * 3 * sizeof(float), hipHostMallocDefault));
+        LV_HIP(hipMalloc(&d_pts, n * 3 * sizeof(float)));
+        pts_cap = n;
+    }
+    const char* b = static_cast<const char*>(pts);
+    for (size_t i = 0; i < n; ++i) std::memcpy(h_pts + 3 * i, b + i * stride, 3 * sizeof(float));
+    LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    return LV_OK;
+}
+
+// room for the per-start outputs of n starts (status, cost; n + 1 counts and offsets)
+int PlanStore::reserve_starts(size_t n) {
+    if (n <= starts_cap) return LV_OK;
+    hipFree(d_status);
+    hipFree(d_pcost);
+    hipFree(d_cnt);
+    hipFree(d_off);
+    d_status = nullptr;
+    d_pcost = nullptr;
+    d_cnt = d_off = nullptr;
+    starts_cap = 0;
+    LV_HIP(hipMalloc(&d_status, n * sizeof(int32_t)));
+    LV_HIP(hipMalloc(&d_pcost, n * sizeof(uint32_t)));
+    LV_HIP(hipMalloc(&d_cnt, (n + 1) * sizeof(unsigned long long)));
+    LV_HIP(hipMalloc(&d_off, (n + 1) * sizeof(unsigned long long)));
+    starts_cap = n;
+    return LV_OK;
+}
+
+int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_params& p, const uint8_t* cost, size_t n_cost, const void* goals,
+                     size_t stride, size_t n_goals, uint64_t stats[4]) {
+    PlanGrid g{};
+    g.nx = dist.grid.nx;
+    g.ny = dist.grid.ny;
+    g.nz = dist.grid.nz;
+    g.planar = dist.prm.planar != 0;
+    g.max_m = plan_max_m(p.connectivity);
+    for (int a = 0; a < 3; ++a) g.origin[a] = dist.origin[a];
+    g.resolution = dist.grid.resolution;
+    const size_t nc = dist.n_vox;
+    const size_t nt = g.planar ? (size_t)((g.nx + 31) / 32) * (size_t)((g.ny + 31) / 32)
+                               : (size_t)((g.nx + 7) / 8) * (size_t)((g.ny + 7) / 8) * (size_t)((g.nz + 7) / 8);
+    int rc = stage(stream, goals, stride, n_goals);
+    if (rc) return rc;
+    if (nc > cap_cells) {
+        hipFree(d_cost);
+        hipFree(d_pot);
+        d_cost = nullptr;
+        d_pot = nullptr;
+        cap_cells = 0;
+        LV_HIP(hipMalloc(&d_cost, nc * sizeof(uint8_t)));
+        LV_HIP(hipMalloc(&d_pot, nc * sizeof(uint32_t)));
+        cap_cells = nc;
+    }
+    if (nt > cap_tiles) {
+        hipFree(d_active);
+        d_active = nullptr;
+        cap_tiles = 0;
+        LV_HIP(hipMalloc(&d_active, 2 * nt * sizeof(uint32_t)));
+        cap_tiles = nt;
+    }
+    if (!d_table) LV_HIP(hipMalloc(&d_table, PLAN_MAX_COST));
+    if (!d_round) LV_HIP(hipMalloc(&d_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t)));
+    if (!h_round) LV_HIP(hipHostMalloc((void**)&h_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t), hipHostMallocDefault));
+    if (!d_stats) LV_HIP(hipMalloc(&d_stats, 4 * sizeof(unsigned long long)));
+    if (!h_stats) LV_HIP(hipHostMalloc((void**)&h_stats, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    built = false;   // (the old plan's buffers are overwritten from here on; the new one stands when the rounds are through)
+    LV_HIP(hipMemcpyAsync(d_table, cost, n_cost, hipMemcpyHostToDevice, stream));
+    LV_HIP(hipMemsetAsync(d_active, 0, 2 * nt * sizeof(uint32_t), stream));
+    LV_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(plan_cost_kernel, dim3(blocks_of(nc)), dim3(256), 0, stream, dist.d_s2, p.min_clear_s2, d_table, (int)n_cost, (uint32_t)nc,
+                       d_cost, d_pot);
+    if (g.planar)
+        hipLaunchKernelGGL((plan_seed_kernel<32, 32, 1>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, d_pts, (uint32_t)n_goals, d_cost, d_pot,
+                           d_active, d_stats);
+    else
+        hipLaunchKernelGGL((plan_seed_kernel<8, 8, 8>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, d_pts, (uint32_t)n_goals, d_cost, d_pot,
+                           d_active, d_stats);
+    LV_HIP(hipGetLastError());
+    // the rounds: a batch of launches, then one look at the batch's words.  Once a round lowers nothing no later one does.
+    size_t done = 0;   // rounds launched so far
+    bool finished = false;
+    while (!finished) {
+        if (done > nc) { set_error("lv_occ_plan_build: no fixpoint after %zu rounds", done); return LV_ESTATE; }   // (not reachable)
+        LV_HIP(hipMemsetAsync(d_round, 0, PLAN_ROUNDS_PER_READ * sizeof(uint32_t), stream));
+        for (int r = 0; r < PLAN_ROUNDS_PER_READ; ++r) {
+            uint32_t* cur = d_active + ((done + (size_t)r) & 1) * nt;
+            uint32_t* nxt = d_active + ((done + (size_t)r + 1) & 1) * nt;
+            if (g.planar) hipLaunchKernelGGL((plan_round_kernel<32, 32, 1>), dim3((uint32_t)nt), dim3(256), 0, stream, g, d_cost, d_pot, cur, nxt, d_round + r);
+            else hipLaunchKernelGGL((plan_round_kernel<8, 8, 8>), dim3((uint32_t)nt), dim3(256), 0, stream, g, d_cost, d_pot, cur, nxt, d_round + r);
+        }
+        LV_HIP(hipGetLastError());
+        LV_HIP(hipMemcpyAsync(h_round, d_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        LV_HIP(hipStreamSynchronize(stream));
+        for (int r = 0; r < PLAN_ROUNDS_PER_READ && !finished; ++r) {
+            ++done;
+            finished = h_round[r] == 0;
+        }
+    }
+    hipLaunchKernelGGL(plan_stats_kernel, dim3(blocks_of(nc) < 1024u ? blocks_of(nc) : 1024u), dim3(256), 0, stream, d_cost, d_pot, (uint32_t)nc, d_stats);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = (uint64_t)h_stats[i];
+    prm = p;
+    grid = g;
+    n_cells = nc;
+    n_tiles = nt;
+    rounds = (int)done;
+    stale = 0;
+    built = true;
+    return LV_OK;
+}
+
+int PlanStore::fetch(hipStream_t stream, uint32_t* potential, uint8_t* cell_cost) {
+    if (potential) LV_HIP(hipMemcpyAsync(potential, d_pot, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (cell_cost) LV_HIP(hipMemcpyAsync(cell_cost, d_cost, n_cells * sizeof(uint8_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int PlanStore::paths(hipStream_t stream, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets,
+                     int32_t* cells, size_t capacity, size_t* total) {
+    *total = 0;
+    offsets[0] = 0;
+    if (n == 0) return LV_OK;
+    int rc = stage(stream, starts, stride, n);
+    if (!rc) rc = reserve_starts(n);
+    if (rc) return rc;
+    hipLaunchKernelGGL(plan_paths_kernel<false>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, d_pts, (uint32_t)n, d_status, d_pcost,
+                       d_cnt, (const unsigned long long*)nullptr, (int32_t*)nullptr);
+    LV_HIP(hipGetLastError());
+    size_t bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt, d_off, (int)(n + 1), stream));
+    if (bytes > tmp_cap) {
+        hipFree(d_tmp);
+        d_tmp = nullptr;
+        tmp_cap = 0;
+        LV_HIP(hipMalloc(&d_tmp, bytes));
+        tmp_cap = bytes;
+    }
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_cnt, d_off, (int)(n + 1), stream));
+    static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets are copied out as size_t");
+    LV_HIP(hipMemcpyAsync(offsets, d_off, (n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipMemcpyAsync(cost, d_pcost, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    const size_t tot = offsets[n];
+    *total = tot;
+    if (!cells) return LV_OK;   // count only: any total
+    if (capacity < tot) { set_error("capacity %zu < %zu path cells", capacity, tot); return LV_EINVAL; }
+    if (tot > (size_t)0x7FFFFFFF) {
+        set_error("%zu path cells: one call returns at most 2^31 - 1 (split the starts; the count-only call has no limit)", tot);
+        return LV_EINVAL;
+    }
+    if (tot == 0) return LV_OK;
+    if (tot > cells_cap) {
+        hipFree(d_cells);
+        d_cells = nullptr;
+        cells_cap = 0;
+        LV_HIP(hipMalloc(&d_cells, tot * sizeof(int32_t)));
+        cells_cap = tot;
+    }
+    hipLaunchKernelGGL(plan_paths_kernel<true>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, d_pts, (uint32_t)n, d_status, d_pcost,
+                       d_cnt, (const unsigned long long*)d_off, d_cells);
+    LV_HIP(hipGetLastError());
+    LV_HIP(hipMemcpyAsync(cells, d_cells, tot * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+}  // namespace lv

@@ -3,7 +3,9 @@ octomap_server's projected map hand to navigation.  integrate() takes any number
 the shape of nav_msgs/OccupancyGrid, save_grid / load_grid keep a grid as an .npz next to prelocalise.save_map's map, and
 map_point_states() tells which points of the device map lie in space that the accumulated evidence says is free.
 distance_field() / clearance() give the Euclidean distance to the nearest obstacle (lv_occ_distance_*, "Distance field") and
-costmap_from_distance() costmap_2d's inflation costs from it."""
+costmap_from_distance() costmap_2d's inflation costs from it.  plan() / routes() build the cost-to-go to a set of goals over that
+field and walk routes down it (lv_occ_plan_*, "Planner": navfn / global_planner), with inflation_cost_table() and min_clear_s2()
+turning costmap_2d's parameters into the planner's integer ones."""
 from __future__ import annotations
 
 import math
@@ -121,3 +123,63 @@ def costmap_from_distance(dist_m, inscribed_radius: float, inflation_radius: flo
         cost[(d > 0) & (d <= inscribed_radius)] = 253
         cost[d <= 0] = 254
     return cost
+
+
+def inflation_cost_table(resolution: float, inscribed_radius: float, inflation_radius: float, cost_scaling_factor: float = 10.0,
+                         neutral: int = 50) -> np.ndarray:
+    """The planner's cost table (uint8) from costmap_2d's inflation law: entry t is costmap_from_distance at t whole cells
+    (t * resolution metres) plus `neutral` (navfn's cost of a free cell), clamped to 1..255.  It runs to the first whole-cell
+    distance beyond inflation_radius, whose cost every farther cell shares (at most 1025 entries)."""
+    n = min(int(math.floor(float(inflation_radius) / float(resolution))) + 2, 1025) if inflation_radius > 0 else 2
+    d = np.arange(max(n, 1), dtype=np.float64) * float(resolution)
+    c = costmap_from_distance(d, inscribed_radius, inflation_radius, cost_scaling_factor).astype(np.int64) + int(neutral)
+    return np.clip(c, 1, 255).astype(np.uint8)
+
+
+def min_clear_s2(resolution: float, radius: float) -> int:
+    """The smallest integer s2 (>= 1) whose metre value resolution * sqrtf(s2), in f32 as the distance field computes it, is at
+    least radius: a cell is traversable iff its clearance reaches radius (and it is no obstacle)."""
+    F = np.float32
+    limit = 3 * 1023 * 1023
+    s = min(max(int(math.ceil((float(radius) / float(resolution)) ** 2)), 1), limit)
+
+    def metres(v):
+        return float(F(resolution) * np.sqrt(F(v)))
+
+    while s > 1 and metres(s - 1) >= radius:
+        s -= 1
+    while s < limit and metres(s) < radius:
+        s += 1
+    return s
+
+
+def plan(ctx, goals, robot_radius: float, inflation_radius: float | None = None, cost_scaling_factor: float = 10.0, neutral: int = 50,
+         connectivity: int | None = None):
+    """Builds the cost-to-go to `goals` ([n, 3] world points) over the distance field last built (distance_field() or
+    ctx.occ_distance_build) and returns (info, stats): lv_plan_info, and goals used, traversable cells, reached cells, the
+    largest finite potential.  Cells whose clearance is below robot_radius are blocked; the others cost what costmap_2d's
+    inflation law gives out to inflation_radius (default: 3 robot radii) plus `neutral`.  connectivity: default 8 on a planar
+    field, 26 on a 3-D one."""
+    res = float(ctx.occ_params().resolution)
+    if inflation_radius is None:
+        inflation_radius = 3.0 * robot_radius
+    if connectivity is None:
+        connectivity = 8 if ctx.occ_distance_info().planar else 26
+    table = inflation_cost_table(res, robot_radius, inflation_radius, cost_scaling_factor, neutral)
+    prm = capi.default_plan_params(connectivity=int(connectivity), min_clear_s2=min_clear_s2(res, robot_radius))
+    stats = ctx.occ_plan_build(goals, table, prm)
+    return ctx.occ_plan_info(), stats
+
+
+def routes(ctx, starts):
+    """Per start point (polyline, status, cost): the centres of the path's cells in world coordinates, [n, 3] f32 ([n, 2] in a planar
+    plan; empty unless status is 0), the status (0 a route, 1 no route from there, 2 the start is blocked or outside) and the
+    route's cost (the potential of the start cell, capi.LV_PLAN_UNREACHED without a route)."""
+    status, cost, off, cells = ctx.occ_plan_paths(starts)
+    i = ctx.occ_plan_info()
+    p = ctx.occ_params()
+    res = np.float64(p.resolution)
+    c = cells.astype(np.int64)
+    idx = [c % i.nx, (c // i.nx) % i.ny] + ([] if i.planar else [c // (i.nx * i.ny)])
+    xyz = np.stack([np.float64(p.origin[a]) + (v + 0.5) * res for a, v in enumerate(idx)], axis=1).astype(np.float32)
+    return [(xyz[int(off[s]):int(off[s + 1])], int(status[s]), int(cost[s])) for s in range(len(status))]
