@@ -928,7 +928,7 @@ int lv_map_remove_dynamic(lv_ctx* c, const lv_view* views, size_t n_views, const
         if (rc) return rc;
     }
     uint32_t nr = 0;
-    rc = vis_classify(c->map, c->stream, c->vis.d_blob, q, rank, hits ? c->vis.d_hits : nullptr, remove, &nr);
+    rc = vis_classify(c->map, c->stream, c->vis.d_blob, q, rank, hits ? c->vis.d_hits.p : nullptr, remove, &nr);
     if (rc) return rc;
     if (hits) LV_HIP(hipMemcpy(hits, c->vis.d_hits, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;
@@ -1115,7 +1115,7 @@ int lv_map_cluster(lv_ctx* c, const lv_cluster_params* p, const uint8_t* mask, i
     rc = c->query.ensure_rank(c->map, c->stream, &rank);
     if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
     if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
-    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask : nullptr);
+    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask.p : nullptr);
     size_t C = 0;
     if (!rc) rc = cluster_labels(c->map, c->stream, c->cluster, q, rank, labels != nullptr, &C);
     if (rc) return rc;
@@ -1154,9 +1154,9 @@ int lv_map_remove_clusters(lv_ctx* c, const lv_cluster_params* p, const uint8_t*
     if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
     if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
     if (!rc && seeds) rc = cluster_upload(c, c->cluster.d_seeds, seeds, m);
-    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask : nullptr);
+    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask.p : nullptr);
     uint32_t nr = 0;
-    if (!rc) rc = cluster_remove(c->map, c->stream, c->cluster, q, rank, c->cluster.d_seeds, flags ? c->cluster.d_flags : nullptr, remove, &nr);
+    if (!rc) rc = cluster_remove(c->map, c->stream, c->cluster, q, rank, c->cluster.d_seeds, flags ? c->cluster.d_flags.p : nullptr, remove, &nr);
     if (rc) return rc;
     if (flags) LV_HIP(hipMemcpy(flags, c->cluster.d_flags, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;

@@ -450,17 +450,6 @@ __global__ __launch_bounds__(B_FOLD_THREADS) void batch_solve_kernel(BatchHyp* _
 // ---- host ----------------------------------------------------------------------------------------------------------------
 namespace {
 
-template <class T>
-int grow(T** p, size_t& cap, size_t need) {
-    if (need <= cap) return LV_OK;
-    if (*p) LV_HIP(hipFree(*p));
-    *p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(reinterpret_cast<void**>(p), need * sizeof(T)));
-    cap = need;
-    return LV_OK;
-}
-
 template <int K>
 void launch_batch_pass(hipStream_t s, const MapView& map, const float4* scan, uint32_t n, BatchHyp* hyps, uint32_t mc, float4* qrec,
                        uint32_t qstride, double* part, int nfit, const MatchParams& mp, KfDev* sink) {
@@ -491,22 +480,17 @@ int BatchStore::run(const lv_params& prm, int max_blocks, const MapView& map, co
     const size_t chunk = chunk_size(n, K);
     const int nfit = fit_grid_size(n, max_blocks);
     const size_t mc_max = chunk < m ? chunk : m;
-    int rc = grow(&d_hyp, hyp_cap, m);
-    if (!rc) rc = grow(&d_qrec, qrec_cap, mc_max * qrec_slots(K) * (size_t)n);
-    if (!rc) rc = grow(&d_part, part_cap, mc_max * (size_t)nfit * SUMS_LEN);
+    int rc = d_hyp.need(m);
+    if (!rc) rc = d_qrec.need(mc_max * qrec_slots(K) * (size_t)n);
+    if (!rc) rc = d_part.need(mc_max * (size_t)nfit * SUMS_LEN);
     if (!rc && !d_sink) {
-        LV_HIP(hipMalloc(&d_sink, sizeof(KfDev)));
-        LV_HIP(hipMemsetAsync(d_sink, 0, sizeof(KfDev), stream));
+        rc = d_sink.need(1);
+        if (!rc) LV_HIP(hipMemsetAsync(d_sink, 0, sizeof(KfDev), stream));
     }
+    // (every call ends with a wait on the stream: nothing reads the pinned records when they grow)
+    if (!rc) rc = h_hyp.need(m);
     if (rc) return rc;
     // every hypothesis starts as lv_update's first pass does: x_prop = x, P_prop = P_post = P, the pass constants from the host
-    if (m > h_cap) {
-        if (h_hyp) LV_HIP(hipHostFree(h_hyp));
-        h_hyp = nullptr;
-        h_cap = 0;
-        LV_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_hyp), m * sizeof(BatchHyp), hipHostMallocDefault));
-        h_cap = m;
-    }
     for (size_t i = 0; i < m; ++i) {
         BatchHyp& h = h_hyp[i];
         std::memset(&h, 0, sizeof(h));
@@ -568,19 +552,12 @@ int BatchStore::run(const lv_params& prm, int max_blocks, const MapView& map, co
     return LV_OK;
 }
 
-void BatchStore::release() {
-    hipFree(d_hyp);
-    hipFree(d_qrec);
-    hipFree(d_part);
-    hipFree(d_sink);
-    hipHostFree(h_hyp);
-    h_hyp = nullptr;
-    h_cap = 0;
-    d_hyp = nullptr;
-    d_qrec = nullptr;
-    d_part = nullptr;
-    d_sink = nullptr;
-    hyp_cap = qrec_cap = part_cap = 0;
+void BatchStore::release() {   // (chunk_hyp, an option of the context, stays)
+    d_hyp.release();
+    d_qrec.release();
+    d_part.release();
+    d_sink.release();
+    h_hyp.release();
 }
 
 }  // namespace lv

@@ -195,58 +195,25 @@ __global__ __launch_bounds__(256) void cluster_classify_kernel(float4* __restric
     orig[id].x = c_inf();
 }
 
-template <class T>
-int grow(T*& p, size_t n) {
-    if (p) hipFree(p);
-    p = nullptr;
-    LV_HIP(hipMalloc((void**)&p, n * sizeof(T)));
-    return LV_OK;
-}
-
-inline uint32_t grid_of(size_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
-int ensure_tmp(ClusterStore& st, size_t bytes) {
-    if (bytes <= st.tmp_cap && st.d_tmp) return LV_OK;
-    if (st.d_tmp) hipFree(st.d_tmp);
-    st.d_tmp = nullptr;
-    st.tmp_cap = 0;
-    LV_HIP(hipMalloc(&st.d_tmp, bytes ? bytes : 1));
-    st.tmp_cap = bytes;
-    return LV_OK;
-}
-
 }  // namespace
 
 int ClusterStore::ensure(size_t n_ids, size_t m) {
-    int rc = LV_OK;
-    if (n_ids > id_cap) {
-        id_cap = 0;
-        rc = grow(d_parent, n_ids);
-        if (!rc) rc = grow(d_size, n_ids);
-        if (!rc) rc = grow(d_lab, n_ids);
-        if (!rc) rc = grow(d_flag, n_ids);
-        if (!rc) rc = grow(d_pos, n_ids + 1);
-        if (rc) return rc;
-        id_cap = n_ids;
-    }
-    if (m > m_cap) {
-        m_cap = 0;
-        rc = grow(d_labels, m);
-        if (!rc) rc = grow(d_mask, m);
-        if (!rc) rc = grow(d_seeds, m);
-        if (!rc) rc = grow(d_flags, m);
-        if (rc) return rc;
-        m_cap = m;
-    }
-    if (!h_word) LV_HIP(hipHostMalloc((void**)&h_word, 4 * sizeof(uint32_t), hipHostMallocDefault));
-    return LV_OK;
+    int rc = d_parent.need(n_ids);
+    if (!rc) rc = d_size.need(n_ids);
+    if (!rc) rc = d_lab.need(n_ids);
+    if (!rc) rc = d_flag.need(n_ids);
+    if (!rc) rc = d_pos.need(n_ids + 1);
+    if (!rc) rc = d_labels.need(m);
+    if (!rc) rc = d_mask.need(m);
+    if (!rc) rc = d_seeds.need(m);
+    if (!rc) rc = d_flags.need(m);
+    if (!rc) rc = h_word.need(4);
+    return rc;
 }
 
 void ClusterStore::release() {
-    hipFree(d_parent); hipFree(d_size); hipFree(d_lab); hipFree(d_flag); hipFree(d_pos); hipFree(d_key); hipFree(d_key2); hipFree(d_labels);
-    hipFree(d_sizes); hipFree(d_mask); hipFree(d_seeds); hipFree(d_flags); hipFree(d_tmp);
-    if (h_word) hipHostFree(h_word);
-    *this = ClusterStore();
+    d_parent.release(); d_size.release(); d_lab.release(); d_flag.release(); d_pos.release(); d_key.release(); d_key2.release();
+    d_labels.release(); d_sizes.release(); d_mask.release(); d_seeds.release(); d_flags.release(); d_tmp.release(); h_word.release();
 }
 
 int cluster_components(const MapStore& map, hipStream_t stream, ClusterStore& st, const ClusterRule& q, const uint32_t* rank, const uint8_t* mask) {
@@ -255,11 +222,11 @@ int cluster_components(const MapStore& map, hipStream_t stream, ClusterStore& st
     // (one wavefront per id: a launch takes fewer than 2^32 threads)
     if (map.n_ids > 0x03FFFFF0u) { set_error("map of %u ids: clustering takes at most %u", map.n_ids, 0x03FFFFF0u); return LV_EINVAL; }
     const uint32_t ids = map.n_ids;
-    hipLaunchKernelGGL(cluster_init_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, mask, st.d_parent, st.d_size, st.d_lab);
+    hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, mask, st.d_parent, st.d_size, st.d_lab);
     LV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cluster_link_kernel, dim3(grid_of(ids, CWAVES)), dim3(CTHREADS), 0, stream, v, q.radius, st.d_parent);
+    hipLaunchKernelGGL(cluster_link_kernel, dim3(blocks_of(ids, CWAVES)), dim3(CTHREADS), 0, stream, v, q.radius, st.d_parent);
     LV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, ids, st.d_parent, st.d_size);
+    hipLaunchKernelGGL(cluster_flatten_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, ids, st.d_parent, st.d_size);
     LV_HIP(hipGetLastError());
     return LV_OK;
 }
@@ -269,13 +236,13 @@ int cluster_labels(const MapStore& map, hipStream_t stream, ClusterStore& st, co
     *n_clusters = 0;
     const uint32_t ids = map.n_ids;
     if (ids == 0) return LV_OK;
-    hipLaunchKernelGGL(cluster_flag_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, ids, st.d_parent, st.d_size, q, st.d_flag);
+    hipLaunchKernelGGL(cluster_flag_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, ids, st.d_parent, st.d_size, q, st.d_flag);
     LV_HIP(hipGetLastError());
     size_t bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, st.d_flag, st.d_pos, (int)ids, stream));
-    int rc = ensure_tmp(st, bytes);
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, st.d_flag.p, st.d_pos.p, (int)ids, stream));
+    int rc = st.d_tmp.need(bytes ? bytes : 1);
     if (rc) return rc;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(st.d_tmp, bytes, st.d_flag, st.d_pos, (int)ids, stream));
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(st.d_tmp.p, bytes, st.d_flag.p, st.d_pos.p, (int)ids, stream));
     hipLaunchKernelGGL(cluster_total_kernel, dim3(1), dim3(64), 0, stream, st.d_pos, st.d_flag, ids, st.d_pos + ids);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(st.h_word, st.d_pos + ids, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -283,26 +250,22 @@ int cluster_labels(const MapStore& map, hipStream_t stream, ClusterStore& st, co
     const uint32_t C = st.h_word[0];
     *n_clusters = C;
     if (C) {
-        if (C > st.key_cap) {
-            st.key_cap = 0;
-            rc = grow(st.d_key, C);
-            if (!rc) rc = grow(st.d_key2, C);
-            if (!rc) rc = grow(st.d_sizes, C);
-            if (rc) return rc;
-            st.key_cap = C;
-        }
-        hipLaunchKernelGGL(cluster_key_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, ids, st.d_flag, st.d_pos, st.d_size, st.d_key);
+        rc = st.d_key.need(C);
+        if (!rc) rc = st.d_key2.need(C);
+        if (!rc) rc = st.d_sizes.need(C);
+        if (rc) return rc;
+        hipLaunchKernelGGL(cluster_key_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, ids, st.d_flag, st.d_pos, st.d_size, st.d_key);
         LV_HIP(hipGetLastError());
         bytes = 0;
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, st.d_key, st.d_key2, (int)C, 0, 64, stream));
-        rc = ensure_tmp(st, bytes);
+        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, st.d_key.p, st.d_key2.p, (int)C, 0, 64, stream));
+        rc = st.d_tmp.need(bytes ? bytes : 1);
         if (rc) return rc;
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortKeys(st.d_tmp, bytes, st.d_key, st.d_key2, (int)C, 0, 64, stream));
-        hipLaunchKernelGGL(cluster_number_kernel, dim3(grid_of(C, 256)), dim3(256), 0, stream, st.d_key2, C, st.d_lab, st.d_sizes);
+        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortKeys(st.d_tmp.p, bytes, st.d_key.p, st.d_key2.p, (int)C, 0, 64, stream));
+        hipLaunchKernelGGL(cluster_number_kernel, dim3(blocks_of(C, 256)), dim3(256), 0, stream, st.d_key2, C, st.d_lab, st.d_sizes);
         LV_HIP(hipGetLastError());
     }
     if (want_labels) {
-        hipLaunchKernelGGL(cluster_scatter_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_lab, st.d_labels);
+        hipLaunchKernelGGL(cluster_scatter_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_lab, st.d_labels);
         LV_HIP(hipGetLastError());
     }
     LV_HIP(hipStreamSynchronize(stream));
@@ -315,14 +278,14 @@ int cluster_remove(MapStore& map, hipStream_t stream, ClusterStore& st, const Cl
     const uint32_t ids = map.n_ids;
     if (!map.built || map.m == 0 || ids == 0) return LV_OK;
     if (q.seeded) {
-        hipLaunchKernelGGL(cluster_seed_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, ids, rank, st.d_parent, seeds, st.d_lab);
+        hipLaunchKernelGGL(cluster_seed_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, ids, rank, st.d_parent, seeds, st.d_lab);
         LV_HIP(hipGetLastError());
     }
     int rc = map.ensure_counters();
     if (rc) return rc;
     // n_new .. dropped are contiguous (MapCounters; lv_map.hip reset_batch_counters)
     LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
-    hipLaunchKernelGGL(cluster_classify_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_size, st.d_lab, q,
+    hipLaunchKernelGGL(cluster_classify_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_size, st.d_lab, q,
                        flags, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {

@@ -114,21 +114,20 @@ struct ClusterRule {
 
 // The buffers of lv_map_cluster / lv_map_remove_clusters (grown on demand, kept)
 struct ClusterStore {
-    uint32_t* d_parent = nullptr;   // by id: the union-find, then (flattened) every included id's root
-    uint32_t* d_size = nullptr;     // by id: at a root, the size of its component
-    int32_t* d_lab = nullptr;       // by id: at a root, its cluster's label or -1; removal: 1 at a root whose component holds a seed
-    uint32_t* d_flag = nullptr;     // by id: 1 at a reported root; d_pos: its exclusive scan (n_ids + 1: the last entry is C)
-    uint32_t* d_pos = nullptr;
-    uint64_t* d_key = nullptr;      // the reported roots' order keys, and their sorted copy
-    uint64_t* d_key2 = nullptr;
-    int32_t* d_labels = nullptr;    // outputs at living ranks
-    uint32_t* d_sizes = nullptr;    // sizes in cluster order
-    uint8_t* d_mask = nullptr;      // the caller's mask / seeds / the flags returned, at living ranks
-    uint8_t* d_seeds = nullptr;
-    uint8_t* d_flags = nullptr;
-    void* d_tmp = nullptr;          // hipcub scratch
-    uint32_t* h_word = nullptr;     // pinned: C read back by the host
-    size_t id_cap = 0, key_cap = 0, m_cap = 0, tmp_cap = 0;
+    DevBuf<uint32_t> d_parent;      // by id: the union-find, then (flattened) every included id's root
+    DevBuf<uint32_t> d_size;        // by id: at a root, the size of its component
+    DevBuf<int32_t> d_lab;          // by id: at a root, its cluster's label or -1; removal: 1 at a root whose component holds a seed
+    DevBuf<uint32_t> d_flag;        // by id: 1 at a reported root; d_pos: its exclusive scan (n_ids + 1: the last entry is C)
+    DevBuf<uint32_t> d_pos;
+    DevBuf<uint64_t> d_key;         // the reported roots' order keys, and their sorted copy
+    DevBuf<uint64_t> d_key2;
+    DevBuf<int32_t> d_labels;       // outputs at living ranks
+    DevBuf<uint32_t> d_sizes;       // sizes in cluster order
+    DevBuf<uint8_t> d_mask;         // the caller's mask / seeds / the flags returned, at living ranks
+    DevBuf<uint8_t> d_seeds;
+    DevBuf<uint8_t> d_flags;
+    DevBuf<void> d_tmp;             // hipcub scratch
+    PinBuf<uint32_t> h_word;        // C read back by the host
     int ensure(size_t n_ids, size_t m);
     void release();
 };

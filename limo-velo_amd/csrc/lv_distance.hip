@@ -169,48 +169,25 @@ __global__ __launch_bounds__(256) void dist_query_kernel(const int32_t* __restri
     }
 }
 
-inline uint32_t blocks_of(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 }  // namespace
 
 void DistStore::release() {
-    if (h_pts) hipHostFree(h_pts);
-    if (h_stats) hipHostFree(h_stats);
-    hipFree(d_s2);
-    hipFree(d_tmp);
-    hipFree(d_bits);
-    hipFree(d_stats);
-    hipFree(d_part);
-    hipFree(d_pts);
-    hipFree(d_out);
+    d_s2.release(); d_tmp.release(); d_bits.release(); d_part.release(); stats.release(); pts.release(); d_out.release();
     *this = DistStore();
 }
 
-int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t stats[4]) {
+int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t out[4]) {
     const DistGrid g = dist_grid_of(occ.grid, p);
     const size_t nv = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
     const size_t nw = (size_t)g.wx * (size_t)g.ny * (size_t)g.nz;
     LV_HIP(hipStreamSynchronize(stream));
-    if (nv > cap_vox || nw > cap_words) {
-        built = false;
-        hipFree(d_s2);
-        hipFree(d_tmp);
-        hipFree(d_bits);
-        hipFree(d_part);
-        d_s2 = d_tmp = nullptr;
-        d_bits = nullptr;
-        d_part = nullptr;
-        cap_vox = cap_words = 0;
-        LV_HIP(hipMalloc(&d_s2, nv * sizeof(int32_t)));
-        LV_HIP(hipMalloc(&d_tmp, nv * sizeof(int32_t)));
-        LV_HIP(hipMalloc(&d_bits, nw * sizeof(uint32_t)));
-        LV_HIP(hipMalloc(&d_part, (size_t)blocks_of(nv) * 4 * sizeof(unsigned long long)));
-        cap_vox = nv;
-        cap_words = nw;
-    }
-    if (!d_stats) LV_HIP(hipMalloc(&d_stats, 4 * sizeof(unsigned long long)));
-    if (!h_stats) LV_HIP(hipHostMalloc((void**)&h_stats, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-    built = false;   // (until the passes are through)
+    built = false;   // (before a buffer goes, and until the passes are through)
+    int rc = d_s2.need(nv);
+    if (!rc) rc = d_tmp.need(nv);
+    if (!rc) rc = d_bits.need(nw);
+    if (!rc) rc = d_part.need((size_t)blocks_of(nv) * 4);
+    if (!rc) rc = stats.need();
+    if (rc) return rc;
     const int k0 = p.k_lo < 0 ? 0 : p.k_lo, k1 = p.k_hi >= occ.grid.nz ? occ.grid.nz - 1 : p.k_hi;
     const size_t rows = (size_t)g.ny * (size_t)g.nz;
     const uint32_t n_waves = (uint32_t)(rows * (((size_t)g.nx + 63) / 64));
@@ -219,12 +196,10 @@ int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_
     hipLaunchKernelGGL(dist_x_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_bits, g, (uint32_t)nv, d_s2);
     hipLaunchKernelGGL(dist_y_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_s2, g, (uint32_t)nv, d_tmp);
     hipLaunchKernelGGL(dist_z_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_tmp, g, p.max_cells, (uint32_t)nv, d_s2, d_part);
-    hipLaunchKernelGGL(dist_stats_kernel, dim3(1), dim3(1024), 0, stream, d_part, blocks_of(nv), d_stats);
+    hipLaunchKernelGGL(dist_stats_kernel, dim3(1), dim3(1024), 0, stream, d_part, blocks_of(nv), stats.d);
     LV_HIP(hipGetLastError());
-    LV_HIP(hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    if (stats)
-        for (int i = 0; i < 4; ++i) stats[i] = (uint64_t)h_stats[i];
+    rc = stats.read(stream, out);
+    if (rc) return rc;
     prm = p;
     grid = g;
     for (int a = 0; a < 3; ++a) origin[a] = occ.grid.origin[a];
@@ -237,7 +212,7 @@ int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_
 int DistStore::fetch(hipStream_t stream, int32_t* s2, float* metres) {
     if (metres) {
         hipLaunchKernelGGL(dist_metres_kernel, dim3(blocks_of(n_vox)), dim3(256), 0, stream, d_s2, grid.resolution, (uint32_t)n_vox,
-                           reinterpret_cast<float*>(d_tmp));
+                           reinterpret_cast<float*>(d_tmp.p));
         LV_HIP(hipGetLastError());
         LV_HIP(hipMemcpyAsync(metres, d_tmp, n_vox * sizeof(float), hipMemcpyDeviceToHost, stream));
     }
@@ -246,26 +221,17 @@ int DistStore::fetch(hipStream_t stream, int32_t* s2, float* metres) {
     return LV_OK;
 }
 
-int DistStore::query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* dist, float* grad) {
+int DistStore::query(hipStream_t stream, const void* points, size_t stride, size_t n, float* dist, float* grad) {
     if (n == 0) return LV_OK;
-    LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the pinned buffer may still be pending)
-    if (n > pts_cap) {
-        if (h_pts) hipHostFree(h_pts);
-        hipFree(d_pts);
-        hipFree(d_out);
-        h_pts = d_pts = d_out = nullptr;
-        pts_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&h_pts, n * 3 * sizeof(float), hipHostMallocDefault));
-        LV_HIP(hipMalloc(&d_pts, n * 3 * sizeof(float)));
-        LV_HIP(hipMalloc(&d_out, n * 4 * sizeof(float)));
-        pts_cap = n;
-    }
-    const char* b = static_cast<const char*>(pts);
-    for (size_t i = 0; i < n; ++i) std::memcpy(h_pts + 3 * i, b + i * stride, 3 * sizeof(float));
-    LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+    int rc = pts.reserve(stream, n);
+    if (!rc) rc = d_out.need(4 * n);
+    if (rc) return rc;
+    pts.append(points, stride, n);
+    rc = pts.upload(stream);
+    if (rc) return rc;
     DistOrigin o;
     std::memcpy(o.o, origin, sizeof(o.o));
-    hipLaunchKernelGGL(dist_query_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_s2, grid, o, prm.planar != 0, d_pts, (uint32_t)n,
+    hipLaunchKernelGGL(dist_query_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_s2, grid, o, prm.planar != 0, pts.d, (uint32_t)n,
                        grad != nullptr, d_out);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(dist, d_out, n * sizeof(float), hipMemcpyDeviceToHost, stream));

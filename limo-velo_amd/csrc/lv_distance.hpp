@@ -191,20 +191,16 @@ struct DistStore {
     lv_distance_params prm{};
     DistGrid grid{};
     float origin[3] = {0.f, 0.f, 0.f};
-    size_t n_vox = 0, cap_vox = 0;   // of the field; of the two value buffers
-    size_t cap_words = 0;
-    int32_t* d_s2 = nullptr;         // the field: (k * ny + j) * nx + i
-    int32_t* d_tmp = nullptr;        // the Y pass's output; lv_occ_distance_fetch's metres
-    uint32_t* d_bits = nullptr;      // obstacle bitmap, the occupancy bitmaps' layout
-    unsigned long long* d_part = nullptr;    // one record of 4 per workgroup of the Z pass
-    unsigned long long* d_stats = nullptr;
-    unsigned long long* h_stats = nullptr;   // pinned
-    float* h_pts = nullptr;          // pinned staging of the query points
-    float* d_pts = nullptr;
-    float* d_out = nullptr;          // per point dist, then grad[3]
-    size_t pts_cap = 0;
+    size_t n_vox = 0;                // of the field
+    DevBuf<int32_t> d_s2;            // the field: (k * ny + j) * nx + i
+    DevBuf<int32_t> d_tmp;           // the Y pass's output; lv_occ_distance_fetch's metres
+    DevBuf<uint32_t> d_bits;         // obstacle bitmap, the occupancy bitmaps' layout
+    DevBuf<unsigned long long> d_part;   // one record of 4 per workgroup of the Z pass
+    Counters4 stats;
+    PointStage pts;                  // the query points
+    DevBuf<float> d_out;             // per point dist, then grad[3]
 
-    int build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t stats[4]);
+    int build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t out[4]);
     int fetch(hipStream_t stream, int32_t* s2, float* metres);
     int query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* dist, float* grad);
     void release();

@@ -9,6 +9,7 @@
 #include "../../include/limovelo_hip.h"
 #include "lv_device.hpp"
 #include "lv_common.hpp"
+#include "lv_buffers.hpp"
 #include "lv_exchange.hpp"
 #include "lv_mapinc.hpp"
 
@@ -188,23 +189,21 @@ struct MapStore {
 // Map queries (lv_query.hip): batched k-NN / radius / box searches of arbitrary points against the active store.  Owns its staging
 // and result buffers (grown on demand, freed by release); nothing here is shared with the update or the background rebuild.
 struct QueryStore {
-    float* d_q = nullptr;          // queries, packed xyz
-    uint32_t* d_idx = nullptr;     // k-NN: n x k results; radius: the ids found; box: the ranks found
-    float* d_d2 = nullptr;         // k-NN / radius: their distances; box: their xyz
-    int32_t* d_found = nullptr;
-    uint32_t* d_idx2 = nullptr;    // radius: the segmented sort's output
-    float* d_d22 = nullptr;
-    uint32_t* d_off = nullptr;     // box: positions (n_ids + 1)
-    uint32_t* d_cnt = nullptr;     // box: flags by id
-    uint64_t* d_roff = nullptr;    // radius: per-query counts -> exclusive offsets of the queries' segments (n + 1), 64-bit
-    uint64_t* d_rcnt = nullptr;
-    void* d_tmp = nullptr;         // hipcub scratch
-    uint32_t* d_rank = nullptr;    // rank among the living by id, valid for the map whose stamp is rank_gen
-    uint32_t* d_flag = nullptr;
-    size_t q_cap = 0, idx_cap = 0, d2_cap = 0, found_cap = 0, idx2_cap = 0, d22_cap = 0, off_cap = 0, cnt_cap = 0, roff_cap = 0, rcnt_cap = 0, tmp_cap = 0, rank_cap = 0,
-           flag_cap = 0;
+    PointStage pts;                // queries, packed xyz (doubling from QUERY_FLOOR floats)
+    DevBuf<uint32_t> d_idx;        // k-NN: n x k results; radius: the ids found; box: the ranks found
+    DevBuf<float> d_d2;            // k-NN / radius: their distances; box: their xyz
+    DevBuf<int32_t> d_found;
+    DevBuf<uint32_t> d_idx2;       // radius: the segmented sort's output
+    DevBuf<float> d_d22;
+    DevBuf<uint32_t> d_off;        // box: positions (n_ids + 1)
+    DevBuf<uint32_t> d_cnt;        // box: flags by id
+    DevBuf<uint64_t> d_roff;       // radius: per-query counts -> exclusive offsets of the queries' segments (n + 1), 64-bit
+    DevBuf<uint64_t> d_rcnt;
+    DevBuf<void> d_tmp;            // hipcub scratch
+    DevBuf<uint32_t> d_rank;       // rank among the living by id, valid for the map whose stamp is rank_gen
+    DevBuf<uint32_t> d_flag;
     uint64_t rank_gen = 0;
-    uint32_t* h_word = nullptr;    // pinned: a total read back by the host
+    PinBuf<uint32_t> h_word;       // a total read back by the host
     int stage_queries(hipStream_t stream, const void* q, size_t stride, size_t n);
     // nullptr when ranks equal ids (no dead id); else d_rank, rebuilt when the map's stamp moved
     int ensure_rank(const MapStore& map, hipStream_t stream, const uint32_t** rank);
@@ -225,12 +224,11 @@ struct BatchHyp;
 // more is processed chunk after chunk (results do not depend on the chunking)
 constexpr size_t BATCH_RECORD_BUDGET = (size_t)256 << 20;
 struct BatchStore {
-    BatchHyp* d_hyp = nullptr;
-    BatchHyp* h_hyp = nullptr;     // pinned
-    float4* d_qrec = nullptr;
-    double* d_part = nullptr;
-    KfDev* d_sink = nullptr;
-    size_t hyp_cap = 0, h_cap = 0, qrec_cap = 0, part_cap = 0;
+    DevBuf<BatchHyp> d_hyp;
+    PinBuf<BatchHyp> h_hyp;
+    DevBuf<float4> d_qrec;
+    DevBuf<double> d_part;
+    DevBuf<KfDev> d_sink;
     int chunk_hyp = 0;             // lv_set_option "batch_chunk_hypotheses": at most this many hypotheses per chunk (0: the budget alone)
     size_t chunk_size(uint32_t n, int num_match) const;
     // m hypotheses xs (prior covariance P) against the map and the scan (n sorted points): solve = false runs one pass without

@@ -154,19 +154,10 @@ __global__ __launch_bounds__(256) void occ_query_kernel(const float* __restrict_
     out[i] = v;
 }
 
-inline uint32_t grid_of(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 }  // namespace
 
 void OccStore::release() {
-    if (h_pts) hipHostFree(h_pts);
-    if (h_stats) hipHostFree(h_stats);
-    hipFree(d_L);
-    hipFree(d_bits);
-    hipFree(d_stats);
-    hipFree(d_pts);
-    hipFree(d_out);
-    hipFree(d_proj);
+    d_L.release(); d_bits.release(); stats.release(); pts.release(); d_out.release(); d_proj.release();
     *this = OccStore();
 }
 
@@ -176,17 +167,17 @@ int OccStore::configure(hipStream_t stream, const lv_occupancy_params& p) {
     const OccGrid g = occ_grid_of(p);
     const size_t nv = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
     const size_t nw = (((size_t)g.wx * (size_t)p.ny * (size_t)p.nz) + 3) & ~(size_t)3;
-    LV_HIP(hipMalloc(&d_L, nv * sizeof(float)));
-    LV_HIP(hipMalloc(&d_bits, 2 * nw * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&d_stats, 4 * sizeof(unsigned long long)));
-    LV_HIP(hipMalloc(&d_proj, (size_t)p.nx * (size_t)p.ny));
-    LV_HIP(hipHostMalloc((void**)&h_stats, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+    int rc = d_L.need(nv);
+    if (!rc) rc = d_bits.need(2 * nw);
+    if (!rc) rc = d_proj.need((size_t)p.nx * (size_t)p.ny);
+    if (!rc) rc = stats.need();
+    if (rc) return rc;
     LV_HIP(hipMemsetAsync(d_bits, 0, 2 * nw * sizeof(uint32_t), stream));
     prm = p;
     grid = g;
     n_vox = nv;
     n_words = nw;
-    const int rc = clear(stream);
+    rc = clear(stream);
     if (rc) return rc;
     configured = true;
     return LV_OK;
@@ -198,40 +189,19 @@ int OccStore::clear(hipStream_t stream) {
     return LV_OK;
 }
 
-// room for n_points packed points in the pinned and the device staging buffers
-int OccStore::stage(hipStream_t stream, size_t n_points) {
-    LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the pinned buffer may still be pending)
-    if (n_points > h_pts_cap) {
-        if (h_pts) hipHostFree(h_pts);
-        h_pts = nullptr;
-        h_pts_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&h_pts, n_points * 3 * sizeof(float), hipHostMallocDefault));
-        h_pts_cap = n_points;
-    }
-    if (n_points > d_pts_cap) {
-        hipFree(d_pts);
-        d_pts = nullptr;
-        d_pts_cap = 0;
-        LV_HIP(hipMalloc(&d_pts, n_points * 3 * sizeof(float)));
-        d_pts_cap = n_points;
-    }
-    return LV_OK;
-}
-
-int OccStore::integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t stats[4]) {
+int OccStore::integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t out[4]) {
     size_t total = 0;
     for (size_t v = 0; v < n_views; ++v) total += views[v].n;
-    if (total) {
-        const int rc = stage(stream, total);
+    int rc = LV_OK;
+    if (total) {   // every view's returns in one upload
+        rc = pts.reserve(stream, total);
         if (rc) return rc;
-        size_t o = 0;
-        for (size_t v = 0; v < n_views; ++v) {
-            const char* b = static_cast<const char*>(views[v].points);
-            for (size_t i = 0; i < views[v].n; ++i, ++o) std::memcpy(h_pts + 3 * o, b + i * views[v].stride, 3 * sizeof(float));
-        }
-        LV_HIP(hipMemcpyAsync(d_pts, h_pts, total * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        for (size_t v = 0; v < n_views; ++v) pts.append(views[v].points, views[v].stride, views[v].n);
+        rc = pts.upload(stream);
+        if (rc) return rc;
     }
-    LV_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), stream));
+    rc = stats.zero(stream);
+    if (rc) return rc;
     uint32_t* crossed = d_bits;
     uint32_t* hit = d_bits + n_words;
     size_t o = 0;
@@ -242,36 +212,26 @@ int OccStore::integrate(hipStream_t stream, const lv_view* views, size_t n_views
             OccPose pose;
             std::memcpy(pose.R, views[v].R, sizeof(pose.R));
             std::memcpy(pose.t, views[v].t, sizeof(pose.t));
-            hipLaunchKernelGGL(occ_march_kernel, dim3(grid_of(n)), dim3(256), 0, stream, d_pts + 3 * o, (uint32_t)n, grid, pose, qs[0], qs[1],
-                               qs[2], crossed, hit, d_stats);
-            hipLaunchKernelGGL(occ_fold_kernel, dim3(grid_of(n_words / 4)), dim3(256), 0, stream, d_L, reinterpret_cast<uint4*>(crossed),
-                               reinterpret_cast<uint4*>(hit), (uint32_t)(n_words / 4), grid, d_stats);
+            hipLaunchKernelGGL(occ_march_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, pts.d + 3 * o, (uint32_t)n, grid, pose, qs[0], qs[1],
+                               qs[2], crossed, hit, stats.d);
+            hipLaunchKernelGGL(occ_fold_kernel, dim3(blocks_of(n_words / 4)), dim3(256), 0, stream, d_L, reinterpret_cast<uint4*>(crossed),
+                               reinterpret_cast<uint4*>(hit), (uint32_t)(n_words / 4), grid, stats.d);
             LV_HIP(hipGetLastError());
         }
         o += n;
     }
-    LV_HIP(hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    if (stats)
-        for (int i = 0; i < 4; ++i) stats[i] = (uint64_t)h_stats[i];
-    return LV_OK;
+    return stats.read(stream, out);
 }
 
-int OccStore::query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* logodds) {
+int OccStore::query(hipStream_t stream, const void* points, size_t stride, size_t n, float* logodds) {
     if (n == 0) return LV_OK;
-    int rc = stage(stream, n);
+    int rc = pts.reserve(stream, n);
+    if (!rc) rc = d_out.need(n);
     if (rc) return rc;
-    if (n > d_out_cap) {
-        hipFree(d_out);
-        d_out = nullptr;
-        d_out_cap = 0;
-        LV_HIP(hipMalloc(&d_out, n * sizeof(float)));
-        d_out_cap = n;
-    }
-    const char* b = static_cast<const char*>(pts);
-    for (size_t i = 0; i < n; ++i) std::memcpy(h_pts + 3 * i, b + i * stride, 3 * sizeof(float));
-    LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(occ_query_kernel, dim3(grid_of(n)), dim3(256), 0, stream, d_L, grid, d_pts, (uint32_t)n, d_out);
+    pts.append(points, stride, n);
+    rc = pts.upload(stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(occ_query_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_L, grid, pts.d, (uint32_t)n, d_out);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(logodds, d_out, n * sizeof(float), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));
@@ -281,7 +241,7 @@ int OccStore::query(hipStream_t stream, const void* pts, size_t stride, size_t n
 int OccStore::project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d) {
     const int k0 = k_lo < 0 ? 0 : k_lo, k1 = k_hi >= grid.nz ? grid.nz - 1 : k_hi;
     const size_t plane = (size_t)grid.nx * (size_t)grid.ny;
-    hipLaunchKernelGGL(occ_project_kernel, dim3(grid_of(plane)), dim3(256), 0, stream, d_L, grid, k0, k1, prm.l_occ, prm.l_free, d_proj);
+    hipLaunchKernelGGL(occ_project_kernel, dim3(blocks_of(plane)), dim3(256), 0, stream, d_L, grid, k0, k1, prm.l_occ, prm.l_free, d_proj);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(grid2d, d_proj, plane, hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/limovelo_hip.h"
+#include "lv_buffers.hpp"
 
 #define LV_OCC_HD __host__ __device__ inline
 
@@ -178,27 +179,21 @@ struct OccStore {
     OccGrid grid{};
     size_t n_vox = 0;
     size_t n_words = 0;            // words of ONE bitmap, padded to a multiple of 4 (the fold reads uint4)
-    float* d_L = nullptr;          // log-odds, (k * ny + j) * nx + i; NaN = never observed
-    uint32_t* d_bits = nullptr;    // crossed bitmap, then hit bitmap: bit (i & 31) of word (k * ny + j) * wx + (i >> 5); all zero between views
-    unsigned long long* d_stats = nullptr;   // 4 counters of the call in flight
-    unsigned long long* h_stats = nullptr;   // pinned
-    float* h_pts = nullptr;        // pinned staging: packed x, y, z of every view's returns (or of the query points)
-    float* d_pts = nullptr;
-    float* d_out = nullptr;        // lv_occ_query's results
-    int8_t* d_proj = nullptr;      // lv_occ_project's result (nx * ny)
-    size_t h_pts_cap = 0, d_pts_cap = 0, d_out_cap = 0;
+    DevBuf<float> d_L;             // log-odds, (k * ny + j) * nx + i; NaN = never observed
+    DevBuf<uint32_t> d_bits;       // crossed bitmap, then hit bitmap: bit (i & 31) of word (k * ny + j) * wx + (i >> 5); all zero between views
+    Counters4 stats;               // the 4 counters of the call in flight
+    PointStage pts;                // every view's returns, or the query points
+    DevBuf<float> d_out;           // lv_occ_query's results
+    DevBuf<int8_t> d_proj;         // lv_occ_project's result (nx * ny)
 
     int configure(hipStream_t stream, const lv_occupancy_params& p);
     int clear(hipStream_t stream);
-    int integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t stats[4]);
+    int integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t out[4]);
     int query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* logodds);
     int project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d);
     int fetch(hipStream_t stream, float* logodds);
     int load(hipStream_t stream, const float* logodds);
     void release();
-
-   private:
-    int stage(hipStream_t stream, size_t n_points);
 };
 
 }  // namespace lv

@@ -199,42 +199,24 @@ __global__ __launch_bounds__(256) void paint_color_kernel(const float4* __restri
     if (seen) seen[k] = (uint8_t)n;
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return LV_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(&p, n * sizeof(T)));
-    cap = n;
-    return LV_OK;
-}
-
-inline uint32_t grid_of(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 }  // namespace
 
 int PaintStore::run(const MapStore& map, hipStream_t stream, const lv_camera_view* views, const PaintCam* cams, const PaintRule& q,
                     const uint32_t* rank, bool want_rgb, bool want_depth, bool want_seen) {
     const size_t m = map.m;
-    int rc = grow(d_raw, raw_cap, q.raw_bytes);
-    if (!rc) rc = grow(d_tex, tex_cap, q.total_pixels);
-    if (!rc) rc = grow(d_cell, cell_cap, q.total_cells);
-    if (!rc && q.window > 0) rc = grow(d_tmp, tmp_cap, q.total_cells);
-    if (!rc && want_rgb) rc = grow(d_rgb, rgb_cap, 3 * m);
-    if (!rc && want_depth) rc = grow(d_depth, depth_cap, m);
-    if (!rc && want_seen) rc = grow(d_seen, seen_cap, m);
+    int rc = d_raw.need(q.raw_bytes);
+    if (!rc) rc = d_tex.need(q.total_pixels);
+    if (!rc) rc = d_cell.need(q.total_cells);
+    if (!rc && q.window > 0) rc = d_tmp.need(q.total_cells);
+    if (!rc && want_rgb) rc = d_rgb.need(3 * m);
+    if (!rc && want_depth) rc = d_depth.need(m);
+    if (!rc && want_seen) rc = d_seen.need(m);
+    if (!rc) rc = d_cams.need(PAINT_MAX_VIEWS);
     if (rc) return rc;
-    if (!d_cams) LV_HIP(hipMalloc((void**)&d_cams, PAINT_MAX_VIEWS * sizeof(PaintCam)));
     LV_HIP(hipStreamSynchronize(stream));   // (the previous call's copies out of the pinned buffers)
-    if (!h_cams) LV_HIP(hipHostMalloc((void**)&h_cams, PAINT_MAX_VIEWS * sizeof(PaintCam), hipHostMallocDefault));
-    if (q.raw_bytes > h_raw_cap) {
-        if (h_raw) hipHostFree(h_raw);
-        h_raw = nullptr;
-        h_raw_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&h_raw, q.raw_bytes, hipHostMallocDefault));
-        h_raw_cap = q.raw_bytes;
-    }
+    rc = h_cams.need(PAINT_MAX_VIEWS);
+    if (!rc) rc = h_raw.need(q.raw_bytes);
+    if (rc) return rc;
     // the images' rows, back to back (one copy when the caller's rows already are)
     for (int w = 0; w < q.n_views; ++w) {
         const lv_camera_view& v = views[w];
@@ -251,31 +233,22 @@ int PaintStore::run(const MapStore& map, hipStream_t stream, const lv_camera_vie
     LV_HIP(hipMemcpyAsync(d_cams, h_cams, (size_t)q.n_views * sizeof(PaintCam), hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemcpyAsync(d_raw, h_raw, q.raw_bytes, hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemsetD32Async((hipDeviceptr_t)d_cell, 0x7F800000, q.total_cells, stream));
-    hipLaunchKernelGGL(paint_unpack_kernel, dim3(grid_of(q.max_pixels), q.n_views), dim3(256), 0, stream, d_raw, d_cams, d_tex);
-    hipLaunchKernelGGL(paint_zbuf_kernel, dim3(grid_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_cams, q, d_cell);
+    hipLaunchKernelGGL(paint_unpack_kernel, dim3(blocks_of(q.max_pixels), q.n_views), dim3(256), 0, stream, d_raw, d_cams, d_tex);
+    hipLaunchKernelGGL(paint_zbuf_kernel, dim3(blocks_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_cams, q, d_cell);
     if (q.window > 0) {
-        hipLaunchKernelGGL(paint_min_x_kernel, dim3(grid_of(q.max_cells), q.n_views), dim3(256), 0, stream, d_cell, d_tmp, d_cams, q.window);
-        hipLaunchKernelGGL(paint_min_y_kernel, dim3(grid_of(q.max_cells), q.n_views), dim3(256), 0, stream, d_tmp, d_cell, d_cams, q.window);
+        hipLaunchKernelGGL(paint_min_x_kernel, dim3(blocks_of(q.max_cells), q.n_views), dim3(256), 0, stream, d_cell, d_tmp, d_cams, q.window);
+        hipLaunchKernelGGL(paint_min_y_kernel, dim3(blocks_of(q.max_cells), q.n_views), dim3(256), 0, stream, d_tmp, d_cell, d_cams, q.window);
     }
-    hipLaunchKernelGGL(paint_color_kernel, dim3(grid_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_cams, q, d_cell, d_tex, rank,
-                       want_rgb ? d_rgb : nullptr, want_depth ? d_depth : nullptr, want_seen ? d_seen : nullptr);
+    hipLaunchKernelGGL(paint_color_kernel, dim3(blocks_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_cams, q, d_cell, d_tex, rank,
+                       want_rgb ? d_rgb.p : nullptr, want_depth ? d_depth.p : nullptr, want_seen ? d_seen.p : nullptr);
     LV_HIP(hipGetLastError());
     LV_HIP(hipStreamSynchronize(stream));
     return LV_OK;
 }
 
 void PaintStore::release() {
-    if (h_raw) hipHostFree(h_raw);
-    if (h_cams) hipHostFree(h_cams);
-    hipFree(d_raw);
-    hipFree(d_cams);
-    hipFree(d_tex);
-    hipFree(d_cell);
-    hipFree(d_tmp);
-    hipFree(d_rgb);
-    hipFree(d_depth);
-    hipFree(d_seen);
-    *this = PaintStore();
+    h_raw.release(); h_cams.release(); d_raw.release(); d_cams.release(); d_tex.release(); d_cell.release(); d_tmp.release();
+    d_rgb.release(); d_depth.release(); d_seen.release();
 }
 
 }  // namespace lv

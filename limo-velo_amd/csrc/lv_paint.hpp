@@ -40,17 +40,16 @@ struct PaintRule {
 // The buffers of lv_map_paint (grown on demand, kept; released by lv_destroy): staged image bytes (pinned and on the device),
 // the views, the packed texels, the occlusion cells and their filter's intermediate, the outputs by rank.
 struct PaintStore {
-    uint8_t* h_raw = nullptr;
-    PaintCam* h_cams = nullptr;   // pinned, PAINT_MAX_VIEWS entries
-    uint8_t* d_raw = nullptr;
-    PaintCam* d_cams = nullptr;
-    uint32_t* d_tex = nullptr;
-    uint32_t* d_cell = nullptr;
-    uint32_t* d_tmp = nullptr;
-    float* d_rgb = nullptr;
-    float* d_depth = nullptr;
-    uint8_t* d_seen = nullptr;
-    size_t h_raw_cap = 0, raw_cap = 0, tex_cap = 0, cell_cap = 0, tmp_cap = 0, rgb_cap = 0, depth_cap = 0, seen_cap = 0;
+    PinBuf<uint8_t> h_raw;
+    PinBuf<PaintCam> h_cams;      // PAINT_MAX_VIEWS entries
+    DevBuf<uint8_t> d_raw;
+    DevBuf<PaintCam> d_cams;
+    DevBuf<uint32_t> d_tex;
+    DevBuf<uint32_t> d_cell;
+    DevBuf<uint32_t> d_tmp;
+    DevBuf<float> d_rgb;
+    DevBuf<float> d_depth;
+    DevBuf<uint8_t> d_seen;
     // Stages and unpacks the images, builds the occlusion buffers from every living point of `map` and writes the outputs of its
     // m living points at their ranks (rank NULL: ranks are ids) into d_rgb / d_depth / d_seen (those wanted), on `stream`.
     // cams: the views (tex_off, cell_off and raw_off filled in by the caller).  Synchronises the stream.

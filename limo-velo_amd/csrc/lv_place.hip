@@ -196,17 +196,6 @@ __global__ __launch_bounds__(256) void place_topk_kernel(const uint64_t* __restr
     }
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t want) {
-    if (want <= cap) return LV_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(&p, want * sizeof(T)));
-    cap = want;
-    return LV_OK;
-}
-
 void rot_of(const double* q, double R[9]) {
     const double x = q[0], y = q[1], z = q[2], w = q[3];
     R[0] = 1.0 - 2.0 * (y * y + z * z);
@@ -246,23 +235,22 @@ PlaceRule PlaceStore::rule() const {
 }
 
 int PlaceStore::reserve(hipStream_t stream, size_t want) {
-    if (!d_q) LV_HIP(hipMalloc((void**)&d_q, PLACE_MAX_BINS * sizeof(uint32_t)));
-    if (!d_top[0]) {
-        const size_t stage = (PLACE_MAX_COUNT / PLACE_TOPK_CHUNK) * PLACE_MAX_K;
-        LV_HIP(hipMalloc((void**)&d_top[0], stage * sizeof(uint64_t)));
-        LV_HIP(hipMalloc((void**)&d_top[1], stage * sizeof(uint64_t)));
-    }
+    int rc = d_q.need(PLACE_MAX_BINS);
+    const size_t stage = (PLACE_MAX_COUNT / PLACE_TOPK_CHUNK) * PLACE_MAX_K;
+    if (!rc) rc = d_top[0].need(stage);
+    if (!rc) rc = d_top[1].need(stage);
+    if (rc) return rc;
     const size_t B = (size_t)bins();
-    if (want * B <= cap) return grow(d_keys, keys_cap, want);
-    size_t places = std::max<size_t>(want, std::min(PLACE_MAX_COUNT, std::max<size_t>(1024, 2 * (cap / B))));
-    float* p = nullptr;
-    LV_HIP(hipMalloc((void**)&p, places * B * sizeof(float)));
-    if (n) LV_HIP(hipMemcpyAsync(p, d_desc, n * B * sizeof(float), hipMemcpyDeviceToDevice, stream));
+    if (want * B <= d_desc.cap) return d_keys.need(want);
+    size_t places = std::max<size_t>(want, std::min(PLACE_MAX_COUNT, std::max<size_t>(1024, 2 * (d_desc.cap / B))));
+    DevBuf<float> grown;   // (the first n places move over before the old buffer goes)
+    rc = grown.need(places * B);
+    if (rc) return rc;
+    if (n) LV_HIP(hipMemcpyAsync(grown, d_desc, n * B * sizeof(float), hipMemcpyDeviceToDevice, stream));
     LV_HIP(hipStreamSynchronize(stream));
-    if (d_desc) hipFree(d_desc);
-    d_desc = p;
-    cap = places * B;
-    return grow(d_keys, keys_cap, places);
+    d_desc.release();
+    d_desc = grown;
+    return d_keys.need(places);
 }
 
 int PlaceStore::describe(const ScanStore& scan, hipStream_t stream, const PlaceFrame& f, uint32_t* out) {
@@ -327,8 +315,8 @@ int PlaceStore::add_map(const MapStore& map, hipStream_t stream, const double* c
         for (size_t c = 0; c < cells; ++c) start[c + 1] += start[c];
         std::vector<uint32_t> fill(start.begin(), start.end() - 1);
         for (size_t i = 0; i < k; ++i) items[fill[cell[i]]++] = (uint32_t)i;
-        rc = grow(d_cent, cent_cap, k);
-        if (!rc) rc = grow(d_cstart, cstart_cap, cells + 1 + k);
+        rc = d_cent.need(k);
+        if (!rc) rc = d_cstart.need(cells + 1 + k);
         if (rc) return rc;
         d_citems = d_cstart + cells + 1;
         LV_HIP(hipMemcpyAsync(d_cent, cf.data(), k * sizeof(float4), hipMemcpyHostToDevice, stream));
@@ -412,13 +400,7 @@ int PlaceStore::fetch(hipStream_t stream, float* desc, double* cs) const {
 }
 
 void PlaceStore::release() {
-    hipFree(d_desc);
-    hipFree(d_q);
-    hipFree(d_keys);
-    hipFree(d_top[0]);
-    hipFree(d_top[1]);
-    hipFree(d_cent);
-    hipFree(d_cstart);
+    d_desc.release(); d_q.release(); d_keys.release(); d_top[0].release(); d_top[1].release(); d_cent.release(); d_cstart.release();
     *this = PlaceStore();
 }
 

@@ -30,16 +30,13 @@ struct PlaceStore {
     lv_place_params prm{20, 60, 0.f, 80.f, 2.f};
     size_t n = 0;                      // places held
     std::vector<double> centres;       // 3 n
-    float* d_desc = nullptr;           // cap * n_bins
-    size_t cap = 0;
-    uint32_t* d_q = nullptr;           // the query descriptor (f32 bits), PLACE_MAX_BINS
-    uint64_t* d_keys = nullptr;        // one retrieval key per place: (distance bits << 32) | (id << 6) | shift
-    size_t keys_cap = 0;
-    uint64_t* d_top[2] = {nullptr, nullptr};   // the top-k stages, ping-pong
-    float4* d_cent = nullptr;          // lv_place_add_map: the call's centres in f32 and their 2-D grid (CSR)
-    uint32_t* d_cstart = nullptr;
-    uint32_t* d_citems = nullptr;
-    size_t cent_cap = 0, cstart_cap = 0;
+    DevBuf<float> d_desc;              // room for d_desc.cap / n_bins places
+    DevBuf<uint32_t> d_q;              // the query descriptor (f32 bits), PLACE_MAX_BINS
+    DevBuf<uint64_t> d_keys;           // one retrieval key per place: (distance bits << 32) | (id << 6) | shift
+    DevBuf<uint64_t> d_top[2];         // the top-k stages, ping-pong
+    DevBuf<float4> d_cent;             // lv_place_add_map: the call's centres in f32 and their 2-D grid (CSR)
+    DevBuf<uint32_t> d_cstart;         // cells + 1 starts, then the call's items
+    uint32_t* d_citems = nullptr;      // (inside d_cstart)
 
     PlaceRule rule() const;
     int bins() const { return prm.n_rings * prm.n_sectors; }

@@ -240,69 +240,24 @@ __global__ __launch_bounds__(256) void plan_paths_kernel(PlanGrid g, const uint8
     }
 }
 
-inline uint32_t blocks_of(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 }  // namespace
 
 void PlanStore::release() {
-    if (h_round) hipHostFree(h_round);
-    if (h_stats) hipHostFree(h_stats);
-    if (h_pts) hipHostFree(h_pts);
-    hipFree(d_cost);
-    hipFree(d_pot);
-    hipFree(d_active);
-    hipFree(d_table);
-    hipFree(d_round);
-    hipFree(d_stats);
-    hipFree(d_pts);
-    hipFree(d_status);
-    hipFree(d_pcost);
-    hipFree(d_cnt);
-    hipFree(d_off);
-    hipFree(d_cells);
-    hipFree(d_tmp);
+    d_cost.release(); d_pot.release(); d_active.release(); d_table.release(); d_round.release(); h_round.release(); stats.release();
+    pts.release(); d_status.release(); d_pcost.release(); d_cnt.release(); d_off.release(); d_cells.release(); d_tmp.release();
     *this = PlanStore();
 }
 
-// n points (goals or starts) of 3 floats into d_pts
-int PlanStore::stage(hipStream_t stream, const void* pts, size_t stride, size_t n) {
-    LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the pinned buffer may still be pending)
-    if (n > pts_cap) {
-        if (h_pts) hipHostFree(h_pts);
-        hipFree(d_pts);
-        h_pts = d_pts = nullptr;
-        pts_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&h_pts, n * 3 * sizeof(float), hipHostMallocDefault));
-        LV_HIP(hipMalloc(&d_pts, n * 3 * sizeof(float)));
-        pts_cap = n;
-    }
-    const char* b = static_cast<const char*>(pts);
-    for (size_t i = 0; i < n; ++i) std::memcpy(h_pts + 3 * i, b + i * stride, 3 * sizeof(float));
-    LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-    return LV_OK;
-}
-
-// room for the per-start outputs of n starts (status, cost; n + 1 counts and offsets)
-int PlanStore::reserve_starts(size_t n) {
-    if (n <= starts_cap) return LV_OK;
-    hipFree(d_status);
-    hipFree(d_pcost);
-    hipFree(d_cnt);
-    hipFree(d_off);
-    d_status = nullptr;
-    d_pcost = nullptr;
-    d_cnt = d_off = nullptr;
-    starts_cap = 0;
-    LV_HIP(hipMalloc(&d_status, n * sizeof(int32_t)));
-    LV_HIP(hipMalloc(&d_pcost, n * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&d_cnt, (n + 1) * sizeof(unsigned long long)));
-    LV_HIP(hipMalloc(&d_off, (n + 1) * sizeof(unsigned long long)));
-    starts_cap = n;
-    return LV_OK;
+// n points (goals or starts) into pts.d
+int PlanStore::stage(hipStream_t stream, const void* points, size_t stride, size_t n) {
+    const int rc = pts.reserve(stream, n);
+    if (rc) return rc;
+    pts.append(points, stride, n);
+    return pts.upload(stream);
 }
 
 int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_params& p, const uint8_t* cost, size_t n_cost, const void* goals,
-                     size_t stride, size_t n_goals, uint64_t stats[4]) {
+                     size_t stride, size_t n_goals, uint64_t out[4]) {
     PlanGrid g{};
     g.nx = dist.grid.nx;
     g.ny = dist.grid.ny;
@@ -316,40 +271,26 @@ int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_pa
                                : (size_t)((g.nx + 7) / 8) * (size_t)((g.ny + 7) / 8) * (size_t)((g.nz + 7) / 8);
     int rc = stage(stream, goals, stride, n_goals);
     if (rc) return rc;
-    if (nc > cap_cells) {
-        hipFree(d_cost);
-        hipFree(d_pot);
-        d_cost = nullptr;
-        d_pot = nullptr;
-        cap_cells = 0;
-        LV_HIP(hipMalloc(&d_cost, nc * sizeof(uint8_t)));
-        LV_HIP(hipMalloc(&d_pot, nc * sizeof(uint32_t)));
-        cap_cells = nc;
-    }
-    if (nt > cap_tiles) {
-        hipFree(d_active);
-        d_active = nullptr;
-        cap_tiles = 0;
-        LV_HIP(hipMalloc(&d_active, 2 * nt * sizeof(uint32_t)));
-        cap_tiles = nt;
-    }
-    if (!d_table) LV_HIP(hipMalloc(&d_table, PLAN_MAX_COST));
-    if (!d_round) LV_HIP(hipMalloc(&d_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t)));
-    if (!h_round) LV_HIP(hipHostMalloc((void**)&h_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t), hipHostMallocDefault));
-    if (!d_stats) LV_HIP(hipMalloc(&d_stats, 4 * sizeof(unsigned long long)));
-    if (!h_stats) LV_HIP(hipHostMalloc((void**)&h_stats, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-    built = false;   // (the old plan's buffers are overwritten from here on; the new one stands when the rounds are through)
+    built = false;   // (before a buffer goes: the old plan's are overwritten from here on; the new one stands when the rounds are through)
+    rc = d_cost.need(nc);
+    if (!rc) rc = d_pot.need(nc);
+    if (!rc) rc = d_active.need(2 * nt);
+    if (!rc) rc = d_table.need(PLAN_MAX_COST);
+    if (!rc) rc = d_round.need(PLAN_ROUNDS_PER_READ);
+    if (!rc) rc = h_round.need(PLAN_ROUNDS_PER_READ);
+    if (rc) return rc;
     LV_HIP(hipMemcpyAsync(d_table, cost, n_cost, hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemsetAsync(d_active, 0, 2 * nt * sizeof(uint32_t), stream));
-    LV_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), stream));
+    rc = stats.zero(stream);
+    if (rc) return rc;
     hipLaunchKernelGGL(plan_cost_kernel, dim3(blocks_of(nc)), dim3(256), 0, stream, dist.d_s2, p.min_clear_s2, d_table, (int)n_cost, (uint32_t)nc,
                        d_cost, d_pot);
     if (g.planar)
-        hipLaunchKernelGGL((plan_seed_kernel<32, 32, 1>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, d_pts, (uint32_t)n_goals, d_cost, d_pot,
-                           d_active, d_stats);
+        hipLaunchKernelGGL((plan_seed_kernel<32, 32, 1>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, pts.d, (uint32_t)n_goals, d_cost, d_pot,
+                           d_active, stats.d);
     else
-        hipLaunchKernelGGL((plan_seed_kernel<8, 8, 8>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, d_pts, (uint32_t)n_goals, d_cost, d_pot,
-                           d_active, d_stats);
+        hipLaunchKernelGGL((plan_seed_kernel<8, 8, 8>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, pts.d, (uint32_t)n_goals, d_cost, d_pot,
+                           d_active, stats.d);
     LV_HIP(hipGetLastError());
     // the rounds: a batch of launches, then one look at the batch's words.  Once a round lowers nothing no later one does.
     size_t done = 0;   // rounds launched so far
@@ -371,12 +312,10 @@ int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_pa
             finished = h_round[r] == 0;
         }
     }
-    hipLaunchKernelGGL(plan_stats_kernel, dim3(blocks_of(nc) < 1024u ? blocks_of(nc) : 1024u), dim3(256), 0, stream, d_cost, d_pot, (uint32_t)nc, d_stats);
+    hipLaunchKernelGGL(plan_stats_kernel, dim3(blocks_of(nc) < 1024u ? blocks_of(nc) : 1024u), dim3(256), 0, stream, d_cost, d_pot, (uint32_t)nc, stats.d);
     LV_HIP(hipGetLastError());
-    LV_HIP(hipMemcpyAsync(h_stats, d_stats, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    if (stats)
-        for (int i = 0; i < 4; ++i) stats[i] = (uint64_t)h_stats[i];
+    rc = stats.read(stream, out);
+    if (rc) return rc;
     prm = p;
     grid = g;
     n_cells = nc;
@@ -400,21 +339,19 @@ int PlanStore::paths(hipStream_t stream, const void* starts, size_t stride, size
     offsets[0] = 0;
     if (n == 0) return LV_OK;
     int rc = stage(stream, starts, stride, n);
-    if (!rc) rc = reserve_starts(n);
+    if (!rc) rc = d_status.need(n);
+    if (!rc) rc = d_pcost.need(n);
+    if (!rc) rc = d_cnt.need(n + 1);
+    if (!rc) rc = d_off.need(n + 1);
     if (rc) return rc;
-    hipLaunchKernelGGL(plan_paths_kernel<false>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, d_pts, (uint32_t)n, d_status, d_pcost,
+    hipLaunchKernelGGL(plan_paths_kernel<false>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, pts.d, (uint32_t)n, d_status, d_pcost,
                        d_cnt, (const unsigned long long*)nullptr, (int32_t*)nullptr);
     LV_HIP(hipGetLastError());
     size_t bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt, d_off, (int)(n + 1), stream));
-    if (bytes > tmp_cap) {
-        hipFree(d_tmp);
-        d_tmp = nullptr;
-        tmp_cap = 0;
-        LV_HIP(hipMalloc(&d_tmp, bytes));
-        tmp_cap = bytes;
-    }
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_cnt, d_off, (int)(n + 1), stream));
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt.p, d_off.p, (int)(n + 1), stream));
+    rc = d_tmp.need(bytes);
+    if (rc) return rc;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_cnt.p, d_off.p, (int)(n + 1), stream));
     static_assert(sizeof(size_t) == sizeof(unsigned long long), "offsets are copied out as size_t");
     LV_HIP(hipMemcpyAsync(offsets, d_off, (n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -429,15 +366,10 @@ int PlanStore::paths(hipStream_t stream, const void* starts, size_t stride, size
         return LV_EINVAL;
     }
     if (tot == 0) return LV_OK;
-    if (tot > cells_cap) {
-        hipFree(d_cells);
-        d_cells = nullptr;
-        cells_cap = 0;
-        LV_HIP(hipMalloc(&d_cells, tot * sizeof(int32_t)));
-        cells_cap = tot;
-    }
-    hipLaunchKernelGGL(plan_paths_kernel<true>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, d_pts, (uint32_t)n, d_status, d_pcost,
-                       d_cnt, (const unsigned long long*)d_off, d_cells);
+    rc = d_cells.need(tot);
+    if (rc) return rc;
+    hipLaunchKernelGGL(plan_paths_kernel<true>, dim3(blocks_of(n + 1)), dim3(256), 0, stream, grid, d_cost, d_pot, pts.d, (uint32_t)n, d_status, d_pcost,
+                       d_cnt, (const unsigned long long*)d_off.p, d_cells);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(cells, d_cells, tot * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));

@@ -193,39 +193,31 @@ struct PlanStore {
     int rounds = 0;
     lv_plan_params prm{};
     PlanGrid grid{};
-    size_t n_cells = 0, cap_cells = 0;
-    size_t n_tiles = 0, cap_tiles = 0;
-    uint8_t* d_cost = nullptr;       // the cost byte per cell, the field's linear index
-    uint32_t* d_pot = nullptr;       // P
-    uint32_t* d_active = nullptr;    // 2 * n_tiles flags: the tiles of this round, of the next
-    uint8_t* d_table = nullptr;      // the cost table (PLAN_MAX_COST bytes)
-    uint32_t* d_round = nullptr;     // PLAN_ROUNDS_PER_READ words: round r of a batch lowered something
-    uint32_t* h_round = nullptr;     // pinned
-    unsigned long long* d_stats = nullptr;
-    unsigned long long* h_stats = nullptr;   // pinned
-    float* h_pts = nullptr;          // pinned staging of goal and start points
-    float* d_pts = nullptr;
-    size_t pts_cap = 0;
-    int32_t* d_status = nullptr;     // per start
-    uint32_t* d_pcost = nullptr;
-    unsigned long long* d_cnt = nullptr;   // per start the path's length, one more entry of 0 (the scan's last offset is the total)
-    unsigned long long* d_off = nullptr;
-    size_t starts_cap = 0;
-    int32_t* d_cells = nullptr;
-    size_t cells_cap = 0;
-    void* d_tmp = nullptr;           // the scan's scratch
-    size_t tmp_cap = 0;
+    size_t n_cells = 0, n_tiles = 0;
+    DevBuf<uint8_t> d_cost;          // the cost byte per cell, the field's linear index
+    DevBuf<uint32_t> d_pot;          // P
+    DevBuf<uint32_t> d_active;       // 2 * n_tiles flags: the tiles of this round, of the next
+    DevBuf<uint8_t> d_table;         // the cost table (PLAN_MAX_COST bytes)
+    DevBuf<uint32_t> d_round;        // PLAN_ROUNDS_PER_READ words: round r of a batch lowered something
+    PinBuf<uint32_t> h_round;
+    Counters4 stats;
+    PointStage pts;                  // goal and start points
+    DevBuf<int32_t> d_status;        // per start
+    DevBuf<uint32_t> d_pcost;
+    DevBuf<unsigned long long> d_cnt;   // per start the path's length, one more entry of 0 (the scan's last offset is the total)
+    DevBuf<unsigned long long> d_off;
+    DevBuf<int32_t> d_cells;
+    DevBuf<void> d_tmp;              // the scan's scratch
 
     int build(hipStream_t stream, const DistStore& dist, const lv_plan_params& p, const uint8_t* cost, size_t n_cost, const void* goals,
-              size_t stride, size_t n_goals, uint64_t stats[4]);
+              size_t stride, size_t n_goals, uint64_t out[4]);
     int fetch(hipStream_t stream, uint32_t* potential, uint8_t* cell_cost);
     int paths(hipStream_t stream, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* cells,
               size_t capacity, size_t* total);
     void release();
 
    private:
-    int stage(hipStream_t stream, const void* pts, size_t stride, size_t n);
-    int reserve_starts(size_t n);
+    int stage(hipStream_t stream, const void* points, size_t stride, size_t n);
 };
 
 }  // namespace lv

@@ -28,7 +28,6 @@
 
 #include <cmath>
 #include <cstring>
-#include <vector>
 
 namespace lv {
 
@@ -198,42 +197,16 @@ __global__ void query_remap_kernel(uint32_t* __restrict__ v, uint32_t n, const u
     if (i < n) v[i] = rank[v[i]];
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return LV_OK;
-    size_t c = cap ? cap : 1024;
-    while (c < need) c *= 2;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc((void**)&p, c * sizeof(T)));
-    cap = c;
-    return LV_OK;
-}
-int grow_bytes(void*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return LV_OK;
-    size_t c = cap ? cap : 4096;
-    while (c < need) c *= 2;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(&p, c));
-    cap = c;
-    return LV_OK;
-}
-uint32_t grid_of(size_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+// the query buffers follow the caller's batch from call to call: they double from these floors (DESIGN "Host-side buffers")
+constexpr size_t QUERY_FLOOR = 1024, QUERY_TMP_FLOOR = 4096;
 
 }  // namespace
 
 int QueryStore::stage_queries(hipStream_t stream, const void* q, size_t stride, size_t n) {
-    int rc = grow(d_q, q_cap, 3 * n);
+    const int rc = pts.reserve(stream, n, QUERY_FLOOR);
     if (rc) return rc;
-    std::vector<float> packed(3 * n);
-    const char* b = static_cast<const char*>(q);
-    for (size_t i = 0; i < n; ++i) std::memcpy(&packed[3 * i], b + i * stride, 3 * sizeof(float));
-    LV_HIP(hipMemcpyAsync(d_q, packed.data(), 3 * n * sizeof(float), hipMemcpyHostToDevice, stream));
-    LV_HIP(hipStreamSynchronize(stream));   // (the pageable source dies with this frame)
-    return LV_OK;
+    pts.append(q, stride, n);
+    return pts.upload(stream);
 }
 
 int QueryStore::ensure_rank(const MapStore& map, hipStream_t stream, const uint32_t** rank) {
@@ -241,17 +214,17 @@ int QueryStore::ensure_rank(const MapStore& map, hipStream_t stream, const uint3
     if (map.n_ids == map.m) return LV_OK;   // no dead id: ranks are ids
     if (map.n_ids > (uint32_t)SCAN_MAX) { set_error("map of %u ids: the rank scan takes at most %d", map.n_ids, SCAN_MAX); return LV_EINVAL; }
     if (rank_gen == map.gen && d_rank) { *rank = d_rank; return LV_OK; }
-    int rc = grow(d_rank, rank_cap, map.n_ids);
+    int rc = d_rank.need_pow2(map.n_ids, QUERY_FLOOR);
     if (rc) return rc;
-    rc = grow(d_flag, flag_cap, map.n_ids);
+    rc = d_flag.need_pow2(map.n_ids, QUERY_FLOOR);
     if (rc) return rc;
-    hipLaunchKernelGGL(query_alive_kernel, dim3(grid_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_flag);
+    hipLaunchKernelGGL(query_alive_kernel, dim3(blocks_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, d_flag);
     LV_HIP(hipGetLastError());
     size_t bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_flag, d_rank, (int)map.n_ids, stream));
-    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_flag.p, d_rank.p, (int)map.n_ids, stream));
+    rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_flag, d_rank, (int)map.n_ids, stream));
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_flag.p, d_rank.p, (int)map.n_ids, stream));
     rank_gen = map.gen;
     *rank = d_rank;
     return LV_OK;
@@ -265,14 +238,14 @@ int QueryStore::knn(const MapStore& map, hipStream_t stream, const void* q, size
     if (n > 0xFFFFFFF0ull / 32) { set_error("too many queries"); return LV_EINVAL; }
     if (n == 0) return LV_OK;
     int rc = stage_queries(stream, q, stride, n);
-    if (!rc) rc = grow(d_idx, idx_cap, n * (size_t)k);
-    if (!rc) rc = grow(d_d2, d2_cap, n * (size_t)k);
-    if (!rc) rc = grow(d_found, found_cap, n);
+    if (!rc) rc = d_idx.need_pow2(n * (size_t)k, QUERY_FLOOR);
+    if (!rc) rc = d_d2.need_pow2(n * (size_t)k, QUERY_FLOOR);
+    if (!rc) rc = d_found.need_pow2(n, QUERY_FLOOR);
     const uint32_t* rank = nullptr;
     if (!rc) rc = ensure_rank(map, stream, &rank);
     if (rc) return rc;
     const float max_d2 = max_dist * max_dist;
-    hipLaunchKernelGGL(query_knn_kernel, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, map.view, d_q, (uint32_t)n, k, max_d2, rank, d_idx,
+    hipLaunchKernelGGL(query_knn_kernel, dim3(blocks_of(n, QWAVES)), dim3(QTHREADS), 0, stream, map.view, pts.d, (uint32_t)n, k, max_d2, rank, d_idx,
                        d_d2, d_found);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(idx, d_idx, n * k * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -291,18 +264,18 @@ int QueryStore::radius(const MapStore& map, hipStream_t stream, const void* q, s
     offsets[0] = 0;
     if (n == 0) return LV_OK;
     int rc = stage_queries(stream, q, stride, n);
-    if (!rc) rc = grow(d_roff, roff_cap, n + 1);
-    if (!rc) rc = grow(d_rcnt, rcnt_cap, n);
+    if (!rc) rc = d_roff.need_pow2(n + 1, QUERY_FLOOR);
+    if (!rc) rc = d_rcnt.need_pow2(n, QUERY_FLOOR);
     if (rc) return rc;
     const MapView v = map.view;
-    hipLaunchKernelGGL(query_radius_kernel<false>, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, d_q, (uint32_t)n, radius, d_rcnt,
+    hipLaunchKernelGGL(query_radius_kernel<false>, dim3(blocks_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, pts.d, (uint32_t)n, radius, d_rcnt,
                        (const uint64_t*)nullptr, (uint32_t*)nullptr, (float*)nullptr);
     LV_HIP(hipGetLastError());
     size_t bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_rcnt, d_roff, (int)n, stream));
-    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_rcnt.p, d_roff.p, (int)n, stream));
+    rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_rcnt, d_roff, (int)n, stream));
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_rcnt.p, d_roff.p, (int)n, stream));
     hipLaunchKernelGGL(query_total_kernel<uint64_t>, dim3(1), dim3(64), 0, stream, d_roff, d_rcnt, (uint32_t)n, d_roff + n);
     LV_HIP(hipGetLastError());
     static_assert(sizeof(size_t) == sizeof(uint64_t), "offsets are copied out as size_t");
@@ -318,26 +291,26 @@ int QueryStore::radius(const MapStore& map, hipStream_t stream, const void* q, s
         return LV_EINVAL;
     }
     if (tot == 0) return LV_OK;
-    rc = grow(d_idx, idx_cap, tot);
-    if (!rc) rc = grow(d_d2, d2_cap, tot);
-    if (!rc) rc = grow(d_idx2, idx2_cap, tot);
-    if (!rc) rc = grow(d_d22, d22_cap, tot);
+    rc = d_idx.need_pow2(tot, QUERY_FLOOR);
+    if (!rc) rc = d_d2.need_pow2(tot, QUERY_FLOOR);
+    if (!rc) rc = d_idx2.need_pow2(tot, QUERY_FLOOR);
+    if (!rc) rc = d_d22.need_pow2(tot, QUERY_FLOOR);
     const uint32_t* rank = nullptr;
     if (!rc) rc = ensure_rank(map, stream, &rank);
     if (rc) return rc;
-    hipLaunchKernelGGL(query_radius_kernel<true>, dim3(grid_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, d_q, (uint32_t)n, radius,
+    hipLaunchKernelGGL(query_radius_kernel<true>, dim3(blocks_of(n, QWAVES)), dim3(QTHREADS), 0, stream, v, pts.d, (uint32_t)n, radius,
                        (uint64_t*)nullptr, (const uint64_t*)d_roff, d_idx, d_d2);
     LV_HIP(hipGetLastError());
     // the lists are unordered: every query's segment by id
     bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, bytes, d_idx, d_idx2, d_d2, d_d22, (int)tot, (int)n, d_roff, d_roff + 1, 0,
+    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, bytes, d_idx.p, d_idx2.p, d_d2.p, d_d22.p, (int)tot, (int)n, d_roff.p, d_roff.p + 1, 0,
                                                                    32, stream));
-    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
-    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(d_tmp, bytes, d_idx, d_idx2, d_d2, d_d22, (int)tot, (int)n, d_roff, d_roff + 1, 0,
+    LV_HIP((hipError_t)hipcub::DeviceSegmentedRadixSort::SortPairs(d_tmp.p, bytes, d_idx.p, d_idx2.p, d_d2.p, d_d22.p, (int)tot, (int)n, d_roff.p, d_roff.p + 1, 0,
                                                                    32, stream));
     if (rank) {
-        hipLaunchKernelGGL(query_remap_kernel, dim3(grid_of(tot, 256)), dim3(256), 0, stream, d_idx2, (uint32_t)tot, rank);
+        hipLaunchKernelGGL(query_remap_kernel, dim3(blocks_of(tot, 256)), dim3(256), 0, stream, d_idx2, (uint32_t)tot, rank);
         LV_HIP(hipGetLastError());
     }
     LV_HIP(hipMemcpyAsync(idx, d_idx2, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -353,18 +326,18 @@ int QueryStore::box(const MapStore& map, hipStream_t stream, const float lo[3], 
     if (map.view.m == 0 || map.n_ids == 0) return LV_OK;
     if (map.n_ids > (uint32_t)SCAN_MAX) { set_error("map of %u ids: a box search scans at most %d", map.n_ids, SCAN_MAX); return LV_EINVAL; }
     const uint32_t ids = map.n_ids;
-    int rc = grow(d_off, off_cap, (size_t)ids + 1);
-    if (!rc) rc = grow(d_cnt, cnt_cap, ids);
-    if (!rc && !h_word) LV_HIP(hipHostMalloc((void**)&h_word, 4 * sizeof(uint32_t), hipHostMallocDefault));
+    int rc = d_off.need_pow2((size_t)ids + 1, QUERY_FLOOR);
+    if (!rc) rc = d_cnt.need_pow2(ids, QUERY_FLOOR);
+    if (!rc) rc = h_word.need(4);
     if (rc) return rc;
-    hipLaunchKernelGGL(query_box_flag_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
+    hipLaunchKernelGGL(query_box_flag_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2],
                        d_cnt);
     LV_HIP(hipGetLastError());
     size_t bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt, d_off, (int)ids, stream));
-    rc = grow_bytes(d_tmp, tmp_cap, bytes);
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_cnt.p, d_off.p, (int)ids, stream));
+    rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp, bytes, d_cnt, d_off, (int)ids, stream));
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_cnt.p, d_off.p, (int)ids, stream));
     hipLaunchKernelGGL(query_total_kernel<uint32_t>, dim3(1), dim3(64), 0, stream, d_off, d_cnt, ids, d_off + ids);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(h_word, d_off + ids, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -374,12 +347,12 @@ int QueryStore::box(const MapStore& map, hipStream_t stream, const float lo[3], 
     if (!idx && !xyz) return LV_OK;   // count only
     if (capacity < tot) { set_error("capacity %zu < %zu results", capacity, tot); return LV_EINVAL; }
     if (tot == 0) return LV_OK;
-    rc = grow(d_idx, idx_cap, tot);
-    if (!rc) rc = grow(d_d2, d2_cap, 3 * tot);
+    rc = d_idx.need_pow2(tot, QUERY_FLOOR);
+    if (!rc) rc = d_d2.need_pow2(3 * tot, QUERY_FLOOR);
     const uint32_t* rank = nullptr;
     if (!rc) rc = ensure_rank(map, stream, &rank);
     if (rc) return rc;
-    hipLaunchKernelGGL(query_box_scatter_kernel, dim3(grid_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, d_cnt, d_off, rank, d_idx, d_d2);
+    hipLaunchKernelGGL(query_box_scatter_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, d_cnt, d_off, rank, d_idx, d_d2);
     LV_HIP(hipGetLastError());
     if (idx) LV_HIP(hipMemcpyAsync(idx, d_idx, tot * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     if (xyz) LV_HIP(hipMemcpyAsync(xyz, d_d2, 3 * tot * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -388,9 +361,9 @@ int QueryStore::box(const MapStore& map, hipStream_t stream, const float lo[3], 
 }
 
 void QueryStore::release() {
-    hipFree(d_q); hipFree(d_idx); hipFree(d_d2); hipFree(d_found); hipFree(d_idx2); hipFree(d_d22); hipFree(d_off); hipFree(d_cnt); hipFree(d_roff); hipFree(d_rcnt);
-    hipFree(d_tmp); hipFree(d_rank); hipFree(d_flag);
-    if (h_word) hipHostFree(h_word);
+    pts.release();
+    d_idx.release(); d_d2.release(); d_found.release(); d_idx2.release(); d_d22.release(); d_off.release(); d_cnt.release();
+    d_roff.release(); d_rcnt.release(); d_tmp.release(); d_rank.release(); d_flag.release(); h_word.release();
     *this = QueryStore();
 }
 

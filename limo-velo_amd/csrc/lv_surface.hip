@@ -255,41 +255,25 @@ __global__ __launch_bounds__(256) void surf_classify_kernel(float4* __restrict__
     orig[id].x = s_inf();
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return LV_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(&p, n * sizeof(T)));
-    cap = n;
-    return LV_OK;
-}
-
-inline uint32_t grid_of(size_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
-
 }  // namespace
 
 int SurfaceStore::ensure(size_t n_ids, size_t m, int job) {
-    int rc = grow(d_val, val_cap, (job == 0 ? 6 : 1) * n_ids);
-    if (!rc && flags_cap < m) rc = grow(d_flags, flags_cap, m);
-    if (!rc && job == 0 && out_cap < m) {
-        size_t c0 = out_cap, c1 = out_cap, c2 = out_cap, c3 = out_cap;
-        rc = grow(d_normals, c0, 3 * m);
-        if (!rc) rc = grow(d_curv, c1, m);
-        if (!rc) rc = grow(d_mean, c2, m);
-        if (!rc) rc = grow(d_used, c3, m);
-        if (!rc) out_cap = m;
+    int rc = d_val.need((job == 0 ? 6 : 1) * n_ids);
+    if (!rc) rc = d_flags.need(m);
+    if (!rc && job == 0) {
+        rc = d_normals.need(3 * m);
+        if (!rc) rc = d_curv.need(m);
+        if (!rc) rc = d_mean.need(m);
+        if (!rc) rc = d_used.need(m);
     }
-    if (rc) return rc;
-    if (!d_part) LV_HIP(hipMalloc(&d_part, 2 * STAT_BLOCKS * sizeof(double)));
-    if (!h_part) LV_HIP(hipHostMalloc((void**)&h_part, 2 * STAT_BLOCKS * sizeof(double), hipHostMallocDefault));
-    return LV_OK;
+    if (!rc) rc = d_part.need(2 * STAT_BLOCKS);
+    if (!rc) rc = h_part.need(2 * STAT_BLOCKS);
+    return rc;
 }
 
 void SurfaceStore::release() {
-    hipFree(d_val); hipFree(d_part); hipFree(d_normals); hipFree(d_curv); hipFree(d_mean); hipFree(d_used); hipFree(d_flags);
-    if (h_part) hipHostFree(h_part);
+    d_val.release(); d_part.release(); d_normals.release(); d_curv.release(); d_mean.release(); d_used.release(); d_flags.release();
+    h_part.release();
     *this = SurfaceStore();
 }
 
@@ -298,8 +282,8 @@ int surface_search(const MapStore& map, hipStream_t stream, SurfaceStore& st, co
     if (!v.bt[0].table || v.m == 0 || map.n_ids == 0) return LV_OK;
     // (one wavefront per id: a launch takes fewer than 2^32 threads)
     if (map.n_ids > 0x03FFFFF0u) { set_error("map of %u ids: the surface search takes at most %u", map.n_ids, 0x03FFFFF0u); return LV_EINVAL; }
-    if (q.job == 2) hipLaunchKernelGGL(surf_ladder_kernel<true>, dim3(grid_of(map.n_ids, SWAVES)), dim3(STHREADS), 0, stream, v, q, rank, st.d_val, st.d_mean, st.d_used);
-    else hipLaunchKernelGGL(surf_ladder_kernel<false>, dim3(grid_of(map.n_ids, SWAVES)), dim3(STHREADS), 0, stream, v, q, rank, st.d_val, st.d_mean, st.d_used);
+    if (q.job == 2) hipLaunchKernelGGL(surf_ladder_kernel<true>, dim3(blocks_of(map.n_ids, SWAVES)), dim3(STHREADS), 0, stream, v, q, rank, st.d_val, st.d_mean, st.d_used);
+    else hipLaunchKernelGGL(surf_ladder_kernel<false>, dim3(blocks_of(map.n_ids, SWAVES)), dim3(STHREADS), 0, stream, v, q, rank, st.d_val, st.d_mean, st.d_used);
     LV_HIP(hipGetLastError());
     st.val_gen = map.gen;
     st.val_rule = q;
@@ -308,7 +292,7 @@ int surface_search(const MapStore& map, hipStream_t stream, SurfaceStore& st, co
 
 int surface_finish(const MapStore& map, hipStream_t stream, SurfaceStore& st, const SurfRule& q, const uint32_t* rank) {
     if (map.n_ids == 0) return LV_OK;
-    hipLaunchKernelGGL(surf_finish_kernel, dim3(grid_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, q, rank, st.d_val, st.d_used,
+    hipLaunchKernelGGL(surf_finish_kernel, dim3(blocks_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, q, rank, st.d_val, st.d_used,
                        st.d_normals, st.d_curv);
     LV_HIP(hipGetLastError());
     return LV_OK;
@@ -355,8 +339,8 @@ int surface_outliers(MapStore& map, hipStream_t stream, SurfaceStore& st, SurfRu
     if (rc) return rc;
     // n_new .. dropped are contiguous (MapCounters; lv_map.hip reset_batch_counters)
     LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
-    hipLaunchKernelGGL(surf_classify_kernel, dim3(grid_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, st.d_val, q.job, q.threshold,
-                       rank, want_flags ? st.d_flags : nullptr, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
+    hipLaunchKernelGGL(surf_classify_kernel, dim3(blocks_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, st.d_val, q.job, q.threshold,
+                       rank, want_flags ? st.d_flags.p : nullptr, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {
         LV_HIP(hipStreamSynchronize(stream));

@@ -153,15 +153,14 @@ struct SurfRule {
 
 // The buffers of lv_map_normals / lv_map_remove_outliers (grown on demand, kept)
 struct SurfaceStore {
-    double* d_val = nullptr;        // by id: 6 covariance entries (job 0) or the point's value (jobs 1, 2)
-    double* d_part = nullptr;       // block partials of the statistics; the journaled rule's device copy
-    float* d_normals = nullptr;     // outputs at living ranks
-    float* d_curv = nullptr;
-    float* d_mean = nullptr;
-    int32_t* d_used = nullptr;
-    uint8_t* d_flags = nullptr;
-    double* h_part = nullptr;       // pinned
-    size_t val_cap = 0, out_cap = 0, flags_cap = 0;
+    DevBuf<double> d_val;           // by id: 6 covariance entries (job 0) or the point's value (jobs 1, 2)
+    DevBuf<double> d_part;          // block partials of the statistics; the journaled rule's device copy
+    DevBuf<float> d_normals;        // outputs at living ranks
+    DevBuf<float> d_curv;
+    DevBuf<float> d_mean;
+    DevBuf<int32_t> d_used;
+    DevBuf<uint8_t> d_flags;
+    PinBuf<double> h_part;
     uint64_t val_gen = 0;           // the map stamp (MapStore::gen) and rule d_val was computed for by the last surface_search
     SurfRule val_rule{};
     int ensure(size_t n_ids, size_t m, int job);

@@ -128,19 +128,6 @@ __global__ __launch_bounds__(256) void vis_classify_kernel(float4* __restrict__ 
     orig[id].x = vis_inf();
 }
 
-template <class T>
-int grow(T*& p, size_t& cap, size_t n) {
-    if (n <= cap) return LV_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    LV_HIP(hipMalloc(&p, n * sizeof(T)));
-    cap = n;
-    return LV_OK;
-}
-
-inline uint32_t grid_of(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 }  // namespace
 
 int VisStore::build(hipStream_t stream, const lv_view* views, size_t n_views, const VisRule& q) {
@@ -148,27 +135,14 @@ int VisStore::build(hipStream_t stream, const lv_view* views, size_t n_views, co
     for (size_t v = 0; v < n_views; ++v) n += views[v].n;
     const size_t pose_bytes = vis_pose_bytes(q.n_views);
     const size_t blob = vis_blob_bytes(q);
-    if (blob > blob_cap) {
-        if (d_blob) hipFree(d_blob);
-        d_blob = nullptr;
-        blob_cap = 0;
-        LV_HIP(hipMalloc(&d_blob, blob));
-        blob_cap = blob;
-    }
     const size_t pixels = (size_t)q.n_views * q.width * q.height;
-    int rc = grow(d_tmp, tmp_cap, pixels);
-    if (!rc && n) rc = grow(d_pts, d_pts_cap, n);
+    int rc = d_blob.need(blob);
+    if (!rc) rc = d_tmp.need(pixels);
+    if (!rc) rc = d_pts.need(n);
     if (rc) return rc;
-    if (n > h_pts_cap) {
-        LV_HIP(hipStreamSynchronize(stream));   // (a copy out of the old buffer may still be pending)
-        if (h_pts) hipHostFree(h_pts);
-        h_pts = nullptr;
-        h_pts_cap = 0;
-        LV_HIP(hipHostMalloc((void**)&h_pts, n * sizeof(float4), hipHostMallocDefault));
-        h_pts_cap = n;
-    } else {
-        LV_HIP(hipStreamSynchronize(stream));   // (the previous call's copy out of h_pts)
-    }
+    LV_HIP(hipStreamSynchronize(stream));   // (the previous call's copy out of h_pts, before it is overwritten or freed)
+    rc = h_pts.need(n);
+    if (rc) return rc;
     float pose[VIS_MAX_VIEWS * 12];
     size_t o = 0;
     for (size_t v = 0; v < n_views; ++v) {
@@ -185,16 +159,16 @@ int VisStore::build(hipStream_t stream, const lv_view* views, size_t n_views, co
     }
     // (pose is a stack array: the copy must have landed before this frame returns)
     LV_HIP(hipMemcpyAsync(d_blob, pose, n_views * 12 * sizeof(float), hipMemcpyHostToDevice, stream));
-    float* img = reinterpret_cast<float*>(static_cast<char*>(d_blob) + pose_bytes);
+    float* img = reinterpret_cast<float*>(static_cast<char*>(d_blob.p) + pose_bytes);
     LV_HIP(hipMemsetD32Async((hipDeviceptr_t)img, 0x7F800000, pixels, stream));
     if (n) {
         LV_HIP(hipMemcpyAsync(d_pts, h_pts, n * sizeof(float4), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(vis_image_kernel, dim3(grid_of(n)), dim3(256), 0, stream, d_pts, (uint32_t)n, q, reinterpret_cast<uint32_t*>(img));
+        hipLaunchKernelGGL(vis_image_kernel, dim3(blocks_of(n)), dim3(256), 0, stream, d_pts, (uint32_t)n, q, reinterpret_cast<uint32_t*>(img));
         LV_HIP(hipGetLastError());
     }
     if (q.window > 0) {
-        hipLaunchKernelGGL(vis_min_cols_kernel, dim3(grid_of(pixels)), dim3(256), 0, stream, img, d_tmp, (uint32_t)pixels, q.width, q.window);
-        hipLaunchKernelGGL(vis_min_rows_kernel, dim3(grid_of(pixels)), dim3(256), 0, stream, d_tmp, img, (uint32_t)pixels, q.width, q.height,
+        hipLaunchKernelGGL(vis_min_cols_kernel, dim3(blocks_of(pixels)), dim3(256), 0, stream, img, d_tmp, (uint32_t)pixels, q.width, q.window);
+        hipLaunchKernelGGL(vis_min_rows_kernel, dim3(blocks_of(pixels)), dim3(256), 0, stream, d_tmp, img, (uint32_t)pixels, q.width, q.height,
                            q.window);
         LV_HIP(hipGetLastError());
     }
@@ -202,15 +176,14 @@ int VisStore::build(hipStream_t stream, const lv_view* views, size_t n_views, co
     return LV_OK;
 }
 
-int VisStore::ensure_hits(size_t n) { return grow(d_hits, hits_cap, n); }
+int VisStore::ensure_hits(size_t n) { return d_hits.need(n); }
 
 void VisStore::release() {
-    if (h_pts) hipHostFree(h_pts);
-    hipFree(d_pts);
-    hipFree(d_blob);
-    hipFree(d_tmp);
-    hipFree(d_hits);
-    *this = VisStore();
+    h_pts.release();
+    d_pts.release();
+    d_blob.release();
+    d_tmp.release();
+    d_hits.release();
 }
 
 int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const VisRule& q, const uint32_t* rank, uint8_t* hits, bool remove,
@@ -223,7 +196,7 @@ int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const Vi
     LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
     const float* pose = static_cast<const float*>(d_blob);
     const float* img = reinterpret_cast<const float*>(static_cast<const char*>(d_blob) + vis_pose_bytes(q.n_views));
-    hipLaunchKernelGGL(vis_classify_kernel, dim3(grid_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, pose, img, q, rank, hits,
+    hipLaunchKernelGGL(vis_classify_kernel, dim3(blocks_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, pose, img, q, rank, hits,
                        remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {

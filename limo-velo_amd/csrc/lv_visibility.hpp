@@ -33,12 +33,11 @@ int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const Vi
 // The buffers of lv_map_remove_dynamic (grown on demand, kept): staged returns, the blob and the filter's intermediate image,
 // the hit counts.
 struct VisStore {
-    float4* h_pts = nullptr;     // pinned: the returns of every view, w = the view's index
-    float4* d_pts = nullptr;
-    void* d_blob = nullptr;
-    float* d_tmp = nullptr;
-    uint8_t* d_hits = nullptr;
-    size_t h_pts_cap = 0, d_pts_cap = 0, blob_cap = 0, tmp_cap = 0, hits_cap = 0;
+    PinBuf<float4> h_pts;        // the returns of every view, w = the view's index
+    DevBuf<float4> d_pts;
+    DevBuf<void> d_blob;
+    DevBuf<float> d_tmp;
+    DevBuf<uint8_t> d_hits;
     // the blob of the call (poses + window-min images) from the views, on `stream`
     int build(hipStream_t stream, const lv_view* views, size_t n_views, const VisRule& q);
     int ensure_hits(size_t n);

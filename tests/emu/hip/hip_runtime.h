@@ -70,6 +70,7 @@ struct State {
     std::function<bool(const char* call)> fail;
     uintptr_t next_handle = 0x1000;
     std::atomic<long> mallocs{0}, frees{0}, events_created{0}, events_destroyed{0}, streams_created{0}, streams_destroyed{0};
+    std::atomic<size_t> last_alloc_bytes{0};   // of the last successful hipMalloc / hipHostMalloc
 };
 inline State& state() { static State s; return s; }
 inline hipError_t call(const char* name, hipStream_t s = nullptr, hipEvent_t e = nullptr) {
@@ -114,7 +115,7 @@ inline hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) { return emu_hip:
 inline hipError_t hipEventSynchronize(hipEvent_t ev) { return emu_hip::call("hipEventSynchronize", nullptr, ev); }
 inline hipError_t hipMalloc(void** p, size_t bytes) {
     hipError_t e = emu_hip::call("hipMalloc");
-    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; }
+    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; emu_hip::state().last_alloc_bytes = bytes; }
     return e;
 }
 template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { return hipMalloc(reinterpret_cast<void**>(p), bytes); }
@@ -134,7 +135,7 @@ inline hipError_t hipMemset(void* dst, int v, size_t bytes) {
 }
 inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
     hipError_t e = emu_hip::call("hipHostMalloc");
-    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; }
+    if (e == hipSuccess) { *p = std::malloc(bytes ? bytes : 1); ++emu_hip::state().mallocs; emu_hip::state().last_alloc_bytes = bytes; }
     return e;
 }
 inline hipError_t hipHostFree(void* p) {
