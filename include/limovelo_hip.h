@@ -651,6 +651,68 @@ int  lv_occ_plan_info(lv_ctx* ctx, lv_plan_info* out);
 /* Frees the plan. */
 int  lv_occ_plan_clear(lv_ctx* ctx);
 
+/* ---- Frontiers ---------------------------------------------------------------------------------------
+ * Where to go next when the site is not mapped yet: the boundary between space observed free and space never observed, grouped
+ * into clusters and ranked by what the planner says it costs to get there (Yamauchi's frontiers, explore_lite,
+ * frontier_exploration, the frontier clusters of FUEL in 3-D; the reference has no counterpart).  Connected-component labelling
+ * of the grid on the device.  The rule is integer arithmetic once the cell states are decided, so it is exactly defined: a pure
+ * function of the grid and the parameters, the same bits whatever the schedule.
+ *   cells, 3-D (planar = 0)  the voxels of the grid, linear index (k * ny + j) * nx + i.  A voxel is FREE iff L <= l_free,
+ *            OCCUPIED iff L >= l_occ, UNKNOWN iff L is NaN; one with l_free < L < l_occ is none of the three.
+ *   cells, planar (planar != 0)  those of lv_occ_project(k_lo, k_hi), with the same clipping (k_lo > k_hi: LV_EINVAL).  A cell is
+ *            FREE iff its projected value is 0, OCCUPIED iff it is 100, UNKNOWN iff it is -1.  The result has nx * ny cells, index
+ *            j * nx + i, and behaves as a grid with nz = 1.
+ *   frontier cell  a FREE cell with at least one UNKNOWN face neighbour (4 of them when planar, 6 in 3-D) that lies inside the
+ *            field.  The field's border is not unknown, as it is no obstacle to the distance field.
+ *   clusters  the connected components of the frontier cells under `connectivity`: 4 or 8 for a planar result, 6, 18 or 26 for a
+ *            3-D one (LV_EINVAL otherwise), plain adjacency by the moves of the planner's "moves" paragraph; there is no corner rule
+ *            here.  A component with fewer than min_size (1..2^28) cells is dropped: its cells get no label.
+ *   numbering  labels 0..C-1 by size descending, ties to the smaller `first`: the order of lv_map_cluster.
+ *   labels   one int32 per cell: the cluster's number on its members, LV_FRONTIER_NONE everywhere else.
+ *   per cluster  size; first, the smallest member index; sum[a], the sums of the members' i, j, k; lo and hi, the bounding box
+ *            (inclusive); centre[a] = (2 * sum[a] + size) / (2 * size) in integer division, the centroid rounded half up; rep, the
+ *            member that minimises dx^2 + dy^2 + dz^2 to centre, ties to the smaller index.  rep is always a frontier cell, centre
+ *            need not be.  sum[a] < 2^38.
+ *   stats    FREE cells, UNKNOWN cells, frontier cells (before min_size is applied), clusters reported (C).
+ *   rank     needs a plan (lv_occ_plan_info.built) whose planar, nx, ny, nz equal the frontier's (LV_ESTATE otherwise); reach 0..8
+ *            (LV_EINVAL otherwise).  For cluster c, best_p[c] is the least potential P over all plan cells v within Chebyshev
+ *            distance `reach` of any member of c (in a planar result in (i, j) only), clipped to the field, and best_cell[c] the v
+ *            that attains it, ties to the smaller index.  If every such P is LV_PLAN_UNREACHED: best_p[c] = LV_PLAN_UNREACHED and
+ *            best_cell[c] = -1.  (When the distance field counts unknown as an obstacle every frontier cell has s2 = 1 and is
+ *            blocked for a robot wider than a cell: the cell to drive to is a reachable one nearby.  The planner's edges are
+ *            symmetric, so a plan whose only goal is the robot's position holds the cost from the robot to every cell.)  A stale
+ *            plan, or a stale frontier, is ranked as it is.
+ * The result is a SNAPSHOT of the grid at build time, as the distance field is: lv_occ_integrate, lv_occ_load and lv_occ_clear
+ * leave it in place and set stale = 1; lv_occ_configure frees it; a new build replaces it (a build that fails in the runtime,
+ * LV_EHIP, leaves none; a refused one leaves the old result).  Building never changes a bit of the grid, the distance field or
+ * the plan.  Parameters are judged before the context (LV_EINVAL; "null context" comes last); every call gives LV_ESTATE before
+ * lv_occ_configure, fetch, clusters and rank also before a build (lv_occ_frontier_info reports built = 0 instead).  A refused call
+ * writes nothing, except as stated for lv_occ_frontier_clusters.  Nothing is allocated before the first build; lv_destroy frees
+ * everything.  The calls run on the context's stream and return when their host outputs are written. */
+#define LV_FRONTIER_NONE (-1)
+typedef struct lv_frontier_params { int planar, k_lo, k_hi, connectivity, min_size; } lv_frontier_params;
+typedef struct lv_frontier_info   { int built, planar, nx, ny, nz, stale, n_clusters; lv_frontier_params params; } lv_frontier_info;
+typedef struct lv_frontier_cluster {          /* 72 bytes */
+    int32_t size, first, rep;                 /* cells; smallest member index; representative member index */
+    int32_t centre[3], lo[3], hi[3];          /* rounded centroid; bounding box, inclusive (i, j, k) */
+    uint64_t sum[3];                          /* sums of the members' i, j, k */
+} lv_frontier_cluster;
+/* planar 0, k_lo 0, k_hi 0, connectivity 26, min_size 1. */
+void lv_default_frontier_params(lv_frontier_params* p);
+/* stats (may be NULL): as above. */
+int  lv_occ_frontier_build(lv_ctx* ctx, const lv_frontier_params* p, uint64_t stats[4]);
+/* labels: one value per cell of the result; capacity below the number of cells (or labels NULL): LV_EINVAL. */
+int  lv_occ_frontier_fetch(lv_ctx* ctx, int32_t* labels, size_t capacity);
+/* Count, then fill, as lv_map_radius_search: *n = C always; out == NULL writes only *n; capacity < C: LV_EINVAL with *n still
+ * written. */
+int  lv_occ_frontier_clusters(lv_ctx* ctx, lv_frontier_cluster* out, size_t capacity, size_t* n);
+/* best_p and / or best_cell: C values each; either may be NULL, not both (LV_EINVAL, as is capacity < C). */
+int  lv_occ_frontier_rank(lv_ctx* ctx, int reach, uint32_t* best_p, int32_t* best_cell, size_t capacity);
+/* nx, ny, nz: the result's (nz = 1 when planar); all zero with built = 0. */
+int  lv_occ_frontier_info(lv_ctx* ctx, lv_frontier_info* out);
+/* Frees the result. */
+int  lv_occ_frontier_clear(lv_ctx* ctx);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

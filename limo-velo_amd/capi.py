@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "lv_default_distance_params", "lv_occ_distance_build", "lv_occ_distance_fetch", "lv_occ_distance_query", "lv_occ_distance_info",
     "lv_occ_distance_clear",
     "lv_default_plan_params", "lv_occ_plan_build", "lv_occ_plan_fetch", "lv_occ_plan_paths", "lv_occ_plan_info", "lv_occ_plan_clear",
+    "lv_default_frontier_params", "lv_occ_frontier_build", "lv_occ_frontier_fetch", "lv_occ_frontier_clusters", "lv_occ_frontier_rank",
+    "lv_occ_frontier_info", "lv_occ_frontier_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -211,6 +213,37 @@ PLAN_ARGTYPES = {
                           C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)],
     "lv_occ_plan_info": [C.c_void_p, C.POINTER(PlanInfo)],
     "lv_occ_plan_clear": [C.c_void_p],
+}
+
+LV_FRONTIER_NONE = -1
+
+
+class FrontierParams(C.Structure):  # lv_frontier_params
+    _fields_ = [("planar", C.c_int), ("k_lo", C.c_int), ("k_hi", C.c_int), ("connectivity", C.c_int), ("min_size", C.c_int)]
+
+
+class FrontierInfo(C.Structure):  # lv_frontier_info
+    _fields_ = [("built", C.c_int), ("planar", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("stale", C.c_int),
+                ("n_clusters", C.c_int), ("params", FrontierParams)]
+
+
+class FrontierCluster(C.Structure):  # lv_frontier_cluster (72 bytes)
+    _fields_ = [("size", C.c_int32), ("first", C.c_int32), ("rep", C.c_int32), ("centre", C.c_int32 * 3), ("lo", C.c_int32 * 3),
+                ("hi", C.c_int32 * 3), ("sum", C.c_uint64 * 3)]
+
+
+# the same record as a numpy dtype (Context.occ_frontier_clusters)
+FRONTIER_CLUSTER_DTYPE = np.dtype([("size", np.int32), ("first", np.int32), ("rep", np.int32), ("centre", np.int32, 3), ("lo", np.int32, 3),
+                                   ("hi", np.int32, 3), ("sum", np.uint64, 3)])
+
+# ctypes signatures of the frontiers (include/limovelo_hip.h "Frontiers"; tests/test_occ_frontier_abi.py)
+FRONTIER_ARGTYPES = {
+    "lv_occ_frontier_build": [C.c_void_p, C.POINTER(FrontierParams), C.POINTER(C.c_uint64)],
+    "lv_occ_frontier_fetch": [C.c_void_p, C.POINTER(C.c_int32), C.c_size_t],
+    "lv_occ_frontier_clusters": [C.c_void_p, C.POINTER(FrontierCluster), C.c_size_t, C.POINTER(C.c_size_t)],
+    "lv_occ_frontier_rank": [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t],
+    "lv_occ_frontier_info": [C.c_void_p, C.POINTER(FrontierInfo)],
+    "lv_occ_frontier_clear": [C.c_void_p],
 }
 
 
@@ -435,8 +468,10 @@ def load_library() -> C.CDLL:
         lib.lv_default_distance_params.argtypes = [C.POINTER(DistanceParams)]
         lib.lv_default_plan_params.restype = None
         lib.lv_default_plan_params.argtypes = [C.POINTER(PlanParams)]
+        lib.lv_default_frontier_params.restype = None
+        lib.lv_default_frontier_params.argtypes = [C.POINTER(FrontierParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES}.items():
+                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -528,6 +563,14 @@ def default_distance_params(**kw) -> DistanceParams:
 def default_plan_params(**kw) -> PlanParams:
     p = PlanParams()
     load_library().lv_default_plan_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_frontier_params(**kw) -> FrontierParams:
+    p = FrontierParams()
+    load_library().lv_default_frontier_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -938,6 +981,51 @@ class Context:
 
     def occ_plan_clear(self):
         self._check(self.lib.lv_occ_plan_clear(self.h))
+
+    # --- frontiers (include/limovelo_hip.h "Frontiers")
+    def occ_frontier_build(self, params: FrontierParams | None = None) -> np.ndarray:
+        """lv_occ_frontier_build (default: 3-D, 26-connected, min_size 1); returns stats [4] uint64: FREE cells, UNKNOWN cells,
+        frontier cells, clusters reported."""
+        p = params if params is not None else default_frontier_params()
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_frontier_build(self.h, C.byref(p), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_frontier_info(self) -> FrontierInfo:
+        out = FrontierInfo()
+        self._check(self.lib.lv_occ_frontier_info(self.h, C.byref(out)))
+        return out
+
+    def occ_frontier_fetch(self) -> np.ndarray:
+        """The labels, int32 [nz, ny, nx] ([ny, nx] of a planar result): the cluster's number on its members, -1 elsewhere."""
+        i = self.occ_frontier_info()
+        if not i.built:   # (the library's own refusal)
+            self._check(self.lib.lv_occ_frontier_fetch(self.h, (C.c_int32 * 1)(), C.c_size_t(0)))
+        out = np.full((i.ny, i.nx) if i.planar else (i.nz, i.ny, i.nx), LV_FRONTIER_NONE, np.int32)
+        self._check(self.lib.lv_occ_frontier_fetch(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(out.size)))
+        return out
+
+    def occ_frontier_clusters(self) -> np.ndarray:
+        """The clusters in label order as a structured array (FRONTIER_CLUSTER_DTYPE).  Counts first, then fills."""
+        n = C.c_size_t(0)
+        self._check(self.lib.lv_occ_frontier_clusters(self.h, None, C.c_size_t(0), C.byref(n)))
+        out = np.zeros(int(n.value), FRONTIER_CLUSTER_DTYPE)
+        if out.size:
+            self._check(self.lib.lv_occ_frontier_clusters(self.h, out.ctypes.data_as(C.POINTER(FrontierCluster)), C.c_size_t(out.size), C.byref(n)))
+        return out
+
+    def occ_frontier_rank(self, reach: int = 0):
+        """(best_p uint32 [C], best_cell int32 [C]) over the plan last built: per cluster the least potential within Chebyshev
+        distance `reach` of a member and the cell that has it (LV_PLAN_UNREACHED and -1 where nothing is reached)."""
+        n = int(self.occ_frontier_info().n_clusters)
+        p = np.full(max(n, 1), LV_PLAN_UNREACHED, np.uint32)
+        cell = np.full(max(n, 1), -1, np.int32)
+        self._check(self.lib.lv_occ_frontier_rank(self.h, int(reach), p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  cell.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(n)))
+        return p[:n], cell[:n]
+
+    def occ_frontier_clear(self):
+        self._check(self.lib.lv_occ_frontier_clear(self.h))
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

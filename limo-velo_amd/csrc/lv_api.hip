@@ -15,6 +15,7 @@
 #include "lv_place.hpp"
 #include "lv_distance.hpp"
 #include "lv_plan.hpp"
+#include "lv_frontier.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -53,6 +54,7 @@ struct lv_ctx {
     OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
     DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
     PlanStore plan;     // lv_occ_plan_*: the cost-to-go over that field (lv_plan.hip); nothing allocated before the first build
+    FrontierStore frontier;   // lv_occ_frontier_*: the frontier clusters of that grid (lv_frontier.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -639,6 +641,7 @@ void lv_destroy(lv_ctx* c) {
     c->surface.release();
     c->cluster.release();
     c->place.release();
+    c->frontier.release();
     c->plan.release();
     c->dist.release();
     c->occ.release();
@@ -2426,6 +2429,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     LV_HIP(hipStreamSynchronize(c->stream));
     c->dist.release();   // (the field belongs to the grid it was built from)
     c->plan.release();   // (and the plan to the field)
+    c->frontier.release();   // (the frontier to the grid too)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2443,6 +2447,7 @@ int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t s
         if (w.n > 0xFFFFFFF0ull / 4 || total > 0xFFFFFFF0ull / 4) { set_error("too many returns"); return LV_EINVAL; }
     }
     if (c->dist.built) c->dist.stale = 1;
+    if (c->frontier.built) c->frontier.stale = 1;
     return c->occ.integrate(c->stream, views, n_views, stats);
 }
 
@@ -2480,6 +2485,7 @@ int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) {
         if (!(v != v) && !(v >= lo && v <= hi)) { set_error("lv_occ_load: value %g at %zu outside [%g, %g]", v, i, lo, hi); return LV_EINVAL; }
     }
     if (c->dist.built) c->dist.stale = 1;
+    if (c->frontier.built) c->frontier.stale = 1;
     return c->occ.load(c->stream, logodds);
 }
 
@@ -2487,6 +2493,7 @@ int lv_occ_clear(lv_ctx* c) {
     LV_CHECK_CTX(c);
     LV_OCC_CONFIGURED(c);
     if (c->dist.built) c->dist.stale = 1;
+    if (c->frontier.built) c->frontier.stale = 1;
     return c->occ.clear(c->stream);
 }
 
@@ -2629,6 +2636,94 @@ int lv_occ_plan_clear(lv_ctx* c) {
     LV_OCC_CONFIGURED(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->plan.release();
+    return LV_OK;
+}
+
+// ---- Frontiers (lv_frontier.hip)
+void lv_default_frontier_params(lv_frontier_params* p) {
+    if (!p) return;
+    *p = lv_frontier_params{};
+    p->connectivity = 26;
+    p->min_size = 1;
+}
+
+#define LV_FRONTIER_BUILT(c)                                                   \
+    do {                                                                       \
+        if (!(c)->frontier.built) {                                            \
+            set_error("no frontier: call lv_occ_frontier_build first");        \
+            return LV_ESTATE;                                                  \
+        }                                                                      \
+    } while (0)
+
+// (the parameters are judged before the context, as lv_occ_configure's are)
+int lv_occ_frontier_build(lv_ctx* c, const lv_frontier_params* p, uint64_t stats[4]) {
+    if (const char* why = fr_check_params(p)) { set_error("lv_occ_frontier_build: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    return c->frontier.build(c->stream, c->occ, *p, stats);
+}
+
+int lv_occ_frontier_fetch(lv_ctx* c, int32_t* labels, size_t capacity) {
+    if (!labels) { set_error("lv_occ_frontier_fetch: null labels"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_FRONTIER_BUILT(c);
+    if (capacity < c->frontier.n_cells) { set_error("lv_occ_frontier_fetch: room for %zu values needed", c->frontier.n_cells); return LV_EINVAL; }
+    return c->frontier.fetch(c->stream, labels);
+}
+
+int lv_occ_frontier_clusters(lv_ctx* c, lv_frontier_cluster* out, size_t capacity, size_t* n) {
+    if (!n) { set_error("lv_occ_frontier_clusters: null count"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_FRONTIER_BUILT(c);
+    *n = c->frontier.n_clusters;
+    if (!out) return LV_OK;   // count only
+    if (capacity < c->frontier.n_clusters) { set_error("capacity %zu < %zu clusters", capacity, c->frontier.n_clusters); return LV_EINVAL; }
+    return c->frontier.clusters(c->stream, out);
+}
+
+int lv_occ_frontier_rank(lv_ctx* c, int reach, uint32_t* best_p, int32_t* best_cell, size_t capacity) {
+    if (reach < 0 || reach > FR_MAX_REACH) { set_error("lv_occ_frontier_rank: reach %d: 0..%d", reach, FR_MAX_REACH); return LV_EINVAL; }
+    if (!best_p && !best_cell) { set_error("lv_occ_frontier_rank: best_p and best_cell are both null"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_FRONTIER_BUILT(c);
+    LV_PLAN_BUILT(c);
+    const FrontierGrid& f = c->frontier.grid;
+    const PlanGrid& g = c->plan.grid;
+    if ((f.planar != 0) != (g.planar != 0) || f.nx != g.nx || f.ny != g.ny || f.nz != g.nz) {
+        set_error("lv_occ_frontier_rank: the plan (%d x %d x %d, planar %d) is not of the frontier's cells (%d x %d x %d, planar %d)", g.nx, g.ny, g.nz,
+                  g.planar, f.nx, f.ny, f.nz, f.planar);
+        return LV_ESTATE;
+    }
+    if (capacity < c->frontier.n_clusters) { set_error("capacity %zu < %zu clusters", capacity, c->frontier.n_clusters); return LV_EINVAL; }
+    return c->frontier.rank(c->stream, c->plan, reach, best_p, best_cell);
+}
+
+int lv_occ_frontier_info(lv_ctx* c, lv_frontier_info* out) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    *out = lv_frontier_info{};
+    if (c->frontier.built) {
+        out->built = 1;
+        out->planar = c->frontier.grid.planar;
+        out->nx = c->frontier.grid.nx;
+        out->ny = c->frontier.grid.ny;
+        out->nz = c->frontier.grid.nz;
+        out->stale = c->frontier.stale;
+        out->n_clusters = (int)c->frontier.n_clusters;
+        out->params = c->frontier.prm;
+    }
+    return LV_OK;
+}
+
+int lv_occ_frontier_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_OCC_CONFIGURED(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->frontier.release();
     return LV_OK;
 }
 

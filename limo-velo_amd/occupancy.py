@@ -5,7 +5,9 @@ map_point_states() tells which points of the device map lie in space that the ac
 distance_field() / clearance() give the Euclidean distance to the nearest obstacle (lv_occ_distance_*, "Distance field") and
 costmap_from_distance() costmap_2d's inflation costs from it.  plan() / routes() build the cost-to-go to a set of goals over that
 field and walk routes down it (lv_occ_plan_*, "Planner": navfn / global_planner), with inflation_cost_table() and min_clear_s2()
-turning costmap_2d's parameters into the planner's integer ones."""
+turning costmap_2d's parameters into the planner's integer ones.  frontiers() labels the boundary between free and unknown space into
+clusters (lv_occ_frontier_*, "Frontiers": explore_lite / frontier_exploration) and explore() ranks them by the planner's cost from
+the robot and hands back targets with their routes."""
 from __future__ import annotations
 
 import math
@@ -183,3 +185,80 @@ def routes(ctx, starts):
     idx = [c % i.nx, (c // i.nx) % i.ny] + ([] if i.planar else [c // (i.nx * i.ny)])
     xyz = np.stack([np.float64(p.origin[a]) + (v + 0.5) * res for a, v in enumerate(idx)], axis=1).astype(np.float32)
     return [(xyz[int(off[s]):int(off[s + 1])], int(status[s]), int(cost[s])) for s in range(len(status))]
+
+
+def _cell_centres(p, info, cells) -> np.ndarray:
+    """[n, 3] f32 world coordinates of the centres of linear cell indices of a result with info's nx, ny (a planar result's z is
+    the grid's origin z)."""
+    c = np.asarray(cells).astype(np.int64)
+    return _ijk_centres(p, info, np.stack([c % info.nx, (c // info.nx) % info.ny, c // (info.nx * info.ny)], axis=1))
+
+
+def _ijk_centres(p, info, ijk) -> np.ndarray:
+    res = np.float64(p.resolution)
+    xyz = np.array([float(v) for v in p.origin]) + (np.asarray(ijk, np.float64).reshape(-1, 3) + 0.5) * res
+    if info.planar:
+        xyz[:, 2] = float(p.origin[2])
+    return xyz.astype(np.float32)
+
+
+def _band(p, z_band):
+    if z_band is None:
+        return {}
+    k_lo, k_hi = layers(p, float(z_band[0]), float(z_band[1]))
+    if k_lo > k_hi:
+        k_lo, k_hi = p.nz, p.nz   # (clipped to nothing: every cell unknown)
+    return dict(planar=1, k_lo=k_lo, k_hi=k_hi)
+
+
+def frontiers(ctx, z_band=None, connectivity=None, min_size=1):
+    """Builds the frontier clusters of ctx's grid and returns (labels, clusters).  labels: int32 [nz, ny, nx], or [ny, nx] over the
+    height band z_band = (z_lo, z_hi) (the layers of layers()): the cluster's number on its members, -1 elsewhere.  clusters: a
+    structured array in label order (largest first) with the fields of lv_frontier_cluster plus rep_xyz and centre_xyz, the world
+    coordinates of the centres of those cells.  connectivity: default 8 planar, 26 in 3-D; components below min_size are dropped."""
+    p = ctx.occ_params()
+    kw = _band(p, z_band)
+    kw["connectivity"] = int(connectivity) if connectivity is not None else (8 if kw else 26)
+    ctx.occ_frontier_build(capi.default_frontier_params(min_size=int(min_size), **kw))
+    return ctx.occ_frontier_fetch(), _with_world(p, ctx.occ_frontier_info(), ctx.occ_frontier_clusters())
+
+
+def _with_world(p, info, cl, extra=()):
+    out = np.zeros(len(cl), np.dtype(capi.FRONTIER_CLUSTER_DTYPE.descr + [("rep_xyz", np.float32, 3), ("centre_xyz", np.float32, 3)] + list(extra)))
+    for f in capi.FRONTIER_CLUSTER_DTYPE.names:
+        out[f] = cl[f]
+    out["rep_xyz"] = _cell_centres(p, info, cl["rep"])
+    out["centre_xyz"] = _ijk_centres(p, info, cl["centre"])
+    return out
+
+
+def explore(ctx, robot_xyz, robot_radius: float, z_band=None, reach=None, min_size=1, unknown="obstacle"):
+    """Where to drive next: builds the distance field (3-D, or planar over z_band; unknown space counts as an obstacle unless
+    unknown="free"), a plan whose only goal is the robot (the planner's edges are symmetric: it holds the cost from the robot to
+    every cell), the frontier clusters, and ranks them (reach: cells round a member in which a reachable cell is looked for;
+    default ceil(robot_radius / resolution), at most 8).  Returns (clusters, routes): the clusters of frontiers() ordered by
+    best_p, the cheapest first and the unreachable ones last, with their label, best_p, best_cell and target_xyz (the centre of
+    best_cell; NaN without one); and per cluster the polyline from the robot's cell to the target (empty without a route)."""
+    if unknown not in ("free", "obstacle"):
+        raise ValueError('unknown: "free" or "obstacle"')
+    p = ctx.occ_params()
+    band = _band(p, z_band)
+    if reach is None:
+        reach = min(int(math.ceil(float(robot_radius) / float(p.resolution))), 8)
+    ctx.occ_distance_build(capi.default_distance_params(unknown_is_obstacle=int(unknown == "obstacle"), **band))
+    plan(ctx, np.asarray(robot_xyz, np.float32).reshape(1, 3), robot_radius)
+    ctx.occ_frontier_build(capi.default_frontier_params(connectivity=8 if band else 26, min_size=int(min_size), **band))
+    info = ctx.occ_frontier_info()
+    best_p, best_cell = ctx.occ_frontier_rank(int(reach))
+    order = np.lexsort((np.arange(len(best_p)), best_p))
+    cl = _with_world(p, info, ctx.occ_frontier_clusters()[order],
+                     extra=[("label", np.int32), ("best_p", np.uint32), ("best_cell", np.int32), ("target_xyz", np.float32, 3)])
+    cl["label"], cl["best_p"], cl["best_cell"] = order, best_p[order], best_cell[order]
+    ok = cl["best_cell"] >= 0
+    cl["target_xyz"] = np.nan
+    cl["target_xyz"][ok] = _cell_centres(p, info, cl["best_cell"][ok])
+    lines = [np.zeros((0, 2 if info.planar else 3), np.float32)] * len(cl)
+    if ok.any():
+        for c, (line, _, _) in zip(np.flatnonzero(ok), routes(ctx, cl["target_xyz"][ok])):
+            lines[c] = line[::-1]   # (walked from the target down to the robot: reversed)
+    return cl, lines
