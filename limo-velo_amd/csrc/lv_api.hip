@@ -2414,13 +2414,51 @@ void lv_default_occupancy_params(lv_occupancy_params* p) {
     p->l_free = -0.4f;
 }
 
-#define LV_OCC_CONFIGURED(c)                                                         \
-    do {                                                                             \
-        if (!(c)->occ.configured) {                                                  \
-            set_error("no occupancy grid: call lv_occ_configure first");             \
-            return LV_ESTATE;                                                        \
-        }                                                                            \
+// Leaves the entry point with `code` and the message unless cond holds
+#define LV_REQUIRE(cond, code, msg) \
+    do {                            \
+        if (!(cond)) {              \
+            set_error(msg);         \
+            return code;            \
+        }                           \
     } while (0)
+// The states the entry points below ask for, each after the ones before it
+#define LV_OCC_CTX(c) \
+    LV_CHECK_CTX(c);  \
+    LV_REQUIRE((c)->occ.configured, LV_ESTATE, "no occupancy grid: call lv_occ_configure first")
+#define LV_DIST_BUILT(c) LV_REQUIRE((c)->dist.built, LV_ESTATE, "no distance field: call lv_occ_distance_build first")
+#define LV_PLAN_BUILT(c) LV_REQUIRE((c)->plan.built, LV_ESTATE, "no plan: call lv_occ_plan_build first")
+#define LV_FRONTIER_BUILT(c) LV_REQUIRE((c)->frontier.built, LV_ESTATE, "no frontier: call lv_occ_frontier_build first")
+
+// What was built from the grid (the distance field, the frontier) no longer shows it
+static void occ_grid_changed(lv_ctx* c) {
+    if (c->dist.built) c->dist.stale = 1;
+    if (c->frontier.built) c->frontier.stale = 1;
+}
+
+// What was built from the distance field (the plan) no longer shows it
+static void occ_field_changed(lv_ctx* c) {
+    if (c->plan.built) c->plan.stale = 1;
+}
+
+}  // extern "C"
+
+// What lv_distance_info, lv_plan_info and lv_frontier_info share; true: s is built (the caller adds what is its own)
+template <class Info, class Store>
+static bool occ_fill_info(Info* out, const Store& s, bool planar) {
+    *out = Info{};
+    if (!s.built) return false;
+    out->built = 1;
+    out->planar = planar;
+    out->nx = s.grid.nx;
+    out->ny = s.grid.ny;
+    out->nz = s.grid.nz;
+    out->stale = s.stale;
+    out->params = s.prm;
+    return true;
+}
+
+extern "C" {
 
 // (the parameters are judged before the context: what is wrong with them is reported whatever else is)
 int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
@@ -2434,8 +2472,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
 }
 
 int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!views) { set_error("null argument"); return LV_EINVAL; }
     if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
     size_t total = 0;
@@ -2446,22 +2483,19 @@ int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t s
         total += w.n;
         if (w.n > 0xFFFFFFF0ull / 4 || total > 0xFFFFFFF0ull / 4) { set_error("too many returns"); return LV_EINVAL; }
     }
-    if (c->dist.built) c->dist.stale = 1;
-    if (c->frontier.built) c->frontier.stale = 1;
+    occ_grid_changed(c);
     return c->occ.integrate(c->stream, views, n_views, stats);
 }
 
 int lv_occ_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* logodds) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (n && (!pts || !logodds || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
     if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
     return c->occ.query(c->stream, pts, stride, n, logodds);
 }
 
 int lv_occ_project(lv_ctx* c, int k_lo, int k_hi, int8_t* grid2d, size_t capacity) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
     if (!grid2d || capacity < plane) { set_error("grid2d: room for nx * ny = %zu values needed", plane); return LV_EINVAL; }
     if (k_lo > k_hi) { set_error("layers %d..%d: k_lo <= k_hi", k_lo, k_hi); return LV_EINVAL; }
@@ -2469,37 +2503,31 @@ int lv_occ_project(lv_ctx* c, int k_lo, int k_hi, int8_t* grid2d, size_t capacit
 }
 
 int lv_occ_fetch(lv_ctx* c, float* logodds, size_t capacity) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!logodds || capacity < c->occ.n_vox) { set_error("logodds: room for nx * ny * nz = %zu values needed", c->occ.n_vox); return LV_EINVAL; }
     return c->occ.fetch(c->stream, logodds);
 }
 
 int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!logodds || n != c->occ.n_vox) { set_error("lv_occ_load: %zu values for a grid of %zu voxels", n, c->occ.n_vox); return LV_EINVAL; }
     const float lo = c->occ.prm.l_min, hi = c->occ.prm.l_max;
     for (size_t i = 0; i < n; ++i) {
         const float v = logodds[i];
         if (!(v != v) && !(v >= lo && v <= hi)) { set_error("lv_occ_load: value %g at %zu outside [%g, %g]", v, i, lo, hi); return LV_EINVAL; }
     }
-    if (c->dist.built) c->dist.stale = 1;
-    if (c->frontier.built) c->frontier.stale = 1;
+    occ_grid_changed(c);
     return c->occ.load(c->stream, logodds);
 }
 
 int lv_occ_clear(lv_ctx* c) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
-    if (c->dist.built) c->dist.stale = 1;
-    if (c->frontier.built) c->frontier.stale = 1;
+    LV_OCC_CTX(c);
+    occ_grid_changed(c);
     return c->occ.clear(c->stream);
 }
 
 int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
     *out = c->occ.prm;
     return LV_OK;
@@ -2514,53 +2542,39 @@ void lv_default_distance_params(lv_distance_params* p) {
 // (the parameters are judged before the context, as lv_occ_configure's are)
 int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats[4]) {
     if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
-    if (c->plan.built) c->plan.stale = 1;
+    LV_OCC_CTX(c);
+    occ_field_changed(c);
     return c->dist.build(c->stream, c->occ, *p, stats);
 }
 
 int lv_occ_distance_fetch(lv_ctx* c, int32_t* s2, float* metres, size_t capacity) {
     if (!s2 && !metres) { set_error("lv_occ_distance_fetch: s2 and metres are both null"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
-    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    LV_OCC_CTX(c);
+    LV_DIST_BUILT(c);
     if (capacity < c->dist.n_vox) { set_error("lv_occ_distance_fetch: room for %zu values needed", c->dist.n_vox); return LV_EINVAL; }
     return c->dist.fetch(c->stream, s2, metres);
 }
 
 int lv_occ_distance_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* dist, float* grad) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
-    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    LV_OCC_CTX(c);
+    LV_DIST_BUILT(c);
     if (n && (!pts || !dist || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
     if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
     return c->dist.query(c->stream, pts, stride, n, dist, grad);
 }
 
 int lv_occ_distance_info(lv_ctx* c, lv_distance_info* out) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
-    *out = lv_distance_info{};
-    if (c->dist.built) {
-        out->built = 1;
-        out->planar = c->dist.prm.planar != 0;
-        out->nx = c->dist.grid.nx;
-        out->ny = c->dist.grid.ny;
-        out->nz = c->dist.grid.nz;
-        out->stale = c->dist.stale;
-        out->params = c->dist.prm;
-    }
+    occ_fill_info(out, c->dist, c->dist.prm.planar != 0);
     return LV_OK;
 }
 
 int lv_occ_distance_clear(lv_ctx* c) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->dist.release();
-    if (c->plan.built) c->plan.stale = 1;
+    occ_field_changed(c);
     return LV_OK;
 }
 
@@ -2572,29 +2586,19 @@ void lv_default_plan_params(lv_plan_params* p) {
     p->min_clear_s2 = 1;
 }
 
-#define LV_PLAN_BUILT(c)                                                       \
-    do {                                                                       \
-        if (!(c)->plan.built) {                                                \
-            set_error("no plan: call lv_occ_plan_build first");                \
-            return LV_ESTATE;                                                  \
-        }                                                                      \
-    } while (0)
-
 // (parameters, table and counts are judged before the context, as lv_occ_configure's parameters are)
 int lv_occ_plan_build(lv_ctx* c, const lv_plan_params* p, const uint8_t* cost, size_t n_cost, const void* goals, size_t stride, size_t n_goals,
                       uint64_t stats[4]) {
     if (const char* why = plan_check(p, cost, n_cost, goals, stride, n_goals)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
-    if (!c->dist.built) { set_error("no distance field: call lv_occ_distance_build first"); return LV_ESTATE; }
+    LV_OCC_CTX(c);
+    LV_DIST_BUILT(c);
     if (const char* why = plan_check_field(p->connectivity, c->dist.prm.planar != 0)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
     return c->plan.build(c->stream, c->dist, *p, cost, n_cost, goals, stride, n_goals, stats);
 }
 
 int lv_occ_plan_fetch(lv_ctx* c, uint32_t* potential, uint8_t* cell_cost, size_t capacity) {
     if (!potential && !cell_cost) { set_error("lv_occ_plan_fetch: potential and cell_cost are both null"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_PLAN_BUILT(c);
     if (capacity < c->plan.n_cells) { set_error("lv_occ_plan_fetch: room for %zu values needed", c->plan.n_cells); return LV_EINVAL; }
     return c->plan.fetch(c->stream, potential, cell_cost);
@@ -2602,8 +2606,7 @@ int lv_occ_plan_fetch(lv_ctx* c, uint32_t* potential, uint8_t* cell_cost, size_t
 
 int lv_occ_plan_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* cells,
                       size_t capacity, size_t* total) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_PLAN_BUILT(c);
     if (!offsets || !total || (n && (!starts || !status || !cost || stride < 12))) {
         set_error("bad start array (stride %zu) or null status / cost / offsets / total", stride);
@@ -2614,26 +2617,14 @@ int lv_occ_plan_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, in
 }
 
 int lv_occ_plan_info(lv_ctx* c, lv_plan_info* out) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
-    *out = lv_plan_info{};
-    if (c->plan.built) {
-        out->built = 1;
-        out->planar = c->plan.grid.planar;
-        out->nx = c->plan.grid.nx;
-        out->ny = c->plan.grid.ny;
-        out->nz = c->plan.grid.nz;
-        out->stale = c->plan.stale;
-        out->rounds = c->plan.rounds;
-        out->params = c->plan.prm;
-    }
+    if (occ_fill_info(out, c->plan, c->plan.grid.planar != 0)) out->rounds = c->plan.rounds;
     return LV_OK;
 }
 
 int lv_occ_plan_clear(lv_ctx* c) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->plan.release();
     return LV_OK;
@@ -2647,26 +2638,16 @@ void lv_default_frontier_params(lv_frontier_params* p) {
     p->min_size = 1;
 }
 
-#define LV_FRONTIER_BUILT(c)                                                   \
-    do {                                                                       \
-        if (!(c)->frontier.built) {                                            \
-            set_error("no frontier: call lv_occ_frontier_build first");        \
-            return LV_ESTATE;                                                  \
-        }                                                                      \
-    } while (0)
-
 // (the parameters are judged before the context, as lv_occ_configure's are)
 int lv_occ_frontier_build(lv_ctx* c, const lv_frontier_params* p, uint64_t stats[4]) {
     if (const char* why = fr_check_params(p)) { set_error("lv_occ_frontier_build: %s", why); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     return c->frontier.build(c->stream, c->occ, *p, stats);
 }
 
 int lv_occ_frontier_fetch(lv_ctx* c, int32_t* labels, size_t capacity) {
     if (!labels) { set_error("lv_occ_frontier_fetch: null labels"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_FRONTIER_BUILT(c);
     if (capacity < c->frontier.n_cells) { set_error("lv_occ_frontier_fetch: room for %zu values needed", c->frontier.n_cells); return LV_EINVAL; }
     return c->frontier.fetch(c->stream, labels);
@@ -2674,8 +2655,7 @@ int lv_occ_frontier_fetch(lv_ctx* c, int32_t* labels, size_t capacity) {
 
 int lv_occ_frontier_clusters(lv_ctx* c, lv_frontier_cluster* out, size_t capacity, size_t* n) {
     if (!n) { set_error("lv_occ_frontier_clusters: null count"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_FRONTIER_BUILT(c);
     *n = c->frontier.n_clusters;
     if (!out) return LV_OK;   // count only
@@ -2686,8 +2666,7 @@ int lv_occ_frontier_clusters(lv_ctx* c, lv_frontier_cluster* out, size_t capacit
 int lv_occ_frontier_rank(lv_ctx* c, int reach, uint32_t* best_p, int32_t* best_cell, size_t capacity) {
     if (reach < 0 || reach > FR_MAX_REACH) { set_error("lv_occ_frontier_rank: reach %d: 0..%d", reach, FR_MAX_REACH); return LV_EINVAL; }
     if (!best_p && !best_cell) { set_error("lv_occ_frontier_rank: best_p and best_cell are both null"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_FRONTIER_BUILT(c);
     LV_PLAN_BUILT(c);
     const FrontierGrid& f = c->frontier.grid;
@@ -2702,26 +2681,14 @@ int lv_occ_frontier_rank(lv_ctx* c, int reach, uint32_t* best_p, int32_t* best_c
 }
 
 int lv_occ_frontier_info(lv_ctx* c, lv_frontier_info* out) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
-    *out = lv_frontier_info{};
-    if (c->frontier.built) {
-        out->built = 1;
-        out->planar = c->frontier.grid.planar;
-        out->nx = c->frontier.grid.nx;
-        out->ny = c->frontier.grid.ny;
-        out->nz = c->frontier.grid.nz;
-        out->stale = c->frontier.stale;
-        out->n_clusters = (int)c->frontier.n_clusters;
-        out->params = c->frontier.prm;
-    }
+    if (occ_fill_info(out, c->frontier, c->frontier.grid.planar != 0)) out->n_clusters = (int)c->frontier.n_clusters;
     return LV_OK;
 }
 
 int lv_occ_frontier_clear(lv_ctx* c) {
-    LV_CHECK_CTX(c);
-    LV_OCC_CONFIGURED(c);
+    LV_OCC_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->frontier.release();
     return LV_OK;

@@ -3,14 +3,14 @@
 //
 // One build is five kernels on the context's stream, every one with its lanes along x so that each load and store of a wavefront is
 // one contiguous run of a row:
-//   dist_classify_kernel  one wavefront per 64 consecutive x of a row: the obstacle test per lane (the planar field walks its
-//                         band of layers), one __ballot, two words of the one-bit-per-voxel bitmap (the occupancy bitmaps' layout).
+//   dist_classify_kernel  one wavefront per 64 consecutive x of a row: the obstacle test per lane (the planar field projects its
+//                         band of layers: grid_project_column), one __ballot, two words of the one-bit-per-voxel bitmap (the occupancy bitmaps' layout).
 //   dist_x_kernel         one lane per voxel: the nearest set bit of its row (the nearest clear one for an obstacle of a signed
 //                         field) by clz / ctz over the row's at most 32 words, which sit in L2.  Writes +-dx^2, +-FAR or 0.
 //   dist_y_kernel         one lane per voxel: dist_pass_line along y (stride nx).  The wavefront's neighbours in x read the
 //                         neighbouring words, so every step of the outward scan is a coalesced load.
-//   dist_z_kernel         the same along z (stride nx * ny), then truncation and the stats: sums and maxima folded per wavefront
-//                         and per workgroup, one partial record per workgroup.
+//   dist_z_kernel         the same along z (stride nx * ny), then truncation and the stats: sums and maxima folded per workgroup
+//                         (block_fold4), one partial record per workgroup.
 //   dist_stats_kernel     one workgroup folds the partial records (integer sums and maxima: the order does not matter).  One
 //                         atomic per wavefront on the four counters instead was measured: the atomics on four addresses took
 //                         6.3 of the 9.7 ms of a build of the default grid.
@@ -59,23 +59,9 @@ __global__ __launch_bounds__(256) void dist_x_kernel(const uint32_t* __restrict_
 __global__ __launch_bounds__(256) void dist_y_kernel(const int32_t* __restrict__ in, DistGrid g, uint32_t n, int32_t* __restrict__ out) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
-    const uint32_t plane = (uint32_t)g.nx * (uint32_t)g.ny;
-    const uint32_t k = v / plane, r = v - k * plane;
-    const uint32_t j = r / (uint32_t)g.nx, i = r - j * (uint32_t)g.nx;
-    out[v] = dist_pass_line(in + (size_t)k * plane + i, (size_t)g.nx, g.ny, (int)j, g.reach);
-}
-
-__device__ __forceinline__ unsigned long long dist_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long dist_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
+    int i, j, k;
+    grid_ijk(g, v, i, j, k);
+    out[v] = dist_pass_line(in + grid_at(g, i, 0, k), (size_t)g.nx, g.ny, j, g.reach);
 }
 
 // part: per workgroup obstacles, finite values, largest finite d2_out, largest finite d2_in
@@ -96,24 +82,8 @@ __global__ __launch_bounds__(256) void dist_z_kernel(const int32_t* __restrict__
             else mi = (unsigned long long)(-s);
         }
     }
-    ob = dist_wave_sum(ob);
-    fin = dist_wave_sum(fin);
-    mo = dist_wave_max(mo);
-    mi = dist_wave_max(mi);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) {
-        sh[wave][0] = ob;
-        sh[wave][1] = fin;
-        sh[wave][2] = mo;
-        sh[wave][3] = mi;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const uint32_t c = threadIdx.x;
-        unsigned long long a = sh[0][c];
-        for (uint32_t w = 1; w < 4; ++w) a = c < 2 ? a + sh[w][c] : (sh[w][c] > a ? sh[w][c] : a);
-        part[(size_t)blockIdx.x * 4 + c] = a;
-    }
+    unsigned long long a;
+    if (block_fold4(sh, ob, fin, mo, mi, a)) part[(size_t)blockIdx.x * 4 + threadIdx.x] = a;
 }
 
 // one workgroup of 1024: the n_blocks partial records of dist_z_kernel into stats[4]
@@ -127,24 +97,8 @@ __global__ __launch_bounds__(1024) void dist_stats_kernel(const unsigned long lo
         mo = o > mo ? o : mo;
         mi = i > mi ? i : mi;
     }
-    ob = dist_wave_sum(ob);
-    fin = dist_wave_sum(fin);
-    mo = dist_wave_max(mo);
-    mi = dist_wave_max(mi);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) {
-        sh[wave][0] = ob;
-        sh[wave][1] = fin;
-        sh[wave][2] = mo;
-        sh[wave][3] = mi;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const uint32_t c = threadIdx.x;
-        unsigned long long a = sh[0][c];
-        for (uint32_t w = 1; w < 16; ++w) a = c < 2 ? a + sh[w][c] : (sh[w][c] > a ? sh[w][c] : a);
-        stats[c] = a;
-    }
+    unsigned long long a;
+    if (block_fold4(sh, ob, fin, mo, mi, a)) stats[threadIdx.x] = a;
 }
 
 __global__ __launch_bounds__(256) void dist_metres_kernel(const int32_t* __restrict__ s2, float resolution, uint32_t n, float* __restrict__ out) {
@@ -178,7 +132,7 @@ void DistStore::release() {
 
 int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t out[4]) {
     const DistGrid g = dist_grid_of(occ.grid, p);
-    const size_t nv = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
+    const size_t nv = grid_cells(g);
     const size_t nw = (size_t)g.wx * (size_t)g.ny * (size_t)g.nz;
     LV_HIP(hipStreamSynchronize(stream));
     built = false;   // (before a buffer goes, and until the passes are through)
@@ -188,7 +142,8 @@ int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_
     if (!rc) rc = d_part.need((size_t)blocks_of(nv) * 4);
     if (!rc) rc = stats.need();
     if (rc) return rc;
-    const int k0 = p.k_lo < 0 ? 0 : p.k_lo, k1 = p.k_hi >= occ.grid.nz ? occ.grid.nz - 1 : p.k_hi;
+    int k0, k1;
+    grid_clip_band(p.k_lo, p.k_hi, occ.grid.nz, k0, k1);
     const size_t rows = (size_t)g.ny * (size_t)g.nz;
     const uint32_t n_waves = (uint32_t)(rows * (((size_t)g.nx + 63) / 64));
     hipLaunchKernelGGL(dist_classify_kernel, dim3((n_waves + 3) / 4), dim3(256), 0, stream, occ.d_L, g, p.planar != 0, k0, k1, occ.prm.l_occ,

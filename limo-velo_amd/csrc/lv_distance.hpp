@@ -31,15 +31,10 @@ struct DistGrid {
 // 3-D field: L >= l_occ (NaN compares false), or unknown when unknown counts
 LV_OCC_HD bool dist_obstacle(float L, float l_occ, bool unknown_is_obstacle) { return L >= l_occ || (unknown_is_obstacle && L != L); }
 
-// planar field: column c of lv_occ_project over the clipped layers k0..k1 (k0 > k1: an empty band, every cell -1)
+// planar field: column c of lv_occ_project over the clipped layers k0..k1 is 100, or -1 when unknown counts
 LV_OCC_HD bool dist_obstacle_planar(const float* L, size_t plane, size_t c, int k0, int k1, float l_occ, float l_free, bool unknown_is_obstacle) {
-    bool occ = false, fre = false;
-    for (int k = k0; k <= k1; ++k) {
-        const float v = L[(size_t)k * plane + c];
-        occ |= v >= l_occ;
-        fre |= v <= l_free;
-    }
-    return occ || (unknown_is_obstacle && !fre);   // 100, or -1
+    const int v = grid_project_column(L, plane, c, k0, k1, l_occ, l_free);
+    return v == 100 || (unknown_is_obstacle && v == -1);
 }
 
 // word w of a bitmap row; inv: the complement, without the bits past nx
@@ -140,19 +135,15 @@ LV_OCC_HD float dist_gradient(float m_minus, float m0, float m_plus, bool has_mi
 
 // One query point against a finished field: dist, and grad[3] when grad is not NULL
 LV_OCC_HD void dist_query_point(const DistGrid& g, const float origin[3], bool planar, const int32_t* s2, const float p[3], float* dist, float* grad) {
-    int32_t q[3] = {0, 0, 0};
-    bool ok = true;
-    for (int a = 0; a < (planar ? 2 : 3); ++a) ok = occ_quant(p[a], origin[a], g.resolution, q[a]) && ok;
-    const int32_t v[3] = {q[0] >> 8, q[1] >> 8, q[2] >> 8};
-    const int n[3] = {g.nx, g.ny, g.nz};
-    ok = ok && (uint32_t)v[0] < (uint32_t)g.nx && (uint32_t)v[1] < (uint32_t)g.ny && (uint32_t)v[2] < (uint32_t)g.nz;
-    if (!ok) {
+    int i, j, k;
+    if (!grid_cell_of(g, origin, g.resolution, planar, p, i, j, k)) {
         *dist = __uint_as_float(0x7FC00000u);
         if (grad) grad[0] = grad[1] = grad[2] = 0.0f;
         return;
     }
     const size_t step[3] = {1, (size_t)g.nx, (size_t)g.nx * (size_t)g.ny};
-    const size_t at = ((size_t)v[2] * (size_t)g.ny + (size_t)v[1]) * (size_t)g.nx + (size_t)v[0];
+    const int v[3] = {i, j, k}, n[3] = {g.nx, g.ny, g.nz};
+    const size_t at = grid_at(g, i, j, k);
     const float m0 = dist_metres(s2[at], g.resolution);
     *dist = m0;
     if (!grad) return;
@@ -192,7 +183,7 @@ struct DistStore {
     DistGrid grid{};
     float origin[3] = {0.f, 0.f, 0.f};
     size_t n_vox = 0;                // of the field
-    DevBuf<int32_t> d_s2;            // the field: (k * ny + j) * nx + i
+    DevBuf<int32_t> d_s2;            // the field, by grid_at
     DevBuf<int32_t> d_tmp;           // the Y pass's output; lv_occ_distance_fetch's metres
     DevBuf<uint32_t> d_bits;         // obstacle bitmap, the occupancy bitmaps' layout
     DevBuf<unsigned long long> d_part;   // one record of 4 per workgroup of the Z pass

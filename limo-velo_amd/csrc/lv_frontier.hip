@@ -3,7 +3,7 @@
 //
 // A build is connected-component labelling in tiles on the context's stream:
 //   fr_tile_kernel      one workgroup of 256 per tile (32 x 32 cells planar, 32 x 8 x 4 in 3-D; 4 cells per lane).  The states of the
-//                       tile and a one-cell halo go into LDS (3-D: one read of L per cell instead of seven; planar: the column's
+//                       tile's haloed box (HaloTile, lv_grid.hpp) go into LDS (3-D: one read of L per cell instead of seven; planar: the column's
 //                       projection), the frontier predicate runs on the LDS tile, and the tile's frontier cells are labelled in LDS
 //                       to the tile's fixpoint: every cell takes the least label among its neighbours (fr_neighbour), then the
 //                       label of its label, until nothing changes.  Only a cell's owner writes its label and labels only fall, so
@@ -38,42 +38,12 @@ namespace {
 constexpr int FR_PX = 32, FR_PY = 32, FR_PZ = 1;   // a planar tile
 constexpr int FR_VX = 32, FR_VY = 8, FR_VZ = 4;    // a 3-D tile
 
-// A workgroup's tile with its one-cell halo in LDS; coordinates are local to the tile, -1 .. T
-template <int TX, int TY, int TZ>
+// The accessor of lv_frontier.hpp over a workgroup's HaloTile in LDS
+template <class T>
 struct FrTile {
-    static constexpr int HZ = TZ > 1 ? 1 : 0;   // a planar result has no halo in z
-    static constexpr int LX = TX + 2, LY = TY + 2, LZ = TZ + 2 * HZ;
-    static constexpr int CELLS = TX * TY * TZ, LCELLS = LX * LY * LZ;
     const uint8_t* s;
-    __device__ __forceinline__ static int at(int i, int j, int k) { return ((k + HZ) * LY + (j + 1)) * LX + (i + 1); }
-    __device__ __forceinline__ int state(int i, int j, int k) const { return s[at(i, j, k)]; }
+    __device__ __forceinline__ int state(int i, int j, int k) const { return s[T::at(i, j, k)]; }
 };
-
-__device__ __forceinline__ unsigned long long fr_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned long long fr_wave_min(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int fr_wave_min(int v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const int w = __shfl_xor(v, o);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int fr_wave_max(int v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const int w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 // the neighbour offsets of the connectivity as a mask over plan_move's 27 (uniform: scalar work)
 __device__ __forceinline__ uint32_t fr_neighbour_mask(const FrontierGrid& g) {
@@ -89,35 +59,36 @@ __device__ __forceinline__ uint32_t fr_neighbour_mask(const FrontierGrid& g) {
 template <int TX, int TY, int TZ>
 __global__ __launch_bounds__(256) void fr_tile_kernel(const float* __restrict__ L, FrontierGrid g, int k0, int k1, float l_free, float l_occ,
                                                       uint32_t* __restrict__ parent, unsigned long long* __restrict__ stats) {
-    using T = FrTile<TX, TY, TZ>;
+    using T = HaloTile<TX, TY, TZ>;
     constexpr int NPT = T::CELLS / 256;   // cells per lane
     static_assert(T::CELLS % 256 == 0, "a tile is a whole number of cells per lane");
     __shared__ uint8_t ss[T::LCELLS];
     __shared__ uint32_t sl[T::LCELLS];
     const uint32_t t = blockIdx.x, tid = threadIdx.x;
-    const int tiles_x = (g.nx + TX - 1) / TX, tiles_y = (g.ny + TY - 1) / TY;
-    const int tx = (int)(t % (uint32_t)tiles_x), ty = (int)((t / (uint32_t)tiles_x) % (uint32_t)tiles_y), tz = (int)(t / (uint32_t)(tiles_x * tiles_y));
+    int tx, ty, tz;
+    T::origin_of(g, t, tx, ty, tz);
     const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
     const size_t plane = (size_t)g.nx * (size_t)g.ny;
     for (int l = (int)tid; l < T::LCELLS; l += 256) {
-        const int gi = x0 + l % T::LX - 1, gj = y0 + (l / T::LX) % T::LY - 1, gk = z0 + l / (T::LX * T::LY) - T::HZ;
+        int di, dj, dk;
+        T::halo_of(l, di, dj, dk);
         int st = FR_OUTSIDE;
-        if ((uint32_t)gi < (uint32_t)g.nx && (uint32_t)gj < (uint32_t)g.ny && (uint32_t)gk < (uint32_t)g.nz) {
-            const size_t col = (size_t)gj * (size_t)g.nx + (size_t)gi;
-            st = g.planar ? fr_state_column(L, plane, col, k0, k1, l_free, l_occ) : fr_state_voxel(L[(size_t)gk * plane + col], l_free, l_occ);
+        if (grid_inside(g, x0 + di, y0 + dj, z0 + dk)) {
+            const size_t cell = grid_at(g, x0 + di, y0 + dj, z0 + dk);   // (planar: z0 + dk = 0, the cell is the column)
+            st = g.planar ? fr_state_column(L, plane, cell, k0, k1, l_free, l_occ) : fr_state_voxel(L[cell], l_free, l_occ);
         }
         ss[l] = (uint8_t)st;
         sl[l] = CL_NONE;
     }
     __syncthreads();
-    const T tile{ss};
+    const FrTile<T> tile{ss};
     int at[NPT];
     bool mine[NPT];
     unsigned long long n_free = 0, n_unknown = 0, n_frontier = 0;
 #pragma unroll
     for (int q = 0; q < NPT; ++q) {
-        const int c = (int)tid + q * 256;
-        const int i = c % TX, j = (c / TX) % TY, k = c / (TX * TY);
+        int i, j, k;
+        T::local_of((int)tid + q * 256, i, j, k);
         at[q] = T::at(i, j, k);
         const int st = ss[at[q]];   // (FR_OUTSIDE past the field's edge: neither counted nor a frontier)
         n_free += st == FR_FREE;
@@ -163,25 +134,20 @@ __global__ __launch_bounds__(256) void fr_tile_kernel(const float* __restrict__ 
     }
 #pragma unroll
     for (int q = 0; q < NPT; ++q) {
-        const int c = (int)tid + q * 256;
-        const int gi = x0 + c % TX, gj = y0 + (c / TX) % TY, gk = z0 + c / (TX * TY);
-        if (gi >= g.nx || gj >= g.ny || gk >= g.nz) continue;
+        int i, j, k;
+        T::local_of((int)tid + q * 256, i, j, k);
+        if (x0 + i >= g.nx || y0 + j >= g.ny || z0 + k >= g.nz) continue;
         uint32_t p = CL_NONE;
-        if (mine[q]) {
-            const int a = (int)sl[at[q]];
-            const int li = a % T::LX - 1, lj = (a / T::LX) % T::LY - 1, lk = a / (T::LX * T::LY) - T::HZ;
-            p = (uint32_t)(((size_t)(z0 + lk) * (size_t)g.ny + (size_t)(y0 + lj)) * (size_t)g.nx + (size_t)(x0 + li));
+        if (mine[q]) {   // the LDS label back to the global cell it stands for
+            int li, lj, lk;
+            T::halo_of((int)sl[at[q]], li, lj, lk);
+            p = (uint32_t)grid_at(g, x0 + li, y0 + lj, z0 + lk);
         }
-        parent[((size_t)gk * (size_t)g.ny + (size_t)gj) * (size_t)g.nx + (size_t)gi] = p;
+        parent[grid_at(g, x0 + i, y0 + j, z0 + k)] = p;
     }
-    n_free = fr_wave_sum(n_free);
-    n_unknown = fr_wave_sum(n_unknown);
-    n_frontier = fr_wave_sum(n_frontier);
-    if ((tid & 63u) == 0) {
-        if (n_free) atomicAdd(&stats[0], n_free);
-        if (n_unknown) atomicAdd(&stats[1], n_unknown);
-        if (n_frontier) atomicAdd(&stats[2], n_frontier);
-    }
+    wave_add_to(&stats[0], n_free);
+    wave_add_to(&stats[1], n_unknown);
+    wave_add_to(&stats[2], n_frontier);
 }
 
 // (tx, ty, tz: the tile edges of fr_tile_kernel)
@@ -194,9 +160,9 @@ __global__ __launch_bounds__(256) void fr_seam_kernel(FrontierGrid g, int tx, in
         int dx, dy, dz;
         if (!fr_neighbour(mv, g.max_m, g.planar != 0, dx, dy, dz)) continue;
         const int ni = i + dx, nj = j + dy, nk = k + dz;
-        if ((uint32_t)ni >= (uint32_t)g.nx || (uint32_t)nj >= (uint32_t)g.ny || (uint32_t)nk >= (uint32_t)g.nz) continue;
+        if (!grid_inside(g, ni, nj, nk)) continue;
         if (ni / tx == i / tx && nj / ty == j / ty && nk / tz == k / tz) continue;   // (the tile has joined them)
-        const uint32_t v = (uint32_t)(((size_t)nk * (size_t)g.ny + (size_t)nj) * (size_t)g.nx + (size_t)ni);
+        const uint32_t v = (uint32_t)grid_at(g, ni, nj, nk);
         if (cl_load(parent + v) != CL_NONE) cl_link(parent, c, v);
     }
 }
@@ -244,9 +210,9 @@ __global__ __launch_bounds__(256) void fr_accumulate_kernel(FrontierGrid g, uint
         unsigned long long s[3];
         int lo[3], hi[3];
         for (int a = 0; a < 3; ++a) {
-            s[a] = fr_wave_sum(valid ? (unsigned long long)v[a] : 0ull);
-            lo[a] = fr_wave_min(valid ? v[a] : 0x7FFFFFFF);
-            hi[a] = fr_wave_max(valid ? v[a] : -1);
+            s[a] = wave_sum(valid ? (unsigned long long)v[a] : 0ull);
+            lo[a] = wave_min(valid ? v[a] : 0x7FFFFFFF);
+            hi[a] = wave_max(valid ? v[a] : -1);
         }
         if ((int)(threadIdx.x & 63u) == src) {
             atomicAdd(&size[d0], (uint32_t)members);
@@ -305,7 +271,7 @@ __device__ __forceinline__ void fr_bid(unsigned long long* best, bool valid, int
     const int src = __ffsll((long long)vm) - 1;
     const int32_t lab0 = __shfl(lab, src);
     if (__ballot(valid && lab != lab0) == 0) {
-        const unsigned long long b = fr_wave_min(valid ? bid : ~0ull);
+        const unsigned long long b = wave_min(valid ? bid : ~0ull);
         if ((int)(threadIdx.x & 63u) == src && b != ~0ull) atomicMin(&best[lab0], b);
     } else if (valid && bid != ~0ull) {
         atomicMin(&best[lab], bid);
@@ -371,11 +337,12 @@ int FrontierStore::build(hipStream_t stream, const OccStore& occ, const lv_front
     g.nz = p.planar ? 1 : occ.grid.nz;
     g.planar = p.planar != 0;
     g.max_m = plan_max_m(p.connectivity);
-    const size_t nc = (size_t)g.nx * (size_t)g.ny * (size_t)g.nz;
+    const size_t nc = grid_cells(g);
     const uint32_t n = (uint32_t)nc;
-    const int k0 = p.k_lo < 0 ? 0 : p.k_lo, k1 = p.k_hi >= occ.grid.nz ? occ.grid.nz - 1 : p.k_hi;   // lv_occ_project's clipping
+    int k0, k1;
+    grid_clip_band(p.k_lo, p.k_hi, occ.grid.nz, k0, k1);
     const int tx = g.planar ? FR_PX : FR_VX, ty = g.planar ? FR_PY : FR_VY, tz = g.planar ? FR_PZ : FR_VZ;
-    const size_t nt = (size_t)((g.nx + tx - 1) / tx) * (size_t)((g.ny + ty - 1) / ty) * (size_t)((g.nz + tz - 1) / tz);
+    const size_t nt = g.planar ? HaloTile<FR_PX, FR_PY, FR_PZ>::tiles(g) : HaloTile<FR_VX, FR_VY, FR_VZ>::tiles(g);
     LV_HIP(hipStreamSynchronize(stream));   // (the pinned words below are free)
     built = false;   // (before a buffer goes: the old result's are overwritten from here on)
     n_clusters = 0;
@@ -387,12 +354,8 @@ int FrontierStore::build(hipStream_t stream, const OccStore& occ, const lv_front
     if (!rc) rc = stats.zero(stream);
     if (rc) return rc;
     LV_HIP(hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned long long), stream));
-    if (g.planar)
-        hipLaunchKernelGGL((fr_tile_kernel<FR_PX, FR_PY, FR_PZ>), dim3((uint32_t)nt), dim3(256), 0, stream, occ.d_L, g, k0, k1, occ.prm.l_free,
-                           occ.prm.l_occ, d_parent, stats.d);
-    else
-        hipLaunchKernelGGL((fr_tile_kernel<FR_VX, FR_VY, FR_VZ>), dim3((uint32_t)nt), dim3(256), 0, stream, occ.d_L, g, k0, k1, occ.prm.l_free,
-                           occ.prm.l_occ, d_parent, stats.d);
+    const auto tile_kernel = g.planar ? fr_tile_kernel<FR_PX, FR_PY, FR_PZ> : fr_tile_kernel<FR_VX, FR_VY, FR_VZ>;
+    hipLaunchKernelGGL(tile_kernel, dim3((uint32_t)nt), dim3(256), 0, stream, occ.d_L, g, k0, k1, occ.prm.l_free, occ.prm.l_occ, d_parent, stats.d);
     hipLaunchKernelGGL(fr_seam_kernel, dim3(blocks_of(nc)), dim3(256), 0, stream, g, tx, ty, tz, n, d_parent);
     hipLaunchKernelGGL(fr_flatten_kernel, dim3(blocks_of(nc)), dim3(256), 0, stream, n, d_parent, d_root, d_cnt);
     LV_HIP(hipGetLastError());

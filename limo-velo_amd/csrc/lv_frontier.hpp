@@ -39,18 +39,12 @@ LV_OCC_HD int fr_state_voxel(float L, float l_free, float l_occ) {
     return L != L ? FR_UNKNOWN : L >= l_occ ? FR_OCCUPIED : L <= l_free ? FR_FREE : FR_OTHER;
 }
 
-// planar: a value of lv_occ_project
+// planar: a value of lv_occ_project (grid_project_column)
 LV_OCC_HD int fr_state_projected(int v) { return v == 100 ? FR_OCCUPIED : v == 0 ? FR_FREE : FR_UNKNOWN; }
 
-// planar: column c of lv_occ_project over the clipped layers k0..k1 (k0 > k1: an empty band, every cell -1)
+// planar: column c of lv_occ_project over the clipped layers k0..k1
 LV_OCC_HD int fr_state_column(const float* L, size_t plane, size_t c, int k0, int k1, float l_free, float l_occ) {
-    bool occ = false, fre = false;
-    for (int k = k0; k <= k1; ++k) {
-        const float v = L[(size_t)k * plane + c];
-        occ |= v >= l_occ;
-        fre |= v <= l_free;
-    }
-    return fr_state_projected(occ ? 100 : fre ? 0 : -1);
+    return fr_state_projected(grid_project_column(L, plane, c, k0, k1, l_occ, l_free));
 }
 
 // A FREE cell with an UNKNOWN face neighbour inside the field (outside cells answer FR_OUTSIDE: the border is not unknown)
@@ -82,11 +76,7 @@ LV_OCC_HD uint64_t fr_rep_key(const int32_t centre[3], int i, int j, int k, uint
     return ((uint64_t)(dx * dx + dy * dy + dz * dz) << 32) | (uint64_t)cell;
 }
 
-LV_OCC_HD void fr_cell_ijk(const FrontierGrid& g, uint32_t cell, int& i, int& j, int& k) {
-    i = (int)(cell % (uint32_t)g.nx);
-    j = (int)((cell / (uint32_t)g.nx) % (uint32_t)g.ny);
-    k = (int)(cell / ((uint32_t)g.nx * (uint32_t)g.ny));
-}
+LV_OCC_HD void fr_cell_ijk(const FrontierGrid& g, uint32_t cell, int& i, int& j, int& k) { grid_ijk(g, cell, i, j, k); }
 
 constexpr uint64_t FR_RANK_NONE = ~0ull;   // (LV_PLAN_UNREACHED << 32) | (uint32_t)-1: what rank reports without a reached cell
 
@@ -99,7 +89,7 @@ LV_OCC_HD uint64_t fr_rank_window(const FrontierGrid& g, const uint32_t* pot, in
     uint64_t best = FR_RANK_NONE;
     for (int c = k0; c <= k1; ++c)
         for (int b = j0; b <= j1; ++b) {
-            const size_t row = ((size_t)c * (size_t)g.ny + (size_t)b) * (size_t)g.nx;
+            const size_t row = grid_at(g, 0, b, c);
             for (int a = i0; a <= i1; ++a) {
                 const uint32_t p = pot[row + (size_t)a];
                 if (p == PLAN_UNREACHED) continue;

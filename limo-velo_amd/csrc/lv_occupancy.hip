@@ -33,12 +33,6 @@ __device__ __forceinline__ void occ_or(uint32_t* word, uint32_t bits) {
     if ((*word & bits) != bits) atomicOr(word, bits);
 }
 
-// wave-wide sum of a small per-lane count, one 64-bit atomic per wavefront that has anything to add
-__device__ __forceinline__ void occ_count(unsigned long long* dst, uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(dst, (unsigned long long)v);
-}
-
 // pts: n returns (packed x, y, z) of one view; qs: its quantised sensor origin.  crossed / hit: the bitmaps.
 __global__ __launch_bounds__(256) void occ_march_kernel(const float* __restrict__ pts, uint32_t n, OccGrid g, OccPose pose, int32_t qsx,
                                                         int32_t qsy, int32_t qsz, uint32_t* crossed, uint32_t* hit,
@@ -85,8 +79,8 @@ __global__ __launch_bounds__(256) void occ_march_kernel(const float* __restrict_
         }
         if (cur != OCC_NO_WORD) occ_or(crossed + cur, bits);
     }
-    occ_count(stats + 0, kind != OCC_RAY_IGNORED ? 1u : 0u);
-    occ_count(stats + 1, kind == OCC_RAY_CUT ? 1u : 0u);
+    wave_add_to(stats + 0, kind != OCC_RAY_IGNORED ? 1u : 0u);
+    wave_add_to(stats + 1, kind == OCC_RAY_CUT ? 1u : 0u);
 }
 
 // the voxels of one word take their update; returns nothing, counts through nf / nh
@@ -122,8 +116,8 @@ __global__ __launch_bounds__(256) void occ_fold_kernel(float* __restrict__ L, ui
             if (h.x | h.y | h.z | h.w) hit[i] = zero;
         }
     }
-    occ_count(stats + 2, nf);
-    occ_count(stats + 3, nh);
+    wave_add_to(stats + 2, nf);
+    wave_add_to(stats + 3, nh);
 }
 
 // one lane per column (i, j); k0..k1 already clipped (k0 > k1: an empty band)
@@ -132,26 +126,15 @@ __global__ __launch_bounds__(256) void occ_project_kernel(const float* __restric
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t plane = (uint32_t)g.nx * (uint32_t)g.ny;
     if (c >= plane) return;
-    bool occ = false, fre = false;
-    for (int k = k0; k <= k1; ++k) {
-        const float v = L[(size_t)k * plane + c];
-        occ |= v >= l_occ;
-        fre |= v <= l_free;
-    }
-    out[c] = occ ? (int8_t)100 : (fre ? (int8_t)0 : (int8_t)-1);
+    out[c] = (int8_t)grid_project_column(L, plane, c, k0, k1, l_occ, l_free);
 }
 
 __global__ __launch_bounds__(256) void occ_query_kernel(const float* __restrict__ L, OccGrid g, const float* __restrict__ pts, uint32_t n,
                                                         float* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    int32_t q[3];
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) ok = occ_quant(pts[3 * (size_t)i + a], g.origin[a], g.resolution, q[a]) && ok;
-    float v = __uint_as_float(OCC_NAN_BITS);
-    if (ok && occ_in_grid(g, q[0] >> 8, q[1] >> 8, q[2] >> 8))
-        v = L[((size_t)(q[2] >> 8) * (size_t)g.ny + (size_t)(q[1] >> 8)) * (size_t)g.nx + (size_t)(q[0] >> 8)];
-    out[i] = v;
+    int ci, cj, ck;
+    out[i] = grid_cell_of(g, g.origin, g.resolution, false, pts + 3 * (size_t)i, ci, cj, ck) ? L[grid_at(g, ci, cj, ck)] : __uint_as_float(OCC_NAN_BITS);
 }
 
 }  // namespace
@@ -165,7 +148,7 @@ int OccStore::configure(hipStream_t stream, const lv_occupancy_params& p) {
     LV_HIP(hipStreamSynchronize(stream));
     release();
     const OccGrid g = occ_grid_of(p);
-    const size_t nv = (size_t)p.nx * (size_t)p.ny * (size_t)p.nz;
+    const size_t nv = grid_cells(g);
     const size_t nw = (((size_t)g.wx * (size_t)p.ny * (size_t)p.nz) + 3) & ~(size_t)3;
     int rc = d_L.need(nv);
     if (!rc) rc = d_bits.need(2 * nw);
@@ -239,7 +222,8 @@ int OccStore::query(hipStream_t stream, const void* points, size_t stride, size_
 }
 
 int OccStore::project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d) {
-    const int k0 = k_lo < 0 ? 0 : k_lo, k1 = k_hi >= grid.nz ? grid.nz - 1 : k_hi;
+    int k0, k1;
+    grid_clip_band(k_lo, k_hi, grid.nz, k0, k1);
     const size_t plane = (size_t)grid.nx * (size_t)grid.ny;
     hipLaunchKernelGGL(occ_project_kernel, dim3(blocks_of(plane)), dim3(256), 0, stream, d_L, grid, k0, k1, prm.l_occ, prm.l_free, d_proj);
     LV_HIP(hipGetLastError());

@@ -5,26 +5,20 @@
 // rules and world transform, the integer walk and the log-odds update.  The kernels of lv_occupancy.hip run exactly these
 // functions; tests/emu/occupancy_emu.cpp compiles them with g++ through tests/emu/hip/hip_runtime.h and tests/test_occupancy_host.py
 // holds them to tests/occupancy_ref.py.  After occ_quant every step is integer arithmetic, so the three agree on every voxel.
+// The quantisation itself, the cell arithmetic and the projection of a column are lv_grid.hpp's.
 #pragma once
-
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
 
 #include "../../include/limovelo_hip.h"
 #include "lv_buffers.hpp"
-
-#define LV_OCC_HD __host__ __device__ inline
+#include "lv_grid.hpp"
 
 namespace lv {
 
 constexpr int OCC_MAX_VIEWS = 32;
 constexpr int OCC_MAX_DIM = 1024;
 constexpr uint64_t OCC_MAX_VOXELS = (uint64_t)1 << 28;
-constexpr float OCC_SUB = 256.0f;            // sub-units per voxel (Q)
 constexpr float OCC_T_LIMIT = 8192.0f;       // a sensor origin this many voxels from the grid's origin gives no evidence
 constexpr float OCC_RANGE_LIMIT = 4096.0f;   // max_range / resolution
-constexpr float OCC_Q_LIMIT = 16777216.0f;   // 2^24: a return quantising to this or beyond on an axis is ignored
 
 // The grid and the constants of one lv_occ_integrate / lv_occ_query as the kernels take them
 struct OccGrid {
@@ -36,17 +30,6 @@ struct OccGrid {
     float max_range;
     float l_hit, l_miss, l_min, l_max;
 };
-
-// The quantised coordinate as f32, before the cast: floorf(((p - origin) / resolution) * 256) in exactly that order
-LV_OCC_HD float occ_quant_f(float p, float origin, float resolution) { return floorf(((p - origin) / resolution) * OCC_SUB); }
-
-// false: non-finite, or too far to be cast (only a world point farther than 65536 voxels from the origin is)
-LV_OCC_HD bool occ_quant(float p, float origin, float resolution, int32_t& q) {
-    const float f = occ_quant_f(p, origin, resolution);
-    if (!(fabsf(f) < OCC_Q_LIMIT)) return false;
-    q = (int32_t)f;
-    return true;
-}
 
 // The view's sensor origin in sub-units; false: the view gives no evidence (t non-finite or >= 8192 voxels from the origin)
 LV_OCC_HD bool occ_view_origin(const OccGrid& g, const float t[3], int32_t qs[3]) {
@@ -128,9 +111,7 @@ LV_OCC_HD int occ_walk_step(OccWalk& w) {
     return a;
 }
 
-LV_OCC_HD bool occ_in_grid(const OccGrid& g, int32_t i, int32_t j, int32_t k) {
-    return (uint32_t)i < (uint32_t)g.nx && (uint32_t)j < (uint32_t)g.ny && (uint32_t)k < (uint32_t)g.nz;
-}
+LV_OCC_HD bool occ_in_grid(const OccGrid& g, int32_t i, int32_t j, int32_t k) { return grid_inside(g, i, j, k); }
 
 // true: the walk stands outside the grid on an axis it does not move back along, so neither a later cell nor ve is in the grid
 LV_OCC_HD bool occ_walk_left(const OccGrid& g, const OccWalk& w) {
@@ -179,7 +160,7 @@ struct OccStore {
     OccGrid grid{};
     size_t n_vox = 0;
     size_t n_words = 0;            // words of ONE bitmap, padded to a multiple of 4 (the fold reads uint4)
-    DevBuf<float> d_L;             // log-odds, (k * ny + j) * nx + i; NaN = never observed
+    DevBuf<float> d_L;             // log-odds by grid_at; NaN = never observed
     DevBuf<uint32_t> d_bits;       // crossed bitmap, then hit bitmap: bit (i & 31) of word (k * ny + j) * wx + (i >> 5); all zero between views
     Counters4 stats;               // the 4 counters of the call in flight
     PointStage pts;                // every view's returns, or the query points

@@ -5,7 +5,7 @@
 //   plan_seed_kernel    one lane per goal: P = 0 in its cell; its tile, and each neighbouring tile that has the cell in its halo,
 //                       active for the first round.
 //   plan_round_kernel   one workgroup of 256 per tile (32 x 32 cells planar, 8 x 8 x 8 in 3-D), one launch per round over all tiles; a
-//                       tile that is not active leaves at once.  An active one loads its cells and a one-cell halo of P and cost
+//                       tile that is not active leaves at once.  An active one loads P and cost of its haloed box (HaloTile, lv_grid.hpp)
 //                       into LDS, works out per cell the mask of allowed moves (plan_move_allowed on the LDS tile), and relaxes
 //                       (plan_relax) inside LDS until nothing changes, at most as often as the tile has cells.  Lowered values go
 //                       back to global memory (only the owner writes a cell), and the neighbouring tiles that see a lowered border
@@ -29,6 +29,9 @@ namespace lv {
 
 namespace {
 
+constexpr int PLAN_PX = 32, PLAN_PY = 32, PLAN_PZ = 1;   // a planar tile
+constexpr int PLAN_VX = 8, PLAN_VY = 8, PLAN_VZ = 8;     // a 3-D tile
+
 __global__ __launch_bounds__(256) void plan_cost_kernel(const int32_t* __restrict__ s2, int min_clear_s2, const uint8_t* __restrict__ table,
                                                         int n_cost, uint32_t n, uint8_t* __restrict__ cost, uint32_t* __restrict__ pot) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -46,11 +49,11 @@ __global__ __launch_bounds__(256) void plan_seed_kernel(PlanGrid g, const float*
     const float p[3] = {pts[3 * (size_t)q], pts[3 * (size_t)q + 1], pts[3 * (size_t)q + 2]};
     int i, j, k;
     if (!plan_cell_of(g, p, i, j, k)) return;
-    const size_t at = ((size_t)k * (size_t)g.ny + (size_t)j) * (size_t)g.nx + (size_t)i;
+    const size_t at = grid_at(g, i, j, k);
     if (!cost[at]) return;
     pot[at] = 0u;   // (several goals in one cell store the same value)
     // the goal's tile, and every tile that holds the goal cell in its halo: a goal is never "lowered", so no round would wake them
-    const int tiles_x = (g.nx + TX - 1) / TX, tiles_y = (g.ny + TY - 1) / TY, tiles_z = (g.nz + TZ - 1) / TZ;
+    const GridDims td = HaloTile<TX, TY, TZ>::tile_dims(g);
     const int tx = i / TX, ty = j / TY, tz = k / TZ;
     const int li = i - tx * TX, lj = j - ty * TY, lk = k - tz * TZ;
     for (int mv = 0; mv < 27; ++mv) {
@@ -60,23 +63,18 @@ __global__ __launch_bounds__(256) void plan_seed_kernel(PlanGrid g, const float*
             (dz > 0 && lk != TZ - 1))
             continue;
         const int ux = tx + dx, uy = ty + dy, uz = tz + dz;
-        if ((uint32_t)ux < (uint32_t)tiles_x && (uint32_t)uy < (uint32_t)tiles_y && (uint32_t)uz < (uint32_t)tiles_z)
-            active[((size_t)uz * (size_t)tiles_y + (size_t)uy) * (size_t)tiles_x + (size_t)ux] = 1u;
+        if (grid_inside(td, ux, uy, uz)) active[grid_at(td, ux, uy, uz)] = 1u;
     }
     atomicAdd(&stats[0], 1ull);
 }
 
-// A workgroup's tile with its one-cell halo in LDS; coordinates are local to the tile, -1 .. T
-template <int TX, int TY, int TZ>
+// The accessor of lv_plan.hpp over a workgroup's HaloTile in LDS
+template <class T>
 struct PlanTile {
-    static constexpr int HZ = TZ > 1 ? 1 : 0;   // a planar field has no halo in z
-    static constexpr int LX = TX + 2, LY = TY + 2, LZ = TZ + 2 * HZ;
-    static constexpr int CELLS = TX * TY * TZ, LCELLS = LX * LY * LZ;
     const uint8_t* c;
     const uint32_t* p;
-    __device__ __forceinline__ static int at(int i, int j, int k) { return ((k + HZ) * LY + (j + 1)) * LX + (i + 1); }
-    __device__ __forceinline__ uint32_t cost(int i, int j, int k) const { return c[at(i, j, k)]; }
-    __device__ __forceinline__ uint32_t pot(int i, int j, int k) const { return p[at(i, j, k)]; }
+    __device__ __forceinline__ uint32_t cost(int i, int j, int k) const { return c[T::at(i, j, k)]; }
+    __device__ __forceinline__ uint32_t pot(int i, int j, int k) const { return p[T::at(i, j, k)]; }
 };
 
 enum : uint32_t { PLAN_F_AGAIN = 1u << 6, PLAN_F_LOWERED = 1u << 7 };   // above the six face bits
@@ -84,7 +82,7 @@ enum : uint32_t { PLAN_F_AGAIN = 1u << 6, PLAN_F_LOWERED = 1u << 7 };   // above
 template <int TX, int TY, int TZ>
 __global__ __launch_bounds__(256) void plan_round_kernel(PlanGrid g, const uint8_t* __restrict__ cost, uint32_t* pot, uint32_t* cur, uint32_t* nxt,
                                                          uint32_t* round_word) {
-    using T = PlanTile<TX, TY, TZ>;
+    using T = HaloTile<TX, TY, TZ>;
     constexpr int NPT = T::CELLS / 256;   // cells per lane
     static_assert(T::CELLS % 256 == 0, "a tile is a whole number of cells per lane");
     __shared__ uint32_t sp[T::LCELLS];
@@ -98,25 +96,27 @@ __global__ __launch_bounds__(256) void plan_round_kernel(PlanGrid g, const uint8
     }
     __syncthreads();
     if (!s_flag) return;   // (the whole workgroup)
-    const int tiles_x = (g.nx + TX - 1) / TX, tiles_y = (g.ny + TY - 1) / TY, tiles_z = (g.nz + TZ - 1) / TZ;
-    const int tx = (int)(t % (uint32_t)tiles_x), ty = (int)((t / (uint32_t)tiles_x) % (uint32_t)tiles_y), tz = (int)(t / (uint32_t)(tiles_x * tiles_y));
+    const GridDims td = T::tile_dims(g);
+    int tx, ty, tz;
+    T::origin_of(g, t, tx, ty, tz);
     const int x0 = tx * TX, y0 = ty * TY, z0 = tz * TZ;
     for (int l = (int)tid; l < T::LCELLS; l += 256) {
-        const int gi = x0 + l % T::LX - 1, gj = y0 + (l / T::LX) % T::LY - 1, gk = z0 + l / (T::LX * T::LY) - T::HZ;
-        const bool in = (uint32_t)gi < (uint32_t)g.nx && (uint32_t)gj < (uint32_t)g.ny && (uint32_t)gk < (uint32_t)g.nz;
-        const size_t at = ((size_t)gk * (size_t)g.ny + (size_t)gj) * (size_t)g.nx + (size_t)gi;
+        int di, dj, dk;
+        T::halo_of(l, di, dj, dk);
+        const bool in = grid_inside(g, x0 + di, y0 + dj, z0 + dk);
+        const size_t at = grid_at(g, x0 + di, y0 + dj, z0 + dk);
         sc[l] = in ? cost[at] : (uint8_t)0;
         sp[l] = in ? pot[at] : PLAN_UNREACHED;
     }
     __syncthreads();
-    const T tile{sc, sp};
+    const PlanTile<T> tile{sc, sp};
     const int mv0 = TZ > 1 ? 0 : 9, mv1 = TZ > 1 ? 27 : 18;
     uint32_t mask[NPT], first[NPT];
     int at[NPT];
 #pragma unroll
     for (int q = 0; q < NPT; ++q) {
-        const int c = (int)tid + q * 256;
-        const int i = c % TX, j = (c / TX) % TY, k = c / (TX * TY);
+        int i, j, k;
+        T::local_of((int)tid + q * 256, i, j, k);
         at[q] = T::at(i, j, k);
         first[q] = sp[at[q]];
         uint32_t m = 0;
@@ -155,9 +155,9 @@ __global__ __launch_bounds__(256) void plan_round_kernel(PlanGrid g, const uint8
     for (int q = 0; q < NPT; ++q) {
         const uint32_t now = sp[at[q]];
         if (now < first[q]) {
-            const int c = (int)tid + q * 256;
-            const int i = c % TX, j = (c / TX) % TY, k = c / (TX * TY);
-            pot[((size_t)(z0 + k) * (size_t)g.ny + (size_t)(y0 + j)) * (size_t)g.nx + (size_t)(x0 + i)] = now;
+            int i, j, k;
+            T::local_of((int)tid + q * 256, i, j, k);
+            pot[grid_at(g, x0 + i, y0 + j, z0 + k)] = now;
             faces |= PLAN_F_LOWERED | (i == 0 ? 1u : 0u) | (i == TX - 1 ? 2u : 0u) | (j == 0 ? 4u : 0u) | (j == TY - 1 ? 8u : 0u);
             if (TZ > 1) faces |= (k == 0 ? 16u : 0u) | (k == TZ - 1 ? 32u : 0u);
         }
@@ -175,23 +175,9 @@ __global__ __launch_bounds__(256) void plan_round_kernel(PlanGrid g, const uint8
         } else {
             const uint32_t need = (dx < 0 ? 1u : 0u) | (dx > 0 ? 2u : 0u) | (dy < 0 ? 4u : 0u) | (dy > 0 ? 8u : 0u) | (dz < 0 ? 16u : 0u) | (dz > 0 ? 32u : 0u);
             const int ux = tx + dx, uy = ty + dy, uz = tz + dz;
-            if ((f & need) == need && (uint32_t)ux < (uint32_t)tiles_x && (uint32_t)uy < (uint32_t)tiles_y && (uint32_t)uz < (uint32_t)tiles_z)
-                nxt[((size_t)uz * (size_t)tiles_y + (size_t)uy) * (size_t)tiles_x + (size_t)ux] = 1u;
+            if ((f & need) == need && grid_inside(td, ux, uy, uz)) nxt[grid_at(td, ux, uy, uz)] = 1u;
         }
     }
-}
-
-__device__ __forceinline__ unsigned long long plan_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long plan_wave_max(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
 }
 
 // stats[1..3]: traversable cells, reached cells, the largest finite P (grid-stride: one atomic per counter and wavefront)
@@ -206,14 +192,10 @@ __global__ __launch_bounds__(256) void plan_stats_kernel(const uint8_t* __restri
             top = p > top ? p : top;
         }
     }
-    trav = plan_wave_sum(trav);
-    reached = plan_wave_sum(reached);
-    top = plan_wave_max(top);
-    if ((threadIdx.x & 63u) == 0) {
-        if (trav) atomicAdd(&stats[1], trav);
-        if (reached) atomicAdd(&stats[2], reached);
-        if (top) atomicMax(&stats[3], top);
-    }
+    wave_add_to(&stats[1], trav);
+    wave_add_to(&stats[2], reached);
+    top = wave_max(top);
+    if ((threadIdx.x & 63u) == 0 && top) atomicMax(&stats[3], top);
 }
 
 // cnt[n] = 0 makes the exclusive scan's entry n the total
@@ -267,8 +249,7 @@ int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_pa
     for (int a = 0; a < 3; ++a) g.origin[a] = dist.origin[a];
     g.resolution = dist.grid.resolution;
     const size_t nc = dist.n_vox;
-    const size_t nt = g.planar ? (size_t)((g.nx + 31) / 32) * (size_t)((g.ny + 31) / 32)
-                               : (size_t)((g.nx + 7) / 8) * (size_t)((g.ny + 7) / 8) * (size_t)((g.nz + 7) / 8);
+    const size_t nt = g.planar ? HaloTile<PLAN_PX, PLAN_PY, PLAN_PZ>::tiles(g) : HaloTile<PLAN_VX, PLAN_VY, PLAN_VZ>::tiles(g);
     int rc = stage(stream, goals, stride, n_goals);
     if (rc) return rc;
     built = false;   // (before a buffer goes: the old plan's are overwritten from here on; the new one stands when the rounds are through)
@@ -285,12 +266,9 @@ int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_pa
     if (rc) return rc;
     hipLaunchKernelGGL(plan_cost_kernel, dim3(blocks_of(nc)), dim3(256), 0, stream, dist.d_s2, p.min_clear_s2, d_table, (int)n_cost, (uint32_t)nc,
                        d_cost, d_pot);
-    if (g.planar)
-        hipLaunchKernelGGL((plan_seed_kernel<32, 32, 1>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, pts.d, (uint32_t)n_goals, d_cost, d_pot,
-                           d_active, stats.d);
-    else
-        hipLaunchKernelGGL((plan_seed_kernel<8, 8, 8>), dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, pts.d, (uint32_t)n_goals, d_cost, d_pot,
-                           d_active, stats.d);
+    const auto seed_kernel = g.planar ? plan_seed_kernel<PLAN_PX, PLAN_PY, PLAN_PZ> : plan_seed_kernel<PLAN_VX, PLAN_VY, PLAN_VZ>;
+    const auto round_kernel = g.planar ? plan_round_kernel<PLAN_PX, PLAN_PY, PLAN_PZ> : plan_round_kernel<PLAN_VX, PLAN_VY, PLAN_VZ>;
+    hipLaunchKernelGGL(seed_kernel, dim3(blocks_of(n_goals)), dim3(256), 0, stream, g, pts.d, (uint32_t)n_goals, d_cost, d_pot, d_active, stats.d);
     LV_HIP(hipGetLastError());
     // the rounds: a batch of launches, then one look at the batch's words.  Once a round lowers nothing no later one does.
     size_t done = 0;   // rounds launched so far
@@ -301,8 +279,7 @@ int PlanStore::build(hipStream_t stream, const DistStore& dist, const lv_plan_pa
         for (int r = 0; r < PLAN_ROUNDS_PER_READ; ++r) {
             uint32_t* cur = d_active + ((done + (size_t)r) & 1) * nt;
             uint32_t* nxt = d_active + ((done + (size_t)r + 1) & 1) * nt;
-            if (g.planar) hipLaunchKernelGGL((plan_round_kernel<32, 32, 1>), dim3((uint32_t)nt), dim3(256), 0, stream, g, d_cost, d_pot, cur, nxt, d_round + r);
-            else hipLaunchKernelGGL((plan_round_kernel<8, 8, 8>), dim3((uint32_t)nt), dim3(256), 0, stream, g, d_cost, d_pot, cur, nxt, d_round + r);
+            hipLaunchKernelGGL(round_kernel, dim3((uint32_t)nt), dim3(256), 0, stream, g, d_cost, d_pot, cur, nxt, d_round + r);
         }
         LV_HIP(hipGetLastError());
         LV_HIP(hipMemcpyAsync(h_round, d_round, PLAN_ROUNDS_PER_READ * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));

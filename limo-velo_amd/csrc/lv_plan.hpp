@@ -112,16 +112,9 @@ LV_OCC_HD bool plan_next(const F& f, int max_m, bool planar, int& i, int& j, int
     return false;
 }
 
-// The cell of a world point, quantised as lv_occ_query does it; false: non-finite or outside the field (planar: z is not used)
+// The cell of a world point by the grid's one rule (planar: z is not used)
 LV_OCC_HD bool plan_cell_of(const PlanGrid& g, const float p[3], int& i, int& j, int& k) {
-    int32_t q[3] = {0, 0, 0};
-    bool ok = true;
-    for (int a = 0; a < (g.planar ? 2 : 3); ++a) ok = occ_quant(p[a], g.origin[a], g.resolution, q[a]) && ok;
-    if (!ok) return false;
-    i = q[0] >> 8;
-    j = q[1] >> 8;
-    k = q[2] >> 8;
-    return (uint32_t)i < (uint32_t)g.nx && (uint32_t)j < (uint32_t)g.ny && (uint32_t)k < (uint32_t)g.nz;
+    return grid_cell_of(g, g.origin, g.resolution, g.planar != 0, p, i, j, k);
 }
 
 // The finished (or growing) field in linear memory
@@ -129,8 +122,8 @@ struct PlanView {
     const uint8_t* c;
     const uint32_t* p;
     int nx, ny, nz;
-    LV_OCC_HD size_t at(int i, int j, int k) const { return ((size_t)k * (size_t)ny + (size_t)j) * (size_t)nx + (size_t)i; }
-    LV_OCC_HD bool inside(int i, int j, int k) const { return (uint32_t)i < (uint32_t)nx && (uint32_t)j < (uint32_t)ny && (uint32_t)k < (uint32_t)nz; }
+    LV_OCC_HD size_t at(int i, int j, int k) const { return grid_at(*this, i, j, k); }
+    LV_OCC_HD bool inside(int i, int j, int k) const { return grid_inside(*this, i, j, k); }
     LV_OCC_HD uint32_t cost(int i, int j, int k) const { return inside(i, j, k) ? c[at(i, j, k)] : 0u; }
     LV_OCC_HD uint32_t pot(int i, int j, int k) const { return p[at(i, j, k)]; }
 };
@@ -153,7 +146,7 @@ LV_OCC_HD uint64_t plan_walk(const PlanGrid& g, const PlanView& f, const float p
     }
     *status = PLAN_PATH_OK;
     *cost = p0;
-    const uint64_t cap = (uint64_t)g.nx * (uint64_t)g.ny * (uint64_t)g.nz;
+    const uint64_t cap = grid_cells(g);
     uint64_t n = 0;
     for (;;) {
         if (cells) cells[n] = (int32_t)f.at(i, j, k);
@@ -194,7 +187,7 @@ struct PlanStore {
     lv_plan_params prm{};
     PlanGrid grid{};
     size_t n_cells = 0, n_tiles = 0;
-    DevBuf<uint8_t> d_cost;          // the cost byte per cell, the field's linear index
+    DevBuf<uint8_t> d_cost;          // the cost byte per cell, by grid_at
     DevBuf<uint32_t> d_pot;          // P
     DevBuf<uint32_t> d_active;       // 2 * n_tiles flags: the tiles of this round, of the next
     DevBuf<uint8_t> d_table;         // the cost table (PLAN_MAX_COST bytes)
