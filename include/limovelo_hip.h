@@ -713,6 +713,61 @@ int  lv_occ_frontier_info(lv_ctx* ctx, lv_frontier_info* out);
 /* Frees the result. */
 int  lv_occ_frontier_clear(lv_ctx* ctx);
 
+/* ---- Ray casting -------------------------------------------------------------------------------------
+ * What a sensor would see from a given place, and how much unknown space a pose would uncover: line of sight, simulated range
+ * scans, and the information gain of a candidate view that explore_lite, NBVP and FUEL weigh a frontier by (the reference has no
+ * counterpart).  The walk of the "Occupancy grid" section, unchanged, but READING the log-odds instead of writing them.  The rule
+ * is integer arithmetic once the ends are quantised and the cell states decided, so it is exactly defined: a pure function of
+ * the grid and the arguments, the same bits whatever the schedule.  No float leaves the device.
+ *   cell states  those of the 3-D cells of "Frontiers": FREE iff L <= l_free, OCCUPIED iff L >= l_occ, UNKNOWN iff L is NaN; a
+ *            voxel with l_free < L < l_occ is OTHER.
+ *   ends     lv_occ_raycast: `from` is quantised as a view's sensor origin is (per axis c = (p - origin) / resolution must have
+ *            |c| < 8192, then qs = (int32) floorf(c * 256.0f)) and `to` as a return's world point is (qe = (int32)
+ *            floorf(((p - origin) / resolution) * 256.0f), |qe| < 2^24), f32 operations in exactly that order.  A ray one of whose
+ *            ends fails (non-finite included) is IGNORED.  lv_occ_view_gain: qs, qe and which returns are ignored or cut are
+ *            exactly those of lv_occ_integrate for the same view ("quantisation", "returns"); R must be finite (LV_EINVAL).
+ *            These are the bounds under which the walk's products fit in int64: for a view every product stays below 2^41, as
+ *            argued there; for lv_occ_raycast |qs| < 2^21 and |qe| < 2^24 give ad_a < 2^25 and n_a < 2^26, every product below 2^51.
+ *   cells of a ray  c_0 = vs, c_1, ..., c_S = ve: the cells the walk of "Occupancy grid" stands in, S = r_x + r_y + r_z.  Step
+ *            s >= 1 enters c_s across axis a_s (0, 1, 2) at the fraction num_s / den_s of the segment qs -> qe, where num_s is n_a
+ *            as it stood BEFORE the step added 256 to it and den_s = ad_a; 0 <= num_s <= den_s (0 only when qs lies on a cell
+ *            face and the ray leaves through it at once).  Cells outside the grid belong to the sequence but have no state:
+ *            they neither stop a ray nor count.
+ *   stop     a cell inside the grid stops a ray iff it is OCCUPIED, or UNKNOWN while stop_unknown != 0.  c_0 is examined like
+ *            every other cell.  s* is the least s whose c_s stops the ray.
+ *   result, STOPPED  cell = the linear index of c_s*; steps = s*; axis = a_s*; num / den = num_s* / den_s* (s* = 0: axis -1, num 0,
+ *            den 1); n_free and n_unknown count the in-grid FREE and UNKNOWN cells among c_0 .. c_(s* - 1).  The point where the
+ *            ray enters the cell is qs + (qe - qs) * num / den sub-units: metres are the caller's business.
+ *   result, CLEAR  (no cell stops the ray) cell = the linear index of ve, -1 if ve is outside the grid; steps = S; axis = -1;
+ *            num = den = 1; the counts run over c_0 .. c_S.
+ *   result, IGNORED  status 0, cell -1, every other field 0.
+ *   view gain  per view v (an lv_view whose returns are the end points of a scan pattern in the sensor frame), with rays
+ *            stopping at OCCUPIED cells only, cut and hit returns alike: gain[4v + 0] = rays used (returns not ignored),
+ *            gain[4v + 1] = rays stopped, gain[4v + 2] = the DISTINCT in-grid UNKNOWN cells that lie before the stop on at least
+ *            one used ray of v (c_0 .. c_(s* - 1); c_0 .. c_S, ve included, for a ray that does not stop), gain[4v + 3] the same for
+ *            FREE cells.  Views are independent of each other and of their order.  A view that gives no evidence ("quantisation":
+ *            its origin fails, or n = 0) yields four zeros.
+ * Both calls read the LIVE grid, not a snapshot, and change no bit of the grid, the distance field, the plan or the frontier
+ * result, nor any stale flag.  Parameters and NULL or short arguments are judged before the context (LV_EINVAL, nothing
+ * written; "null context" comes last); both give LV_ESTATE before lv_occ_configure.  Nothing is allocated before the first call;
+ * lv_occ_configure and lv_destroy free everything.  The calls run on the context's stream and return when their host outputs
+ * are written. */
+#define LV_RAY_IGNORED 0
+#define LV_RAY_CLEAR   1
+#define LV_RAY_STOPPED 2
+typedef struct lv_ray_params { int stop_unknown; } lv_ray_params;
+typedef struct lv_ray_result {                /* 32 bytes */
+    int32_t status, cell, steps, axis, n_free, n_unknown, num, den;
+} lv_ray_result;
+/* stop_unknown 0. */
+void lv_default_ray_params(lv_ray_params* p);
+/* from, to: n world points each, the first three floats of every stride bytes (strides >= 12); out: n results.  n = 0 succeeds
+ * and writes nothing; n < 2^31 - 1. */
+int  lv_occ_raycast(lv_ctx* ctx, const lv_ray_params* p, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
+                    lv_ray_result* out);
+/* n_views 1..32; gain: n_views x 4 counters as above. */
+int  lv_occ_view_gain(lv_ctx* ctx, const lv_view* views, size_t n_views, uint64_t* gain);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "lv_default_plan_params", "lv_occ_plan_build", "lv_occ_plan_fetch", "lv_occ_plan_paths", "lv_occ_plan_info", "lv_occ_plan_clear",
     "lv_default_frontier_params", "lv_occ_frontier_build", "lv_occ_frontier_fetch", "lv_occ_frontier_clusters", "lv_occ_frontier_rank",
     "lv_occ_frontier_info", "lv_occ_frontier_clear",
+    "lv_default_ray_params", "lv_occ_raycast", "lv_occ_view_gain",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -244,6 +245,27 @@ FRONTIER_ARGTYPES = {
     "lv_occ_frontier_rank": [C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_size_t],
     "lv_occ_frontier_info": [C.c_void_p, C.POINTER(FrontierInfo)],
     "lv_occ_frontier_clear": [C.c_void_p],
+}
+
+LV_RAY_IGNORED, LV_RAY_CLEAR, LV_RAY_STOPPED = 0, 1, 2
+
+
+class RayParams(C.Structure):  # lv_ray_params
+    _fields_ = [("stop_unknown", C.c_int)]
+
+
+class RayResult(C.Structure):  # lv_ray_result (32 bytes)
+    _fields_ = [("status", C.c_int32), ("cell", C.c_int32), ("steps", C.c_int32), ("axis", C.c_int32), ("n_free", C.c_int32),
+                ("n_unknown", C.c_int32), ("num", C.c_int32), ("den", C.c_int32)]
+
+
+# the same record as a numpy dtype (Context.occ_raycast)
+RAY_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in RayResult._fields_])
+
+# ctypes signatures of the ray casting (include/limovelo_hip.h "Ray casting"; tests/test_occ_ray_abi.py)
+RAY_ARGTYPES = {
+    "lv_occ_raycast": [C.c_void_p, C.POINTER(RayParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(RayResult)],
+    "lv_occ_view_gain": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(C.c_uint64)],
 }
 
 
@@ -470,8 +492,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_plan_params.argtypes = [C.POINTER(PlanParams)]
         lib.lv_default_frontier_params.restype = None
         lib.lv_default_frontier_params.argtypes = [C.POINTER(FrontierParams)]
+        lib.lv_default_ray_params.restype = None
+        lib.lv_default_ray_params.argtypes = [C.POINTER(RayParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES}.items():
+                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
+                               **RAY_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -571,6 +596,14 @@ def default_plan_params(**kw) -> PlanParams:
 def default_frontier_params(**kw) -> FrontierParams:
     p = FrontierParams()
     load_library().lv_default_frontier_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_ray_params(**kw) -> RayParams:
+    p = RayParams()
+    load_library().lv_default_ray_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1026,6 +1059,28 @@ class Context:
 
     def occ_frontier_clear(self):
         self._check(self.lib.lv_occ_frontier_clear(self.h))
+
+    # --- ray casting (include/limovelo_hip.h "Ray casting")
+    def occ_raycast(self, frm, to, params: RayParams | None = None) -> np.ndarray:
+        """lv_occ_raycast of the rays frm[i] -> to[i] ([n, 3] world points each; default: stop at occupied cells only); returns a
+        structured array [n] of RAY_RESULT_DTYPE."""
+        p = params if params is not None else default_ray_params()
+        a, sa, n = _points(np.asarray(frm, np.float32).reshape(-1, 3))
+        b, sb, nb = _points(np.asarray(to, np.float32).reshape(-1, 3))
+        if n != nb:
+            raise ValueError("occ_raycast: as many `to` points as `from` points")
+        out = np.zeros(n, RAY_RESULT_DTYPE)
+        self._check(self.lib.lv_occ_raycast(self.h, C.byref(p), a.ctypes.data_as(C.c_void_p), C.c_size_t(sa), b.ctypes.data_as(C.c_void_p),
+                                            C.c_size_t(sb), C.c_size_t(n), out.ctypes.data_as(C.POINTER(RayResult))))
+        return out
+
+    def occ_view_gain(self, views) -> np.ndarray:
+        """lv_occ_view_gain over views = [(R [3, 3], t [3], pattern end points [n, 3] sensor frame)] (1..32 of them); returns
+        [n_views, 4] uint64: rays used, rays stopped, distinct unknown cells seen, distinct free cells seen."""
+        arr, keep = view_array(views)
+        gain = np.zeros((len(views), 4), np.uint64)
+        self._check(self.lib.lv_occ_view_gain(self.h, arr, C.c_size_t(len(views)), gain.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return gain
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

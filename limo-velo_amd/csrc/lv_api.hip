@@ -16,6 +16,7 @@
 #include "lv_distance.hpp"
 #include "lv_plan.hpp"
 #include "lv_frontier.hpp"
+#include "lv_ray.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -55,6 +56,7 @@ struct lv_ctx {
     DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
     PlanStore plan;     // lv_occ_plan_*: the cost-to-go over that field (lv_plan.hip); nothing allocated before the first build
     FrontierStore frontier;   // lv_occ_frontier_*: the frontier clusters of that grid (lv_frontier.hip); nothing allocated before the first build
+    RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -641,6 +643,7 @@ void lv_destroy(lv_ctx* c) {
     c->surface.release();
     c->cluster.release();
     c->place.release();
+    c->ray.release();
     c->frontier.release();
     c->plan.release();
     c->dist.release();
@@ -2430,8 +2433,9 @@ void lv_default_occupancy_params(lv_occupancy_params* p) {
 #define LV_PLAN_BUILT(c) LV_REQUIRE((c)->plan.built, LV_ESTATE, "no plan: call lv_occ_plan_build first")
 #define LV_FRONTIER_BUILT(c) LV_REQUIRE((c)->frontier.built, LV_ESTATE, "no frontier: call lv_occ_frontier_build first")
 
-// What was built from the grid (the distance field, the frontier) no longer shows it
+// What was built from the grid (the distance field, the frontier, the rays' packed states) no longer shows it
 static void occ_grid_changed(lv_ctx* c) {
+    c->ray.packed = false;
     if (c->dist.built) c->dist.stale = 1;
     if (c->frontier.built) c->frontier.stale = 1;
 }
@@ -2468,6 +2472,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     c->dist.release();   // (the field belongs to the grid it was built from)
     c->plan.release();   // (and the plan to the field)
     c->frontier.release();   // (the frontier to the grid too)
+    c->ray.release();        // (and the packed states)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2692,6 +2697,40 @@ int lv_occ_frontier_clear(lv_ctx* c) {
     LV_HIP(hipStreamSynchronize(c->stream));
     c->frontier.release();
     return LV_OK;
+}
+
+// ---- Ray casting (lv_ray.hip)
+void lv_default_ray_params(lv_ray_params* p) {
+    if (!p) return;
+    *p = lv_ray_params{};
+}
+
+// (the arguments are judged before the context, as lv_occ_frontier_build's are)
+int lv_occ_raycast(lv_ctx* c, const lv_ray_params* p, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
+                   lv_ray_result* out) {
+    if (!p) { set_error("lv_occ_raycast: null params"); return LV_EINVAL; }
+    if (n >= RAY_MAX_N) { set_error("lv_occ_raycast: too many rays"); return LV_EINVAL; }
+    if (n && (!from || !to || !out || from_stride < 12 || to_stride < 12)) {
+        set_error("lv_occ_raycast: bad point arrays (strides %zu, %zu) or null output", from_stride, to_stride);
+        return LV_EINVAL;
+    }
+    LV_OCC_CTX(c);
+    return c->ray.raycast(c->stream, c->occ, *p, from, from_stride, to, to_stride, n, out);
+}
+
+int lv_occ_view_gain(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t* gain) {
+    if (!views || !gain) { set_error("lv_occ_view_gain: null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("lv_occ_view_gain: n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
+    size_t total = 0;
+    for (size_t v = 0; v < n_views; ++v) {
+        const lv_view& w = views[v];
+        for (int i = 0; i < 9; ++i) if (!std::isfinite(w.R[i])) { set_error("lv_occ_view_gain: view %zu: non-finite R", v); return LV_EINVAL; }
+        if (w.n && (!w.points || w.stride < 12)) { set_error("lv_occ_view_gain: view %zu: bad point array (stride %zu)", v, w.stride); return LV_EINVAL; }
+        total += w.n;
+        if (w.n > 0xFFFFFFF0ull / 4 || total > 0xFFFFFFF0ull / 4) { set_error("lv_occ_view_gain: too many returns"); return LV_EINVAL; }
+    }
+    LV_OCC_CTX(c);
+    return c->ray.view_gain(c->stream, c->occ, views, n_views, gain);
 }
 
 }  // extern "C"

@@ -7,7 +7,9 @@ costmap_from_distance() costmap_2d's inflation costs from it.  plan() / routes()
 field and walk routes down it (lv_occ_plan_*, "Planner": navfn / global_planner), with inflation_cost_table() and min_clear_s2()
 turning costmap_2d's parameters into the planner's integer ones.  frontiers() labels the boundary between free and unknown space into
 clusters (lv_occ_frontier_*, "Frontiers": explore_lite / frontier_exploration) and explore() ranks them by the planner's cost from
-the robot and hands back targets with their routes."""
+the robot and hands back targets with their routes.  raycast() / line_of_sight() / simulate_scan() ask what a sensor would see
+from a place and view_gain() how much unknown space a pose would uncover (lv_occ_raycast, lv_occ_view_gain, "Ray casting"); with a
+gain_pattern explore() reports that gain at every target."""
 from __future__ import annotations
 
 import math
@@ -232,13 +234,79 @@ def _with_world(p, info, cl, extra=()):
     return out
 
 
-def explore(ctx, robot_xyz, robot_radius: float, z_band=None, reach=None, min_size=1, unknown="obstacle"):
+def _sub_units(p, pts) -> np.ndarray:
+    """[n, 3] int64: world points quantised as the device does, floorf(((p - origin) / resolution) * 256) in f32 in that order (a
+    sensor origin and a return's world point differ in their limits only).  Meaningful for rays that were not ignored."""
+    F = np.float32
+    with np.errstate(all="ignore"):
+        q = np.floor(((np.asarray(pts, F).reshape(-1, 3) - np.array([v for v in p.origin], F)) / F(p.resolution)) * F(256))
+    return np.where(np.abs(q) < 2.0 ** 24, q, 0).astype(np.int64)
+
+
+def raycast(ctx, frm, to, stop_unknown=False):
+    """lv_occ_raycast of the rays frm[i] -> to[i] ([n, 3] world points): (results, range_m).  results: the structured array of
+    capi.RAY_RESULT_DTYPE (status capi.LV_RAY_IGNORED / CLEAR / STOPPED, the cell that stopped the ray, steps, the axis and the
+    fraction num / den at which it was entered, the free and unknown cells passed before).  range_m [n] f64: the distance in
+    metres from frm to where a STOPPED ray enters its cell, resolution / 256 * |qe - qs| * num / den over the quantised ends;
+    inf for CLEAR rays, NaN for IGNORED ones.  stop_unknown: unknown cells stop a ray as occupied ones do."""
+    frm = np.asarray(frm, np.float32).reshape(-1, 3)
+    to = np.asarray(to, np.float32).reshape(-1, 3)
+    res = ctx.occ_raycast(frm, to, capi.default_ray_params(stop_unknown=int(bool(stop_unknown))))
+    p = ctx.occ_params()
+    d = (_sub_units(p, to) - _sub_units(p, frm)).astype(np.float64)
+    length = np.sqrt((d ** 2).sum(axis=1))
+    rng = np.full(len(res), np.nan)
+    rng[res["status"] == capi.LV_RAY_CLEAR] = np.inf
+    h = res["status"] == capi.LV_RAY_STOPPED
+    rng[h] = np.float64(p.resolution) / 256.0 * length[h] * res["num"][h] / res["den"][h]
+    return res, rng
+
+
+def line_of_sight(ctx, a, b) -> np.ndarray:
+    """[n] bool: no occupied voxel lies on the segment a[i] -> b[i] (false for rays lv_occ_raycast ignores)."""
+    return ctx.occ_raycast(a, b)["status"] == capi.LV_RAY_CLEAR
+
+
+def scan_pattern(n_az: int, n_el: int, el_lo: float, el_hi: float, max_range: float) -> np.ndarray:
+    """[n_el * n_az, 3] f32: the end points, in the sensor frame, of a spinning LiDAR's beams of length max_range: n_az azimuths
+    2 pi a / n_az, n_el elevations from el_lo to el_hi (radians, inclusive), elevation-major."""
+    az = 2.0 * np.pi * np.arange(int(n_az)) / int(n_az)
+    el = np.linspace(float(el_lo), float(el_hi), int(n_el))
+    e, a = np.meshgrid(el, az, indexing="ij")
+    return (float(max_range) * np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], axis=-1)).reshape(-1, 3).astype(np.float32)
+
+
+def simulate_scan(ctx, R, t, pattern) -> np.ndarray:
+    """[n] f64 ranges in metres (raycast's range_m) of the beams of `pattern` (sensor frame) from the pose (R, t): inf where a
+    beam meets no occupied voxel before its end."""
+    R = np.asarray(R, np.float32).reshape(3, 3)
+    t = np.asarray(t, np.float32).reshape(3)
+    to = (np.asarray(pattern, np.float32).reshape(-1, 3) @ R.T + t).astype(np.float32)
+    return raycast(ctx, np.broadcast_to(t, to.shape), to)[1]
+
+
+def view_gain(ctx, positions, pattern, yaws=None) -> np.ndarray:
+    """lv_occ_view_gain of `pattern` (scan_pattern) at each of positions [n, 3], turned about z by yaws [n] (default 0), 32 views
+    per call: [n, 4] uint64 — rays used, rays stopped, distinct unknown voxels seen, distinct free voxels seen."""
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    yaws = np.zeros(len(pos)) if yaws is None else np.asarray(yaws, np.float64).reshape(-1)
+    views = [(np.array([[math.cos(y), -math.sin(y), 0.0], [math.sin(y), math.cos(y), 0.0], [0.0, 0.0, 1.0]], np.float32), t, pattern)
+             for t, y in zip(pos, yaws)]
+    out = np.zeros((len(views), 4), np.uint64)
+    for c0 in range(0, len(views), MAX_VIEWS):
+        out[c0:c0 + MAX_VIEWS] = ctx.occ_view_gain(views[c0:c0 + MAX_VIEWS])
+    return out
+
+
+def explore(ctx, robot_xyz, robot_radius: float, z_band=None, reach=None, min_size=1, unknown="obstacle", gain_pattern=None):
     """Where to drive next: builds the distance field (3-D, or planar over z_band; unknown space counts as an obstacle unless
     unknown="free"), a plan whose only goal is the robot (the planner's edges are symmetric: it holds the cost from the robot to
     every cell), the frontier clusters, and ranks them (reach: cells round a member in which a reachable cell is looked for;
     default ceil(robot_radius / resolution), at most 8).  Returns (clusters, routes): the clusters of frontiers() ordered by
     best_p, the cheapest first and the unreachable ones last, with their label, best_p, best_cell and target_xyz (the centre of
-    best_cell; NaN without one); and per cluster the polyline from the robot's cell to the target (empty without a route)."""
+    best_cell; NaN without one); and per cluster the polyline from the robot's cell to the target (empty without a route).
+    gain_pattern (scan_pattern): the clusters also get gain_unknown and gain_free, view_gain() of that pattern at target_xyz (0
+    without a target); the order stays by best_p, weighing cost against gain is the caller's."""
     if unknown not in ("free", "obstacle"):
         raise ValueError('unknown: "free" or "obstacle"')
     p = ctx.occ_params()
@@ -252,12 +320,16 @@ def explore(ctx, robot_xyz, robot_radius: float, z_band=None, reach=None, min_si
     best_p, best_cell = ctx.occ_frontier_rank(int(reach))
     order = np.lexsort((np.arange(len(best_p)), best_p))
     cl = _with_world(p, info, ctx.occ_frontier_clusters()[order],
-                     extra=[("label", np.int32), ("best_p", np.uint32), ("best_cell", np.int32), ("target_xyz", np.float32, 3)])
+                     extra=[("label", np.int32), ("best_p", np.uint32), ("best_cell", np.int32), ("target_xyz", np.float32, 3)] +
+                     ([("gain_unknown", np.uint64), ("gain_free", np.uint64)] if gain_pattern is not None else []))
     cl["label"], cl["best_p"], cl["best_cell"] = order, best_p[order], best_cell[order]
     ok = cl["best_cell"] >= 0
     cl["target_xyz"] = np.nan
     cl["target_xyz"][ok] = _cell_centres(p, info, cl["best_cell"][ok])
     lines = [np.zeros((0, 2 if info.planar else 3), np.float32)] * len(cl)
+    if gain_pattern is not None and ok.any():
+        gain = view_gain(ctx, cl["target_xyz"][ok], gain_pattern)
+        cl["gain_unknown"][ok], cl["gain_free"][ok] = gain[:, 2], gain[:, 3]
     if ok.any():
         for c, (line, _, _) in zip(np.flatnonzero(ok), routes(ctx, cl["target_xyz"][ok])):
             lines[c] = line[::-1]   # (walked from the target down to the robot: reversed)
