@@ -2,8 +2,8 @@
 // where the points lie (include/limovelo_hip.h "Map clustering"; the union-find and the rules: lv_cluster.hpp).
 //
 //   cluster_init_kernel      one lane per id: parent = id for an included living id, CL_NONE otherwise; sizes 0, labels -1.
-//   cluster_link_kernel      one wavefront per included id i walks the source query_radius_kernel would choose for the query
-//                            (p_i, radius) with its primitives (lv_query_dev.hpp): the level-0 run while the radius is inside the
+//   cluster_link_kernel      one wavefront per included id i walks the fixed-radius source of the query (p_i, radius)
+//                            (radius_source / stream_radius, lv_query_dev.hpp): the level-0 run while the radius is inside the
 //                            level-0 bound, else the level-2 lists covering [p - r, p + r], else every id.  A hit j counts only
 //                            if j < i (every edge is taken once, from its higher end) and j is included.  Per chunk of 64
 //                            candidates every hitting lane finds its root, the wavefront takes the minimum over those and i's
@@ -16,8 +16,8 @@
 //   labels                   flag the reported roots, scan, scatter their keys (~size << 32 | root), sort (hipcub radix sort), give
 //                            every sorted root its position as label, scatter the labels to the living ranks.
 //   removal                  cluster_seed_kernel marks the roots of seeded points; cluster_classify_kernel flags the members of the
-//                            components the rule removes and appends them to the map's dead list (one atomic per wavefront, as
-//                            surf_classify_kernel), retired by MapStore::kill_dead_list.
+//                            components the rule removes and appends them to the map's dead list (dead_list_append,
+//                            lv_query_dev.hpp), retired by MapStore::retire_dead_list.
 // The partition is a pure function of the living points, the mask and the radius: the order in which links land changes the
 // trees on the way, never the components, and a finished root is always its component's smallest id.
 #include "lv_cluster.hpp"
@@ -35,17 +35,12 @@ namespace {
 constexpr int CWAVES = 4;   // wavefronts (points) per workgroup
 constexpr int CTHREADS = CWAVES * 64;
 
-__device__ __forceinline__ float c_inf() { return __uint_as_float(0x7F800000u); }
-// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
-__device__ __forceinline__ bool c_alive(const float4& p) { return p.x < c_inf() && p.x > -c_inf(); }
-__device__ __forceinline__ uint32_t c_rank(const uint32_t* rank, uint32_t id) { return rank ? rank[id] : id; }
-
 __global__ __launch_bounds__(256) void cluster_init_kernel(const float4* __restrict__ orig, uint32_t n_ids, const uint32_t* __restrict__ rank,
                                                            const uint8_t* __restrict__ mask, uint32_t* __restrict__ parent,
                                                            uint32_t* __restrict__ size, int32_t* __restrict__ lab) {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_ids) return;
-    const bool in = c_alive(orig[id]) && (!mask || mask[c_rank(rank, id)] != 0);
+    const bool in = pt_alive(orig[id]) && (!mask || mask[rank_of(rank, id)] != 0);
     parent[id] = in ? id : CL_NONE;
     size[id] = 0u;
     lab[id] = -1;
@@ -77,34 +72,7 @@ __global__ __launch_bounds__(CTHREADS) void cluster_link_kernel(MapView map, flo
         mine = m;
     };
     const QGeom geo = make_geom(map, qx, qy, qz);
-    bool lists = false, run = false;
-    int lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};
-    if (geo.amax < CELL_FAR) {   // (query_radius_kernel's choice of source)
-        if (radius < search_radius(map, geo, 0)) {
-            run = true;
-        } else {
-            const float qq[3] = {qx, qy, qz};
-            uint64_t nl = 1;
-            bool fits = true;
-            for (int a = 0; a < 3; ++a) {
-                const int l = (cell_coord(qq[a] - radius, map.origin[a], map.inv_cell) >> 2) - 1;
-                const int h = (cell_coord(qq[a] + radius, map.origin[a], map.inv_cell) >> 2) + 1;
-                fits = fits && l >= 0 && h < (1 << 19) && h >= l;
-                lo[a] = l;
-                ext[a] = h - l + 1;
-                nl *= (uint64_t)(fits ? ext[a] : 1);
-            }
-            lists = fits && nl <= (uint64_t)map.n_ids;
-        }
-    }
-    if (run) {
-        const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
-        stream_run(map, b0.x, b0.y, lane, visit);
-    } else if (lists) {
-        stream_lists(map, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], lane, s_pref[w], s_start[w], visit);
-    } else {
-        stream_all(map, lane, visit);
-    }
+    stream_radius(map, radius_source(map, geo, qx, qy, qz, radius), geo, lane, s_pref[w], s_start[w], visit);
 }
 
 __global__ __launch_bounds__(256) void cluster_flatten_kernel(uint32_t n_ids, uint32_t* parent, uint32_t* __restrict__ size) {
@@ -130,9 +98,6 @@ __global__ __launch_bounds__(256) void cluster_flag_kernel(uint32_t n_ids, const
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id < n_ids) flag[id] = (parent[id] == id && cl_reported(size[id], q.min_size, q.max_size)) ? 1u : 0u;
 }
-__global__ void cluster_total_kernel(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ flag, uint32_t n, uint32_t* __restrict__ out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = n ? pos[n - 1] + flag[n - 1] : 0u;
-}
 __global__ __launch_bounds__(256) void cluster_key_kernel(uint32_t n_ids, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
                                                           const uint32_t* __restrict__ size, uint64_t* __restrict__ key) {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,9 +115,9 @@ __global__ __launch_bounds__(256) void cluster_scatter_kernel(const float4* __re
                                                               const uint32_t* __restrict__ parent, const int32_t* __restrict__ lab,
                                                               int32_t* __restrict__ labels) {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= n_ids || !c_alive(orig[id])) return;
+    if (id >= n_ids || !pt_alive(orig[id])) return;
     const uint32_t root = parent[id];
-    labels[c_rank(rank, id)] = root == CL_NONE ? -1 : lab[root];
+    labels[rank_of(rank, id)] = root == CL_NONE ? -1 : lab[root];
 }
 
 // lab[root] = 1 where the component holds a seeded included point (every writer stores the same value)
@@ -161,7 +126,7 @@ __global__ __launch_bounds__(256) void cluster_seed_kernel(uint32_t n_ids, const
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_ids) return;
     const uint32_t root = parent[id];
-    if (root != CL_NONE && seeds[c_rank(rank, id)] != 0) lab[root] = 1;
+    if (root != CL_NONE && seeds[rank_of(rank, id)] != 0) lab[root] = 1;
 }
 
 // One lane per id: flags (optional) at the point's rank; remove: the members of the removed components go to the dead list
@@ -174,25 +139,13 @@ __global__ __launch_bounds__(256) void cluster_classify_kernel(float4* __restric
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     bool gone = false;
     if (id < n_ids) p = orig[id];
-    if (id < n_ids && c_alive(p)) {
+    if (id < n_ids && pt_alive(p)) {
         const uint32_t root = parent[id];
         const bool out = root != CL_NONE && cl_removed(size[root], q.min_size, q.max_size, q.seeded != 0, lab[root] == 1);
-        if (flags) flags[c_rank(rank, id)] = out ? 1 : 0;
+        if (flags) flags[rank_of(rank, id)] = out ? 1 : 0;
         gone = remove && out;
     }
-    // wave-aggregated append to the dead list: one atomic per wavefront
-    const unsigned long long mask = __ballot(gone);
-    if (mask == 0ull) return;
-    const int lane = (int)(threadIdx.x & 63u);
-    const int leader = __ffsll((long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&cnt->n_dead, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (!gone) return;
-    const uint32_t di = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (di < dead_cap) dead[di] = make_float4(p.x, p.y, p.z, __uint_as_float(id));
-    else atomicExch(&cnt->overflow, 1u);
-    orig[id].x = c_inf();
+    dead_list_append(gone, p, id, orig, dead, dead_cap, cnt);
 }
 
 }  // namespace
@@ -243,7 +196,7 @@ int cluster_labels(const MapStore& map, hipStream_t stream, ClusterStore& st, co
     int rc = st.d_tmp.need(bytes ? bytes : 1);
     if (rc) return rc;
     LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(st.d_tmp.p, bytes, st.d_flag.p, st.d_pos.p, (int)ids, stream));
-    hipLaunchKernelGGL(cluster_total_kernel, dim3(1), dim3(64), 0, stream, st.d_pos, st.d_flag, ids, st.d_pos + ids);
+    hipLaunchKernelGGL(scan_total_kernel<uint32_t>, dim3(1), dim3(64), 0, stream, st.d_pos, st.d_flag, ids, st.d_pos + ids);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(st.h_word, st.d_pos + ids, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));
@@ -283,8 +236,8 @@ int cluster_remove(MapStore& map, hipStream_t stream, ClusterStore& st, const Cl
     }
     int rc = map.ensure_counters();
     if (rc) return rc;
-    // n_new .. dropped are contiguous (MapCounters; lv_map.hip reset_batch_counters)
-    LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
+    rc = map.reset_batch_counters(stream);
+    if (rc) return rc;
     hipLaunchKernelGGL(cluster_classify_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_size, st.d_lab, q,
                        flags, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
     LV_HIP(hipGetLastError());
@@ -292,20 +245,7 @@ int cluster_remove(MapStore& map, hipStream_t stream, ClusterStore& st, const Cl
         LV_HIP(hipStreamSynchronize(stream));
         return LV_OK;
     }
-    // retire the dead list: the bookkeeping of surface_outliers (lv_surface.hip)
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    const uint32_t n_dead = map.h_cnt->n_dead;
-    rc = map.kill_dead_list(stream, n_dead < map.dead_cap ? n_dead : (uint32_t)map.dead_cap);
-    if (rc) return rc;
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    map.m -= n_dead;
-    map.tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
-    if (n_removed) *n_removed = n_dead;
-    map.refresh_view();
-    if (map.m == 0) { map.n_ids = 0; return map.rebuild(stream); }
-    return LV_OK;
+    return map.retire_dead_list(stream, n_removed);
 }
 
 }  // namespace lv

@@ -159,10 +159,16 @@ struct MapStore {
     // Add_Points's (the box rule applies among the new points themselves)
     int add_staged(hipStream_t stream, uint32_t k, int downsample, float box_length, bool build_if_empty);
     int ensure_counters();
+    int reset_batch_counters(hipStream_t stream);   // n_new, n_dead, overflow, dropped of every instance back to zero (after ensure_counters)
     int reserve_batch(size_t k);
     int evict_box(hipStream_t stream, const float lo[3], const float hi[3], int keep_inside, uint32_t* n_evicted);
     int evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_evicted);
     int kill_dead_list(hipStream_t stream, uint32_t n_dead);
+    // A removed point turns DEAD_ENTRIES_PER_POINT entries into tombstones: kill_dead_list runs inc_kill_kernel once per bucket
+    // level (27 neighbourhood buckets each) and instance 0 also kills the entry in the point's level-2 voxel list
+    static constexpr uint64_t DEAD_ENTRIES_PER_POINT = 27 * BUCKET_LEVELS + 1;
+    int retire_dead_list(hipStream_t stream, uint32_t* n_removed);                  // the filled dead list: kill, then finish_removal
+    int finish_removal(hipStream_t stream, uint32_t n_dead, uint32_t* n_removed);   // m, tombstones, view; an emptied map is rebuilt
     int ensure_boxes(hipStream_t stream, float box_length);
     int ensure_alive_scratch();
     bool needs_relinearise(size_t incoming) const;

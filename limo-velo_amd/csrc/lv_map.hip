@@ -1144,6 +1144,31 @@ int MapStore::kill_dead_list(hipStream_t stream, uint32_t n_dead) {
     return LV_OK;
 }
 
+// The counted retirement every removal ends with (evict_box, evict_oldest, vis_classify, surface_outliers, cluster_remove): the
+// caller's kernel has appended the leaving points to the dead list and raised n_dead; their bucket and list entries die here.
+// (dead_cap is the id capacity: the list cannot overflow; were it to, only its stored part is killed, while every counted point
+// has left `orig` all the same.)
+int MapStore::retire_dead_list(hipStream_t stream, uint32_t* n_removed) {
+    LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    const uint32_t n_dead = h_cnt->n_dead;
+    const int rc = kill_dead_list(stream, n_dead < dead_cap ? n_dead : (uint32_t)dead_cap);
+    if (rc) return rc;
+    LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
+    LV_HIP(hipStreamSynchronize(stream));
+    return finish_removal(stream, n_dead, n_removed);
+}
+
+// the bookkeeping of n_dead points whose entries are dead by now; an emptied map starts over
+int MapStore::finish_removal(hipStream_t stream, uint32_t n_dead, uint32_t* n_removed) {
+    m -= n_dead;
+    tombstones += (uint64_t)n_dead * DEAD_ENTRIES_PER_POINT;
+    if (n_removed) *n_removed = n_dead;
+    refresh_view();
+    if (m == 0) { n_ids = 0; return rebuild(stream); }
+    return LV_OK;
+}
+
 // (the kernels of the incremental insert that are not one-thread-per-item live here, not in lv_mapinc.hpp: that header is
 // also compiled for the host by tests/emu)
 // Stable sort of a small batch's (box key, input index) pairs by ONE workgroup (bitonic network in LDS over the composite
@@ -1442,10 +1467,10 @@ __global__ void inc_clear_groups_kernel(IncBoth Bo, int reset_counters, uint32_t
     if (l < (uint32_t)REPL_LEVELS) G.table[l][e] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
 }
 
-static int reset_batch_counters(MapStore& S, hipStream_t stream) {
+int MapStore::reset_batch_counters(hipStream_t stream) {
     // n_new .. dropped are contiguous (MapCounters)
     for (int l = 0; l < BUCKET_LEVELS; ++l)
-        LV_HIP(hipMemsetAsync(&S.d_cnt[l].n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
+        LV_HIP(hipMemsetAsync(&d_cnt[l].n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
     return LV_OK;
 }
 
@@ -1472,7 +1497,7 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
         if (rc) return rc;
         rc = ensure_counters();
         if (rc) return rc;
-        rc = reset_batch_counters(*this, stream);
+        rc = reset_batch_counters(stream);
         if (rc) return rc;
         have_boxes = false;
         rc = ensure_boxes(stream, box_length);
@@ -1532,7 +1557,7 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     // (the first down-sampling insert): their build may raise `overflow`, so the reset has to come before it
     const bool reset_early = downsample && !have_boxes;
     if (reset_early) {
-        rc = reset_batch_counters(*this, stream);
+        rc = reset_batch_counters(stream);
         if (rc) return rc;
     }
     // the two instances of the insert machinery (MapStore::rw) with their work lists and scratch
@@ -1717,7 +1742,7 @@ int MapStore::settle(hipStream_t stream) {
     last_new = v[0];
     have_last_new = true;
     m -= n_dead;
-    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
+    tombstones += (uint64_t)n_dead * DEAD_ENTRIES_PER_POINT;
     dropped_total += v[2];
     ++incremental_adds;
     refresh_view();
@@ -1729,9 +1754,8 @@ int MapStore::evict_box(hipStream_t stream, const float lo[3], const float hi[3]
     if (n_evicted) *n_evicted = 0;
     { int rcs = settle(stream); if (rcs) return rcs; }
     if (!built || m == 0) return LV_OK;
-    int rc = reset_batch_counters(*this, stream);
+    int rc = reset_batch_counters(stream);
     if (rc) return rc;
-    uint32_t n_dead = 0;
     if (sweep_evict) {   // (see inc_evict_sweep_kernel)
         const uint32_t g_mark = (n_ids + 255) / 256;
         hipLaunchKernelGGL(inc_evict_mark_kernel, dim3(g_mark < 2048u ? g_mark : 2048u), dim3(256), 0, stream, d_orig, n_ids, lo[0], lo[1], lo[2], hi[0],
@@ -1747,24 +1771,11 @@ int MapStore::evict_box(hipStream_t stream, const float lo[3], const float hi[3]
         LV_HIP(hipGetLastError());
         LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
         LV_HIP(hipStreamSynchronize(stream));
-        n_dead = h_cnt->n_dead;
-    } else {
-        hipLaunchKernelGGL(inc_evict_box_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, stream, d_orig, n_ids, lo[0], lo[1], lo[2], hi[0],
-                           hi[1], hi[2], keep_inside, d_dead, (uint32_t)dead_cap, d_cnt);
-        LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-        LV_HIP(hipStreamSynchronize(stream));
-        n_dead = h_cnt->n_dead;
-        rc = kill_dead_list(stream, n_dead);
-        if (rc) return rc;
-        LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-        LV_HIP(hipStreamSynchronize(stream));
+        return finish_removal(stream, h_cnt->n_dead, n_evicted);   // (the sweep wrote the tombstones itself)
     }
-    m -= n_dead;
-    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
-    if (n_evicted) *n_evicted = n_dead;
-    refresh_view();
-    if (m == 0) { n_ids = 0; return rebuild(stream); }
-    return LV_OK;
+    hipLaunchKernelGGL(inc_evict_box_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, stream, d_orig, n_ids, lo[0], lo[1], lo[2], hi[0], hi[1],
+                       hi[2], keep_inside, d_dead, (uint32_t)dead_cap, d_cnt);
+    return retire_dead_list(stream, n_evicted);
 }
 
 int MapStore::evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_evicted) {
@@ -1774,7 +1785,7 @@ int MapStore::evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_ev
     if (n_oldest > m) n_oldest = m;
     int rc = ensure_alive_scratch();
     if (rc) return rc;
-    rc = reset_batch_counters(*this, stream);
+    rc = reset_batch_counters(stream);
     if (rc) return rc;
     const uint32_t grid = (n_ids + 255) / 256;
     hipLaunchKernelGGL(inc_alive_flags_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_alive);
@@ -1782,19 +1793,7 @@ int MapStore::evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_ev
     LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp, tmp, d_alive, d_apos, (int)n_ids, stream));
     hipLaunchKernelGGL(inc_evict_oldest_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_apos, n_oldest, d_dead,
                        (uint32_t)dead_cap, d_cnt);
-    LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    const uint32_t n_dead = h_cnt->n_dead;
-    rc = kill_dead_list(stream, n_dead);
-    if (rc) return rc;
-    LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    m -= n_dead;
-    tombstones += (uint64_t)n_dead * (27 * BUCKET_LEVELS + 1);
-    if (n_evicted) *n_evicted = n_dead;
-    refresh_view();
-    if (m == 0) { n_ids = 0; return rebuild(stream); }
-    return LV_OK;
+    return retire_dead_list(stream, n_evicted);
 }
 
 }  // namespace lv

@@ -38,7 +38,9 @@
 namespace lv {
 
 constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
-constexpr int INC_SLOTS_PER_POINT = 27 * REPL_LEVELS + 1;   // per instance: a point's 27 buckets + its level-2 voxel's list (instance 0 only)
+// work items per point of ONE instance's passes (insert, kill): a point's 27 buckets + its level-2 voxel's list (instance 0 only).  Not
+// the tombstone count of a removed point, which sums the instances: MapStore::DEAD_ENTRIES_PER_POINT (lv_host.hpp)
+constexpr int INC_SLOTS_PER_POINT = 27 * REPL_LEVELS + 1;
 constexpr int INC_LEVELS = REPL_LEVELS + 1;                 // tables: bt[0], voxel lists
 constexpr uint16_t BACKPOS_FAR = 0xFFFFu;                   // back-position of an entry beyond 16 bits: found by binary search over the run's ids
 constexpr int CELL_SLOT = REPL_LEVELS;                      // index of the voxel-list table in the per-table arrays
@@ -60,7 +62,7 @@ struct MapCounters {
     uint32_t overflow;                 // a pool, a table or a work list ran full: re-linearise
     uint32_t dropped;                  // new points that were not finite or outside the voxel range
     uint32_t box_slots_used;
-    uint32_t tombstones;               // (unused on the device: the host counts INC_SLOTS_PER_POINT per deleted point)
+    uint32_t tombstones;               // (unused on the device: the host counts MapStore::DEAD_ENTRIES_PER_POINT per deleted point)
     uint32_t gslots_used;              // occupied slots of the tile-group table
 };
 
@@ -114,6 +116,10 @@ struct RegroupPlan {   // per listed group: the table slot, old start, new start
     uint32_t slot[8], from[8], to[8], count[8], cap[8];
 };
 
+// a living id: a deleted id reads x = +inf (every tool that walks `orig` tests this one)
+__device__ __forceinline__ bool pt_alive(const float4& p) { return p.x < __uint_as_float(0x7F800000u) && p.x > -__uint_as_float(0x7F800000u); }
+__device__ __forceinline__ float pos_inf() { return __uint_as_float(0x7F800000u); }
+
 // The kernels below are compiled by ONE translation unit (lv_map.hip, or the host emulation in tests/emu): it
 // defines LV_MAPINC_KERNELS before including this header; everybody else only sees the types above.
 #ifdef LV_MAPINC_KERNELS
@@ -139,9 +145,6 @@ __device__ __forceinline__ uint32_t inc_thread_id() { return inc_block_of(blockI
             __VA_ARGS__;                                                                                                       \
         }                                                                                                                      \
     }
-
-__device__ __forceinline__ bool pt_alive(const float4& p) { return p.x < __uint_as_float(0x7F800000u) && p.x > -__uint_as_float(0x7F800000u); }
-__device__ __forceinline__ float pos_inf() { return __uint_as_float(0x7F800000u); }
 
 __device__ __forceinline__ uint64_t entry_key(const uint4& e) { return (uint64_t)e.x | ((uint64_t)e.y << 32); }
 

@@ -11,7 +11,8 @@
 //   paint_color_kernel   one lane per id: reads orig once, loops over the views, the occlusion test, the bilinear sample and the
 //                        blend; writes the outputs at the point's living rank.
 // paint_zbuf_kernel and paint_color_kernel project through the same inline paint_project, so z, u and v are the same bits in
-// both passes and a cell's foremost point always finds itself in front.
+// both passes and a cell's foremost point always finds itself in front.  The living-id test is pt_alive (lv_mapinc.hpp).  The file
+// walks no neighbourhood, so it takes nothing from lv_query_dev.hpp: its one rank lookup stays a ternary.
 #include "lv_paint.hpp"
 
 #include <cstring>
@@ -19,10 +20,6 @@
 namespace lv {
 
 namespace {
-
-__device__ __forceinline__ float paint_inf() { return __uint_as_float(0x7F800000u); }
-// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
-__device__ __forceinline__ bool paint_alive(const float4& p) { return p.x < paint_inf() && p.x > -paint_inf(); }
 
 // Steps 1-3 of the rule: the camera-frame depth z and the pixel coordinates (u, v) of world point p; false when the view does not
 // judge it.  Every sum left to right, nothing fused (-ffp-contract=off).
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void paint_zbuf_kernel(const float4* __restric
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_ids) return;
     const float4 p = orig[id];
-    if (!paint_alive(p)) return;
+    if (!pt_alive(p)) return;
     for (int w = 0; w < q.n_views; ++w) {
         const PaintCam& c = cams[w];
         float z, u, v;
@@ -160,9 +157,9 @@ __global__ __launch_bounds__(256) void paint_color_kernel(const float4* __restri
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_ids) return;
     const float4 p = orig[id];
-    if (!paint_alive(p)) return;
+    if (!pt_alive(p)) return;
     uint32_t n = 0;
-    float best = paint_inf();
+    float best = pos_inf();
     float3 acc = make_float3(0.f, 0.f, 0.f);
     for (int w = 0; w < q.n_views; ++w) {
         const PaintCam& c = cams[w];

@@ -1,7 +1,8 @@
 // lv_query.hip — map queries: batched k-NN, radius and box searches of arbitrary map-frame points against the device map
 // (ikd-Tree's Nearest_Search / Radius_Search / Box_Search, which the update's own search does not expose).
 //
-// k-NN (query_knn_kernel): ONE wavefront per query walks the ladder of the update's search (lv_match.hip) —
+// k-NN (query_knn_kernel): ONE wavefront per query walks the ladder of the update's search (lv_match.hip), written
+// once as knn_ladder (lv_query_dev.hpp) —
 //   level 0  the query voxel's neighbourhood bucket (one contiguous id-sorted run of 12-byte points),
 //   level 1  the region of its tile group while the group is in one piece (extent > 0),
 //   level 2  the 27 level-2 voxel lists around it,
@@ -16,10 +17,11 @@
 // by min(top[i], chunk[63 - i]) (the 64 smallest of the union, bitonic) and cleaned up by 6 bitonic steps.  No LDS except the
 // 2 x 64 words of list offsets a wavefront needs on the list levels.
 //
-// Radius: a count kernel and a fill kernel walk the same source per query — the level-0 run if the radius is inside the level-0
-// radius bound, else the level-2 lists covering [q - r, q + r] (one list of margin per side), else (more lists than ids, or
-// outside the voxel range) every id — with an exclusive scan of the counts in between; the segments are then sorted by id
-// (hipcub segmented radix sort).  Box: one pass over the ids with inc_evict_box_kernel's predicate, a scan, a scatter in id order.
+// Radius: a count kernel and a fill kernel walk the same source per query (radius_source / stream_radius, lv_query_dev.hpp) — the
+// level-0 run if the radius is inside the level-0 radius bound, else the level-2 lists covering [q - r, q + r] (one list of margin
+// per side), else (more lists than ids, or outside the voxel range) every id — with an exclusive scan of the counts in between; the
+// segments are then sorted by id (hipcub segmented radix sort).
+// Box: one pass over the ids with inc_evict_box_kernel's predicate, a scan, a scatter in id order.
 // Results carry ids until the end; the rank among the living comes from a device scan of the alive flags (QueryStore::ensure_rank),
 // rebuilt only when the map's stamp (MapStore::gen) moved and skipped when no id is dead.
 #include "lv_query_dev.hpp"
@@ -39,12 +41,6 @@ constexpr uint32_t NO_IDX = 0xFFFFFFFFu;
 // hipcub counts the items of a scan / sort in an int: the largest query batch, id range or result set handed to one
 constexpr int SCAN_MAX = 0x7FFFFFFF;
 
-// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
-__device__ __forceinline__ bool q_alive(const float4& p) { return p.x < __uint_as_float(0x7F800000u) && p.x > -__uint_as_float(0x7F800000u); }
-
-
-__device__ __forceinline__ uint32_t to_rank(const uint32_t* rank, uint32_t id) { return rank ? rank[id] : id; }
-
 __global__ __launch_bounds__(QTHREADS) void query_knn_kernel(MapView map, const float* __restrict__ q, uint32_t n, int k, float max_d2,
                                                              const uint32_t* __restrict__ rank, uint32_t* __restrict__ idx,
                                                              float* __restrict__ d2, int32_t* __restrict__ found) {
@@ -63,39 +59,11 @@ __global__ __launch_bounds__(QTHREADS) void query_knn_kernel(MapView map, const 
             t.offer(ok && admitted(d, max_d2) ? make_key(d, id) : none_key(), lane);
         };
         const QGeom geo = make_geom(map, qx, qy, qz);
-        bool done = false;
-        if (geo.amax < CELL_FAR) {
-            const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
-            stream_run(map, b0.x, b0.y, lane, visit);
-            done = t.accept(search_radius(map, geo, 0), max_d2);
-            if (!done) {
-                const uint2 g1 = probe(map.gt, pack_cell((uint32_t)(geo.c0x >> 1), (uint32_t)(geo.c0y >> 1), (uint32_t)(geo.c0z >> 1)));
-                if (g1.y > 0) {   // (extent 0: the group is not in one piece)
-                    t.reset();
-                    stream_run(map, g1.x, g1.y, lane, visit);
-                    done = t.accept(search_radius(map, geo, 1), max_d2);
-                }
-            }
-            if (!done) {
-                t.reset();
-                stream_lists(map, (geo.c0x >> 2) - 1, (geo.c0y >> 2) - 1, (geo.c0z >> 2) - 1, 3, 3, 3, lane, s_pref[w], s_start[w], visit);
-                done = t.accept(search_radius(map, geo, 2), max_d2);
-            }
-            if (!done) {
-                t.reset();
-                stream_lists(map, ((geo.c0x >> 3) - 1) * 2, ((geo.c0y >> 3) - 1) * 2, ((geo.c0z >> 3) - 1) * 2, 6, 6, 6, lane, s_pref[w], s_start[w],
-                             visit);
-                done = t.accept(search_radius(map, geo, 3), max_d2);
-            }
-        }
-        if (!done) {
-            t.reset();
-            stream_all(map, lane, visit);
-        }
+        knn_ladder(map, geo, t, max_d2, lane, s_pref[w], s_start[w], visit);
     }
     const bool real = !is_none(t.top) && lane < k;
     if (lane < k) {
-        idx[(size_t)qi * k + lane] = real ? to_rank(rank, key_lo(t.top)) : NO_IDX;
+        idx[(size_t)qi * k + lane] = real ? rank_of(rank, key_lo(t.top)) : NO_IDX;
         if (d2) d2[(size_t)qi * k + lane] = real ? __uint_as_float(key_hi(t.top)) : __uint_as_float(0x7F800000u);
     }
     const int nf = __popcll(__ballot(real));
@@ -133,38 +101,14 @@ __global__ __launch_bounds__(QTHREADS) void query_radius_kernel(MapView map, con
     const bool finite = __builtin_isfinite(qx) && __builtin_isfinite(qy) && __builtin_isfinite(qz);
     if (map.m != 0 && finite) {
         const QGeom geo = make_geom(map, qx, qy, qz);
-        bool lists = false;
-        int lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};
-        if (geo.amax < CELL_FAR) {
-            if (radius < search_radius(map, geo, 0)) {   // every point within the radius lies in the level-0 block
-                const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
-                stream_run(map, b0.x, b0.y, lane, visit);
-                if (!FILL && lane == 0) counts[qi] = got;
-                return;
-            }
-            // the level-2 lists covering [q - r, q + r], one list of margin per side for the rounding of the voxel coordinates
-            const float qq[3] = {qx, qy, qz};
-            uint64_t nl = 1;
-            bool fits = true;
-            for (int a = 0; a < 3; ++a) {
-                const int l = (cell_coord(qq[a] - radius, map.origin[a], map.inv_cell) >> 2) - 1;
-                const int h = (cell_coord(qq[a] + radius, map.origin[a], map.inv_cell) >> 2) + 1;
-                fits = fits && l >= 0 && h < (1 << 19) && h >= l;
-                lo[a] = l;
-                ext[a] = h - l + 1;
-                nl *= (uint64_t)(fits ? ext[a] : 1);
-            }
-            lists = fits && nl <= (uint64_t)map.n_ids;
-        }
-        if (lists) stream_lists(map, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], lane, s_pref[w], s_start[w], visit);
-        else stream_all(map, lane, visit);
+        stream_radius(map, radius_source(map, geo, qx, qy, qz, radius), geo, lane, s_pref[w], s_start[w], visit);
     }
     if (!FILL && lane == 0) counts[qi] = got;
 }
 
 __global__ void query_alive_kernel(const float4* __restrict__ orig, uint32_t n_ids, uint32_t* __restrict__ flag) {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id < n_ids) flag[id] = q_alive(orig[id]) ? 1u : 0u;
+    if (id < n_ids) flag[id] = pt_alive(orig[id]) ? 1u : 0u;
 }
 // inc_evict_box_kernel's predicate (lv_mapinc.hpp): living and inside [lo, hi], both faces inclusive
 __global__ void query_box_flag_kernel(const float4* __restrict__ orig, uint32_t n_ids, float lx, float ly, float lz, float hx, float hy, float hz,
@@ -173,7 +117,7 @@ __global__ void query_box_flag_kernel(const float4* __restrict__ orig, uint32_t 
     if (id >= n_ids) return;
     const float4 p = orig[id];
     const bool inside = p.x >= lx && p.x <= hx && p.y >= ly && p.y <= hy && p.z >= lz && p.z <= hz;
-    flag[id] = (q_alive(p) && inside) ? 1u : 0u;
+    flag[id] = (pt_alive(p) && inside) ? 1u : 0u;
 }
 __global__ void query_box_scatter_kernel(const float4* __restrict__ orig, uint32_t n_ids, const uint32_t* __restrict__ flag,
                                          const uint32_t* __restrict__ pos, const uint32_t* __restrict__ rank, uint32_t* __restrict__ out_idx,
@@ -182,15 +126,10 @@ __global__ void query_box_scatter_kernel(const float4* __restrict__ orig, uint32
     if (id >= n_ids || !flag[id]) return;
     const uint32_t p = pos[id];
     const float4 v = orig[id];
-    out_idx[p] = to_rank(rank, id);
+    out_idx[p] = rank_of(rank, id);
     out_xyz[3 * (size_t)p] = v.x;
     out_xyz[3 * (size_t)p + 1] = v.y;
     out_xyz[3 * (size_t)p + 2] = v.z;
-}
-// the total of an exclusive scan: last offset + last count
-template <class T>
-__global__ void query_total_kernel(const T* __restrict__ excl, const T* __restrict__ cnt, uint32_t n, T* __restrict__ out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = n ? excl[n - 1] + cnt[n - 1] : T(0);
 }
 __global__ void query_remap_kernel(uint32_t* __restrict__ v, uint32_t n, const uint32_t* __restrict__ rank) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -276,7 +215,7 @@ int QueryStore::radius(const MapStore& map, hipStream_t stream, const void* q, s
     rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
     LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_rcnt.p, d_roff.p, (int)n, stream));
-    hipLaunchKernelGGL(query_total_kernel<uint64_t>, dim3(1), dim3(64), 0, stream, d_roff, d_rcnt, (uint32_t)n, d_roff + n);
+    hipLaunchKernelGGL(scan_total_kernel<uint64_t>, dim3(1), dim3(64), 0, stream, d_roff, d_rcnt, (uint32_t)n, d_roff + n);
     LV_HIP(hipGetLastError());
     static_assert(sizeof(size_t) == sizeof(uint64_t), "offsets are copied out as size_t");
     LV_HIP(hipMemcpyAsync(offsets, d_roff, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
@@ -338,7 +277,7 @@ int QueryStore::box(const MapStore& map, hipStream_t stream, const float lo[3], 
     rc = d_tmp.need_pow2(bytes, QUERY_TMP_FLOOR);
     if (rc) return rc;
     LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_tmp.p, bytes, d_cnt.p, d_off.p, (int)ids, stream));
-    hipLaunchKernelGGL(query_total_kernel<uint32_t>, dim3(1), dim3(64), 0, stream, d_off, d_cnt, ids, d_off + ids);
+    hipLaunchKernelGGL(scan_total_kernel<uint32_t>, dim3(1), dim3(64), 0, stream, d_off, d_cnt, ids, d_off + ids);
     LV_HIP(hipGetLastError());
     LV_HIP(hipMemcpyAsync(h_word, d_off + ids, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));

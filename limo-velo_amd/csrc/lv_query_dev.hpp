@@ -1,7 +1,9 @@
-// lv_query_dev.hpp — wavefront primitives of the map queries (lv_query.hip) shared with the surface kernels (lv_surface.hip):
-// the running top-k of one query (TopK over wave_sort64), the hash probe of a grid table and the three candidate streams of the
-// ladder (a level-0 run, the level-2 voxel lists of a box, every id).  Moved here unchanged from lv_query.hip, whose kernels
-// compile to the same instructions with it.
+// lv_query_dev.hpp — what the map tools share on the device (lv_query.hip, lv_surface.hip, lv_cluster.hip, lv_visibility.hip;
+// DESIGN.md "Map-tool helpers"): the running top-k of one query (TopK over wave_sort64), the hash probe of a grid
+// table, the three candidate streams (a level-0 run, the level-2 voxel lists of a box, every id) and the two walks made of them
+// — the k-NN ladder (knn_ladder) and the fixed-radius walk (radius_source + stream_radius) — besides the rank of an id among
+// the living (rank_of), the wave-aggregated append to the map's dead list (dead_list_append) and the total of an exclusive
+// scan (scan_total_kernel).  The living-id test is pt_alive (lv_mapinc.hpp).
 #pragma once
 
 #include "lv_search_dev.hpp"
@@ -141,6 +143,112 @@ __device__ __forceinline__ void stream_lists(const MapView& map, int bx, int by,
             visit(p.x, p.y, p.z, __float_as_uint(p.w), ok);
         }
     }
+}
+
+// The k-NN ladder of one query (one wavefront; lv_query.hip header): the level-0 run, the tile group's region while the group is
+// in one piece, the 27 level-2 lists, the 216 lists of the level-3 block, every id — each rung searched from scratch (t.reset())
+// until one is accepted (TopK::accept).  t arrives reset; visit offers the candidates to it.
+template <class F>
+__device__ __forceinline__ void knn_ladder(const MapView& map, const QGeom& geo, TopK& t, float max_d2, int lane, uint32_t* s_pref,
+                                           uint32_t* s_start, F&& visit) {
+    bool done = false;
+    if (geo.amax < CELL_FAR) {
+        const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
+        stream_run(map, b0.x, b0.y, lane, visit);
+        done = t.accept(search_radius(map, geo, 0), max_d2);
+        if (!done) {
+            const uint2 g1 = probe(map.gt, pack_cell((uint32_t)(geo.c0x >> 1), (uint32_t)(geo.c0y >> 1), (uint32_t)(geo.c0z >> 1)));
+            if (g1.y > 0) {   // (extent 0: the group is not in one piece)
+                t.reset();
+                stream_run(map, g1.x, g1.y, lane, visit);
+                done = t.accept(search_radius(map, geo, 1), max_d2);
+            }
+        }
+        if (!done) {
+            t.reset();
+            stream_lists(map, (geo.c0x >> 2) - 1, (geo.c0y >> 2) - 1, (geo.c0z >> 2) - 1, 3, 3, 3, lane, s_pref, s_start, visit);
+            done = t.accept(search_radius(map, geo, 2), max_d2);
+        }
+        if (!done) {
+            t.reset();
+            stream_lists(map, ((geo.c0x >> 3) - 1) * 2, ((geo.c0y >> 3) - 1) * 2, ((geo.c0z >> 3) - 1) * 2, 6, 6, 6, lane, s_pref, s_start, visit);
+            done = t.accept(search_radius(map, geo, 3), max_d2);
+        }
+    }
+    if (!done) {
+        t.reset();
+        stream_all(map, lane, visit);
+    }
+}
+
+// The candidates of a fixed-radius walk around (qx, qy, qz): the level-0 run while the radius is inside the level-0 bound (every
+// point within it lies in the level-0 block), else the level-2 lists covering [q - r, q + r] with one list of margin per side for
+// the rounding of the voxel coordinates, else (more lists than ids, or outside the voxel range) every id.
+struct RadiusSource {
+    bool run, lists;     // neither: every id
+    int lo[3], ext[3];   // lists: the box of lists (level-2 voxel coordinates)
+};
+__device__ __forceinline__ RadiusSource radius_source(const MapView& map, const QGeom& geo, float qx, float qy, float qz, float radius) {
+    RadiusSource s = {false, false, {0, 0, 0}, {0, 0, 0}};
+    if (geo.amax < CELL_FAR) {
+        if (radius < search_radius(map, geo, 0)) {
+            s.run = true;
+        } else {
+            const float qq[3] = {qx, qy, qz};
+            uint64_t nl = 1;
+            bool fits = true;
+            for (int a = 0; a < 3; ++a) {
+                const int l = (cell_coord(qq[a] - radius, map.origin[a], map.inv_cell) >> 2) - 1;
+                const int h = (cell_coord(qq[a] + radius, map.origin[a], map.inv_cell) >> 2) + 1;
+                fits = fits && l >= 0 && h < (1 << 19) && h >= l;
+                s.lo[a] = l;
+                s.ext[a] = h - l + 1;
+                nl *= (uint64_t)(fits ? s.ext[a] : 1);
+            }
+            s.lists = fits && nl <= (uint64_t)map.n_ids;
+        }
+    }
+    return s;
+}
+template <class F>
+__device__ __forceinline__ void stream_radius(const MapView& map, const RadiusSource& src, const QGeom& geo, int lane, uint32_t* s_pref,
+                                              uint32_t* s_start, F&& visit) {
+    if (src.run) {
+        const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
+        stream_run(map, b0.x, b0.y, lane, visit);
+    } else if (src.lists) {
+        stream_lists(map, src.lo[0], src.lo[1], src.lo[2], src.ext[0], src.ext[1], src.ext[2], lane, s_pref, s_start, visit);
+    } else {
+        stream_all(map, lane, visit);
+    }
+}
+
+// the rank of a living id among the living (rank NULL: no id is dead, ranks are ids)
+__device__ __forceinline__ uint32_t rank_of(const uint32_t* __restrict__ rank, uint32_t id) { return rank ? rank[id] : id; }
+
+// Wave-aggregated append to the map's dead list, called by every lane of the wavefront: the lanes with `gone` store (x, y, z, id)
+// of their point p behind one atomicAdd per wavefront on n_dead and make the id read x = +inf from here on.  An entry beyond
+// dead_cap raises `overflow` instead of being stored.
+__device__ __forceinline__ void dead_list_append(bool gone, const float4& p, uint32_t id, float4* __restrict__ orig, float4* __restrict__ dead,
+                                                 uint32_t dead_cap, MapCounters* cnt) {
+    const unsigned long long mask = __ballot(gone);
+    if (mask == 0ull) return;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int leader = __ffsll((long long)mask) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(&cnt->n_dead, (uint32_t)__popcll(mask));
+    base = __shfl(base, leader);
+    if (!gone) return;
+    const uint32_t di = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    if (di < dead_cap) dead[di] = make_float4(p.x, p.y, p.z, __uint_as_float(id));
+    else atomicExch(&cnt->overflow, 1u);
+    orig[id].x = pos_inf();
+}
+
+// the total of an exclusive scan: last offset + last count
+template <class T>
+__global__ void scan_total_kernel(const T* __restrict__ excl, const T* __restrict__ cnt, uint32_t n, T* __restrict__ out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = n ? excl[n - 1] + cnt[n - 1] : T(0);
 }
 
 }  // namespace lv

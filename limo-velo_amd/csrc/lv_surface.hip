@@ -2,8 +2,8 @@
 // small reduction over them (include/limovelo_hip.h "Surface normals and outlier removal").
 //
 // The queries ARE the map's points:
-//   surf_ladder_kernel  one wavefront per id walks the full ladder exactly as query_knn_kernel does, with its primitives
-//                       (lv_query_dev.hpp; query_radius_kernel's choice of source for the radius count), and reduces in place:
+//   surf_ladder_kernel  one wavefront per id walks knn_ladder (lv_query_dev.hpp; radius_source / stream_radius for the radius
+//                       count) around its own point and reduces in place:
 //                       the top-k sits one neighbour per lane, so each lane forms its own f64 offset and square root and leaves
 //                       them in 1 KiB of LDS per wavefront; distance sum, mean and covariance are then summed in neighbour
 //                       order, six lanes owning one covariance entry each.  The rule that needs distances only gathers nothing.
@@ -12,8 +12,8 @@
 //                       eigen-solve is lane-per-point work.
 // Outliers: the ladder kernel keeps only the point's value (mean distance, or the count inside the radius);
 //   surf_stat_kernel    block partials of sum d / sum (d - mu)^2 over the finite values, f64, folded in block order on the host;
-//   surf_classify_kernel one lane per id: flag at the living rank, the outliers appended to the map's dead list (one atomic per
-//                       wavefront, as vis_classify_kernel), retired by MapStore::kill_dead_list.
+//   surf_classify_kernel one lane per id: flag at the living rank, the outliers appended to the map's dead list (dead_list_append,
+//                       lv_query_dev.hpp), retired by MapStore::retire_dead_list.
 // A workgroup-per-voxel kernel over LDS-staged bucket runs was built and measured at 4.2 times the ladder's time;
 // it is not shipped.  No scratch, no float atomics: every output is a pure function of the living points and the rule.
 #include "lv_surface.hpp"
@@ -30,10 +30,6 @@ namespace {
 constexpr int SWAVES = 4;   // wavefronts per workgroup
 constexpr int STHREADS = SWAVES * 64;
 constexpr int STAT_BLOCKS = 256;
-
-__device__ __forceinline__ float s_inf() { return __uint_as_float(0x7F800000u); }
-// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
-__device__ __forceinline__ bool s_alive(const float4& p) { return p.x < s_inf() && p.x > -s_inf(); }
 
 // what one wavefront needs to sum over its neighbours in order
 struct WaveScratch {
@@ -59,7 +55,7 @@ __device__ __forceinline__ void surf_reduce(const MapView& map, const TopK& t, i
     wave_lds_fence();
     double dsum = 0.0;
     for (int j = 0; j < n; ++j) dsum += s.r[j];
-    const double inf = (double)s_inf();
+    const double inf = (double)pos_inf();
     if (q.job == 1) {   // the point and k others, or it has no finite value
         if (lane == 0) val[id] = n == q.k ? dsum / (double)(n - 1) : inf;
         return;
@@ -80,13 +76,13 @@ __device__ __forceinline__ void surf_reduce(const MapView& map, const TopK& t, i
     for (int j = 0; j < n; ++j) acc += (s.o[j][a] - ma) * (s.o[j][b] - mb);
     if (lane < 6) val[6 * (size_t)id + lane] = acc / dn;
     if (lane == 0) {
-        const uint32_t r = rank ? rank[id] : id;
-        mean_dist[r] = n > 1 ? (float)(dsum / (double)(n - 1)) : s_inf();
+        const uint32_t r = rank_of(rank, id);
+        mean_dist[r] = n > 1 ? (float)(dsum / (double)(n - 1)) : pos_inf();
         n_used[r] = n;
     }
 }
 
-// one wavefront per id: query_knn_kernel's ladder (RADIUS: query_radius_kernel's sources) for the map point `id`
+// one wavefront per id: knn_ladder (RADIUS: the fixed-radius walk) for the map point `id`
 template <bool RADIUS>
 __global__ __launch_bounds__(STHREADS) void surf_ladder_kernel(MapView map, SurfRule q, const uint32_t* __restrict__ rank,
                                                                double* __restrict__ val,
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(STHREADS) void surf_ladder_kernel(MapView map, Surf
     const uint32_t id = blockIdx.x * (uint32_t)SWAVES + (uint32_t)w;
     if (id >= map.n_ids) return;   // (wavefront-uniform, as the dead ids below)
     const float4 P = map.orig[id];
-    if (!s_alive(P)) return;
+    if (!pt_alive(P)) return;
     const float qx = P.x, qy = P.y, qz = P.z;
     const float max_d2 = q.max_dist * q.max_dist;
     const QGeom geo = make_geom(map, qx, qy, qz);
@@ -108,34 +104,7 @@ __global__ __launch_bounds__(STHREADS) void surf_ladder_kernel(MapView map, Surf
             const float d = calc_dist(qx, qy, qz, Xyz{x, y, z});
             got += (uint32_t)__popcll(__ballot(ok && admitted(d, max_d2) && cid != id));
         };
-        bool lists = false, run = false;
-        int lo[3] = {0, 0, 0}, ext[3] = {0, 0, 0};
-        if (geo.amax < CELL_FAR) {
-            if (radius < search_radius(map, geo, 0)) {
-                run = true;
-            } else {
-                const float qq[3] = {qx, qy, qz};
-                uint64_t nl = 1;
-                bool fits = true;
-                for (int a = 0; a < 3; ++a) {
-                    const int l = (cell_coord(qq[a] - radius, map.origin[a], map.inv_cell) >> 2) - 1;
-                    const int h = (cell_coord(qq[a] + radius, map.origin[a], map.inv_cell) >> 2) + 1;
-                    fits = fits && l >= 0 && h < (1 << 19) && h >= l;
-                    lo[a] = l;
-                    ext[a] = h - l + 1;
-                    nl *= (uint64_t)(fits ? ext[a] : 1);
-                }
-                lists = fits && nl <= (uint64_t)map.n_ids;
-            }
-        }
-        if (run) {
-            const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
-            stream_run(map, b0.x, b0.y, lane, visit);
-        } else if (lists) {
-            stream_lists(map, lo[0], lo[1], lo[2], ext[0], ext[1], ext[2], lane, s_pref[w], s_start[w], visit);
-        } else {
-            stream_all(map, lane, visit);
-        }
+        stream_radius(map, radius_source(map, geo, qx, qy, qz, radius), geo, lane, s_pref[w], s_start[w], visit);
         if (lane == 0) val[id] = (double)got;
         return;
     }
@@ -146,35 +115,7 @@ __global__ __launch_bounds__(STHREADS) void surf_ladder_kernel(MapView map, Surf
         const float d = calc_dist(qx, qy, qz, Xyz{x, y, z});
         t.offer(ok && admitted(d, max_d2) ? make_key(d, cid) : none_key(), lane);
     };
-    bool done = false;
-    if (geo.amax < CELL_FAR) {
-        const uint2 b0 = probe(map.bt[0], pack_cell((uint32_t)geo.c0x, (uint32_t)geo.c0y, (uint32_t)geo.c0z));
-        stream_run(map, b0.x, b0.y, lane, visit);
-        done = t.accept(search_radius(map, geo, 0), max_d2);
-        if (!done) {
-            const uint2 g1 = probe(map.gt, pack_cell((uint32_t)(geo.c0x >> 1), (uint32_t)(geo.c0y >> 1), (uint32_t)(geo.c0z >> 1)));
-            if (g1.y > 0) {   // (extent 0: the group is not in one piece)
-                t.reset();
-                stream_run(map, g1.x, g1.y, lane, visit);
-                done = t.accept(search_radius(map, geo, 1), max_d2);
-            }
-        }
-        if (!done) {
-            t.reset();
-            stream_lists(map, (geo.c0x >> 2) - 1, (geo.c0y >> 2) - 1, (geo.c0z >> 2) - 1, 3, 3, 3, lane, s_pref[w], s_start[w], visit);
-            done = t.accept(search_radius(map, geo, 2), max_d2);
-        }
-        if (!done) {
-            t.reset();
-            stream_lists(map, ((geo.c0x >> 3) - 1) * 2, ((geo.c0y >> 3) - 1) * 2, ((geo.c0z >> 3) - 1) * 2, 6, 6, 6, lane, s_pref[w], s_start[w],
-                         visit);
-            done = t.accept(search_radius(map, geo, 3), max_d2);
-        }
-    }
-    if (!done) {
-        t.reset();
-        stream_all(map, lane, visit);
-    }
+    knn_ladder(map, geo, t, max_d2, lane, s_pref[w], s_start[w], visit);
     surf_reduce(map, t, lane, qx, qy, qz, id, q, rank, s_ws[w], val, mean_dist, n_used);
 }
 
@@ -185,8 +126,8 @@ __global__ __launch_bounds__(256) void surf_finish_kernel(const float4* __restri
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_ids) return;
     const float4 p = orig[id];
-    if (!s_alive(p)) return;
-    const uint32_t r = rank ? rank[id] : id;
+    if (!pt_alive(p)) return;
+    const uint32_t r = rank_of(rank, id);
     const double* c = val + 6 * (size_t)id;
     float n0, n1, n2, cv;
     surf_normal(c[0], c[1], c[2], c[3], c[4], c[5], n_used[r], q.min_neighbours, q.orient, q.viewpoint[0] - (double)p.x, q.viewpoint[1] - (double)p.y,
@@ -203,9 +144,9 @@ __global__ __launch_bounds__(256) void surf_stat_kernel(const float4* __restrict
     __shared__ double s_s[256], s_c[256];
     double s = 0.0, c = 0.0;
     for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < n_ids; id += gridDim.x * blockDim.x) {
-        if (!s_alive(orig[id])) continue;
+        if (!pt_alive(orig[id])) continue;
         const double v = val[id];
-        if (!(v < (double)s_inf())) continue;
+        if (!(v < (double)pos_inf())) continue;
         if (pass == 0) { s += v; c += 1.0; }
         else { const double d = v - mu; s += d * d; }
     }
@@ -234,25 +175,13 @@ __global__ __launch_bounds__(256) void surf_classify_kernel(float4* __restrict__
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     bool gone = false;
     if (id < n_ids) p = orig[id];
-    if (id < n_ids && s_alive(p)) {
+    if (id < n_ids && pt_alive(p)) {
         const double v = val[id];
         const bool out = job == 1 ? v > threshold : v < threshold;
-        if (flags) flags[rank ? rank[id] : id] = out ? 1 : 0;
+        if (flags) flags[rank_of(rank, id)] = out ? 1 : 0;
         gone = remove && out;
     }
-    // wave-aggregated append to the dead list: one atomic per wavefront
-    const unsigned long long mask = __ballot(gone);
-    if (mask == 0ull) return;
-    const int lane = (int)(threadIdx.x & 63u);
-    const int leader = __ffsll((long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&cnt->n_dead, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (!gone) return;
-    const uint32_t di = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (di < dead_cap) dead[di] = make_float4(p.x, p.y, p.z, __uint_as_float(id));
-    else atomicExch(&cnt->overflow, 1u);
-    orig[id].x = s_inf();
+    dead_list_append(gone, p, id, orig, dead, dead_cap, cnt);
 }
 
 }  // namespace
@@ -337,8 +266,8 @@ int surface_outliers(MapStore& map, hipStream_t stream, SurfaceStore& st, SurfRu
     }
     rc = map.ensure_counters();
     if (rc) return rc;
-    // n_new .. dropped are contiguous (MapCounters; lv_map.hip reset_batch_counters)
-    LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
+    rc = map.reset_batch_counters(stream);
+    if (rc) return rc;
     hipLaunchKernelGGL(surf_classify_kernel, dim3(blocks_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, st.d_val, q.job, q.threshold,
                        rank, want_flags ? st.d_flags.p : nullptr, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
     LV_HIP(hipGetLastError());
@@ -346,20 +275,7 @@ int surface_outliers(MapStore& map, hipStream_t stream, SurfaceStore& st, SurfRu
         LV_HIP(hipStreamSynchronize(stream));
         return LV_OK;
     }
-    // retire the dead list: the bookkeeping of vis_classify (lv_visibility.hip)
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    const uint32_t n_dead = map.h_cnt->n_dead;
-    rc = map.kill_dead_list(stream, n_dead < map.dead_cap ? n_dead : (uint32_t)map.dead_cap);
-    if (rc) return rc;
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    map.m -= n_dead;
-    map.tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
-    if (n_removed) *n_removed = n_dead;
-    map.refresh_view();
-    if (map.m == 0) { map.n_ids = 0; return map.rebuild(stream); }
-    return LV_OK;
+    return map.retire_dead_list(stream, n_removed);
 }
 
 }  // namespace lv

@@ -8,9 +8,11 @@
 //   vis_min_rows_kernel  along the rows (clipped at the image's edge);
 //   vis_classify_kernel  one lane per id: reads orig once, loops over the views, gathers from the filtered images (512 KiB per
 //                        2048 x 64 view: they stay in the L2 / Infinity Cache), writes the hit count at the point's living rank
-//                        and appends the removed ids to the map's dead list, one atomic per wavefront.
-// The dead list is then retired by MapStore::kill_dead_list, the path of MapStore::evict_oldest.
+//                        and appends the removed ids to the map's dead list (dead_list_append, lv_query_dev.hpp).
+// The dead list is then retired by MapStore::retire_dead_list, the path of every removal.
 #include "lv_visibility.hpp"
+
+#include "lv_query_dev.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -20,10 +22,6 @@ namespace lv {
 namespace {
 
 constexpr float VIS_PI = 3.14159265358979323846f;
-
-__device__ __forceinline__ float vis_inf() { return __uint_as_float(0x7F800000u); }
-// a living id (lv_mapinc.hpp pt_alive: a deleted id reads x = +inf)
-__device__ __forceinline__ bool vis_alive(const float4& p) { return p.x < vis_inf() && p.x > -vis_inf(); }
 
 // the pixel of a sensor-frame point (x, y, z) with x*x + y*y = xy2; false outside the rows
 __device__ __forceinline__ bool vis_pixel(const VisRule& q, float x, float y, float z, float xy2, uint32_t& pix) {
@@ -43,7 +41,7 @@ __global__ __launch_bounds__(256) void vis_image_kernel(const float4* __restrict
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 p = pts[i];
-    if (!(fabsf(p.x) < vis_inf() && fabsf(p.y) < vis_inf() && fabsf(p.z) < vis_inf())) return;
+    if (!(fabsf(p.x) < pos_inf() && fabsf(p.y) < pos_inf() && fabsf(p.z) < pos_inf())) return;
     const float xy2 = p.x * p.x + p.y * p.y;
     const float r = sqrtf(xy2 + p.z * p.z);
     if (!(r > q.min_range)) return;
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(256) void vis_classify_kernel(float4* __restrict__ 
     float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
     bool gone = false;
     if (id < n_ids) p = orig[id];
-    if (id < n_ids && vis_alive(p)) {
+    if (id < n_ids && pt_alive(p)) {
         const size_t plane = (size_t)q.width * (size_t)q.height;
         uint32_t h = 0;
         for (int v = 0; v < q.n_views; ++v) {
@@ -108,24 +106,12 @@ __global__ __launch_bounds__(256) void vis_classify_kernel(float4* __restrict__ 
             uint32_t pix;
             if (!vis_pixel(q, x, y, z, xy2, pix)) continue;
             const float ri = img[(size_t)v * plane + pix];
-            if (ri < vis_inf() && ri - r > fmaxf(q.margin_abs, q.margin_rel * r)) ++h;
+            if (ri < pos_inf() && ri - r > fmaxf(q.margin_abs, q.margin_rel * r)) ++h;
         }
-        if (hits) hits[rank ? rank[id] : id] = (uint8_t)h;
+        if (hits) hits[rank_of(rank, id)] = (uint8_t)h;
         gone = remove && h >= (uint32_t)q.min_hits;
     }
-    // wave-aggregated append to the dead list: one atomic per wavefront
-    const unsigned long long mask = __ballot(gone);
-    if (mask == 0ull) return;
-    const int lane = (int)(threadIdx.x & 63u);
-    const int leader = __ffsll((long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&cnt->n_dead, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    if (!gone) return;
-    const uint32_t di = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    if (di < dead_cap) dead[di] = make_float4(p.x, p.y, p.z, __uint_as_float(id));
-    else atomicExch(&cnt->overflow, 1u);
-    orig[id].x = vis_inf();
+    dead_list_append(gone, p, id, orig, dead, dead_cap, cnt);
 }
 
 }  // namespace
@@ -192,8 +178,8 @@ int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const Vi
     if (!map.built || map.m == 0) return LV_OK;
     int rc = map.ensure_counters();
     if (rc) return rc;
-    // n_new .. dropped are contiguous (MapCounters; lv_map.hip reset_batch_counters)
-    LV_HIP(hipMemsetAsync(&map.d_cnt->n_new, 0, offsetof(MapCounters, box_slots_used) - offsetof(MapCounters, n_new), stream));
+    rc = map.reset_batch_counters(stream);
+    if (rc) return rc;
     const float* pose = static_cast<const float*>(d_blob);
     const float* img = reinterpret_cast<const float*>(static_cast<const char*>(d_blob) + vis_pose_bytes(q.n_views));
     hipLaunchKernelGGL(vis_classify_kernel, dim3(blocks_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, pose, img, q, rank, hits,
@@ -203,20 +189,7 @@ int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const Vi
         LV_HIP(hipStreamSynchronize(stream));
         return LV_OK;
     }
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    const uint32_t n_dead = map.h_cnt->n_dead;
-    // (dead_cap is the id capacity: the list cannot overflow; were it to, only its stored part is retired)
-    rc = map.kill_dead_list(stream, n_dead < map.dead_cap ? n_dead : (uint32_t)map.dead_cap);
-    if (rc) return rc;
-    LV_HIP(hipMemcpyAsync(map.h_cnt, map.d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    map.m -= n_dead;
-    map.tombstones += (uint64_t)n_dead * INC_SLOTS_PER_POINT;
-    if (n_removed) *n_removed = n_dead;
-    map.refresh_view();
-    if (map.m == 0) { map.n_ids = 0; return map.rebuild(stream); }
-    return LV_OK;
+    return map.retire_dead_list(stream, n_removed);
 }
 
 }  // namespace lv

@@ -29,5 +29,5 @@ with capi.Context() as ctx:
         ctx.map_add_scan(downsample=True)
         ctx.synchronize()
         ts.append((time.perf_counter() - t0) * 1e3)
-        dead.append((ctx.map_stats()["tombstones"] - tomb0) // 28)   # (28 entries per deleted point: its 27 level-0 runs + its voxel list)
+        dead.append((ctx.map_stats()["tombstones"] - tomb0) // 55)   # (55 entries per deleted point: its 27 runs on each of the two bucket levels + its voxel list; MapStore::DEAD_ENTRIES_PER_POINT)
     print(mode, "insert ms (synchronised):", [round(t, 3) for t in ts], "map", ctx.map_size(), "deleted per insert", dead)
