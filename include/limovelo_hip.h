@@ -768,6 +768,92 @@ int  lv_occ_raycast(lv_ctx* ctx, const lv_ray_params* p, const void* from, size_
 /* n_views 1..32; gain: n_views x 4 counters as above. */
 int  lv_occ_view_gain(lv_ctx* ctx, const lv_view* views, size_t n_views, uint64_t* gain);
 
+/* ---- Elevation map -----------------------------------------------------------------------------------
+ * A 2.5-D height map of the ground with a traversability class per cell, from the points of the device map or from the caller's:
+ * ANYbotics' elevation_mapping and traversability_estimation, Autoware's points2costmap, the terrain layer of grid_map (the
+ * reference has no counterpart).  Where the planar products of "Occupancy grid" call a cell an obstacle when any voxel of a fixed
+ * band of layers is occupied, here every cell carries its own ground height, and what is lethal follows from the step to the
+ * neighbouring cells, the slope and the height of what stands on the ground; what hangs above the robot is ignored.  Integer
+ * arithmetic after one quantisation, integer min / max / add only: a pure function of the point SET and the parameters, the same
+ * bits whatever the order of the points and the schedule.
+ *   grid     origin[3], resolution (finite, > 0), nx, ny each 1..4096, nx * ny <= 2^24; cell index j * nx + i (the layout of
+ *            nav_msgs/OccupancyGrid).  origin[2] is the zero of the height scale.
+ *   point    per axis q_a = (int32) floorf(((p_a - origin_a) / resolution) * 256.0f), f32 operations in exactly that order (the
+ *            quantisation of lv_occ_query: 256 sub-units per cell).  A point is IGNORED if an axis fails (non-finite, or
+ *            |q_a| >= 2^24) or if its cell (q_x >> 8, q_y >> 8) lies outside the grid; otherwise it is USED in that cell c with
+ *            the integer height z = q_z.
+ *   layers   n(c) = the used points of c; lo(c) = min z.  The BODY BAND of c is its points with z - lo(c) <= head: nb(c) their
+ *            number, top(c) their max z.  Points above the band are OVERHANG: they count in n and in nothing else.  A cell with
+ *            n = 0 has lo = LV_ELEV_NONE, top = -LV_ELEV_NONE, nb = 0.  c is KNOWN iff nb(c) >= min_points.
+ *   terrain  per KNOWN cell, its neighbours being the KNOWN cells of its 8-neighbourhood inside the grid: span = top - lo;
+ *            step = max |lo(c') - lo(c)| over the neighbours, 0 with none; g_x from the cells at i - 1 and i + 1: lo(i+1) - lo(i-1)
+ *            with both known, 2 * (lo(i+1) - lo(i)) with only i + 1, 2 * (lo(i) - lo(i-1)) with only i - 1, 0 with neither; g_y
+ *            likewise along j; slope2 = min(g_x^2 + g_y^2, 2^31 - 1) computed in int64: tan^2 of the slope is slope2 / 512^2.
+ *            Cells that are not known store span = step = slope2 = 0.
+ *   class    int8: -1 if the cell is not known; 100 if span > max_span or step > max_step or slope2 > max_slope2; 0 otherwise.
+ *   height   metres: origin[2] + resolution * ((float)lo / 256.0f), f32, unfused, in that order; NaN where the cell is not known.
+ *   limits   min_points 1..2^20; head, max_span, max_step 0..2^25 (sub-units); max_slope2 0..2^31 - 1.
+ *   source   pts == NULL (n is ignored): the living points of the device map, after the insert in flight has settled, as
+ *            lv_map_paint reads them; a map that is not built or empty gives a built elevation map with every cell unknown and
+ *            all-zero stats.  Otherwise n (< 2^31) caller points, the first three floats of every stride bytes (stride >= 12);
+ *            n = 0 is allowed.
+ *   query    the cell of a point is that of lv_occ_distance_query in a planar field: x and y quantised, z not used (it may be
+ *            anything).  height and cls of that cell; NaN and -1 for a non-finite x or y and for a point outside the grid.
+ * The result is a SNAPSHOT of its source: later inserts into and removals from the map do not change it; a new build replaces it,
+ * a build refused with LV_EINVAL leaves it in place; lv_elev_clear and lv_destroy free it.  A build changes no bit of the map,
+ * the occupancy grid or anything built from it.
+ *   distance from cells  lv_occ_distance_build_cells builds the planar field of "Distance field" exactly as lv_occ_distance_build
+ *            does with planar != 0, but over the caller's cells instead of the projected ones: cells[j * nx + i], n == nx * ny of
+ *            the configured occupancy grid (else LV_EINVAL).  A cell is an obstacle iff its value is 100; with
+ *            unknown_is_obstacle any negative value is one too; every other value is not an obstacle.  p->planar must be non-zero;
+ *            k_lo / k_hi are not used and are reported back as given.  Truncation, signed fields, stats, fetch, query, info, the
+ *            stale rule and what the planner and the frontier ranking do with the field are those of lv_occ_distance_build, so a
+ *            class grid of this section (merged with lv_occ_project or not) becomes the planner's obstacles.  LV_ESTATE before
+ *            lv_occ_configure; a refused call leaves the old field in place.
+ * Parameters and NULL or short arguments are judged before the context (LV_EINVAL, nothing written;
+ * "null context" comes last); lv_elev_fetch and lv_elev_query give LV_ESTATE before a build (lv_elev_info reports built = 0
+ * instead).  Nothing is allocated before the first build.  The calls run on the context's stream and return when their host
+ * outputs are written. */
+#define LV_ELEV_NONE 2147483647
+#define LV_ELEV_LO         0   /* int32 */
+#define LV_ELEV_TOP        1   /* int32 */
+#define LV_ELEV_SPAN       2   /* int32 */
+#define LV_ELEV_STEP       3   /* int32 */
+#define LV_ELEV_SLOPE2     4   /* int32 */
+#define LV_ELEV_COUNT      5   /* uint32: n */
+#define LV_ELEV_BAND_COUNT 6   /* uint32: nb */
+#define LV_ELEV_CLASS      7   /* int8 */
+#define LV_ELEV_HEIGHT     8   /* float */
+typedef struct lv_elevation_params {
+    float origin[3];
+    float resolution;
+    int nx, ny;
+    int min_points;
+    int head, max_span, max_step;   /* sub-units: 256 per cell */
+    int max_slope2;
+} lv_elevation_params;
+typedef struct lv_elevation_info {
+    int built, nx, ny, from_map;
+    uint64_t n_points;              /* source points swept: the caller's n, or the map's living points */
+    lv_elevation_params params;
+} lv_elevation_info;
+/* The footprint of lv_default_occupancy_params: origin (-51.2, -51.2, -3.2), resolution 0.2, 512 x 512; min_points 3; head 1920
+ * (1.5 m), max_span 153 (0.12 m), max_step 128 (0.10 m), each floor(metres / resolution * 256); max_slope2 34727 =
+ * floor((512 tan 20 deg)^2). */
+void lv_default_elevation_params(lv_elevation_params* p);
+/* stats (may be NULL): points used, overhang points, known cells, lethal cells. */
+int  lv_elev_build(lv_ctx* ctx, const lv_elevation_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]);
+/* out: nx * ny elements of the layer's type; capacity in elements. */
+int  lv_elev_fetch(lv_ctx* ctx, int layer, void* out, size_t capacity);
+/* height, cls: n values each; either may be NULL, not both. */
+int  lv_elev_query(lv_ctx* ctx, const void* pts, size_t stride, size_t n, float* height, int8_t* cls);
+/* All zero with built = 0. */
+int  lv_elev_info(lv_ctx* ctx, lv_elevation_info* out);
+/* Frees the elevation map. */
+int  lv_elev_clear(lv_ctx* ctx);
+/* cells: n = nx * ny values of the occupancy grid's plane; stats as lv_occ_distance_build's. */
+int  lv_occ_distance_build_cells(lv_ctx* ctx, const lv_distance_params* p, const int8_t* cells, size_t n, uint64_t stats[4]);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

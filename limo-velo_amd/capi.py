@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "lv_default_frontier_params", "lv_occ_frontier_build", "lv_occ_frontier_fetch", "lv_occ_frontier_clusters", "lv_occ_frontier_rank",
     "lv_occ_frontier_info", "lv_occ_frontier_clear",
     "lv_default_ray_params", "lv_occ_raycast", "lv_occ_view_gain",
+    "lv_default_elevation_params", "lv_elev_build", "lv_elev_fetch", "lv_elev_query", "lv_elev_info", "lv_elev_clear",
+    "lv_occ_distance_build_cells",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -266,6 +268,34 @@ RAY_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in RayResult._fields_])
 RAY_ARGTYPES = {
     "lv_occ_raycast": [C.c_void_p, C.POINTER(RayParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(RayResult)],
     "lv_occ_view_gain": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(C.c_uint64)],
+}
+
+LV_ELEV_NONE = 2147483647
+(LV_ELEV_LO, LV_ELEV_TOP, LV_ELEV_SPAN, LV_ELEV_STEP, LV_ELEV_SLOPE2, LV_ELEV_COUNT, LV_ELEV_BAND_COUNT, LV_ELEV_CLASS,
+ LV_ELEV_HEIGHT) = range(9)
+# name and numpy type of every layer of lv_elev_fetch, by its number
+ELEV_LAYERS = (("lo", np.int32), ("top", np.int32), ("span", np.int32), ("step", np.int32), ("slope2", np.int32), ("count", np.uint32),
+               ("band_count", np.uint32), ("cls", np.int8), ("height", np.float32))
+
+
+class ElevationParams(C.Structure):  # lv_elevation_params
+    _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("min_points", C.c_int),
+                ("head", C.c_int), ("max_span", C.c_int), ("max_step", C.c_int), ("max_slope2", C.c_int)]
+
+
+class ElevationInfo(C.Structure):  # lv_elevation_info
+    _fields_ = [("built", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("from_map", C.c_int), ("n_points", C.c_uint64),
+                ("params", ElevationParams)]
+
+
+# ctypes signatures of the elevation map (include/limovelo_hip.h "Elevation map"; tests/test_elevation_abi.py)
+ELEVATION_ARGTYPES = {
+    "lv_elev_build": [C.c_void_p, C.POINTER(ElevationParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)],
+    "lv_elev_fetch": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
+    "lv_elev_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int8)],
+    "lv_elev_info": [C.c_void_p, C.POINTER(ElevationInfo)],
+    "lv_elev_clear": [C.c_void_p],
+    "lv_occ_distance_build_cells": [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(C.c_int8), C.c_size_t, C.POINTER(C.c_uint64)],
 }
 
 
@@ -494,9 +524,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_frontier_params.argtypes = [C.POINTER(FrontierParams)]
         lib.lv_default_ray_params.restype = None
         lib.lv_default_ray_params.argtypes = [C.POINTER(RayParams)]
+        lib.lv_default_elevation_params.restype = None
+        lib.lv_default_elevation_params.argtypes = [C.POINTER(ElevationParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -606,6 +638,17 @@ def default_ray_params(**kw) -> RayParams:
     load_library().lv_default_ray_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
+    return p
+
+
+def default_elevation_params(**kw) -> ElevationParams:
+    p = ElevationParams()
+    load_library().lv_default_elevation_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -1073,6 +1116,57 @@ class Context:
         self._check(self.lib.lv_occ_raycast(self.h, C.byref(p), a.ctypes.data_as(C.c_void_p), C.c_size_t(sa), b.ctypes.data_as(C.c_void_p),
                                             C.c_size_t(sb), C.c_size_t(n), out.ctypes.data_as(C.POINTER(RayResult))))
         return out
+
+    # --- elevation map (include/limovelo_hip.h "Elevation map")
+    def elev_build(self, params: ElevationParams | None = None, points=None) -> np.ndarray:
+        """lv_elev_build from points [n, 3] (None: the living points of the device map); returns stats [4] uint64: points used,
+        overhang points, known cells, lethal cells."""
+        p = params if params is not None else default_elevation_params()
+        stats = np.zeros(4, np.uint64)
+        if points is None:
+            a, stride, n = None, 0, 0
+        else:
+            a, stride, n = _points(np.asarray(points, np.float32).reshape(-1, 3))
+            if n == 0:   # (no points, but still "caller points": a pointer that is not NULL)
+                a, stride = np.zeros((1, 3), np.float32), 12
+        self._check(self.lib.lv_elev_build(self.h, C.byref(p), None if a is None else C.c_void_p(a.ctypes.data), C.c_size_t(stride), C.c_size_t(n),
+                                           stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def elev_info(self) -> ElevationInfo:
+        out = ElevationInfo()
+        self._check(self.lib.lv_elev_info(self.h, C.byref(out)))
+        return out
+
+    def elev_fetch(self, layer: int) -> np.ndarray:
+        """[ny, nx] of the layer's type (ELEV_LAYERS): lv_elev_fetch."""
+        i = self.elev_info()
+        dtype = ELEV_LAYERS[layer][1] if 0 <= int(layer) < len(ELEV_LAYERS) else np.int32
+        out = np.zeros((i.ny, i.nx) if i.built else (1, 1), dtype)
+        self._check(self.lib.lv_elev_fetch(self.h, int(layer), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size)))
+        return out
+
+    def elev_query(self, pts):
+        """(height [n] f32 metres, cls [n] int8) of the cell each world point's x, y fall in; NaN and -1 outside the grid."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        h = np.full(n, np.nan, np.float32)
+        k = np.full(n, -1, np.int8)
+        self._check(self.lib.lv_elev_query(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                           h.ctypes.data_as(C.POINTER(C.c_float)), k.ctypes.data_as(C.POINTER(C.c_int8))))
+        return h, k
+
+    def elev_clear(self):
+        self._check(self.lib.lv_elev_clear(self.h))
+
+    def occ_distance_build_cells(self, cells, params: DistanceParams | None = None) -> np.ndarray:
+        """lv_occ_distance_build_cells over cells (int8, [ny, nx] of the occupancy grid: 100 an obstacle, negative unknown); default
+        parameters: planar = 1.  Returns lv_occ_distance_build's stats."""
+        p = params if params is not None else default_distance_params(planar=1)
+        a = np.ascontiguousarray(cells, np.int8)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_distance_build_cells(self.h, C.byref(p), a.ctypes.data_as(C.POINTER(C.c_int8)), C.c_size_t(a.size),
+                                                         stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
 
     def occ_view_gain(self, views) -> np.ndarray:
         """lv_occ_view_gain over views = [(R [3, 3], t [3], pattern end points [n, 3] sensor frame)] (1..32 of them); returns

@@ -17,6 +17,7 @@
 #include "lv_plan.hpp"
 #include "lv_frontier.hpp"
 #include "lv_ray.hpp"
+#include "lv_elevation.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -57,6 +58,7 @@ struct lv_ctx {
     PlanStore plan;     // lv_occ_plan_*: the cost-to-go over that field (lv_plan.hip); nothing allocated before the first build
     FrontierStore frontier;   // lv_occ_frontier_*: the frontier clusters of that grid (lv_frontier.hip); nothing allocated before the first build
     RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
+    ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -644,6 +646,7 @@ void lv_destroy(lv_ctx* c) {
     c->cluster.release();
     c->place.release();
     c->ray.release();
+    c->elev.release();
     c->frontier.release();
     c->plan.release();
     c->dist.release();
@@ -2549,7 +2552,7 @@ int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats
     if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
     LV_OCC_CTX(c);
     occ_field_changed(c);
-    return c->dist.build(c->stream, c->occ, *p, stats);
+    return c->dist.build(c->stream, c->occ, *p, nullptr, stats);
 }
 
 int lv_occ_distance_fetch(lv_ctx* c, int32_t* s2, float* metres, size_t capacity) {
@@ -2731,6 +2734,91 @@ int lv_occ_view_gain(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t* 
     }
     LV_OCC_CTX(c);
     return c->ray.view_gain(c->stream, c->occ, views, n_views, gain);
+}
+
+// ---- Elevation map (lv_elevation.hip)
+void lv_default_elevation_params(lv_elevation_params* p) {
+    if (!p) return;
+    *p = lv_elevation_params{};
+    p->origin[0] = -51.2f;
+    p->origin[1] = -51.2f;
+    p->origin[2] = -3.2f;
+    p->resolution = 0.2f;
+    p->nx = 512;
+    p->ny = 512;
+    p->min_points = 3;
+    p->head = 1920;        // 1.5 m: floor(m / resolution * 256)
+    p->max_span = 153;     // 0.12 m
+    p->max_step = 128;     // 0.10 m
+    p->max_slope2 = 34727; // floor((512 tan 20 deg)^2)
+}
+
+#define LV_ELEV_BUILT(c) LV_REQUIRE((c)->elev.built, LV_ESTATE, "no elevation map: call lv_elev_build first")
+
+// (the arguments are judged before the context, as lv_occ_raycast's are).  The map source is read as lv_map_paint reads it:
+// the insert in flight settled, a finished background rebuild adopted, then the active store.
+int lv_elev_build(lv_ctx* c, const lv_elevation_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (const char* why = elev_check_params(p)) { set_error("lv_elev_build: %s", why); return LV_EINVAL; }
+    if (pts && stride < 12) { set_error("lv_elev_build: bad point array (stride %zu)", stride); return LV_EINVAL; }
+    if (pts && n >= ELEV_MAX_N) { set_error("lv_elev_build: too many points"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    if (!pts) {
+        LV_SETTLE_MAP(c);
+        LV_RELIN_POLL(c);
+        const bool any = c->map.built && c->map.m > 0;
+        return c->elev.build(c->stream, *p, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, any ? c->map.m : 0u, nullptr, 0, 0, stats);
+    }
+    return c->elev.build(c->stream, *p, nullptr, 0, 0, pts, stride, n, stats);
+}
+
+int lv_elev_fetch(lv_ctx* c, int layer, void* out, size_t capacity) {
+    if (!elev_layer_size(layer)) { set_error("lv_elev_fetch: layer %d: LV_ELEV_LO .. LV_ELEV_HEIGHT", layer); return LV_EINVAL; }
+    if (!out) { set_error("lv_elev_fetch: null output"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_ELEV_BUILT(c);
+    if (capacity < c->elev.n_cells) { set_error("lv_elev_fetch: room for nx * ny = %zu values needed", c->elev.n_cells); return LV_EINVAL; }
+    return c->elev.fetch(c->stream, layer, out);
+}
+
+int lv_elev_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* height, int8_t* cls) {
+    if (!height && !cls) { set_error("lv_elev_query: height and cls are both null"); return LV_EINVAL; }
+    if (n && (!pts || stride < 12)) { set_error("lv_elev_query: bad point array (stride %zu)", stride); return LV_EINVAL; }
+    if (n >= ELEV_MAX_N) { set_error("lv_elev_query: too many points"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_ELEV_BUILT(c);
+    return c->elev.query(c->stream, pts, stride, n, height, cls);
+}
+
+int lv_elev_info(lv_ctx* c, lv_elevation_info* out) {
+    if (!out) { set_error("lv_elev_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *out = lv_elevation_info{};
+    if (!c->elev.built) return LV_OK;
+    out->built = 1;
+    out->nx = c->elev.grid.nx;
+    out->ny = c->elev.grid.ny;
+    out->from_map = c->elev.from_map;
+    out->n_points = c->elev.n_points;
+    out->params = c->elev.prm;
+    return LV_OK;
+}
+
+int lv_elev_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->elev.release();
+    return LV_OK;
+}
+
+// The planar distance field over the caller's cells ("Elevation map": distance from cells); everything but the source of the
+// obstacles is lv_occ_distance_build's
+int lv_occ_distance_build_cells(lv_ctx* c, const lv_distance_params* p, const int8_t* cells, size_t n, uint64_t stats[4]) {
+    if (const char* why = dist_check_params_cells(p, cells)) { set_error("lv_occ_distance_build_cells: %s", why); return LV_EINVAL; }
+    LV_OCC_CTX(c);
+    const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
+    if (n != plane) { set_error("lv_occ_distance_build_cells: %zu cells for a plane of nx * ny = %zu", n, plane); return LV_EINVAL; }
+    occ_field_changed(c);
+    return c->dist.build(c->stream, c->occ, *p, cells, stats);
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 // one contiguous run of a row:
 //   dist_classify_kernel  one wavefront per 64 consecutive x of a row: the obstacle test per lane (the planar field projects its
 //                         band of layers: grid_project_column), one __ballot, two words of the one-bit-per-voxel bitmap (the occupancy bitmaps' layout).
+//                         dist_classify_cells_kernel is the same over the caller's plane of cells (lv_occ_distance_build_cells): it
+//                         writes the same bitmap, and everything after it is shared.
 //   dist_x_kernel         one lane per voxel: the nearest set bit of its row (the nearest clear one for an obstacle of a signed
 //                         field) by clz / ctz over the row's at most 32 words, which sit in L2.  Writes +-dx^2, +-FAR or 0.
 //   dist_y_kernel         one lane per voxel: dist_pass_line along y (stride nx).  The wavefront's neighbours in x read the
@@ -47,6 +49,26 @@ __global__ __launch_bounds__(256) void dist_classify_kernel(const float* __restr
     const unsigned long long m = __ballot(ob);
     const uint32_t word = seg * 2u + (lane >> 5);
     if ((lane & 31u) == 0 && word < (uint32_t)g.wx) bits[(size_t)row * (size_t)g.wx + word] = (uint32_t)(m >> (lane & 32u));
+}
+
+// the wavefront's ballot into its two words of the bitmap
+__device__ __forceinline__ void dist_store_ballot(bool ob, const DistGrid& g, uint32_t row, uint32_t seg, uint32_t lane, uint32_t* __restrict__ bits) {
+    const unsigned long long m = __ballot(ob);
+    const uint32_t word = seg * 2u + (lane >> 5);
+    if ((lane & 31u) == 0 && word < (uint32_t)g.wx) bits[(size_t)row * (size_t)g.wx + word] = (uint32_t)(m >> (lane & 32u));
+}
+
+// n_waves = ny * ceil(nx / 64); cells: the caller's plane, index j * nx + i
+__global__ __launch_bounds__(256) void dist_classify_cells_kernel(const int8_t* __restrict__ cells, DistGrid g, int unknown, uint32_t n_waves,
+                                                                  uint32_t* __restrict__ bits) {
+    const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (wave >= n_waves) return;   // (whole wavefronts leave together)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t per_row = ((uint32_t)g.nx + 63u) / 64u;
+    const uint32_t row = wave / per_row, seg = wave - row * per_row;
+    const uint32_t i = seg * 64u + lane;
+    const bool ob = i < (uint32_t)g.nx && dist_obstacle_cell(cells[(size_t)row * (size_t)g.nx + i], unknown != 0);
+    dist_store_ballot(ob, g, row, seg, lane, bits);
 }
 
 __global__ __launch_bounds__(256) void dist_x_kernel(const uint32_t* __restrict__ bits, DistGrid g, uint32_t n, int32_t* __restrict__ out) {
@@ -126,11 +148,11 @@ __global__ __launch_bounds__(256) void dist_query_kernel(const int32_t* __restri
 }  // namespace
 
 void DistStore::release() {
-    d_s2.release(); d_tmp.release(); d_bits.release(); d_part.release(); stats.release(); pts.release(); d_out.release();
+    d_s2.release(); d_tmp.release(); d_bits.release(); d_part.release(); stats.release(); pts.release(); d_out.release(); d_cells.release();
     *this = DistStore();
 }
 
-int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t out[4]) {
+int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, const int8_t* cells, uint64_t out[4]) {
     const DistGrid g = dist_grid_of(occ.grid, p);
     const size_t nv = grid_cells(g);
     const size_t nw = (size_t)g.wx * (size_t)g.ny * (size_t)g.nz;
@@ -141,13 +163,21 @@ int DistStore::build(hipStream_t stream, const OccStore& occ, const lv_distance_
     if (!rc) rc = d_bits.need(nw);
     if (!rc) rc = d_part.need((size_t)blocks_of(nv) * 4);
     if (!rc) rc = stats.need();
+    if (!rc && cells) rc = d_cells.need(nv);
     if (rc) return rc;
     int k0, k1;
     grid_clip_band(p.k_lo, p.k_hi, occ.grid.nz, k0, k1);
     const size_t rows = (size_t)g.ny * (size_t)g.nz;
     const uint32_t n_waves = (uint32_t)(rows * (((size_t)g.nx + 63) / 64));
-    hipLaunchKernelGGL(dist_classify_kernel, dim3((n_waves + 3) / 4), dim3(256), 0, stream, occ.d_L, g, p.planar != 0, k0, k1, occ.prm.l_occ,
-                       occ.prm.l_free, p.unknown_is_obstacle != 0, n_waves, d_bits);
+    if (cells) {
+        // (from the caller's pageable memory: the copy has left it when the call returns, which the read of the stats waits for)
+        LV_HIP(hipMemcpyAsync(d_cells.p, cells, nv, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(dist_classify_cells_kernel, dim3((n_waves + 3) / 4), dim3(256), 0, stream, d_cells.p, g, p.unknown_is_obstacle != 0,
+                           n_waves, d_bits);
+    } else {
+        hipLaunchKernelGGL(dist_classify_kernel, dim3((n_waves + 3) / 4), dim3(256), 0, stream, occ.d_L, g, p.planar != 0, k0, k1, occ.prm.l_occ,
+                           occ.prm.l_free, p.unknown_is_obstacle != 0, n_waves, d_bits);
+    }
     hipLaunchKernelGGL(dist_x_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_bits, g, (uint32_t)nv, d_s2);
     hipLaunchKernelGGL(dist_y_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_s2, g, (uint32_t)nv, d_tmp);
     hipLaunchKernelGGL(dist_z_kernel, dim3(blocks_of(nv)), dim3(256), 0, stream, d_tmp, g, p.max_cells, (uint32_t)nv, d_s2, d_part);

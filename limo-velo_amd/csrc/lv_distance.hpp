@@ -37,6 +37,9 @@ LV_OCC_HD bool dist_obstacle_planar(const float* L, size_t plane, size_t c, int 
     return v == 100 || (unknown_is_obstacle && v == -1);
 }
 
+// planar field over the caller's cells (lv_occ_distance_build_cells): the value is 100, or negative when unknown counts
+LV_OCC_HD bool dist_obstacle_cell(int v, bool unknown_is_obstacle) { return v == 100 || (unknown_is_obstacle && v < 0); }
+
 // word w of a bitmap row; inv: the complement, without the bits past nx
 LV_OCC_HD uint32_t dist_word(const uint32_t* row, int wx, int nx, int w, bool inv) {
     uint32_t v = row[w];
@@ -163,6 +166,15 @@ inline const char* dist_check_params(const lv_distance_params* p) {
     return nullptr;
 }
 
+// The same for lv_occ_distance_build_cells: a planar field, whose layers are not used
+inline const char* dist_check_params_cells(const lv_distance_params* p, const int8_t* cells) {
+    if (!p) return "null params";
+    if (p->max_cells < 0 || p->max_cells > DIST_MAX_CELLS) return "max_cells: 0 (no truncation) or 1..1024";
+    if (!p->planar) return "planar: a field over cells is planar (planar != 0)";
+    if (!cells) return "null cells";
+    return nullptr;
+}
+
 inline DistGrid dist_grid_of(const OccGrid& o, const lv_distance_params& p) {
     DistGrid g{};
     g.nx = o.nx;
@@ -190,8 +202,10 @@ struct DistStore {
     Counters4 stats;
     PointStage pts;                  // the query points
     DevBuf<float> d_out;             // per point dist, then grad[3]
+    DevBuf<int8_t> d_cells;          // lv_occ_distance_build_cells: the caller's cells (not allocated before the first such build)
 
-    int build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, uint64_t out[4]);
+    // cells: NULL (the obstacles come from the grid), or nx * ny values of the plane (p.planar != 0)
+    int build(hipStream_t stream, const OccStore& occ, const lv_distance_params& p, const int8_t* cells, uint64_t out[4]);
     int fetch(hipStream_t stream, int32_t* s2, float* metres);
     int query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* dist, float* grad);
     void release();
