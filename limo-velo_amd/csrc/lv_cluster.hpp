@@ -102,15 +102,9 @@ LV_CL_HD bool cl_removed(uint32_t size, uint32_t min_size, uint32_t max_size, bo
 
 #if !defined(LV_CLUSTER_HOST_ONLY)
 #include "lv_host.hpp"
+#include "lv_rules.hpp"   // ClusterRule
 
 namespace lv {
-
-// The resolved rule of one call, as the kernels take it
-struct ClusterRule {
-    float radius;
-    uint32_t min_size, max_size;
-    int seeded;   // lv_map_remove_clusters: 1 with seeds (object growth), 0 without (debris)
-};
 
 // The buffers of lv_map_cluster / lv_map_remove_clusters (grown on demand, kept)
 struct ClusterStore {

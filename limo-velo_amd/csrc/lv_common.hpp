@@ -1,6 +1,7 @@
 // lv_common.hpp — host declarations shared by lv_host.hpp, lv_rebuild.hpp, lv_filter.hpp, lv_exchange.hpp and lv_buffers.hpp (the
 // last four must build without lv_host.hpp: their host tests compile them against a HIP stand-in, tests/emu/hip/hip_runtime.h; so
-// do lv_occupancy.hpp, lv_distance.hpp and lv_plan.hpp, which include lv_buffers.hpp).  set_error keeps the message lv_last_error returns
+// do lv_occupancy.hpp, lv_distance.hpp and lv_plan.hpp, which include lv_buffers.hpp; lv_rules.hpp needs no HIP header at all and
+// declares set_error itself).  set_error keeps the message lv_last_error returns
 // (include/limovelo_hip.h), LV_HIP turns a failed HIP call into LV_EHIP.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,15 +2,10 @@
 // (include/limovelo_hip.h "Place recognition"; kernels and host side in lv_place.hip).
 #pragma once
 #include "lv_host.hpp"
+#include "lv_rules.hpp"   // PLACE_MAX_*
 
 namespace lv {
 
-constexpr int PLACE_MAX_RINGS = 32;
-constexpr int PLACE_MAX_SECTORS = 64;                       // one lane per shift in the scoring wavefront
-constexpr int PLACE_MAX_BINS = PLACE_MAX_RINGS * PLACE_MAX_SECTORS;
-constexpr size_t PLACE_MAX_COUNT = (size_t)1 << 20;         // ids fit the 20 bits of the retrieval key
-constexpr size_t PLACE_MAX_MAP_CENTRES = 65536;             // per lv_place_add_map call
-constexpr int PLACE_MAX_K = 64;
 constexpr int PLACE_TOPK_CHUNK = 4096;                      // keys per workgroup of the top-k selection (256 lanes x 16)
 
 // The rule as the kernels take it: ring_w = (rmax - rmin) / n_rings and sector_w = 2 pi / n_sectors in f32

@@ -133,23 +133,9 @@ LV_SURF_HD void surf_normal(double c0, double c1, double c2, double c3, double c
 
 #if !defined(LV_SURFACE_HOST_ONLY)
 #include "lv_host.hpp"
+#include "lv_rules.hpp"   // SURF_MAX_K, SurfRule
 
 namespace lv {
-
-constexpr int SURF_MAX_K = 32;
-
-// The resolved rule of one call, as the kernels take it
-struct SurfRule {
-    int job;               // 0: normals (covariance + mean distance), 1: statistical outliers (mean distance), 2: radius outliers (count)
-    int k;                 // jobs 0, 1: neighbours searched, the point itself included (job 1: the caller's k + 1); job 2: unused, 0
-    int min_neighbours;
-    int orient;
-    float max_dist;        // jobs 0, 1; job 2: the radius
-    float std_mul;         // job 1
-    double viewpoint[3];
-    double threshold;      // jobs 1, 2: what a point's value is judged against
-    int fixed_threshold;   // job 1: threshold is given (a replay), not computed from the store's own statistics
-};
 
 // The buffers of lv_map_normals / lv_map_remove_outliers (grown on demand, kept)
 struct SurfaceStore {

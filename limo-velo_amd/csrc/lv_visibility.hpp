@@ -2,21 +2,9 @@
 // removal"; kernels and host side in lv_visibility.hip).
 #pragma once
 #include "lv_host.hpp"
+#include "lv_rules.hpp"   // VIS_MAX_*, VisRule
 
 namespace lv {
-
-constexpr int VIS_MAX_VIEWS = 32;
-constexpr size_t VIS_MAX_PIXELS = (size_t)1 << 20;   // width * height of one view's image
-constexpr int VIS_MAX_WINDOW = 8;
-
-// The rule of one call, as the kernels take it (angles in radians, the bin scales precomputed on the host)
-struct VisRule {
-    int width, height, n_views, window, min_hits;
-    float inv_col;      // width / (2 pi): columns per radian of azimuth
-    float v_min;        // lowest elevation (rad)
-    float inv_row;      // height / (v_max - v_min): rows per radian of elevation
-    float min_range, max_range, margin_abs, margin_rel;
-};
 
 // Bytes of the device blob a call classifies against: the views' poses (12 floats each: R row-major, t), padded to 256 B, then
 // the n_views window-min images (height x width f32 each).  The background rebuild journals exactly this blob.
