@@ -854,6 +854,75 @@ int  lv_elev_clear(lv_ctx* ctx);
 /* cells: n = nx * ny values of the occupancy grid's plane; stats as lv_occ_distance_build's. */
 int  lv_occ_distance_build_cells(lv_ctx* ctx, const lv_distance_params* p, const int8_t* cells, size_t n, uint64_t stats[4]);
 
+/* ---- Rollouts ----------------------------------------------------------------------------------------
+ * The local planner of move_base / nav2 on the device: K candidate control sequences are rolled forward through a unicycle model
+ * from one start pose, the ones that collide are cut short, and the rest are scored against the plan (base_local_planner's
+ * trajectory rollout, dwa_local_planner, the MPPI controller of nav2; the reference has no counterpart).  Every f32 operation and
+ * its order are stated below and the sine and cosine are one fixed polynomial, so a rollout is exactly defined: a pure function
+ * of the plan, the field and the arguments, the same bits whatever the schedule.
+ *   reads    the plan last built: its cost bytes c and its potential P, with the plan's own origin and resolution.  It must be
+ *            planar (LV_ESTATE otherwise).  With n_fp > 0 the distance field last built is read too; its planar, nx, ny must
+ *            equal the plan's (LV_ESTATE otherwise).  A stale plan or field is used as it is.  Nothing is snapshotted, and no bit
+ *            of the grid, the field, the plan or the frontier result changes, nor any stale flag.
+ *   inputs   start = (x0, y0, th0), world metres and radians; K sequences of Tc pairs (v, w), m/s and rad/s, laid out
+ *            [K][Tc][2]; T steps of dt seconds, step s = 1..T using pair min(s - 1, Tc - 1) (Tc = 1: one constant command, as
+ *            DWA samples them; Tc = T: a full sequence, as MPPI does); n_fp footprint points (fx, fy) in the body frame, laid out
+ *            [n_fp][2].  Nothing here needs to be finite: what a non-finite value leads to is stated under "pose test".
+ *   motion   all in f32, no operation fused, in exactly this order.  A heading th is USABLE iff fabsf(th) < 1048576.0f (NaN is
+ *            not).  (sn, cs) = the sine and cosine of th_(s-1) by the library's fixed polynomial (f32 -> f64, k = rint(x * 2 / pi),
+ *            a three-term Cody-Waite reduction, two six-term polynomials in r^2, the quadrant from (int) k & 3, rounded to f32:
+ *            the bound above is the one under which (int) k is defined); d = v * dt; x_s = x_(s-1) + d * cs;
+ *            y_s = y_(s-1) + d * sn; th_s = th_(s-1) + w * dt.  A step may jump over a cell: keep |v| * dt at or below the
+ *            resolution; there is no sub-stepping.
+ *   pose test  for s = 1..T pose s is BAD for the first of these reasons that applies, and good otherwise.  1: th_(s-1) is not
+ *            usable (before the step; it counts against pose s).  2: th_s is not usable.  3: (x_s, y_s) has no cell in the plan
+ *            (quantised as lv_occ_plan_paths quantises a start; non-finite coordinates end here).  4: the cell's cost byte is 0.
+ *            5: a footprint point has no cell in the field.  6: a footprint point's s2 < fp_clear_s2.  Footprint point g of
+ *            pose s is (x_s + (cs' * fx - sn' * fy), y_s + (sn' * fx + cs' * fy)) with (sn', cs') the sine and cosine of th_s, the
+ *            very values step s + 1 uses; every point is judged for reason 5 before any for reason 6.  Pose 0 is not examined:
+ *            a robot standing in an inflated cell can still leave it.  n_ok = the number of good poses before the first bad one.
+ *   result   per sequence.  status LV_ROLLOUT_CLEAR iff n_ok = T, else LV_ROLLOUT_STOPPED; steps = n_ok; why = 0 when clear,
+ *            else the reason that made pose n_ok + 1 bad; cell_end = the plan's linear index of pose n_ok's cell, -1 if it has
+ *            none (possible only for n_ok = 0); p_end = P there, LV_PLAN_UNREACHED without a cell; p_min = the least P over
+ *            the poses 0..n_ok that have a cell and s_min the first step that attains it (LV_PLAN_UNREACHED and -1 if none has
+ *            one); cost_sum = the sum of the cost bytes of poses 1..n_ok.
+ *   poses    K x (T + 1) x 3 floats (x, y, th): rows 0..n_ok of a sequence are its poses, every float of a later row is the bit
+ *            pattern 0x7FC00000.
+ *   score    p_sel = p_end with goal_mode 0, p_min with goal_mode 1.  A sequence is ELIGIBLE iff steps >= min_steps and
+ *            p_sel != LV_PLAN_UNREACHED; its score is w_cost * cost_sum + w_goal * p_sel + w_stop * (T - steps) in uint64 (below
+ *            2^50: the weights are at most 65535); the score of any other is UINT64_MAX.
+ *   best     best[0] = the eligible index with the least (score, index), best[1] = its score; both -1 if none is eligible.
+ *   limits   T 1..1024; Tc 1..T; dt finite and > 0; n_fp 0..64, footprint non-NULL when n_fp > 0; fp_clear_s2 1..3 * 1023^2;
+ *            min_steps 0..T; goal_mode 0 or 1; weights 0..65535; K 0..2^20, controls non-NULL when K > 0; start non-NULL;
+ *            results, poses, score and best may each be NULL, but not all four.  K * Tc <= 2^24 pairs (128 MiB of controls,
+ *            pinned on the host and again on the device), and with poses K * (T + 1) <= 2^24 rows (192 MiB).  K = 0 succeeds
+ *            and writes best only; like every other call it is answered after the states below (LV_ESTATE comes first).
+ * Parameters and NULL arguments are judged before the context (LV_EINVAL, nothing written; "null context" comes last);
+ * LV_ESTATE before lv_occ_configure, before a plan build, and as stated under "reads".  A refused call writes nothing.  Nothing
+ * is allocated before the first call; lv_occ_configure and lv_destroy free everything.  The call runs on the context's stream
+ * and returns when its host outputs are written. */
+#define LV_ROLLOUT_CLEAR   1
+#define LV_ROLLOUT_STOPPED 2
+typedef struct lv_rollout_params {
+    int T, Tc;
+    float dt;
+    int fp_clear_s2;
+    uint32_t w_cost, w_goal, w_stop;
+    int min_steps, goal_mode;
+} lv_rollout_params;
+typedef struct lv_rollout_result {            /* 32 bytes */
+    int32_t status, steps, why, cell_end;
+    uint32_t p_end, p_min;
+    int32_t s_min;
+    uint32_t cost_sum;
+} lv_rollout_result;
+/* T 32, Tc 1, dt 0.1, fp_clear_s2 1, w_cost 1, w_goal 1, w_stop 0, min_steps 1, goal_mode 0. */
+void lv_default_rollout_params(lv_rollout_params* p);
+/* start: 3 floats; controls: K x Tc x 2 floats; footprint: n_fp x 2 floats; results: K records; poses: K x (T + 1) x 3 floats;
+ * score: K values; best: 2 values. */
+int  lv_occ_rollout(lv_ctx* ctx, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint,
+                    size_t n_fp, lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

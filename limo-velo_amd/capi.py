@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "lv_default_ray_params", "lv_occ_raycast", "lv_occ_view_gain",
     "lv_default_elevation_params", "lv_elev_build", "lv_elev_fetch", "lv_elev_query", "lv_elev_info", "lv_elev_clear",
     "lv_occ_distance_build_cells",
+    "lv_default_rollout_params", "lv_occ_rollout",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -298,6 +299,28 @@ ELEVATION_ARGTYPES = {
     "lv_occ_distance_build_cells": [C.c_void_p, C.POINTER(DistanceParams), C.POINTER(C.c_int8), C.c_size_t, C.POINTER(C.c_uint64)],
 }
 
+LV_ROLLOUT_CLEAR, LV_ROLLOUT_STOPPED = 1, 2
+
+
+class RolloutParams(C.Structure):  # lv_rollout_params
+    _fields_ = [("T", C.c_int), ("Tc", C.c_int), ("dt", C.c_float), ("fp_clear_s2", C.c_int), ("w_cost", C.c_uint32), ("w_goal", C.c_uint32),
+                ("w_stop", C.c_uint32), ("min_steps", C.c_int), ("goal_mode", C.c_int)]
+
+
+class RolloutResult(C.Structure):  # lv_rollout_result (32 bytes)
+    _fields_ = [("status", C.c_int32), ("steps", C.c_int32), ("why", C.c_int32), ("cell_end", C.c_int32), ("p_end", C.c_uint32),
+                ("p_min", C.c_uint32), ("s_min", C.c_int32), ("cost_sum", C.c_uint32)]
+
+
+# the same record as a numpy dtype (Context.occ_rollout)
+ROLLOUT_RESULT_DTYPE = np.dtype([(f, np.uint32 if t is C.c_uint32 else np.int32) for f, t in RolloutResult._fields_])
+
+# ctypes signatures of the rollouts (include/limovelo_hip.h "Rollouts"; tests/test_occ_rollout_abi.py)
+ROLLOUT_ARGTYPES = {
+    "lv_occ_rollout": [C.c_void_p, C.POINTER(RolloutParams), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float),
+                       C.c_size_t, C.POINTER(RolloutResult), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+}
+
 
 def camera_view(frame):
     """(LvCameraView, image array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, image
@@ -526,9 +549,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_ray_params.argtypes = [C.POINTER(RayParams)]
         lib.lv_default_elevation_params.restype = None
         lib.lv_default_elevation_params.argtypes = [C.POINTER(ElevationParams)]
+        lib.lv_default_rollout_params.restype = None
+        lib.lv_default_rollout_params.argtypes = [C.POINTER(RolloutParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -649,6 +674,14 @@ def default_elevation_params(**kw) -> ElevationParams:
             p.origin[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_rollout_params(**kw) -> RolloutParams:
+    p = RolloutParams()
+    load_library().lv_default_rollout_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -1167,6 +1200,41 @@ class Context:
         self._check(self.lib.lv_occ_distance_build_cells(self.h, C.byref(p), a.ctypes.data_as(C.POINTER(C.c_int8)), C.c_size_t(a.size),
                                                          stats.ctypes.data_as(C.POINTER(C.c_uint64))))
         return stats
+
+    # --- rollouts (include/limovelo_hip.h "Rollouts")
+    def occ_rollout(self, start, controls, params: RolloutParams | None = None, footprint=None, want=("results", "best")) -> dict:
+        """lv_occ_rollout of the control sequences controls [K, Tc, 2] (v, w) from the pose start (x, y, th); params.Tc is set from
+        the array.  footprint: [n_fp, 2] body-frame points or None.  want: which of "results" ([K] ROLLOUT_RESULT_DTYPE), "poses"
+        ([K, T + 1, 3] f32), "score" ([K] uint64) and "best" ([2] int64: index, score; -1, -1 if none) to fetch; returns them in a
+        dict."""
+        src = params if params is not None else default_rollout_params()
+        p = RolloutParams.from_buffer_copy(src)
+        u = np.ascontiguousarray(controls, np.float32)
+        if u.ndim != 3 or u.shape[2] != 2:
+            raise ValueError("occ_rollout: controls [K, Tc, 2]")
+        K = u.shape[0]
+        if K:
+            p.Tc = u.shape[1]
+        s0 = np.ascontiguousarray(start, np.float32).reshape(3)
+        fp = np.zeros((0, 2), np.float32) if footprint is None else np.ascontiguousarray(footprint, np.float32).reshape(-1, 2)
+        out = {}
+        if "results" in want:
+            out["results"] = np.zeros(K, ROLLOUT_RESULT_DTYPE)
+        if "poses" in want:
+            out["poses"] = np.zeros((K, p.T + 1, 3), np.float32)
+        if "score" in want:
+            out["score"] = np.zeros(K, np.uint64)
+        if "best" in want:
+            out["best"] = np.zeros(2, np.int64)
+
+        def ptr(name, t):
+            return out[name].ctypes.data_as(C.POINTER(t)) if name in out else None
+
+        fptr = C.POINTER(C.c_float)
+        self._check(self.lib.lv_occ_rollout(self.h, C.byref(p), s0.ctypes.data_as(fptr), u.ctypes.data_as(fptr) if K else None, C.c_size_t(K),
+                                            fp.ctypes.data_as(fptr) if len(fp) else None, C.c_size_t(len(fp)), ptr("results", RolloutResult),
+                                            ptr("poses", C.c_float), ptr("score", C.c_uint64), ptr("best", C.c_int64)))
+        return out
 
     def occ_view_gain(self, views) -> np.ndarray:
         """lv_occ_view_gain over views = [(R [3, 3], t [3], pattern end points [n, 3] sensor frame)] (1..32 of them); returns

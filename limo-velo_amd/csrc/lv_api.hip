@@ -18,6 +18,7 @@
 #include "lv_frontier.hpp"
 #include "lv_ray.hpp"
 #include "lv_elevation.hpp"
+#include "lv_rollout.hpp"
 #include "lv_occupancy.hpp"
 
 #include <chrono>
@@ -59,6 +60,7 @@ struct lv_ctx {
     FrontierStore frontier;   // lv_occ_frontier_*: the frontier clusters of that grid (lv_frontier.hip); nothing allocated before the first build
     RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
+    RolloutStore rollout;   // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -646,6 +648,7 @@ void lv_destroy(lv_ctx* c) {
     c->cluster.release();
     c->place.release();
     c->ray.release();
+    c->rollout.release();
     c->elev.release();
     c->frontier.release();
     c->plan.release();
@@ -2230,6 +2233,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     c->plan.release();   // (and the plan to the field)
     c->frontier.release();   // (the frontier to the grid too)
     c->ray.release();        // (and the packed states)
+    c->rollout.release();    // (and the rollouts' buffers)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2559,6 +2563,44 @@ int lv_occ_distance_build_cells(lv_ctx* c, const lv_distance_params* p, const in
     if (n != plane) { set_error("lv_occ_distance_build_cells: %zu cells for a plane of nx * ny = %zu", n, plane); return LV_EINVAL; }
     occ_field_changed(c);
     return c->dist.build(c->stream, c->occ, *p, cells, stats);
+}
+
+// ---- Rollouts (lv_rollout.hip)
+void lv_default_rollout_params(lv_rollout_params* p) {
+    if (!p) return;
+    *p = lv_rollout_params{};
+    p->T = 32;
+    p->Tc = 1;
+    p->dt = 0.1f;
+    p->fp_clear_s2 = 1;
+    p->w_cost = 1;
+    p->w_goal = 1;
+    p->w_stop = 0;
+    p->min_steps = 1;
+    p->goal_mode = 0;
+}
+
+// (the arguments are judged before the context, as lv_occ_plan_build's are)
+int lv_occ_rollout(lv_ctx* c, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint, size_t n_fp,
+                   lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best) {
+    if (const char* why = rollout_check(p, start, controls, K, footprint, n_fp, results, poses, score, best)) {
+        set_error("lv_occ_rollout: %s", why);
+        return LV_EINVAL;
+    }
+    LV_OCC_CTX(c);
+    LV_PLAN_BUILT(c);
+    const PlanGrid& g = c->plan.grid;
+    if (!g.planar) { set_error("lv_occ_rollout: the plan is 3-D: rollouts run on a planar plan"); return LV_ESTATE; }
+    if (n_fp) {
+        LV_DIST_BUILT(c);
+        const DistGrid& f = c->dist.grid;
+        if (!c->dist.prm.planar || f.nx != g.nx || f.ny != g.ny) {
+            set_error("lv_occ_rollout: the distance field (%d x %d, planar %d) is not of the plan's cells (%d x %d, planar)", f.nx, f.ny,
+                      c->dist.prm.planar, g.nx, g.ny);
+            return LV_ESTATE;
+        }
+    }
+    return c->rollout.run(c->stream, c->plan, c->dist, *p, start, controls, K, footprint, n_fp, results, poses, score, best);
 }
 
 }  // extern "C"

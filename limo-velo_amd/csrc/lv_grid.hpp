@@ -140,10 +140,19 @@ struct HaloTile {
 #ifdef __HIPCC__
 
 // ---- wavefront folds: every lane of the wavefront calls them, every lane gets the result
+// over the aligned groups of G lanes (a power of two, 1..64): every lane gets its own group's result
+template <int G, class T, class Op>
+__device__ __forceinline__ T group_fold(T v, Op op) {
+    for (int o = G / 2; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+    return v;
+}
+template <int G, class T>
+__device__ __forceinline__ T group_min(T v) {
+    return group_fold<G>(v, [](T a, T b) { return b < a ? b : a; });
+}
 template <class T, class Op>
 __device__ __forceinline__ T wave_fold(T v, Op op) {
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-    return v;
+    return group_fold<64>(v, op);
 }
 template <class T>
 __device__ __forceinline__ T wave_sum(T v) {
