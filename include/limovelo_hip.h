@@ -923,6 +923,95 @@ void lv_default_rollout_params(lv_rollout_params* p);
 int  lv_occ_rollout(lv_ctx* ctx, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint,
                     size_t n_fp, lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best);
 
+/* ---- TSDF and mesh -------------------------------------------------------------------------------------
+ * A truncated signed distance field fused from the sweeps, and a triangle mesh of its zero surface: the TSDF layer of Voxblox
+ * and nvblox with its mesh integrator ("a mesh of what the robot saw"; the reference has no counterpart).  The sweeps are the
+ * lv_view of "Occupancy grid".  The volume is a grid of its own, held by the context, independent of the occupancy grid and of
+ * the map.  Like every map product here the rule is integer arithmetic after one quantisation step: a pure function of the
+ * inputs, bitwise reproducible, independent of scheduling.
+ *   grid     origin, resolution, nx, ny, nz, min_range, max_range with the limits, the indexing (x fastest) and the quantisation
+ *            (Q = 256 sub-units per voxel) of "Occupancy grid".  trunc_cells 1..16, T = trunc_cells * 256 sub-units; max_weight
+ *            1..2^18; carve 0 or 1.  Each voxel holds two int32: a sum S and a weight W; W = 0 means never observed; always
+ *            |S| <= T * W.
+ *   returns  exactly those of "Occupancy grid": the view's origin qs (a view that gives no evidence there gives none here), the
+ *            ignored returns, the CUT returns, the unfused world transform and the quantised end point qe.
+ *   one ray  all in int64.  d = qe - qs, l2 = d . d (< 2^52), len = floor(sqrt(l2)) exactly (the f64 root corrected by integer
+ *            comparison).  len = 0: the ray gives nothing and is not counted.  Per axis ext_a = (d_a * T) / len by truncating
+ *            division (|ext_a| <= T), qb = qe + ext, qa = qe - ext.  A HIT return walks start -> qb by the walk of "Occupancy
+ *            grid", where start = qs if carve != 0 or len <= T, otherwise qa.  A CUT return gives nothing and is not counted
+ *            when carve = 0; with carve != 0 it walks qs -> qe and every cell takes s = T.
+ *            Every cell v the walk stands in, the first and the last included, has the centre c = 256 * v + 128 per axis and
+ *            s = floor((qe - c) . d / len) (floor division; always against the original qe and d).  s < -T: no contribution;
+ *            s > T: s = T.  Cells outside the grid are skipped.  The cell's contribution is (dS += s, dW += 1); the walk never
+ *            stands in a cell twice, so a ray contributes to a cell at most once.
+ *   one call  1..32 views carrying at most 2^24 returns together (LV_EINVAL beyond).  The contributions of all rays of all
+ *            views are summed per voxel, (dS, dW); integer sums commute, so neither the order of the returns nor how they are
+ *            split over the views of the call matters.  Then every voxel with dW > 0 folds: Wn = W + dW, Sn = S + dS; if
+ *            Wn > max_weight then S = floor(Sn * max_weight / Wn) (floor division; the product stays below 2^55) and
+ *            W = max_weight, otherwise S = Sn and W = Wn.
+ *   stats    rays used (the returns that walked: CUT ones only with carve), rays cut (those of them that were CUT),
+ *            contributions (the sum of dW), voxels touched (those with dW > 0).
+ *   metres   m = resolution * (((float)S / (float)W) / 256.0f), f32 and unfused; NaN where W = 0.  Positive between the sensor
+ *            and the surface, negative behind it.
+ *   mesh     naive surface nets, every step an integer.  A voxel is KNOWN iff W >= min_weight (the build's argument, >= 1) and
+ *            INSIDE iff S < 0.  Cell (i, j, k), 0 <= i <= nx - 2 and likewise in y and z, has the 8 voxel centres
+ *            (i..i+1, j..j+1, k..k+1) as corners; it is ACTIVE iff all 8 are known and they are not all of one sign.  A crossing
+ *            sits on a cell edge from voxel A to B = A + e_a whose ends differ in sign: num = S_A * W_B,
+ *            den = S_A * W_B - S_B * W_A, both negated if den < 0, t = (256 * num) / den (0..256); the crossing is A's centre
+ *            (256 * A + 128) plus t along axis a.  The vertex of an active cell is, per axis, the sum of its crossings'
+ *            coordinates divided by their count (1..12; every term is non-negative): int32[3] sub-units.  In metres
+ *            origin_a + resolution * ((float)v_a / 256.0f), f32 and unfused.  Vertices are numbered in the order of their cell's
+ *            linear index.
+ *            A face comes from a grid edge (p, a), from voxel p to p + e_a, whose ends are both known and differ in sign.  With
+ *            b = (a + 1) % 3 and c = (a + 2) % 3 the four cells round the edge are p offset in (b, c) by (-1, -1), (0, -1), (0, 0),
+ *            (-1, 0).  The edge gives a quad iff all four exist and are active (otherwise it is counted as refused); its
+ *            vertices q0..q3 are those cells' in that order if p is inside, q0, q3, q2, q1 if p is outside, so that normals point
+ *            from inside to outside, towards where the sensor was.  The quad is the triangles (q0, q1, q2) and (q0, q2, q3),
+ *            uint32 indices.  Faces are ordered by 3 * linear(p) + a.
+ * The mesh is a SNAPSHOT of the volume at build time, as the distance field is of its grid: lv_tsdf_integrate, lv_tsdf_load and
+ * lv_tsdf_clear leave it in place and set stale = 1; lv_tsdf_configure and lv_tsdf_mesh_clear free it; a new build replaces it.
+ * Every call below except lv_default_tsdf_params and lv_tsdf_configure gives LV_ESTATE before lv_tsdf_configure, and
+ * lv_tsdf_mesh_fetch also before a build (lv_tsdf_mesh_info reports built = 0 instead).  Arguments outside the limits give
+ * LV_EINVAL and change nothing; lv_tsdf_configure's parameters are judged before the context, as lv_occ_configure's are.  The
+ * calls run on the context's stream and return when their host outputs are written.  Nothing is allocated before
+ * lv_tsdf_configure; lv_destroy frees everything. */
+typedef struct lv_tsdf_params {
+    float origin[3]; float resolution; int nx, ny, nz;
+    float min_range, max_range;              /* 0 < min_range < max_range */
+    int trunc_cells;                         /* 1..16 */
+    int max_weight;                          /* 1..2^18 */
+    int carve;                               /* 0 or 1 */
+} lv_tsdf_params;
+typedef struct lv_mesh_info { int built, stale, min_weight, reserved; uint64_t vertices, triangles, active_cells, refused_edges; } lv_mesh_info;
+/* Defaults: the occupancy grid's footprint (0.2 m voxels, 512 x 512 x 64, origin -51.2, -51.2, -3.2, ranges 1..80 m),
+ * trunc_cells 3, max_weight 10000, carve 0. */
+void lv_default_tsdf_params(lv_tsdf_params* p);
+/* Allocates the volume, every voxel unobserved; reconfiguring discards the volume and its mesh. */
+int  lv_tsdf_configure(lv_ctx* ctx, const lv_tsdf_params* p);
+/* n_views 1..32, at most 2^24 returns in all.  stats (may be NULL) as above. */
+int  lv_tsdf_integrate(lv_ctx* ctx, const lv_view* views, size_t n_views, uint64_t stats[4]);
+/* metres and weight (either may be NULL, not both) of the voxel each world point falls in (quantised as lv_occ_query does);
+ * NaN and 0 outside the grid and for non-finite points. */
+int  lv_tsdf_query(lv_ctx* ctx, const void* pts, size_t stride, size_t n, float* metres, int32_t* weight);
+/* S, W, metres: nx * ny * nz values each (capacity below that: LV_EINVAL); any may be NULL, not all. */
+int  lv_tsdf_fetch(lv_ctx* ctx, int32_t* S, int32_t* W, float* metres, size_t capacity);
+/* Replaces the volume.  n must equal nx * ny * nz; every voxel 0 <= W <= max_weight and |S| <= T * W (LV_EINVAL otherwise,
+ * volume unchanged). */
+int  lv_tsdf_load(lv_ctx* ctx, const int32_t* S, const int32_t* W, size_t n);
+/* Every voxel back to unobserved. */
+int  lv_tsdf_clear(lv_ctx* ctx);
+int  lv_tsdf_get_params(lv_ctx* ctx, lv_tsdf_params* out);
+/* min_weight >= 1 (LV_EINVAL otherwise).  counts (may be NULL): vertices, triangles, active cells, edges refused for a missing
+ * cell.  A volume without a surface gives LV_OK and an empty mesh. */
+int  lv_tsdf_mesh_build(lv_ctx* ctx, int min_weight, uint64_t counts[4]);
+/* xyz: 3 floats per vertex (metres); sub: 3 int32 per vertex (sub-units); tri: 3 uint32 per triangle.  Any may be NULL, not all.
+ * cap_vertices below the vertex count with xyz or sub given, or cap_triangles below the triangle count with tri given: LV_EINVAL,
+ * nothing written. */
+int  lv_tsdf_mesh_fetch(lv_ctx* ctx, float* xyz, int32_t* sub, uint32_t* tri, size_t cap_vertices, size_t cap_triangles);
+int  lv_tsdf_mesh_info(lv_ctx* ctx, lv_mesh_info* out);
+/* Frees the mesh. */
+int  lv_tsdf_mesh_clear(lv_ctx* ctx);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

@@ -48,6 +48,8 @@ ABI_SYMBOLS = [
     "lv_default_elevation_params", "lv_elev_build", "lv_elev_fetch", "lv_elev_query", "lv_elev_info", "lv_elev_clear",
     "lv_occ_distance_build_cells",
     "lv_default_rollout_params", "lv_occ_rollout",
+    "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
+    "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -322,6 +324,32 @@ ROLLOUT_ARGTYPES = {
 }
 
 
+class TsdfParams(C.Structure):  # lv_tsdf_params
+    _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("min_range", C.c_float), ("max_range", C.c_float), ("trunc_cells", C.c_int), ("max_weight", C.c_int), ("carve", C.c_int)]
+
+
+class MeshInfo(C.Structure):  # lv_mesh_info
+    _fields_ = [("built", C.c_int), ("stale", C.c_int), ("min_weight", C.c_int), ("reserved", C.c_int), ("vertices", C.c_uint64),
+                ("triangles", C.c_uint64), ("active_cells", C.c_uint64), ("refused_edges", C.c_uint64)]
+
+
+# ctypes signatures of the TSDF and its mesh (include/limovelo_hip.h "TSDF and mesh"; tests/test_tsdf_abi.py)
+TSDF_ARGTYPES = {
+    "lv_tsdf_configure": [C.c_void_p, C.POINTER(TsdfParams)],
+    "lv_tsdf_integrate": [C.c_void_p, C.POINTER(View), C.c_size_t, C.POINTER(C.c_uint64)],
+    "lv_tsdf_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
+    "lv_tsdf_fetch": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_size_t],
+    "lv_tsdf_load": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_size_t],
+    "lv_tsdf_clear": [C.c_void_p],
+    "lv_tsdf_get_params": [C.c_void_p, C.POINTER(TsdfParams)],
+    "lv_tsdf_mesh_build": [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)],
+    "lv_tsdf_mesh_fetch": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_size_t, C.c_size_t],
+    "lv_tsdf_mesh_info": [C.c_void_p, C.POINTER(MeshInfo)],
+    "lv_tsdf_mesh_clear": [C.c_void_p],
+}
+
+
 def camera_view(frame):
     """(LvCameraView, image array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, image
     ([h, w, 3] or [h, w] uint8; rows may be strided), optional format (LV_IMAGE_*; default RGB8, MONO8 for a 2-D image) and dist
@@ -551,9 +579,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_elevation_params.argtypes = [C.POINTER(ElevationParams)]
         lib.lv_default_rollout_params.restype = None
         lib.lv_default_rollout_params.argtypes = [C.POINTER(RolloutParams)]
+        lib.lv_default_tsdf_params.restype = None
+        lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **TSDF_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -682,6 +712,17 @@ def default_rollout_params(**kw) -> RolloutParams:
     load_library().lv_default_rollout_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
+    return p
+
+
+def default_tsdf_params(**kw) -> TsdfParams:
+    p = TsdfParams()
+    load_library().lv_default_tsdf_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -1243,6 +1284,98 @@ class Context:
         gain = np.zeros((len(views), 4), np.uint64)
         self._check(self.lib.lv_occ_view_gain(self.h, arr, C.c_size_t(len(views)), gain.ctypes.data_as(C.POINTER(C.c_uint64))))
         return gain
+
+    # --- TSDF and mesh (include/limovelo_hip.h "TSDF and mesh")
+    def tsdf_configure(self, params: TsdfParams | None = None):
+        """lv_tsdf_configure: allocates the volume (default: lv_default_tsdf_params), every voxel unobserved."""
+        p = params if params is not None else default_tsdf_params()
+        self._check(self.lib.lv_tsdf_configure(self.h, C.byref(p)))
+
+    def tsdf_params(self) -> TsdfParams:
+        p = TsdfParams()
+        self._check(self.lib.lv_tsdf_get_params(self.h, C.byref(p)))
+        return p
+
+    def tsdf_integrate(self, views) -> np.ndarray:
+        """lv_tsdf_integrate over views = [(R [3, 3], t [3], points [n, 3] sensor frame)] (1..32 of them, one call); returns stats
+        [4] uint64: rays used, rays cut, contributions, voxels touched."""
+        arr, keep = view_array(views)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_tsdf_integrate(self.h, arr, C.c_size_t(len(views)), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def tsdf_query(self, pts):
+        """(metres [n] f32, weight [n] int32) of the voxel each world point falls in; NaN and 0 outside the grid."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        m = np.full(n, np.nan, np.float32)
+        w = np.zeros(n, np.int32)
+        self._check(self.lib.lv_tsdf_query(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                           m.ctypes.data_as(C.POINTER(C.c_float)), w.ctypes.data_as(C.POINTER(C.c_int32))))
+        return m, w
+
+    def tsdf_fetch(self, S=True, W=True, metres=False) -> dict:
+        """dict of the wanted arrays, [nz, ny, nx] each: S and W int32, metres f32 (NaN where W = 0)."""
+        p = self.tsdf_params()
+        shape = (p.nz, p.ny, p.nx)
+        out = {}
+        if S:
+            out["S"] = np.zeros(shape, np.int32)
+        if W:
+            out["W"] = np.zeros(shape, np.int32)
+        if metres:
+            out["metres"] = np.zeros(shape, np.float32)
+
+        def ptr(name, ct):
+            return out[name].ctypes.data_as(C.POINTER(ct)) if name in out else None
+
+        self._check(self.lib.lv_tsdf_fetch(self.h, ptr("S", C.c_int32), ptr("W", C.c_int32), ptr("metres", C.c_float),
+                                           C.c_size_t(p.nx * p.ny * p.nz)))
+        return out
+
+    def tsdf_load(self, S, W):
+        a = np.ascontiguousarray(S, np.int32)
+        b = np.ascontiguousarray(W, np.int32)
+        if a.size != b.size:
+            raise ValueError("tsdf_load: S and W of one size")
+        self._check(self.lib.lv_tsdf_load(self.h, a.ctypes.data_as(C.POINTER(C.c_int32)), b.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(a.size)))
+
+    def tsdf_clear(self):
+        self._check(self.lib.lv_tsdf_clear(self.h))
+
+    def tsdf_mesh_build(self, min_weight: int = 1) -> np.ndarray:
+        """lv_tsdf_mesh_build; returns counts [4] uint64: vertices, triangles, active cells, edges refused for a missing cell."""
+        counts = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_tsdf_mesh_build(self.h, int(min_weight), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return counts
+
+    def tsdf_mesh_info(self) -> MeshInfo:
+        out = MeshInfo()
+        self._check(self.lib.lv_tsdf_mesh_info(self.h, C.byref(out)))
+        return out
+
+    def tsdf_mesh_fetch(self, xyz=True, sub=True, tri=True) -> dict:
+        """dict of the wanted arrays of the mesh last built: xyz [V, 3] f32 metres, sub [V, 3] int32 sub-units, tri [F, 3] uint32."""
+        i = self.tsdf_mesh_info()
+        if not i.built:
+            raise LvError("limovelo_hip error -4: no mesh: call lv_tsdf_mesh_build first")   # (LV_ESTATE, as the library answers)
+        nv, nt = int(i.vertices), int(i.triangles)
+        out = {}
+        if xyz:
+            out["xyz"] = np.zeros((nv, 3), np.float32)
+        if sub:
+            out["sub"] = np.zeros((nv, 3), np.int32)
+        if tri:
+            out["tri"] = np.zeros((nt, 3), np.uint32)
+
+        def ptr(name, ct):
+            return out[name].ctypes.data_as(C.POINTER(ct)) if name in out else None
+
+        self._check(self.lib.lv_tsdf_mesh_fetch(self.h, ptr("xyz", C.c_float), ptr("sub", C.c_int32), ptr("tri", C.c_uint32), C.c_size_t(nv),
+                                                C.c_size_t(nt)))
+        return out
+
+    def tsdf_mesh_clear(self):
+        self._check(self.lib.lv_tsdf_mesh_clear(self.h))
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

@@ -20,6 +20,7 @@
 #include "lv_elevation.hpp"
 #include "lv_rollout.hpp"
 #include "lv_occupancy.hpp"
+#include "lv_tsdf.hpp"
 
 #include <chrono>
 
@@ -61,6 +62,7 @@ struct lv_ctx {
     RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     RolloutStore rollout;   // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
+    TsdfStore tsdf;     // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -654,6 +656,7 @@ void lv_destroy(lv_ctx* c) {
     c->plan.release();
     c->dist.release();
     c->occ.release();
+    c->tsdf.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -2601,6 +2604,128 @@ int lv_occ_rollout(lv_ctx* c, const lv_rollout_params* p, const float* start, co
         }
     }
     return c->rollout.run(c->stream, c->plan, c->dist, *p, start, controls, K, footprint, n_fp, results, poses, score, best);
+}
+
+// ---- TSDF and mesh (lv_tsdf.hip)
+void lv_default_tsdf_params(lv_tsdf_params* p) {
+    if (!p) return;
+    lv_occupancy_params o;
+    lv_default_occupancy_params(&o);   // (the occupancy grid's footprint)
+    *p = lv_tsdf_params{};
+    for (int a = 0; a < 3; ++a) p->origin[a] = o.origin[a];
+    p->resolution = o.resolution;
+    p->nx = o.nx;
+    p->ny = o.ny;
+    p->nz = o.nz;
+    p->min_range = o.min_range;
+    p->max_range = o.max_range;
+    p->trunc_cells = 3;
+    p->max_weight = 10000;
+    p->carve = 0;
+}
+
+#define LV_TSDF_CTX(c) \
+    LV_CHECK_CTX(c);   \
+    LV_REQUIRE((c)->tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first")
+
+// The mesh no longer shows the volume
+static void tsdf_changed(lv_ctx* c) {
+    if (c->tsdf.mesh.built) c->tsdf.mesh.stale = 1;
+}
+
+// (the parameters are judged before the context, as lv_occ_configure's are)
+int lv_tsdf_configure(lv_ctx* c, const lv_tsdf_params* p) {
+    if (const char* why = tsdf_check_params(p)) { set_error("lv_tsdf_configure: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->tsdf.configure(c->stream, *p);
+}
+
+int lv_tsdf_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) {
+    LV_TSDF_CTX(c);
+    if (!views) { set_error("lv_tsdf_integrate: null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("lv_tsdf_integrate: n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
+    if (int rc = views_ok(views, n_views, "lv_tsdf_integrate: ", false, TSDF_MAX_RETURNS)) return rc;   // (t is not judged: lv_rules.hpp)
+    tsdf_changed(c);
+    return c->tsdf.integrate(c->stream, views, n_views, stats);
+}
+
+int lv_tsdf_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* metres, int32_t* weight) {
+    LV_TSDF_CTX(c);
+    if (!metres && !weight) { set_error("lv_tsdf_query: metres and weight are both null"); return LV_EINVAL; }
+    if (n && (!pts || stride < 12)) { set_error("lv_tsdf_query: bad point array (stride %zu)", stride); return LV_EINVAL; }
+    if (n > 0xFFFFFFF0ull / 4) { set_error("lv_tsdf_query: too many points"); return LV_EINVAL; }
+    return c->tsdf.query(c->stream, pts, stride, n, metres, weight);
+}
+
+int lv_tsdf_fetch(lv_ctx* c, int32_t* S, int32_t* W, float* metres, size_t capacity) {
+    LV_TSDF_CTX(c);
+    if (!S && !W && !metres) { set_error("lv_tsdf_fetch: S, W and metres are all null"); return LV_EINVAL; }
+    if (capacity < c->tsdf.n_vox) { set_error("lv_tsdf_fetch: room for nx * ny * nz = %zu values needed", c->tsdf.n_vox); return LV_EINVAL; }
+    return c->tsdf.fetch(c->stream, S, W, metres);
+}
+
+int lv_tsdf_load(lv_ctx* c, const int32_t* S, const int32_t* W, size_t n) {
+    LV_TSDF_CTX(c);
+    if (!S || !W || n != c->tsdf.n_vox) { set_error("lv_tsdf_load: %zu values for a volume of %zu voxels, or a null array", n, c->tsdf.n_vox); return LV_EINVAL; }
+    const size_t bad = tsdf_check_volume(c->tsdf.grid, S, W, n);
+    if (bad != n) {
+        set_error("lv_tsdf_load: voxel %zu: S = %d, W = %d: 0 <= W <= max_weight and |S| <= T * W", bad, S[bad], W[bad]);
+        return LV_EINVAL;
+    }
+    tsdf_changed(c);
+    return c->tsdf.load(c->stream, S, W);
+}
+
+int lv_tsdf_clear(lv_ctx* c) {
+    LV_TSDF_CTX(c);
+    tsdf_changed(c);
+    return c->tsdf.clear(c->stream);
+}
+
+int lv_tsdf_get_params(lv_ctx* c, lv_tsdf_params* out) {
+    LV_TSDF_CTX(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    *out = c->tsdf.prm;
+    return LV_OK;
+}
+
+int lv_tsdf_mesh_build(lv_ctx* c, int min_weight, uint64_t counts[4]) {
+    LV_TSDF_CTX(c);
+    if (min_weight < 1) { set_error("lv_tsdf_mesh_build: min_weight = %d: at least 1", min_weight); return LV_EINVAL; }
+    return c->tsdf.mesh_build(c->stream, min_weight, counts);
+}
+
+int lv_tsdf_mesh_fetch(lv_ctx* c, float* xyz, int32_t* sub, uint32_t* tri, size_t cap_vertices, size_t cap_triangles) {
+    LV_TSDF_CTX(c);
+    LV_REQUIRE(c->tsdf.mesh.built, LV_ESTATE, "no mesh: call lv_tsdf_mesh_build first");
+    if (!xyz && !sub && !tri) { set_error("lv_tsdf_mesh_fetch: xyz, sub and tri are all null"); return LV_EINVAL; }
+    const TsdfMesh& m = c->tsdf.mesh;
+    if ((xyz || sub) && cap_vertices < m.counts[0]) { set_error("lv_tsdf_mesh_fetch: room for %llu vertices needed", (unsigned long long)m.counts[0]); return LV_EINVAL; }
+    if (tri && cap_triangles < m.counts[1]) { set_error("lv_tsdf_mesh_fetch: room for %llu triangles needed", (unsigned long long)m.counts[1]); return LV_EINVAL; }
+    return c->tsdf.mesh_fetch(c->stream, xyz, sub, tri);
+}
+
+int lv_tsdf_mesh_info(lv_ctx* c, lv_mesh_info* out) {
+    LV_TSDF_CTX(c);
+    if (!out) { set_error("null argument"); return LV_EINVAL; }
+    const TsdfMesh& m = c->tsdf.mesh;
+    *out = lv_mesh_info{};
+    if (!m.built) return LV_OK;
+    out->built = 1;
+    out->stale = m.stale;
+    out->min_weight = m.min_weight;
+    out->vertices = m.counts[0];
+    out->triangles = m.counts[1];
+    out->active_cells = m.counts[2];
+    out->refused_edges = m.counts[3];
+    return LV_OK;
+}
+
+int lv_tsdf_mesh_clear(lv_ctx* c) {
+    LV_TSDF_CTX(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->tsdf.mesh_release();
+    return LV_OK;
 }
 
 }  // extern "C"
