@@ -423,6 +423,75 @@ int  lv_map_cluster(lv_ctx* ctx, const lv_cluster_params* p, const uint8_t* mask
 int  lv_map_remove_clusters(lv_ctx* ctx, const lv_cluster_params* p, const uint8_t* mask, const uint8_t* seeds, uint8_t* flags,
                             size_t* n_removed);
 
+/* ---- Plane segmentation ---------------------------------------------------------------------------
+ * The dominant planes of the device map and the points that lie on them (PCL's SACSegmentation with SACMODEL_PLANE, and its
+ * axis-constrained forms SACMODEL_PERPENDICULAR_PLANE / SACMODEL_PARALLEL_PLANE): "the floor is this plane, these points belong
+ * to it, those are the walls".  lv_map_planes extracts up to max_planes planes from the living points, one after the other;
+ * each plane's members leave the candidates of the next.  The result is exactly defined: a pure function of the living points
+ * in map order, the mask and the parameters, bitwise reproducible.  The map is read, never changed.
+ *
+ * 1. Candidates.  Round r = 0, 1, ...: the INCLUDED living points (mask == NULL: all; otherwise those whose mask byte is
+ *    non-zero, as in lv_map_cluster) that no earlier plane has taken, in map order, c[0 .. n).  n < 3 or n < min_inliers: stop.
+ * 2. Draws.  Hypothesis h (0 .. iterations-1) of round r draws i_j = umulhi64(u_j, n), j = 0, 1, 2, with
+ *    u_j = mix(seed ^ mix((r << 40) | (h << 8) | j)) and mix(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) *
+ *    0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31) (splitmix64), all in 64 bits.  Two equal draws
+ *    make the hypothesis invalid.
+ * 3. Plane of a hypothesis, p_j = c[i_j], in f64, unfused, in the order written: u = p1 - p0, v = p2 - p0, c = u x v
+ *    (cx = uy vz - uz vy, cy = uz vx - ux vz, cz = ux vy - uy vx); cc = (cx^2 + cy^2) + cz^2, uu and vv likewise.  Invalid iff
+ *    !(cc > 1e-12 * (uu * vv)) (a sliver).  n^ = c / sqrt(cc), per component.  Sign: constraint 1: n^ . a^ >= 0 for the
+ *    normalised axis a^ (dot product (x + y) + z); otherwise, and when that dot product is 0, the component of largest
+ *    magnitude is positive, ties to the lower axis (the orient-0 rule of lv_map_normals).  Constraint, on
+ *    t = |(n^x a^x + n^y a^y) + n^z a^z|: constraint 1 needs t >= cos(max_angle), constraint 2 needs t <= sin(max_angle),
+ *    otherwise the hypothesis is invalid; a^ = axis / |axis| and both thresholds are formed once, in f64.
+ *    normal = n^ rounded to f32, anchor = p0.
+ * 4. Inlier test, in f32, unfused: q = p - anchor per coordinate, s = (nx qx + ny qy) + nz qz; inlier iff fabsf(s) <= distance.
+ * 5. Winner: the valid hypothesis with the most inliers among the candidates (its `support`), ties to the smaller h.  No valid
+ *    hypothesis, or support < min_inliers: stop, this round reports no plane.
+ * 6. Refit (refine != 0), over the winner's inliers: g = (int32) rintf((p - anchor) * 256) per coordinate (the f32
+ *    subtraction, the exact scaling, round half to even); a point with any |g| > 2^22 stays an inlier but is left out of the
+ *    sums.  Exact integer sums n_fit, S1[3], S2[6] (xx, xy, xz, yy, yz, zz); M = n_fit S2 - S1 S1^T exactly (128-bit), each entry
+ *    converted to f64 once; the eigenvector of M's smallest eigenvalue l0 (the solver of lv_map_normals, f64) with the sign rule
+ *    of step 3, rounded to f32, is the new normal; the new anchor is (float)((double)anchor + (double)S1 / (256.0 * n_fit)) per
+ *    coordinate; rms = sqrt(max(l0, 0)) / (256 n_fit) metres.  n_fit < 3: the hypothesis' plane stands, bit 0 of flags clear.
+ *    The constraint judges hypotheses only, not the refit.
+ * 7. Labels: the members of plane r are the inliers of the FINAL plane among this round's candidates (step 4); they get label r.
+ *
+ * Read-only and ordered like lv_map_knn: it sees every earlier insert, eviction and rebuild, reads the active store while a
+ * background rebuild runs and never waits for one. */
+typedef struct lv_plane_params {
+    float    distance;     /* > 0, finite: inlier iff |s| <= distance (step 4) */
+    uint32_t iterations;   /* K, hypotheses per plane, 1..65536 */
+    uint32_t max_planes;   /* 1..32 */
+    uint32_t min_inliers;  /* >= 3: extraction stops when the best hypothesis has fewer */
+    uint64_t seed;
+    int      constraint;   /* 0 none; 1 normal within max_angle of axis (floors, ceilings);
+                              2 normal within max_angle of the plane perpendicular to axis (walls) */
+    float    axis[3];      /* constraint != 0: finite, non-zero; normalised in f64 */
+    float    max_angle;    /* constraint != 0: radians, in (0, pi/2) */
+    int      refine;       /* != 0: least-squares refit over the inliers, then reclassify once */
+} lv_plane_params;
+typedef struct lv_plane {
+    float    normal[3], anchor[3];   /* the plane: (p - anchor) . normal = 0 */
+    double   d;                      /* -(normal . anchor) in f64, (x + y) + z: normal . p + d = 0 */
+    double   rms;                    /* refit only: sqrt(max(l0, 0)) / (256 n_fit), metres; else NaN */
+    uint32_t inliers;                /* final label count */
+    uint32_t support;                /* count of the winning hypothesis */
+    uint32_t hypothesis;             /* index of the winning hypothesis */
+    uint32_t candidates;             /* candidates of this round */
+    uint32_t n_fit;                  /* points in the refit sums */
+    uint32_t flags;                  /* bit 0: refit done */
+} lv_plane;
+/* Defaults: distance 0.1, iterations 512, max_planes 1, min_inliers 100, seed 0, constraint 0, axis (0, 0, 1),
+ * max_angle 10 degrees, refine 1. */
+void lv_default_plane_params(lv_plane_params* p);
+/* mask: NULL, or lv_map_size() bytes in map order, 0 = excluded.  labels: NULL, or `capacity` entries of room, lv_map_size()
+ * written in map order (capacity < lv_map_size(): LV_EINVAL): the plane's index in extraction order, -1 for a point on no plane.
+ * planes: NULL, or the first min(P, planes_capacity) records in extraction order.  *n_planes (may be NULL) = P.  Parameters
+ * outside the limits or a NULL params give LV_EINVAL with the reason in lv_last_error() and write nothing; an empty or unbuilt
+ * map gives LV_OK, P = 0, nothing else written. */
+int  lv_map_planes(lv_ctx* ctx, const lv_plane_params* p, const uint8_t* mask, int32_t* labels, size_t capacity,
+                   lv_plane* planes, size_t planes_capacity, size_t* n_planes);
+
 /* ---- Place recognition ---------------------------------------------------------------------------
  * Where in a saved map am I, with no pose prior (the front half of the reference's "Prelocalization with a previously saved HD
  * map")?  A place is a Scan Context descriptor (Kim & Kim, IROS 2018) with its centre, a LiDAR origin in the world.  The context

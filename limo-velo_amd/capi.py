@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "lv_default_paint_params", "lv_map_paint",
     "lv_default_surface_params", "lv_default_outlier_params", "lv_map_normals", "lv_map_remove_outliers",
     "lv_default_cluster_params", "lv_map_cluster", "lv_map_remove_clusters",
+    "lv_default_plane_params", "lv_map_planes",
     "lv_default_place_params", "lv_place_configure", "lv_place_describe", "lv_place_add_scan", "lv_place_add_map", "lv_place_query",
     "lv_place_count", "lv_place_clear", "lv_place_fetch", "lv_place_load",
     "lv_default_occupancy_params", "lv_occ_configure", "lv_occ_integrate", "lv_occ_query", "lv_occ_project", "lv_occ_fetch", "lv_occ_load",
@@ -137,6 +138,30 @@ CLUSTER_ARGTYPES = {
                        C.c_size_t, C.POINTER(C.c_size_t)],
     "lv_map_remove_clusters": [C.c_void_p, C.POINTER(ClusterParams), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                C.POINTER(C.c_size_t)],
+}
+
+
+class PlaneParams(C.Structure):  # lv_plane_params
+    _fields_ = [("distance", C.c_float), ("iterations", C.c_uint32), ("max_planes", C.c_uint32), ("min_inliers", C.c_uint32),
+                ("seed", C.c_uint64), ("constraint", C.c_int), ("axis", C.c_float * 3), ("max_angle", C.c_float), ("refine", C.c_int)]
+
+
+class Plane(C.Structure):  # lv_plane (64 bytes)
+    _fields_ = [("normal", C.c_float * 3), ("anchor", C.c_float * 3), ("d", C.c_double), ("rms", C.c_double), ("inliers", C.c_uint32),
+                ("support", C.c_uint32), ("hypothesis", C.c_uint32), ("candidates", C.c_uint32), ("n_fit", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# the same record as a numpy dtype (Context.map_planes)
+PLANE_DTYPE = np.dtype([("normal", np.float32, 3), ("anchor", np.float32, 3), ("d", np.float64), ("rms", np.float64), ("inliers", np.uint32),
+                        ("support", np.uint32), ("hypothesis", np.uint32), ("candidates", np.uint32), ("n_fit", np.uint32),
+                        ("flags", np.uint32)])
+PLANE_MAX_PLANES = 32
+PLANE_CHUNK, PLANE_TILE = 256, 1024   # the scoring kernel's hypotheses / candidates per workgroup (PL_CHUNK, PL_TILE of lv_planes.hpp)
+
+# ctypes signatures of the plane segmentation (include/limovelo_hip.h "Plane segmentation"; tests/test_planes_abi.py)
+PLANE_ARGTYPES = {
+    "lv_map_planes": [C.c_void_p, C.POINTER(PlaneParams), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(Plane),
+                      C.c_size_t, C.POINTER(C.c_size_t)],
 }
 
 
@@ -561,6 +586,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_outlier_params.argtypes = [C.POINTER(OutlierParams)]
         lib.lv_default_cluster_params.restype = None
         lib.lv_default_cluster_params.argtypes = [C.POINTER(ClusterParams)]
+        lib.lv_default_plane_params.restype = None
+        lib.lv_default_plane_params.argtypes = [C.POINTER(PlaneParams)]
         lib.lv_default_place_params.restype = None
         lib.lv_default_place_params.argtypes = [C.POINTER(PlaceParams)]
         lib.lv_place_count.restype = C.c_size_t
@@ -582,7 +609,7 @@ def load_library() -> C.CDLL:
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
+                               **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **TSDF_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -642,6 +669,17 @@ def default_cluster_params(**kw) -> ClusterParams:
     load_library().lv_default_cluster_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
+    return p
+
+
+def default_plane_params(**kw) -> PlaneParams:
+    p = PlaneParams()
+    load_library().lv_default_plane_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "axis":
+            p.axis[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -974,6 +1012,21 @@ class Context:
         nr = C.c_size_t(0)
         self._check(self.lib.lv_map_remove_clusters(self.h, C.byref(p), mp, sp, flags.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(nr)))
         return dict(flags=flags, n_removed=int(nr.value))
+
+    # --- plane segmentation
+    def map_planes(self, params: PlaneParams | None = None, mask=None) -> dict:
+        """dict(labels [m] int32 in map order (the plane's index in extraction order, -1: on no plane), planes [P] records
+        (PLANE_DTYPE) in extraction order, n_planes = P): lv_map_planes; mask: None or [m] in map order, 0 = excluded."""
+        p = params if params is not None else default_plane_params()
+        m = self.map_size()
+        keep, mp = self._point_bytes(mask, "mask")
+        labels = np.full(m, -1, np.int32)
+        planes = np.zeros(PLANE_MAX_PLANES, PLANE_DTYPE)
+        P = C.c_size_t(0)
+        self._check(self.lib.lv_map_planes(self.h, C.byref(p), mp, labels.ctypes.data_as(C.POINTER(C.c_int32)), C.c_size_t(m),
+                                           planes.ctypes.data_as(C.POINTER(Plane)), C.c_size_t(PLANE_MAX_PLANES), C.byref(P)))
+        n = int(P.value)
+        return dict(labels=labels, planes=planes[:n].copy(), n_planes=n)
 
     # --- map painting
     def map_paint(self, views, params: LvPaintParams | None = None):

@@ -11,6 +11,7 @@
 #include "lv_visibility.hpp"
 #include "lv_surface.hpp"
 #include "lv_cluster.hpp"
+#include "lv_planes.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
 #include "lv_distance.hpp"
@@ -54,6 +55,7 @@ struct lv_ctx {
     PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
     SurfaceStore surface;   // lv_map_normals / lv_map_remove_outliers: their own buffers (lv_surface.hip)
     ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
+    PlaneStore planes;      // lv_map_planes: its own buffers (lv_planes.hip); nothing allocated before the first call
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
     DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
@@ -648,6 +650,7 @@ void lv_destroy(lv_ctx* c) {
     c->paint.release();
     c->surface.release();
     c->cluster.release();
+    c->planes.release();
     c->place.release();
     c->ray.release();
     c->rollout.release();
@@ -1050,6 +1053,37 @@ int lv_map_remove_clusters(lv_ctx* c, const lv_cluster_params* p, const uint8_t*
     if (rc) return rc;
     if (flags) LV_HIP(hipMemcpy(flags, c->cluster.d_flags, m, hipMemcpyDeviceToHost));
     if (n_removed) *n_removed = nr;
+    return LV_OK;
+}
+
+// ---- Plane segmentation (lv_planes.hip)
+void lv_default_plane_params(lv_plane_params* p) { default_plane_params(p); }
+
+// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
+int lv_map_planes(lv_ctx* c, const lv_plane_params* p, const uint8_t* mask, int32_t* labels, size_t capacity, lv_plane* planes,
+                  size_t planes_capacity, size_t* n_planes) {
+    LV_CHECK_CTX(c);
+    PlaneRule q{};
+    int rc = plane_rule(p, &q);
+    if (rc) return rc;
+    LV_SETTLE_MAP(c);
+    LV_RELIN_POLL(c);
+    const size_t m = c->map.m;
+    if (labels && capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
+    if (n_planes) *n_planes = 0;
+    if (!c->map.built || m == 0) return LV_OK;
+    const uint32_t* rank = nullptr;
+    rc = c->query.ensure_rank(c->map, c->stream, &rank);
+    if (!rc) rc = c->planes.ensure(c->map.n_ids, m, q.iterations);
+    if (!rc && mask) rc = cluster_upload(c, c->planes.d_mask, mask, m);
+    lv_plane found[PLANE_MAX_PLANES];
+    size_t P = 0;
+    if (!rc) rc = planes_extract(c->map, c->stream, c->planes, q, rank, mask ? c->planes.d_mask.p : nullptr, labels != nullptr, found, &P);
+    if (rc) return rc;
+    if (labels) LV_HIP(hipMemcpy(labels, c->planes.d_labels, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const size_t np = P < planes_capacity ? P : planes_capacity;
+    if (planes && np) std::memcpy(planes, found, np * sizeof(lv_plane));
+    if (n_planes) *n_planes = P;
     return LV_OK;
 }
 
