@@ -1081,6 +1081,54 @@ int  lv_tsdf_mesh_info(lv_ctx* ctx, lv_mesh_info* out);
 /* Frees the mesh. */
 int  lv_tsdf_mesh_clear(lv_ctx* ctx);
 
+/* ---- Rolling volumes -------------------------------------------------------------------------------------
+ * The occupancy grid and the TSDF volume follow the robot (costmap_2d's rolling_window, the local maps of Voxblox / nvblox, the
+ * ring buffers of FIESTA / ego-planner; the reference has no counterpart).  lv_volume_recentre moves a volume by whole voxels:
+ * the contents stay where they are in the world, the box moves, what leaves it is forgotten and what enters it is never
+ * observed.  Nothing is interpolated: no bit of a surviving value changes.
+ *   rule     a volume keeps the origin it was configured with, origin0, and an accumulated shift s[3] (int32 voxels, zero after
+ *            configure).  A recentre by d[3]: s' = s + d; origin'[a] = origin0[a] + (float)s'[a] * resolution (f32, unfused, in
+ *            that order: the origin depends on s' alone, so +d then -d gives back origin0 bit for bit); new voxel (i, j, k) holds
+ *            what old voxel (i + d_x, j + d_y, k + d_z) held if that lies inside the grid, otherwise it is never observed (NaN,
+ *            bits 0x7FC00000, in the occupancy grid; S = 0, W = 0 in the TSDF).  |d[a]| <= 2^20, |s'[a]| <= 2^20 and origin'
+ *            finite (LV_EINVAL otherwise, nothing changes).  |d[a]| >= n_a is legal and leaves every voxel never observed.
+ *            d = (0, 0, 0) does nothing at all: nothing goes stale, no buffer is touched, the stats are zero.
+ *   after    a non-zero recentre of LV_VOLUME_OCC: lv_occ_get_params reports origin'; the distance field and the frontier are
+ *            stale (as after lv_occ_integrate) and the next ray cast classifies the grid anew.  The field and the plan are
+ *            snapshots with their own origin: lv_occ_distance_query, lv_occ_plan_paths and lv_occ_rollout go on answering for
+ *            the same world points with the same bits.  The frontier's cells are indices: lv_occ_frontier_rank gives LV_ESTATE
+ *            unless the frontier and the plan were both built at the grid's present accumulated shift (lv_volume_shift_info
+ *            reports the three), that is until field, plan and frontier have been rebuilt.  Of LV_VOLUME_SURFACE:
+ *            lv_tsdf_get_params reports origin'; a built mesh is stale (its vertices are metres and stay right).
+ *   mark     lv_occ_mark fills voxels from points, the way back from the map to the grid: a strip the grid has just scrolled
+ *            into is unknown to it although the point map may know it.  Source as lv_elev_build: pts = NULL reads the living
+ *            points of the device map (after the insert in flight has settled), otherwise n < 2^31 caller points, stride >= 12.
+ *            A point is used iff it quantises into the grid ("Occupancy grid") and its voxel lies in the inclusive box lo..hi
+ *            clipped to the grid (a box that is empty after clipping marks nothing).  Per voxel the integer count c of the points
+ *            used; a voxel with c >= min_points (1..2^20) is a candidate.  only_unknown != 0: a candidate whose L is NaN gets
+ *            L = fminf(fmaxf(l_mark, l_min), l_max), any other is left alone (ray evidence is never overridden).
+ *            only_unknown == 0: every candidate gets L = fminf(fmaxf((isnan(L) ? 0 : L) + l_mark, l_min), l_max), once per call.
+ *            l_mark finite and non-zero; a negative value marks free space.  A pure function of the point set, in any order.
+ *            The field and the frontier go stale iff a voxel was written.
+ * The arguments are judged before the context (LV_EINVAL, the null context last), then LV_ESTATE if the volume is not configured,
+ * then the accumulated shift.  The occupancy grid's second buffer (nx * ny * nz floats) is allocated by the first non-zero
+ * recentre or the first lv_occ_mark and kept until lv_occ_configure; the TSDF moves through the scratch it already has. */
+#define LV_VOLUME_OCC     0   /* the occupancy grid */
+#define LV_VOLUME_SURFACE 1   /* the TSDF volume */
+typedef struct lv_volume_shifts {
+    int32_t grid[3], surface[3];             /* accumulated shift of each volume (0 if not configured) */
+    int32_t field[3], plan[3], frontier[3];  /* the grid shift each snapshot was built at (0 if not built) */
+} lv_volume_shifts;
+/* stats (may be NULL): voxels kept, voxels exposed (now never observed), voxels that held evidence (L not NaN; W > 0) and left
+ * the volume, 0. */
+int  lv_volume_recentre(lv_ctx* ctx, int volume, const int32_t shift[3], uint64_t stats[4]);
+int  lv_volume_shift_info(lv_ctx* ctx, lv_volume_shifts* out);
+typedef struct lv_occ_mark_params { int lo[3], hi[3]; int min_points; int only_unknown; float l_mark; } lv_occ_mark_params;
+/* Defaults: the whole grid (lo 0, hi 2^30), min_points 1, only_unknown 1, l_mark 0.85. */
+void lv_default_occ_mark_params(lv_occ_mark_params* p);
+/* stats (may be NULL): points used, voxels holding >= min_points, voxels marked, voxels left alone because they were observed. */
+int  lv_occ_mark(lv_ctx* ctx, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

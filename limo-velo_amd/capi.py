@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "lv_default_rollout_params", "lv_occ_rollout",
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
+    "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -375,6 +376,27 @@ TSDF_ARGTYPES = {
 }
 
 
+LV_VOLUME_OCC, LV_VOLUME_SURFACE = 0, 1
+VOLUME_SHIFT_LIMIT = 1 << 20
+
+
+class VolumeShifts(C.Structure):  # lv_volume_shifts
+    _fields_ = [("grid", C.c_int32 * 3), ("surface", C.c_int32 * 3), ("field", C.c_int32 * 3), ("plan", C.c_int32 * 3),
+                ("frontier", C.c_int32 * 3)]
+
+
+class OccMarkParams(C.Structure):  # lv_occ_mark_params
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("min_points", C.c_int), ("only_unknown", C.c_int), ("l_mark", C.c_float)]
+
+
+# ctypes signatures of the rolling volumes (include/limovelo_hip.h "Rolling volumes"; tests/test_volume_recentre_abi.py)
+VOLUME_ARGTYPES = {
+    "lv_volume_recentre": [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)],
+    "lv_volume_shift_info": [C.c_void_p, C.POINTER(VolumeShifts)],
+    "lv_occ_mark": [C.c_void_p, C.POINTER(OccMarkParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)],
+}
+
+
 def camera_view(frame):
     """(LvCameraView, image array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, image
     ([h, w, 3] or [h, w] uint8; rows may be strided), optional format (LV_IMAGE_*; default RGB8, MONO8 for a 2-D image) and dist
@@ -608,9 +630,11 @@ def load_library() -> C.CDLL:
         lib.lv_default_rollout_params.argtypes = [C.POINTER(RolloutParams)]
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
+        lib.lv_default_occ_mark_params.restype = None
+        lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **TSDF_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -759,6 +783,17 @@ def default_tsdf_params(**kw) -> TsdfParams:
     for k, v in kw.items():
         if k == "origin":
             p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def default_occ_mark_params(**kw) -> OccMarkParams:
+    p = OccMarkParams()
+    load_library().lv_default_occ_mark_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("lo", "hi"):
+            getattr(p, k)[:] = [int(x) for x in v]
         else:
             setattr(p, k, v)
     return p
@@ -1429,6 +1464,35 @@ class Context:
 
     def tsdf_mesh_clear(self):
         self._check(self.lib.lv_tsdf_mesh_clear(self.h))
+
+    # --- rolling volumes (include/limovelo_hip.h "Rolling volumes")
+    def volume_recentre(self, volume: int, shift) -> np.ndarray:
+        """lv_volume_recentre of LV_VOLUME_OCC or LV_VOLUME_SURFACE by shift (3 whole voxels); returns stats [4] uint64: voxels kept,
+        exposed, that held evidence and left the volume, 0."""
+        d = (C.c_int32 * 3)(*[int(v) for v in shift])
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_volume_recentre(self.h, int(volume), d, stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def volume_shift_info(self) -> VolumeShifts:
+        out = VolumeShifts()
+        self._check(self.lib.lv_volume_shift_info(self.h, C.byref(out)))
+        return out
+
+    def occ_mark(self, params: OccMarkParams | None = None, points=None) -> np.ndarray:
+        """lv_occ_mark from points [n, 3] (None: the living points of the device map); returns stats [4] uint64: points used,
+        voxels holding >= min_points, voxels marked, voxels left alone because they were observed."""
+        p = params if params is not None else default_occ_mark_params()
+        stats = np.zeros(4, np.uint64)
+        if points is None:
+            a, stride, n = None, 0, 0
+        else:
+            a, stride, n = _points(np.asarray(points, np.float32).reshape(-1, 3))
+            if n == 0:   # (no points, but still "caller points": a pointer that is not NULL)
+                a, stride = np.zeros((1, 3), np.float32), 12
+        self._check(self.lib.lv_occ_mark(self.h, C.byref(p), None if a is None else C.c_void_p(a.ctypes.data), C.c_size_t(stride), C.c_size_t(n),
+                                         stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")
     def place_configure(self, params: PlaceParams | None = None):

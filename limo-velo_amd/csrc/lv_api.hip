@@ -2242,6 +2242,12 @@ static void occ_field_changed(lv_ctx* c) {
     if (c->plan.built) c->plan.stale = 1;
 }
 
+// The field remembers the grid's accumulated shift at its build ("Rolling volumes"); hands rc on
+static int dist_built_at(lv_ctx* c, int rc) {
+    if (rc == LV_OK) std::memcpy(c->dist.shift, c->occ.shift, sizeof(c->dist.shift));
+    return rc;
+}
+
 }  // extern "C"
 
 // What lv_distance_info, lv_plan_info and lv_frontier_info share; true: s is built (the caller adds what is its own)
@@ -2340,7 +2346,7 @@ int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats
     if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
     LV_OCC_CTX(c);
     occ_field_changed(c);
-    return c->dist.build(c->stream, c->occ, *p, nullptr, stats);
+    return dist_built_at(c, c->dist.build(c->stream, c->occ, *p, nullptr, stats));
 }
 
 int lv_occ_distance_fetch(lv_ctx* c, int32_t* s2, float* metres, size_t capacity) {
@@ -2389,7 +2395,9 @@ int lv_occ_plan_build(lv_ctx* c, const lv_plan_params* p, const uint8_t* cost, s
     LV_OCC_CTX(c);
     LV_DIST_BUILT(c);
     if (const char* why = plan_check_field(p->connectivity, c->dist.prm.planar != 0)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
-    return c->plan.build(c->stream, c->dist, *p, cost, n_cost, goals, stride, n_goals, stats);
+    const int rc = c->plan.build(c->stream, c->dist, *p, cost, n_cost, goals, stride, n_goals, stats);
+    if (rc == LV_OK) std::memcpy(c->plan.shift, c->dist.shift, sizeof(c->plan.shift));   // (the plan lies where its field does)
+    return rc;
 }
 
 int lv_occ_plan_fetch(lv_ctx* c, uint32_t* potential, uint8_t* cell_cost, size_t capacity) {
@@ -2438,7 +2446,9 @@ void lv_default_frontier_params(lv_frontier_params* p) {
 int lv_occ_frontier_build(lv_ctx* c, const lv_frontier_params* p, uint64_t stats[4]) {
     if (const char* why = fr_check_params(p)) { set_error("lv_occ_frontier_build: %s", why); return LV_EINVAL; }
     LV_OCC_CTX(c);
-    return c->frontier.build(c->stream, c->occ, *p, stats);
+    const int rc = c->frontier.build(c->stream, c->occ, *p, stats);
+    if (rc == LV_OK) std::memcpy(c->frontier.shift, c->occ.shift, sizeof(c->frontier.shift));
+    return rc;
 }
 
 int lv_occ_frontier_fetch(lv_ctx* c, int32_t* labels, size_t capacity) {
@@ -2470,6 +2480,13 @@ int lv_occ_frontier_rank(lv_ctx* c, int reach, uint32_t* best_p, int32_t* best_c
     if ((f.planar != 0) != (g.planar != 0) || f.nx != g.nx || f.ny != g.ny || f.nz != g.nz) {
         set_error("lv_occ_frontier_rank: the plan (%d x %d x %d, planar %d) is not of the frontier's cells (%d x %d x %d, planar %d)", g.nx, g.ny, g.nz,
                   g.planar, f.nx, f.ny, f.nz, f.planar);
+        return LV_ESTATE;
+    }
+    // (cell indices of different boxes do not pair, and the cells handed back are read in the grid's box of now)
+    if (std::memcmp(c->frontier.shift, c->plan.shift, sizeof(c->plan.shift)) != 0 || std::memcmp(c->frontier.shift, c->occ.shift, sizeof(c->occ.shift)) != 0) {
+        set_error("lv_occ_frontier_rank: the frontier was built at grid shift (%d, %d, %d), the plan at (%d, %d, %d), the grid is at (%d, %d, %d): "
+                  "rebuild the field, the plan and the frontier", c->frontier.shift[0], c->frontier.shift[1], c->frontier.shift[2], c->plan.shift[0],
+                  c->plan.shift[1], c->plan.shift[2], c->occ.shift[0], c->occ.shift[1], c->occ.shift[2]);
         return LV_ESTATE;
     }
     if (capacity < c->frontier.n_clusters) { set_error("capacity %zu < %zu clusters", capacity, c->frontier.n_clusters); return LV_EINVAL; }
@@ -2599,7 +2616,7 @@ int lv_occ_distance_build_cells(lv_ctx* c, const lv_distance_params* p, const in
     const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
     if (n != plane) { set_error("lv_occ_distance_build_cells: %zu cells for a plane of nx * ny = %zu", n, plane); return LV_EINVAL; }
     occ_field_changed(c);
-    return c->dist.build(c->stream, c->occ, *p, cells, stats);
+    return dist_built_at(c, c->dist.build(c->stream, c->occ, *p, cells, stats));
 }
 
 // ---- Rollouts (lv_rollout.hip)
@@ -2759,6 +2776,90 @@ int lv_tsdf_mesh_clear(lv_ctx* c) {
     LV_TSDF_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->tsdf.mesh_release();
+    return LV_OK;
+}
+
+// ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)
+// (the arguments are judged before the context, as lv_occ_raycast's are; the accumulated shift needs the volume)
+int lv_volume_recentre(lv_ctx* c, int volume, const int32_t shift[3], uint64_t stats[4]) {
+    if (volume != LV_VOLUME_OCC && volume != LV_VOLUME_SURFACE) { set_error("lv_volume_recentre: volume %d: LV_VOLUME_OCC or LV_VOLUME_SURFACE", volume); return LV_EINVAL; }
+    if (!shift) { set_error("lv_volume_recentre: null shift"); return LV_EINVAL; }
+    for (int a = 0; a < 3; ++a)
+        if (shift[a] < -GRID_SHIFT_LIMIT || shift[a] > GRID_SHIFT_LIMIT) { set_error("lv_volume_recentre: shift: each component within +-2^20 voxels"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    const bool occ = volume == LV_VOLUME_OCC;
+    if (occ) LV_REQUIRE(c->occ.configured, LV_ESTATE, "no occupancy grid: call lv_occ_configure first");
+    else LV_REQUIRE(c->tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first");
+    int32_t s_new[3];
+    float origin_new[3];
+    const char* why = occ ? grid_shift_check(c->occ.origin0, c->occ.prm.resolution, c->occ.shift, shift, s_new, origin_new)
+                          : grid_shift_check(c->tsdf.origin0, c->tsdf.prm.resolution, c->tsdf.shift, shift, s_new, origin_new);
+    if (why) { set_error("lv_volume_recentre: %s", why); return LV_EINVAL; }
+    if (!(shift[0] | shift[1] | shift[2])) {   // nothing moves: nothing goes stale, no buffer is touched
+        if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+        return LV_OK;
+    }
+    // (what was built from the volume goes stale once it has moved: a call that fails has changed nothing)
+    if (occ) {
+        const int rc = c->occ.recentre(c->stream, shift, s_new, origin_new, stats);
+        if (rc == LV_OK) occ_grid_changed(c);
+        return rc;
+    }
+    const int rc = c->tsdf.recentre(c->stream, shift, s_new, origin_new, stats);
+    if (rc == LV_OK) tsdf_changed(c);
+    return rc;
+}
+
+int lv_volume_shift_info(lv_ctx* c, lv_volume_shifts* out) {
+    if (!out) { set_error("lv_volume_shift_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *out = lv_volume_shifts{};
+    for (int a = 0; a < 3; ++a) {
+        if (c->occ.configured) out->grid[a] = c->occ.shift[a];
+        if (c->tsdf.configured) out->surface[a] = c->tsdf.shift[a];
+        if (c->occ.configured && c->dist.built) out->field[a] = c->dist.shift[a];
+        if (c->occ.configured && c->plan.built) out->plan[a] = c->plan.shift[a];
+        if (c->occ.configured && c->frontier.built) out->frontier[a] = c->frontier.shift[a];
+    }
+    return LV_OK;
+}
+
+void lv_default_occ_mark_params(lv_occ_mark_params* p) {
+    if (!p) return;
+    *p = lv_occ_mark_params{};
+    for (int a = 0; a < 3; ++a) p->hi[a] = 1 << 30;   // (clipped to the grid: the whole of it)
+    p->min_points = 1;
+    p->only_unknown = 1;
+    p->l_mark = 0.85f;
+}
+
+// (the arguments are judged before the context, as lv_elev_build's are).  The map source is read as lv_elev_build reads it.
+int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (!p) { set_error("lv_occ_mark: null params"); return LV_EINVAL; }
+    if (p->min_points < 1 || p->min_points > (1 << 20)) { set_error("lv_occ_mark: min_points = %d: must be in 1..2^20", p->min_points); return LV_EINVAL; }
+    if (!(std::isfinite(p->l_mark) && p->l_mark != 0.f)) { set_error("lv_occ_mark: l_mark: finite and not zero"); return LV_EINVAL; }
+    if (pts && stride < 12) { set_error("lv_occ_mark: bad point array (stride %zu)", stride); return LV_EINVAL; }
+    if (pts && n >= ((size_t)1 << 31)) { set_error("lv_occ_mark: too many points"); return LV_EINVAL; }
+    LV_OCC_CTX(c);
+    int lo[3], hi[3];
+    if (!grid_clip_box(c->occ.grid, p->lo, p->hi, lo, hi)) {   // nothing to mark
+        if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+        return LV_OK;
+    }
+    uint64_t st[4] = {0, 0, 0, 0};
+    int rc;
+    if (!pts) {
+        LV_SETTLE_MAP(c);
+        LV_RELIN_POLL(c);
+        const bool any = c->map.built && c->map.m > 0;
+        rc = c->occ.mark(c->stream, *p, lo, hi, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, nullptr, 0, 0, st);
+    } else {
+        rc = c->occ.mark(c->stream, *p, lo, hi, nullptr, 0, pts, stride, n, st);
+    }
+    if (rc) return rc;
+    if (st[2]) occ_grid_changed(c);
+    if (stats)
+        for (int i = 0; i < 4; ++i) stats[i] = st[i];
     return LV_OK;
 }
 

@@ -191,6 +191,7 @@ inline DistGrid dist_grid_of(const OccGrid& o, const lv_distance_params& p) {
 struct DistStore {
     bool built = false;
     int stale = 0;
+    int32_t shift[3] = {0, 0, 0};   // the grid's accumulated shift at the build (lv_volume_shift_info)
     lv_distance_params prm{};
     DistGrid grid{};
     float origin[3] = {0.f, 0.f, 0.f};

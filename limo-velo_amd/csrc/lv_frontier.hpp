@@ -130,6 +130,7 @@ inline const char* fr_check_params(const lv_frontier_params* p) {
 struct FrontierStore {
     bool built = false;
     int stale = 0;
+    int32_t shift[3] = {0, 0, 0};   // the grid's accumulated shift at the build: lv_occ_frontier_rank pairs cells of one shift only
     lv_frontier_params prm{};
     FrontierGrid grid{};
     size_t n_cells = 0, n_clusters = 0;

@@ -5,6 +5,9 @@
 // coordinate, the cell of a world point, the projection of a column over a band of layers, and the LDS tile with a one-cell halo
 // that the planner and the frontier labelling work in.  tests/emu/grid_emu.cpp compiles it with g++ through
 // tests/emu/hip/hip_runtime.h and tests/test_grid_host.py holds it to numpy by equality.
+// The rolling volumes' rule (the origin at an accumulated shift, the limits, the source cell of a shifted voxel, the box clip, the
+// rule of a marked voxel: lv_volume_recentre, lv_occ_mark) is in that part too; tests/emu/recentre_emu.cpp and
+// tests/test_recentre_host.py hold it to tests/recentre_ref.py.
 // The second part (hipcc only) is the wavefront folds and what the kernels build from them.
 #pragma once
 
@@ -95,6 +98,79 @@ LV_OCC_HD int grid_project_column(const float* L, size_t plane, size_t c, int k0
     return occ ? 100 : fre ? 0 : -1;
 }
 
+// ---- rolling volumes (DESIGN.md "Rolling volumes"): a volume keeps the origin it was configured with and a whole-voxel shift s
+constexpr int32_t GRID_SHIFT_LIMIT = 1 << 20;   // of one recentre and of the accumulated shift, per axis
+
+// The origin at accumulated shift s: f32, unfused, in exactly this order.  A function of s alone, so no path leaves a residue.
+LV_OCC_HD float grid_shift_origin(float origin0, int32_t s, float resolution) { return origin0 + (float)s * resolution; }
+
+// A recentre by d of a volume at accumulated shift s.  NULL: legal, s_new and origin_new are filled; otherwise what is wrong
+// (and nothing is to change).  d is tested before it is added: it may be any int32.
+LV_OCC_HD const char* grid_shift_check(const float origin0[3], float resolution, const int32_t s[3], const int32_t d[3], int32_t s_new[3],
+                                       float origin_new[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (d[a] < -GRID_SHIFT_LIMIT || d[a] > GRID_SHIFT_LIMIT) return "shift: each component within +-2^20 voxels";
+    for (int a = 0; a < 3; ++a) {
+        s_new[a] = s[a] + d[a];
+        if (s_new[a] < -GRID_SHIFT_LIMIT || s_new[a] > GRID_SHIFT_LIMIT) return "shift: the accumulated shift stays within +-2^20 voxels";
+        origin_new[a] = grid_shift_origin(origin0[a], s_new[a], resolution);
+        if (!(fabsf(origin_new[a]) < __builtin_huge_valf())) return "shift: the new origin must be finite";
+    }
+    return nullptr;
+}
+
+// The old voxel whose contents new voxel (i, j, k) takes after a recentre by (dx, dy, dz); false: it lies outside the grid and
+// the new voxel is never observed
+template <class G>
+LV_OCC_HD bool grid_shift_source(const G& g, int32_t dx, int32_t dy, int32_t dz, int i, int j, int k, int& si, int& sj, int& sk) {
+    si = i + dx;
+    sj = j + dy;
+    sk = k + dz;
+    return grid_inside(g, si, sj, sk);
+}
+
+// The old voxel that new voxel (i, j, k) answers for when it is exposed: (i, j, k) mirrored in the grid.  c + d lies outside
+// exactly when mirror(c) - d does, so the exposed new voxels and the old voxels that leave the volume pair off one to one.
+template <class G>
+LV_OCC_HD void grid_shift_mirror(const G& g, int i, int j, int k, int& mi, int& mj, int& mk) {
+    mi = g.nx - 1 - i;
+    mj = g.ny - 1 - j;
+    mk = g.nz - 1 - k;
+}
+
+// the inclusive voxel box lo..hi clipped to the grid; false: nothing is left
+template <class G>
+LV_OCC_HD bool grid_clip_box(const G& g, const int lo[3], const int hi[3], int clo[3], int chi[3]) {
+    const int n[3] = {g.nx, g.ny, g.nz};
+    bool any = true;
+    for (int a = 0; a < 3; ++a) {
+        clo[a] = lo[a] < 0 ? 0 : lo[a];
+        chi[a] = hi[a] >= n[a] ? n[a] - 1 : hi[a];
+        any = any && clo[a] <= chi[a];
+    }
+    return any;
+}
+
+// lv_occ_mark's rule for a voxel that holds `count` points; true: L is rewritten.  observed: the voxel was a candidate and was
+// left alone because it had been observed.
+LV_OCC_HD bool grid_mark_voxel(uint32_t count, uint32_t min_points, bool only_unknown, float l_mark, float l_min, float l_max, float& L,
+                               bool& candidate, bool& observed) {
+    candidate = count >= min_points;
+    observed = false;
+    if (!candidate) return false;
+    const bool unknown = L != L;
+    if (only_unknown) {
+        if (!unknown) {
+            observed = true;
+            return false;
+        }
+        L = fminf(fmaxf(l_mark, l_min), l_max);
+        return true;
+    }
+    L = fminf(fmaxf((unknown ? 0.0f : L) + l_mark, l_min), l_max);
+    return true;
+}
+
 // ---- A workgroup's tile of TX x TY x TZ cells with its one-cell halo, as it lies in LDS.  Local coordinates run -1 .. T.
 template <int TX, int TY, int TZ>
 struct HaloTile {
@@ -172,6 +248,14 @@ template <class T>
 __device__ __forceinline__ void wave_add_to(unsigned long long* dst, T v) {
     v = wave_sum(v);
     if ((threadIdx.x & 63u) == 0 && v) atomicAdd(dst, (unsigned long long)v);
+}
+
+// The workgroups of a launch that strides over its items and folds its counts once per workgroup (the recentre and mark passes):
+// 8 workgroups of 256 lanes on each of the 256 CUs fill the chip; more would only add atomics on the counters
+constexpr uint32_t GRID_STRIDE_BLOCKS = 2048;
+__host__ inline uint32_t grid_stride_blocks(size_t items) {
+    const size_t need = (items + 255) / 256;
+    return (uint32_t)(need < GRID_STRIDE_BLOCKS ? need : GRID_STRIDE_BLOCKS);
 }
 
 // Two sums (s0, s1) and two maxima (m0, m1) over a workgroup of W wavefronts, per wavefront and then across them through sh.

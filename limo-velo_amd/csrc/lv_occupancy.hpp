@@ -161,6 +161,9 @@ struct OccStore {
     size_t n_vox = 0;
     size_t n_words = 0;            // words of ONE bitmap, padded to a multiple of 4 (the fold reads uint4)
     DevBuf<float> d_L;             // log-odds by grid_at; NaN = never observed
+    DevBuf<float> d_L2;            // a recentre gathers into it and the two swap; lv_occ_mark's counts.  Not allocated before the first of either
+    float origin0[3] = {0.f, 0.f, 0.f};   // the origin of configure(); prm.origin and grid.origin are grid_shift_origin(origin0, shift)
+    int32_t shift[3] = {0, 0, 0};  // the accumulated recentre, in voxels
     DevBuf<uint32_t> d_bits;       // crossed bitmap, then hit bitmap: bit (i & 31) of word (k * ny + j) * wx + (i >> 5); all zero between views
     Counters4 stats;               // the 4 counters of the call in flight
     PointStage pts;                // every view's returns, or the query points
@@ -174,6 +177,11 @@ struct OccStore {
     int project(hipStream_t stream, int k_lo, int k_hi, int8_t* grid2d);
     int fetch(hipStream_t stream, float* logodds);
     int load(hipStream_t stream, const float* logodds);
+    // d: not all zero; s_new, origin_new: grid_shift_check's.  out: voxels kept, exposed, that held evidence and left, 0
+    int recentre(hipStream_t stream, const int32_t d[3], const int32_t s_new[3], const float origin_new[3], uint64_t out[4]);
+    // lo..hi: already clipped to the grid, not empty.  The points: map_orig (the map's float4 per id, n_ids of them; the living ones count) or the caller's
+    int mark(hipStream_t stream, const lv_occ_mark_params& p, const int lo[3], const int hi[3], const void* map_orig, uint32_t n_ids,
+             const void* points, size_t stride, size_t n, uint64_t out[4]);
     void release();
 };
 

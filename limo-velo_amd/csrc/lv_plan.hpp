@@ -183,6 +183,7 @@ inline const char* plan_check_field(int connectivity, bool planar) {
 struct PlanStore {
     bool built = false;
     int stale = 0;
+    int32_t shift[3] = {0, 0, 0};   // the shift of the field it was built from
     int rounds = 0;
     lv_plan_params prm{};
     PlanGrid grid{};

@@ -11,6 +11,10 @@
 // (tsdf_vertex_kernel), faces per voxel 0..3 (tsdf_face_count_kernel), exclusive sum, the faces (tsdf_face_emit_kernel).  All of
 // them read S and W from global memory: the 8 corners of a cell are shared with its neighbours through L2, nothing is staged.
 // lv_tsdf_query / the metres of lv_tsdf_fetch are one-lane-per-item streaming kernels; load / clear are copies and fills.
+// lv_volume_recentre (DESIGN.md "Rolling volumes") stages the moved volume in the call's scratch, which is all zero between
+// calls and holds 8 bytes per voxel, so nothing is allocated: tsdf_shift_gather_kernel writes (S, W) of every voxel's source
+// cell into its scratch word, two voxels and one 16-byte store per lane (an exposed voxel's word is 0, which is S = 0, W = 0),
+// and tsdf_shift_unpack_kernel moves the words into S and W, four voxels per lane, and zeroes them again.
 #include "lv_tsdf.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -82,6 +86,73 @@ __global__ __launch_bounds__(256) void tsdf_fold_kernel(int32_t* __restrict__ S,
     }
     wave_add_to(stats + 2, contributions);
     wave_add_to(stats + 3, touched);
+}
+
+// scratch word c = S of the source cell in the low half, W in the high half.  A workgroup strides over the pairs and adds its
+// two counts once, as occ_shift_kernel does: stats[1] += exposed voxels, stats[2] += voxels that left (W > 0, see grid_shift_mirror)
+__global__ __launch_bounds__(256) void tsdf_shift_gather_kernel(const int32_t* __restrict__ S, const int32_t* __restrict__ W,
+                                                                unsigned long long* __restrict__ scratch, GridDims g, int32_t dx, int32_t dy,
+                                                                int32_t dz, uint32_t n_vox, unsigned long long* stats) {
+    __shared__ unsigned long long sh[4][4];
+    const uint32_t pairs = (n_vox + 1u) / 2u;
+    unsigned long long exposed = 0, left = 0;
+    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < pairs; t += gridDim.x * 256u) {
+        const uint32_t c0 = 2u * t;
+        int i, j, k, si, sj, sk;
+        grid_ijk(g, c0, i, j, k);
+        const uint32_t n = n_vox - c0 < 2u ? n_vox - c0 : 2u;
+        uint32_t e[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t q = 0; q < 2; ++q) {
+            if (q < n) {
+                if (grid_shift_source(g, dx, dy, dz, i, j, k, si, sj, sk)) {
+                    const size_t at = grid_at(g, si, sj, sk);
+                    e[2 * q] = (uint32_t)S[at];
+                    e[2 * q + 1] = (uint32_t)W[at];
+                } else {
+                    grid_shift_mirror(g, i, j, k, si, sj, sk);
+                    left += W[grid_at(g, si, sj, sk)] > 0 ? 1u : 0u;
+                    ++exposed;
+                }
+                if (++i == g.nx) {   // the next voxel of the pair
+                    i = 0;
+                    if (++j == g.ny) {
+                        j = 0;
+                        ++k;
+                    }
+                }
+            }
+        }
+        if (n == 2u)
+            *reinterpret_cast<uint4*>(scratch + c0) = make_uint4(e[0], e[1], e[2], e[3]);
+        else
+            scratch[c0] = ((unsigned long long)e[1] << 32) | (unsigned long long)e[0];
+    }
+    unsigned long long a;
+    if (block_fold4(sh, exposed, left, 0ull, 0ull, a) && threadIdx.x < 2 && a) atomicAdd(stats + 1 + threadIdx.x, a);
+}
+
+// S, W of four voxels from their scratch words, which go back to zero
+__global__ __launch_bounds__(256) void tsdf_shift_unpack_kernel(int32_t* __restrict__ S, int32_t* __restrict__ W, unsigned long long* __restrict__ scratch,
+                                                                uint32_t n_vox) {
+    const uint32_t c0 = 4u * (blockIdx.x * blockDim.x + threadIdx.x);
+    if (c0 >= n_vox) return;
+    if (n_vox - c0 >= 4u) {
+        uint4* w = reinterpret_cast<uint4*>(scratch + c0);
+        const uint4 a = w[0], b = w[1];
+        *reinterpret_cast<uint4*>(S + c0) = make_uint4(a.x, a.z, b.x, b.z);
+        *reinterpret_cast<uint4*>(W + c0) = make_uint4(a.y, a.w, b.y, b.w);
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+        w[0] = zero;
+        w[1] = zero;
+    } else {   // the volume's last one to three voxels
+        for (uint32_t c = c0; c < n_vox; ++c) {
+            const unsigned long long word = scratch[c];
+            S[c] = (int32_t)(uint32_t)word;
+            W[c] = (int32_t)(uint32_t)(word >> 32);
+            scratch[c] = 0;
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void tsdf_metres_kernel(const int32_t* __restrict__ S, const int32_t* __restrict__ W, uint32_t n_vox,
@@ -209,6 +280,7 @@ int TsdfStore::configure(hipStream_t stream, const lv_tsdf_params& p) {
     LV_HIP(hipMemsetAsync(d_scratch, 0, nv * sizeof(unsigned long long), stream));
     prm = p;
     grid = g;
+    for (int a = 0; a < 3; ++a) origin0[a] = p.origin[a];
     n_vox = nv;
     rc = clear(stream);
     if (rc) return rc;
@@ -291,6 +363,31 @@ int TsdfStore::load(hipStream_t stream, const int32_t* S, const int32_t* W) {
     LV_HIP(hipMemcpyAsync(d_S, S, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemcpyAsync(d_W, W, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     LV_HIP(hipStreamSynchronize(stream));
+    return LV_OK;
+}
+
+int TsdfStore::recentre(hipStream_t stream, const int32_t d[3], const int32_t s_new[3], const float origin_new[3], uint64_t out[4]) {
+    int rc = stats.zero(stream);
+    if (rc) return rc;
+    const GridDims g{grid.occ.nx, grid.occ.ny, grid.occ.nz};
+    hipLaunchKernelGGL(tsdf_shift_gather_kernel, dim3(grid_stride_blocks((n_vox + 1) / 2)), dim3(256), 0, stream, d_S.p, d_W.p, d_scratch.p, g, d[0], d[1], d[2],
+                       (uint32_t)n_vox, stats.d.p);
+    hipLaunchKernelGGL(tsdf_shift_unpack_kernel, dim3(blocks_of((n_vox + 3) / 4)), dim3(256), 0, stream, d_S.p, d_W.p, d_scratch.p, (uint32_t)n_vox);
+    LV_HIP(hipGetLastError());
+    uint64_t st[4];
+    rc = stats.read(stream, st);   // (waits for the stream)
+    if (rc) return rc;
+    if (out) {
+        out[0] = (uint64_t)n_vox - st[1];   // a voxel is kept or exposed
+        out[1] = st[1];
+        out[2] = st[2];
+        out[3] = 0;
+    }
+    for (int a = 0; a < 3; ++a) {
+        shift[a] = s_new[a];
+        prm.origin[a] = origin_new[a];
+        grid.occ.origin[a] = origin_new[a];
+    }
     return LV_OK;
 }
 

@@ -249,6 +249,8 @@ struct TsdfStore {
     size_t n_vox = 0;
     DevBuf<int32_t> d_S, d_W;                 // by grid_at; W = 0: never observed
     DevBuf<unsigned long long> d_scratch;     // one packed word per voxel; all zero between calls
+    float origin0[3] = {0.f, 0.f, 0.f};       // the origin of configure(); prm.origin and grid.occ.origin follow the shift
+    int32_t shift[3] = {0, 0, 0};             // the accumulated recentre, in voxels
     Counters4 stats;
     PointStage pts;                           // every view's returns, or the query points
     DevBuf<float> d_out;                      // lv_tsdf_query's metres, lv_tsdf_fetch's metres
@@ -263,6 +265,8 @@ struct TsdfStore {
     int query(hipStream_t stream, const void* pts, size_t stride, size_t n, float* metres, int32_t* weight);
     int fetch(hipStream_t stream, int32_t* S, int32_t* W, float* metres);
     int load(hipStream_t stream, const int32_t* S, const int32_t* W);
+    // as OccStore::recentre; a voxel held evidence iff W > 0
+    int recentre(hipStream_t stream, const int32_t d[3], const int32_t s_new[3], const float origin_new[3], uint64_t out[4]);
     int mesh_build(hipStream_t stream, int min_weight, uint64_t counts[4]);
     int mesh_fetch(hipStream_t stream, float* xyz, int32_t* sub, uint32_t* tri);
     void mesh_release();

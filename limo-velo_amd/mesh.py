@@ -1,12 +1,14 @@
 """TSDF fusion and the surface mesh (include/limovelo_hip.h "TSDF and mesh"): thin helpers over Context.tsdf_*.  like_occupancy()
 gives a volume the footprint of an occupancy grid, integrate() fuses sweeps of any number, distance() reads the field in metres,
-build() returns the triangle mesh of the zero surface, save_ply() writes it (ASCII or binary little-endian), and save() / load()
-keep the volume as an .npz next to occupancy.save_grid's grid."""
+build() returns the triangle mesh of the zero surface, save_ply() writes it (ASCII or binary little-endian), save() / load()
+keep the volume as an .npz next to occupancy.save_grid's grid, and recentre() / follow() move the volume's box with the robot
+(lv_volume_recentre, "Rolling volumes")."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import capi
+from .occupancy import follow_shift
 
 MAX_VIEWS = 32   # views per lv_tsdf_integrate
 
@@ -98,3 +100,17 @@ def load(ctx, path: str):
     ctx.tsdf_configure(p)
     ctx.tsdf_load(S, W)
     return p
+
+
+def recentre(ctx, shift) -> np.ndarray:
+    """lv_volume_recentre of the TSDF volume by shift (3 whole voxels); a built mesh goes stale (its vertices are metres and stay
+    right).  Returns stats [4] uint64: voxels kept, exposed (now unobserved), that had W > 0 and left the volume, 0."""
+    return ctx.volume_recentre(capi.LV_VOLUME_SURFACE, shift)
+
+
+def follow(ctx, position, keep=0.25, step=32, axes=(True, True, False)):
+    """occupancy.follow() for the TSDF volume: returns the shift applied, (0, 0, 0) when the volume stayed."""
+    d = follow_shift(ctx.tsdf_params(), position, keep, step, axes)
+    if any(d):
+        recentre(ctx, d)
+    return d

@@ -9,7 +9,9 @@ turning costmap_2d's parameters into the planner's integer ones.  frontiers() la
 clusters (lv_occ_frontier_*, "Frontiers": explore_lite / frontier_exploration) and explore() ranks them by the planner's cost from
 the robot and hands back targets with their routes.  raycast() / line_of_sight() / simulate_scan() ask what a sensor would see
 from a place and view_gain() how much unknown space a pose would uncover (lv_occ_raycast, lv_occ_view_gain, "Ray casting"); with a
-gain_pattern explore() reports that gain at every target."""
+gain_pattern explore() reports that gain at every target.  recentre() / follow() move the grid's box with the robot by whole
+voxels (lv_volume_recentre, "Rolling volumes"), exposed_boxes() names the strips a shift uncovered and mark_from_map() fills them
+from the device map's points (lv_occ_mark)."""
 from __future__ import annotations
 
 import math
@@ -334,3 +336,74 @@ def explore(ctx, robot_xyz, robot_radius: float, z_band=None, reach=None, min_si
         for c, (line, _, _) in zip(np.flatnonzero(ok), routes(ctx, cl["target_xyz"][ok])):
             lines[c] = line[::-1]   # (walked from the target down to the robot: reversed)
     return cl, lines
+
+
+def recentre(ctx, shift) -> np.ndarray:
+    """lv_volume_recentre of the grid by shift (3 whole voxels): the box moves, the contents stay where they are in the world.
+    Returns stats [4] uint64: voxels kept, exposed (now never observed), that held evidence and left the grid, 0."""
+    return ctx.volume_recentre(capi.LV_VOLUME_OCC, shift)
+
+
+def follow_shift(params, position, keep=0.25, step=32, axes=(True, True, False)):
+    """The shift follow() would apply to a volume with `params` (origin, resolution, nx, ny, nz) for a robot at `position`: per
+    followed axis, 0 while the position's voxel is within keep * n voxels of the centre voxel n // 2, otherwise the multiple of
+    `step` nearest to that offset (halves away from zero are rounded up), within the +-2^20 of one recentre."""
+    F = np.float32
+    if int(step) < 1:
+        raise ValueError("step: at least one voxel")
+    n = (int(params.nx), int(params.ny), int(params.nz))
+    out = [0, 0, 0]
+    for a in range(3):
+        if not axes[a]:
+            continue
+        with np.errstate(all="ignore"):
+            v = np.floor((F(position[a]) - F(params.origin[a])) / F(params.resolution))   # (f32, as the device quantises)
+        if not np.isfinite(v):
+            raise ValueError("follow: the position is not finite")
+        off = int(v) - n[a] // 2
+        if abs(off) > float(keep) * n[a]:
+            d = int(step) * int(math.floor(off / int(step) + 0.5))
+            out[a] = max(-capi.VOLUME_SHIFT_LIMIT, min(capi.VOLUME_SHIFT_LIMIT, d))
+    return tuple(out)
+
+
+def follow(ctx, position, keep=0.25, step=32, axes=(True, True, False)):
+    """Keeps the grid round the robot: when the voxel of `position` is more than keep * n voxels from the grid's centre on a
+    followed axis (default x and y), the grid is recentred along that axis by the multiple of `step` voxels that brings the
+    position nearest the centre.  Returns the shift applied, (0, 0, 0) when the grid stayed."""
+    d = follow_shift(ctx.occ_params(), position, keep, step, axes)
+    if any(d):
+        recentre(ctx, d)
+    return d
+
+
+def exposed_boxes(params, shift):
+    """The voxels a recentre by `shift` left never observed, as up to three disjoint inclusive voxel boxes [(lo, hi)] of the
+    SHIFTED grid, in the form lv_occ_mark takes: the strip across x, the strip across y of what x kept, the strip across z of
+    what x and y kept.  (A shift of a whole grid or more gives the whole grid as one box.)"""
+    n = (int(params.nx), int(params.ny), int(params.nz))
+    kept, gone = [], []
+    for a in range(3):
+        d = max(-n[a], min(n[a], int(shift[a])))
+        kept.append((0, n[a] - d - 1) if d >= 0 else (-d, n[a] - 1))
+        gone.append((n[a] - d, n[a] - 1) if d > 0 else (0, -d - 1))   # (d == 0: 0..-1, empty)
+    full = [(0, n[a] - 1) for a in range(3)]
+    boxes = []
+    for a in range(3):
+        ranges = [kept[b] if b < a else (gone[b] if b == a else full[b]) for b in range(3)]
+        if all(lo <= hi for lo, hi in ranges):
+            boxes.append((tuple(r[0] for r in ranges), tuple(r[1] for r in ranges)))
+    return boxes
+
+
+def mark_from_map(ctx, box=None, min_points=1, only_unknown=True, l_mark=None) -> np.ndarray:
+    """lv_occ_mark from the living points of the device map: a voxel of `box` = (lo, hi) (inclusive voxel indices, default the
+    whole grid) that holds at least min_points of them becomes occupied by l_mark (default 0.85; negative marks free space).
+    only_unknown: only never observed voxels are written, ray evidence stays.  Returns stats [4] uint64: points used, voxels
+    holding >= min_points, voxels marked, voxels left alone because they were observed."""
+    kw = dict(min_points=int(min_points), only_unknown=int(bool(only_unknown)))
+    if box is not None:
+        kw.update(lo=box[0], hi=box[1])
+    if l_mark is not None:
+        kw["l_mark"] = float(l_mark)
+    return ctx.occ_mark(capi.default_occ_mark_params(**kw))
