@@ -1208,6 +1208,16 @@ int    lv_scan_deskew_window(lv_ctx* ctx, double t1, double t2, const lv_motion_
                              const lv_motion_state* Xt2, float downsample_prec, size_t* n_window);
 
 size_t lv_scan_size(lv_ctx* ctx);
+/* Which chain produced the current scan in the last lv_scan_deskew / lv_scan_downsample / lv_scan_deskew_window call: the
+ * one-launch chain for windows of up to 2048 points (SMALL), the two-launch chain for windows of up to 16 384 points from the
+ * LiDAR buffer (LARGE), or the general chain (GENERAL: also when one of the others declined and the general chain ran
+ * instead).  NONE: no such call yet, a call without points, or the scan was uploaded with lv_scan_set.  All three chains
+ * produce the same bits; this is for tests and diagnostics.  Reads a host field: no device work, no wait. */
+#define LV_SCAN_ROUTE_NONE    0
+#define LV_SCAN_ROUTE_SMALL   1
+#define LV_SCAN_ROUTE_LARGE   2
+#define LV_SCAN_ROUTE_GENERAL 3
+int    lv_scan_route(lv_ctx* ctx);
 int    lv_scan_fetch(lv_ctx* ctx, float* xyz_out, size_t capacity);
 
 /* One IKFoM::h_share_model evaluation (registered at src/Modules/Localizator.cpp:112) =

@@ -24,7 +24,7 @@ NS = 23
 ABI_SYMBOLS = [
     "lv_default_params", "lv_last_error", "lv_version", "lv_create", "lv_destroy", "lv_set_stream", "lv_get_stream",
     "lv_synchronize", "lv_map_build", "lv_map_add", "lv_map_add_scan", "lv_map_evict_box", "lv_map_evict_oldest", "lv_map_relinearise", "lv_map_get_stats",
-    "lv_map_size", "lv_map_fetch", "lv_scan_set", "lv_scan_deskew", "lv_scan_downsample", "lv_scan_size", "lv_scan_fetch", "lv_iterate", "lv_pseudo_measurement",
+    "lv_map_size", "lv_map_fetch", "lv_scan_set", "lv_scan_deskew", "lv_scan_downsample", "lv_scan_size", "lv_scan_route", "lv_scan_fetch", "lv_iterate", "lv_pseudo_measurement",
     "lv_map_relinearise_async", "lv_map_reserve_rebuild", "lv_map_rebuild_status", "lv_update", "lv_filter_set", "lv_filter_get", "lv_predict", "lv_correct", "lv_get_degeneracy_values", "lv_update_begin", "lv_pass_reduce", "lv_sums_device_ptr", "lv_set_sums_buffer", "lv_pass_solve", "lv_update_end",
     "lv_set_capture", "lv_fetch_knn", "lv_fetch_matches", "lv_fetch_neighbors", "lv_set_record_dump", "lv_last_update_fused", "lv_last_passes", "lv_set_fused_pass", "lv_set_option", "lv_get_pass_clocks", "lv_pass_geometry", "lv_fetch_rows", "lv_calculate_H", "lv_get_timing", "lv_set_profiling", "lv_get_phase_clocks", "lv_get_solve_clocks", "lv_get_level_histogram",
     "lv_comm_unique_id", "lv_comm_init", "lv_comm_destroy", "lv_comm_world", "lv_comm_set_shard_max", "lv_set_comm_fused", "lv_comm_set_host_gather", "lv_comm_peer_export", "lv_comm_peer_init",
@@ -510,6 +510,7 @@ class IngestParams(C.Structure):  # lv_ingest_params
 
 POINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("z", "f4"), ("pad_", "f4"), ("time", "f8"), ("intensity", "f4"), ("range", "f4")])
 LIDAR_VELODYNE, LIDAR_HESAI, LIDAR_OUSTER, LIDAR_CUSTOM = 0, 1, 2, 3
+SCAN_ROUTE_NONE, SCAN_ROUTE_SMALL, SCAN_ROUTE_LARGE, SCAN_ROUTE_GENERAL = 0, 1, 2, 3   # LV_SCAN_ROUTE_*
 
 
 class Params(C.Structure):
@@ -587,6 +588,8 @@ def load_library() -> C.CDLL:
         lib.lv_version.restype = C.c_char_p
         lib.lv_scan_size.restype = C.c_size_t
         lib.lv_scan_size.argtypes = [C.c_void_p]
+        lib.lv_scan_route.restype = C.c_int
+        lib.lv_scan_route.argtypes = [C.c_void_p]
         lib.lv_map_size.restype = C.c_size_t
         lib.lv_cloud_size.restype = C.c_size_t
         lib.lv_cloud_size.argtypes = [C.c_void_p]
@@ -1639,6 +1642,10 @@ class Context:
 
     def scan_size(self) -> int:
         return int(self.lib.lv_scan_size(self.h))
+
+    def scan_route(self) -> int:
+        """SCAN_ROUTE_*: the chain that produced the current scan (a decline followed by the general chain: general)."""
+        return int(self.lib.lv_scan_route(self.h))
 
     def scan_fetch(self) -> np.ndarray:
         n = self.scan_size()

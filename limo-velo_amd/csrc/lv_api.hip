@@ -1370,6 +1370,7 @@ int lv_scan_set(lv_ctx* c, const void* points, size_t stride, size_t n) {
         if (z < bmin[2]) bmin[2] = z;
     }
     c->scan.n = (uint32_t)n;
+    c->scan.route = LV_SCAN_ROUTE_NONE;   // (uploaded as it is: no voxel grid ran)
     c->ranks.shard_max = 0;   // (a new scan: the caller tells its largest shard again)
     c->dbg_valid = false;
     c->qrec_valid = false;
@@ -1388,6 +1389,7 @@ int lv_scan_deskew(lv_ctx* c, const void* points, size_t stride, size_t time_off
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
+    c->scan.route = LV_SCAN_ROUTE_NONE;
     c->ranks.shard_max = 0;
     if (n == 0) return LV_OK;
     int rc = ensure_stage(c, n + (n + 1) / 2);  // float4 xyz + packed doubles behind them
@@ -1419,6 +1421,7 @@ int lv_scan_downsample(lv_ctx* c, const void* points, size_t stride, size_t n, f
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
+    c->scan.route = LV_SCAN_ROUTE_NONE;
     c->ranks.shard_max = 0;
     if (n == 0) return LV_OK;
     int rc = ensure_stage(c, n);
@@ -1595,6 +1598,7 @@ int lv_scan_deskew_window(lv_ctx* c, double t1, double t2, const lv_motion_state
     c->dbg_valid = false;
     c->qrec_valid = false;
     c->scan.n = 0;
+    c->scan.route = LV_SCAN_ROUTE_NONE;
     c->ranks.shard_max = 0;
     uint32_t lo = 0, hi = 0;
     int rc = c->scan.reserve_raw(1, n_states);   // (the bounds words exist: the window kernel resets them on the way)
@@ -1628,6 +1632,7 @@ int lv_scan_deskew_window(lv_ctx* c, double t1, double t2, const lv_motion_state
 }
 
 size_t lv_scan_size(lv_ctx* c) { return c ? c->scan.n : 0; }
+int lv_scan_route(lv_ctx* c) { return c ? c->scan.route : LV_SCAN_ROUTE_NONE; }
 
 int lv_scan_fetch(lv_ctx* c, float* xyz_out, size_t capacity) {
     LV_CHECK_CTX(c);

@@ -322,6 +322,7 @@ struct ScanStore {
     size_t sort_tmp_bytes = 0;
     size_t capacity = 0;
     uint32_t n = 0;
+    int route = 0;               // what produced the scan: LV_SCAN_ROUTE_* (lv_scan_route); a decline followed by the general chain: general
     uint32_t* d_tile_order = nullptr;  // search-kernel tiles, farthest-from-sensor first (order_tiles)
     uint32_t n_tiles = 0, tile_cap = 0;
     uint32_t tile_points = 0;          // scan points per search-kernel workgroup (256 / lanes_per_query); 0: no ordering

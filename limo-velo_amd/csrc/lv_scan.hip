@@ -698,6 +698,7 @@ int ScanStore::window_small(hipStream_t stream, const float4* src, uint32_t n_in
     if (!note_wait(notes, 0, 2, seq, v, stream)) { set_error("window kernel did not report"); return LV_EHIP; }
     if (v[1]) { *fell_back = true; return LV_OK; }
     n = v[0];
+    route = LV_SCAN_ROUTE_SMALL;
     n_tiles = n ? (n + tile_points - 1) / tile_points : 0;
     return LV_OK;
 }
@@ -740,6 +741,7 @@ int ScanStore::window_large(hipStream_t stream, const CloudPoint* cloud, uint32_
     }
     if (v[1]) { *fell_back = true; return LV_OK; }
     n = v[0];
+    route = LV_SCAN_ROUTE_LARGE;
     n_tiles = n ? (n + tile_points - 1) / tile_points : 0;
     return LV_OK;
 }
@@ -775,6 +777,7 @@ int ScanStore::voxel_and_sort(hipStream_t stream, uint32_t n_in, float leaf, flo
     LV_HIP(hipStreamSynchronize(stream));
     if (leaf > 0.f) n_out = hb[6];
     n = n_out;
+    route = LV_SCAN_ROUTE_GENERAL;
     if (hb[0] == 0xFFFFFFFFu) n = 0;  // no finite point survived
     if (n == 0) return LV_OK;
     auto unflip = [](unsigned u) { unsigned v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; float f; memcpy(&f, &v, 4); return f; };

@@ -110,7 +110,15 @@ def test_large_window_chain_equals_the_general_chain(capi, oracle, lv, scene_sma
     """Windows beyond 2048 raw points take four launches + the library sort (deskew_bounds_kernel straight from the LiDAR
     buffer, leaf keys, sort, window_tail_kernel: heads, scan, centroids, Morton order, tile order by one workgroup, the counts
     back as a note) instead of the thirteen-launch chain; beyond 4096 points OUT the tail declines and the general chain runs.
-    Same points in the same order, the same Morton / tile order behind them: the update that consumes the scan is bit-identical."""
+    Same points in the same order, the same Morton / tile order behind them: the update that consumes the scan is bit-identical.
+
+    The route each case takes (lv_scan_route) is asserted.  The tail finishes only in (6000, 0.5): 2568 points in, 2558 out.
+    (20000, 1.0), (40000, 2.0) and (40000, 0.5, 0.2) have 7040, 7952 and 12919 points out: the tail DECLINES and both arms run
+    the general chain.  (40000, 1.0, 0.45) and (3000, 0.5) hold 1895 and 1427 points: the one-launch chain for small windows
+    takes them in both arms.  The large route with leaves of many points: tests/test_gpu_voxel_grid.py."""
+    routes = {(6000, 0.5): (capi.SCAN_ROUTE_LARGE, capi.SCAN_ROUTE_GENERAL), (40000, 1.0): (capi.SCAN_ROUTE_SMALL, capi.SCAN_ROUTE_SMALL),
+              (3000, 0.5): (capi.SCAN_ROUTE_SMALL, capi.SCAN_ROUTE_SMALL)}
+    route_on, route_off = routes.get((n_msg, leaf), (capi.SCAN_ROUTE_GENERAL, capi.SCAN_ROUTE_GENERAL))
     sc = scene_small
     raw, f, stamp = cm.make_message("velodyne", n_msg, seed=11, wire=True, stamp_sec=50.2)
     gf, of = _formats(capi, oracle, f)
@@ -136,6 +144,7 @@ def test_large_window_chain_equals_the_general_chain(capi, oracle, lv, scene_sma
             ctx.set_option("large_window", on)
             nw = ctx.scan_deskew_window(t1, t2, states, xt2, downsample_prec=leaf)
             got = ctx.scan_fetch()
+            assert ctx.scan_route() == (route_on if on else route_off), (on, ctx.scan_route())
             x, P, passes, tr, sums = ctx.update(sc["x_init"], sc["P0"])
             res[on] = (nw, got, x, P, passes, [s_["n_valid"] for s_ in sums])
     assert res[1][0] == res[0][0] == len(sel)
