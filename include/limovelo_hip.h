@@ -992,6 +992,47 @@ void lv_default_rollout_params(lv_rollout_params* p);
 int  lv_occ_rollout(lv_ctx* ctx, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint,
                     size_t n_fp, lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best);
 
+/* ---- Localisation ------------------------------------------------------------------------------------
+ * The measurement update of AMCL on the device: K candidate poses are weighed against one scan by the likelihood field, which is
+ * a lookup of every scan end point in the distance field (Probabilistic Robotics, table 6.3; amcl's likelihood_field model; the
+ * reference has no counterpart).  A particle filter around it finds and tracks the robot in a saved grid from a scan alone, with
+ * no point map and no pose prior.  Every f32 operation and its order are stated below and the sine and cosine are the fixed
+ * polynomial of "Rollouts", so a weight is exactly defined: a pure function of the field and the arguments, the same bits
+ * whatever the schedule.
+ *   reads    the distance field last built, planar or 3-D, with the field's own origin and resolution (the ones it was built
+ *            at: it answers after lv_volume_recentre as it did before).  A stale field is used as it is.  Nothing is
+ *            snapshotted, and no bit of the grid, the field, the plan or the frontier result changes, nor any stale flag.
+ *   inputs   poses [K][4] = (x, y, z, th), world metres and radians; beams [B][3] = the scan's end points (ex, ey, ez) in a
+ *            gravity-aligned body frame (x forward, z up); table = n_table costs, the caller's negative log-likelihood of an end
+ *            point by the SQUARED voxel distance to the nearest obstacle, entry t for s2 = t (the caller supplies it as the
+ *            planner's caller supplies the clearance-to-cost table).  Nothing here needs to be finite.
+ *   rule     per particle, all in f32, no operation fused, in exactly this order.  th is USABLE iff fabsf(th) < 1048576.0f (NaN
+ *            is not).  An unusable th gives n_in = 0 and the score UINT64_MAX.  Otherwise (sn, cs) = the sine and cosine of th
+ *            by the polynomial of "Rollouts", and for beam b: px = x + (cs * ex - sn * ey); py = y + (sn * ex + cs * ey);
+ *            pz = z + ez.  The cell of (px, py, pz) is the one lv_occ_distance_query finds: quantised per axis (q, then q >> 8)
+ *            and tested against the field; in a planar field z is not used and may be anything.  A point without a cell
+ *            (non-finite, too far to quantise, outside the field) costs out_cost.  Otherwise s2 is the field's value there,
+ *            idx = 0 if s2 <= 0, else min(s2, n_table - 1) (so LV_OCC_FAR takes the last entry and the inside of a signed
+ *            field entry 0), and the cost is table[idx].
+ *   result   n_in = the number of beams that have a cell; score = the sum of the B costs in uint64; if n_in < min_inside the
+ *            score is UINT64_MAX instead (n_in stays).
+ *   best     best[0] = the index with the least (score, index) among the scores that are not UINT64_MAX, best[1] = its score;
+ *            both -1 when there is none.
+ *   limits   K 0..2^20, poses non-NULL when K > 0; B 1..65536; K * B <= 2^30; n_table 1..4096; every table entry and out_cost
+ *            <= 2^24, so a score stays below 2^40; min_inside 0..B; beams and table non-NULL; score, n_in and best may each be
+ *            NULL, but not all three.  K = 0 succeeds and writes best only; like every other call it is answered after the
+ *            states below (LV_ESTATE comes first).
+ * Parameters and NULL arguments are judged before the context (LV_EINVAL, nothing written; "null context" comes last);
+ * LV_ESTATE before lv_occ_configure and before a field build.  A refused call writes nothing.  Nothing is allocated before the
+ * first call; lv_occ_configure and lv_destroy free everything.  The call runs on the context's stream and returns when its host
+ * outputs are written. */
+typedef struct lv_mcl_params { uint32_t out_cost; int min_inside; } lv_mcl_params;
+/* out_cost 0 (the table's last entry is NOT implied), min_inside 1. */
+void lv_default_mcl_params(lv_mcl_params* p);
+/* poses: K x 4 floats; beams: B x 3 floats; table: n_table values; score: K values; n_in: K values; best: 2 values. */
+int  lv_occ_mcl_weigh(lv_ctx* ctx, const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B,
+                      const uint32_t* table, size_t n_table, uint64_t* score, uint32_t* n_in, int64_t* best);
+
 /* ---- TSDF and mesh -------------------------------------------------------------------------------------
  * A truncated signed distance field fused from the sweeps, and a triangle mesh of its zero surface: the TSDF layer of Voxblox
  * and nvblox with its mesh integrator ("a mesh of what the robot saw"; the reference has no counterpart).  The sweeps are the

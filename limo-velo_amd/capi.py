@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "lv_default_elevation_params", "lv_elev_build", "lv_elev_fetch", "lv_elev_query", "lv_elev_info", "lv_elev_clear",
     "lv_occ_distance_build_cells",
     "lv_default_rollout_params", "lv_occ_rollout",
+    "lv_default_mcl_params", "lv_occ_mcl_weigh",
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
@@ -350,6 +351,19 @@ ROLLOUT_ARGTYPES = {
 }
 
 
+class MclParams(C.Structure):  # lv_mcl_params
+    _fields_ = [("out_cost", C.c_uint32), ("min_inside", C.c_int)]
+
+
+MCL_NO_SCORE = 2 ** 64 - 1
+
+# ctypes signatures of the localisation (include/limovelo_hip.h "Localisation"; tests/test_occ_mcl_abi.py)
+MCL_ARGTYPES = {
+    "lv_occ_mcl_weigh": [C.c_void_p, C.POINTER(MclParams), C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float), C.c_size_t,
+                         C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)],
+}
+
+
 class TsdfParams(C.Structure):  # lv_tsdf_params
     _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("min_range", C.c_float), ("max_range", C.c_float), ("trunc_cells", C.c_int), ("max_weight", C.c_int), ("carve", C.c_int)]
@@ -631,13 +645,15 @@ def load_library() -> C.CDLL:
         lib.lv_default_elevation_params.argtypes = [C.POINTER(ElevationParams)]
         lib.lv_default_rollout_params.restype = None
         lib.lv_default_rollout_params.argtypes = [C.POINTER(RolloutParams)]
+        lib.lv_default_mcl_params.restype = None
+        lib.lv_default_mcl_params.argtypes = [C.POINTER(MclParams)]
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         lib.lv_default_occ_mark_params.restype = None
         lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -775,6 +791,14 @@ def default_elevation_params(**kw) -> ElevationParams:
 def default_rollout_params(**kw) -> RolloutParams:
     p = RolloutParams()
     load_library().lv_default_rollout_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_mcl_params(**kw) -> MclParams:
+    p = MclParams()
+    load_library().lv_default_mcl_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1366,6 +1390,40 @@ class Context:
         self._check(self.lib.lv_occ_rollout(self.h, C.byref(p), s0.ctypes.data_as(fptr), u.ctypes.data_as(fptr) if K else None, C.c_size_t(K),
                                             fp.ctypes.data_as(fptr) if len(fp) else None, C.c_size_t(len(fp)), ptr("results", RolloutResult),
                                             ptr("poses", C.c_float), ptr("score", C.c_uint64), ptr("best", C.c_int64)))
+        return out
+
+    # --- localisation (include/limovelo_hip.h "Localisation")
+    def occ_mcl_weigh(self, poses, beams, table, params: MclParams | None = None, want=("score", "n_in", "best")) -> dict:
+        """lv_occ_mcl_weigh of the poses [K, 4] (x, y, z, th) under the scan end points beams [B, 3] (body frame) and the cost
+        table [n_table] uint32 by squared voxel distance.  want: which of "score" ([K] uint64, MCL_NO_SCORE where not eligible),
+        "n_in" ([K] uint32) and "best" ([2] int64: index, score; -1, -1 if none) to fetch; returns them in a dict."""
+        p = params if params is not None else default_mcl_params()
+        x = np.ascontiguousarray(poses, np.float32)
+        e = np.ascontiguousarray(beams, np.float32)
+        t = np.ascontiguousarray(table, np.uint32)
+        if x.ndim != 2 or x.shape[1] != 4:
+            raise ValueError("occ_mcl_weigh: poses [K, 4]")
+        if e.ndim != 2 or e.shape[1] != 3:
+            raise ValueError("occ_mcl_weigh: beams [B, 3]")
+        if t.ndim != 1:
+            raise ValueError("occ_mcl_weigh: table [n_table]")
+        K = x.shape[0]
+        out = {}
+        if "score" in want:
+            out["score"] = np.zeros(K, np.uint64)
+        if "n_in" in want:
+            out["n_in"] = np.zeros(K, np.uint32)
+        if "best" in want:
+            out["best"] = np.zeros(2, np.int64)
+
+        def ptr(name, ct):
+            return out[name].ctypes.data_as(C.POINTER(ct)) if name in out else None
+
+        fptr = C.POINTER(C.c_float)
+        self._check(self.lib.lv_occ_mcl_weigh(self.h, C.byref(p), x.ctypes.data_as(fptr) if K else None, C.c_size_t(K),
+                                              e.ctypes.data_as(fptr) if len(e) else None, C.c_size_t(len(e)),
+                                              t.ctypes.data_as(C.POINTER(C.c_uint32)) if len(t) else None, C.c_size_t(len(t)),
+                                              ptr("score", C.c_uint64), ptr("n_in", C.c_uint32), ptr("best", C.c_int64)))
         return out
 
     def occ_view_gain(self, views) -> np.ndarray:

@@ -20,6 +20,7 @@
 #include "lv_ray.hpp"
 #include "lv_elevation.hpp"
 #include "lv_rollout.hpp"
+#include "lv_mcl.hpp"
 #include "lv_occupancy.hpp"
 #include "lv_tsdf.hpp"
 
@@ -64,6 +65,7 @@ struct lv_ctx {
     RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     RolloutStore rollout;   // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
+    MclStore mcl;       // lv_occ_mcl_weigh: its own buffers (lv_mcl.hip); nothing allocated before the first call
     TsdfStore tsdf;     // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
@@ -654,6 +656,7 @@ void lv_destroy(lv_ctx* c) {
     c->place.release();
     c->ray.release();
     c->rollout.release();
+    c->mcl.release();
     c->elev.release();
     c->frontier.release();
     c->plan.release();
@@ -2282,6 +2285,7 @@ int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     c->frontier.release();   // (the frontier to the grid too)
     c->ray.release();        // (and the packed states)
     c->rollout.release();    // (and the rollouts' buffers)
+    c->mcl.release();        // (and the localisation's)
     return c->occ.configure(c->stream, *p);
 }
 
@@ -2660,6 +2664,26 @@ int lv_occ_rollout(lv_ctx* c, const lv_rollout_params* p, const float* start, co
         }
     }
     return c->rollout.run(c->stream, c->plan, c->dist, *p, start, controls, K, footprint, n_fp, results, poses, score, best);
+}
+
+// ---- Localisation (lv_mcl.hip)
+void lv_default_mcl_params(lv_mcl_params* p) {
+    if (!p) return;
+    *p = lv_mcl_params{};
+    p->out_cost = 0;
+    p->min_inside = 1;
+}
+
+// (the arguments are judged before the context, as lv_occ_rollout's are)
+int lv_occ_mcl_weigh(lv_ctx* c, const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B, const uint32_t* table,
+                     size_t n_table, uint64_t* score, uint32_t* n_in, int64_t* best) {
+    if (const char* why = mcl_check(p, poses, K, beams, B, table, n_table, score, n_in, best)) {
+        set_error("lv_occ_mcl_weigh: %s", why);
+        return LV_EINVAL;
+    }
+    LV_OCC_CTX(c);
+    LV_DIST_BUILT(c);
+    return c->mcl.run(c->stream, c->dist, *p, poses, K, beams, B, table, n_table, score, n_in, best);
 }
 
 // ---- TSDF and mesh (lv_tsdf.hip)
