@@ -1312,6 +1312,66 @@ int lv_correct(lv_ctx* ctx, int* passes);
  * stated and tested tolerance 1e-9 relative to the largest eigenvalue (tests/test_gpu_configs.py, tests/test_gpu_parity.py). */
 int lv_get_degeneracy_values(lv_ctx* ctx, double* eig, int capacity_passes, int* n_passes);
 
+/* ---- Aiding observations -----------------------------------------------------------------------------
+ * Measurements other than the scan — a GPS or barometer position, a wheel or Doppler velocity, a zero-velocity update, an AHRS
+ * attitude — applied to the resident filter on the device as one more update of the same error-state filter, in order with the
+ * queued lv_predict calls and without a host round trip:  lv_filter_set -> lv_predict ... -> lv_observe -> lv_correct -> lv_filter_get.
+ *
+ * dofs as lv_predict: pos 0, rot 3, offR 6, offT 9, vel 12, bg 15, ba 18, grav 21 (2); rot [+] d = R Exp(d).  R = the rotation
+ * matrix of x.rot, p = x.pos, v = x.vel:
+ *   kind            h(x)           innovation y            non-zero blocks of H (3 x 23): first, second
+ *   POSITION        p + R lever    z - h                   pos: I              rot: -(R hat(lever))
+ *   VELOCITY_WORLD  v              z - h  (ZUPT: z = 0)    vel: I              -
+ *   VELOCITY_BODY   R^T v          z - h                   vel: R^T            rot: hat(R^T v)
+ *   ATTITUDE        -              so3_log(q^-1 (x) z)     rot: I              -       (first order in y: the right Jacobian of
+ *                                                                                       the logarithm is taken as I)
+ * Rule per observation, all f64; the rows k = 0..m-1 are the components whose mask bit is set, ascending (m = popcount(mask));
+ * H_k, y_k, R_kl below are the rows / entries of those components.  Every sum starts at 0.0 and adds its terms left to right in
+ * the order written; "blocks" means the first block's three columns in ascending order, then the second block's:
+ *   1. PHt[i][k] = sum over blocks of P[i][c] H_k[c]                          (23 x m)
+ *      S[k][l]   = (sum over blocks of H_k[c] PHt[c][l]) + R_kl               (l <= k: the lower triangle is what is used)
+ *   2. Cholesky S = L L^T by columns j = 0..m-1: d = S[j][j] - L[j][0]^2 - ... - L[j][j-1]^2 (subtracted one after the other);
+ *      d <= 0 or non-finite: status 2; L[j][j] = sqrt(d); for i > j: L[i][j] = (S[i][j] - L[i][0] L[j][0] - ... ) / L[j][j]
+ *   3. w = L^-1 y by forward substitution (w[i] = (y[i] - L[i][0] w[0] - ...) / L[i][i]); nis = w[0]^2 + ... ; gate > 0 and
+ *      nis > gate: status 1
+ *   4. row i of K: t = L^-1 PHt[i] forward, K[i] = L^-T t backward (K[i][k] = (t[k] - L[k+1][k] K[i][k+1] - ...) / L[k][k], terms in
+ *      ascending row of L); dx[i] = K[i][0] y_0 + ...; x <- x [+] dx (the state's boxplus: so3 blocks R Exp(d), S2 gravity)
+ *   5. A[i][c] = (i == c) - (K[i][0] H_0[c] + ...) on the columns of the blocks, (i == c) elsewhere;
+ *      AP[i][j] = A[i][0] P[0][j] + ... + A[i][22] P[22][j];  KR[i][l] = K[i][0] R_0l + ...
+ *      P[i][j] = (AP[i][0] A[j][0] + ... + AP[i][22] A[j][22]) + (KR[i][0] K[j][0] + ...)        (Joseph form)
+ *   6. ... computed for i <= j and stored to [i][j] and [j][i]: the stored P is exactly symmetric.
+ * The device contracts a * b + c into fused operations and takes sin / cos / atan from its own few-ulp versions, so it follows
+ * this rule to rounding (1e-12 on a single observation, tests/test_gpu_observe.py), not bit for bit.  The reset Jacobian of the
+ * SO(3) and S2 blocks after [+] is not applied to P (second order in dx; DESIGN.md "knowing differences").
+ * Status 1 and 2 leave x and P exactly as they were; rows = m, y = the full 3-dim innovation, nis = 0 with status 2.
+ *
+ * lv_observe applies obs[0..n-1] (1 <= n <= LV_OBSERVE_BATCH) one after the other in ONE launch: the second sees the first's
+ * posterior.  Queued predictions are launched first, so calls take effect in the order they were made.  out == NULL: enqueue
+ * only (the 100 Hz form); out != NULL: waits for the context's stream and writes n results.  lv_observe_results waits and returns
+ * the results of the last lv_observe (*n = their number, may be NULL; capacity below it: LV_EINVAL; LV_ESTATE before any).
+ * An unknown kind, a mask outside 1..7, a non-finite z, R, lever or gate, gate < 0, a non-zero lever with a kind other than
+ * POSITION, an ATTITUDE z with | |z| - 1 | > 1e-6, n outside 1..LV_OBSERVE_BATCH or a NULL obs give LV_EINVAL before anything
+ * is enqueued: the filter and the queue are untouched.  LV_ESTATE before lv_filter_set.  Afterwards the filter is on the device
+ * (a following lv_correct starts from it, lv_map_add_scan transforms with it, lv_filter_get copies it).
+ * With a multi-GPU communicator the filter is replicated and the update deterministic: every rank calls lv_observe with the same
+ * observations, as with lv_predict. */
+enum { LV_OBS_POSITION = 1, LV_OBS_VELOCITY_WORLD = 2, LV_OBS_VELOCITY_BODY = 3, LV_OBS_ATTITUDE = 4 };
+typedef struct lv_observation {
+    int    kind;       /* LV_OBS_* */
+    int    mask;       /* bits 0..2: which components of the 3-dim innovation are used; 1..7 */
+    double z[4];       /* POSITION / VELOCITY_*: z[0..2]; ATTITUDE: unit quaternion x,y,z,w (the state's order) */
+    double R[9];       /* 3x3 row-major covariance of the full 3-dim observation; the masked rows/cols are used */
+    double lever[3];   /* POSITION only: antenna in the IMU frame; others: must be 0 */
+    double gate;       /* > 0: reject when NIS > gate; 0: no gate */
+} lv_observation;
+typedef struct lv_observe_result { int status; int rows; double nis; double y[3]; } lv_observe_result;
+/* status: 0 applied, 1 gated out, 2 S not positive definite (state untouched in 1 and 2) */
+#define LV_OBSERVE_BATCH 8
+/* kind as given, mask 7, z = 0 (ATTITUDE: the identity quaternion), R = I, lever = 0, gate = 0 */
+void lv_default_observation(lv_observation* o, int kind);
+int  lv_observe(lv_ctx* ctx, const lv_observation* obs, size_t n, lv_observe_result* out /* NULL: no wait */);
+int  lv_observe_results(lv_ctx* ctx, lv_observe_result* out, size_t capacity, size_t* n);  /* of the last lv_observe; waits */
+
 /* Split form of lv_update for multi-GPU runs (scan points sharded across ranks, map replicated):
  *   lv_update_begin(x, P)
  *   repeat MAX_NUM_ITERS+1 times:

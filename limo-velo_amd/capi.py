@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
+    "lv_default_observation", "lv_observe", "lv_observe_results",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -364,6 +365,41 @@ MCL_ARGTYPES = {
 }
 
 
+OBS_POSITION, OBS_VELOCITY_WORLD, OBS_VELOCITY_BODY, OBS_ATTITUDE = 1, 2, 3, 4   # LV_OBS_*
+OBSERVE_BATCH = 8   # LV_OBSERVE_BATCH
+
+
+class Observation(C.Structure):  # lv_observation
+    _fields_ = [("kind", C.c_int), ("mask", C.c_int), ("z", C.c_double * 4), ("R", C.c_double * 9), ("lever", C.c_double * 3),
+                ("gate", C.c_double)]
+
+
+class ObserveResult(C.Structure):  # lv_observe_result
+    _fields_ = [("status", C.c_int), ("rows", C.c_int), ("nis", C.c_double), ("y", C.c_double * 3)]
+
+
+# ctypes signatures of the aiding observations (include/limovelo_hip.h "Aiding observations"; tests/test_observe_abi.py)
+OBSERVE_ARGTYPES = {
+    "lv_observe": [C.c_void_p, C.POINTER(Observation), C.c_size_t, C.POINTER(ObserveResult)],
+    "lv_observe_results": [C.c_void_p, C.POINTER(ObserveResult), C.c_size_t, C.POINTER(C.c_size_t)],
+}
+
+
+def default_observation(kind: int, **kw) -> Observation:
+    o = Observation()
+    load_library().lv_default_observation(C.byref(o), int(kind))
+    for k, v in kw.items():
+        if k in ("z", "R", "lever"):
+            a = np.asarray(v, np.float64).ravel()
+            arr = getattr(o, k)
+            assert a.size <= len(arr), (k, a.size)
+            for i, t in enumerate(a):
+                arr[i] = float(t)
+        else:
+            setattr(o, k, v)
+    return o
+
+
 class TsdfParams(C.Structure):  # lv_tsdf_params
     _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("min_range", C.c_float), ("max_range", C.c_float), ("trunc_cells", C.c_int), ("max_weight", C.c_int), ("carve", C.c_int)]
@@ -651,9 +687,12 @@ def load_library() -> C.CDLL:
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         lib.lv_default_occ_mark_params.restype = None
         lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
+        lib.lv_default_observation.restype = None
+        lib.lv_default_observation.argtypes = [C.POINTER(Observation), C.c_int]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES}.items():
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
+                               **OBSERVE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -1777,6 +1816,29 @@ class Context:
         g = np.ascontiguousarray(gyro, np.float64)
         self._check(self.lib.lv_predict(self.h, C.c_double(dt), Qm.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p),
                                         g.ctypes.data_as(C.c_void_p)))
+
+    # --- aiding observations (include/limovelo_hip.h "Aiding observations"; limo_velo_amd.aiding builds the records)
+    def observe(self, obs_list, wait=False):
+        """Applies 1..OBSERVE_BATCH observations (capi.Observation, or one of them) to the resident filter, in order, behind the
+        queued predictions.  wait=False only enqueues and returns None; wait=True returns the results as observe_results() does."""
+        if isinstance(obs_list, Observation):
+            obs_list = [obs_list]
+        n = len(obs_list)
+        arr = (Observation * max(n, 1))(*obs_list)
+        out = (ObserveResult * max(n, 1))() if wait else None
+        self._check(self.lib.lv_observe(self.h, arr, n, out))
+        return [self._observe_dict(r) for r in out[:n]] if wait else None
+
+    def observe_results(self):
+        """The results of the last observe(): a list of dicts {status, rows, nis, y}.  Waits for the stream."""
+        out = (ObserveResult * OBSERVE_BATCH)()
+        n = C.c_size_t(0)
+        self._check(self.lib.lv_observe_results(self.h, out, OBSERVE_BATCH, C.byref(n)))
+        return [self._observe_dict(r) for r in out[: n.value]]
+
+    @staticmethod
+    def _observe_dict(r):
+        return dict(status=int(r.status), rows=int(r.rows), nis=float(r.nis), y=np.array(r.y[:], np.float64))
 
     def correct(self, want_passes=True) -> int:
         p = C.c_int(0)

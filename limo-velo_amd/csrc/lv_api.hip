@@ -80,6 +80,8 @@ struct lv_ctx {
 
     KfDev* d_kf = nullptr;
     ResidentFilter filter;   // x, P resident between lv_filter_set / lv_predict / lv_correct / lv_filter_get (lv_filter.hpp)
+    lv_observe_result* d_obs = nullptr;   // lv_observe: the records of the last call (LV_OBSERVE_BATCH), and how many
+    int n_obs = 0;
     KfDev* h_kf = nullptr;  // pinned mirror (logs / trace downloads)
     KfHostIO* h_io = nullptr;  // pinned, host-mapped mailbox: update inputs and results (no copy kernels)
     KfHostIO* d_io = nullptr;  // its device address
@@ -608,6 +610,8 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     LV_HIP(hipMalloc(&c->d_kf, sizeof(KfDev)));
     LV_HIP(hipMemset(c->d_kf, 0, sizeof(KfDev)));
     if (int rf = c->filter.alloc()) return rf;
+    LV_HIP(hipMalloc(&c->d_obs, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
+    LV_HIP(hipMemset(c->d_obs, 0, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
     LV_HIP(hipHostMalloc((void**)&c->h_kf, sizeof(KfDev), hipHostMallocDefault));
     std::memset(c->h_kf, 0, sizeof(KfDev));
     LV_HIP(hipHostMalloc((void**)&c->h_io, sizeof(KfHostIO), hipHostMallocMapped));
@@ -670,6 +674,7 @@ void lv_destroy(lv_ctx* c) {
     if (c->h_kf) hipHostFree(c->h_kf);
     if (c->h_io) hipHostFree(c->h_io);
     c->filter.release();
+    hipFree(c->d_obs);
     if (c->h_states_ring) hipHostFree(c->h_states_ring);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_cpart[0]); hipFree(c->d_cpart[1]); hipFree(c->d_pclk); hipFree(c->d_wgcost[0]); hipFree(c->d_wgcost[1]);
@@ -1982,6 +1987,26 @@ int lv_predict(lv_ctx* c, double dt, const double* Q, const double acc[3], const
     LV_CHECK_CTX(c);
     if (!Q || !acc || !gyro) { set_error("null argument"); return LV_EINVAL; }
     return c->filter.predict(c->stream, c->d_kf, dt, Q, acc, gyro);
+}
+
+// ---- aiding observations (lv_observe.hip; the argument rules: lv_observe.hpp) --------------------------
+void lv_default_observation(lv_observation* o, int kind) { default_observation(o, kind); }
+
+int lv_observe_results(lv_ctx* c, lv_observe_result* out, size_t capacity, size_t* n) {
+    LV_CHECK_CTX(c);
+    if (c->n_obs == 0) { set_error("lv_observe_results before lv_observe"); return LV_ESTATE; }
+    if (n) *n = (size_t)c->n_obs;
+    if (!out || capacity < (size_t)c->n_obs) { set_error("lv_observe_results: room for %zu of %d results", out ? capacity : (size_t)0, c->n_obs); return LV_EINVAL; }
+    LV_HIP(hipMemcpyAsync(out, c->d_obs, (size_t)c->n_obs * sizeof(lv_observe_result), hipMemcpyDeviceToHost, c->stream));
+    LV_HIP(hipStreamSynchronize(c->stream));
+    return LV_OK;
+}
+
+int lv_observe(lv_ctx* c, const lv_observation* obs, size_t n, lv_observe_result* out) {
+    LV_CHECK_CTX(c);
+    if (int r = c->filter.observe(c->stream, c->d_kf, obs, n, c->d_obs)) return r;
+    c->n_obs = (int)n;
+    return out ? lv_observe_results(c, out, n, nullptr) : LV_OK;
 }
 
 int lv_correct(lv_ctx* c, int* passes) {

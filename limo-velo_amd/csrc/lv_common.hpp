@@ -26,6 +26,9 @@ struct KfDev; struct FilterDev;
 constexpr int PREDICT_BATCH = 8;   // (== PREDICT_BATCH_MAX of lv_predict.hip)
 int launch_predict(hipStream_t stream, FilterDev* f, const KfDev* src, const double* Q, int n, const double (*steps)[7]);
 int launch_kf_to_filter(hipStream_t stream, const KfDev* kf, FilterDev* f);
+// lv_observe.hip: n <= LV_OBSERVE_BATCH checked observations applied to f one after the other in one launch; d_results (device)
+// receives one record each
+int launch_observe(hipStream_t stream, FilterDev* f, const lv_observation* obs, int n, lv_observe_result* d_results);
 
 void set_slice_pause_us(uint32_t us);   // lv_map.hip: the calling THREAD's sliced launches are spaced by that many microseconds (0: back to back)
 

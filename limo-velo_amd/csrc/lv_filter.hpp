@@ -5,7 +5,9 @@
 // - h is not overwritten while an upload out of it may be in flight (set waits on ev_up);
 // - a queued prediction reads kf if the filter was in kf when it was queued, d otherwise; the queue is flushed before anything
 //   else reads, replaces or overwrites the filter or kf;
-// - kf is copied to d (materialise) before an update by value, lv_iterate or lv_calculate_H makes kf its working copy.
+// - kf is copied to d (materialise) before an update by value, lv_iterate or lv_calculate_H makes kf its working copy;
+// - an aiding observation (lv_observe) works on d: queue flushed, h uploaded, kf materialised first; afterwards the filter is d's
+//   and the mailbox no longer holds it (tests/test_observe_host.py).
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -14,6 +16,7 @@
 
 #include "lv_common.hpp"
 #include "lv_device.hpp"
+#include "lv_observe.hpp"
 
 namespace lv {
 
@@ -136,6 +139,17 @@ struct ResidentFilter {
         if (int r = from_filter ? LV_OK : materialise(s, kf)) return r;
         if (where == Where::Copied) where = Where::Device;   // (the mailbox is about to receive this update's results)
         return LV_OK;
+    }
+    // lv_observe: aiding observations applied to d in one launch, behind the queued predictions (calls keep their order in time).
+    // The posterior of a correct leaves kf first; afterwards the filter is d's, and the mailbox no longer holds it.
+    int observe(hipStream_t s, const KfDev* kf, const lv_observation* obs, size_t n_obs, lv_observe_result* d_results) {
+        if (int r = need("lv_observe")) return r;
+        if (int r = observations_ok(obs, n_obs)) return r;   // (before anything is enqueued)
+        if (int r = flush(s, kf)) return r;
+        if (int r = upload(s)) return r;
+        if (int r = materialise(s, kf)) return r;
+        where = Where::Device, latest = Source::Filter;
+        return launch_observe(s, d, obs, (int)n_obs, d_results);
     }
     void correct_done() { where = Where::Kf; }
     // a failed correct (kf may hold a half-iterated state, d an older one) or peer exchange: the caller re-seeds the filter

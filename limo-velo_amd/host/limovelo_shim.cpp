@@ -501,6 +501,11 @@ void Localizator::propagate(const IMU& imu) {                            // :159
     host_stale_ = true;
 }
 
+void Localizator::observe(const lv_observation* obs, size_t n) {
+    check(lv_observe(HipRuntime::ctx(), obs, n, nullptr), "lv_observe");
+    host_stale_ = true;
+}
+
 void Localizator::propagate_to(double t) {                               // :59-75
     propagate_to(Accumulator::getInstance().get_imus(last_time_integrated, t), t);
 }

@@ -308,6 +308,10 @@ class Localizator {
     // the same with the IMU interval handed in by the caller
     void propagate_to(const IMUs& imus, double t);
     void propagate(const IMU& imu);          // Localizator.cpp:159-173
+    // not in the reference (its TODO: GPS, 9-dof IMUs): n <= LV_OBSERVE_BATCH aiding observations applied to the filter on the
+    // device, in order with the propagations (lv_observe, enqueue only); a GPS / wheel / AHRS callback calls it between
+    // propagate_to and correct
+    void observe(const lv_observation* obs, size_t n);
     void calculate_H(const state_ikfom&, const Matches&, MatrixXd& H, VectorXd& h);
     State latest_state();
     int last_passes = 0;  // measurement passes of the last correct()
