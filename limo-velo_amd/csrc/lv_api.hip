@@ -14,15 +14,8 @@
 #include "lv_planes.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
-#include "lv_distance.hpp"
-#include "lv_plan.hpp"
-#include "lv_frontier.hpp"
-#include "lv_ray.hpp"
 #include "lv_elevation.hpp"
-#include "lv_rollout.hpp"
-#include "lv_mcl.hpp"
-#include "lv_occupancy.hpp"
-#include "lv_tsdf.hpp"
+#include "lv_volumes.hpp"
 
 #include <chrono>
 
@@ -58,15 +51,8 @@ struct lv_ctx {
     ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
     PlaneStore planes;      // lv_map_planes: its own buffers (lv_planes.hip); nothing allocated before the first call
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
-    OccStore occ;       // lv_occ_*: the occupancy grid and its buffers (lv_occupancy.hip); nothing allocated before lv_occ_configure
-    DistStore dist;     // lv_occ_distance_*: the distance field over that grid (lv_distance.hip); nothing allocated before the first build
-    PlanStore plan;     // lv_occ_plan_*: the cost-to-go over that field (lv_plan.hip); nothing allocated before the first build
-    FrontierStore frontier;   // lv_occ_frontier_*: the frontier clusters of that grid (lv_frontier.hip); nothing allocated before the first build
-    RayStore ray;       // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
+    VolumeTools vol;    // lv_occ_*, lv_tsdf_*, lv_volume_*: the two volumes, what is built from them and what keeps those honest (lv_volumes.hpp)
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
-    RolloutStore rollout;   // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
-    MclStore mcl;       // lv_occ_mcl_weigh: its own buffers (lv_mcl.hip); nothing allocated before the first call
-    TsdfStore tsdf;     // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
     MapRebuild<MapStore> rebuild;   // the background re-linearisation of `map` (lv_rebuild.hpp)
 
@@ -658,15 +644,8 @@ void lv_destroy(lv_ctx* c) {
     c->cluster.release();
     c->planes.release();
     c->place.release();
-    c->ray.release();
-    c->rollout.release();
-    c->mcl.release();
     c->elev.release();
-    c->frontier.release();
-    c->plan.release();
-    c->dist.release();
-    c->occ.release();
-    c->tsdf.release();
+    c->vol.release();
     c->batch.release();
     c->scan.release();
     free_capture(c);
@@ -2227,327 +2206,133 @@ int lv_get_phase_clocks(lv_ctx* c, long long* out, int capacity_blocks, int* n_b
     return LV_OK;
 }
 
+// ---- The volume tools (lv_volumes.hpp: what each call asks for, and what makes what stale).  An entry point judges here what it
+// judges before the context (what is wrong with those arguments is reported whatever else is), then the context, then c->vol.
 // ---- Occupancy grid (lv_occupancy.hip)
-void lv_default_occupancy_params(lv_occupancy_params* p) {
-    if (!p) return;
-    p->origin[0] = -51.2f;
-    p->origin[1] = -51.2f;
-    p->origin[2] = -3.2f;
-    p->resolution = 0.2f;
-    p->nx = 512;
-    p->ny = 512;
-    p->nz = 64;
-    p->min_range = 1.f;
-    p->max_range = 80.f;
-    p->l_hit = 0.85f;
-    p->l_miss = -0.4f;
-    p->l_min = -2.f;
-    p->l_max = 3.5f;
-    p->l_occ = 0.4f;
-    p->l_free = -0.4f;
-}
+void lv_default_occupancy_params(lv_occupancy_params* p) { default_occupancy_params(p); }
 
-// Leaves the entry point with `code` and the message unless cond holds
-#define LV_REQUIRE(cond, code, msg) \
-    do {                            \
-        if (!(cond)) {              \
-            set_error(msg);         \
-            return code;            \
-        }                           \
-    } while (0)
-// The states the entry points below ask for, each after the ones before it
-#define LV_OCC_CTX(c) \
-    LV_CHECK_CTX(c);  \
-    LV_REQUIRE((c)->occ.configured, LV_ESTATE, "no occupancy grid: call lv_occ_configure first")
-#define LV_DIST_BUILT(c) LV_REQUIRE((c)->dist.built, LV_ESTATE, "no distance field: call lv_occ_distance_build first")
-#define LV_PLAN_BUILT(c) LV_REQUIRE((c)->plan.built, LV_ESTATE, "no plan: call lv_occ_plan_build first")
-#define LV_FRONTIER_BUILT(c) LV_REQUIRE((c)->frontier.built, LV_ESTATE, "no frontier: call lv_occ_frontier_build first")
-
-// What was built from the grid (the distance field, the frontier, the rays' packed states) no longer shows it
-static void occ_grid_changed(lv_ctx* c) {
-    c->ray.packed = false;
-    if (c->dist.built) c->dist.stale = 1;
-    if (c->frontier.built) c->frontier.stale = 1;
-}
-
-// What was built from the distance field (the plan) no longer shows it
-static void occ_field_changed(lv_ctx* c) {
-    if (c->plan.built) c->plan.stale = 1;
-}
-
-// The field remembers the grid's accumulated shift at its build ("Rolling volumes"); hands rc on
-static int dist_built_at(lv_ctx* c, int rc) {
-    if (rc == LV_OK) std::memcpy(c->dist.shift, c->occ.shift, sizeof(c->dist.shift));
-    return rc;
-}
-
-}  // extern "C"
-
-// What lv_distance_info, lv_plan_info and lv_frontier_info share; true: s is built (the caller adds what is its own)
-template <class Info, class Store>
-static bool occ_fill_info(Info* out, const Store& s, bool planar) {
-    *out = Info{};
-    if (!s.built) return false;
-    out->built = 1;
-    out->planar = planar;
-    out->nx = s.grid.nx;
-    out->ny = s.grid.ny;
-    out->nz = s.grid.nz;
-    out->stale = s.stale;
-    out->params = s.prm;
-    return true;
-}
-
-extern "C" {
-
-// (the parameters are judged before the context: what is wrong with them is reported whatever else is)
 int lv_occ_configure(lv_ctx* c, const lv_occupancy_params* p) {
     if (const char* why = occ_check_params(p)) { set_error("lv_occ_configure: %s", why); return LV_EINVAL; }
     LV_CHECK_CTX(c);
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->dist.release();   // (the field belongs to the grid it was built from)
-    c->plan.release();   // (and the plan to the field)
-    c->frontier.release();   // (the frontier to the grid too)
-    c->ray.release();        // (and the packed states)
-    c->rollout.release();    // (and the rollouts' buffers)
-    c->mcl.release();        // (and the localisation's)
-    return c->occ.configure(c->stream, *p);
+    return c->vol.occ_configure(c->stream, *p);
 }
 
-int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) {
-    LV_OCC_CTX(c);
-    if (!views) { set_error("null argument"); return LV_EINVAL; }
-    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
-    if (int rc = views_ok(views, n_views, "", false, 0xFFFFFFF0ull / 4)) return rc;   // (t is not judged: lv_rules.hpp)
-    occ_grid_changed(c);
-    return c->occ.integrate(c->stream, views, n_views, stats);
-}
+// (these judge nothing before the context: the grid comes first, then their arguments, in VolumeTools)
+int lv_occ_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) { LV_CHECK_CTX(c); return c->vol.occ_integrate(c->stream, views, n_views, stats); }
+int lv_occ_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* logodds) { LV_CHECK_CTX(c); return c->vol.occ_query(c->stream, pts, stride, n, logodds); }
+int lv_occ_project(lv_ctx* c, int k_lo, int k_hi, int8_t* grid2d, size_t capacity) { LV_CHECK_CTX(c); return c->vol.occ_project(c->stream, k_lo, k_hi, grid2d, capacity); }
+int lv_occ_fetch(lv_ctx* c, float* logodds, size_t capacity) { LV_CHECK_CTX(c); return c->vol.occ_fetch(c->stream, logodds, capacity); }
+int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) { LV_CHECK_CTX(c); return c->vol.occ_load(c->stream, logodds, n); }
+int lv_occ_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.occ_clear(c->stream); }
+int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) { LV_CHECK_CTX(c); return c->vol.occ_get_params(out); }
 
-int lv_occ_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* logodds) {
-    LV_OCC_CTX(c);
-    if (n && (!pts || !logodds || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
-    if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
-    return c->occ.query(c->stream, pts, stride, n, logodds);
-}
+void lv_default_occ_mark_params(lv_occ_mark_params* p) { default_occ_mark_params(p); }
 
-int lv_occ_project(lv_ctx* c, int k_lo, int k_hi, int8_t* grid2d, size_t capacity) {
-    LV_OCC_CTX(c);
-    const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
-    if (!grid2d || capacity < plane) { set_error("grid2d: room for nx * ny = %zu values needed", plane); return LV_EINVAL; }
-    if (k_lo > k_hi) { set_error("layers %d..%d: k_lo <= k_hi", k_lo, k_hi); return LV_EINVAL; }
-    return c->occ.project(c->stream, k_lo, k_hi, grid2d);
-}
-
-int lv_occ_fetch(lv_ctx* c, float* logodds, size_t capacity) {
-    LV_OCC_CTX(c);
-    if (!logodds || capacity < c->occ.n_vox) { set_error("logodds: room for nx * ny * nz = %zu values needed", c->occ.n_vox); return LV_EINVAL; }
-    return c->occ.fetch(c->stream, logodds);
-}
-
-int lv_occ_load(lv_ctx* c, const float* logodds, size_t n) {
-    LV_OCC_CTX(c);
-    if (!logodds || n != c->occ.n_vox) { set_error("lv_occ_load: %zu values for a grid of %zu voxels", n, c->occ.n_vox); return LV_EINVAL; }
-    const float lo = c->occ.prm.l_min, hi = c->occ.prm.l_max;
-    for (size_t i = 0; i < n; ++i) {
-        const float v = logodds[i];
-        if (!(v != v) && !(v >= lo && v <= hi)) { set_error("lv_occ_load: value %g at %zu outside [%g, %g]", v, i, lo, hi); return LV_EINVAL; }
+// The map source is read as lv_elev_build reads it, and only once there is a box to mark.
+int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (!p) { set_error("lv_occ_mark: null params"); return LV_EINVAL; }
+    if (p->min_points < 1 || p->min_points > (1 << 20)) { set_error("lv_occ_mark: min_points = %d: must be in 1..2^20", p->min_points); return LV_EINVAL; }
+    if (!(std::isfinite(p->l_mark) && p->l_mark != 0.f)) { set_error("lv_occ_mark: l_mark: finite and not zero"); return LV_EINVAL; }
+    if (pts && stride < 12) { set_error("lv_occ_mark: bad point array (stride %zu)", stride); return LV_EINVAL; }
+    if (pts && n >= ((size_t)1 << 31)) { set_error("lv_occ_mark: too many points"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    int lo[3], hi[3];
+    bool any_box = false;
+    if (int rc = c->vol.occ_mark_box(*p, lo, hi, stats, &any_box)) return rc;
+    if (!any_box) return LV_OK;
+    bool any = false;
+    if (!pts) {
+        LV_SETTLE_MAP(c);
+        LV_RELIN_POLL(c);
+        any = c->map.built && c->map.m > 0;
     }
-    occ_grid_changed(c);
-    return c->occ.load(c->stream, logodds);
-}
-
-int lv_occ_clear(lv_ctx* c) {
-    LV_OCC_CTX(c);
-    occ_grid_changed(c);
-    return c->occ.clear(c->stream);
-}
-
-int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) {
-    LV_OCC_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    *out = c->occ.prm;
-    return LV_OK;
+    return c->vol.occ_mark(c->stream, *p, lo, hi, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, pts, stride, n, stats);
 }
 
 // ---- Distance field (lv_distance.hip)
-void lv_default_distance_params(lv_distance_params* p) {
-    if (!p) return;
-    *p = lv_distance_params{};
-}
+void lv_default_distance_params(lv_distance_params* p) { default_distance_params(p); }
 
-// (the parameters are judged before the context, as lv_occ_configure's are)
 int lv_occ_distance_build(lv_ctx* c, const lv_distance_params* p, uint64_t stats[4]) {
     if (const char* why = dist_check_params(p)) { set_error("lv_occ_distance_build: %s", why); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    occ_field_changed(c);
-    return dist_built_at(c, c->dist.build(c->stream, c->occ, *p, nullptr, stats));
+    LV_CHECK_CTX(c);
+    return c->vol.distance_build(c->stream, *p, stats);
+}
+
+int lv_occ_distance_build_cells(lv_ctx* c, const lv_distance_params* p, const int8_t* cells, size_t n, uint64_t stats[4]) {
+    if (const char* why = dist_check_params_cells(p, cells)) { set_error("lv_occ_distance_build_cells: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.distance_build_cells(c->stream, *p, cells, n, stats);
 }
 
 int lv_occ_distance_fetch(lv_ctx* c, int32_t* s2, float* metres, size_t capacity) {
     if (!s2 && !metres) { set_error("lv_occ_distance_fetch: s2 and metres are both null"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_DIST_BUILT(c);
-    if (capacity < c->dist.n_vox) { set_error("lv_occ_distance_fetch: room for %zu values needed", c->dist.n_vox); return LV_EINVAL; }
-    return c->dist.fetch(c->stream, s2, metres);
+    LV_CHECK_CTX(c);
+    return c->vol.distance_fetch(c->stream, s2, metres, capacity);
 }
 
-int lv_occ_distance_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* dist, float* grad) {
-    LV_OCC_CTX(c);
-    LV_DIST_BUILT(c);
-    if (n && (!pts || !dist || stride < 12)) { set_error("bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
-    if (n > 0xFFFFFFF0ull / 4) { set_error("too many points"); return LV_EINVAL; }
-    return c->dist.query(c->stream, pts, stride, n, dist, grad);
-}
-
-int lv_occ_distance_info(lv_ctx* c, lv_distance_info* out) {
-    LV_OCC_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    occ_fill_info(out, c->dist, c->dist.prm.planar != 0);
-    return LV_OK;
-}
-
-int lv_occ_distance_clear(lv_ctx* c) {
-    LV_OCC_CTX(c);
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->dist.release();
-    occ_field_changed(c);
-    return LV_OK;
-}
+int lv_occ_distance_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* dist, float* grad) { LV_CHECK_CTX(c); return c->vol.distance_query(c->stream, pts, stride, n, dist, grad); }
+int lv_occ_distance_info(lv_ctx* c, lv_distance_info* out) { LV_CHECK_CTX(c); return c->vol.distance_info(out); }
+int lv_occ_distance_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.distance_clear(c->stream); }
 
 // ---- Planner (lv_plan.hip)
-void lv_default_plan_params(lv_plan_params* p) {
-    if (!p) return;
-    *p = lv_plan_params{};
-    p->connectivity = 8;
-    p->min_clear_s2 = 1;
-}
+void lv_default_plan_params(lv_plan_params* p) { default_plan_params(p); }
 
-// (parameters, table and counts are judged before the context, as lv_occ_configure's parameters are)
 int lv_occ_plan_build(lv_ctx* c, const lv_plan_params* p, const uint8_t* cost, size_t n_cost, const void* goals, size_t stride, size_t n_goals,
                       uint64_t stats[4]) {
     if (const char* why = plan_check(p, cost, n_cost, goals, stride, n_goals)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_DIST_BUILT(c);
-    if (const char* why = plan_check_field(p->connectivity, c->dist.prm.planar != 0)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
-    const int rc = c->plan.build(c->stream, c->dist, *p, cost, n_cost, goals, stride, n_goals, stats);
-    if (rc == LV_OK) std::memcpy(c->plan.shift, c->dist.shift, sizeof(c->plan.shift));   // (the plan lies where its field does)
-    return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.plan_build(c->stream, *p, cost, n_cost, goals, stride, n_goals, stats);
 }
 
 int lv_occ_plan_fetch(lv_ctx* c, uint32_t* potential, uint8_t* cell_cost, size_t capacity) {
     if (!potential && !cell_cost) { set_error("lv_occ_plan_fetch: potential and cell_cost are both null"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_PLAN_BUILT(c);
-    if (capacity < c->plan.n_cells) { set_error("lv_occ_plan_fetch: room for %zu values needed", c->plan.n_cells); return LV_EINVAL; }
-    return c->plan.fetch(c->stream, potential, cell_cost);
+    LV_CHECK_CTX(c);
+    return c->vol.plan_fetch(c->stream, potential, cell_cost, capacity);
 }
 
 int lv_occ_plan_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* cells,
                       size_t capacity, size_t* total) {
-    LV_OCC_CTX(c);
-    LV_PLAN_BUILT(c);
-    if (!offsets || !total || (n && (!starts || !status || !cost || stride < 12))) {
-        set_error("bad start array (stride %zu) or null status / cost / offsets / total", stride);
-        return LV_EINVAL;
-    }
-    if (n >= (size_t)0x7FFFFFFF) { set_error("%zu starts: one call takes fewer than 2^31 - 1", n); return LV_EINVAL; }
-    return c->plan.paths(c->stream, starts, stride, n, status, cost, offsets, cells, capacity, total);
+    LV_CHECK_CTX(c);
+    return c->vol.plan_paths(c->stream, starts, stride, n, status, cost, offsets, cells, capacity, total);
 }
 
-int lv_occ_plan_info(lv_ctx* c, lv_plan_info* out) {
-    LV_OCC_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    if (occ_fill_info(out, c->plan, c->plan.grid.planar != 0)) out->rounds = c->plan.rounds;
-    return LV_OK;
-}
-
-int lv_occ_plan_clear(lv_ctx* c) {
-    LV_OCC_CTX(c);
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->plan.release();
-    return LV_OK;
-}
+int lv_occ_plan_info(lv_ctx* c, lv_plan_info* out) { LV_CHECK_CTX(c); return c->vol.plan_info(out); }
+int lv_occ_plan_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.plan_clear(c->stream); }
 
 // ---- Frontiers (lv_frontier.hip)
-void lv_default_frontier_params(lv_frontier_params* p) {
-    if (!p) return;
-    *p = lv_frontier_params{};
-    p->connectivity = 26;
-    p->min_size = 1;
-}
+void lv_default_frontier_params(lv_frontier_params* p) { default_frontier_params(p); }
 
-// (the parameters are judged before the context, as lv_occ_configure's are)
 int lv_occ_frontier_build(lv_ctx* c, const lv_frontier_params* p, uint64_t stats[4]) {
     if (const char* why = fr_check_params(p)) { set_error("lv_occ_frontier_build: %s", why); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    const int rc = c->frontier.build(c->stream, c->occ, *p, stats);
-    if (rc == LV_OK) std::memcpy(c->frontier.shift, c->occ.shift, sizeof(c->frontier.shift));
-    return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.frontier_build(c->stream, *p, stats);
 }
 
 int lv_occ_frontier_fetch(lv_ctx* c, int32_t* labels, size_t capacity) {
     if (!labels) { set_error("lv_occ_frontier_fetch: null labels"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_FRONTIER_BUILT(c);
-    if (capacity < c->frontier.n_cells) { set_error("lv_occ_frontier_fetch: room for %zu values needed", c->frontier.n_cells); return LV_EINVAL; }
-    return c->frontier.fetch(c->stream, labels);
+    LV_CHECK_CTX(c);
+    return c->vol.frontier_fetch(c->stream, labels, capacity);
 }
 
 int lv_occ_frontier_clusters(lv_ctx* c, lv_frontier_cluster* out, size_t capacity, size_t* n) {
     if (!n) { set_error("lv_occ_frontier_clusters: null count"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_FRONTIER_BUILT(c);
-    *n = c->frontier.n_clusters;
-    if (!out) return LV_OK;   // count only
-    if (capacity < c->frontier.n_clusters) { set_error("capacity %zu < %zu clusters", capacity, c->frontier.n_clusters); return LV_EINVAL; }
-    return c->frontier.clusters(c->stream, out);
+    LV_CHECK_CTX(c);
+    return c->vol.frontier_clusters(c->stream, out, capacity, n);
 }
 
 int lv_occ_frontier_rank(lv_ctx* c, int reach, uint32_t* best_p, int32_t* best_cell, size_t capacity) {
     if (reach < 0 || reach > FR_MAX_REACH) { set_error("lv_occ_frontier_rank: reach %d: 0..%d", reach, FR_MAX_REACH); return LV_EINVAL; }
     if (!best_p && !best_cell) { set_error("lv_occ_frontier_rank: best_p and best_cell are both null"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    LV_FRONTIER_BUILT(c);
-    LV_PLAN_BUILT(c);
-    const FrontierGrid& f = c->frontier.grid;
-    const PlanGrid& g = c->plan.grid;
-    if ((f.planar != 0) != (g.planar != 0) || f.nx != g.nx || f.ny != g.ny || f.nz != g.nz) {
-        set_error("lv_occ_frontier_rank: the plan (%d x %d x %d, planar %d) is not of the frontier's cells (%d x %d x %d, planar %d)", g.nx, g.ny, g.nz,
-                  g.planar, f.nx, f.ny, f.nz, f.planar);
-        return LV_ESTATE;
-    }
-    // (cell indices of different boxes do not pair, and the cells handed back are read in the grid's box of now)
-    if (std::memcmp(c->frontier.shift, c->plan.shift, sizeof(c->plan.shift)) != 0 || std::memcmp(c->frontier.shift, c->occ.shift, sizeof(c->occ.shift)) != 0) {
-        set_error("lv_occ_frontier_rank: the frontier was built at grid shift (%d, %d, %d), the plan at (%d, %d, %d), the grid is at (%d, %d, %d): "
-                  "rebuild the field, the plan and the frontier", c->frontier.shift[0], c->frontier.shift[1], c->frontier.shift[2], c->plan.shift[0],
-                  c->plan.shift[1], c->plan.shift[2], c->occ.shift[0], c->occ.shift[1], c->occ.shift[2]);
-        return LV_ESTATE;
-    }
-    if (capacity < c->frontier.n_clusters) { set_error("capacity %zu < %zu clusters", capacity, c->frontier.n_clusters); return LV_EINVAL; }
-    return c->frontier.rank(c->stream, c->plan, reach, best_p, best_cell);
+    LV_CHECK_CTX(c);
+    return c->vol.frontier_rank(c->stream, reach, best_p, best_cell, capacity);
 }
 
-int lv_occ_frontier_info(lv_ctx* c, lv_frontier_info* out) {
-    LV_OCC_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    if (occ_fill_info(out, c->frontier, c->frontier.grid.planar != 0)) out->n_clusters = (int)c->frontier.n_clusters;
-    return LV_OK;
-}
-
-int lv_occ_frontier_clear(lv_ctx* c) {
-    LV_OCC_CTX(c);
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->frontier.release();
-    return LV_OK;
-}
+int lv_occ_frontier_info(lv_ctx* c, lv_frontier_info* out) { LV_CHECK_CTX(c); return c->vol.frontier_info(out); }
+int lv_occ_frontier_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.frontier_clear(c->stream); }
 
 // ---- Ray casting (lv_ray.hip)
-void lv_default_ray_params(lv_ray_params* p) {
-    if (!p) return;
-    *p = lv_ray_params{};
-}
+void lv_default_ray_params(lv_ray_params* p) { default_ray_params(p); }
 
-// (the arguments are judged before the context, as lv_occ_frontier_build's are)
 int lv_occ_raycast(lv_ctx* c, const lv_ray_params* p, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
                    lv_ray_result* out) {
     if (!p) { set_error("lv_occ_raycast: null params"); return LV_EINVAL; }
@@ -2556,16 +2341,83 @@ int lv_occ_raycast(lv_ctx* c, const lv_ray_params* p, const void* from, size_t f
         set_error("lv_occ_raycast: bad point arrays (strides %zu, %zu) or null output", from_stride, to_stride);
         return LV_EINVAL;
     }
-    LV_OCC_CTX(c);
-    return c->ray.raycast(c->stream, c->occ, *p, from, from_stride, to, to_stride, n, out);
+    LV_CHECK_CTX(c);
+    return c->vol.raycast(c->stream, *p, from, from_stride, to, to_stride, n, out);
 }
 
 int lv_occ_view_gain(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t* gain) {
     if (!views || !gain) { set_error("lv_occ_view_gain: null argument"); return LV_EINVAL; }
     if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("lv_occ_view_gain: n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
     if (int rc = views_ok(views, n_views, "lv_occ_view_gain: ", false, 0xFFFFFFF0ull / 4)) return rc;   // (t is not judged: lv_rules.hpp)
-    LV_OCC_CTX(c);
-    return c->ray.view_gain(c->stream, c->occ, views, n_views, gain);
+    LV_CHECK_CTX(c);
+    return c->vol.view_gain(c->stream, views, n_views, gain);
+}
+
+// ---- Rollouts (lv_rollout.hip)
+void lv_default_rollout_params(lv_rollout_params* p) { default_rollout_params(p); }
+
+int lv_occ_rollout(lv_ctx* c, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint, size_t n_fp,
+                   lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best) {
+    if (const char* why = rollout_check(p, start, controls, K, footprint, n_fp, results, poses, score, best)) {
+        set_error("lv_occ_rollout: %s", why);
+        return LV_EINVAL;
+    }
+    LV_CHECK_CTX(c);
+    return c->vol.rollout_run(c->stream, *p, start, controls, K, footprint, n_fp, results, poses, score, best);
+}
+
+// ---- Localisation (lv_mcl.hip)
+void lv_default_mcl_params(lv_mcl_params* p) { default_mcl_params(p); }
+
+int lv_occ_mcl_weigh(lv_ctx* c, const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B, const uint32_t* table,
+                     size_t n_table, uint64_t* score, uint32_t* n_in, int64_t* best) {
+    if (const char* why = mcl_check(p, poses, K, beams, B, table, n_table, score, n_in, best)) {
+        set_error("lv_occ_mcl_weigh: %s", why);
+        return LV_EINVAL;
+    }
+    LV_CHECK_CTX(c);
+    return c->vol.mcl_weigh(c->stream, *p, poses, K, beams, B, table, n_table, score, n_in, best);
+}
+
+// ---- TSDF and mesh (lv_tsdf.hip)
+void lv_default_tsdf_params(lv_tsdf_params* p) { default_tsdf_params(p); }
+
+int lv_tsdf_configure(lv_ctx* c, const lv_tsdf_params* p) {
+    if (const char* why = tsdf_check_params(p)) { set_error("lv_tsdf_configure: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.tsdf_configure(c->stream, *p);
+}
+
+// (these judge nothing before the context: the volume comes first, then their arguments, in VolumeTools)
+int lv_tsdf_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) { LV_CHECK_CTX(c); return c->vol.tsdf_integrate(c->stream, views, n_views, stats); }
+int lv_tsdf_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* metres, int32_t* weight) { LV_CHECK_CTX(c); return c->vol.tsdf_query(c->stream, pts, stride, n, metres, weight); }
+int lv_tsdf_fetch(lv_ctx* c, int32_t* S, int32_t* W, float* metres, size_t capacity) { LV_CHECK_CTX(c); return c->vol.tsdf_fetch(c->stream, S, W, metres, capacity); }
+int lv_tsdf_load(lv_ctx* c, const int32_t* S, const int32_t* W, size_t n) { LV_CHECK_CTX(c); return c->vol.tsdf_load(c->stream, S, W, n); }
+int lv_tsdf_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.tsdf_clear(c->stream); }
+int lv_tsdf_get_params(lv_ctx* c, lv_tsdf_params* out) { LV_CHECK_CTX(c); return c->vol.tsdf_get_params(out); }
+int lv_tsdf_mesh_build(lv_ctx* c, int min_weight, uint64_t counts[4]) { LV_CHECK_CTX(c); return c->vol.mesh_build(c->stream, min_weight, counts); }
+int lv_tsdf_mesh_fetch(lv_ctx* c, float* xyz, int32_t* sub, uint32_t* tri, size_t cap_vertices, size_t cap_triangles) {
+    LV_CHECK_CTX(c);
+    return c->vol.mesh_fetch(c->stream, xyz, sub, tri, cap_vertices, cap_triangles);
+}
+int lv_tsdf_mesh_info(lv_ctx* c, lv_mesh_info* out) { LV_CHECK_CTX(c); return c->vol.mesh_info(out); }
+int lv_tsdf_mesh_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.mesh_clear(c->stream); }
+
+// ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)
+int lv_volume_recentre(lv_ctx* c, int volume, const int32_t shift[3], uint64_t stats[4]) {
+    if (volume != LV_VOLUME_OCC && volume != LV_VOLUME_SURFACE) { set_error("lv_volume_recentre: volume %d: LV_VOLUME_OCC or LV_VOLUME_SURFACE", volume); return LV_EINVAL; }
+    if (!shift) { set_error("lv_volume_recentre: null shift"); return LV_EINVAL; }
+    for (int a = 0; a < 3; ++a)
+        if (shift[a] < -GRID_SHIFT_LIMIT || shift[a] > GRID_SHIFT_LIMIT) { set_error("lv_volume_recentre: shift: each component within +-2^20 voxels"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.recentre(c->stream, volume, shift, stats);
+}
+
+int lv_volume_shift_info(lv_ctx* c, lv_volume_shifts* out) {
+    if (!out) { set_error("lv_volume_shift_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    c->vol.shift_info(out);
+    return LV_OK;
 }
 
 // ---- Elevation map (lv_elevation.hip)
@@ -2639,281 +2491,6 @@ int lv_elev_clear(lv_ctx* c) {
     LV_CHECK_CTX(c);
     LV_HIP(hipStreamSynchronize(c->stream));
     c->elev.release();
-    return LV_OK;
-}
-
-// The planar distance field over the caller's cells ("Elevation map": distance from cells); everything but the source of the
-// obstacles is lv_occ_distance_build's
-int lv_occ_distance_build_cells(lv_ctx* c, const lv_distance_params* p, const int8_t* cells, size_t n, uint64_t stats[4]) {
-    if (const char* why = dist_check_params_cells(p, cells)) { set_error("lv_occ_distance_build_cells: %s", why); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    const size_t plane = (size_t)c->occ.grid.nx * (size_t)c->occ.grid.ny;
-    if (n != plane) { set_error("lv_occ_distance_build_cells: %zu cells for a plane of nx * ny = %zu", n, plane); return LV_EINVAL; }
-    occ_field_changed(c);
-    return dist_built_at(c, c->dist.build(c->stream, c->occ, *p, cells, stats));
-}
-
-// ---- Rollouts (lv_rollout.hip)
-void lv_default_rollout_params(lv_rollout_params* p) {
-    if (!p) return;
-    *p = lv_rollout_params{};
-    p->T = 32;
-    p->Tc = 1;
-    p->dt = 0.1f;
-    p->fp_clear_s2 = 1;
-    p->w_cost = 1;
-    p->w_goal = 1;
-    p->w_stop = 0;
-    p->min_steps = 1;
-    p->goal_mode = 0;
-}
-
-// (the arguments are judged before the context, as lv_occ_plan_build's are)
-int lv_occ_rollout(lv_ctx* c, const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint, size_t n_fp,
-                   lv_rollout_result* results, float* poses, uint64_t* score, int64_t* best) {
-    if (const char* why = rollout_check(p, start, controls, K, footprint, n_fp, results, poses, score, best)) {
-        set_error("lv_occ_rollout: %s", why);
-        return LV_EINVAL;
-    }
-    LV_OCC_CTX(c);
-    LV_PLAN_BUILT(c);
-    const PlanGrid& g = c->plan.grid;
-    if (!g.planar) { set_error("lv_occ_rollout: the plan is 3-D: rollouts run on a planar plan"); return LV_ESTATE; }
-    if (n_fp) {
-        LV_DIST_BUILT(c);
-        const DistGrid& f = c->dist.grid;
-        if (!c->dist.prm.planar || f.nx != g.nx || f.ny != g.ny) {
-            set_error("lv_occ_rollout: the distance field (%d x %d, planar %d) is not of the plan's cells (%d x %d, planar)", f.nx, f.ny,
-                      c->dist.prm.planar, g.nx, g.ny);
-            return LV_ESTATE;
-        }
-    }
-    return c->rollout.run(c->stream, c->plan, c->dist, *p, start, controls, K, footprint, n_fp, results, poses, score, best);
-}
-
-// ---- Localisation (lv_mcl.hip)
-void lv_default_mcl_params(lv_mcl_params* p) {
-    if (!p) return;
-    *p = lv_mcl_params{};
-    p->out_cost = 0;
-    p->min_inside = 1;
-}
-
-// (the arguments are judged before the context, as lv_occ_rollout's are)
-int lv_occ_mcl_weigh(lv_ctx* c, const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B, const uint32_t* table,
-                     size_t n_table, uint64_t* score, uint32_t* n_in, int64_t* best) {
-    if (const char* why = mcl_check(p, poses, K, beams, B, table, n_table, score, n_in, best)) {
-        set_error("lv_occ_mcl_weigh: %s", why);
-        return LV_EINVAL;
-    }
-    LV_OCC_CTX(c);
-    LV_DIST_BUILT(c);
-    return c->mcl.run(c->stream, c->dist, *p, poses, K, beams, B, table, n_table, score, n_in, best);
-}
-
-// ---- TSDF and mesh (lv_tsdf.hip)
-void lv_default_tsdf_params(lv_tsdf_params* p) {
-    if (!p) return;
-    lv_occupancy_params o;
-    lv_default_occupancy_params(&o);   // (the occupancy grid's footprint)
-    *p = lv_tsdf_params{};
-    for (int a = 0; a < 3; ++a) p->origin[a] = o.origin[a];
-    p->resolution = o.resolution;
-    p->nx = o.nx;
-    p->ny = o.ny;
-    p->nz = o.nz;
-    p->min_range = o.min_range;
-    p->max_range = o.max_range;
-    p->trunc_cells = 3;
-    p->max_weight = 10000;
-    p->carve = 0;
-}
-
-#define LV_TSDF_CTX(c) \
-    LV_CHECK_CTX(c);   \
-    LV_REQUIRE((c)->tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first")
-
-// The mesh no longer shows the volume
-static void tsdf_changed(lv_ctx* c) {
-    if (c->tsdf.mesh.built) c->tsdf.mesh.stale = 1;
-}
-
-// (the parameters are judged before the context, as lv_occ_configure's are)
-int lv_tsdf_configure(lv_ctx* c, const lv_tsdf_params* p) {
-    if (const char* why = tsdf_check_params(p)) { set_error("lv_tsdf_configure: %s", why); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    return c->tsdf.configure(c->stream, *p);
-}
-
-int lv_tsdf_integrate(lv_ctx* c, const lv_view* views, size_t n_views, uint64_t stats[4]) {
-    LV_TSDF_CTX(c);
-    if (!views) { set_error("lv_tsdf_integrate: null argument"); return LV_EINVAL; }
-    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("lv_tsdf_integrate: n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
-    if (int rc = views_ok(views, n_views, "lv_tsdf_integrate: ", false, TSDF_MAX_RETURNS)) return rc;   // (t is not judged: lv_rules.hpp)
-    tsdf_changed(c);
-    return c->tsdf.integrate(c->stream, views, n_views, stats);
-}
-
-int lv_tsdf_query(lv_ctx* c, const void* pts, size_t stride, size_t n, float* metres, int32_t* weight) {
-    LV_TSDF_CTX(c);
-    if (!metres && !weight) { set_error("lv_tsdf_query: metres and weight are both null"); return LV_EINVAL; }
-    if (n && (!pts || stride < 12)) { set_error("lv_tsdf_query: bad point array (stride %zu)", stride); return LV_EINVAL; }
-    if (n > 0xFFFFFFF0ull / 4) { set_error("lv_tsdf_query: too many points"); return LV_EINVAL; }
-    return c->tsdf.query(c->stream, pts, stride, n, metres, weight);
-}
-
-int lv_tsdf_fetch(lv_ctx* c, int32_t* S, int32_t* W, float* metres, size_t capacity) {
-    LV_TSDF_CTX(c);
-    if (!S && !W && !metres) { set_error("lv_tsdf_fetch: S, W and metres are all null"); return LV_EINVAL; }
-    if (capacity < c->tsdf.n_vox) { set_error("lv_tsdf_fetch: room for nx * ny * nz = %zu values needed", c->tsdf.n_vox); return LV_EINVAL; }
-    return c->tsdf.fetch(c->stream, S, W, metres);
-}
-
-int lv_tsdf_load(lv_ctx* c, const int32_t* S, const int32_t* W, size_t n) {
-    LV_TSDF_CTX(c);
-    if (!S || !W || n != c->tsdf.n_vox) { set_error("lv_tsdf_load: %zu values for a volume of %zu voxels, or a null array", n, c->tsdf.n_vox); return LV_EINVAL; }
-    const size_t bad = tsdf_check_volume(c->tsdf.grid, S, W, n);
-    if (bad != n) {
-        set_error("lv_tsdf_load: voxel %zu: S = %d, W = %d: 0 <= W <= max_weight and |S| <= T * W", bad, S[bad], W[bad]);
-        return LV_EINVAL;
-    }
-    tsdf_changed(c);
-    return c->tsdf.load(c->stream, S, W);
-}
-
-int lv_tsdf_clear(lv_ctx* c) {
-    LV_TSDF_CTX(c);
-    tsdf_changed(c);
-    return c->tsdf.clear(c->stream);
-}
-
-int lv_tsdf_get_params(lv_ctx* c, lv_tsdf_params* out) {
-    LV_TSDF_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    *out = c->tsdf.prm;
-    return LV_OK;
-}
-
-int lv_tsdf_mesh_build(lv_ctx* c, int min_weight, uint64_t counts[4]) {
-    LV_TSDF_CTX(c);
-    if (min_weight < 1) { set_error("lv_tsdf_mesh_build: min_weight = %d: at least 1", min_weight); return LV_EINVAL; }
-    return c->tsdf.mesh_build(c->stream, min_weight, counts);
-}
-
-int lv_tsdf_mesh_fetch(lv_ctx* c, float* xyz, int32_t* sub, uint32_t* tri, size_t cap_vertices, size_t cap_triangles) {
-    LV_TSDF_CTX(c);
-    LV_REQUIRE(c->tsdf.mesh.built, LV_ESTATE, "no mesh: call lv_tsdf_mesh_build first");
-    if (!xyz && !sub && !tri) { set_error("lv_tsdf_mesh_fetch: xyz, sub and tri are all null"); return LV_EINVAL; }
-    const TsdfMesh& m = c->tsdf.mesh;
-    if ((xyz || sub) && cap_vertices < m.counts[0]) { set_error("lv_tsdf_mesh_fetch: room for %llu vertices needed", (unsigned long long)m.counts[0]); return LV_EINVAL; }
-    if (tri && cap_triangles < m.counts[1]) { set_error("lv_tsdf_mesh_fetch: room for %llu triangles needed", (unsigned long long)m.counts[1]); return LV_EINVAL; }
-    return c->tsdf.mesh_fetch(c->stream, xyz, sub, tri);
-}
-
-int lv_tsdf_mesh_info(lv_ctx* c, lv_mesh_info* out) {
-    LV_TSDF_CTX(c);
-    if (!out) { set_error("null argument"); return LV_EINVAL; }
-    const TsdfMesh& m = c->tsdf.mesh;
-    *out = lv_mesh_info{};
-    if (!m.built) return LV_OK;
-    out->built = 1;
-    out->stale = m.stale;
-    out->min_weight = m.min_weight;
-    out->vertices = m.counts[0];
-    out->triangles = m.counts[1];
-    out->active_cells = m.counts[2];
-    out->refused_edges = m.counts[3];
-    return LV_OK;
-}
-
-int lv_tsdf_mesh_clear(lv_ctx* c) {
-    LV_TSDF_CTX(c);
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->tsdf.mesh_release();
-    return LV_OK;
-}
-
-// ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)
-// (the arguments are judged before the context, as lv_occ_raycast's are; the accumulated shift needs the volume)
-int lv_volume_recentre(lv_ctx* c, int volume, const int32_t shift[3], uint64_t stats[4]) {
-    if (volume != LV_VOLUME_OCC && volume != LV_VOLUME_SURFACE) { set_error("lv_volume_recentre: volume %d: LV_VOLUME_OCC or LV_VOLUME_SURFACE", volume); return LV_EINVAL; }
-    if (!shift) { set_error("lv_volume_recentre: null shift"); return LV_EINVAL; }
-    for (int a = 0; a < 3; ++a)
-        if (shift[a] < -GRID_SHIFT_LIMIT || shift[a] > GRID_SHIFT_LIMIT) { set_error("lv_volume_recentre: shift: each component within +-2^20 voxels"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    const bool occ = volume == LV_VOLUME_OCC;
-    if (occ) LV_REQUIRE(c->occ.configured, LV_ESTATE, "no occupancy grid: call lv_occ_configure first");
-    else LV_REQUIRE(c->tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first");
-    int32_t s_new[3];
-    float origin_new[3];
-    const char* why = occ ? grid_shift_check(c->occ.origin0, c->occ.prm.resolution, c->occ.shift, shift, s_new, origin_new)
-                          : grid_shift_check(c->tsdf.origin0, c->tsdf.prm.resolution, c->tsdf.shift, shift, s_new, origin_new);
-    if (why) { set_error("lv_volume_recentre: %s", why); return LV_EINVAL; }
-    if (!(shift[0] | shift[1] | shift[2])) {   // nothing moves: nothing goes stale, no buffer is touched
-        if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-        return LV_OK;
-    }
-    // (what was built from the volume goes stale once it has moved: a call that fails has changed nothing)
-    if (occ) {
-        const int rc = c->occ.recentre(c->stream, shift, s_new, origin_new, stats);
-        if (rc == LV_OK) occ_grid_changed(c);
-        return rc;
-    }
-    const int rc = c->tsdf.recentre(c->stream, shift, s_new, origin_new, stats);
-    if (rc == LV_OK) tsdf_changed(c);
-    return rc;
-}
-
-int lv_volume_shift_info(lv_ctx* c, lv_volume_shifts* out) {
-    if (!out) { set_error("lv_volume_shift_info: null argument"); return LV_EINVAL; }
-    LV_CHECK_CTX(c);
-    *out = lv_volume_shifts{};
-    for (int a = 0; a < 3; ++a) {
-        if (c->occ.configured) out->grid[a] = c->occ.shift[a];
-        if (c->tsdf.configured) out->surface[a] = c->tsdf.shift[a];
-        if (c->occ.configured && c->dist.built) out->field[a] = c->dist.shift[a];
-        if (c->occ.configured && c->plan.built) out->plan[a] = c->plan.shift[a];
-        if (c->occ.configured && c->frontier.built) out->frontier[a] = c->frontier.shift[a];
-    }
-    return LV_OK;
-}
-
-void lv_default_occ_mark_params(lv_occ_mark_params* p) {
-    if (!p) return;
-    *p = lv_occ_mark_params{};
-    for (int a = 0; a < 3; ++a) p->hi[a] = 1 << 30;   // (clipped to the grid: the whole of it)
-    p->min_points = 1;
-    p->only_unknown = 1;
-    p->l_mark = 0.85f;
-}
-
-// (the arguments are judged before the context, as lv_elev_build's are).  The map source is read as lv_elev_build reads it.
-int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
-    if (!p) { set_error("lv_occ_mark: null params"); return LV_EINVAL; }
-    if (p->min_points < 1 || p->min_points > (1 << 20)) { set_error("lv_occ_mark: min_points = %d: must be in 1..2^20", p->min_points); return LV_EINVAL; }
-    if (!(std::isfinite(p->l_mark) && p->l_mark != 0.f)) { set_error("lv_occ_mark: l_mark: finite and not zero"); return LV_EINVAL; }
-    if (pts && stride < 12) { set_error("lv_occ_mark: bad point array (stride %zu)", stride); return LV_EINVAL; }
-    if (pts && n >= ((size_t)1 << 31)) { set_error("lv_occ_mark: too many points"); return LV_EINVAL; }
-    LV_OCC_CTX(c);
-    int lo[3], hi[3];
-    if (!grid_clip_box(c->occ.grid, p->lo, p->hi, lo, hi)) {   // nothing to mark
-        if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
-        return LV_OK;
-    }
-    uint64_t st[4] = {0, 0, 0, 0};
-    int rc;
-    if (!pts) {
-        LV_SETTLE_MAP(c);
-        LV_RELIN_POLL(c);
-        const bool any = c->map.built && c->map.m > 0;
-        rc = c->occ.mark(c->stream, *p, lo, hi, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, nullptr, 0, 0, st);
-    } else {
-        rc = c->occ.mark(c->stream, *p, lo, hi, nullptr, 0, pts, stride, n, st);
-    }
-    if (rc) return rc;
-    if (st[2]) occ_grid_changed(c);
-    if (stats)
-        for (int i = 0; i < 4; ++i) stats[i] = st[i];
     return LV_OK;
 }
 

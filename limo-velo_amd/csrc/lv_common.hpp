@@ -21,6 +21,15 @@ void set_error(const char* fmt, ...);
         }                                                                                         \
     } while (0)
 
+// Leaves the function with `code` and the message unless cond holds
+#define LV_REQUIRE(cond, code, msg) \
+    do {                            \
+        if (!(cond)) {              \
+            ::lv::set_error(msg);   \
+            return code;            \
+        }                           \
+    } while (0)
+
 struct KfDev; struct FilterDev;
 // lv_predict.hip: n <= PREDICT_BATCH steps {dt, acc[3], gyro[3]} with one Q in one launch, from kf->x / P_post if src != nullptr
 constexpr int PREDICT_BATCH = 8;   // (== PREDICT_BATCH_MAX of lv_predict.hip)

@@ -158,6 +158,11 @@ LV_OCC_HD void dist_query_point(const DistGrid& g, const float origin[3], bool p
     }
 }
 
+inline void default_distance_params(lv_distance_params* p) {
+    if (!p) return;
+    *p = lv_distance_params{};
+}
+
 // The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_occ_distance_build: LV_EINVAL)
 inline const char* dist_check_params(const lv_distance_params* p) {
     if (!p) return "null params";

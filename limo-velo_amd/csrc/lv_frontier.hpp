@@ -113,6 +113,13 @@ LV_OCC_HD void fr_cluster_record(lv_frontier_cluster& c, uint32_t size, uint32_t
     }
 }
 
+inline void default_frontier_params(lv_frontier_params* p) {
+    if (!p) return;
+    *p = lv_frontier_params{};
+    p->connectivity = 26;
+    p->min_size = 1;
+}
+
 // The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_occ_frontier_build: LV_EINVAL)
 inline const char* fr_check_params(const lv_frontier_params* p) {
     if (!p) return "null params";

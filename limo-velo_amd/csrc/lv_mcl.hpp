@@ -110,6 +110,13 @@ struct MclOneLane {
     LV_OCC_HD uint32_t count(uint32_t v) const { return v; }
 };
 
+inline void default_mcl_params(lv_mcl_params* p) {
+    if (!p) return;
+    *p = lv_mcl_params{};
+    p->out_cost = 0;
+    p->min_inside = 1;
+}
+
 // Everything that can be judged without a context: NULL when it holds, otherwise what is wrong (lv_occ_mcl_weigh: LV_EINVAL)
 inline const char* mcl_check(const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B, const uint32_t* table, size_t n_table,
                              const void* score, const void* n_in, const void* best) {

@@ -122,6 +122,35 @@ LV_OCC_HD bool occ_walk_left(const OccGrid& g, const OccWalk& w) {
 // One update of a voxel: unknown (NaN) starts from 0, the sum is clamped
 LV_OCC_HD float occ_update(float L, float delta, float l_min, float l_max) { return fminf(fmaxf((L != L ? 0.0f : L) + delta, l_min), l_max); }
 
+inline void default_occupancy_params(lv_occupancy_params* p) {
+    if (!p) return;
+    p->origin[0] = -51.2f;
+    p->origin[1] = -51.2f;
+    p->origin[2] = -3.2f;
+    p->resolution = 0.2f;
+    p->nx = 512;
+    p->ny = 512;
+    p->nz = 64;
+    p->min_range = 1.f;
+    p->max_range = 80.f;
+    p->l_hit = 0.85f;
+    p->l_miss = -0.4f;
+    p->l_min = -2.f;
+    p->l_max = 3.5f;
+    p->l_occ = 0.4f;
+    p->l_free = -0.4f;
+}
+
+// (lv_occ_mark judges its parameters in lv_api.hip, before the context)
+inline void default_occ_mark_params(lv_occ_mark_params* p) {
+    if (!p) return;
+    *p = lv_occ_mark_params{};
+    for (int a = 0; a < 3; ++a) p->hi[a] = 1 << 30;   // (clipped to the grid: the whole of it)
+    p->min_points = 1;
+    p->only_unknown = 1;
+    p->l_mark = 0.85f;
+}
+
 // The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_occ_configure: LV_EINVAL)
 inline const char* occ_check_params(const lv_occupancy_params* p) {
     if (!p) return "null params";

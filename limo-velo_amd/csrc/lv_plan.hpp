@@ -157,6 +157,13 @@ LV_OCC_HD uint64_t plan_walk(const PlanGrid& g, const PlanView& f, const float p
     return n;
 }
 
+inline void default_plan_params(lv_plan_params* p) {
+    if (!p) return;
+    *p = lv_plan_params{};
+    p->connectivity = 8;
+    p->min_clear_s2 = 1;
+}
+
 // Everything that can be judged without a context: NULL when it holds, otherwise what is wrong (lv_occ_plan_build: LV_EINVAL)
 inline const char* plan_check(const lv_plan_params* p, const uint8_t* cost, size_t n_cost, const void* goals, size_t stride, size_t n_goals) {
     if (!p) return "null params";

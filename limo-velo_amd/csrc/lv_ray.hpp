@@ -15,6 +15,11 @@ namespace lv {
 
 constexpr uint64_t RAY_MAX_N = 0x7FFFFFFFull;   // lv_occ_raycast: n below this
 
+inline void default_ray_params(lv_ray_params* p) {
+    if (!p) return;
+    *p = lv_ray_params{};
+}
+
 // ---- the packed states: 2 bits per voxel (FR_OTHER, FR_FREE, FR_OCCUPIED, FR_UNKNOWN = 0..3), 16 consecutive x per word, every
 // x row starting a word: voxel (i, j, k) is bits 2 * (i & 15) .. + 1 of word (k * ny + j) * wx16 + (i >> 4)
 LV_OCC_HD int ray_wx16(int nx) { return (nx + 15) / 16; }

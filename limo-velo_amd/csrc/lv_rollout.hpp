@@ -195,6 +195,20 @@ struct RolloutOneLane {
     LV_OCC_HD bool writes() const { return true; }
 };
 
+inline void default_rollout_params(lv_rollout_params* p) {
+    if (!p) return;
+    *p = lv_rollout_params{};
+    p->T = 32;
+    p->Tc = 1;
+    p->dt = 0.1f;
+    p->fp_clear_s2 = 1;
+    p->w_cost = 1;
+    p->w_goal = 1;
+    p->w_stop = 0;
+    p->min_steps = 1;
+    p->goal_mode = 0;
+}
+
 // Everything that can be judged without a context: NULL when it holds, otherwise what is wrong (lv_occ_rollout: LV_EINVAL)
 inline const char* rollout_check(const lv_rollout_params* p, const float* start, const float* controls, size_t K, const float* footprint,
                                  size_t n_fp, const void* results, const void* poses, const void* score, const void* best) {

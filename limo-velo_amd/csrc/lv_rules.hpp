@@ -1,6 +1,8 @@
 // lv_rules.hpp — the argument rules of the tools on the point map: limits, defaults, what a call is refused for (LV_EINVAL and the
 // message; the first refusal wins, nothing is touched) and the resolved rule the kernels take.  Pure host arithmetic on
 // include/limovelo_hip.h, no HIP header: plain g++ compiles it (tests/test_rules_host.py).  lv_api.hip judges the context first.
+// (The tools on the volumes keep their argument rules in their own headers, lv_occupancy.hpp .. lv_tsdf.hpp, and what they ask
+// of the context's state, with what makes what stale, in lv_volumes.hpp; of this header they share views_ok.)
 #pragma once
 #include <cmath>
 #include <cstddef>

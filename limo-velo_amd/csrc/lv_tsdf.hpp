@@ -188,6 +188,23 @@ LV_OCC_HD int tsdf_edge_face(const G& g, const int32_t* S, const int32_t* W, int
     return 1;
 }
 
+inline void default_tsdf_params(lv_tsdf_params* p) {
+    if (!p) return;
+    lv_occupancy_params o;
+    default_occupancy_params(&o);   // (the occupancy grid's footprint)
+    *p = lv_tsdf_params{};
+    for (int a = 0; a < 3; ++a) p->origin[a] = o.origin[a];
+    p->resolution = o.resolution;
+    p->nx = o.nx;
+    p->ny = o.ny;
+    p->nz = o.nz;
+    p->min_range = o.min_range;
+    p->max_range = o.max_range;
+    p->trunc_cells = 3;
+    p->max_weight = 10000;
+    p->carve = 0;
+}
+
 // The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_tsdf_configure: LV_EINVAL)
 inline const char* tsdf_check_params(const lv_tsdf_params* p) {
     if (!p) return "null params";
