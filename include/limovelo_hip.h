@@ -720,6 +720,77 @@ int  lv_occ_plan_info(lv_ctx* ctx, lv_plan_info* out);
 /* Frees the plan. */
 int  lv_occ_plan_clear(lv_ctx* ctx);
 
+/* ---- Lattice planner ---------------------------------------------------------------------------------
+ * The cost-to-go of a car-like robot: over states (cell, heading) of the planar plan last built, with the caller's table of motion
+ * primitives as directed edges (SBPL's (x, y, theta) lattice, the State Lattice planner of nav2; the reference has no
+ * counterpart).  Edge costs are integers, so V is again the unique fixpoint of relaxation: a pure function of the plan's cost
+ * bytes, the table and the goals, the same bits whatever order the device relaxes in.  No float enters the rule after the cells
+ * of goal and start points are quantised; headings are integers.
+ *   source   the PLANAR plan last built: its cost bytes c(cell) (0 = blocked), nx, ny, origin and resolution.  The lattice keeps
+ *            its own copy (a snapshot).  A 3-D plan is refused with LV_ESTATE.
+ *   states   (i, j, h), h in 0..H-1, H in 1..16, linear index (h * ny + j) * nx + i.  nx * ny * H <= 2^28 (LV_EINVAL beyond).
+ *   table    H * P records, P in 1..16; record h * P + p is primitive p of heading h.  length = 0: the slot is empty.  LV_EINVAL,
+ *            with a message that names the record, for a field out of range, reserved != 0, unused sweep entries that are not 0,
+ *            a non-empty record with di == dj == 0 and h_to == h (a self loop), and for a table with no non-empty record.  A turn
+ *            on the spot (di == dj == 0, h_to != h) is allowed.
+ *   move     primitive p from u = (i, j, h) leads to v = (i + di, j + dj, h_to).  It is allowed iff the start cell, the end
+ *            cell and every sweep cell (offsets from the START cell) are inside the grid and have c != 0.
+ *            edge = length * (c(u) + c(v)) + penalty: directed, at least 2.  Sweep cells add no cost.
+ *   goals    1..65536 records of 3 floats and an int32 h, `stride` bytes (>= 16) apart.  The cell is quantised as
+ *            lv_occ_plan_build quantises a goal (z is not used); h = -1: all H states of the cell.  A goal that is non-finite,
+ *            outside the grid, in a blocked cell or has h outside -1..H-1 is ignored; `goals used` counts the records that are
+ *            not.  With no usable goal the build succeeds and every state is unreached.
+ *   V        one uint32 per state: the least total edge cost over sequences of allowed primitives from the state to any goal
+ *            state, 0 on goal states; LV_LATTICE_UNREACHED if that cost is >= 0xFFFFFFFF, if the cell is blocked, or if no
+ *            sequence exists.  A relaxation whose 64-bit sum reaches 0xFFFFFFFF is dropped, as the planner's is.
+ *   path     per start record (3 floats, int32 h; h = -1: the heading with the least V at that cell, ties to the smaller h).
+ *            status 2: non-finite, outside the grid, in a blocked cell, or h outside -1..H-1; 1: V there is unreached; 0
+ *            otherwise.  cost[i] = V of the start state (LV_LATTICE_UNREACHED for status 1 and 2).  With status 0 the path is the
+ *            sequence of state indices from the start state to a state with V = 0, both included: from s the next state is the
+ *            successor of the FIRST p in 0..P-1 that is non-empty, allowed and has edge + V(succ) == V(s).
+ * The lattice is a SNAPSHOT of the plan: lv_occ_plan_build (once its own checks have passed, whatever it then returns) and
+ * lv_occ_plan_clear leave it in place and set stale = 1; a distance build or a grid edit does not touch it (the plan says of
+ * itself that it is stale); after lv_volume_recentre it keeps answering for the same world points through its own origin;
+ * lv_occ_configure frees it; a new build replaces it (one that fails in the runtime, LV_EHIP, leaves built = 0; a refused one
+ * leaves the old lattice bit for bit).  lv_occ_lattice_build judges parameters, table and counts before the context (LV_EINVAL;
+ * "null context" comes last), then asks for the grid, a plan and a planar plan (LV_ESTATE), then for the state count (LV_EINVAL).
+ * fetch and paths give LV_ESTATE before lv_occ_configure and before a lattice build (lv_occ_lattice_info reports built = 0
+ * instead).  A refused call writes nothing, except as stated for lv_occ_lattice_paths.  Nothing is allocated before the first
+ * build; lv_destroy frees everything. */
+#define LV_LATTICE_REACH 8
+#define LV_LATTICE_MAX_SWEEP 10
+#define LV_LATTICE_UNREACHED 0xFFFFFFFFu
+typedef struct lv_lattice_prim {   /* 32 bytes */
+    int8_t   di, dj;        /* end cell minus start cell, each |.| <= LV_LATTICE_REACH */
+    uint8_t  h_to;          /* heading at the end, 0..H-1 */
+    uint8_t  n_sweep;       /* 0..LV_LATTICE_MAX_SWEEP cells passed between the two ends */
+    uint16_t length;        /* 0: the slot is empty.  Otherwise it multiplies c(u) + c(v); 10 = one cell, the planner's scale */
+    uint16_t reserved;      /* 0 */
+    uint32_t penalty;       /* added once per use (reversing, turning), <= 2^24 */
+    int8_t   sweep[LV_LATTICE_MAX_SWEEP][2];   /* offsets from the START cell, each |.| <= LV_LATTICE_REACH; unused entries 0 */
+} lv_lattice_prim;
+typedef struct lv_lattice_params { int H, P; } lv_lattice_params;
+/* rounds, tile (the edge of a workgroup's tile of cells, 16 or 8) and reach (the largest |offset| of the table) tell how the
+ * device got there; they are not part of the rule. */
+typedef struct lv_lattice_info { int built, nx, ny, H, P, stale, rounds, tile, reach; lv_lattice_params params; } lv_lattice_info;
+/* H 16, P 3. */
+void lv_default_lattice_params(lv_lattice_params* p);
+/* prims: n_prims = H * P records.  stats (may be NULL): goals used, traversable states, reached states, the largest finite V. */
+int  lv_occ_lattice_build(lv_ctx* ctx, const lv_lattice_params* p, const lv_lattice_prim* prims, size_t n_prims, const void* goals,
+                          size_t stride, size_t n_goals, uint64_t stats[4]);
+/* V: one value per state.  capacity below nx * ny * H: LV_EINVAL. */
+int  lv_occ_lattice_fetch(lv_ctx* ctx, uint32_t* V, size_t capacity);
+/* CSR output exactly as lv_occ_plan_paths does it, over states: start i's path is states[offsets[i] .. offsets[i + 1]).
+ * states == NULL: count only.  prims (may be NULL; ignored in a count-only call) runs parallel to states: the primitive taken
+ * out of each state, 255 at a path's last state.  capacity < *total, or a total above 2^31 - 1: LV_EINVAL with status, cost,
+ * offsets and *total still written.  n < 2^31 - 1. */
+int  lv_occ_lattice_paths(lv_ctx* ctx, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets,
+                          int32_t* states, uint8_t* prims, size_t capacity, size_t* total);
+/* All zero with built = 0. */
+int  lv_occ_lattice_info(lv_ctx* ctx, lv_lattice_info* out);
+/* Frees the lattice. */
+int  lv_occ_lattice_clear(lv_ctx* ctx);
+
 /* ---- Frontiers ---------------------------------------------------------------------------------------
  * Where to go next when the site is not mapped yet: the boundary between space observed free and space never observed, grouped
  * into clusters and ranked by what the planner says it costs to get there (Yamauchi's frontiers, explore_lite,

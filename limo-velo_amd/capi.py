@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "lv_default_distance_params", "lv_occ_distance_build", "lv_occ_distance_fetch", "lv_occ_distance_query", "lv_occ_distance_info",
     "lv_occ_distance_clear",
     "lv_default_plan_params", "lv_occ_plan_build", "lv_occ_plan_fetch", "lv_occ_plan_paths", "lv_occ_plan_info", "lv_occ_plan_clear",
+    "lv_default_lattice_params", "lv_occ_lattice_build", "lv_occ_lattice_fetch", "lv_occ_lattice_paths", "lv_occ_lattice_info",
+    "lv_occ_lattice_clear",
     "lv_default_frontier_params", "lv_occ_frontier_build", "lv_occ_frontier_fetch", "lv_occ_frontier_clusters", "lv_occ_frontier_rank",
     "lv_occ_frontier_info", "lv_occ_frontier_clear",
     "lv_default_ray_params", "lv_occ_raycast", "lv_occ_view_gain",
@@ -247,6 +249,42 @@ PLAN_ARGTYPES = {
                           C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_size_t)],
     "lv_occ_plan_info": [C.c_void_p, C.POINTER(PlanInfo)],
     "lv_occ_plan_clear": [C.c_void_p],
+}
+
+LV_LATTICE_REACH, LV_LATTICE_MAX_SWEEP, LV_LATTICE_UNREACHED = 8, 10, 0xFFFFFFFF
+
+
+class LatticePrim(C.Structure):  # lv_lattice_prim (32 bytes)
+    _fields_ = [("di", C.c_int8), ("dj", C.c_int8), ("h_to", C.c_uint8), ("n_sweep", C.c_uint8), ("length", C.c_uint16), ("reserved", C.c_uint16),
+                ("penalty", C.c_uint32), ("sweep", (C.c_int8 * 2) * LV_LATTICE_MAX_SWEEP)]
+
+
+# the same record as a numpy dtype (Context.occ_lattice_build, limo_velo_amd.lattice)
+LATTICE_PRIM_DTYPE = np.dtype([("di", np.int8), ("dj", np.int8), ("h_to", np.uint8), ("n_sweep", np.uint8), ("length", np.uint16),
+                               ("reserved", np.uint16), ("penalty", np.uint32), ("sweep", np.int8, (LV_LATTICE_MAX_SWEEP, 2))])
+assert LATTICE_PRIM_DTYPE.itemsize == C.sizeof(LatticePrim) == 32
+# a goal or start record: a world point and a heading bin (-1: any)
+LATTICE_POSE_DTYPE = np.dtype([("xyz", np.float32, 3), ("h", np.int32)])
+
+
+class LatticeParams(C.Structure):  # lv_lattice_params
+    _fields_ = [("H", C.c_int), ("P", C.c_int)]
+
+
+class LatticeInfo(C.Structure):  # lv_lattice_info
+    _fields_ = [("built", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("H", C.c_int), ("P", C.c_int), ("stale", C.c_int), ("rounds", C.c_int),
+                ("tile", C.c_int), ("reach", C.c_int), ("params", LatticeParams)]
+
+
+# ctypes signatures of the lattice planner (include/limovelo_hip.h "Lattice planner")
+LATTICE_ARGTYPES = {
+    "lv_occ_lattice_build": [C.c_void_p, C.POINTER(LatticeParams), C.POINTER(LatticePrim), C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                             C.POINTER(C.c_uint64)],
+    "lv_occ_lattice_fetch": [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t],
+    "lv_occ_lattice_paths": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
+                             C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t)],
+    "lv_occ_lattice_info": [C.c_void_p, C.POINTER(LatticeInfo)],
+    "lv_occ_lattice_clear": [C.c_void_p],
 }
 
 LV_FRONTIER_NONE = -1
@@ -673,6 +711,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_distance_params.argtypes = [C.POINTER(DistanceParams)]
         lib.lv_default_plan_params.restype = None
         lib.lv_default_plan_params.argtypes = [C.POINTER(PlanParams)]
+        lib.lv_default_lattice_params.restype = None
+        lib.lv_default_lattice_params.argtypes = [C.POINTER(LatticeParams)]
         lib.lv_default_frontier_params.restype = None
         lib.lv_default_frontier_params.argtypes = [C.POINTER(FrontierParams)]
         lib.lv_default_ray_params.restype = None
@@ -690,7 +730,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_observation.restype = None
         lib.lv_default_observation.argtypes = [C.POINTER(Observation), C.c_int]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
-                               **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **FRONTIER_ARGTYPES,
+                               **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
+                               **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
@@ -798,6 +839,26 @@ def default_plan_params(**kw) -> PlanParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_lattice_params(**kw) -> LatticeParams:
+    p = LatticeParams()
+    load_library().lv_default_lattice_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def lattice_poses(poses) -> np.ndarray:
+    """Goal or start records (LATTICE_POSE_DTYPE) from records, or from rows (x, y, z, h): h the heading bin, -1 for any."""
+    a = np.asarray(poses)
+    if a.dtype == LATTICE_POSE_DTYPE:
+        return np.ascontiguousarray(a).reshape(-1)
+    a = np.asarray(a, np.float64).reshape(-1, 4)
+    out = np.zeros(len(a), LATTICE_POSE_DTYPE)
+    out["xyz"] = a[:, :3].astype(np.float32)
+    out["h"] = a[:, 3].astype(np.int32)
+    return out
 
 
 def default_frontier_params(**kw) -> FrontierParams:
@@ -1285,6 +1346,57 @@ class Context:
 
     def occ_plan_clear(self):
         self._check(self.lib.lv_occ_plan_clear(self.h))
+
+    # --- lattice planner (include/limovelo_hip.h "Lattice planner")
+    def occ_lattice_build(self, goals, prims, params: LatticeParams | None = None) -> np.ndarray:
+        """lv_occ_lattice_build over the planar plan last built: goals as lattice_poses takes them, prims the table as
+        LATTICE_PRIM_DTYPE records of shape [H, P] (params default: the table's shape).  Returns stats [4] uint64: goals used,
+        traversable states, reached states, the largest finite V."""
+        t = np.ascontiguousarray(prims, LATTICE_PRIM_DTYPE)
+        p = params if params is not None else default_lattice_params(H=t.shape[0], P=t.shape[1] if t.ndim > 1 else 1)
+        g = lattice_poses(goals)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_lattice_build(self.h, C.byref(p), t.ctypes.data_as(C.POINTER(LatticePrim)), C.c_size_t(t.size),
+                                                  g.ctypes.data_as(C.c_void_p), C.c_size_t(LATTICE_POSE_DTYPE.itemsize), C.c_size_t(len(g)),
+                                                  stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_lattice_info(self) -> LatticeInfo:
+        out = LatticeInfo()
+        self._check(self.lib.lv_occ_lattice_info(self.h, C.byref(out)))
+        return out
+
+    def occ_lattice_fetch(self) -> np.ndarray:
+        """V, uint32 [H, ny, nx]."""
+        i = self.occ_lattice_info()
+        if not i.built:   # (the library's own refusal)
+            self._check(self.lib.lv_occ_lattice_fetch(self.h, (C.c_uint32 * 1)(), C.c_size_t(0)))
+        V = np.zeros((i.H, i.ny, i.nx), np.uint32)
+        self._check(self.lib.lv_occ_lattice_fetch(self.h, V.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(V.size)))
+        return V
+
+    def occ_lattice_paths(self, starts):
+        """(status [n] int32, cost [n] uint32, offsets [n + 1] uint64, states [total] int32, prims [total] uint8), CSR: start i's
+        path is states[offsets[i]:offsets[i + 1]], linear state indices from the start state to a goal state; prims the primitive
+        taken out of each state, 255 at a path's last.  Counts first, then fills."""
+        a = lattice_poses(starts)
+        n = len(a)
+        status = np.full(n, 2, np.int32)
+        cost = np.full(n, LV_LATTICE_UNREACHED, np.uint32)
+        off = np.zeros(n + 1, np.uint64)
+        total = C.c_size_t(0)
+        args = (self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(LATTICE_POSE_DTYPE.itemsize), C.c_size_t(n), status.ctypes.data_as(C.POINTER(C.c_int32)),
+                cost.ctypes.data_as(C.POINTER(C.c_uint32)), off.ctypes.data_as(C.POINTER(C.c_size_t)))
+        self._check(self.lib.lv_occ_lattice_paths(*args, None, None, C.c_size_t(0), C.byref(total)))
+        states = np.empty(int(total.value), np.int32)
+        taken = np.empty(int(total.value), np.uint8)
+        if states.size:
+            self._check(self.lib.lv_occ_lattice_paths(*args, states.ctypes.data_as(C.POINTER(C.c_int32)), taken.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                      C.c_size_t(states.size), C.byref(total)))
+        return status, cost, off, states, taken
+
+    def occ_lattice_clear(self):
+        self._check(self.lib.lv_occ_lattice_clear(self.h))
 
     # --- frontiers (include/limovelo_hip.h "Frontiers")
     def occ_frontier_build(self, params: FrontierParams | None = None) -> np.ndarray:

@@ -2299,6 +2299,36 @@ int lv_occ_plan_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, in
 int lv_occ_plan_info(lv_ctx* c, lv_plan_info* out) { LV_CHECK_CTX(c); return c->vol.plan_info(out); }
 int lv_occ_plan_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.plan_clear(c->stream); }
 
+// ---- Lattice planner (lv_lattice.hip)
+void lv_default_lattice_params(lv_lattice_params* p) { default_lattice_params(p); }
+
+int lv_occ_lattice_build(lv_ctx* c, const lv_lattice_params* p, const lv_lattice_prim* prims, size_t n_prims, const void* goals, size_t stride,
+                         size_t n_goals, uint64_t stats[4]) {
+    size_t rec = LAT_NO_RECORD;
+    if (const char* why = lattice_check(p, prims, n_prims, goals, stride, n_goals, &rec)) {
+        if (rec == LAT_NO_RECORD) set_error("lv_occ_lattice_build: %s", why);
+        else set_error("lv_occ_lattice_build: record %zu (heading %zu, primitive %zu): %s", rec, rec / (size_t)p->P, rec % (size_t)p->P, why);
+        return LV_EINVAL;
+    }
+    LV_CHECK_CTX(c);
+    return c->vol.lattice_build(c->stream, *p, prims, goals, stride, n_goals, stats);
+}
+
+int lv_occ_lattice_fetch(lv_ctx* c, uint32_t* V, size_t capacity) {
+    if (!V) { set_error("lv_occ_lattice_fetch: null V"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.lattice_fetch(c->stream, V, capacity);
+}
+
+int lv_occ_lattice_paths(lv_ctx* c, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* states,
+                         uint8_t* prims, size_t capacity, size_t* total) {
+    LV_CHECK_CTX(c);
+    return c->vol.lattice_paths(c->stream, starts, stride, n, status, cost, offsets, states, prims, capacity, total);
+}
+
+int lv_occ_lattice_info(lv_ctx* c, lv_lattice_info* out) { LV_CHECK_CTX(c); return c->vol.lattice_info(out); }
+int lv_occ_lattice_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.lattice_clear(c->stream); }
+
 // ---- Frontiers (lv_frontier.hip)
 void lv_default_frontier_params(lv_frontier_params* p) { default_frontier_params(p); }
 

@@ -23,19 +23,25 @@
 //     (after its plane-size check)            |                                             |   where built
 //   lv_occ_distance_clear                     | after the synchronise and the release       |
 //   ------------------------------------------+---------------------------------------------+---------------------------------
-//   a build of field, plan or frontier        | after success only                          | dist.shift = occ.shift;
-//                                             |                                             |   plan.shift = dist.shift;
-//                                             |                                             |   frontier.shift = occ.shift
+//   lv_occ_plan_build (after its connectivity | before the store call, whatever it returns  | PLAN EDIT: lattice.stale = 1
+//     check)                                  |                                             |   where built
+//   lv_occ_plan_clear                         | after the synchronise and the release       |
+//   ------------------------------------------+---------------------------------------------+---------------------------------
+//   a build of field, plan, frontier or       | after success only                          | dist.shift = occ.shift;
+//     lattice                                 |                                             |   plan.shift = dist.shift;
+//                                             |                                             |   frontier.shift = occ.shift;
+//                                             |                                             |   lattice.shift = plan.shift
 //   ------------------------------------------+---------------------------------------------+---------------------------------
 //   lv_occ_configure                          | after one hipStreamSynchronize              | releases dist, plan, frontier,
-//                                             |                                             |   ray, rollout, mcl in that
-//                                             |                                             |   order, then occ.configure
+//                                             |                                             |   ray, rollout, mcl, lattice in
+//                                             |                                             |   that order, then occ.configure
 //   ------------------------------------------+---------------------------------------------+---------------------------------
 //   lv_tsdf_integrate, lv_tsdf_load (after    | before the store call                       | SURFACE EDIT: mesh.stale = 1
 //     tsdf_check_volume), lv_tsdf_clear       |                                             |   where built
 //   lv_volume_recentre (SURFACE)              | after success, non-zero shift               |
 //
-// A grid edit does not touch the plan: the plan shows the FIELD, and the field says of itself that it is stale.
+// A grid edit does not touch the plan: the plan shows the FIELD, and the field says of itself that it is stale.  In the same way
+// a field edit or a grid edit does not touch the lattice: it shows the PLAN.
 //
 // WHAT A CALL ASKS FOR, in this order, after whatever its entry point judges before the context (LV_ESTATE and the message of
 // the macros below unless said otherwise; then the arguments the entry point left, LV_EINVAL):
@@ -45,6 +51,8 @@
 //   frontier  _build: GRID.  _fetch, _clusters: GRID, FRONTIER.  _rank: GRID, FRONTIER, PLAN, then plan and frontier of one
 //             shape, then frontier, plan and grid at one shift (both LV_ESTATE), then the capacity.
 //   rays      GRID.
+//   lattice   _build: GRID, PLAN, a planar plan (LV_ESTATE), then nx * ny * H <= 2^28 (LV_EINVAL).  _fetch, _paths: GRID, LATTICE,
+//             then their arguments.  _info, _clear: GRID.
 //   rollout   GRID, PLAN, a planar plan; with a footprint FIELD, then a planar field of the plan's nx, ny (all LV_ESTATE).
 //   mcl       GRID, FIELD.
 //   surface   every lv_tsdf_* call but lv_tsdf_configure: SURFACE, then its arguments.  lv_tsdf_mesh_fetch: SURFACE, MESH.
@@ -56,6 +64,7 @@
 
 #include "lv_distance.hpp"
 #include "lv_frontier.hpp"
+#include "lv_lattice.hpp"
 #include "lv_mcl.hpp"
 #include "lv_occupancy.hpp"
 #include "lv_plan.hpp"
@@ -71,6 +80,7 @@ namespace lv {
 #define LV_DIST_BUILT LV_REQUIRE(dist.built, LV_ESTATE, "no distance field: call lv_occ_distance_build first")
 #define LV_PLAN_BUILT LV_REQUIRE(plan.built, LV_ESTATE, "no plan: call lv_occ_plan_build first")
 #define LV_FRONTIER_BUILT LV_REQUIRE(frontier.built, LV_ESTATE, "no frontier: call lv_occ_frontier_build first")
+#define LV_LATTICE_BUILT LV_REQUIRE(lattice.built, LV_ESTATE, "no lattice: call lv_occ_lattice_build first")
 #define LV_SURFACE_CONFIGURED LV_REQUIRE(tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first")
 
 // What lv_distance_info, lv_plan_info and lv_frontier_info share; true: s is built (the caller adds what is its own)
@@ -96,9 +106,10 @@ struct VolumeTools {
     RayStore ray;             // lv_occ_raycast / lv_occ_view_gain: the packed cell states of that grid (lv_ray.hip); nothing allocated before the first call
     RolloutStore rollout;     // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
     MclStore mcl;             // lv_occ_mcl_weigh: its own buffers (lv_mcl.hip); nothing allocated before the first call
+    LatticeStore lattice;     // lv_occ_lattice_*: the cost-to-go over (cell, heading) of the planar plan (lv_lattice.hip); nothing allocated before the first build
     TsdfStore tsdf;           // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure
 
-    // ---- the table's three edits and its stamps
+    // ---- the table's four edits and its stamps
     void grid_edited() {
         ray.packed = false;
         if (dist.built) dist.stale = 1;
@@ -106,6 +117,9 @@ struct VolumeTools {
     }
     void field_edited() {
         if (plan.built) plan.stale = 1;
+    }
+    void plan_edited() {
+        if (lattice.built) lattice.stale = 1;
     }
     void surface_edited() {
         if (tsdf.mesh.built) tsdf.mesh.stale = 1;
@@ -125,6 +139,7 @@ struct VolumeTools {
         ray.release();        // (and the packed states)
         rollout.release();    // (and the rollouts' buffers)
         mcl.release();        // (and the localisation's)
+        lattice.release();    // (the lattice belongs to the plan)
         return occ.configure(stream, p);
     }
 
@@ -257,6 +272,7 @@ struct VolumeTools {
         LV_GRID_CONFIGURED;
         LV_DIST_BUILT;
         if (const char* why = plan_check_field(p.connectivity, dist.prm.planar != 0)) { set_error("lv_occ_plan_build: %s", why); return LV_EINVAL; }
+        plan_edited();
         return built_at(plan.build(stream, dist, p, cost, n_cost, goals, stride, n_goals, stats), plan.shift, dist.shift);   // (the plan lies where its field does)
     }
 
@@ -290,6 +306,63 @@ struct VolumeTools {
         LV_GRID_CONFIGURED;
         LV_HIP(hipStreamSynchronize(stream));
         plan.release();
+        plan_edited();
+        return LV_OK;
+    }
+
+    // ---- Lattice planner (lv_lattice.hip).  Only these methods reach the store's out-of-line members.
+    int lattice_build(hipStream_t stream, const lv_lattice_params& p, const lv_lattice_prim* prims, const void* goals, size_t stride, size_t n_goals,
+                      uint64_t stats[4]) {
+        LV_GRID_CONFIGURED;
+        LV_PLAN_BUILT;
+        const PlanGrid& g = plan.grid;
+        if (!g.planar) { set_error("lv_occ_lattice_build: the plan is 3-D: the lattice runs on a planar plan"); return LV_ESTATE; }
+        const size_t n_states = (size_t)g.nx * (size_t)g.ny * (size_t)p.H;
+        if (n_states > LAT_MAX_STATES) { set_error("lv_occ_lattice_build: nx * ny * H = %zu states: at most 2^28", n_states); return LV_EINVAL; }
+        return built_at(lattice.build(stream, plan, p, prims, goals, stride, n_goals, stats), lattice.shift, plan.shift);   // (the lattice lies where its plan does)
+    }
+
+    int lattice_fetch(hipStream_t stream, uint32_t* V, size_t capacity) {
+        LV_GRID_CONFIGURED;
+        LV_LATTICE_BUILT;
+        if (capacity < lattice.n_states) { set_error("lv_occ_lattice_fetch: room for %zu values needed", lattice.n_states); return LV_EINVAL; }
+        return lattice.fetch(stream, V);
+    }
+
+    int lattice_paths(hipStream_t stream, const void* starts, size_t stride, size_t n, int32_t* status, uint32_t* cost, size_t* offsets, int32_t* states,
+                      uint8_t* prims, size_t capacity, size_t* total) {
+        LV_GRID_CONFIGURED;
+        LV_LATTICE_BUILT;
+        if (!offsets || !total || (n && (!starts || !status || !cost || stride < 16))) {
+            set_error("lv_occ_lattice_paths: bad start array (stride %zu) or null status / cost / offsets / total", stride);
+            return LV_EINVAL;
+        }
+        if (n >= (size_t)0x7FFFFFFF) { set_error("lv_occ_lattice_paths: %zu starts: one call takes fewer than 2^31 - 1", n); return LV_EINVAL; }
+        return lattice.paths(stream, starts, stride, n, status, cost, offsets, states, prims, capacity, total);
+    }
+
+    int lattice_info(lv_lattice_info* out) {
+        LV_GRID_CONFIGURED;
+        if (!out) { set_error("null argument"); return LV_EINVAL; }
+        *out = lv_lattice_info{};
+        if (!lattice.built) return LV_OK;
+        out->built = 1;
+        out->nx = lattice.grid.nx;
+        out->ny = lattice.grid.ny;
+        out->H = lattice.grid.H;
+        out->P = lattice.grid.P;
+        out->stale = lattice.stale;
+        out->rounds = lattice.rounds;
+        out->tile = lattice.tile;
+        out->reach = lattice.reach;
+        out->params = lattice.prm;
+        return LV_OK;
+    }
+
+    int lattice_clear(hipStream_t stream) {
+        LV_GRID_CONFIGURED;
+        LV_HIP(hipStreamSynchronize(stream));
+        lattice.release();
         return LV_OK;
     }
 
@@ -519,6 +592,7 @@ struct VolumeTools {
         ray.release();
         rollout.release();
         mcl.release();
+        lattice.release();
         frontier.release();
         plan.release();
         dist.release();
@@ -531,6 +605,7 @@ struct VolumeTools {
 #undef LV_DIST_BUILT
 #undef LV_PLAN_BUILT
 #undef LV_FRONTIER_BUILT
+#undef LV_LATTICE_BUILT
 #undef LV_SURFACE_CONFIGURED
 
 }  // namespace lv
