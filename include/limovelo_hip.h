@@ -1583,6 +1583,115 @@ int lv_fetch_rows(lv_ctx* ctx, double* H, double* h);
 int lv_calculate_H(lv_ctx* ctx, const lv_state* x, const float* p_world, const float* abcd, const float* dist, size_t n,
                    double* H, double* h);
 
+/* ---- Pose graph --------------------------------------------------------------------------------------
+ * A pose-graph optimiser on the device: it spreads loop closures and GPS fixes back over a trajectory.  Independent of the map
+ * and of the volumes; everything in f64; bitwise reproducible from call to call (no float atomics, fixed summation orders).
+ * The rule is the __host__ __device__ code of limo-velo_amd/csrc/lv_graph.hpp; tests/graph_ref.py restates it in numpy.
+ *
+ *   node      (t, q): position and unit quaternion x, y, z, w as in lv_state, R = R(q).  An increment d = (dt, dth) acts as
+ *             t <- t + dt, R <- R Exp(dth) (q <- q * exp(dth / 2), then renormalised): position additive, rotation on the right,
+ *             the filter's convention.  A fixed node takes no increment.
+ *   edge      (i, j, tz, qz, info, huber): r = [ Ri^T (tj - ti) - tz ; Log(Rz^T Ri^T Rj) ].  With dv = Ri^T (tj - ti) and
+ *             J = Jr^-1(r_th): dr_t/dt_i = -Ri^T, dr_t/dth_i = [dv]x, dr_t/dt_j = Ri^T, dr_th/dth_j = J, dr_th/dth_i = -J Rj^T Ri,
+ *             every other block zero.  Jr^-1(p) = I + [p]x / 2 + c [p]x^2, c = 1 / th^2 - (1 + cos th) / (2 th sin th), and
+ *             c = 1 / 12 + th^2 / 720 below th = 1e-4 (th = |p|).  Log takes the quaternion with w >= 0: |r_th| <= pi.
+ *   prior     (i, tp, qp, lever, info, huber): r = [ ti + Ri lever - tp ; Log(Rp^T Ri) ]; dr_t/dt_i = I,
+ *             dr_t/dth_i = -Ri [lever]x, dr_th/dth_i = Jr^-1(r_th).  A GPS fix is a prior whose rotation rows and columns of info
+ *             are zero.
+ *   info      a symmetric 6 x 6 matrix given as the 21 entries of its upper triangle, row by row (00 01 .. 05 11 12 .. 55), rows
+ *             and columns ordered (t, th).  It may be positive semi-definite.
+ *   cost      s = r^T info r per factor; cost = 1/2 sum rho(s), rho = s without Huber (huber = 0), else rho = s for
+ *             sqrt(s) <= huber and 2 huber sqrt(s) - huber^2 beyond.  Weight w = 1 or huber / sqrt(s).  The Gauss-Newton blocks are
+ *             J^T (w info) J, the gradient J^T (w info) r; there is no second-order term.
+ *   loop      Levenberg-Marquardt on (H + lambda diag H) d = -g, lambda starting at lambda_init.  The system is solved by
+ *             conjugate gradients from d = 0, preconditioned by the inverses of the 6 x 6 diagonal blocks of H + lambda diag H
+ *             (a Cholesky in the order k = 0..5, column by column; a pivot that is not positive gives that component a zero row
+ *             and column: it does not move).  The solve stops after the iteration at which r^T z <= pcg_tol^2 (r^T z)_0, at
+ *             pcg_max_iterations, or when p^T A p is not positive.  The trial poses are x + d.  A step is ACCEPTED when
+ *             cost_new <= cost_old + 64 eps |cost_old| (eps = 2^-52; the slack lets the loop pass the cost's rounding floor); then
+ *             lambda <- max(lambda / 3, lambda_min), otherwise the poses stay and lambda <- min(4 lambda, lambda_max).  The
+ *             status is LV_GRAPH_CONVERGED when an accepted step has max-norm (over all 6 n components) <= step_tol, the loop
+ *             ends there; otherwise it ends after max_iterations iterations (accepted + rejected) with LV_GRAPH_MAX_ITERATIONS.
+ *   sums      a node's diagonal block and gradient are summed over its incidence list (its edges by ascending edge id, then its
+ *             priors by ascending id) in list order; a list longer than 64 entries is split over the 64 lanes of a wavefront
+ *             (lane l takes entries l, l + 64, ... in order) and folded by a fixed tree.  The cost and the dot products are
+ *             workgroup partials (fixed tree) summed in workgroup order by a fixed tree.  Nothing depends on arrival order.
+ *   limits    n <= 2^20 nodes, n_edges <= 2^22, n_priors <= 2^20.  lv_graph_set gives LV_EINVAL, naming the record and the
+ *             field, for: an index out of range; i == j; a non-finite number; a quaternion whose norm is off 1 by more than 1e-6;
+ *             a negative diagonal entry of info; a negative huber; a graph with neither a fixed node nor a prior.  The records
+ *             are judged before the context ("null context" comes last), and a rejected call writes nothing: the graph held before
+ *             stays bit for bit.  lv_graph_optimise gives LV_EINVAL for parameters outside: max_iterations 1..10000,
+ *             pcg_max_iterations 1..100000, 0 < pcg_tol < 1, step_tol >= 0, 0 < lambda_min <= lambda_init <= lambda_max, all finite.
+ * Every call below except lv_default_graph_params gives LV_ESTATE before lv_graph_set (and after lv_graph_clear); lv_graph_get_info
+ * reports set = 0 instead.  lv_graph_set keeps the given poses as x0 and as the current poses; lv_graph_optimise moves the current
+ * poses and may be called again (it continues from them).  The calls run on the context's stream and return when their outputs
+ * are written.  lv_destroy releases the store. */
+#define LV_GRAPH_CONVERGED 0
+#define LV_GRAPH_MAX_ITERATIONS 1
+#define LV_GRAPH_MAX_NODES (1u << 20)
+#define LV_GRAPH_MAX_EDGES (1u << 22)
+#define LV_GRAPH_MAX_PRIORS (1u << 20)
+typedef struct lv_graph_pose {   /* 56 bytes */
+    double t[3];
+    double q[4];                 /* x, y, z, w */
+} lv_graph_pose;
+typedef struct lv_graph_edge {   /* 240 bytes */
+    uint32_t i, j;
+    double   t[3];               /* tz */
+    double   q[4];               /* qz */
+    double   info[21];
+    double   huber;              /* 0: no Huber */
+} lv_graph_edge;
+typedef struct lv_graph_prior {  /* 264 bytes */
+    uint32_t i;
+    uint32_t reserved;           /* must be 0 */
+    double   t[3];               /* tp */
+    double   q[4];               /* qp */
+    double   lever[3];
+    double   info[21];
+    double   huber;
+} lv_graph_prior;
+typedef struct lv_graph_params {
+    int32_t max_iterations;      /* 100 */
+    int32_t pcg_max_iterations;  /* 1000 */
+    double  pcg_tol;             /* 1e-2 */
+    double  step_tol;            /* 1e-8 */
+    double  lambda_init;         /* 1e-4 */
+    double  lambda_min;          /* 1e-10 */
+    double  lambda_max;          /* 1e8 */
+} lv_graph_params;
+typedef struct lv_graph_info {
+    int32_t  set;                /* a graph is held */
+    int32_t  status;             /* of the last lv_graph_optimise: LV_GRAPH_CONVERGED or LV_GRAPH_MAX_ITERATIONS; -1 before one */
+    uint32_t n, n_edges, n_priors, n_fixed;
+    uint32_t longest_list;       /* entries of the longest incidence list */
+    uint32_t accepted, rejected; /* iterations of the last optimise */
+    uint32_t pcg_iterations;     /* conjugate-gradient iterations of the last optimise, in total */
+    double   initial_cost, final_cost;
+    double   last_step;          /* max-norm of the last accepted step (0 when none was) */
+    double   lambda;             /* after the last iteration */
+} lv_graph_info;
+void lv_default_graph_params(lv_graph_params* p);
+/* Copies the graph to the device and builds its incidence lists.  fixed: n bytes, nonzero = fixed, or NULL (none fixed).  edges /
+ * priors may be NULL when their count is 0.  Replaces the graph held before. */
+int lv_graph_set(lv_ctx* ctx, const lv_graph_pose* poses, size_t n, const uint8_t* fixed, const lv_graph_edge* edges, size_t n_edges,
+                 const lv_graph_prior* priors, size_t n_priors);
+/* Runs the loop above from the current poses.  params NULL: the defaults.  info may be NULL. */
+int lv_graph_optimise(lv_ctx* ctx, const lv_graph_params* params, lv_graph_info* info);
+/* The current poses; capacity < n: LV_EINVAL. */
+int lv_graph_fetch(lv_ctx* ctx, lv_graph_pose* poses, size_t capacity);
+/* s = r^T info r of every edge (n_edges values) and prior (n_priors values) at the current poses, unweighted: a caller vets loop
+ * closures with it.  Either pointer may be NULL. */
+int lv_graph_chi2(lv_ctx* ctx, double* edge_s, double* prior_s);
+/* out[k] = T_now[key] T_x0[key]^-1 p[k]: n points (x, y, z as f32 at the start of every `stride` bytes, stride >= 12) moved by the
+ * correction of their key's node, computed in f64 and rounded once to f32; out: 3 n floats.  D = (R_now R_0^T, t_now - D_R t_0) is
+ * formed once per key (a node whose pose equals its x0 bit for bit gives the identity exactly) and row sums run left to right:
+ * out = ((D0 x + D1 y) + D2 z) + Dt per row.  A key >= the node count: LV_EINVAL, nothing written.  n <= 2^28. */
+int lv_graph_warp_points(lv_ctx* ctx, const void* pts, size_t stride, const uint32_t* keys, size_t n, float* out);
+int lv_graph_get_info(lv_ctx* ctx, lv_graph_info* info);
+/* Forgets the graph (the buffers stay for the next one). */
+int lv_graph_clear(lv_ctx* ctx);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 typedef struct lv_timing {
     float last_update_ms;      /* device time of the last lv_update (HIP events on the ctx stream) */

@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
     "lv_default_observation", "lv_observe", "lv_observe_results",
+    "lv_default_graph_params", "lv_graph_set", "lv_graph_optimise", "lv_graph_fetch", "lv_graph_chi2", "lv_graph_warp_points",
+    "lv_graph_get_info", "lv_graph_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -185,6 +187,55 @@ PLACE_ARGTYPES = {
     "lv_place_clear": [C.c_void_p],
     "lv_place_fetch": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
     "lv_place_load": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_size_t],
+}
+
+
+class GraphPose(C.Structure):  # lv_graph_pose (56 bytes)
+    _fields_ = [("t", C.c_double * 3), ("q", C.c_double * 4)]
+
+
+class GraphEdge(C.Structure):  # lv_graph_edge (240 bytes)
+    _fields_ = [("i", C.c_uint32), ("j", C.c_uint32), ("t", C.c_double * 3), ("q", C.c_double * 4), ("info", C.c_double * 21),
+                ("huber", C.c_double)]
+
+
+class GraphPrior(C.Structure):  # lv_graph_prior (264 bytes)
+    _fields_ = [("i", C.c_uint32), ("reserved", C.c_uint32), ("t", C.c_double * 3), ("q", C.c_double * 4), ("lever", C.c_double * 3),
+                ("info", C.c_double * 21), ("huber", C.c_double)]
+
+
+class GraphParams(C.Structure):  # lv_graph_params
+    _fields_ = [("max_iterations", C.c_int32), ("pcg_max_iterations", C.c_int32), ("pcg_tol", C.c_double), ("step_tol", C.c_double),
+                ("lambda_init", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
+class GraphInfo(C.Structure):  # lv_graph_info
+    _fields_ = [("set", C.c_int32), ("status", C.c_int32), ("n", C.c_uint32), ("n_edges", C.c_uint32), ("n_priors", C.c_uint32),
+                ("n_fixed", C.c_uint32), ("longest_list", C.c_uint32), ("accepted", C.c_uint32), ("rejected", C.c_uint32),
+                ("pcg_iterations", C.c_uint32), ("initial_cost", C.c_double), ("final_cost", C.c_double), ("last_step", C.c_double),
+                ("lambda_", C.c_double)]
+
+    def as_dict(self):
+        return {("lambda" if f == "lambda_" else f): getattr(self, f) for f, _ in self._fields_}
+
+
+GRAPH_CONVERGED, GRAPH_MAX_ITERATIONS = 0, 1
+# numpy views of the records (the same bytes as GraphPose, GraphEdge, GraphPrior)
+GRAPH_POSE_DTYPE = np.dtype([("t", "f8", 3), ("q", "f8", 4)])
+GRAPH_EDGE_DTYPE = np.dtype([("i", "u4"), ("j", "u4"), ("t", "f8", 3), ("q", "f8", 4), ("info", "f8", 21), ("huber", "f8")])
+GRAPH_PRIOR_DTYPE = np.dtype([("i", "u4"), ("reserved", "u4"), ("t", "f8", 3), ("q", "f8", 4), ("lever", "f8", 3), ("info", "f8", 21),
+                              ("huber", "f8")])
+
+# ctypes signatures of the pose graph (include/limovelo_hip.h "Pose graph"; tests/test_graph_abi.py)
+GRAPH_ARGTYPES = {
+    "lv_graph_set": [C.c_void_p, C.POINTER(GraphPose), C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(GraphEdge), C.c_size_t,
+                     C.POINTER(GraphPrior), C.c_size_t],
+    "lv_graph_optimise": [C.c_void_p, C.POINTER(GraphParams), C.POINTER(GraphInfo)],
+    "lv_graph_fetch": [C.c_void_p, C.POINTER(GraphPose), C.c_size_t],
+    "lv_graph_chi2": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "lv_graph_warp_points": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_float)],
+    "lv_graph_get_info": [C.c_void_p, C.POINTER(GraphInfo)],
+    "lv_graph_clear": [C.c_void_p],
 }
 
 
@@ -729,11 +780,13 @@ def load_library() -> C.CDLL:
         lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
         lib.lv_default_observation.restype = None
         lib.lv_default_observation.argtypes = [C.POINTER(Observation), C.c_int]
+        lib.lv_default_graph_params.restype = None
+        lib.lv_default_graph_params.argtypes = [C.POINTER(GraphParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
-                               **OBSERVE_ARGTYPES}.items():
+                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -809,6 +862,14 @@ def default_plane_params(**kw) -> PlaneParams:
 def default_place_params(**kw) -> PlaceParams:
     p = PlaceParams()
     load_library().lv_default_place_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_graph_params(**kw) -> GraphParams:
+    p = GraphParams()
+    load_library().lv_default_graph_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1783,6 +1844,57 @@ class Context:
         d = np.ascontiguousarray(np.asarray(desc, np.float32).reshape(len(c), -1))
         self._check(self.lib.lv_place_load(self.h, d.ctypes.data_as(C.POINTER(C.c_float)), c.ctypes.data_as(C.POINTER(C.c_double)),
                                            C.c_size_t(len(c))))
+
+    # --- pose graph (include/limovelo_hip.h "Pose graph")
+    def graph_set(self, poses, fixed=None, edges=None, priors=None):
+        """lv_graph_set: poses [n, 7] f64 (t, q = x y z w), fixed [n] bool or None, edges GRAPH_EDGE_DTYPE, priors GRAPH_PRIOR_DTYPE."""
+        x = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 7))
+        f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, bool).astype(np.uint8))
+        e = np.ascontiguousarray(np.zeros(0, GRAPH_EDGE_DTYPE) if edges is None else np.asarray(edges, GRAPH_EDGE_DTYPE).reshape(-1))
+        p = np.ascontiguousarray(np.zeros(0, GRAPH_PRIOR_DTYPE) if priors is None else np.asarray(priors, GRAPH_PRIOR_DTYPE).reshape(-1))
+        self._check(self.lib.lv_graph_set(self.h, x.ctypes.data_as(C.POINTER(GraphPose)), C.c_size_t(len(x)),
+                                          None if f is None else f.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          e.ctypes.data_as(C.POINTER(GraphEdge)) if len(e) else None, C.c_size_t(len(e)),
+                                          p.ctypes.data_as(C.POINTER(GraphPrior)) if len(p) else None, C.c_size_t(len(p))))
+
+    def graph_optimise(self, params: GraphParams | None = None, **kw) -> dict:
+        """lv_graph_optimise with the given parameters (default: lv_default_graph_params changed by kw); the info record as a dict."""
+        p = params if params is not None else default_graph_params(**kw)
+        info = GraphInfo()
+        self._check(self.lib.lv_graph_optimise(self.h, C.byref(p), C.byref(info)))
+        return info.as_dict()
+
+    def graph_info(self) -> dict:
+        info = GraphInfo()
+        self._check(self.lib.lv_graph_get_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def graph_fetch(self) -> np.ndarray:
+        """[n, 7] f64: the current poses."""
+        out = np.zeros((self.graph_info()["n"], 7))
+        self._check(self.lib.lv_graph_fetch(self.h, out.ctypes.data_as(C.POINTER(GraphPose)), C.c_size_t(len(out))))
+        return out
+
+    def graph_chi2(self):
+        """(edge_s [n_edges], prior_s [n_priors]) f64: r^T info r of every factor at the current poses."""
+        i = self.graph_info()
+        es, ps = np.zeros(i["n_edges"]), np.zeros(i["n_priors"])
+        self._check(self.lib.lv_graph_chi2(self.h, es.ctypes.data_as(C.POINTER(C.c_double)), ps.ctypes.data_as(C.POINTER(C.c_double))))
+        return es, ps
+
+    def graph_warp_points(self, pts, keys) -> np.ndarray:
+        """[n, 3] f32: pts moved by the correction of their key's node (lv_graph_warp_points)."""
+        a, stride, n = _points(pts)
+        k = np.ascontiguousarray(keys, np.uint32)
+        if len(k) != n:
+            raise ValueError("one key per point")
+        out = np.zeros((n, 3), np.float32)
+        self._check(self.lib.lv_graph_warp_points(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), k.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  C.c_size_t(n), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def graph_clear(self):
+        self._check(self.lib.lv_graph_clear(self.h))
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

@@ -14,6 +14,7 @@
 #include "lv_planes.hpp"
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
+#include "lv_graph.hpp"
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
 
@@ -51,6 +52,7 @@ struct lv_ctx {
     ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
     PlaneStore planes;      // lv_map_planes: its own buffers (lv_planes.hip); nothing allocated before the first call
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
+    GraphStore graph;   // lv_graph_*: the pose graph and the solver's vectors (lv_graph.hip); nothing allocated before lv_graph_set
     VolumeTools vol;    // lv_occ_*, lv_tsdf_*, lv_volume_*: the two volumes, what is built from them and what keeps those honest (lv_volumes.hpp)
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
@@ -644,6 +646,7 @@ void lv_destroy(lv_ctx* c) {
     c->cluster.release();
     c->planes.release();
     c->place.release();
+    c->graph.release();
     c->elev.release();
     c->vol.release();
     c->batch.release();
@@ -1201,6 +1204,70 @@ int lv_place_load(lv_ctx* c, const float* desc, const double* centres, size_t n)
     if (int rc = place_centres_ok(centres, n)) return rc;
     if (c->place.n + n > PLACE_MAX_COUNT) { set_error("the place database holds 2^20 places"); return LV_ERANGE; }
     return c->place.load(c->stream, desc, centres, n);
+}
+
+// ---- Pose graph (lv_graph.hip)
+void lv_default_graph_params(lv_graph_params* p) { default_graph_params(p); }
+
+#define LV_GRAPH_SET(c) LV_REQUIRE((c)->graph.set, LV_ESTATE, "no pose graph: call lv_graph_set first")
+
+int lv_graph_set(lv_ctx* c, const lv_graph_pose* poses, size_t n, const uint8_t* fixed, const lv_graph_edge* edges, size_t n_edges,
+                 const lv_graph_prior* priors, size_t n_priors) {
+    if (int rc = graph_check(poses, n, fixed, edges, n_edges, priors, n_priors)) return rc;   // (before the context: "null context" comes last)
+    LV_CHECK_CTX(c);
+    return c->graph.assign(c->stream, poses, n, fixed, edges, n_edges, priors, n_priors);
+}
+
+int lv_graph_optimise(lv_ctx* c, const lv_graph_params* params, lv_graph_info* info) {
+    lv_graph_params prm;
+    default_graph_params(&prm);
+    if (params) prm = *params;
+    if (int rc = graph_params_ok(&prm)) return rc;
+    LV_CHECK_CTX(c);
+    LV_GRAPH_SET(c);
+    const int rc = c->graph.optimise(c->stream, prm);
+    if (!rc && info) *info = c->graph.info;
+    return rc;
+}
+
+int lv_graph_fetch(lv_ctx* c, lv_graph_pose* poses, size_t capacity) {
+    if (!poses) { set_error("null poses"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_GRAPH_SET(c);
+    if (capacity < c->graph.n) { set_error("capacity %zu < %zu nodes", capacity, c->graph.n); return LV_EINVAL; }
+    return c->graph.fetch(c->stream, poses);
+}
+
+int lv_graph_chi2(lv_ctx* c, double* edge_s, double* prior_s) {
+    LV_CHECK_CTX(c);
+    LV_GRAPH_SET(c);
+    return c->graph.chi2(c->stream, edge_s, prior_s);
+}
+
+int lv_graph_warp_points(lv_ctx* c, const void* pts, size_t stride, const uint32_t* keys, size_t n, float* out) {
+    if (n > GRAPH_MAX_WARP) { set_error("n = %zu above 2^28", n); return LV_EINVAL; }
+    if (n && (!pts || !keys || !out)) { set_error("null argument"); return LV_EINVAL; }
+    if (n && stride < 12) { set_error("stride %zu below 12", stride); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_GRAPH_SET(c);
+    for (size_t k = 0; k < n; ++k)
+        if (keys[k] >= c->graph.n) { set_error("key %zu = %u: the graph holds %zu nodes", k, keys[k], c->graph.n); return LV_EINVAL; }
+    return c->graph.warp(c->stream, pts, stride, keys, n, out);
+}
+
+int lv_graph_get_info(lv_ctx* c, lv_graph_info* info) {
+    if (!info) { set_error("null info"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *info = c->graph.info;
+    if (!c->graph.set) info->status = -1;
+    return LV_OK;
+}
+
+int lv_graph_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_GRAPH_SET(c);
+    c->graph.clear();
+    return LV_OK;
 }
 
 int lv_map_relinearise(lv_ctx* c) {
