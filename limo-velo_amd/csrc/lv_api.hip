@@ -7,6 +7,7 @@
 
 #include "lv_filter.hpp"
 #include "lv_host.hpp"
+#include "lv_knobs.hpp"
 #include "lv_rebuild.hpp"
 #include "lv_visibility.hpp"
 #include "lv_surface.hpp"
@@ -60,76 +61,16 @@ struct lv_ctx {
 
     ScanStore scan;
     CloudStore cloud;   // row f-4: device-resident LiDAR buffer
-    float4* h_stage = nullptr;  // pinned upload staging
-    size_t h_stage_cap = 0;
+    PinBuf<float4> h_stage;     // pinned upload staging (doubling from 4096 points: ensure_stage)
     MotionState* h_states_ring = nullptr;   // pinned: the motion states of lv_scan_deskew_window, 8 slots of 64 (a copy out of the
     int states_slot = 0;                    // caller's pageable memory blocks the host; every cycle synchronises at least once, so
                                             // a slot is free again long before its turn comes round)
 
-    KfDev* d_kf = nullptr;
     ResidentFilter filter;   // x, P resident between lv_filter_set / lv_predict / lv_correct / lv_filter_get (lv_filter.hpp)
     lv_observe_result* d_obs = nullptr;   // lv_observe: the records of the last call (LV_OBSERVE_BATCH), and how many
     int n_obs = 0;
-    KfDev* h_kf = nullptr;  // pinned mirror (logs / trace downloads)
-    KfHostIO* h_io = nullptr;  // pinned, host-mapped mailbox: update inputs and results (no copy kernels)
-    KfHostIO* d_io = nullptr;  // its device address
-    int update_seq = 0;        // number of the update in flight (the finishing pass echoes it into h_io->seq)
-    bool spin_wait = true;     // lv_update_end polls the mailbox before falling back to hipStreamSynchronize (LV_SPIN_WAIT=0: off)
-    double* d_partials = nullptr;
-    double* d_groups = nullptr;    // group records (reduce stage 1)
-    int ngroups = 0;
-    double* d_sums = nullptr;      // record in use (own or caller-provided)
-    double* d_sums_own = nullptr;
-    double* h_sums = nullptr;  // pinned
-    int max_blocks = 1024;
-    int grid = 1;
-    bool fold_direct = false;      // this pass: solve_kernel reads the block partials directly
-    bool tile_lpt = true;          // dispatch the search tiles farthest-first (LV_TILE_LPT=0: plain order, A/B knob)
-    float4* d_qrec = nullptr;      // search -> fit hand-over: 8 float4 planes of qstride entries (one record per scan point)
-    uint32_t qstride = 0;
-    // one launch per pass (pass_kernel, lv_pass_dev.hpp): compact workgroup partials, ping-pong by pass parity
-    double* d_cpart[2] = {nullptr, nullptr};
     RankExchange ranks;   // multi-GPU: how the partials of every pass reach every rank (lv_exchange.hpp)
-    uint32_t* d_wgcost[2] = {nullptr, nullptr};   // per searching workgroup: how long its search + fits took (picks the next bookkeeper)
-    int pass_max_wg = 256;         // search workgroups of pass_kernel: all resident at once (one 1024-thread workgroup per CU)
-    bool fused_pass = true;        // LV_FUSED_PASS=0: the three-kernel pass (search / fit / solve) also where pass_kernel applies
-    bool record_dump = false;      // lv_set_record_dump: pass_kernel also writes its hand-over records to d_qrec (lv_fetch_neighbors)
-    bool last_update_fused = false;
-    long long* d_pclk = nullptr;   // LV_PASS_CLK=1: phase stamps of pass_kernel's workgroups (lv_get_pass_clocks)
-    int pclk_wg = 0;
-    bool keeper_by_cost = true;       // LV_KEEPER_BY_COST=0: the last searching workgroup always keeps the books (A/B knob)
-    int fused_multi_round = -1;       // LV_FUSED_MULTI: 1 = pass_kernel whatever the rounds per workgroup, 0 = up to three (the rule of
-                                      // round 3), -1 (default) = up to PK_DEFAULT_MAX_ROUNDS (three with estimate_extrinsics)
-    bool fused_ext = true;         // LV_FUSED_EXT=0: the three-kernel pass with estimate_extrinsics (one launch per pass measured 22.1 k vs 21.4 k it/s, r03)
-
-    // capture (debug / API-parity) buffers, sized for the current scan
-    bool capture = false;
-    size_t cap_n = 0;
-    DebugOut dbg{};
-    bool dbg_valid = false;
-    bool qrec_valid = false;       // d_qrec holds the records of a pass over the CURRENT scan (lv_fetch_neighbors)
-
-    bool begin_pending = false;    // the update's state waits in h_begin for the first search launch (no begin kernel)
-    BeginArg h_begin;
-    int fallback_base = 0;         // device counter value before the update in flight (the device never resets it)
-    long mailbox_resyncs = 0;      // updates whose mailbox checksum did not match at first sight (stream synchronised instead)
-
-    int pass_index = -1;           // index of the pass being enqueued by lv_update's three-kernel loop (events of its collective)
-    bool coll_timed = false;       // the last profiled update recorded events around its collectives
-    bool fast_fit = false;       // lv_set_option "fast_fit": the opt-in approximate plane fit of pass_kernel (v_rcp / v_sqrt + Newton; NOT bit-exact)
-    bool multi_overlap = true;   // multi-round scans: plane fits beside the next round's search (LV_MULTI_OVERLAP=0: round 3's barrier form)
-    bool in_update = false;
-    bool want_log = false;         // download trace / per-pass sums at lv_update_end
-    int passes_issued = 0;
-
-    bool profiling = false;
-    bool phase_clocks = false;     // lv_set_profiling(ctx, 2): per-workgroup phase stamps of the match kernel
-    long long* d_clk = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_pass;  // 3 per pass: before match kernel, after it, after reduce_partials + solve
-    hipEvent_t ev_mid = nullptr;      // set while a profiled pass is in flight: recorded right after the match kernel
-    std::vector<hipEvent_t> ev_coll;  // 2 per pass: around the pass' collective (multi-GPU forms, profiled updates)
-    lv_timing timing{};
+    UpdateDriver upd{prm, filter, ranks};   // the iterated update: kf, the mailbox, its buffers, routes and profiling (lv_update.hpp)
 };
 
 namespace {
@@ -162,19 +103,6 @@ struct SlowCall {
         }                                        \
     } while (0)
 
-// The peer-mapped exchange (lv_peer.hip) failed in an earlier launch of this context (a rank of the node gave up waiting for
-// another, or met a rank that had): whatever those launches computed is built on stale partials.  Nothing of it is adopted
-// — the resident filter is declared unset — and every later call of the data path fails until the exchange is torn down
-// (lv_comm_destroy) and the filter re-seeded.
-static int peer_poisoned(lv_ctx* c) {
-    if (!c->ranks.failed()) return LV_OK;
-    c->filter.drop();
-    c->in_update = false;
-    set_error("peer-mapped gather: a rank of the node did not publish its partials in time (or reported a failed exchange): the update "
-              "was not adopted; lv_comm_destroy, then lv_filter_set / a new exchange");
-    return LV_ESTATE;
-}
-
 // an incremental insert leaves its outcome in flight (MapStore::settle): pick it up before the map's bookkeeping is used
 #define LV_SETTLE_MAP(c)                               \
     do {                                               \
@@ -183,17 +111,10 @@ static int peer_poisoned(lv_ctx* c) {
     } while (0)
 
 int ensure_stage(lv_ctx* c, size_t n) {
-    if (n <= c->h_stage_cap) return LV_OK;
-    size_t cap = c->h_stage_cap ? c->h_stage_cap : 4096;
-    while (cap < n) cap *= 2;
+    if (n <= c->h_stage.cap) return LV_OK;
     // a copy out of the old buffer may still be pending on the (possibly caller-supplied, non-blocking) stream
     LV_HIP(hipStreamSynchronize(c->stream));
-    if (c->h_stage) hipHostFree(c->h_stage);
-    c->h_stage = nullptr;
-    c->h_stage_cap = 0;
-    LV_HIP(hipHostMalloc((void**)&c->h_stage, cap * sizeof(float4), hipHostMallocDefault));
-    c->h_stage_cap = cap;
-    return LV_OK;
+    return c->h_stage.need_pow2(n, 4096);
 }
 
 inline void read_xyz(const void* base, size_t stride, size_t i, float& x, float& y, float& z) {
@@ -201,295 +122,53 @@ inline void read_xyz(const void* base, size_t stride, size_t i, float& x, float&
     x = p[0]; y = p[1]; z = p[2];
 }
 
-void free_capture(lv_ctx* c) {
-    hipFree(c->dbg.knn_idx); hipFree(c->dbg.knn_d2); hipFree(c->dbg.valid); hipFree(c->dbg.p_world);
-    hipFree(c->dbg.abcd); hipFree(c->dbg.dist); hipFree(c->dbg.rows); hipFree(c->dbg.h);
-    c->dbg = DebugOut{};
-    c->cap_n = 0;
-    c->dbg_valid = false;
-    c->qrec_valid = false;
+// what the update driver works on (lv_update.hpp): the context's stream, the map's view and the current scan
+UpdateInputs inputs(const lv_ctx* c) {
+    return {c->stream, &c->map.view, c->scan.d_sorted, c->scan.n, c->scan.d_tile_order, c->scan.n_tiles, c->scan.tile_points};
 }
 
-int ensure_capture(lv_ctx* c, size_t n) {
-    if (n <= c->cap_n && c->dbg.knn_idx) return LV_OK;
-    free_capture(c);
-    size_t cap = n ? n : 1;
-    LV_HIP(hipMalloc(&c->dbg.knn_idx, cap * c->prm.NUM_MATCH_POINTS * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&c->dbg.knn_d2, cap * c->prm.NUM_MATCH_POINTS * sizeof(float)));
-    LV_HIP(hipMalloc(&c->dbg.valid, cap));
-    LV_HIP(hipMalloc(&c->dbg.p_world, cap * 3 * sizeof(float)));
-    LV_HIP(hipMalloc(&c->dbg.abcd, cap * 4 * sizeof(float)));
-    LV_HIP(hipMalloc(&c->dbg.dist, cap * sizeof(float)));
-    LV_HIP(hipMalloc(&c->dbg.rows, cap * 12 * sizeof(double)));
-    LV_HIP(hipMalloc(&c->dbg.h, cap * sizeof(double)));
-    c->cap_n = cap;
-    return LV_OK;
+// a new scan is on its way: nothing captured, handed over or told about the one before holds any longer
+void new_scan(lv_ctx* c) {
+    c->upd.new_scan();
+    c->scan.n = 0, c->scan.route = LV_SCAN_ROUTE_NONE;   // (until a chain says what produced it)
+    c->ranks.shard_max = 0;               // (the caller tells its largest shard again)
 }
 
-// eigenvalues (cyclic Jacobi, 8 sweeps, unsorted: the order degeneracy_stage of lv_solve_dev.hpp leaves them in) of the 6 x 6
-// pose block of the H^T H packed in a 96-double sums record
-static void host_pose_eigenvalues(const double* rec, double eig[6]) {
-    double A[6][6];
-    int idx = 0;
-    for (int i = 0; i < 12; ++i)
-        for (int j = i; j < 12; ++j) {
-            if (j < 6) { A[i][j] = rec[idx]; A[j][i] = rec[idx]; }
-            ++idx;
+enum class StageW { Zero, Index };
+// repack n caller points into the pinned staging buffer (float4; w = 0 or the point's index as bits), optionally keeping the
+// smallest coordinates seen in bmin and each point's f64 time stamp (time_offset bytes into it) in times.  The caller has made
+// room (ensure_stage) and synchronised the stream since the last use.
+void stage_points(lv_ctx* c, const void* points, size_t stride, size_t n, StageW w_rule, float* bmin = nullptr, double* times = nullptr,
+                  size_t time_offset = 0) {
+    for (size_t i = 0; i < n; ++i) {
+        float x, y, z, w = 0.f;
+        read_xyz(points, stride, i, x, y, z);
+        if (w_rule == StageW::Index) {
+            const uint32_t ui = (uint32_t)i;
+            std::memcpy(&w, &ui, 4);
         }
-    for (int sweep = 0; sweep < 8; ++sweep)
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) {
-                const double apq = A[p][q];
-                if (std::fabs(apq) < 1e-300) continue;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 6; ++k) {
-                    const double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 6; ++k) {
-                    const double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-            }
-    for (int i = 0; i < 6; ++i) eig[i] = A[i][i];
-}
-
-void unpack_sums(const double* rec, lv_sums* out) {
-    int idx = 0;
-    for (int i = 0; i < 12; ++i)
-        for (int j = i; j < 12; ++j) {
-            out->HTH[i * 12 + j] = rec[idx];
-            out->HTH[j * 12 + i] = rec[idx];
-            ++idx;
-        }
-    for (int i = 0; i < 12; ++i) out->HTh[i] = rec[78 + i];
-    out->n_valid = (int64_t)rec[90];
-    out->sum_h2 = rec[91];
-}
-
-// x_host: x / P_prop ride in the first launch's arguments (or kf_begin_kernel's); else kf_begin_kernel installs prior.dev in kf
-int begin_device(lv_ctx* c, const double* x_host, bool defer, const ResidentFilter::Prior& prior = {}) {
-    if (int rf = c->filter.begin_update(c->stream, c->d_kf, prior.dev != nullptr)) return rf;
-    c->begin_pending = false;
-    if (c->capture) LV_HIP(hipMemsetAsync(c->d_kf->level_hist, 0, sizeof(int) * 8, c->stream));   // instrumentation of capturing passes
-    if (defer && x_host && c->scan.n > 0 && c->map.view.m > 0) {
-        // the first search launch installs everything (x_host: x followed by P_prop, KfHostIO layout)
-        std::memcpy(c->h_begin.x, x_host, sizeof(c->h_begin.x));
-        std::memcpy(c->h_begin.P, x_host + NX, sizeof(c->h_begin.P));
-        compute_pose_consts(c->h_begin.x, &c->h_begin.pose);
-        c->begin_pending = true;
-    } else {
-        int rc = launch_kf_begin(c->stream, c->d_kf, c->d_io, x_host, prior.dev, prior.dev_in_kf);
-        if (rc) return rc;
+        c->h_stage[i] = make_float4(x, y, z, w);
+        if (times) std::memcpy(&times[i], reinterpret_cast<const char*>(points) + i * stride + time_offset, sizeof(double));
+        if (bmin) bmin[0] = x < bmin[0] ? x : bmin[0], bmin[1] = y < bmin[1] ? y : bmin[1], bmin[2] = z < bmin[2] ? z : bmin[2];
     }
-    c->grid = fit_grid_size(c->scan.n, c->max_blocks);
-    if ((uint32_t)c->scan.n > c->qstride) {
-        uint32_t cap = c->qstride ? c->qstride : 4096;
-        while (cap < (uint32_t)c->scan.n) cap *= 2;
-        LV_HIP(hipStreamSynchronize(c->stream));
-        hipFree(c->d_qrec);
-        c->d_qrec = nullptr;
-        c->qstride = 0;
-        LV_HIP(hipMalloc(&c->d_qrec, (size_t)cap * qrec_slots(c->prm.NUM_MATCH_POINTS) * sizeof(float4)));
-        c->qstride = cap;
-    }
-    return LV_OK;
 }
 
-int begin_common(lv_ctx* c, const lv_state* x, const double* P, bool defer = true) {
-    KfHostIO* io = c->h_io;
-    std::memcpy(io->x_in, x, sizeof(double) * NX);
-    if (P) {
-        std::memcpy(io->P_in, P, sizeof(double) * NS * NS);
-    } else {
-        for (int i = 0; i < NS * NS; ++i) io->P_in[i] = (i / NS == i % NS) ? 1.0 : 0.0;
-    }
-    c->update_seq = (c->update_seq + 1) & 0x3fffffff;
-    return begin_device(c, io->x_in, defer);   // x_in and P_in (contiguous) ride in the kernel arguments
-}
-
-int pass_solve(lv_ctx* c, bool from_groups);
-
-int pass_reduce(lv_ctx* c, bool finalize) {
-    MatchParams mp;
-    mp.R_inv = 1.0 / c->prm.LiDAR_noise;
-    mp.max_dist_plane_sq = c->prm.MAX_DIST_PLANE * c->prm.MAX_DIST_PLANE;
-    mp.planes_threshold = c->prm.PLANES_THRESHOLD;
-    mp.estimate_extrinsics = c->prm.estimate_extrinsics;
-    DebugOut dbg{};
-    if (c->capture) {
-        int rc = ensure_capture(c, c->scan.n);
-        if (rc) return rc;
-        dbg = c->dbg;
-        c->dbg_valid = true;
-    }
-    if (c->phase_clocks) {
-        if (!c->d_clk) LV_HIP(hipMalloc(&c->d_clk, (size_t)(c->max_blocks + 8) * 16 * sizeof(long long)));
-        dbg.clk = c->d_clk;
-        dbg.clk_blocks = c->grid;
-    }
-    int rc = LV_OK;
-    c->qrec_valid = c->scan.n > 0;
-    if (c->scan.n > 0) {
-        rc = launch_search(c->stream, c->prm.lanes_per_query, c->map.view, c->scan.d_sorted, c->scan.n, c->d_kf, c->d_qrec,
-                           c->qstride, c->tile_lpt ? c->scan.d_tile_order : nullptr, c->scan.n_tiles, mp.max_dist_plane_sq, dbg,
-                           c->begin_pending ? &c->h_begin : nullptr, c->d_io, c->prm.NUM_MATCH_POINTS);
-        c->begin_pending = false;
-    }
-    if (rc) return rc;
-    if (c->ev_mid) LV_HIP(hipEventRecord(c->ev_mid, c->stream));   // profiled pass: brackets the search kernel
-    rc = launch_fit_reduce(c->stream, c->d_qrec, c->qstride, c->scan.n, c->d_kf, mp, c->d_partials, c->grid, dbg, c->prm.NUM_MATCH_POINTS);
-    if (rc) return rc;
-    // few enough block partials (a 64k-point scan leaves 256): solve_kernel folds them itself in one memory
-    // round trip; otherwise stage 1 of the reduction runs as its own kernel
-    c->fold_direct = !finalize && c->grid <= solve_direct_records();
-    if (c->fold_direct) return LV_OK;
-    if (finalize && c->grid <= solve_direct_records())   // the rank's record straight from its block partials
-        return launch_reduce_final(c->stream, c->d_partials, c->grid, c->d_sums, c->d_kf);
-    rc = launch_reduce_groups(c->stream, c->d_partials, c->grid, c->d_groups, &c->ngroups, c->d_kf);
-    if (rc) return rc;
-    if (finalize) return launch_reduce_final(c->stream, c->d_groups, c->ngroups, c->d_sums, c->d_kf);
-    return LV_OK;
-}
-
-// one measurement pass + solve as lv_update / lv_correct run it.  With a communicator (multi-GPU): the rank's
-// record is all-reduced in place on the stream and every rank solves from the identical record.
-int pass_full(lv_ctx* c) {
-    // (a rank without points still runs the pass: its partials are zeros and solve_prep must run)
-    const bool reduced = c->ranks.transport == RankExchange::Transport::Rccl;
-    if (int rc = pass_reduce(c, reduced)) return rc;
-    if (reduced) {
-        const int i = c->pass_index;
-        const bool timed = c->profiling && i >= 0 && (size_t)(2 * i + 1) < c->ev_coll.size();
-        if (timed) LV_HIP(hipEventRecord(c->ev_coll[2 * i], c->stream));
-        if (int rc = c->ranks.allreduce(c->stream, c->d_sums)) return rc;
-        if (timed) { LV_HIP(hipEventRecord(c->ev_coll[2 * i + 1], c->stream)); c->coll_timed = true; }
-    }
-    return pass_solve(c, !reduced);
-}
-
-int pass_solve(lv_ctx* c, bool from_groups) {
-    SolveParams sp;
-    sp.R = c->prm.LiDAR_noise;
-    sp.R_inv = 1.0 / c->prm.LiDAR_noise;
-    for (int i = 0; i < NS; ++i) sp.limits[i] = c->prm.LIMITS[i];
-    sp.maximum_iter = c->prm.MAX_NUM_ITERS;
-    sp.estimate_extrinsics = c->prm.estimate_extrinsics;
-    sp.seq = c->update_seq;
-    sp.degeneracy_mode = c->prm.degeneracy_mode;
-    sp.degeneracy_threshold = c->prm.degeneracy_threshold;
-    if (from_groups && c->fold_direct) return launch_solve(c->stream, c->d_kf, c->d_io, c->d_partials, c->grid, c->d_sums, sp);
-    if (from_groups) return launch_solve(c->stream, c->d_kf, c->d_io, c->d_groups, c->ngroups, c->d_sums, sp);
-    return launch_solve(c->stream, c->d_kf, c->d_io, c->d_sums, 1, nullptr, sp);
-}
-
-// One launch per pass (pass_kernel) applies to the plain single-GPU update: no capture / phase clocks, no
-// communicator (the all-reduce sits between fit and solve), no degeneracy stage, 8 lanes per scan point.
-// the scan size that fixes pass_kernel's geometry: the local scan, or with a communicator the largest shard over the ranks
-// (every rank launches the same grid; workgroups without a tile contribute zero partials)
-// KF_FAULT_BIT (a bounded wait inside pass_kernel expired) rides in the device's fallback counter.  It fails the update that
-// raised it — and only that one: the host clears the bit on the device once it has reported it (the stream is idle at that
-// point), so the context stays usable, and everything that uses the word as a counter masks the bit out.
-static int report_kf_fault(lv_ctx* c, int raw) {
-    const int cnt = raw & (int)~KF_FAULT_BIT;
-    LV_HIP(hipStreamSynchronize(c->stream));
-    LV_HIP(hipMemcpy(&c->d_kf->fallback_queries, &cnt, sizeof(int), hipMemcpyHostToDevice));
-    c->h_io->fallback_queries = cnt;
-    c->fallback_base = cnt;
-    set_error("a bounded wait inside pass_kernel expired: this update's results are invalid (the flag has been cleared; the context stays usable)");
-    return LV_EHIP;
-}
-static inline int fallback_count(int raw) { return raw & (int)~KF_FAULT_BIT; }
-
-// doubles per compact workgroup partial (PassDims<W>::OW, lv_pass_dev.hpp): 32 for the 6-column rows, 96 with extrinsics
-static inline size_t partial_width(const lv_ctx* c) { return c->prm.estimate_extrinsics ? 96u : 32u; }
-uint32_t pass_geometry_points(const lv_ctx* c) { return c->ranks.multi_rank() ? (uint32_t)c->ranks.shard_max : c->scan.n; }
-
-bool pass_fused_applies(const lv_ctx* c) {
-    // (multi-round scans run pass_kernel<.., MULTI>: a round's plane fits run on four wavefronts beside the next round's search
-    // on the other twelve; measured r04 per update: 131 072 points 191.8 us, 196 608 249.1, 262 144 304.9 against 329.3 with
-    // three kernels.  The estimate_extrinsics build keeps round 3's form — a barrier either side of every round's fits — and
-    // its limit of three rounds: 262 144 points 356 vs 352 us)
-    if (c->ranks.multi_rank() ? !c->ranks.fused_ready(c->scan.n) : c->scan.n == 0) return false;   // (a rank without points still runs every launch)
-    int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
-    pass_grid_size(pass_geometry_points(c), c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
-    // (round 5: estimate_extrinsics takes the overlapped multi-round form as well — its rows staged in two halves — so the
-    // limit of three rounds it had is gone: xaloc.yaml's configuration stays on one launch per pass up to the same sixteen)
-    const int max_rounds = c->fused_multi_round > 0 ? INT32_MAX : c->fused_multi_round == 0 ? 3 : PK_DEFAULT_MAX_ROUNDS;
-    if (rounds > max_rounds) return false;
-    if (c->ranks.multi_rank() && !c->ranks.fits((size_t)nwg * partial_width(c))) return false;
-    // (degeneracy_mode 1 only REPORTS eigenvalues: derived on the host from the logged sums, lv_get_degeneracy_values)
-    return c->fused_pass && !c->capture && !c->phase_clocks && c->prm.degeneracy_mode <= 1 && c->prm.NUM_MATCH_POINTS == KNN &&
-           c->prm.lanes_per_query == 8 && (c->prm.estimate_extrinsics == 0 || c->fused_ext) && c->map.view.m > 0;
-}
-
-// The whole iterated update as npass + 1 launches: launch i = [solve of pass i-1 in every workgroup] + pass i, the
-// closing launch (one workgroup) = the solve of the last pass.  begin_device() ran before: either the state waits in
-// h_begin (begin_pending: it rides in the first launch's kernel arguments) or a begin kernel installed it in d_kf.
-int update_fused(lv_ctx* c) {
-    const int npass = c->prm.MAX_NUM_ITERS + 1;
-    PassLaunch pl{};
-    pl.map = &c->map.view;
-    pl.scan = c->scan.d_sorted;
-    pl.tile_order = (c->tile_lpt && c->scan.tile_points == 32u && c->scan.n_tiles == (c->scan.n + 31u) / 32u) ? c->scan.d_tile_order : nullptr;
-    pl.n = c->scan.n;
-    pl.kf = c->d_kf;
-    pl.io = c->d_io;
-    pl.sums_out = c->d_sums;
-    pl.mp.R_inv = 1.0 / c->prm.LiDAR_noise;
-    pl.mp.max_dist_plane_sq = c->prm.MAX_DIST_PLANE * c->prm.MAX_DIST_PLANE;
-    pl.mp.planes_threshold = c->prm.PLANES_THRESHOLD;
-    pl.mp.estimate_extrinsics = c->prm.estimate_extrinsics;
-    pl.mp.fast_fit = c->fast_fit && !c->prm.estimate_extrinsics;
-    pl.sp.R = c->prm.LiDAR_noise;
-    pl.sp.R_inv = 1.0 / c->prm.LiDAR_noise;
-    for (int i = 0; i < NS; ++i) pl.sp.limits[i] = c->prm.LIMITS[i];
-    pl.sp.maximum_iter = c->prm.MAX_NUM_ITERS;
-    pl.sp.estimate_extrinsics = c->prm.estimate_extrinsics;
-    pl.sp.seq = c->update_seq;
-    pl.sp.degeneracy_mode = 0;
-    pl.sp.degeneracy_threshold = c->prm.degeneracy_threshold;
-    int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
-    pass_grid_size(pass_geometry_points(c), c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
-    const bool gathered = c->ranks.multi_rank();              // multi-GPU: the partials of all ranks, gathered after every launch
-    const size_t slot = (size_t)nwg * partial_width(c);       // doubles per rank in the gather buffers (compact records)
-    pl.multi_overlap = c->multi_overlap;
-    pl.qrec = c->record_dump ? c->d_qrec : nullptr;
-    c->pclk_wg = nwg + dedicated;   // (the last slot is the bookkeeping workgroup either way)
-    pl.qstride = c->qstride;
-    c->qrec_valid = c->record_dump;
-    c->last_update_fused = true;
-    for (int i = 0; i <= npass; ++i) {
-        const bool closing = i == npass;
-        pl.mode = i == 0 ? (c->begin_pending ? 0 : 2) : 1;
-        pl.recs_in = gathered ? c->ranks.d_gather[(i + 1) & 1] : c->d_cpart[(i + 1) & 1];
-        pl.part_out = gathered ? c->ranks.part_out(i & 1, slot) : c->d_cpart[i & 1];
-        pl.nrec = c->ranks.nrec(nwg);
-        pl.cost_in = (i > 0 && c->keeper_by_cost) ? c->d_wgcost[(i + 1) & 1] : nullptr;
-        pl.cost_out = c->d_wgcost[i & 1];
-        pl.nwg = nwg;
-        pl.rounds = closing ? 0 : rounds;
-        pl.steps = steps;
-        pl.dedicated = dedicated;
-        pl.launch = i;
-        pl.clk = c->d_pclk ? c->d_pclk + (size_t)i * (c->pass_max_wg + 1) * pass_clock_words() : nullptr;
-        if (c->profiling && !closing) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 0], c->stream));
-        int rc = launch_pass(c->stream, pl, (i == 0 && c->begin_pending) ? &c->h_begin : nullptr);
-        c->begin_pending = false;
-        if (rc) return rc;
-        if (c->profiling && !closing) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 1], c->stream));   // (the pass kernel alone)
-        if (gathered && !closing) {
-            if (c->profiling) LV_HIP(hipEventRecord(c->ev_coll[2 * i], c->stream));
-            if ((rc = c->ranks.exchange(c->stream, i, slot))) return rc;
-            if (c->profiling) LV_HIP(hipEventRecord(c->ev_coll[2 * i + 1], c->stream));
-        }
-        if (c->profiling && !closing) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 2], c->stream));
-    }
-    c->coll_timed = gathered && c->profiling;
+// lv_create, once the context exists: the knobs out of the environment, then streams, events and buffers
+int create_in(lv_ctx* c) {
+    c->scan.tile_points = 256u / (uint32_t)c->prm.lanes_per_query;
+    c->map.cell = c->prm.voxel_size;
+    hipDeviceProp_t prop;
+    LV_HIP(hipGetDeviceProperties(&prop, c->device));
+    LV_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    LV_HIP(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+    c->rebuild.create_streams(c->device, /*quiet=*/true);   // (a failure is retried by the first background rebuild)
+    LV_HIP(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
+    if (int rk = Knobs<lv_ctx>::read_environment(*c)) return rk;
+    if (int ru = c->upd.alloc(prop.multiProcessorCount)) return ru;
+    if (int rf = c->filter.alloc()) return rf;
+    LV_HIP(hipMalloc(&c->d_obs, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
+    LV_HIP(hipMemset(c->d_obs, 0, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
     return LV_OK;
 }
 
@@ -552,77 +231,10 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
     if (!c) { set_error("out of host memory"); return LV_EINVAL; }
     c->prm = *params;
     c->device = device;
-    c->scan.tile_points = 256u / (uint32_t)S;
-    c->map.cell = params->voxel_size;
-    hipDeviceProp_t prop;
-    LV_HIP(hipGetDeviceProperties(&prop, device));
-    int per_cu = 4;
-    if (const char* e = getenv("LV_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : 4;  // tuning knob
-    if (const char* e = getenv("LV_TILE_LPT")) c->tile_lpt = atoi(e) != 0;
-    if (const char* e = getenv("LV_SPIN_WAIT")) c->spin_wait = atoi(e) != 0;
-    if (const char* e = getenv("LV_FUSED_PASS")) c->fused_pass = atoi(e) != 0;
-    if (const char* e = getenv("LV_FUSED_EXT")) c->fused_ext = atoi(e) != 0;
-    if (const char* e = getenv("LV_FUSED_MULTI")) c->fused_multi_round = atoi(e) != 0 ? 1 : 0;
-    if (const char* e = getenv("LV_ASYNC_RELINEARISE")) c->rebuild.opt.async = atoi(e) != 0;
-    if (const char* e = getenv("LV_RELIN_SLICE_WGS")) c->rebuild.opt.slice_wgs = (uint32_t)atol(e);
-    if (const char* e = getenv("LV_RELIN_PAUSE_US")) c->rebuild.opt.pause_us = (uint32_t)atol(e);
-    if (const char* e = getenv("LV_MULTI_OVERLAP")) c->multi_overlap = atoi(e) != 0;   // A/B: 0 = every round's fits between two barriers
-    if (const char* e = getenv("LV_KEEPER_BY_COST")) c->keeper_by_cost = atoi(e) != 0;
-    if (const char* e = getenv("LV_COMM_FUSED")) c->ranks.fused = atoi(e) != 0;
-    if (const char* e = getenv("LV_SMALL_WINDOW")) c->scan.small_enabled = atoi(e) != 0;
-    if (const char* e = getenv("LV_LARGE_WINDOW")) c->scan.large_enabled = atoi(e) != 0;
-    if (const char* e = getenv("LV_MAIL_FILTER")) c->filter.mail_filter = atoi(e) != 0;
-    if (const char* e = getenv("LV_SMALL_INSERT")) c->map.small_front = atoi(e) != 0;
-    if (const char* e = getenv("LV_SURV_LIST")) c->map.surv_list = atoi(e) != 0;
-    // (the stamp buffer below is strided by pass_max_wg + 1 workgroup slots: fix the grid limit first)
-    c->pass_max_wg = prop.multiProcessorCount;
-    if (const char* e = getenv("LV_PASS_WG")) c->pass_max_wg = atoi(e) > 0 ? atoi(e) : c->pass_max_wg;
-    if (const char* e = getenv("LV_PASS_CLK")) {
-        if (atoi(e) != 0) {
-            const size_t words = (size_t)(MAX_PASSES + 1) * (c->pass_max_wg + 1) * pass_clock_words();   // per launch of an update
-            LV_HIP(hipMalloc(&c->d_pclk, words * sizeof(long long)));
-            LV_HIP(hipMemset(c->d_pclk, 0, words * sizeof(long long)));
-        }
+    if (int rc = create_in(c)) {   // (what was created so far goes; *out stays null)
+        lv_destroy(c);
+        return rc;
     }
-    c->max_blocks = prop.multiProcessorCount * per_cu;
-    if (c->max_blocks < 64) c->max_blocks = 64;
-    LV_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    LV_HIP(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-    c->rebuild.create_streams(device, /*quiet=*/true);   // (a failure is retried by the first background rebuild)
-    LV_HIP(hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
-    if (const char* e = getenv("LV_OVERLAP_INSERT")) c->overlap_insert = atoi(e) != 0;
-    if (const char* e = getenv("LV_BATCH_PREDICT")) c->filter.batch_predict = atoi(e) != 0;
-    if (const char* e = getenv("LV_MERGED_INSERT")) c->map.merged_back = atoi(e) != 0;
-    if (const char* e = getenv("LV_SWEEP_EVICT")) c->map.sweep_evict = atoi(e) != 0;
-    LV_HIP(hipMalloc(&c->d_kf, sizeof(KfDev)));
-    LV_HIP(hipMemset(c->d_kf, 0, sizeof(KfDev)));
-    if (int rf = c->filter.alloc()) return rf;
-    LV_HIP(hipMalloc(&c->d_obs, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
-    LV_HIP(hipMemset(c->d_obs, 0, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
-    LV_HIP(hipHostMalloc((void**)&c->h_kf, sizeof(KfDev), hipHostMallocDefault));
-    std::memset(c->h_kf, 0, sizeof(KfDev));
-    LV_HIP(hipHostMalloc((void**)&c->h_io, sizeof(KfHostIO), hipHostMallocMapped));
-    std::memset(c->h_io, 0, sizeof(KfHostIO));
-    LV_HIP(hipHostGetDevicePointer((void**)&c->d_io, c->h_io, 0));
-    LV_HIP(hipMalloc(&c->d_partials, (size_t)(c->max_blocks + 8) * SUMS_LEN * sizeof(double)));
-    LV_HIP(hipMalloc(&c->d_groups, (size_t)(c->max_blocks / 32 + 2) * SUMS_LEN * sizeof(double)));
-    for (int i = 0; i < 2; ++i) {
-        LV_HIP(hipMalloc(&c->d_cpart[i], (size_t)(c->pass_max_wg + 8) * SUMS_LEN * sizeof(double)));
-        LV_HIP(hipMemset(c->d_cpart[i], 0, (size_t)(c->pass_max_wg + 8) * SUMS_LEN * sizeof(double)));
-        LV_HIP(hipMalloc(&c->d_wgcost[i], (size_t)(c->pass_max_wg + 8) * sizeof(uint32_t)));
-        LV_HIP(hipMemset(c->d_wgcost[i], 0, (size_t)(c->pass_max_wg + 8) * sizeof(uint32_t)));
-    }
-    LV_HIP(hipMalloc(&c->d_sums_own, SUMS_LEN * sizeof(double)));
-    LV_HIP(hipMemset(c->d_sums_own, 0, SUMS_LEN * sizeof(double)));
-    c->d_sums = c->d_sums_own;
-    LV_HIP(hipHostMalloc((void**)&c->h_sums, SUMS_LEN * sizeof(double), hipHostMallocDefault));
-    LV_HIP(hipEventCreate(&c->ev_begin));
-    LV_HIP(hipEventCreate(&c->ev_end));
-    c->ev_pass.resize((size_t)(params->MAX_NUM_ITERS + 1) * 3);
-    for (auto& ev : c->ev_pass) LV_HIP(hipEventCreate(&ev));
-    c->ev_coll.resize((size_t)(params->MAX_NUM_ITERS + 1) * 2);
-    for (auto& ev : c->ev_coll) LV_HIP(hipEventCreate(&ev));
     *out = c;
     return LV_OK;
 }
@@ -632,7 +244,7 @@ static CtxStreams ctx_streams(lv_ctx* c) {
     return {c->stream, c->side_stream, c->ev_staged, c->overlap_insert && c->side_stream && c->stream == c->own_stream};
 }
 
-void lv_destroy(lv_ctx* c) {
+void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part of the way: everything here takes what is not there)
     if (!c) return;
     hipSetDevice(c->device);
     c->cloud.release();
@@ -651,21 +263,12 @@ void lv_destroy(lv_ctx* c) {
     c->vol.release();
     c->batch.release();
     c->scan.release();
-    free_capture(c);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->h_kf) hipHostFree(c->h_kf);
-    if (c->h_io) hipHostFree(c->h_io);
+    c->h_stage.release();
     c->filter.release();
     hipFree(c->d_obs);
     if (c->h_states_ring) hipHostFree(c->h_states_ring);
-    if (c->h_sums) hipHostFree(c->h_sums);
-    hipFree(c->d_cpart[0]); hipFree(c->d_cpart[1]); hipFree(c->d_pclk); hipFree(c->d_wgcost[0]); hipFree(c->d_wgcost[1]);
     c->ranks.release();
-    hipFree(c->d_qrec); hipFree(c->d_clk); hipFree(c->d_kf); hipFree(c->d_partials); hipFree(c->d_groups); hipFree(c->d_sums_own);
-    if (c->ev_begin) hipEventDestroy(c->ev_begin);
-    if (c->ev_end) hipEventDestroy(c->ev_end);
-    for (auto ev : c->ev_pass) hipEventDestroy(ev);
-    for (auto ev : c->ev_coll) hipEventDestroy(ev);
+    c->upd.release();
     if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
     if (c->ev_staged) hipEventDestroy(c->ev_staged);
     if (c->own_stream) hipStreamDestroy(c->own_stream);
@@ -674,7 +277,7 @@ void lv_destroy(lv_ctx* c) {
 
 int lv_set_stream(lv_ctx* c, void* hip_stream) {
     LV_CHECK_CTX(c);
-    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
+    if (int rp = c->filter.flush(c->stream, c->upd.d_kf)) return rp;
     // whatever is still tied to the OLD stream is settled on it: a remembered Buffer::clear (CloudStore keeps the stream it was
     // issued on: the caller may destroy that stream after this call) and the outcome of an incremental map insert
     { int rs = c->cloud.settle(); if (rs) return rs; }
@@ -687,7 +290,7 @@ int lv_set_stream(lv_ctx* c, void* hip_stream) {
 void* lv_get_stream(lv_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int lv_synchronize(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
+    if (int rp = c->filter.flush(c->stream, c->upd.d_kf)) return rp;
     LV_HIP(hipStreamSynchronize(c->stream));
     if (c->side_stream) LV_HIP(hipStreamSynchronize(c->side_stream));
     return LV_OK;
@@ -695,14 +298,9 @@ int lv_synchronize(lv_ctx* c) {
 
 // repack caller points into the pinned staging buffer (float4) and upload them to `dst` (device)
 static int stage_map_points(lv_ctx* c, const void* points, size_t stride, size_t n, float4* dst) {
-    int rc = ensure_stage(c, n);
-    if (rc) return rc;
+    if (int rc = ensure_stage(c, n)) return rc;
     LV_HIP(hipStreamSynchronize(c->stream));  // staging buffer reuse
-    for (size_t i = 0; i < n; ++i) {
-        float x, y, z;
-        read_xyz(points, stride, i, x, y, z);
-        c->h_stage[i] = make_float4(x, y, z, 0.f);
-    }
+    stage_points(c, points, stride, n, StageW::Zero);
     if (n) LV_HIP(hipMemcpyAsync(dst, c->h_stage, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     return LV_OK;
 }
@@ -796,13 +394,13 @@ int lv_map_add_scan(lv_ctx* c, int downsample) {
     LV_RELIN_POLL(c);
     const uint32_t n = c->scan.n;
     if (n == 0) return LV_OK;   // Mapper::add returns on an empty cloud (Mapper.cpp:20)
-    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
+    if (int rp = c->filter.flush(c->stream, c->upd.d_kf)) return rp;
     int rc = c->rebuild.maybe_start(c->map, n);
     if (rc) return rc;
     rc = c->map.reserve_batch(n);
     if (rc) return rc;
     if (int ru = c->filter.upload(c->stream)) return ru;
-    const double* x = c->filter.scan_x(c->d_kf);
+    const double* x = c->filter.scan_x(c->upd.d_kf);
     hipLaunchKernelGGL(scan_to_world_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, x, c->scan.d_raw, n, c->map.d_new);
     LV_HIP(hipGetLastError());
     // The insert depends on nothing but the world points just staged, and nothing depends on it until the next search: it runs
@@ -1371,13 +969,13 @@ int lv_map_box_search(lv_ctx* c, const float lo[3], const float hi[3], uint32_t*
 static int batch_common(lv_ctx* c, const lv_state* xs, size_t m, const double* P, bool solve, lv_state* x_out, double* P_out, int* passes,
                         lv_sums* out) {
     if (c->ranks.multi_rank()) { set_error("multi-hypothesis updates run on one GPU: this context has a multi-GPU communicator"); return LV_ESTATE; }
-    if (c->in_update) { set_error("multi-hypothesis update inside lv_update_begin / lv_update_end"); return LV_ESTATE; }
+    if (c->upd.in_update) { set_error("multi-hypothesis update inside lv_update_begin / lv_update_end"); return LV_ESTATE; }
     if (passes) std::memset(passes, 0, m * sizeof(int));
     if (out) std::memset(out, 0, m * sizeof(lv_sums));
     if (P_out) for (size_t i = 0; i < m; ++i) std::memcpy(P_out + i * NS * NS, P, sizeof(double) * NS * NS);
     if (c->map.view.m == 0 || c->scan.n == 0) return LV_OK;   // every state unchanged, passes 0, n_valid 0
     std::vector<double> recs(out ? m * SUMS_LEN : 0);
-    int rc = c->batch.run(c->prm, c->max_blocks, c->map.view, c->scan.d_sorted, c->scan.n, c->stream, xs, m, P, solve, x_out, P_out, passes,
+    int rc = c->batch.run(c->prm, c->upd.max_blocks, c->map.view, c->scan.d_sorted, c->scan.n, c->stream, xs, m, P, solve, x_out, P_out, passes,
                           out ? recs.data() : nullptr);
     if (rc) return rc;
     if (out) for (size_t i = 0; i < m; ++i) unpack_sums(recs.data() + i * SUMS_LEN, &out[i]);
@@ -1406,28 +1004,13 @@ int lv_scan_set(lv_ctx* c, const void* points, size_t stride, size_t n) {
     LV_CHECK_CTX(c);
     if (n && (!points || stride < 12)) { set_error("bad point array (stride %zu)", stride); return LV_EINVAL; }
     if (n > 0xFFFFFFF0ull) { set_error("scan too large"); return LV_EINVAL; }
-    int rc = ensure_stage(c, n);
-    if (rc) return rc;
-    rc = c->scan.reserve(n);
-    if (rc) return rc;
+    if (int rc = ensure_stage(c, n)) return rc;
+    if (int rc = c->scan.reserve(n)) return rc;
     LV_HIP(hipStreamSynchronize(c->stream));  // staging buffer reuse
     float bmin[3] = {INFINITY, INFINITY, INFINITY};
-    for (size_t i = 0; i < n; ++i) {
-        float x, y, z;
-        read_xyz(points, stride, i, x, y, z);
-        uint32_t ui = (uint32_t)i;
-        float w;
-        std::memcpy(&w, &ui, 4);
-        c->h_stage[i] = make_float4(x, y, z, w);
-        if (x < bmin[0]) bmin[0] = x;
-        if (y < bmin[1]) bmin[1] = y;
-        if (z < bmin[2]) bmin[2] = z;
-    }
-    c->scan.n = (uint32_t)n;
-    c->scan.route = LV_SCAN_ROUTE_NONE;   // (uploaded as it is: no voxel grid ran)
-    c->ranks.shard_max = 0;   // (a new scan: the caller tells its largest shard again)
-    c->dbg_valid = false;
-    c->qrec_valid = false;
+    stage_points(c, points, stride, n, StageW::Index, bmin);
+    new_scan(c);
+    c->scan.n = (uint32_t)n;   // (uploaded as it is: no voxel grid ran, the route stays "none")
     if (n == 0) return LV_OK;
     LV_HIP(hipMemcpyAsync(c->scan.d_raw, c->h_stage, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     return c->scan.sort(c->stream, bmin, c->prm.voxel_size);
@@ -1440,24 +1023,13 @@ int lv_scan_deskew(lv_ctx* c, const void* points, size_t stride, size_t time_off
     if (n && (!points || stride < 12 || time_offset + 8 > stride)) { set_error("bad point array (stride %zu, time offset %zu)", stride, time_offset); return LV_EINVAL; }
     if (!states || n_states < 2 || !Xt2) { set_error("need >= 2 surrounding states and Xt2"); return LV_EINVAL; }
     if (n > 0xFFFFFFF0ull) { set_error("scan too large"); return LV_EINVAL; }
-    c->dbg_valid = false;
-    c->qrec_valid = false;
-    c->scan.n = 0;
-    c->scan.route = LV_SCAN_ROUTE_NONE;
-    c->ranks.shard_max = 0;
+    new_scan(c);
     if (n == 0) return LV_OK;
-    int rc = ensure_stage(c, n + (n + 1) / 2);  // float4 xyz + packed doubles behind them
-    if (rc) return rc;
-    rc = c->scan.reserve_raw(n, n_states);
-    if (rc) return rc;
+    if (int rc = ensure_stage(c, n + (n + 1) / 2)) return rc;  // float4 xyz + packed doubles behind them
+    if (int rc = c->scan.reserve_raw(n, n_states)) return rc;
     LV_HIP(hipStreamSynchronize(c->stream));  // staging buffer reuse
     double* h_times = reinterpret_cast<double*>(c->h_stage + n);
-    for (size_t i = 0; i < n; ++i) {
-        float x, y, z;
-        read_xyz(points, stride, i, x, y, z);
-        c->h_stage[i] = make_float4(x, y, z, 0.f);
-        std::memcpy(&h_times[i], reinterpret_cast<const char*>(points) + i * stride + time_offset, sizeof(double));
-    }
+    stage_points(c, points, stride, n, StageW::Zero, nullptr, h_times, time_offset);
     LV_HIP(hipMemcpyAsync(c->scan.d_in, c->h_stage, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     LV_HIP(hipMemcpyAsync(c->scan.d_times, h_times, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     LV_HIP(hipMemcpyAsync(c->scan.d_states, states, n_states * sizeof(MotionState), hipMemcpyHostToDevice, c->stream));
@@ -1472,27 +1044,13 @@ int lv_scan_downsample(lv_ctx* c, const void* points, size_t stride, size_t n, f
     LV_CHECK_CTX(c);
     if (n && (!points || stride < 12)) { set_error("bad point array (stride %zu)", stride); return LV_EINVAL; }
     if (n > 0xFFFFFFF0ull) { set_error("scan too large"); return LV_EINVAL; }
-    c->dbg_valid = false;
-    c->qrec_valid = false;
-    c->scan.n = 0;
-    c->scan.route = LV_SCAN_ROUTE_NONE;
-    c->ranks.shard_max = 0;
+    new_scan(c);
     if (n == 0) return LV_OK;
-    int rc = ensure_stage(c, n);
-    if (rc) return rc;
-    rc = c->scan.reserve_raw(n, 2);
-    if (rc) return rc;
-    rc = c->scan.reserve(n);
-    if (rc) return rc;
+    if (int rc = ensure_stage(c, n)) return rc;
+    if (int rc = c->scan.reserve_raw(n, 2)) return rc;
+    if (int rc = c->scan.reserve(n)) return rc;
     LV_HIP(hipStreamSynchronize(c->stream));  // staging buffer reuse
-    for (size_t i = 0; i < n; ++i) {
-        float x, y, z;
-        read_xyz(points, stride, i, x, y, z);
-        uint32_t ui = (uint32_t)i;
-        float w;
-        std::memcpy(&w, &ui, 4);
-        c->h_stage[i] = make_float4(x, y, z, w);
-    }
+    stage_points(c, points, stride, n, StageW::Index);
     float4* dst = downsample_prec > 0.f ? c->scan.d_desk : c->scan.d_raw;
     LV_HIP(hipMemcpyAsync(dst, c->h_stage, n * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     return c->scan.voxel_and_sort(c->stream, (uint32_t)n, downsample_prec, c->prm.voxel_size, true);
@@ -1606,15 +1164,7 @@ int lv_reserve_stream(lv_ctx* c, size_t max_window_points, size_t max_scan_point
         if (!rc) rc = c->map.reserve_batch(max_scan_points);
         if (rc) return rc;
         LV_HIP(note_alloc(c->map.notes));
-        if ((uint32_t)max_scan_points > c->qstride) {
-            uint32_t cap = c->qstride ? c->qstride : 4096;
-            while (cap < (uint32_t)max_scan_points) cap *= 2;
-            hipFree(c->d_qrec);
-            c->d_qrec = nullptr;
-            c->qstride = 0;
-            LV_HIP(hipMalloc(&c->d_qrec, (size_t)cap * qrec_slots(c->prm.NUM_MATCH_POINTS) * sizeof(float4)));
-            c->qstride = cap;
-        }
+        if (int rg = c->upd.grow_records(c->stream, max_scan_points)) return rg;
     }
     return LV_OK;
 }
@@ -1649,11 +1199,7 @@ int lv_scan_deskew_window(lv_ctx* c, double t1, double t2, const lv_motion_state
     LV_CHECK_CTX(c);
     if (n_window) *n_window = 0;
     if (!states || n_states < 2 || !Xt2) { set_error("need >= 2 surrounding states and Xt2"); return LV_EINVAL; }
-    c->dbg_valid = false;
-    c->qrec_valid = false;
-    c->scan.n = 0;
-    c->scan.route = LV_SCAN_ROUTE_NONE;
-    c->ranks.shard_max = 0;
+    new_scan(c);
     uint32_t lo = 0, hi = 0;
     int rc = c->scan.reserve_raw(1, n_states);   // (the bounds words exist: the window kernel resets them on the way)
     if (rc) return rc;
@@ -1702,18 +1248,18 @@ int lv_scan_fetch(lv_ctx* c, float* xyz_out, size_t capacity) {
 
 int lv_set_capture(lv_ctx* c, int enabled) {
     LV_CHECK_CTX(c);
-    c->capture = enabled != 0;
+    c->upd.capture = enabled != 0;
     return LV_OK;
 }
 
 int lv_set_record_dump(lv_ctx* c, int enabled) {
     LV_CHECK_CTX(c);
-    c->record_dump = enabled != 0;
+    c->upd.record_dump = enabled != 0;
     return LV_OK;
 }
 
-int lv_last_update_fused(lv_ctx* c) { return (c && c->last_update_fused) ? 1 : 0; }
-int lv_last_passes(lv_ctx* c) { return c ? c->h_io->passes : 0; }
+int lv_last_update_fused(lv_ctx* c) { return (c && c->upd.last_update_fused) ? 1 : 0; }
+int lv_last_passes(lv_ctx* c) { return c ? c->upd.h_io->passes : 0; }
 
 int lv_pass_geometry(size_t n_scan, int n_cus, int out[4]) {
     if (!out || n_cus < 1 || n_scan > 0xFFFFFFF0ull) { set_error("lv_pass_geometry: bad arguments"); return LV_EINVAL; }
@@ -1723,59 +1269,31 @@ int lv_pass_geometry(size_t n_scan, int n_cus, int out[4]) {
 
 int lv_set_fused_pass(lv_ctx* c, int enabled) {
     LV_CHECK_CTX(c);
-    c->fused_pass = enabled != 0;
+    c->upd.fused_pass = enabled != 0;
     return LV_OK;
 }
 
 int lv_set_option(lv_ctx* c, const char* name, int value) {
     LV_CHECK_CTX(c);
     if (!name) { set_error("null argument"); return LV_EINVAL; }
-    if (c->in_update) { set_error("lv_set_option inside an update"); return LV_ESTATE; }
-    const bool on = value != 0;
-    if (!std::strcmp(name, "fused_pass")) c->fused_pass = on;
-    else if (!std::strcmp(name, "fused_ext")) c->fused_ext = on;
-    else if (!std::strcmp(name, "fast_fit")) c->fast_fit = on;
-    else if (!std::strcmp(name, "async_relinearise")) c->rebuild.opt.async = on;
-    else if (!std::strcmp(name, "async_relinearise_min")) c->rebuild.opt.async_min = value > 0 ? (size_t)value : 0;
-    else if (!std::strcmp(name, "async_relinearise_pause_us")) c->rebuild.opt.pause_us = value > 0 ? (uint32_t)value : 0u;
-    else if (!std::strcmp(name, "async_relinearise_slice_wgs")) c->rebuild.opt.slice_wgs = value > 0 ? (uint32_t)value : 0u;      // 0: whole grids
-    else if (!std::strcmp(name, "async_relinearise_journal_max")) c->rebuild.opt.journal_max = value > 0 ? (size_t)value : 1;
-    else if (!std::strcmp(name, "async_relinearise_test_delay_ms")) c->rebuild.opt.test_delay_ms = value;
-    else if (!std::strcmp(name, "async_relinearise_test_race")) c->rebuild.opt.test_race = on;
-    else if (!std::strcmp(name, "multi_overlap")) c->multi_overlap = on;
-    else if (!std::strcmp(name, "fused_multi_round")) c->fused_multi_round = on ? 1 : 0;
-    else if (!std::strcmp(name, "keeper_by_cost")) c->keeper_by_cost = on;
-    else if (!std::strcmp(name, "tile_lpt")) c->tile_lpt = on;
-    else if (!std::strcmp(name, "spin_wait")) c->spin_wait = on;
-    else if (!std::strcmp(name, "comm_fused")) c->ranks.fused = on;
-    else if (!std::strcmp(name, "mail_filter")) c->filter.mail_filter = on;
-    else if (!std::strcmp(name, "overlap_insert")) c->overlap_insert = on;
-    else if (!std::strcmp(name, "batch_predict")) { if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp; c->filter.batch_predict = on; }
-    else if (!std::strcmp(name, "merged_insert")) c->map.merged_back = on;
-    else if (!std::strcmp(name, "sweep_evict")) c->map.sweep_evict = on;
-    else if (!std::strcmp(name, "small_window")) c->scan.small_enabled = on;
-    else if (!std::strcmp(name, "large_window")) c->scan.large_enabled = on;
-    else if (!std::strcmp(name, "small_insert")) c->map.small_front = on;
-    else if (!std::strcmp(name, "survivor_list")) c->map.surv_list = on;
-    else if (!std::strcmp(name, "batch_chunk_hypotheses")) c->batch.chunk_hyp = value > 0 ? value : 0;
-    else { set_error("lv_set_option: unknown option '%s'", name); return LV_EINVAL; }
-    return LV_OK;
+    if (int rb = c->upd.busy("lv_set_option")) return rb;
+    return Knobs<lv_ctx>::set_option(*c, name, value);   // (the table: lv_knobs.hpp)
 }
 
 int lv_get_pass_clocks(lv_ctx* c, long long* out, int capacity_wg, int* n_wg) {
     LV_CHECK_CTX(c);
-    if (!c->d_pclk) { set_error("no pass clocks: create the context with LV_PASS_CLK=1 in the environment"); return LV_ESTATE; }
+    if (!c->upd.d_pclk) { set_error("no pass clocks: create the context with LV_PASS_CLK=1 in the environment"); return LV_ESTATE; }
     // layout: [launch 0 .. MAX_NUM_ITERS + 1][pass_max_wg + 1 workgroup slots][pass_clock_words()]; slot n_wg - 1 of a launch is
     // its bookkeeping workgroup (stamp 10 = books done); the closing launch has one workgroup (slot 0)
-    const int slots = c->pass_max_wg + 1;
+    const int slots = c->upd.pass_max_wg + 1;
     if (!out) {   // size query: *n_wg = workgroup slots per launch (the stride of the layout)
         if (n_wg) *n_wg = slots;
         return LV_OK;
     }
     if (capacity_wg < slots) { set_error("lv_get_pass_clocks: capacity %d < %d workgroup slots per launch", capacity_wg, slots); return LV_EINVAL; }
     LV_HIP(hipStreamSynchronize(c->stream));
-    LV_HIP(hipMemcpy(out, c->d_pclk, (size_t)(c->prm.MAX_NUM_ITERS + 2) * slots * pass_clock_words() * sizeof(long long), hipMemcpyDeviceToHost));
-    if (n_wg) *n_wg = c->pclk_wg;
+    LV_HIP(hipMemcpy(out, c->upd.d_pclk, (size_t)(c->prm.MAX_NUM_ITERS + 2) * slots * pass_clock_words() * sizeof(long long), hipMemcpyDeviceToHost));
+    if (n_wg) *n_wg = c->upd.pclk_wg;
     return LV_OK;
 }
 
@@ -1783,36 +1301,19 @@ int lv_iterate(lv_ctx* c, const lv_state* x, lv_sums* out) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
     if (!x || !out) { set_error("null argument"); return LV_EINVAL; }
-    std::memset(out, 0, sizeof(*out));
-    if (c->map.view.m == 0 || c->scan.n == 0) { c->dbg_valid = false; return LV_OK; }  // Mapper.cpp:42 — empty Matches
-    const bool cap = c->capture;
-    c->capture = true;  // lv_iterate is the API-parity path: always captures per-point outputs
-    int rc = begin_common(c, x, nullptr);
-    if (!rc) rc = pass_reduce(c, true);
-    c->capture = cap;
-    if (rc) return rc;
-    LV_HIP(hipMemcpyAsync(c->h_sums, c->d_sums, SUMS_LEN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipMemcpyAsync(&c->h_kf->fallback_queries, &c->d_kf->fallback_queries, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    unpack_sums(c->h_sums, out);
-    c->timing.fallback_queries = fallback_count(c->h_kf->fallback_queries) - c->fallback_base;
-    c->fallback_base = fallback_count(c->h_kf->fallback_queries);
-    return LV_OK;
+    return c->upd.iterate(inputs(c), x, out);
 }
 
 int lv_update_begin(lv_ctx* c, const lv_state* x, const double* P) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
     if (!x || !P) { set_error("null argument"); return LV_EINVAL; }
-    c->in_update = true;
-    c->passes_issued = 0;
-    return begin_common(c, x, P);
+    return c->upd.update_begin(inputs(c), x, P);
 }
 
 int lv_pass_reduce(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    if (!c->in_update) { set_error("lv_pass_reduce outside lv_update_begin/end"); return LV_ESTATE; }
-    return pass_reduce(c, true);
+    return c->upd.split_reduce(inputs(c));
 }
 
 // ---- multi-GPU (row e): RCCL issued from the library on the context stream ------------------------------
@@ -1824,33 +1325,33 @@ int lv_comm_unique_id(const char* rccl_library, void* id128) {
 int lv_comm_init(lv_ctx* c, const char* rccl_library, const void* id128, int rank, int world) {
     LV_CHECK_CTX(c);
     if (!id128 || world < 1 || rank < 0 || rank >= world) { set_error("lv_comm_init: bad arguments (rank %d, world %d)", rank, world); return LV_EINVAL; }
-    if (c->in_update) { set_error("lv_comm_init inside an update"); return LV_ESTATE; }
+    if (int rb = c->upd.busy("lv_comm_init")) return rb;
     return c->ranks.init_rccl(rccl_library, id128, rank, world);
 }
 
 int lv_comm_destroy(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    if (c->in_update) { set_error("lv_comm_destroy inside an update"); return LV_ESTATE; }
+    if (int rb = c->upd.busy("lv_comm_destroy")) return rb;
     return c->ranks.destroy(c->stream);
 }
 
 int lv_comm_set_host_gather(lv_ctx* c, int rank, int world, lv_gather_fn fn, void* user) {
     LV_CHECK_CTX(c);
-    if (c->in_update) { set_error("lv_comm_set_host_gather inside an update"); return LV_ESTATE; }
+    if (int rb = c->upd.busy("lv_comm_set_host_gather")) return rb;
     return c->ranks.set_host_gather(c->stream, rank, world, fn, user);
 }
 
 int lv_comm_peer_export(lv_ctx* c, void* handle_blob) {
     LV_CHECK_CTX(c);
     if (!handle_blob) { set_error("null argument"); return LV_EINVAL; }
-    if (c->in_update) { set_error("lv_comm_peer_export inside an update"); return LV_ESTATE; }
-    return c->ranks.peer_export(c->stream, c->pass_max_wg, handle_blob);
+    if (int rb = c->upd.busy("lv_comm_peer_export")) return rb;
+    return c->ranks.peer_export(c->stream, c->upd.pass_max_wg, handle_blob);
 }
 
 int lv_comm_peer_init(lv_ctx* c, int rank, int world, const void* handles) {
     LV_CHECK_CTX(c);
     if (!handles) { set_error("null argument"); return LV_EINVAL; }
-    if (c->in_update) { set_error("lv_comm_peer_init inside an update"); return LV_ESTATE; }
+    if (int rb = c->upd.busy("lv_comm_peer_init")) return rb;
     return c->ranks.peer_init(c->stream, rank, world, handles);
 }
 
@@ -1858,13 +1359,13 @@ int lv_comm_world(lv_ctx* c) { return c ? c->ranks.world : 0; }
 
 int lv_comm_set_shard_max(lv_ctx* c, size_t n_max) {
     LV_CHECK_CTX(c);
-    if (c->in_update) { set_error("lv_comm_set_shard_max inside an update"); return LV_ESTATE; }
+    if (int rb = c->upd.busy("lv_comm_set_shard_max")) return rb;
     if (n_max > 0xFFFFFFF0ull) { set_error("shard too large"); return LV_EINVAL; }
     c->ranks.shard_max = n_max;
     if (!c->ranks.multi_rank() || n_max == 0) return LV_OK;
     int nwg = 0, rounds = 0, steps = 0, dedicated = 0;
-    pass_grid_size((uint32_t)n_max, c->pass_max_wg, &nwg, &steps, &rounds, &dedicated);
-    return c->ranks.reserve(c->stream, (size_t)nwg * partial_width(c));
+    pass_grid_size((uint32_t)n_max, c->upd.pass_max_wg, &nwg, &steps, &rounds, &dedicated);
+    return c->ranks.reserve(c->stream, (size_t)nwg * c->upd.partial_width());
 }
 
 int lv_set_comm_fused(lv_ctx* c, int enabled) {
@@ -1873,147 +1374,28 @@ int lv_set_comm_fused(lv_ctx* c, int enabled) {
     return LV_OK;
 }
 
-void* lv_sums_device_ptr(lv_ctx* c) { return c ? (void*)c->d_sums : nullptr; }
+void* lv_sums_device_ptr(lv_ctx* c) { return c ? (void*)c->upd.d_sums : nullptr; }
 
 int lv_set_sums_buffer(lv_ctx* c, void* device_ptr) {
     LV_CHECK_CTX(c);
-    if (c->in_update) { set_error("lv_set_sums_buffer inside an update"); return LV_ESTATE; }
-    LV_HIP(hipStreamSynchronize(c->stream));
-    c->d_sums = device_ptr ? static_cast<double*>(device_ptr) : c->d_sums_own;
-    return LV_OK;
+    return c->upd.set_sums_buffer(c->stream, device_ptr);
 }
 
 int lv_pass_solve(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    if (!c->in_update) { set_error("lv_pass_solve outside lv_update_begin/end"); return LV_ESTATE; }
-    c->passes_issued++;
-    return pass_solve(c, false);
+    return c->upd.split_solve(c->stream);
 }
-
-// mailbox_wait's `enabled` (lv_filter.hpp): not where something else waits on the stream anyway
-static bool spin_ok(const lv_ctx* c) { return c->spin_wait && !c->profiling && !c->phase_clocks && !c->capture; }
 
 int lv_update_end(lv_ctx* c, lv_state* x, double* P, int* passes) {
     LV_CHECK_CTX(c);
-    if (!c->in_update) { set_error("lv_update_end without lv_update_begin"); return LV_ESTATE; }
-    c->in_update = false;
-    // results were stored into the pinned mailbox by kf_begin_kernel / solve_kernel; the device copy of the logs
-    // is only downloaded when the caller asked for them
-    if (c->want_log) {
-        LV_HIP(hipMemcpyAsync(c->h_kf, c->d_kf, offsetof(KfDev, pose), hipMemcpyDeviceToHost, c->stream));
-        LV_HIP(hipStreamSynchronize(c->stream));
-    } else {
-        const bool seen = mailbox_wait(c->h_io, c->update_seq, spin_ok(c), &c->mailbox_resyncs);
-        if (!seen) LV_HIP(hipStreamSynchronize(c->stream));
-    }
-    const KfHostIO* io = c->h_io;
-    if ((unsigned)io->fallback_queries & KF_FAULT_BIT) { c->in_update = false; return report_kf_fault(c, io->fallback_queries); }
-    c->timing.fallback_queries = fallback_count(io->fallback_queries) - c->fallback_base;
-    c->fallback_base = fallback_count(io->fallback_queries);
-    if (x) std::memcpy(x, io->x, sizeof(double) * NX);
-    if (P) std::memcpy(P, io->P_post, sizeof(double) * NS * NS);
-    if (passes) *passes = io->passes;
-    c->h_kf->passes = io->passes;
-    c->timing.last_passes = c->h_kf->passes;
-    if (c->prm.degeneracy_mode && c->prm.print_degeneracy_values) {   // print_degeneracy_values (config/params.yaml:53)
-        double eig[MAX_PASSES * 6];
-        int np = 0;
-        if (lv_get_degeneracy_values(c, eig, MAX_PASSES, &np) == LV_OK)
-            for (int i = 0; i < np; ++i)
-                fprintf(stderr, "degeneracy eigenvalues (pass %d): %.6g %.6g %.6g %.6g %.6g %.6g\n", i, eig[6 * i], eig[6 * i + 1],
-                        eig[6 * i + 2], eig[6 * i + 3], eig[6 * i + 4], eig[6 * i + 5]);
-    }
-    return LV_OK;
+    return c->upd.update_end(c->stream, x, P, passes);
 }
 
 int lv_update(lv_ctx* c, lv_state* x, double* P, int* passes, lv_sums* per_pass, double* trace) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
     if (!x || !P) { set_error("null argument"); return LV_EINVAL; }
-    if (passes) *passes = 0;
-    c->filter.latest = ResidentFilter::Source::ByValue;
-    if (c->map.view.m == 0) {  // Localizator::correct returns without a map (Localizator.cpp:24)
-        // ... but the state the caller propagated is the one the first map is built with (main.cpp:92,102 -> lv_map_add_scan)
-        if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;   // (a resident filter that still lives in kf moves out before kf->x is overwritten)
-        if (int rm = c->filter.materialise(c->stream, c->d_kf)) return rm;
-        LV_HIP(hipStreamSynchronize(c->stream));   // (x_in of an earlier update may still be in flight)
-        std::memcpy(c->h_io->x_in, x, sizeof(double) * NX);
-        LV_HIP(hipMemcpyAsync(c->d_kf->x, c->h_io->x_in, sizeof(double) * NX, hipMemcpyHostToDevice, c->stream));
-        return LV_OK;
-    }
-    const int npass = c->prm.MAX_NUM_ITERS + 1;
-    if (int rq = peer_poisoned(c)) return rq;
-    if (!x || !P) { set_error("lv_update: null argument"); return LV_EINVAL; }   // (before the snapshot below dereferences them)
-    const bool peer = c->ranks.transport == RankExchange::Transport::PeerMapped;   // (a failed exchange must hand the caller's buffers
-    const lv_state x_prior = *x;                                                      // back untouched: lv_update_end writes into them)
-    const std::vector<double> P_prior(P, peer ? P + NS * NS : P);
-    int rc = lv_update_begin(c, x, P);
-    if (rc) return rc;
-    if (c->profiling) LV_HIP(hipEventRecord(c->ev_begin, c->stream));
-    c->last_update_fused = false;
-    c->coll_timed = false;
-    if (c->ranks.gather_only() && !pass_fused_applies(c)) {
-        c->in_update = false;
-        return c->ranks.refuse_unfused();
-    }
-    if (pass_fused_applies(c)) {
-        rc = update_fused(c);
-        if (rc) { c->in_update = false; return rc; }
-    } else {
-        for (int i = 0; i < npass; ++i) {
-            if (c->profiling) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 0], c->stream));
-            c->ev_mid = c->profiling ? c->ev_pass[3 * i + 1] : nullptr;
-            c->pass_index = i;
-            rc = pass_full(c);
-            c->pass_index = -1;
-            c->ev_mid = nullptr;
-            if (rc) { c->in_update = false; return rc; }
-            if (c->profiling) LV_HIP(hipEventRecord(c->ev_pass[3 * i + 2], c->stream));
-        }
-    }
-    if (c->profiling) LV_HIP(hipEventRecord(c->ev_end, c->stream));
-    int np = 0;
-    c->want_log = (per_pass != nullptr) || (trace != nullptr);
-    rc = lv_update_end(c, x, P, &np);
-    c->want_log = false;
-    if (rc) return rc;
-    if (peer) {
-        // lv_update_end has waited for the update's last launch, so every pull of this update has run: a pull that gave up on a
-        // peer (or met a poisoned flag) has set the sticky status word.  The caller gets its prior back, nothing is adopted.
-        LV_HIP(hipStreamSynchronize(c->stream));
-        if (c->ranks.failed()) {
-            *x = x_prior;
-            std::memcpy(P, P_prior.data(), sizeof(double) * NS * NS);
-            return peer_poisoned(c);
-        }
-    }
-    if (passes) *passes = np;
-    if (per_pass)
-        for (int i = 0; i < np && i < MAX_PASSES; ++i) unpack_sums(c->h_kf->sums_log + (size_t)i * SUMS_LEN, &per_pass[i]);
-    if (trace) std::memcpy(trace, c->h_kf->trace, sizeof(double) * 49 * (size_t)(np < MAX_PASSES ? np : MAX_PASSES));
-    if (c->profiling) {
-        float ms = 0.f, r = 0.f, s = 0.f;
-        hipEventElapsedTime(&ms, c->ev_begin, c->ev_end);
-        c->timing.last_update_ms = ms;
-        int cnt = np > 0 ? np : 1;
-        for (int i = 0; i < np && i < npass; ++i) {
-            float a = 0.f, b = 0.f;
-            hipEventElapsedTime(&a, c->ev_pass[3 * i + 0], c->ev_pass[3 * i + 1]);
-            hipEventElapsedTime(&b, c->ev_pass[3 * i + 1], c->ev_pass[3 * i + 2]);
-            r += a;
-            s += b;
-            if (i < 8) {
-                c->timing.pass_match_ms[i] = a;
-                c->timing.pass_solve_ms[i] = b;
-                float cm = 0.f;
-                if (c->coll_timed) hipEventElapsedTime(&cm, c->ev_coll[2 * i], c->ev_coll[2 * i + 1]);
-                c->timing.pass_collective_ms[i] = cm;
-            }
-        }
-        c->timing.last_reduce_ms = r / cnt;
-        c->timing.last_solve_ms = s / cnt;
-    }
-    return LV_OK;
+    return c->upd.update(inputs(c), x, P, passes, per_pass, trace);
 }
 
 // ---- resident filter (row f-3) ---------------------------------------------------------------------
@@ -2025,14 +1407,13 @@ int lv_filter_set(lv_ctx* c, const lv_state* x, const double* P) {
 
 int lv_filter_get(lv_ctx* c, lv_state* x, double* P) {
     LV_CHECK_CTX(c);
-    const int rc = c->filter.get(c->stream, c->d_kf, c->h_io, c->update_seq, spin_ok(c), &c->mailbox_resyncs, x, P);
-    return rc > 0 ? report_kf_fault(c, rc) : rc;
+    return c->upd.filter_get(c->stream, x, P);
 }
 
 int lv_predict(lv_ctx* c, double dt, const double* Q, const double acc[3], const double gyro[3]) {
     LV_CHECK_CTX(c);
     if (!Q || !acc || !gyro) { set_error("null argument"); return LV_EINVAL; }
-    return c->filter.predict(c->stream, c->d_kf, dt, Q, acc, gyro);
+    return c->filter.predict(c->stream, c->upd.d_kf, dt, Q, acc, gyro);
 }
 
 // ---- aiding observations (lv_observe.hip; the argument rules: lv_observe.hpp) --------------------------
@@ -2050,7 +1431,7 @@ int lv_observe_results(lv_ctx* c, lv_observe_result* out, size_t capacity, size_
 
 int lv_observe(lv_ctx* c, const lv_observation* obs, size_t n, lv_observe_result* out) {
     LV_CHECK_CTX(c);
-    if (int r = c->filter.observe(c->stream, c->d_kf, obs, n, c->d_obs)) return r;
+    if (int r = c->filter.observe(c->stream, c->upd.d_kf, obs, n, c->d_obs)) return r;
     c->n_obs = (int)n;
     return out ? lv_observe_results(c, out, n, nullptr) : LV_OK;
 }
@@ -2058,39 +1439,11 @@ int lv_observe(lv_ctx* c, const lv_observation* obs, size_t n, lv_observe_result
 int lv_correct(lv_ctx* c, int* passes) {
     LV_CHECK_CTX(c);
     LV_SETTLE_MAP(c);
-    if (int rs = c->filter.need("lv_correct")) return rs;
-    if (int rp = c->filter.flush(c->stream, c->d_kf)) return rp;
-    c->filter.latest = ResidentFilter::Source::Filter;
-    if (passes) *passes = 0;
-    if (c->map.view.m == 0) return LV_OK;  // Localizator::correct returns without a map (Localizator.cpp:24)
-    if (int rq = peer_poisoned(c)) return rq;   // (a failed exchange of an EARLIER, asynchronous lv_correct surfaces here at the latest)
-    if (c->ranks.gather_only() && !pass_fused_applies(c))   // (before anything is enqueued: the filter stays exactly where it was)
-        return c->ranks.refuse_unfused();
-    c->update_seq = (c->update_seq + 1) & 0x3fffffff;   // (the finishing pass echoes it into the mailbox: lv_filter_get polls for it)
-    const ResidentFilter::Prior prior = c->filter.prior();
-    int rc = begin_device(c, prior.host, prior.host != nullptr, prior);
-    if (rc) return rc;
-    c->in_update = true;
-    const int npass = c->prm.MAX_NUM_ITERS + 1;
-    c->last_update_fused = false;
-    if (pass_fused_applies(c)) {
-        rc = update_fused(c);
-    } else {
-        for (int i = 0; i < npass && !rc; ++i) rc = pass_full(c);
-    }
-    c->in_update = false;
-    if (rc) { c->filter.drop(); return rc; }   // (an enqueue failed part of the way: passes that did run may have moved kf->x)
-    c->filter.correct_done();
-    if (passes) {  // optional: the only synchronisation point
-        LV_HIP(hipStreamSynchronize(c->stream));
-        if (int rq = peer_poisoned(c)) return rq;
-        *passes = c->h_io->passes;   // stored by solve_kernel into the pinned mailbox
-    }
-    return LV_OK;
+    return c->upd.correct(inputs(c), passes);
 }
 
 static int fetch_check(lv_ctx* c) {
-    if (!c->dbg_valid || !c->dbg.knn_idx) { set_error("no captured pass: call lv_iterate (or lv_set_capture(1) before lv_update)"); return LV_ESTATE; }
+    if (!c->upd.dbg_valid || !c->upd.dbg.knn_idx) { set_error("no captured pass: call lv_iterate (or lv_set_capture(1) before lv_update)"); return LV_ESTATE; }
     LV_HIP(hipStreamSynchronize(c->stream));
     return LV_OK;
 }
@@ -2102,7 +1455,7 @@ int lv_fetch_knn(lv_ctx* c, uint32_t* idx, float* d2) {
     if (rc) return rc;
     const size_t n = c->scan.n, K = (size_t)c->prm.NUM_MATCH_POINTS;
     if (idx) {
-        LV_HIP(hipMemcpy(idx, c->dbg.knn_idx, n * K * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        LV_HIP(hipMemcpy(idx, c->upd.dbg.knn_idx, n * K * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (c->map.n_ids != c->map.m) {   // the kernels report point ids; the API's index space is the rank among the living
             const size_t ids = c->map.n_ids;
             std::vector<float4> pts(ids);
@@ -2114,7 +1467,7 @@ int lv_fetch_knn(lv_ctx* c, uint32_t* idx, float* d2) {
                 if (idx[i] != 0xFFFFFFFFu && idx[i] < ids) idx[i] = rank[idx[i]];
         }
     }
-    if (d2) LV_HIP(hipMemcpy(d2, c->dbg.knn_d2, n * K * sizeof(float), hipMemcpyDeviceToHost));
+    if (d2) LV_HIP(hipMemcpy(d2, c->upd.dbg.knn_d2, n * K * sizeof(float), hipMemcpyDeviceToHost));
     return LV_OK;
 }
 
@@ -2123,10 +1476,10 @@ int lv_fetch_matches(lv_ctx* c, uint8_t* valid, float* p_world, float* abcd, flo
     int rc = fetch_check(c);
     if (rc) return rc;
     const size_t n = c->scan.n;
-    if (valid) LV_HIP(hipMemcpy(valid, c->dbg.valid, n, hipMemcpyDeviceToHost));
-    if (p_world) LV_HIP(hipMemcpy(p_world, c->dbg.p_world, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (abcd) LV_HIP(hipMemcpy(abcd, c->dbg.abcd, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
-    if (dist) LV_HIP(hipMemcpy(dist, c->dbg.dist, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (valid) LV_HIP(hipMemcpy(valid, c->upd.dbg.valid, n, hipMemcpyDeviceToHost));
+    if (p_world) LV_HIP(hipMemcpy(p_world, c->upd.dbg.p_world, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (abcd) LV_HIP(hipMemcpy(abcd, c->upd.dbg.abcd, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    if (dist) LV_HIP(hipMemcpy(dist, c->upd.dbg.dist, n * sizeof(float), hipMemcpyDeviceToHost));
     return LV_OK;
 }
 
@@ -2134,12 +1487,12 @@ int lv_fetch_neighbors(lv_ctx* c, float* nbr_xyz, float* d2, float* p_world, int
     LV_CHECK_CTX(c);
     const size_t n = c->scan.n;
     if (n == 0) return LV_OK;
-    if (!c->qrec_valid || !c->d_qrec || c->qstride < n) { set_error("no pass has run on the current scan"); return LV_ESTATE; }
+    if (!c->upd.qrec_valid || !c->upd.d_qrec || c->upd.qstride < n) { set_error("no pass has run on the current scan"); return LV_ESTATE; }
     LV_HIP(hipStreamSynchronize(c->stream));
     const int K = c->prm.NUM_MATCH_POINTS, NSL = qrec_slots(K);
     std::vector<float4> rec((size_t)NSL * n);
     for (int sl = 0; sl < NSL; ++sl)
-        LV_HIP(hipMemcpy(rec.data() + (size_t)sl * n, c->d_qrec + (size_t)sl * c->qstride, n * sizeof(float4), hipMemcpyDeviceToHost));
+        LV_HIP(hipMemcpy(rec.data() + (size_t)sl * n, c->upd.d_qrec + (size_t)sl * c->upd.qstride, n * sizeof(float4), hipMemcpyDeviceToHost));
     const float inf = std::numeric_limits<float>::infinity();
     const auto dword = [&](size_t q, int w) {   // word w of the distance slots: distance of neighbour w, then `found`
         const float4& v = rec[(size_t)(K + 1 + w / 4) * n + q];
@@ -2172,8 +1525,8 @@ int lv_fetch_rows(lv_ctx* c, double* H, double* h) {
     int rc = fetch_check(c);
     if (rc) return rc;
     const size_t n = c->scan.n;
-    if (H) LV_HIP(hipMemcpy(H, c->dbg.rows, n * 12 * sizeof(double), hipMemcpyDeviceToHost));
-    if (h) LV_HIP(hipMemcpy(h, c->dbg.h, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (H) LV_HIP(hipMemcpy(H, c->upd.dbg.rows, n * 12 * sizeof(double), hipMemcpyDeviceToHost));
+    if (h) LV_HIP(hipMemcpy(h, c->upd.dbg.h, n * sizeof(double), hipMemcpyDeviceToHost));
     return LV_OK;
 }
 
@@ -2182,28 +1535,7 @@ int lv_calculate_H(lv_ctx* c, const lv_state* x, const float* p_world, const flo
     LV_CHECK_CTX(c);
     if (!x || (n && (!p_world || !abcd || !dist || !H || !h))) { set_error("null argument"); return LV_EINVAL; }
     if (n == 0) return LV_OK;
-    if (c->in_update) { set_error("lv_calculate_H inside an update"); return LV_ESTATE; }
-    int rc = begin_common(c, x, nullptr, false);  // derives the pass constants from x on the device (begin kernel)
-    if (rc) return rc;
-    float *d_in = nullptr;
-    double* d_out = nullptr;
-    LV_HIP(hipMalloc(&d_in, n * 8 * sizeof(float)));
-    LV_HIP(hipMalloc(&d_out, n * 13 * sizeof(double)));
-    float* d_pw = d_in;
-    float* d_abcd = d_in + 3 * n;
-    float* d_dist = d_in + 7 * n;
-    hipError_t e1 = hipMemcpyAsync(d_pw, p_world, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    hipError_t e2 = hipMemcpyAsync(d_abcd, abcd, n * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    hipError_t e3 = hipMemcpyAsync(d_dist, dist, n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    rc = (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) ? LV_EHIP : LV_OK;
-    if (!rc) rc = launch_rows_from_matches(c->stream, c->d_kf, d_pw, d_abcd, d_dist, (uint32_t)n, c->prm.estimate_extrinsics, d_out, d_out + n * 12);
-    if (!rc && hipMemcpyAsync(H, d_out, n * 12 * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LV_EHIP;
-    if (!rc && hipMemcpyAsync(h, d_out + n * 12, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = LV_EHIP;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = LV_EHIP;
-    hipFree(d_in);
-    hipFree(d_out);
-    if (rc == LV_EHIP) set_error("lv_calculate_H: HIP error");
-    return rc;
+    return c->upd.calculate_H(inputs(c), x, p_world, abcd, dist, n, H, h);
 }
 
 int lv_get_degeneracy_values(lv_ctx* c, double* eig, int capacity_passes, int* n_passes) {
@@ -2211,31 +1543,14 @@ int lv_get_degeneracy_values(lv_ctx* c, double* eig, int capacity_passes, int* n
     if (n_passes) *n_passes = 0;
     if (!eig || capacity_passes < 0) { set_error("null argument"); return LV_EINVAL; }
     if (c->prm.degeneracy_mode == 0) { set_error("degeneracy_mode is 0: no eigenvalues are computed"); return LV_ESTATE; }
-    LV_HIP(hipStreamSynchronize(c->stream));
-    int np = 0;
-    LV_HIP(hipMemcpy(&np, &c->d_kf->passes, sizeof(int), hipMemcpyDeviceToHost));
-    if (np > MAX_PASSES) np = MAX_PASSES;
-    if (np > capacity_passes) np = capacity_passes;
-    if (np > 0 && c->last_update_fused) {
-        // degeneracy_mode 1 is a REPORT (print_degeneracy_values, config/params.yaml:53): nothing in the update depends on it, so
-        // the one-launch-per-pass form does not compute it on the device at all (a cyclic Jacobi is a serial f64 chain of ~75 us
-        // in one lane) — the eigenvalues of a pass' pose block are derived here, on demand, from the sums record that pass'
-        // bookkeeping logged (KfDev::sums_log), by the same fixed 8 sweeps as degeneracy_stage (lv_solve_dev.hpp)
-        std::vector<double> log((size_t)np * SUMS_LEN);
-        LV_HIP(hipMemcpy(log.data(), c->d_kf->sums_log, log.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (int p = 0; p < np; ++p) host_pose_eigenvalues(&log[(size_t)p * SUMS_LEN], eig + 6 * p);
-    } else if (np > 0) {
-        LV_HIP(hipMemcpy(eig, c->d_kf->degen_eig, (size_t)np * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (n_passes) *n_passes = np;
-    return LV_OK;
+    return c->upd.degeneracy_values(c->stream, eig, capacity_passes, n_passes);
 }
 
 int lv_get_level_histogram(lv_ctx* c, int out[8]) {
     LV_CHECK_CTX(c);
     if (!out) { set_error("null argument"); return LV_EINVAL; }
     LV_HIP(hipStreamSynchronize(c->stream));
-    LV_HIP(hipMemcpy(out, c->d_kf->level_hist, 8 * sizeof(int), hipMemcpyDeviceToHost));
+    LV_HIP(hipMemcpy(out, c->upd.d_kf->level_hist, 8 * sizeof(int), hipMemcpyDeviceToHost));
     return LV_OK;
 }
 
@@ -2243,32 +1558,32 @@ int lv_get_solve_clocks(lv_ctx* c, long long* out, int capacity) {
     LV_CHECK_CTX(c);
     if (!out || capacity < MAX_PASSES * 16) { set_error("capacity must be >= %d", MAX_PASSES * 16); return LV_EINVAL; }
     LV_HIP(hipStreamSynchronize(c->stream));
-    LV_HIP(hipMemcpy(out, c->d_kf->solve_clk, sizeof(long long) * MAX_PASSES * 16, hipMemcpyDeviceToHost));
+    LV_HIP(hipMemcpy(out, c->upd.d_kf->solve_clk, sizeof(long long) * MAX_PASSES * 16, hipMemcpyDeviceToHost));
     return LV_OK;
 }
 
 int lv_get_timing(lv_ctx* c, lv_timing* out) {
     if (!c || !out) { set_error("null argument"); return LV_EINVAL; }
-    *out = c->timing;
-    out->mailbox_resyncs = (int)c->mailbox_resyncs;
+    *out = c->upd.timing;
+    out->mailbox_resyncs = (int)c->upd.mailbox_resyncs;
     return LV_OK;
 }
 
 int lv_set_profiling(lv_ctx* c, int enabled) {
     if (!c) { set_error("null context"); return LV_EINVAL; }
-    c->profiling = enabled == 1;
-    c->phase_clocks = enabled == 2;
+    c->upd.profiling = enabled == 1;
+    c->upd.phase_clocks = enabled == 2;
     return LV_OK;
 }
 
 int lv_get_phase_clocks(lv_ctx* c, long long* out, int capacity_blocks, int* n_blocks) {
     LV_CHECK_CTX(c);
-    if (!c->d_clk) { set_error("no phase clocks captured: lv_set_profiling(ctx, 2) first"); return LV_ESTATE; }
+    if (!c->upd.d_clk) { set_error("no phase clocks captured: lv_set_profiling(ctx, 2) first"); return LV_ESTATE; }
     // layout: grid x 8 shader-clock stamps, then grid x 8 records whose first two entries are wall_clock64()
     // (100 MHz, chip-global) at workgroup start / end
-    const int nb = 2 * c->grid < capacity_blocks ? 2 * c->grid : capacity_blocks;
+    const int nb = 2 * c->upd.grid < capacity_blocks ? 2 * c->upd.grid : capacity_blocks;
     LV_HIP(hipStreamSynchronize(c->stream));
-    LV_HIP(hipMemcpy(out, c->d_clk, (size_t)nb * 8 * sizeof(long long), hipMemcpyDeviceToHost));
+    LV_HIP(hipMemcpy(out, c->upd.d_clk, (size_t)nb * 8 * sizeof(long long), hipMemcpyDeviceToHost));
     if (n_blocks) *n_blocks = nb;
     return LV_OK;
 }

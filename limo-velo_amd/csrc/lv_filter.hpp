@@ -1,5 +1,5 @@
 // lv_filter.hpp — the resident filter (row f-3): where x, P live between lv_filter_set, lv_predict, lv_correct and lv_filter_get,
-// and the queue of predictions waiting to launch.  lv_ctx holds one; the entry points hand it the context's stream, kf and mailbox.
+// and the queue of predictions waiting to launch.  lv_ctx holds one; the update driver (lv_update.hpp) and the entry points hand it the context's stream, kf and mailbox.
 // The 100 Hz cycle set -> correct -> get makes no HIP call on the filter's behalf: the prior rides in the correct's first launch,
 // the posterior stays in kf, the get reads the mailbox.  Rules (tests/test_filter_host.py checks them on the host, fake launches):
 // - h is not overwritten while an upload out of it may be in flight (set waits on ev_up);

@@ -11,6 +11,7 @@
 #include "lv_common.hpp"
 #include "lv_buffers.hpp"
 #include "lv_exchange.hpp"
+#include "lv_update.hpp"
 #include "lv_mapinc.hpp"
 
 namespace lv {
@@ -245,70 +246,9 @@ struct BatchStore {
     void release();
 };
 
-// lv_match.hip
-// search_kernel writes one 128-byte record per scan point (8 float4 planes of qstride entries; qrec_slots(K) planes with K neighbours);
-// fit_reduce_kernel turns them into `grid` block partials (and one extra workgroup runs solve_prep)
-// begin != nullptr: the first launch of an update (no begin kernel ran): the state / covariance / pass constants
-// travel as kernel arguments and one extra workgroup installs them in kf and the mailbox io
-int launch_search(hipStream_t stream, int lanes_per_query, const MapView& map, const float4* scan_sorted, uint32_t n, KfDev* kf,
-                  float4* qrec, uint32_t qstride, const uint32_t* tile_order, uint32_t n_tiles, double max_dist_sq, const DebugOut& dbg,
-                  const BeginArg* begin, KfHostIO* io, int num_match = KNN);
-int launch_fit_reduce(hipStream_t stream, const float4* qrec, uint32_t qstride, uint32_t n, KfDev* kf, const MatchParams& prm,
-                      double* partials, int grid, const DebugOut& dbg, int num_match = KNN);   // num_match: NUM_MATCH_POINTS (3..8; 5 = the tuned build)
-int fit_grid_size(uint32_t n, int max_blocks);
-// lv_solve.hip
-int launch_kf_begin(hipStream_t stream, KfDev* kf, KfHostIO* io, const double* x_host, const FilterDev* filt = nullptr, int filt_in_kf = 0);  // io: device pointer of the pinned mailbox;
-// x_host != nullptr: x (NX doubles) followed by P_prop (NS*NS doubles) on the host, passed as kernel arguments
-int launch_reduce_groups(hipStream_t stream, const double* partials, int nblocks, double* groups, int* ngroups_out, KfDev* kf);
-int solve_direct_records();  // most records solve_kernel folds in one round trip
-int launch_reduce_final(hipStream_t stream, const double* groups, int ngroups, double* sums, KfDev* kf);
-struct SolveParams {
-    double R;
-    double R_inv;
-    double limits[NS];
-    int maximum_iter;
-    int estimate_extrinsics;
-    int seq;   // written to the host mailbox by the pass that finishes the update
-    int degeneracy_mode;           // lv_params
-    double degeneracy_threshold;
-};
-int launch_solve(hipStream_t stream, KfDev* kf, KfHostIO* io, const double* recs, int nrec, double* sums_out, const SolveParams& prm);
-// lv_match.hip — one launch per pass (pass_kernel): prologue solve of the previous pass in every workgroup + search +
-// plane fits + one compact partial per workgroup (lv_pass_dev.hpp)
-struct PassLaunch {
-    const MapView* map;
-    const float4* scan;
-    const uint32_t* tile_order;   // 32-point tiles (ScanStore::order_tiles(32)) or nullptr
-    uint32_t n;
-    KfDev* kf;
-    KfHostIO* io;
-    const double* recs_in;        // compact partials of the previous launch (mode 1), nrec of them
-    double* part_out;
-    double* sums_out;
-    float4* qrec;                 // optional (debug): the hand-over records also go to memory, 8 planes of qstride entries
-    long long* clk;               // optional (instrumentation): 16 stamps per search workgroup
-    uint32_t qstride;
-    int nrec;
-    int mode;                     // 0: the update starts here (state in the BeginArg); 1: solve the previous pass first; 2: state already in kf
-    int rounds, launch, nwg;      // nwg searching workgroups; rounds = 0: closing launch (one workgroup, no search);
-                                  // launch = index of the launch in the update
-    const uint32_t* cost_in;      // per searching workgroup: time of its search + fits in the previous launch (nullptr: none) ...
-    uint32_t* cost_out;           // ... and where this launch leaves its own
-    bool multi_overlap = true;    // rounds > 1: a round's plane fits beside the next round's search (pass_kernel<.., MULTI>); false: round 3's barrier form
-    int steps, dedicated;         // search steps per round (1 or 2); dedicated != 0: one more workgroup only keeps the books
-                                  // (otherwise the last searching workgroup does, after its own fits)
-    MatchParams mp;
-    SolveParams sp;
-};
-void pass_grid_size(uint32_t n, int max_wg, int* nsearch, int* steps, int* rounds, int* dedicated);
-constexpr int PK_DEFAULT_MAX_ROUNDS = 16;   // rounds per workgroup up to which lv_update takes pass_kernel by default (1 M points on 256 CUs)
-int pass_clock_words();   // stamp words per workgroup (PassLaunch::clk)
-int launch_pass(hipStream_t stream, const PassLaunch& pl, const BeginArg* begin);
+// (the launches of the update, their parameter structs and the driver that issues them: lv_update.hpp)
 // lv_predict.hip
 int launch_filter_to_kf(hipStream_t stream, const FilterDev* f, KfDev* kf);
-// lv_rows.hip
-int launch_rows_from_matches(hipStream_t stream, const KfDev* kf, const float* p_world, const float* abcd, const float* dist,
-                             uint32_t n, int estimate_extrinsics, double* H, double* h);
 // lv_scan.hip
 struct CloudPoint;
 struct ScanStore {

@@ -3,7 +3,7 @@
 // UndefinedBehaviorSanitizer), never shipped.  It compiles the product's own ResidentFilter against the stand-in hip_runtime.h
 // next to this file, with fake launches: launch_predict applies a toy step to whichever buffer it is told to read (so a wrong
 // source gives a wrong value), launch_kf_to_filter copies, and a fake update writes a posterior derived from its prior into kf
-// and the mailbox with a correct seqcheck.  The drivers below call the class exactly as the entry points of lv_api.hip do; the
+// and the mailbox with a correct seqcheck.  The drivers below call the class exactly as the update driver (lv_update.hpp) and the entry points of lv_api.hip do; the
 // HIP stand-in logs every call, so a scenario asserts what each step enqueued.  Usage: filter_emu <scenario>; exit 0 = pass.
 #include <hip/hip_runtime.h>
 
@@ -86,7 +86,7 @@ struct Logical {   // the reference model: the filter as the caller sees it
     double x[NX], P[NS * NS];
 };
 
-// a context as lv_api.hip holds it: the filter, kf, the mailbox, the stream and the update number
+// a context as lv_api.hip and its update driver hold it: the filter, kf, the mailbox, the stream and the update number
 struct Ctx {
     ResidentFilter f;
     std::unique_ptr<KfDev> kf{new KfDev()};

@@ -3,8 +3,8 @@
 // It lets tests/emu/mapinc_emu.cpp compile the one-thread-per-item kernels of limo-velo_amd/csrc/lv_mapinc.hpp with
 // g++ and run them as plain loops (one "thread" after another, optionally in reverse or shuffled order), so the
 // bookkeeping of the incremental map can be checked against the oracle in the GPU-less container; and it lets
-// tests/emu/rebuild_emu.cpp and tests/emu/filter_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp and lv_filter.hpp against the
-// fake host API at the end of this file.
+// tests/emu/rebuild_emu.cpp, tests/emu/filter_emu.cpp and tests/emu/update_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp,
+// lv_filter.hpp and lv_update.hpp against the fake host API at the end of this file.
 // Nothing here is linked into, loaded by or reachable from the product library.
 #pragma once
 #include <algorithm>
@@ -57,6 +57,7 @@ typedef struct emu_event* hipEvent_t;
 #define hipStreamNonBlocking 0x01
 #define hipEventDisableTiming 0x02
 #define hipHostMallocDefault 0x0
+#define hipHostMallocMapped 0x2
 
 namespace emu_hip {
 struct Call {
@@ -71,6 +72,7 @@ struct State {
     uintptr_t next_handle = 0x1000;
     std::atomic<long> mallocs{0}, frees{0}, events_created{0}, events_destroyed{0}, streams_created{0}, streams_destroyed{0};
     std::atomic<size_t> last_alloc_bytes{0};   // of the last successful hipMalloc / hipHostMalloc
+    float elapsed_ms = 0.f;                    // what hipEventElapsedTime answers (set by a test)
 };
 inline State& state() { static State s; return s; }
 inline hipError_t call(const char* name, hipStream_t s = nullptr, hipEvent_t e = nullptr) {
@@ -110,6 +112,16 @@ inline hipError_t hipEventCreateWithFlags(hipEvent_t* ev, unsigned) {
     if (e == hipSuccess) { *ev = emu_hip::new_handle<hipEvent_t>(); ++emu_hip::state().events_created; }
     return e;
 }
+inline hipError_t hipEventCreate(hipEvent_t* ev) {
+    hipError_t e = emu_hip::call("hipEventCreate");
+    if (e == hipSuccess) { *ev = emu_hip::new_handle<hipEvent_t>(); ++emu_hip::state().events_created; }
+    return e;
+}
+inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) {
+    hipError_t e = emu_hip::call("hipEventElapsedTime", nullptr, b);
+    if (e == hipSuccess) *ms = emu_hip::state().elapsed_ms;
+    return e;
+}
 inline hipError_t hipEventDestroy(hipEvent_t ev) { ++emu_hip::state().events_destroyed; return emu_hip::call("hipEventDestroy", nullptr, ev); }
 inline hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) { return emu_hip::call("hipEventRecord", s, ev); }
 inline hipError_t hipEventSynchronize(hipEvent_t ev) { return emu_hip::call("hipEventSynchronize", nullptr, ev); }
@@ -128,6 +140,16 @@ inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMe
     if (e == hipSuccess && bytes) std::memcpy(dst, src, bytes);
     return e;
 }
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+    hipError_t e = emu_hip::call("hipMemcpy");
+    if (e == hipSuccess && bytes) std::memcpy(dst, src, bytes);
+    return e;
+}
+inline hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t s) {
+    hipError_t e = emu_hip::call("hipMemsetAsync", s);
+    if (e == hipSuccess && bytes) std::memset(dst, v, bytes);
+    return e;
+}
 inline hipError_t hipMemset(void* dst, int v, size_t bytes) {
     hipError_t e = emu_hip::call("hipMemset");
     if (e == hipSuccess && bytes) std::memset(dst, v, bytes);
@@ -142,3 +164,4 @@ inline hipError_t hipHostFree(void* p) {
     if (p) { std::free(p); ++emu_hip::state().frees; }
     return emu_hip::call("hipHostFree");
 }
+inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) { *dev = host; return emu_hip::call("hipHostGetDevicePointer"); }

@@ -2,9 +2,10 @@
 each entry point makes on the filter's behalf.
 
 tests/emu/filter_emu.cpp compiles the product's own ResidentFilter with g++ against the stand-in tests/emu/hip/hip_runtime.h
-(synchronous, logged calls; counted allocations) and fake launches, and drives it as the entry points of lv_api.hip do.  Each
-scenario runs as its own process, once in a plain build and once under AddressSanitizer + UndefinedBehaviorSanitizer.  The GPU
-side of the same paths is tests/test_gpu_filter.py.
+(synchronous, logged calls; counted allocations) and fake launches, and drives it as the update driver (lv_update.hpp; its own
+host test is tests/test_update_host.py) and the entry points of lv_api.hip do.  Each scenario runs as its own process, once in a
+plain build and once under AddressSanitizer + UndefinedBehaviorSanitizer.  The GPU side of the same paths is
+tests/test_gpu_filter.py.
 """
 import os
 import subprocess
