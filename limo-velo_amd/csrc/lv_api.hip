@@ -62,12 +62,12 @@ struct lv_ctx {
     ScanStore scan;
     CloudStore cloud;   // row f-4: device-resident LiDAR buffer
     PinBuf<float4> h_stage;     // pinned upload staging (doubling from 4096 points: ensure_stage)
-    MotionState* h_states_ring = nullptr;   // pinned: the motion states of lv_scan_deskew_window, 8 slots of 64 (a copy out of the
+    PinBuf<MotionState> h_states_ring;      // pinned: the motion states of lv_scan_deskew_window, 8 slots of 64 (a copy out of the
     int states_slot = 0;                    // caller's pageable memory blocks the host; every cycle synchronises at least once, so
                                             // a slot is free again long before its turn comes round)
 
     ResidentFilter filter;   // x, P resident between lv_filter_set / lv_predict / lv_correct / lv_filter_get (lv_filter.hpp)
-    lv_observe_result* d_obs = nullptr;   // lv_observe: the records of the last call (LV_OBSERVE_BATCH), and how many
+    DevBuf<lv_observe_result> d_obs;      // lv_observe: the records of the last call (LV_OBSERVE_BATCH), and how many
     int n_obs = 0;
     RankExchange ranks;   // multi-GPU: how the partials of every pass reach every rank (lv_exchange.hpp)
     UpdateDriver upd{prm, filter, ranks};   // the iterated update: kf, the mailbox, its buffers, routes and profiling (lv_update.hpp)
@@ -167,7 +167,8 @@ int create_in(lv_ctx* c) {
     if (int rk = Knobs<lv_ctx>::read_environment(*c)) return rk;
     if (int ru = c->upd.alloc(prop.multiProcessorCount)) return ru;
     if (int rf = c->filter.alloc()) return rf;
-    LV_HIP(hipMalloc(&c->d_obs, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
+    LV_TRY(c->h_states_ring.need(8 * 64));
+    LV_TRY(c->d_obs.need(LV_OBSERVE_BATCH));
     LV_HIP(hipMemset(c->d_obs, 0, LV_OBSERVE_BATCH * sizeof(lv_observe_result)));
     return LV_OK;
 }
@@ -265,8 +266,8 @@ void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part o
     c->scan.release();
     c->h_stage.release();
     c->filter.release();
-    hipFree(c->d_obs);
-    if (c->h_states_ring) hipHostFree(c->h_states_ring);
+    c->d_obs.release();
+    c->h_states_ring.release();
     c->ranks.release();
     c->upd.release();
     if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
@@ -1157,7 +1158,6 @@ int lv_reserve_stream(lv_ctx* c, size_t max_window_points, size_t max_scan_point
         if (!rc && c->scan.tile_points) rc = c->scan.reserve_tiles((uint32_t)((max_window_points + c->scan.tile_points - 1) / c->scan.tile_points));
         if (rc) return rc;
         LV_HIP(note_alloc(c->scan.notes));
-        if (!c->h_states_ring) LV_HIP(hipHostMalloc((void**)&c->h_states_ring, 8 * 64 * sizeof(MotionState), hipHostMallocDefault));
     }
     if (max_scan_points) {
         rc = c->scan.reserve(max_scan_points);
@@ -1211,7 +1211,6 @@ int lv_scan_deskew_window(lv_ctx* c, double t1, double t2, const lv_motion_state
     rc = c->scan.reserve_raw(n, n_states);
     if (rc) return rc;
     if (n_states <= 64) {
-        if (!c->h_states_ring) LV_HIP(hipHostMalloc((void**)&c->h_states_ring, 8 * 64 * sizeof(MotionState), hipHostMallocDefault));
         MotionState* slot = c->h_states_ring + (size_t)c->states_slot * 64;
         c->states_slot = (c->states_slot + 1) & 7;
         std::memcpy(slot, states, n_states * sizeof(MotionState));

@@ -1,5 +1,7 @@
-// lv_buffers.hpp — the host-side buffers of the map tools (QueryStore, BatchStore, VisStore, PaintStore, PlaceStore, SurfaceStore,
-// ClusterStore, PlaneStore, OccStore, DistStore, PlanStore, FrontierStore, RayStore, ElevStore, RolloutStore, MclStore, TsdfStore, LatticeStore, GraphStore): a device buffer and its pinned twin that know their capacity, a stage for packed
+// lv_buffers.hpp — the host-side buffers of the map, scan and cloud stores (MapStore, ScanStore, CloudStore: lv_stores.hpp), of the
+// context (d_obs, h_states_ring) and of the map tools (QueryStore, BatchStore, VisStore, PaintStore, PlaceStore, SurfaceStore,
+// ClusterStore, PlaneStore, OccStore, DistStore, PlanStore, FrontierStore, RayStore, ElevStore, RolloutStore, MclStore, TsdfStore,
+// LatticeStore, GraphStore): a device buffer and its pinned twin that know their capacity, a stage for packed
 // points, a record of four counters, and the grid size of a one-lane-per-item launch.  Host code only; tests/emu/buffers_emu.cpp
 // compiles it with g++ against tests/emu/hip/hip_runtime.h and tests/test_buffers_host.py holds it to the rules of DESIGN.md
 // "Host-side buffers".
@@ -30,12 +32,13 @@ template <class T> struct BufElem { static constexpr size_t size = sizeof(T); };
 template <> struct BufElem<void> { static constexpr size_t size = 1; };   // (a byte buffer: hipcub scratch, blobs)
 
 // A pointer and the elements it has room for.  Growth frees and allocates anew (the contents are not kept); after a failed
-// allocation the buffer is {nullptr, 0} and the next call allocates again.
+// allocation the buffer is {nullptr, 0} and the next call allocates again.  grow_keep is the one growth that keeps contents.
 template <class T, class Mem>
 struct Buf {
     T* p = nullptr;
     size_t cap = 0;
     operator T*() const { return p; }
+    T* operator->() const { return p; }
     // room for n elements; grows to exactly n
     int need(size_t n) { return n <= cap ? LV_OK : resize(n); }
     // room for n elements; grows by doubling from `floor` (a buffer whose size follows the caller's batch from call to call)
@@ -56,12 +59,44 @@ struct Buf {
         cap = c;
         return LV_OK;
     }
+    // c elements in a new block whose first `keep` are the old block's [from, from + keep): the new block is allocated first, the
+    // copy runs device to device on `stream` and is waited for, then the old block is freed.  whole_device: every stream is
+    // waited for before the copy (another stream may still write the old block).  When the allocation, a wait or the copy fails the
+    // old block and its capacity stand and LV_EHIP is returned.
+    int grow_keep(size_t c, size_t keep, size_t from, hipStream_t stream, bool whole_device) {
+        void* q = nullptr;
+        LV_HIP(Mem::alloc(&q, c * BufElem<T>::size));
+        const int rc = copy_kept(q, keep, from, stream, whole_device);
+        if (rc) {
+            Mem::free(q);
+            return rc;
+        }
+        T* old = p;
+        p = static_cast<T*>(q);
+        cap = c;
+        if (old) LV_HIP(Mem::free(old));
+        return LV_OK;
+    }
+    int copy_kept(void* q, size_t keep, size_t from, hipStream_t stream, bool whole_device) const {
+        if (whole_device) LV_HIP(hipDeviceSynchronize());
+        const char* src = reinterpret_cast<const char*>(p) + from * BufElem<T>::size;
+        if (p && keep) LV_HIP(hipMemcpyAsync(q, src, keep * BufElem<T>::size, hipMemcpyDeviceToDevice, stream));
+        LV_HIP(hipStreamSynchronize(stream));
+        return LV_OK;
+    }
     void release() {
         if (p) Mem::free(p);
         p = nullptr;
         cap = 0;
     }
 };
+template <class... B> inline void release_all(B&... b) { (b.release(), ...); }
+// room for n elements in every one of the buffers, in the order given; the first failure ends it
+template <class... B> inline int need_all(size_t n, B&... b) {
+    int rc = LV_OK;
+    ((rc = rc ? rc : b.need(n)), ...);
+    return rc;
+}
 template <class T> using DevBuf = Buf<T, DeviceMem>;
 template <class T> using PinBuf = Buf<T, PinnedMem>;   // NOTE: the owner synchronises the stream that reads it before need() / release()
 

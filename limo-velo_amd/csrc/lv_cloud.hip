@@ -154,80 +154,11 @@ __global__ void cloud_unpack_kernel(const CloudPoint* __restrict__ pts, uint32_t
 
 }  // namespace
 
-int CloudStore::reserve_msg(size_t n, size_t bytes) {
-    if (bytes > raw_cap) {
-        size_t cap = raw_cap ? raw_cap : (1u << 20);
-        while (cap < bytes) cap *= 2;
-        LV_HIP(hipDeviceSynchronize());   // (a staging buffer may still be in flight)
-        hipFree(d_rawmsg);
-        if (h_rawmsg) hipHostFree(h_rawmsg);
-        if (h_rawmsg2) hipHostFree(h_rawmsg2);
-        d_rawmsg = nullptr; h_rawmsg = h_rawmsg2 = nullptr; raw_cap = 0;
-        LV_HIP(hipMalloc(&d_rawmsg, cap));
-        LV_HIP(hipHostMalloc((void**)&h_rawmsg, cap, hipHostMallocDefault));
-        LV_HIP(hipHostMalloc((void**)&h_rawmsg2, cap, hipHostMallocDefault));
-        for (int b = 0; b < 2; ++b) {
-            if (!ev_stage[b]) LV_HIP(hipEventCreateWithFlags(&ev_stage[b], hipEventDisableTiming));
-            stage_busy[b] = false;
-        }
-        raw_cap = cap;
-    }
-    if (n > msg_cap) {
-        size_t cap = msg_cap ? msg_cap : 65536;
-        while (cap < n) cap *= 2;
-        hipFree(d_decoded); hipFree(d_kept); hipFree(d_keep); hipFree(d_keys); hipFree(d_keys_sorted); hipFree(d_ids);
-        hipFree(d_ids_sorted); hipFree(d_tmp);
-        d_decoded = d_kept = nullptr; d_keep = nullptr; d_keys = d_keys_sorted = nullptr; d_ids = d_ids_sorted = nullptr; d_tmp = nullptr;
-        msg_cap = 0;
-        LV_HIP(hipMalloc(&d_decoded, cap * sizeof(CloudPoint)));
-        LV_HIP(hipMalloc(&d_kept, cap * sizeof(CloudPoint)));
-        LV_HIP(hipMalloc(&d_keep, cap));
-        LV_HIP(hipMalloc(&d_keys, cap * sizeof(uint64_t)));
-        LV_HIP(hipMalloc(&d_keys_sorted, cap * sizeof(uint64_t)));
-        LV_HIP(hipMalloc(&d_ids, cap * sizeof(uint32_t)));
-        LV_HIP(hipMalloc(&d_ids_sorted, cap * sizeof(uint32_t)));
-        size_t a = 0, b = 0;
-        LV_HIP((hipError_t)hipcub::DeviceSelect::Flagged(nullptr, a, d_decoded, d_keep, d_kept, d_count, (int)cap, (hipStream_t)0));
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, b, d_keys, d_keys_sorted, d_ids, d_ids_sorted, (int)cap, 0, 64,
-                                                               (hipStream_t)0));
-        tmp_bytes = a > b ? a : b;
-        LV_HIP(hipMalloc(&d_tmp, tmp_bytes));
-        msg_cap = cap;
-    }
-    return LV_OK;
-}
-
-int CloudStore::reserve_buffer(hipStream_t stream, size_t total) {
-    if (total <= buf_cap) return LV_OK;
-    // Buffer::clear only advances `head`: before the buffer grows, the living range [head, size) moves to the front when it
-    // fits there without overlapping itself (it does as soon as half of what was ever appended has been cleared) — the buffer of
-    // a stream then stays at a few sweeps instead of doubling for ever (and reallocating, 0.3 ms, every time)
-    const size_t live = size - head;
-    if (head >= live && total - head <= buf_cap) {
-        if (live) LV_HIP(hipMemcpyAsync(d_buf, d_buf + head, live * sizeof(CloudPoint), hipMemcpyDeviceToDevice, stream));
-        size = (uint32_t)live;
-        head = 0;
-        return LV_OK;
-    }
-    size_t cap = buf_cap ? buf_cap : (1u << 18);
-    while (cap < total) cap *= 2;
-    CloudPoint* nb = nullptr;
-    LV_HIP(hipMalloc(&nb, cap * sizeof(CloudPoint)));
-    if (size > head) LV_HIP(hipMemcpyAsync(nb, d_buf + head, (size_t)(size - head) * sizeof(CloudPoint), hipMemcpyDeviceToDevice, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    hipFree(d_buf);
-    d_buf = nb;
-    size -= head;
-    head = 0;
-    buf_cap = cap;
-    return LV_OK;
-}
-
-int CloudStore::init() {
-    if (d_count) return LV_OK;
-    LV_HIP(hipMalloc(&d_count, 4 * sizeof(uint32_t)));
-    LV_HIP(hipHostMalloc((void**)&h_count, 4 * sizeof(uint32_t), hipHostMallocDefault));
-    LV_HIP(note_alloc(notes));
+// hipcub's scratch size for CloudStore::reserve_msg (lv_stores.hpp)
+int select_flagged_scratch(size_t n, size_t* bytes) {
+    *bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceSelect::Flagged(nullptr, *bytes, (CloudPoint*)nullptr, (unsigned char*)nullptr, (CloudPoint*)nullptr,
+                                                      (uint32_t*)nullptr, (int)n, (hipStream_t)0));
     return LV_OK;
 }
 
@@ -268,8 +199,8 @@ int CloudStore::ingest(hipStream_t stream, const void* data, size_t n, const Clo
     const int B = 256;
     const uint32_t grid = (uint32_t)((n + B - 1) / B);
     hipLaunchKernelGGL(cloud_decode_kernel, dim3(grid), dim3(B), 0, stream, d_rawmsg, (uint32_t)n, fmt, prm, begin_time, d_decoded, d_keep);
-    size_t tmp = tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceSelect::Flagged(d_tmp, tmp, d_decoded, d_keep, d_kept, d_count, (int)n, stream));
+    size_t tmp = d_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceSelect::Flagged(d_tmp.p, tmp, d_decoded.p, d_keep.p, d_kept.p, d_count.p, (int)n, stream));
     const uint32_t seq = notes.next();
     hipLaunchKernelGGL(cloud_post_count_kernel, dim3(1), dim3(64), 0, stream, d_count, notes.d + 4, seq);
     LV_HIP(hipGetLastError());
@@ -282,8 +213,8 @@ int CloudStore::ingest(hipStream_t stream, const void* data, size_t n, const Clo
     if (rc) return rc;
     const uint32_t g2 = (m + B - 1) / B;
     hipLaunchKernelGGL(cloud_time_keys_kernel, dim3(g2), dim3(B), 0, stream, d_kept, m, d_keys, d_ids);
-    tmp = tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp, d_keys, d_keys_sorted, d_ids, d_ids_sorted, (int)m, 0, 64, stream));
+    tmp = d_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp, d_keys.p, d_keys_sorted.p, d_ids.p, d_ids_sorted.p, (int)m, 0, 64, stream));
     hipLaunchKernelGGL(cloud_gather_kernel, dim3(g2), dim3(B), 0, stream, d_kept, d_ids_sorted, m, d_buf + size);   // Accumulator::push
     LV_HIP(hipGetLastError());
     size += m;
@@ -339,17 +270,6 @@ int CloudStore::unpack(hipStream_t stream, uint32_t lo, uint32_t n, float4* xyz,
     hipLaunchKernelGGL(cloud_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_buf + lo, n, xyz, times);
     LV_HIP(hipGetLastError());
     return LV_OK;
-}
-
-void CloudStore::release() {
-    hipFree(d_rawmsg); hipFree(d_decoded); hipFree(d_kept); hipFree(d_keep); hipFree(d_keys); hipFree(d_keys_sorted);
-    hipFree(d_ids); hipFree(d_ids_sorted); hipFree(d_tmp); hipFree(d_buf); hipFree(d_count);
-    if (h_rawmsg) hipHostFree(h_rawmsg);
-    if (h_rawmsg2) hipHostFree(h_rawmsg2);
-    for (int b = 0; b < 2; ++b) if (ev_stage[b]) hipEventDestroy(ev_stage[b]);
-    if (h_count) hipHostFree(h_count);
-    note_free(notes);
-    *this = CloudStore();
 }
 
 }  // namespace lv

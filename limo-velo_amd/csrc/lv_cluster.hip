@@ -239,7 +239,7 @@ int cluster_remove(MapStore& map, hipStream_t stream, ClusterStore& st, const Cl
     rc = map.reset_batch_counters(stream);
     if (rc) return rc;
     hipLaunchKernelGGL(cluster_classify_kernel, dim3(blocks_of(ids, 256)), dim3(256), 0, stream, map.d_orig, ids, rank, st.d_parent, st.d_size, st.d_lab, q,
-                       flags, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
+                       flags, remove ? 1 : 0, map.d_dead, (uint32_t)map.d_dead.cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {
         LV_HIP(hipStreamSynchronize(stream));

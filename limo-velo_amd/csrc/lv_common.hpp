@@ -21,6 +21,13 @@ void set_error(const char* fmt, ...);
         }                                                                                         \
     } while (0)
 
+// Leaves the function with the code of a failed step (an int expression: LV_OK or an error whose message is set)
+#define LV_TRY(expr)            \
+    do {                        \
+        const int _rc = (expr); \
+        if (_rc) return _rc;    \
+    } while (0)
+
 // Leaves the function with `code` and the message unless cond holds
 #define LV_REQUIRE(cond, code, msg) \
     do {                            \

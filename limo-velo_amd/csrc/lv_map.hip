@@ -472,23 +472,11 @@ __global__ void staged_ok_kernel(const float4* __restrict__ pts, uint32_t k, uin
     flags[i] = (pt_alive(p) && fabsf(p.y) < pos_inf() && fabsf(p.z) < pos_inf()) ? 1u : 0u;
 }
 
-static inline uint32_t next_pow2(uint64_t v) {
-    uint32_t p = 64;
-    while (p < v) p <<= 1;
-    return p;
-}
 static inline int log2u(uint32_t size) {
     int lg = 0;
     while ((1u << lg) < size) ++lg;
     return lg;
 }
-
-#define LV_REALLOC(ptr, type, count)                                       \
-    do {                                                                   \
-        if (ptr) hipFree(ptr);                                             \
-        ptr = nullptr;                                                     \
-        LV_HIP(hipMalloc(&ptr, (size_t)(count) * sizeof(type)));           \
-    } while (0)
 
 // A (re)build's large grids — millions of small workgroups, 2..10 ms per kernel at 10 M points — go out in SLICES when the store
 // is being rebuilt in the background (MapStore::slice_wgs != 0): a workgroup that needs a whole compute unit (pass_kernel: 1024
@@ -519,92 +507,17 @@ static void launch_sliced(uint32_t slice, K kernel, uint32_t grid, uint32_t bloc
     }
 }
 
-int MapStore::reserve(size_t cap) {
-    if (cap <= capacity) return LV_OK;
-    size_t ncap = capacity ? capacity : 4096;
-    while (ncap < cap) ncap *= 2;
-    float4* n_orig = nullptr;
-    LV_HIP(hipMalloc(&n_orig, ncap * sizeof(float4)));
-    LV_HIP(hipDeviceSynchronize());
-    if (d_orig && n_ids) LV_HIP(hipMemcpy(n_orig, d_orig, (size_t)n_ids * sizeof(float4), hipMemcpyDeviceToDevice));
-    if (d_orig) hipFree(d_orig);
-    d_orig = n_orig;
-    LV_REALLOC(d_orig2, float4, ncap);
-    LV_REALLOC(d_sorted, float4, ncap);
-    LV_REALLOC(d_keys, uint64_t, ncap);
-    LV_REALLOC(d_keys_sorted, uint64_t, ncap);
-    LV_REALLOC(d_idx, uint32_t, ncap);
-    LV_REALLOC(d_idx_sorted, uint32_t, ncap);
-    if (d_sort_tmp) hipFree(d_sort_tmp);
-    d_sort_tmp = nullptr;
-    sort_tmp_bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp_bytes, d_keys, d_keys_sorted, d_idx, d_idx_sorted,
-                                                           (int)ncap, 0, 63, (hipStream_t)0));
-    LV_HIP(hipMalloc(&d_sort_tmp, sort_tmp_bytes));
-    LV_REALLOC(d_dead, float4, ncap);
-    dead_cap = ncap;
-    if (d_box_next) {   // chains are by id: keep them
-        uint32_t* nn = nullptr;
-        LV_HIP(hipMalloc(&nn, ncap * sizeof(uint32_t)));
-        if (n_ids) LV_HIP(hipMemcpy(nn, d_box_next, (size_t)n_ids * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-        hipFree(d_box_next);
-        d_box_next = nn;
-        box_next_cap = ncap;
-    }
-    if (d_backpos[0]) {   // positions inside the buckets are by id: keep them
-        for (int l = 0; l < BUCKET_LEVELS; ++l) {
-            uint16_t* nb = nullptr;
-            LV_HIP(hipMalloc(&nb, ncap * 27 * sizeof(uint16_t)));
-            if (n_ids) LV_HIP(hipMemcpy(nb, d_backpos[l], (size_t)n_ids * 27 * sizeof(uint16_t), hipMemcpyDeviceToDevice));
-            hipFree(d_backpos[l]);
-            d_backpos[l] = nb;
-        }
-        uint32_t* nc = nullptr;
-        LV_HIP(hipMalloc(&nc, ncap * sizeof(uint32_t)));
-        if (n_ids) LV_HIP(hipMemcpy(nc, d_cellpos, (size_t)n_ids * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-        hipFree(d_cellpos);
-        d_cellpos = nc;
-        backptr_cap = ncap;
-    }
-    capacity = ncap;
-    refresh_view();
+// hipcub's scratch sizes for the stores' reserve paths (lv_stores.hpp)
+int sort_pairs_scratch_u64(size_t n, int end_bit, size_t* bytes) {
+    *bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
+                                                           (uint32_t*)nullptr, (int)n, 0, end_bit, (hipStream_t)0));
     return LV_OK;
 }
-
-int MapStore::ensure_alive_scratch() {
-    if (alive_cap >= capacity && d_alive) return LV_OK;
-    LV_REALLOC(d_alive, uint32_t, capacity);
-    LV_REALLOC(d_apos, uint32_t, capacity);
-    if (d_ascan_tmp) hipFree(d_ascan_tmp);
-    d_ascan_tmp = nullptr;
-    ascan_tmp_bytes = 0;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, ascan_tmp_bytes, d_alive, d_apos, (int)capacity, (hipStream_t)0));
-    LV_HIP(hipMalloc(&d_ascan_tmp, ascan_tmp_bytes));
-    alive_cap = capacity;
+int exclusive_sum_scratch(size_t n, size_t* bytes) {
+    *bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, (hipStream_t)0));
     return LV_OK;
-}
-
-void MapStore::release() {
-    hipFree(d_orig); hipFree(d_orig2); hipFree(d_sorted); hipFree(d_keys); hipFree(d_keys_sorted); hipFree(d_idx); hipFree(d_idx_sorted);
-    hipFree(d_sort_tmp); hipFree(d_counts);
-    hipFree(d_cell_slots); hipFree(d_flags); hipFree(d_bcount); hipFree(d_bcap); hipFree(d_boff); hipFree(d_scan_tmp);
-    for (int l = 0; l < BUCKET_LEVELS; ++l) { hipFree(d_btable[l]); hipFree(d_baux[l]); hipFree(d_bxyz[l]); hipFree(d_bidx[l]); hipFree(d_backpos[l]); }
-    hipFree(d_cellpos); hipFree(d_biglist); hipFree(d_gtable); hipFree(d_gext); hipFree(d_goff);
-    hipFree(d_broken); hipFree(d_regroup);
-    hipFree(d_caux); hipFree(d_cell4);
-    for (int l = 0; l < N_OCC; ++l) hipFree(d_tables[l]);
-    hipFree(d_cnt);
-    if (h_cnt) hipHostFree(h_cnt);
-    hipFree(d_new); hipFree(d_nkeys); hipFree(d_nkeys_sorted); hipFree(d_nidx); hipFree(d_nidx_sorted); hipFree(d_nalive);
-    hipFree(d_napos); hipFree(d_nsurv); hipFree(d_nsflag); hipFree(d_nspos); hipFree(d_ntmp); hipFree(d_dead); hipFree(d_alive); hipFree(d_apos); hipFree(d_ascan_tmp);
-    hipFree(d_box); hipFree(d_box_next);
-    for (int l = 0; l < BUCKET_LEVELS; ++l) {
-        hipFree(d_gtab[l]); hipFree(d_gbase[l]); hipFree(d_gslot[l]); hipFree(d_gdst[l]); hipFree(d_prank[l]); hipFree(d_pslot[l]);
-        hipFree(d_rank[l]); hipFree(d_reloc[l]); hipFree(d_comp[l]); hipFree(d_cstage[l]); hipFree(d_cnew[l]);
-    }
-    note_free(notes);
-    hipFree(d_gcnt);
-    *this = MapStore();
 }
 
 static std::atomic<uint64_t> g_map_gen{0};
@@ -675,7 +588,7 @@ void MapStore::stats(MapStats* out) const {
     out->living = m;
     out->ids = n_ids;
     out->capacity = capacity;
-    if (h_cnt && built) {
+    if (h_cnt.p && built) {
         for (int l = 0; l <= BUCKET_LEVELS; ++l) {   // bucket levels 0, 1, then the voxel lists (instance 0's second table)
             const MapCounters& hc = h_cnt[l < BUCKET_LEVELS ? l : 0];
             const int t = l < BUCKET_LEVELS ? 0 : CELL_SLOT;
@@ -699,12 +612,12 @@ void MapStore::stats(MapStats* out) const {
     // every device allocation that grows with the map (the per-batch scratch of an insert does not: reserve_batch)
     uint64_t b = (uint64_t)capacity * (16 + 16 + 16 + 8 + 8 + 4 + 4 + 16);                                   // orig, orig2, sorted, keys x 2, idx x 2, dead
     for (int l = 0; l < BUCKET_LEVELS; ++l) b += (uint64_t)pool_cap[l] * 16 + (uint64_t)btable_size[l] * 32;   // 12-byte points + ids; table + aux
-    b += (uint64_t)pool_cap[POOL_CELL] * 16 + (uint64_t)caux_size * 16 + (uint64_t)backptr_cap * (BUCKET_LEVELS * 27 * 2 + 4);   // lists, their aux; back-positions + cellpos
+    b += (uint64_t)pool_cap[POOL_CELL] * 16 + (uint64_t)d_caux.cap * 16 + (uint64_t)d_cellpos.cap * (BUCKET_LEVELS * 27 * 2 + 4);   // lists, their aux; back-positions + cellpos
     for (int l = 0; l < N_OCC; ++l) b += (uint64_t)table_size[l] * 16;
-    b += (uint64_t)cells_cap * 16 + (uint64_t)biglist_cap * 4;                                                // build scratch per bucket voxel
-    b += (uint64_t)gtable_size * 16 + (uint64_t)gscratch_cap * 8;                                             // tile groups: table + build scratch
-    b += (uint64_t)alive_cap * 8;                                                                             // compaction / eviction flags + ranks
-    b += (uint64_t)box_size * 16 + (uint64_t)box_next_cap * 4;
+    b += (uint64_t)d_boff.cap * 16 + (uint64_t)d_biglist.cap * 4;                                                // build scratch per bucket voxel
+    b += (uint64_t)gtable_size * 16 + (uint64_t)d_goff.cap * 8;                                             // tile groups: table + build scratch
+    b += (uint64_t)d_apos.cap * 8;                                                                             // compaction / eviction flags + ranks
+    b += (uint64_t)box_size * 16 + (uint64_t)d_box_next.cap * 4;
     out->bytes = b;
 }
 
@@ -720,7 +633,7 @@ int MapStore::rebuild(hipStream_t stream) {
         const int rc0 = ensure_counters();
         if (rc0) return rc0;
     }
-    std::memset(h_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters));
+    std::memset(h_cnt.p, 0, BUCKET_LEVELS * sizeof(MapCounters));
     m = n_ids;
     if (m == 0) {
         LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipMemcpyHostToDevice, stream));
@@ -729,7 +642,7 @@ int MapStore::rebuild(hipStream_t stream) {
     }
     const int B = 256;
     const uint32_t grid = (m + B - 1) / B;
-    if (!d_flags) LV_HIP(hipMalloc(&d_flags, 8 * sizeof(uint32_t)));
+    LV_TRY(d_flags.need(8));
     const unsigned init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
     LV_HIP(hipMemcpyAsync(d_flags, init, sizeof(init), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(map_bounds_kernel, dim3(grid < 2048u ? grid : 2048u), dim3(B), 0, stream, d_orig, m, d_flags);
@@ -751,11 +664,11 @@ int MapStore::rebuild(hipStream_t stream) {
     const float inv_cell = 1.0f / cell;
     hipLaunchKernelGGL(map_keys_kernel, dim3(grid), dim3(B), 0, stream, d_orig, m, origin[0], origin[1], origin[2], inv_cell, d_keys,
                        d_idx);
-    size_t tmp = sort_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, tmp, d_keys, d_keys_sorted, d_idx, d_idx_sorted, (int)m,
+    size_t tmp = d_sort_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, tmp, d_keys.p, d_keys_sorted.p, d_idx.p, d_idx_sorted.p, (int)m,
                                                            0, 63, stream));
     hipLaunchKernelGGL(map_gather_kernel, dim3(grid), dim3(B), 0, stream, d_orig, d_idx_sorted, m, d_sorted);
-    if (!d_counts) LV_HIP(hipMalloc(&d_counts, 16 * sizeof(uint32_t)));
+    LV_TRY(d_counts.need(16));
     LV_HIP(hipMemsetAsync(d_counts, 0, 16 * sizeof(uint32_t), stream));
     launch_sliced(slice_wgs * 2, map_count_heads_kernel, grid, (uint32_t)B, stream, (const uint64_t*)d_keys_sorted, m, d_counts);
     uint32_t counts[16];
@@ -769,9 +682,8 @@ int MapStore::rebuild(hipStream_t stream) {
         // (re)builds also give memory BACK: a table 8x larger than this map wants — a rolling window that shrank from its
         // initial extent — is re-allocated (hysteresis: growth doubles, so 8x cannot oscillate)
         if (size > table_size[l] || ((uint64_t)size * 8 <= table_size[l] && table_size[l] > (1u << 20))) {
-            if (d_tables[l]) hipFree(d_tables[l]);
-            d_tables[l] = nullptr;
-            LV_HIP(hipMalloc(&d_tables[l], (size_t)size * sizeof(uint4)));
+            table_size[l] = 0;
+            LV_TRY(d_tables[l].resize(size));
             table_size[l] = size;
         }
         size = table_size[l];
@@ -800,13 +712,25 @@ int MapStore::rebuild(hipStream_t stream) {
         }
     }
     for (int l = 0; l < BUCKET_LEVELS; ++l) h_cnt[l].slots_used[0] = n_bcells[l];
-    h_cnt->gslots_used = n_groups;
-    h_cnt->slots_used[CELL_SLOT] = counts[OCC_CELL];
+    h_cnt[0].gslots_used = n_groups;
+    h_cnt[0].slots_used[CELL_SLOT] = counts[OCC_CELL];
     LV_HIP(hipMemcpyAsync(d_cnt, h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipMemcpyHostToDevice, stream));
     LV_HIP(hipStreamSynchronize(stream));
     built = true;
     refresh_view();
     return LV_OK;
+}
+
+// scratch of a level's build: slots, counts, capacities and offsets per voxel, and the scratch of the scan over them
+int MapStore::reserve_cells(size_t n) {
+    if (n <= d_boff.cap && d_scan_tmp.p) return LV_OK;
+    LV_TRY(d_cell_slots.resize(n));
+    LV_TRY(d_bcount.resize(n));
+    LV_TRY(d_bcap.resize(n));
+    LV_TRY(d_boff.resize(n));
+    size_t bytes = 0;
+    LV_TRY(exclusive_sum_scratch(n, &bytes));
+    return d_scan_tmp.resize(bytes);
 }
 
 // one replicated level (0 or 1); level 0 is also laid out by tile groups
@@ -816,34 +740,20 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
     uint32_t size = next_pow2((uint64_t)n_occupied * 16);  // dilation factor <= 8 keeps the load <= 0.5
     const bool give_back = (uint64_t)size * 8 <= btable_size[level] && btable_size[level] > (1u << 20);   // (see the occupancy tables)
     if (size < btable_size[level] && !give_back) size = btable_size[level];
-    if (backptr_cap < capacity) {   // back-positions and list positions are by id
-        for (int l = 0; l < BUCKET_LEVELS; ++l) LV_REALLOC(d_backpos[l], uint16_t, capacity * 27);
-        LV_REALLOC(d_cellpos, uint32_t, capacity);
-        backptr_cap = capacity;
+    if (d_cellpos.cap < capacity) {   // back-positions and list positions are by id
+        for (int l = 0; l < BUCKET_LEVELS; ++l) LV_TRY(d_backpos[l].resize(capacity * 27));
+        LV_TRY(d_cellpos.resize(capacity));
     }
     for (;;) {
-        if (size != btable_size[level] || !d_btable[level]) {
-            LV_REALLOC(d_btable[level], uint4, size);
-            LV_REALLOC(d_baux[level], SlotAux, size);
+        if (size != btable_size[level]) {
+            btable_size[level] = 0;
+            LV_TRY(d_btable[level].resize(size));
+            LV_TRY(d_baux[level].resize(size));
             btable_size[level] = size;
         }
         const size_t need_cells = (size_t)size / 2;
-        if (need_cells > cells_cap) {
-            LV_REALLOC(d_cell_slots, uint32_t, need_cells);
-            LV_REALLOC(d_bcount, uint32_t, need_cells);
-            LV_REALLOC(d_bcap, uint32_t, need_cells);
-            LV_REALLOC(d_boff, uint32_t, need_cells);
-            if (d_scan_tmp) hipFree(d_scan_tmp);
-            d_scan_tmp = nullptr;
-            scan_tmp_bytes = 0;
-            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp_bytes, d_bcap, d_boff, (int)need_cells, (hipStream_t)0));
-            LV_HIP(hipMalloc(&d_scan_tmp, scan_tmp_bytes));
-            cells_cap = need_cells;
-        }
-        if (need_cells > biglist_cap) {
-            LV_REALLOC(d_biglist, uint32_t, need_cells);
-            biglist_cap = need_cells;
-        }
+        LV_TRY(reserve_cells(need_cells));
+        LV_TRY(d_biglist.need(need_cells));
         LV_HIP(hipMemsetAsync(d_btable[level], 0xFF, (size_t)size * sizeof(uint4), stream));
         LV_HIP(hipMemsetAsync(d_baux[level], 0, (size_t)size * sizeof(SlotAux), stream));
         LV_HIP(hipMemsetAsync(d_flags, 0, 4 * sizeof(uint32_t), stream));
@@ -869,8 +779,8 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
         uint32_t n_big = 0;
         if (level != 0) {
             // level 1 belongs to no group: its runs follow each other in the order the buckets registered
-            size_t stmp = scan_tmp_bytes;
-            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, stmp, d_bcap, d_boff, (int)nb, stream));
+            size_t stmp = d_scan_tmp.cap;
+            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, stmp, d_bcap.p, d_boff.p, (int)nb, stream));
             uint32_t last_off = 0, last_cap = 0, hf[4] = {0, 0, 0, 0};
             LV_HIP(hipMemcpyAsync(&last_off, d_boff + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             LV_HIP(hipMemcpyAsync(&last_cap, d_bcap + (nb - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -881,24 +791,19 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
         }
         while (level == 0) {
             if (gsize > gtable_size || ((uint64_t)gsize * 8 <= gtable_size && gtable_size > (1u << 20))) {
-                LV_REALLOC(d_gtable, uint4, gsize);
+                gtable_size = 0;
+                LV_TRY(d_gtable.resize(gsize));
                 gtable_size = gsize;
             }
             gsize = gtable_size;
-            if (gsize > gscratch_cap) {
-                LV_REALLOC(d_gext, uint32_t, gsize);
-                LV_REALLOC(d_goff, uint32_t, gsize);
-                gscratch_cap = gsize;
+            if (gsize > d_goff.cap) {
+                LV_TRY(d_gext.resize(gsize));
+                LV_TRY(d_goff.resize(gsize));
             }
             {   // (the scan's scratch was sized for the bucket voxels; a group table can be larger for tiny maps and after a retry)
                 size_t need = 0;
-                LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_gext, d_goff, (int)gsize, (hipStream_t)0));
-                if (need > scan_tmp_bytes) {
-                    if (d_scan_tmp) hipFree(d_scan_tmp);
-                    d_scan_tmp = nullptr;
-                    LV_HIP(hipMalloc(&d_scan_tmp, need));
-                    scan_tmp_bytes = need;
-                }
+                LV_TRY(exclusive_sum_scratch(gsize, &need));
+                LV_TRY(d_scan_tmp.need(need));
             }
             LV_HIP(hipMemsetAsync(d_gtable, 0xFF, (size_t)gsize * sizeof(uint4), stream));
             LV_HIP(hipMemsetAsync(d_gext, 0, (size_t)gsize * sizeof(uint32_t), stream));
@@ -906,8 +811,8 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
             GridLevelW gt{d_gtable, gsize - 1, (uint32_t)(64 - log2u(gsize))};
             launch_sliced(slice_wgs * 8, group_join_kernel, (nb + 255) / 256, 256u, stream, bt, (const uint32_t*)d_cell_slots, nb, (const uint32_t*)d_bcap, gt,
                           d_gext, d_boff, d_bcount, d_flags);
-            size_t stmp = scan_tmp_bytes;
-            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, stmp, d_gext, d_goff, (int)gsize, stream));
+            size_t stmp = d_scan_tmp.cap;
+            LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, stmp, d_gext.p, d_goff.p, (int)gsize, stream));
             uint32_t last_off = 0, last_ext = 0, hf[4] = {0, 0, 0, 0};
             LV_HIP(hipMemcpyAsync(&last_off, d_goff + (gsize - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             LV_HIP(hipMemcpyAsync(&last_ext, d_gext + (gsize - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -933,13 +838,13 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
         if (want > 0xFFFFFFF0ull) { set_error("bucket pool exceeds 2^32 entries at level %d", level); return LV_ERANGE; }
         if (want > pool_cap[level] || (want * 3 <= pool_cap[level] && pool_cap[level] > (32u << 20))) {   // (grow, or give back: see the occupancy tables)
             pool_cap[level] = 0;
-            LV_REALLOC(d_bxyz[level], float, want * 3 + 4);
-            LV_REALLOC(d_bidx[level], uint32_t, want);
+            LV_TRY(d_bxyz[level].resize(want * 3 + 4));
+            LV_TRY(d_bidx[level].resize(want));
             pool_cap[level] = (size_t)want;
         }
         // the slack behind every run reads as +inf (a candidate at distance +inf, like a deleted entry): the consumers of a tile
         // group stream its region runs AND slack
-        if (total) LV_HIP(hipMemsetD32Async((hipDeviceptr_t)d_bxyz[level], 0x7F800000, (size_t)total * 3, stream));
+        if (total) LV_HIP(hipMemsetD32Async((hipDeviceptr_t)d_bxyz[level].p, 0x7F800000, (size_t)total * 3, stream));
         BuildOut bo{d_bxyz[level], d_bidx[level], d_backpos[level], d_baux[level], {origin[0], origin[1], origin[2]}, 1.0f / cell, level};
         launch_sliced(slice_wgs, bucket_build_kernel, (nb + 3) / 4, 256u, stream, occ, bt, (const uint32_t*)d_cell_slots, nb, (const float4*)d_sorted,
                       (const uint32_t*)d_bcap, (const uint32_t*)d_boff, bo);
@@ -956,26 +861,12 @@ int MapStore::build_buckets(hipStream_t stream, int level, uint32_t n_occupied) 
 int MapStore::build_cells(hipStream_t stream, uint32_t n_occupied) {
     (void)n_occupied;
     const uint32_t size = table_size[OCC_CELL];
-    if (size > caux_size) {
-        LV_REALLOC(d_caux, SlotAux, size);
-        caux_size = size;
-    }
-    if ((size_t)size > cells_cap) {
-        LV_REALLOC(d_cell_slots, uint32_t, size);
-        LV_REALLOC(d_bcount, uint32_t, size);
-        LV_REALLOC(d_bcap, uint32_t, size);
-        LV_REALLOC(d_boff, uint32_t, size);
-        if (d_scan_tmp) hipFree(d_scan_tmp);
-        d_scan_tmp = nullptr;
-        scan_tmp_bytes = 0;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp_bytes, d_bcap, d_boff, (int)size, (hipStream_t)0));
-        LV_HIP(hipMalloc(&d_scan_tmp, scan_tmp_bytes));
-        cells_cap = size;
-    }
+    LV_TRY(d_caux.need(size));
+    LV_TRY(reserve_cells(size));
     const int B = 256;
     hipLaunchKernelGGL(cell_caps_kernel, dim3((size + B - 1) / B), dim3(B), 0, stream, d_tables[OCC_CELL], size, d_bcap);
-    size_t stmp = scan_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp, stmp, d_bcap, d_boff, (int)size, stream));
+    size_t stmp = d_scan_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_scan_tmp.p, stmp, d_bcap.p, d_boff.p, (int)size, stream));
     uint32_t last_off = 0, last_cap = 0;
     LV_HIP(hipMemcpyAsync(&last_off, d_boff + (size - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipMemcpyAsync(&last_cap, d_bcap + (size - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -985,7 +876,7 @@ int MapStore::build_cells(hipStream_t stream, uint32_t n_occupied) {
     if (want > 0xFFFFFFF0ull) { set_error("voxel-list pool exceeds 2^32 entries"); return LV_ERANGE; }
     if (want > pool_cap[POOL_CELL]) {
         pool_cap[POOL_CELL] = 0;
-        LV_REALLOC(d_cell4, float4, want);
+        LV_TRY(d_cell4.resize(want));
         pool_cap[POOL_CELL] = (size_t)want;
     }
     GridLevelW t2{d_tables[OCC_CELL], size - 1, (uint32_t)(64 - log2u(size))};
@@ -997,72 +888,11 @@ int MapStore::build_cells(hipStream_t stream, uint32_t n_occupied) {
 }
 
 // ---- incremental maintenance: host side ---------------------------------------------------------------------
-int MapStore::reserve_batch(size_t k) {
-    if (k <= batch_cap) return LV_OK;
-    size_t ncap = batch_cap ? batch_cap : 4096;
-    while (ncap < k) ncap *= 2;
-    LV_REALLOC(d_new, float4, ncap);
-    LV_REALLOC(d_nkeys, uint64_t, ncap);
-    LV_REALLOC(d_nkeys_sorted, uint64_t, ncap);
-    LV_REALLOC(d_nidx, uint32_t, ncap);
-    LV_REALLOC(d_nidx_sorted, uint32_t, ncap);
-    LV_REALLOC(d_nalive, uint32_t, ncap);
-    LV_REALLOC(d_napos, uint32_t, ncap);
-    LV_REALLOC(d_nsurv, uint32_t, ncap);
-    LV_REALLOC(d_nsflag, uint32_t, ncap);
-    LV_REALLOC(d_nspos, uint32_t, ncap);
-    gtab_size = next_pow2((uint64_t)ncap * 4);
-    for (int l = 0; l < BUCKET_LEVELS; ++l) {   // (per instance)
-        LV_REALLOC(d_rank[l], uint32_t, ncap * 27 * SORTED_LEVELS);
-        LV_REALLOC(d_prank[l], uint32_t, ncap * REPL_LEVELS);
-        LV_REALLOC(d_pslot[l], uint32_t, ncap * REPL_LEVELS);
-        LV_REALLOC(d_gtab[l], uint4, gtab_size);
-        LV_REALLOC(d_gbase[l], uint32_t, (size_t)gtab_size * GROUP_TARGETS);
-        LV_REALLOC(d_gslot[l], uint32_t, (size_t)gtab_size * GROUP_TARGETS);
-        LV_REALLOC(d_gdst[l], uint4, (size_t)gtab_size * GROUP_TARGETS);
-    }
-    if (!d_gcnt) LV_HIP(hipMalloc(&d_gcnt, BUCKET_LEVELS * 4 * LIST_SHARDS * sizeof(uint32_t)));
-    reloc_cap = (uint32_t)(ncap * 27 > 0x0FFFFFF0ull ? 0x0FFFFFF0ull : ncap * 27);
-    for (int l = 0; l < BUCKET_LEVELS; ++l) LV_REALLOC(d_reloc[l], uint4, reloc_cap);
-    // a batch of k points breaks up at most 27 k groups (one per target bucket), in practice a few per cent of k: more than this
-    // raises `overflow` and the map is re-linearised
-    broken_cap = (uint32_t)(ncap * 2 < 16384 ? 16384 : ncap * 2);   // (sharded 64 ways by table slot: room for an uneven spread)
-    LV_REALLOC(d_broken, uint32_t, broken_cap);
-    LV_REALLOC(d_regroup, RegroupPlan, broken_cap);
-    // runs compacted in place: the list (one entry per run) and the staging area (one entry per bucket entry of a listed run; a
-    // run that finds it full moves instead)
-    comp_cap = reloc_cap < (1u << 18) ? reloc_cap : (1u << 18);
-    cstage_cap = (uint32_t)(ncap * 32 < (1u << 20) ? (1u << 20) : ncap * 32);
-    for (int l = 0; l < BUCKET_LEVELS; ++l) {
-        LV_REALLOC(d_comp[l], uint4, comp_cap);
-        LV_REALLOC(d_cstage[l], float4, cstage_cap);
-        LV_REALLOC(d_cnew[l], uint32_t, cstage_cap);
-    }
-    if (d_ntmp) hipFree(d_ntmp);
-    d_ntmp = nullptr;
-    size_t a = 0, b = 0;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, a, d_nkeys, d_nkeys_sorted, d_nidx, d_nidx_sorted, (int)ncap, 0, 63,
-                                                           (hipStream_t)0));
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, b, d_nalive, d_napos, (int)ncap, (hipStream_t)0));
-    ntmp_bytes = a > b ? a : b;
-    LV_HIP(hipMalloc(&d_ntmp, ntmp_bytes));
-    batch_cap = ncap;
-    return LV_OK;
-}
-
 int MapStore::ensure_boxes(hipStream_t stream, float box_length) {
     if (have_boxes) return LV_OK;
-    const uint32_t size = next_pow2((uint64_t)capacity * 4);
-    if (size > box_size) {
-        LV_REALLOC(d_box, uint4, size);
-        box_size = size;
-    }
-    if (box_next_cap < capacity) {
-        LV_REALLOC(d_box_next, uint32_t, capacity);
-        box_next_cap = capacity;
-    }
+    LV_TRY(reserve_boxes());
     LV_HIP(hipMemsetAsync(d_box, 0xFF, (size_t)box_size * sizeof(uint4), stream));
-    LV_HIP(hipMemsetAsync(&d_cnt->box_slots_used, 0, sizeof(uint32_t), stream));
+    LV_HIP(hipMemsetAsync(&d_cnt[0].box_slots_used, 0, sizeof(uint32_t), stream));
     BoxRW Bx{d_box, d_box_next, box_size - 1, (uint32_t)(64 - log2u(box_size)), (uint32_t)((uint64_t)box_size * 6 / 10), box_length};
     // (ALWAYS sliced: the boxes are built by the first down-sampling insert after a (re)build, on the insert's side stream,
     // beside the cycle's whole-CU launches — 4 ms in one piece at 10 M ids, ~0.1 ms per slice of 1024 workgroups)
@@ -1103,8 +933,8 @@ int MapStore::snapshot_into(MapStore& dst, hipStream_t stream) {
     if (n_ids) {
         const uint32_t grid = (n_ids + 255) / 256;
         hipLaunchKernelGGL(inc_alive_flags_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_alive);
-        size_t tmp = ascan_tmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp, tmp, d_alive, d_apos, (int)n_ids, stream));
+        size_t tmp = d_ascan_tmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp.p, tmp, d_alive.p, d_apos.p, (int)n_ids, stream));
         hipLaunchKernelGGL(inc_compact_kernel, dim3(grid), dim3(256), 0, stream, d_orig, d_alive, d_apos, n_ids, dst.d_orig);
         LV_HIP(hipGetLastError());
     }
@@ -1118,16 +948,14 @@ int MapStore::relinearise(hipStream_t stream) {
     if (n_ids) {
         const uint32_t grid = (n_ids + 255) / 256;
         hipLaunchKernelGGL(inc_alive_flags_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_alive);
-        size_t tmp = ascan_tmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp, tmp, d_alive, d_apos, (int)n_ids, stream));
+        size_t tmp = d_ascan_tmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp.p, tmp, d_alive.p, d_apos.p, (int)n_ids, stream));
         hipLaunchKernelGGL(inc_compact_kernel, dim3(grid), dim3(256), 0, stream, d_orig, d_alive, d_apos, n_ids, d_orig2);
         uint32_t last_pos = 0, last_alive = 0;
         LV_HIP(hipMemcpyAsync(&last_pos, d_apos + (n_ids - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         LV_HIP(hipMemcpyAsync(&last_alive, d_alive + (n_ids - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         LV_HIP(hipStreamSynchronize(stream));
-        float4* t = d_orig;
-        d_orig = d_orig2;
-        d_orig2 = t;
+        std::swap(d_orig, d_orig2);
         n_ids = last_pos + last_alive;
     }
     m = n_ids;
@@ -1146,13 +974,13 @@ int MapStore::kill_dead_list(hipStream_t stream, uint32_t n_dead) {
 
 // The counted retirement every removal ends with (evict_box, evict_oldest, vis_classify, surface_outliers, cluster_remove): the
 // caller's kernel has appended the leaving points to the dead list and raised n_dead; their bucket and list entries die here.
-// (dead_cap is the id capacity: the list cannot overflow; were it to, only its stored part is killed, while every counted point
+// (d_dead.cap is the id capacity: the list cannot overflow; were it to, only its stored part is killed, while every counted point
 // has left `orig` all the same.)
 int MapStore::retire_dead_list(hipStream_t stream, uint32_t* n_removed) {
     LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));
     const uint32_t n_dead = h_cnt->n_dead;
-    const int rc = kill_dead_list(stream, n_dead < dead_cap ? n_dead : (uint32_t)dead_cap);
+    const int rc = kill_dead_list(stream, n_dead < d_dead.cap ? n_dead : (uint32_t)d_dead.cap);
     if (rc) return rc;
     LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
     LV_HIP(hipStreamSynchronize(stream));
@@ -1474,15 +1302,6 @@ int MapStore::reset_batch_counters(hipStream_t stream) {
     return LV_OK;
 }
 
-int MapStore::ensure_counters() {
-    if (d_cnt) return LV_OK;
-    LV_HIP(hipMalloc(&d_cnt, BUCKET_LEVELS * sizeof(MapCounters)));
-    LV_HIP(hipHostMalloc((void**)&h_cnt, BUCKET_LEVELS * sizeof(MapCounters), hipHostMallocDefault));
-    std::memset(h_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters));
-    LV_HIP(hipMemset(d_cnt, 0, BUCKET_LEVELS * sizeof(MapCounters)));
-    return LV_OK;
-}
-
 int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float box_length, bool build_if_empty) {
     if (k == 0) return LV_OK;
     int rc = settle(stream);
@@ -1508,13 +1327,13 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
         const BoxRW Bx{d_box, d_box_next, box_size - 1, (uint32_t)(64 - log2u(box_size)), (uint32_t)((uint64_t)box_size * 6 / 10), box_length};
         const uint32_t gk = (k + 255) / 256;
         hipLaunchKernelGGL(inc_box_keys_kernel, dim3(gk), dim3(256), 0, stream, M, d_new, k, box_length, d_nkeys, d_nidx, d_nalive, 1, 0);
-        size_t tmp = ntmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_ntmp, tmp, d_nkeys, d_nkeys_sorted, d_nidx, d_nidx_sorted, (int)k, 0, 63,
+        size_t tmp = d_ntmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_ntmp.p, tmp, d_nkeys.p, d_nkeys_sorted.p, d_nidx.p, d_nidx_sorted.p, (int)k, 0, 63,
                                                                stream));
         hipLaunchKernelGGL(inc_box_rule_kernel, dim3(gk), dim3(256), 0, stream, Bx, d_orig, d_new, d_nkeys_sorted, d_nidx_sorted, k,
-                           d_nalive, d_dead, (uint32_t)dead_cap, d_cnt);
-        tmp = ntmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp, tmp, d_nalive, d_napos, (int)k, stream));
+                           d_nalive, d_dead, (uint32_t)d_dead.cap, d_cnt);
+        tmp = d_ntmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp.p, tmp, d_nalive.p, d_napos.p, (int)k, stream));
         hipLaunchKernelGGL(inc_commit_points_kernel, dim3(gk), dim3(256), 0, stream, M, Bx, 0, d_new, d_nalive, d_napos, k, 0u);
         LV_HIP(hipGetLastError());
         LV_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(MapCounters), hipMemcpyDeviceToHost, stream));
@@ -1534,8 +1353,8 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
         if (rc) return rc;
         const uint32_t grid = (k + 255) / 256;
         hipLaunchKernelGGL(staged_ok_kernel, dim3(grid), dim3(256), 0, stream, d_new, k, d_alive);
-        size_t tmp = ascan_tmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp, tmp, d_alive, d_apos, (int)k, stream));
+        size_t tmp = d_ascan_tmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp.p, tmp, d_alive.p, d_apos.p, (int)k, stream));
         hipLaunchKernelGGL(inc_compact_kernel, dim3(grid), dim3(256), 0, stream, d_new, d_alive, d_apos, k, d_orig);
         uint32_t last_pos = 0, last_ok = 0;
         LV_HIP(hipMemcpyAsync(&last_pos, d_apos + (k - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -1552,7 +1371,7 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     }
     rc = reserve((size_t)n_ids + k);
     if (rc) return rc;
-    if (have_boxes && box_next_cap < capacity) have_boxes = false;
+    if (have_boxes && d_box_next.cap < capacity) have_boxes = false;
     // the batch counters go back to zero in the launch that clears the group tables — unless the boxes are about to be built
     // (the first down-sampling insert): their build may raise `overflow`, so the reset has to come before it
     const bool reset_early = downsample && !have_boxes;
@@ -1616,30 +1435,30 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     const bool fused_front = small_front && k <= (uint32_t)SMALL_BATCH;
     if (fused_front) {
         hipLaunchKernelGGL(inc_small_front_kernel, dim3(1), dim3(1024), 0, stream, M, Bx, have_boxes ? 1 : 0, G, Bo.i[1].M, Bo.i[1].G, d_new, k, box_length,
-                           downsample, d_nalive, d_napos, d_dead, (uint32_t)dead_cap, n_ids);
+                           downsample, d_nalive, d_napos, d_dead, (uint32_t)d_dead.cap, n_ids);
     } else {
     hipLaunchKernelGGL(inc_box_keys_kernel, dim3(gk), dim3(B), 0, stream, M, d_new, k, box_length, d_nkeys, d_nidx, d_nalive, downsample, 1);
     if (downsample) {
         if (k <= (uint32_t)SMALL_BATCH) {
             hipLaunchKernelGGL(inc_sort_small_kernel, dim3(1), dim3(1024), 0, stream, d_nkeys, d_nidx, k, d_nkeys_sorted, d_nidx_sorted);
         } else {
-            size_t tmp = ntmp_bytes;
-            LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_ntmp, tmp, d_nkeys, d_nkeys_sorted, d_nidx, d_nidx_sorted, (int)k, 0,
+            size_t tmp = d_ntmp.cap;
+            LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_ntmp.p, tmp, d_nkeys.p, d_nkeys_sorted.p, d_nidx.p, d_nidx_sorted.p, (int)k, 0,
                                                                    63, stream));
         }
         hipLaunchKernelGGL(inc_box_rule_kernel, dim3(gk), dim3(B), 0, stream, Bx, d_orig, d_new, d_nkeys_sorted, d_nidx_sorted, k,
-                           d_nalive, d_dead, (uint32_t)dead_cap, d_cnt);
+                           d_nalive, d_dead, (uint32_t)d_dead.cap, d_cnt);
     }
     {
-        size_t tmp = ntmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp, tmp, d_nalive, d_napos, (int)k, stream));
+        size_t tmp = d_ntmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp.p, tmp, d_nalive.p, d_napos.p, (int)k, stream));
     }
     hipLaunchKernelGGL(inc_commit_points_kernel, dim3(gk), dim3(B), 0, stream, M, Bx, have_boxes ? 1 : 0, d_new, d_nalive, d_napos, k,
                        n_ids);
     if (listed) {   // the survivor list in sorted-batch order (flags -> scan -> scatter: three small launches)
         hipLaunchKernelGGL(inc_surv_flag_kernel, dim3(gk), dim3(B), 0, stream, d_nidx_sorted, d_nalive, k, d_nsflag);
-        size_t tmp = ntmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp, tmp, d_nsflag, d_nspos, (int)k, stream));
+        size_t tmp = d_ntmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ntmp.p, tmp, d_nsflag.p, d_nspos.p, (int)k, stream));
         hipLaunchKernelGGL(inc_surv_list_kernel, dim3(gk), dim3(B), 0, stream, d_nidx_sorted, d_nsflag, d_nspos, k, d_nsurv);
     }
     // voxel groups of the survivors, for both instances
@@ -1672,7 +1491,7 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     const uint32_t g_cmp = k <= (uint32_t)SMALL_BATCH ? 64u : 1024u;   // in-place compactions: how many is only known on the device (grid-stride)
     const uint32_t g_kill = counted_kill ? (k <= (uint32_t)SMALL_BATCH ? 256u : 2048u) : 0u;   // the occupants that lost: how many is only known on the device
     if (merged_back) {   // (see inc_kill_register_kernel: every launch serves both instances)
-        hipLaunchKernelGGL(inc_kill_register_kernel, dim3(2u * (g_kill + g_grp)), dim3(B), 0, stream, Bo, d_nalive, k, d_dead, (uint32_t)dead_cap, g_kill, g_grp);
+        hipLaunchKernelGGL(inc_kill_register_kernel, dim3(2u * (g_kill + g_grp)), dim3(B), 0, stream, Bo, d_nalive, k, d_dead, (uint32_t)d_dead.cap, g_kill, g_grp);
         hipLaunchKernelGGL(inc_reserve_both_kernel, dim3(2u * g_grp), dim3(B), 0, stream, Bo, d_nalive, k, rel_cap, g_grp);
         // runs that only their deleted entries made too long are compacted where they lie: staged here, written back below
         hipLaunchKernelGGL(inc_compact_both_kernel<false>, dim3(2u * g_cmp), dim3(B), 0, stream, Bo, g_cmp);
@@ -1688,7 +1507,7 @@ int MapStore::add_staged(hipStream_t stream, uint32_t k, int downsample, float b
     for (int in = 0; in < BUCKET_LEVELS; ++in) {
     const MapRW& Mi = Bo.i[in].M;
     const GroupRW& Gi = Bo.i[in].G;
-    if (counted_kill) hipLaunchKernelGGL(inc_kill_counted_kernel, dim3(g_kill), dim3(B), 0, stream, Mi, d_dead, (uint32_t)dead_cap);
+    if (counted_kill) hipLaunchKernelGGL(inc_kill_counted_kernel, dim3(g_kill), dim3(B), 0, stream, Mi, d_dead, (uint32_t)d_dead.cap);
     hipLaunchKernelGGL(inc_register_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k);
     hipLaunchKernelGGL(inc_reserve_kernel, dim3(g_grp), dim3(B), 0, stream, Mi, Gi, d_nalive, k, Bo.i[in].reloc, rel_cap, Bo.i[in].gcnt);
     hipLaunchKernelGGL(inc_compact_gather_kernel, dim3(g_cmp), dim3(B), 0, stream, Mi);
@@ -1736,7 +1555,7 @@ int MapStore::settle(hipStream_t stream) {
     for (int l = 0; l < BUCKET_LEVELS; ++l)
         pool_low = pool_low || (uint64_t)v[4 + l] * 4 < (uint64_t)(pool_cap[l] > pool_base[l] ? pool_cap[l] - pool_base[l] : 0);
     uint32_t n_dead = pending_n_dead;
-    if (pending_counted_kill) n_dead = v[1] < dead_cap ? v[1] : (uint32_t)dead_cap;
+    if (pending_counted_kill) n_dead = v[1] < d_dead.cap ? v[1] : (uint32_t)d_dead.cap;
     n_ids += v[0];
     m += v[0];
     last_new = v[0];
@@ -1774,7 +1593,7 @@ int MapStore::evict_box(hipStream_t stream, const float lo[3], const float hi[3]
         return finish_removal(stream, h_cnt->n_dead, n_evicted);   // (the sweep wrote the tombstones itself)
     }
     hipLaunchKernelGGL(inc_evict_box_kernel, dim3((n_ids + 255) / 256), dim3(256), 0, stream, d_orig, n_ids, lo[0], lo[1], lo[2], hi[0], hi[1],
-                       hi[2], keep_inside, d_dead, (uint32_t)dead_cap, d_cnt);
+                       hi[2], keep_inside, d_dead, (uint32_t)d_dead.cap, d_cnt);
     return retire_dead_list(stream, n_evicted);
 }
 
@@ -1789,10 +1608,10 @@ int MapStore::evict_oldest(hipStream_t stream, uint32_t n_oldest, uint32_t* n_ev
     if (rc) return rc;
     const uint32_t grid = (n_ids + 255) / 256;
     hipLaunchKernelGGL(inc_alive_flags_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_alive);
-    size_t tmp = ascan_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp, tmp, d_alive, d_apos, (int)n_ids, stream));
+    size_t tmp = d_ascan_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_ascan_tmp.p, tmp, d_alive.p, d_apos.p, (int)n_ids, stream));
     hipLaunchKernelGGL(inc_evict_oldest_kernel, dim3(grid), dim3(256), 0, stream, d_orig, n_ids, d_apos, n_oldest, d_dead,
-                       (uint32_t)dead_cap, d_cnt);
+                       (uint32_t)d_dead.cap, d_cnt);
     return retire_dead_list(stream, n_evicted);
 }
 

@@ -122,6 +122,8 @@ __device__ __forceinline__ float pos_inf() { return __uint_as_float(0x7F800000u)
 
 // The kernels below are compiled by ONE translation unit (lv_map.hip, or the host emulation in tests/emu): it
 // defines LV_MAPINC_KERNELS before including this header; everybody else only sees the types above.
+constexpr int GROUP_TARGETS = 28;   // 27 neighbour buckets + the list of the level-2 voxel the group's voxel lies in
+
 #ifdef LV_MAPINC_KERNELS
 
 // XCD-aware work order.  Consecutive workgroup indices are dealt round-robin to the eight XCDs, each with its own L2; the work
@@ -583,7 +585,6 @@ __global__ void inc_surv_list_kernel(const uint32_t* __restrict__ idx_sorted, co
                                      uint32_t k, uint32_t* __restrict__ surv) {
     inc_surv_list_item(idx_sorted, flag, fpos, k, surv, blockIdx.x * blockDim.x + threadIdx.x);
 }
-constexpr int GROUP_TARGETS = 28;   // 27 neighbour buckets + the list of the level-2 voxel the group's voxel lies in
 // (No global work lists or group counters: an atomic whose result is needed costs ~10 ns when every thread of a
 // launch hits the same address — 400 000 list appends were 4 ms of a 6 ms insert.  The group that reserves the
 // FIRST share of a target's tail (offset 0) owns that target for the rest of the batch: it makes room and commits.)

@@ -619,42 +619,6 @@ __global__ __launch_bounds__(SW_THREADS) void window_tail_kernel(const float4* _
 #undef WT_STAMP
 }
 
-int ScanStore::reserve_raw(size_t cap, size_t n_states) {
-    if (cap > raw_cap) {
-        size_t ncap = raw_cap ? raw_cap : 4096;
-        while (ncap < cap) ncap *= 2;
-        hipFree(d_in); hipFree(d_times); hipFree(d_desk); hipFree(d_vkeys); hipFree(d_vkeys_sorted); hipFree(d_vidx);
-        hipFree(d_vidx_sorted); hipFree(d_heads); hipFree(d_hpos); hipFree(d_vsort_tmp); hipFree(d_vscan_tmp);
-        d_in = d_desk = nullptr; d_times = nullptr; d_vkeys = d_vkeys_sorted = nullptr;
-        d_vidx = d_vidx_sorted = d_heads = d_hpos = nullptr; d_vsort_tmp = d_vscan_tmp = nullptr;
-        LV_HIP(hipMalloc(&d_in, ncap * sizeof(float4)));
-        LV_HIP(hipMalloc(&d_times, ncap * sizeof(double)));
-        LV_HIP(hipMalloc(&d_desk, ncap * sizeof(float4)));
-        LV_HIP(hipMalloc(&d_vkeys, ncap * sizeof(uint64_t)));
-        LV_HIP(hipMalloc(&d_vkeys_sorted, ncap * sizeof(uint64_t)));
-        LV_HIP(hipMalloc(&d_vidx, ncap * sizeof(uint32_t)));
-        LV_HIP(hipMalloc(&d_vidx_sorted, ncap * sizeof(uint32_t)));
-        LV_HIP(hipMalloc(&d_heads, ncap * sizeof(uint32_t)));
-        LV_HIP(hipMalloc(&d_hpos, ncap * sizeof(uint32_t)));
-        vsort_tmp_bytes = 0;
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, vsort_tmp_bytes, d_vkeys, d_vkeys_sorted, d_vidx, d_vidx_sorted,
-                                                               (int)ncap, 0, 63, (hipStream_t)0));
-        LV_HIP(hipMalloc(&d_vsort_tmp, vsort_tmp_bytes));
-        vscan_tmp_bytes = 0;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, vscan_tmp_bytes, d_heads, d_hpos, (int)ncap, (hipStream_t)0));
-        LV_HIP(hipMalloc(&d_vscan_tmp, vscan_tmp_bytes));
-        raw_cap = ncap;
-    }
-    if (n_states > states_cap) {
-        hipFree(d_states);
-        d_states = nullptr;
-        LV_HIP(hipMalloc(&d_states, n_states * sizeof(MotionState)));
-        states_cap = n_states;
-    }
-    if (!d_bounds) LV_HIP(hipMalloc(&d_bounds, 8 * sizeof(unsigned)));
-    return LV_OK;
-}
-
 // d_in / d_times / d_states hold the uploaded raw scan; leaves the de-skewed (and, if leaf > 0, voxel-grid
 // down-sampled) points in d_raw[0 .. n) in output order and Morton-sorts them into d_sorted
 int ScanStore::deskew_downsample(hipStream_t stream, uint32_t n_in, uint32_t n_states, const MotionState& xt2, float leaf,
@@ -719,14 +683,14 @@ int ScanStore::window_large(hipStream_t stream, const CloudPoint* cloud, uint32_
     if (rc) return rc;
     n_tiles = 0;
     LV_HIP(note_alloc(notes));
-    if (!d_tail_clk && getenv("LV_TAIL_CLK")) { LV_HIP(hipMalloc(&d_tail_clk, 8 * sizeof(long long))); LV_HIP(hipMemset(d_tail_clk, 0, 8 * sizeof(long long))); }
+    if (!d_tail_clk && getenv("LV_TAIL_CLK")) { LV_TRY(d_tail_clk.need(8)); LV_HIP(hipMemset(d_tail_clk, 0, 8 * sizeof(long long))); }
     const uint32_t seq = notes.next();
     const int B = 256;
     const uint32_t grid = (n_in + B - 1) / B;
     hipLaunchKernelGGL(deskew_keys_kernel, dim3(grid), dim3(B), 0, stream, cloud, n_in, d_states, n_states, xt2, 1.0f / leaf, d_desk, d_vkeys, d_vidx,
                        d_bounds);
-    size_t tmp = vsort_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_vsort_tmp, tmp, d_vkeys, d_vkeys_sorted, d_vidx, d_vidx_sorted, (int)n_in, 0, 63,
+    size_t tmp = d_vsort_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_vsort_tmp.p, tmp, d_vkeys.p, d_vkeys_sorted.p, d_vidx.p, d_vidx_sorted.p, (int)n_in, 0, 63,
                                                            stream));
     hipLaunchKernelGGL(window_tail_kernel, dim3(1), dim3(SW_THREADS), 0, stream, d_desk, d_vkeys_sorted, d_vidx_sorted, n_in, 1.0f / sort_cell,
                        tile_points, d_raw, d_sorted, d_tile_order, d_bounds, notes.d, seq, d_tail_clk);
@@ -763,12 +727,12 @@ int ScanStore::voxel_and_sort(hipStream_t stream, uint32_t n_in, float leaf, flo
     uint32_t n_out = n_in;
     if (leaf > 0.f) {
         hipLaunchKernelGGL(vg_keys_kernel, dim3(grid), dim3(B), 0, stream, d_desk, n_in, d_bounds, 1.0f / leaf, d_vkeys, d_vidx);
-        size_t tmp = vsort_tmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_vsort_tmp, tmp, d_vkeys, d_vkeys_sorted, d_vidx, d_vidx_sorted, (int)n_in,
+        size_t tmp = d_vsort_tmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_vsort_tmp.p, tmp, d_vkeys.p, d_vkeys_sorted.p, d_vidx.p, d_vidx_sorted.p, (int)n_in,
                                                                0, 63, stream));
         hipLaunchKernelGGL(vg_heads_kernel, dim3(grid), dim3(B), 0, stream, d_vkeys_sorted, n_in, d_heads);
-        size_t stmp = vscan_tmp_bytes;
-        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_vscan_tmp, stmp, d_heads, d_hpos, (int)n_in, stream));
+        size_t stmp = d_vscan_tmp.cap;
+        LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(d_vscan_tmp.p, stmp, d_heads.p, d_hpos.p, (int)n_in, stream));
         hipLaunchKernelGGL(vg_centroid_kernel, dim3(grid), dim3(B), 0, stream, d_desk, d_vkeys_sorted, d_vidx_sorted, d_heads, d_hpos,
                            n_in, d_raw, d_bounds + 6);
     }
@@ -785,35 +749,12 @@ int ScanStore::voxel_and_sort(hipStream_t stream, uint32_t n_in, float leaf, flo
     return sort(stream, bmin, sort_cell);   // Morton order for the match kernel, exactly as lv_scan_set does
 }
 
-int ScanStore::reserve(size_t cap) {
-    if (cap <= capacity) return LV_OK;
-    size_t ncap = capacity ? capacity : 4096;
-    while (ncap < cap) ncap *= 2;
-    hipFree(d_raw); hipFree(d_sorted); hipFree(d_keys); hipFree(d_keys_sorted); hipFree(d_idx); hipFree(d_idx_sorted);
-    hipFree(d_sort_tmp);
-    d_raw = d_sorted = nullptr; d_keys = d_keys_sorted = d_idx = d_idx_sorted = nullptr; d_sort_tmp = nullptr;
-    capacity = 0;
-    LV_HIP(hipMalloc(&d_raw, ncap * sizeof(float4)));
-    LV_HIP(hipMalloc(&d_sorted, ncap * sizeof(float4)));
-    LV_HIP(hipMalloc(&d_keys, ncap * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&d_keys_sorted, ncap * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&d_idx, ncap * sizeof(uint32_t)));
-    LV_HIP(hipMalloc(&d_idx_sorted, ncap * sizeof(uint32_t)));
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp_bytes, d_keys, d_keys_sorted, d_idx, d_idx_sorted,
-                                                           (int)ncap, 0, 30, (hipStream_t)0));
-    LV_HIP(hipMalloc(&d_sort_tmp, sort_tmp_bytes));
-    capacity = ncap;
+// hipcub's scratch size for ScanStore::reserve (lv_stores.hpp)
+int sort_pairs_scratch_u32(size_t n, int end_bit, size_t* bytes) {
+    *bytes = 0;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                                           (uint32_t*)nullptr, (int)n, 0, end_bit, (hipStream_t)0));
     return LV_OK;
-}
-
-void ScanStore::release() {
-    hipFree(d_raw); hipFree(d_sorted); hipFree(d_keys); hipFree(d_keys_sorted); hipFree(d_idx); hipFree(d_idx_sorted);
-    hipFree(d_sort_tmp);
-    hipFree(d_in); hipFree(d_times); hipFree(d_desk); hipFree(d_vkeys); hipFree(d_vkeys_sorted); hipFree(d_vidx);
-    hipFree(d_vidx_sorted); hipFree(d_heads); hipFree(d_hpos); hipFree(d_vsort_tmp); hipFree(d_vscan_tmp); hipFree(d_states);
-    hipFree(d_bounds); hipFree(d_tile_order); hipFree(d_tail_clk);
-    note_free(notes);
-    *this = ScanStore();
 }
 
 // Small scans (the 0.01 s windows of a stream: a few hundred points after the voxel grid): keys, sort, gather, tile ranges
@@ -889,24 +830,12 @@ int ScanStore::sort(hipStream_t stream, const float bbox_min[3], float cell) {
     const uint32_t grid = (n + B - 1) / B;
     hipLaunchKernelGGL(scan_keys_kernel, dim3(grid), dim3(B), 0, stream, d_raw, n, bbox_min[0], bbox_min[1], bbox_min[2],
                        1.0f / cell, d_keys, d_idx);
-    size_t tmp = sort_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, tmp, d_keys, d_keys_sorted, d_idx, d_idx_sorted, (int)n, 0,
+    size_t tmp = d_sort_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, tmp, d_keys.p, d_keys_sorted.p, d_idx.p, d_idx_sorted.p, (int)n, 0,
                                                            30, stream));
     hipLaunchKernelGGL(scan_gather_kernel, dim3(grid), dim3(B), 0, stream, d_raw, d_idx_sorted, n, d_sorted);
     LV_HIP(hipGetLastError());
     return order_tiles(stream, tile_points);
-}
-
-int ScanStore::reserve_tiles(uint32_t nt) {
-    if (nt <= tile_cap) return LV_OK;
-    hipFree(d_tile_order);
-    d_tile_order = nullptr;
-    tile_cap = 0;
-    uint32_t cap = 1024;
-    while (cap < nt) cap *= 2;
-    LV_HIP(hipMalloc(&d_tile_order, cap * sizeof(uint32_t)));
-    tile_cap = cap;
-    return LV_OK;
 }
 
 // Dispatch order of the search kernel's point tiles: tiles whose points lie farthest from the sensor first.
@@ -936,8 +865,8 @@ int ScanStore::order_tiles(hipStream_t stream, uint32_t tile_points) {
     if (rc) return rc;
     // d_keys / d_idx / d_keys_sorted are free again once the points are gathered (nt <= n <= capacity)
     hipLaunchKernelGGL(tile_range_keys_kernel, dim3((nt + 255) / 256), dim3(256), 0, stream, d_sorted, n, tile_points, nt, d_keys, d_idx);
-    size_t tmp = sort_tmp_bytes;
-    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp, tmp, d_keys, d_keys_sorted, d_idx, d_tile_order, (int)nt, 0, 32,
+    size_t tmp = d_sort_tmp.cap;
+    LV_HIP((hipError_t)hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, tmp, d_keys.p, d_keys_sorted.p, d_idx.p, d_tile_order.p, (int)nt, 0, 32,
                                                            stream));
     n_tiles = nt;
     return LV_OK;

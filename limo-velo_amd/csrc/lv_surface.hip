@@ -269,7 +269,7 @@ int surface_outliers(MapStore& map, hipStream_t stream, SurfaceStore& st, SurfRu
     rc = map.reset_batch_counters(stream);
     if (rc) return rc;
     hipLaunchKernelGGL(surf_classify_kernel, dim3(blocks_of(map.n_ids, 256)), dim3(256), 0, stream, map.d_orig, map.n_ids, st.d_val, q.job, q.threshold,
-                       rank, want_flags ? st.d_flags.p : nullptr, remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
+                       rank, want_flags ? st.d_flags.p : nullptr, remove ? 1 : 0, map.d_dead, (uint32_t)map.d_dead.cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {
         LV_HIP(hipStreamSynchronize(stream));

@@ -183,7 +183,7 @@ int vis_classify(MapStore& map, hipStream_t stream, const void* d_blob, const Vi
     const float* pose = static_cast<const float*>(d_blob);
     const float* img = reinterpret_cast<const float*>(static_cast<const char*>(d_blob) + vis_pose_bytes(q.n_views));
     hipLaunchKernelGGL(vis_classify_kernel, dim3(blocks_of(map.n_ids)), dim3(256), 0, stream, map.d_orig, map.n_ids, pose, img, q, rank, hits,
-                       remove ? 1 : 0, map.d_dead, (uint32_t)map.dead_cap, map.d_cnt);
+                       remove ? 1 : 0, map.d_dead, (uint32_t)map.d_dead.cap, map.d_cnt);
     LV_HIP(hipGetLastError());
     if (!remove) {
         LV_HIP(hipStreamSynchronize(stream));

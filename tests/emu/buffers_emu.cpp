@@ -107,6 +107,54 @@ static int failure() {
     return 0;
 }
 
+// grow_keep: the one growth that keeps contents
+static int keep() {
+    hipStream_t s1 = nullptr;
+    if (hipStreamCreateWithFlags(&s1, hipStreamNonBlocking) != hipSuccess) return 2;
+    DevBuf<int> b{};
+    size_t mark = st().log.size();
+    int rc = b.grow_keep(8, 0, 0, s1, false);   // from empty: nothing to copy, nothing to free
+    print_log("empty", mark, s1);
+    printf("from_empty %d %zu %d\n", rc, b.cap, b.p != nullptr);
+    for (int i = 0; i < 8; ++i) b[i] = 100 + i;
+    mark = st().log.size();
+    rc = b.grow_keep(16, 5, 2, s1, false);      // elements [2, 7) to the front, on the stream
+    print_log("stream", mark, s1);
+    printf("kept %d %zu %zu", rc, b.cap, (size_t)st().last_alloc_bytes);
+    for (int i = 0; i < 5; ++i) printf(" %d", b[i]);
+    printf("\n");
+    mark = st().log.size();
+    rc = b.grow_keep(32, 5, 0, nullptr, true);  // the whole device waited for before the copy
+    print_log("device", mark, s1);
+    printf("kept_device %d %zu %d %d\n", rc, b.cap, b[0], b[4]);
+    const int* old = b.p;
+    mark = st().log.size();
+    rc = b.grow_keep(64, 0, 0, s1, false);      // keep == 0: a new block, no copy, the wait stays
+    print_log("none", mark, s1);
+    printf("kept_none %d %zu %d\n", rc, b.cap, b.p != old);
+    for (int i = 0; i < 4; ++i) b[i] = 7 * i;
+    // a failure at each of its calls but the last leaves the old block usable and frees the new one
+    const char* calls[3] = {"hipMalloc", "hipMemcpyAsync", "hipStreamSynchronize"};
+    for (const char* c : calls) {
+        const long m0 = (long)st().mallocs, f0 = (long)st().frees;
+        old = b.p;
+        st().fail = [c](const char* name) { return std::string(name) == c; };
+        rc = b.grow_keep(128, 4, 0, s1, false);
+        st().fail = nullptr;
+        printf("failed %s %d %d %zu %d %ld\n", c, rc == LV_EHIP, b.p == old, b.cap, b[3], ((long)st().mallocs - m0) - ((long)st().frees - f0));
+    }
+    rc = b.grow_keep(128, 4, 0, s1, false);
+    printf("after %d %zu %d\n", rc, b.cap, b[3]);
+    DevBuf<void> v{};
+    rc = v.need(16);
+    std::memcpy(v.p, "0123456789abcdef", 16);
+    rc = rc ? rc : v.grow_keep(32, 6, 10, s1, false);   // (bytes)
+    printf("bytes %d %zu %.6s\n", rc, v.cap, (const char*)v.p);
+    release_all(b, v);
+    printf("released %ld %ld\n", (long)st().mallocs, (long)st().frees);
+    return 0;
+}
+
 static int stage() {
     hipStream_t s1 = nullptr;
     if (hipStreamCreateWithFlags(&s1, hipStreamNonBlocking) != hipSuccess) return 2;
@@ -192,6 +240,7 @@ int main(int argc, char** argv) {
     if (which == "exact") return exact();
     if (which == "doubling") return doubling();
     if (which == "failure") return failure();
+    if (which == "keep") return keep();
     if (which == "stage") return stage();
     if (which == "counters") return counters();
     return 2;

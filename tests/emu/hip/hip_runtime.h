@@ -4,7 +4,7 @@
 // g++ and run them as plain loops (one "thread" after another, optionally in reverse or shuffled order), so the
 // bookkeeping of the incremental map can be checked against the oracle in the GPU-less container; and it lets
 // tests/emu/rebuild_emu.cpp, tests/emu/filter_emu.cpp and tests/emu/update_emu.cpp compile limo-velo_amd/csrc/lv_rebuild.hpp,
-// lv_filter.hpp and lv_update.hpp against the fake host API at the end of this file.
+// lv_filter.hpp and lv_update.hpp, and tests/emu/stores_emu.cpp lv_stores.hpp, against the fake host API at the end of this file.
 // Nothing here is linked into, loaded by or reachable from the product library.
 #pragma once
 #include <algorithm>
@@ -37,6 +37,8 @@ static inline unsigned int __float_as_uint(float f) { unsigned int u; std::memcp
 static inline float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
 static inline int __clzll(long long v) { return v ? __builtin_clzll((unsigned long long)v) : 64; }
 
+#define __HIP_MEMORY_SCOPE_SYSTEM 5
+template <typename T, typename V> static inline void __hip_atomic_store(T* p, V v, int, int) { *p = (T)v; }   // (lv_note.hpp's note_post)
 template <typename T> static inline T atomicAdd(T* p, T v) { T o = *p; *p = (T)(o + v); return o; }
 template <typename T> static inline T atomicExch(T* p, T v) { T o = *p; *p = v; return o; }
 template <typename T> static inline T atomicCAS(T* p, T cmp, T v) { T o = *p; if (o == cmp) *p = v; return o; }

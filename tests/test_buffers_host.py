@@ -69,6 +69,26 @@ def test_failure_and_release(emu):
     assert m == fr == 4
 
 
+def test_growth_that_keeps_contents(emu):
+    f = emu("keep")
+    assert f["empty"][0] == ["hipMalloc", "hipStreamSynchronize@1"]  # growth from empty: no copy, no free
+    assert _ints(f["from_empty"][0]) == [LV_OK, 8, 1]
+    # allocate, copy on the stream, wait, and only then free the old block
+    assert f["stream"][0] == ["hipMalloc", "hipMemcpyAsync@1", "hipStreamSynchronize@1", "hipFree"]
+    assert _ints(f["kept"][0]) == [LV_OK, 16, 16 * 4, 102, 103, 104, 105, 106]   # elements [2, 7) of the old block lead the new one
+    assert f["device"][0] == ["hipMalloc", "hipDeviceSynchronize", "hipMemcpyAsync", "hipStreamSynchronize", "hipFree"]
+    assert _ints(f["kept_device"][0]) == [LV_OK, 32, 102, 106]
+    assert f["none"][0] == ["hipMalloc", "hipStreamSynchronize@1", "hipFree"]    # keep == 0: a new block and the wait, no copy
+    assert _ints(f["kept_none"][0]) == [LV_OK, 64, 1]
+    # the allocation, the copy or the wait failing: LV_EHIP, the old block and capacity untouched and readable, the new block freed
+    assert [v[0] for v in f["failed"]] == ["hipMalloc", "hipMemcpyAsync", "hipStreamSynchronize"]
+    assert all(_ints(v[1:]) == [1, 1, 64, 21, 0] for v in f["failed"])
+    assert _ints(f["after"][0]) == [LV_OK, 128, 21]                  # ... and the same call again succeeds
+    assert f["bytes"][0] == [str(LV_OK), "32", "abcdef"]             # the byte form counts bytes
+    m, fr = _ints(f["released"][0])
+    assert m == fr == 9
+
+
 def test_point_stage(emu):
     f = emu("stage")
     assert _ints(f["empty"][0]) == [LV_OK, 0, 1, 1]                  # 0 points: nothing allocated, nothing uploaded
