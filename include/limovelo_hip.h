@@ -1692,6 +1692,127 @@ int lv_graph_get_info(lv_ctx* ctx, lv_graph_info* info);
 /* Forgets the graph (the buffers stay for the next one). */
 int lv_graph_clear(lv_ctx* ctx);
 
+/* ---- NDT registration --------------------------------------------------------------------------------
+ * Cloud-to-cloud registration by the normal-distributions transform: a TARGET cloud becomes a voxel grid of Gaussians built
+ * once, and a SOURCE cloud is aligned to it from K initial guesses at a time (what PCL's NormalDistributionsTransform::align,
+ * ndt_omp and fast_gicp's NDTCuda do for one guess).  Independent of the filter, the scan and the volumes; the target may be
+ * built from the living points of the device map.  The rule is the __host__ __device__ code of limo-velo_amd/csrc/lv_ndt.hpp;
+ * tests/ndt_ref.py restates it in numpy.  The moments are integer sums, so the target is the same bit for bit whatever the order
+ * of its points; the alignment is f64 with every sum in one order and repeats its own bits from call to call.
+ *
+ *   grid      origin[3], resolution (finite, > 0), nx, ny, nz each 1..1024 with nx * ny * nz <= 2^22; voxel (i, j, k) has index
+ *             (k * ny + j) * nx + i.  min_points 2..2^20, reg finite in 0..1.
+ *   point     per axis q_a = floorf(((p_a - origin_a) / resolution) * 256) in f32, the occupancy grid's quantisation.  A point
+ *             with a non-finite or out-of-range q (|q| >= 2^24), or whose voxel c_a = q_a >> 8 lies outside the grid, is IGNORED.
+ *             Otherwise it is USED in voxel c with the local coordinate r_a = q_a & 255.
+ *   moments   per voxel n (uint32), S1[3] = sum r_a (int64), S2[6] = sum r_a r_b over the upper triangle in the order
+ *             00 01 02 11 12 22 (int64).  Integer atomics: the sums commute.  The points given to a target (build plus adds, USED
+ *             or not) number at most 2^31 - 1, so nothing overflows.
+ *   Gaussian  of a voxel with n >= min_points (a USED voxel), in f64, u = (double)resolution / 256:
+ *               m_a   = ((double)S1_a + 0.5 n) / n                                       (the centre of a sub-unit)
+ *               mu_a  = ((double)origin_a + (double)resolution * c_a) + u * m_a
+ *               C_ab  = (u^2 * ((double)S2_ab - ((double)S1_a * (double)S1_b) / n)) / (n - 1)
+ *               Sigma = C + ((reg * ((C_00 + C_11) + C_22)) / 3 + u^2 / 12) I
+ *             u^2 / 12 is the variance of the quantisation: Sigma is positive definite even for coincident points.  The term in
+ *             reg bounds the condition number by 3 / reg + 1 without an eigenvector basis; this differs knowingly from PCL, which
+ *             clamps the small eigenvalues to a fraction of the largest.  Omega = Sigma^-1 by a 3 x 3 Cholesky, column by
+ *             column.  A voxel that is not USED stores zeros in MEAN, COV and ICOV.
+ *   term      for source point p and pose (t, q), R = R(q): x = R p + t in f64, each row ((R_k0 p_0 + R_k1 p_1) + R_k2 p_2) + t_k.
+ *             The voxel of x is that of x rounded once to f32, by the rule of `point`.  search = 1 takes that voxel; search = 7
+ *             takes it and its six face neighbours in the order 0, +x, -x, +y, -y, +z, -z (ndt_omp's DIRECT1 / DIRECT7).  A voxel
+ *             outside the grid or not USED contributes nothing.  For each remaining voxel, in that order:
+ *               e = x - mu,  Oe = Omega e,  s = e^T Oe,  w = exp((-0.5 d2) s)
+ *               M <- M + w Omega,  b <- b + w Oe,  sw <- sw + w          (M, b, sw start from 0 for every point)
+ *             A point with at least one such voxel counts in n_in and adds, with A = -R [p]x and J = [ I , A ] (3 x 6):
+ *               S <- S + sw,  g <- g + J^T b,  H <- H + J^T M J   (the 21 entries of the upper triangle)
+ *   sums      S, g, H per hypothesis: a workgroup of 256 lanes takes LV_NDT_CHUNK consecutive source points, lane l the points
+ *             l, l + 256, ... of the chunk in ascending order; the wavefronts fold by an xor-butterfly, the four of them add in
+ *             order, and the workgroups' partials are added in chunk order.  No float atomics; nothing depends on arrival order.
+ *   loop      each hypothesis on its own, Levenberg-Marquardt as lv_graph_optimise words it: (H + lambda diag H) d = -g by the
+ *             6 x 6 Cholesky of the pose graph's block inverse (a pivot that is not positive freezes that component), trial pose
+ *             t + dt, q * exp(dth / 2) renormalised.  A step is ACCEPTED when S_new >= S_old - 64 eps |S_old| (eps = 2^-52) and
+ *             d is finite; then lambda <- max(lambda / 3, lambda_min) and the trial's S, g, H, n_in become the current ones (one
+ *             evaluation per iteration); otherwise the pose stays and lambda <- min(4 lambda, lambda_max).
+ *   status    LV_NDT_NO_OVERLAP when n_in = 0 at the guess: the guess is returned bit for bit, score 0.  LV_NDT_CONVERGED when
+ *             an accepted step has max-norm <= step_tol; LV_NDT_MAX_ITERATIONS after max_iterations iterations (accepted +
+ *             rejected; 0 only scores the guesses).
+ *   best      best[0] is the hypothesis with the greatest score, the smaller index winning a tie, among those that are not
+ *             NO_OVERLAP; best[1] its n_in.  -1, -1 with none.
+ *   limits    n < 2^31 points per build or add; K <= 4096 guesses, n_src <= 2^20, K * n_src <= 2^30; d2 finite and > 0,
+ *             search 1 or 7, max_iterations 0..1000, step_tol finite and >= 0, 0 < lambda_min <= lambda_init <= lambda_max < inf;
+ *             a guess must be finite with a quaternion whose norm is within 1e-6 of 1.
+ * Parameters and NULL or short arguments are judged before the context (LV_EINVAL, nothing written, "null context" last).
+ * lv_ndt_add, lv_ndt_fetch and lv_ndt_align give LV_ESTATE before a build (and after lv_ndt_clear); lv_ndt_info reports built = 0
+ * instead.  Nothing is allocated before the first build.  The target is a snapshot of its source; a refused call leaves it in
+ * place bit for bit.  No call changes a bit of the map, the filter, the scan or any other store.  The calls run on the context's
+ * stream and return when their outputs are written; lv_destroy releases the store. */
+#define LV_NDT_CONVERGED 0
+#define LV_NDT_MAX_ITERATIONS 1
+#define LV_NDT_NO_OVERLAP 2
+#define LV_NDT_CHUNK 512          /* source points per workgroup of the evaluation */
+#define LV_NDT_MAX_DIM 1024
+#define LV_NDT_MAX_VOXELS (1u << 22)
+#define LV_NDT_MAX_GUESSES 4096
+#define LV_NDT_MAX_SOURCE (1u << 20)
+#define LV_NDT_COUNT 0   /* uint32 */
+#define LV_NDT_S1    1   /* int64 x 3 */
+#define LV_NDT_S2    2   /* int64 x 6 */
+#define LV_NDT_MEAN  3   /* double x 3 */
+#define LV_NDT_COV   4   /* double x 6: Sigma, upper triangle */
+#define LV_NDT_ICOV  5   /* double x 6: Omega, upper triangle */
+typedef struct lv_ndt_params {   /* 40 bytes */
+    float   origin[3];
+    float   resolution;          /* 1.0 */
+    int32_t nx, ny, nz;          /* 128, 128, 16 over origin -64, -64, -8 */
+    int32_t min_points;          /* 5 */
+    double  reg;                 /* 0.01 */
+} lv_ndt_params;
+typedef struct lv_ndt_align_params {   /* 48 bytes */
+    int32_t search;              /* 7 */
+    int32_t max_iterations;      /* 100 */
+    double  d2;                  /* 0.43312300470355464:Magnusson's value for 1 m voxels and an outlier ratio of 0.55 */
+    double  step_tol;            /* 1e-6 */
+    double  lambda_init;         /* 1e-4 */
+    double  lambda_min;          /* 1e-10 */
+    double  lambda_max;          /* 1e8 */
+} lv_ndt_align_params;
+typedef struct lv_ndt_result {   /* 264 bytes */
+    lv_graph_pose pose;
+    double   score;              /* S at the pose */
+    double   info[21];           /* the upper triangle of H at the pose, laid out as lv_graph_edge.info */
+    double   last_step;          /* max-norm of the last accepted step (0 when none was) */
+    double   lambda;             /* after the last iteration */
+    uint32_t n_in;               /* source points with at least one voxel at the pose */
+    int32_t  status;             /* LV_NDT_CONVERGED, LV_NDT_MAX_ITERATIONS or LV_NDT_NO_OVERLAP */
+    uint32_t accepted, rejected;
+} lv_ndt_result;
+typedef struct lv_ndt_target_info {   /* 80 bytes */
+    int32_t  built;
+    int32_t  from_map;           /* the last build or add read the device map */
+    uint64_t n_used, n_ignored;  /* points of the build and of every add since */
+    uint64_t used_voxels;        /* n >= min_points */
+    uint64_t sparse_voxels;      /* 0 < n < min_points */
+    lv_ndt_params params;
+} lv_ndt_target_info;
+void lv_default_ndt_params(lv_ndt_params* p);
+void lv_default_ndt_align_params(lv_ndt_align_params* p);
+/* Replaces the target by the Gaussians of n points (x, y, z as f32 at the start of every `stride` bytes, stride >= 12); pts = NULL
+ * takes the living points of the device map, as lv_elev_build reads them (stride and n are then not used).  stats (may be NULL):
+ * points used, points ignored, used voxels, occupied voxels below min_points. */
+int lv_ndt_build(lv_ctx* ctx, const lv_ndt_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]);
+/* Accumulates further points into the moments of the target and recomputes its Gaussians: build(a) then add(b) is build(a u b)
+ * bit for bit.  stats: the points of this call, the voxels of the whole target. */
+int lv_ndt_add(lv_ctx* ctx, const void* pts, size_t stride, size_t n, uint64_t stats[4]);
+/* A layer, by voxel: capacity counts voxels (nx * ny * nz needed). */
+int lv_ndt_fetch(lv_ctx* ctx, int layer, void* out, size_t capacity);
+/* Aligns n_src source points from K guesses.  params NULL: the defaults.  results: K records (may be NULL when K = 0); best: 2
+ * values.  K = 0 succeeds and writes best only. */
+int lv_ndt_align(lv_ctx* ctx, const lv_ndt_align_params* params, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses,
+                 size_t K, lv_ndt_result* results, int32_t best[2]);
+int lv_ndt_info(lv_ctx* ctx, lv_ndt_target_info* out);
+/* Forgets the target and frees its memory. */
+int lv_ndt_clear(lv_ctx* ctx);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 typedef struct lv_timing {
     float last_update_ms;      /* device time of the last lv_update (HIP events on the ctx stream) */

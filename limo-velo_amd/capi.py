@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "lv_default_observation", "lv_observe", "lv_observe_results",
     "lv_default_graph_params", "lv_graph_set", "lv_graph_optimise", "lv_graph_fetch", "lv_graph_chi2", "lv_graph_warp_points",
     "lv_graph_get_info", "lv_graph_clear",
+    "lv_default_ndt_params", "lv_default_ndt_align_params", "lv_ndt_build", "lv_ndt_add", "lv_ndt_fetch", "lv_ndt_align", "lv_ndt_info",
+    "lv_ndt_clear",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -236,6 +238,48 @@ GRAPH_ARGTYPES = {
     "lv_graph_warp_points": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_float)],
     "lv_graph_get_info": [C.c_void_p, C.POINTER(GraphInfo)],
     "lv_graph_clear": [C.c_void_p],
+}
+
+
+class NdtParams(C.Structure):  # lv_ndt_params (40 bytes)
+    _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("min_points", C.c_int32), ("reg", C.c_double)]
+
+
+class NdtAlignParams(C.Structure):  # lv_ndt_align_params (48 bytes)
+    _fields_ = [("search", C.c_int32), ("max_iterations", C.c_int32), ("d2", C.c_double), ("step_tol", C.c_double),
+                ("lambda_init", C.c_double), ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
+class NdtResult(C.Structure):  # lv_ndt_result (264 bytes)
+    _fields_ = [("pose", GraphPose), ("score", C.c_double), ("info", C.c_double * 21), ("last_step", C.c_double), ("lambda_", C.c_double),
+                ("n_in", C.c_uint32), ("status", C.c_int32), ("accepted", C.c_uint32), ("rejected", C.c_uint32)]
+
+
+class NdtTargetInfo(C.Structure):  # lv_ndt_target_info (80 bytes)
+    _fields_ = [("built", C.c_int32), ("from_map", C.c_int32), ("n_used", C.c_uint64), ("n_ignored", C.c_uint64), ("used_voxels", C.c_uint64),
+                ("sparse_voxels", C.c_uint64), ("params", NdtParams)]
+
+
+NDT_CONVERGED, NDT_MAX_ITERATIONS, NDT_NO_OVERLAP = 0, 1, 2
+NDT_CHUNK = 512   # LV_NDT_CHUNK: source points per workgroup of the evaluation
+NDT_COUNT, NDT_S1, NDT_S2, NDT_MEAN, NDT_COV, NDT_ICOV = range(6)
+# name, element type and elements per voxel of lv_ndt_fetch's layers
+NDT_LAYERS = (("count", np.uint32, 1), ("S1", np.int64, 3), ("S2", np.int64, 6), ("mean", np.float64, 3), ("cov", np.float64, 6),
+              ("icov", np.float64, 6))
+# the same bytes as NdtResult
+NDT_RESULT_DTYPE = np.dtype([("t", "f8", 3), ("q", "f8", 4), ("score", "f8"), ("info", "f8", 21), ("last_step", "f8"), ("lambda", "f8"),
+                             ("n_in", "u4"), ("status", "i4"), ("accepted", "u4"), ("rejected", "u4")])
+
+# ctypes signatures of the NDT registration (include/limovelo_hip.h "NDT registration"; tests/test_ndt_abi.py)
+NDT_ARGTYPES = {
+    "lv_ndt_build": [C.c_void_p, C.POINTER(NdtParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)],
+    "lv_ndt_add": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)],
+    "lv_ndt_fetch": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t],
+    "lv_ndt_align": [C.c_void_p, C.POINTER(NdtAlignParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(GraphPose), C.c_size_t,
+                     C.POINTER(NdtResult), C.POINTER(C.c_int32)],
+    "lv_ndt_info": [C.c_void_p, C.POINTER(NdtTargetInfo)],
+    "lv_ndt_clear": [C.c_void_p],
 }
 
 
@@ -782,11 +826,15 @@ def load_library() -> C.CDLL:
         lib.lv_default_observation.argtypes = [C.POINTER(Observation), C.c_int]
         lib.lv_default_graph_params.restype = None
         lib.lv_default_graph_params.argtypes = [C.POINTER(GraphParams)]
+        lib.lv_default_ndt_params.restype = None
+        lib.lv_default_ndt_params.argtypes = [C.POINTER(NdtParams)]
+        lib.lv_default_ndt_align_params.restype = None
+        lib.lv_default_ndt_align_params.argtypes = [C.POINTER(NdtAlignParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
-                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES}.items():
+                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -870,6 +918,25 @@ def default_place_params(**kw) -> PlaceParams:
 def default_graph_params(**kw) -> GraphParams:
     p = GraphParams()
     load_library().lv_default_graph_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_ndt_params(**kw) -> NdtParams:
+    p = NdtParams()
+    load_library().lv_default_ndt_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "origin":
+            p.origin[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def default_ndt_align_params(**kw) -> NdtAlignParams:
+    p = NdtAlignParams()
+    load_library().lv_default_ndt_align_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1895,6 +1962,63 @@ class Context:
 
     def graph_clear(self):
         self._check(self.lib.lv_graph_clear(self.h))
+
+    # --- NDT registration (include/limovelo_hip.h "NDT registration"; limo_velo_amd.ndt has the helpers)
+    def _ndt_points(self, points):
+        if points is None:
+            return None, 0, 0
+        a, stride, n = _points(np.asarray(points, np.float32).reshape(-1, 3))
+        if n == 0:   # (no points, but still "caller points": a pointer that is not NULL)
+            a, stride = np.zeros((1, 3), np.float32), 12
+        return a, stride, n
+
+    def ndt_build(self, params: NdtParams | None = None, points=None) -> np.ndarray:
+        """lv_ndt_build from points [n, 3] (None: the living points of the device map); stats [4] uint64: points used, points
+        ignored, used voxels, occupied voxels below min_points."""
+        p = params if params is not None else default_ndt_params()
+        stats = np.zeros(4, np.uint64)
+        a, stride, n = self._ndt_points(points)
+        self._check(self.lib.lv_ndt_build(self.h, C.byref(p), None if a is None else C.c_void_p(a.ctypes.data), C.c_size_t(stride), C.c_size_t(n),
+                                          stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def ndt_add(self, points=None) -> np.ndarray:
+        """lv_ndt_add: further points into the target; stats as ndt_build (the points of this call, the voxels of the whole)."""
+        stats = np.zeros(4, np.uint64)
+        a, stride, n = self._ndt_points(points)
+        self._check(self.lib.lv_ndt_add(self.h, None if a is None else C.c_void_p(a.ctypes.data), C.c_size_t(stride), C.c_size_t(n),
+                                        stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def ndt_info(self) -> NdtTargetInfo:
+        out = NdtTargetInfo()
+        self._check(self.lib.lv_ndt_info(self.h, C.byref(out)))
+        return out
+
+    def ndt_fetch(self, layer: int) -> np.ndarray:
+        """[nz, ny, nx] (COUNT) or [nz, ny, nx, 3 or 6] of the layer's type (NDT_LAYERS): lv_ndt_fetch."""
+        i = self.ndt_info()
+        _, dtype, width = NDT_LAYERS[layer] if 0 <= int(layer) < len(NDT_LAYERS) else ("", np.int64, 1)
+        shape = (i.params.nz, i.params.ny, i.params.nx) if i.built else (1, 1, 1)
+        out = np.zeros(shape + ((width,) if width > 1 else ()), dtype)
+        self._check(self.lib.lv_ndt_fetch(self.h, int(layer), out.ctypes.data_as(C.c_void_p), C.c_size_t(int(np.prod(shape)))))
+        return out
+
+    def ndt_align(self, source, guesses, params: NdtAlignParams | None = None, **kw):
+        """lv_ndt_align of source [n, 3] from guesses [K, 7] f64 (t, q = x y z w): (results, best) with results an array of
+        NDT_RESULT_DTYPE [K] and best = (index, n_in) or (-1, -1)."""
+        p = params if params is not None else default_ndt_align_params(**kw)
+        a, stride, n = _points(np.asarray(source, np.float32).reshape(-1, 3))
+        g = np.ascontiguousarray(np.asarray(guesses, np.float64).reshape(-1, 7))
+        res = np.zeros(len(g), NDT_RESULT_DTYPE)
+        best = np.zeros(2, np.int32)
+        self._check(self.lib.lv_ndt_align(self.h, C.byref(p), a.ctypes.data_as(C.c_void_p) if n else None, C.c_size_t(stride), C.c_size_t(n),
+                                          g.ctypes.data_as(C.POINTER(GraphPose)) if len(g) else None, C.c_size_t(len(g)),
+                                          res.ctypes.data_as(C.POINTER(NdtResult)) if len(g) else None, best.ctypes.data_as(C.POINTER(C.c_int32))))
+        return res, (int(best[0]), int(best[1]))
+
+    def ndt_clear(self):
+        self._check(self.lib.lv_ndt_clear(self.h))
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

@@ -16,6 +16,7 @@
 #include "lv_paint.hpp"
 #include "lv_place.hpp"
 #include "lv_graph.hpp"
+#include "lv_ndt.hpp"
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
 
@@ -54,6 +55,7 @@ struct lv_ctx {
     PlaneStore planes;      // lv_map_planes: its own buffers (lv_planes.hip); nothing allocated before the first call
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     GraphStore graph;   // lv_graph_*: the pose graph and the solver's vectors (lv_graph.hip); nothing allocated before lv_graph_set
+    NdtStore ndt;       // lv_ndt_*: the target's Gaussians and the buffers of an alignment (lv_ndt.hip); nothing allocated before the first build
     VolumeTools vol;    // lv_occ_*, lv_tsdf_*, lv_volume_*: the two volumes, what is built from them and what keeps those honest (lv_volumes.hpp)
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
@@ -260,6 +262,7 @@ void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part o
     c->planes.release();
     c->place.release();
     c->graph.release();
+    c->ndt.release();
     c->elev.release();
     c->vol.release();
     c->batch.release();
@@ -1828,6 +1831,75 @@ int lv_volume_shift_info(lv_ctx* c, lv_volume_shifts* out) {
     if (!out) { set_error("lv_volume_shift_info: null argument"); return LV_EINVAL; }
     LV_CHECK_CTX(c);
     c->vol.shift_info(out);
+    return LV_OK;
+}
+
+// ---- NDT registration (lv_ndt.hip)
+void lv_default_ndt_params(lv_ndt_params* p) { default_ndt_params(p); }
+void lv_default_ndt_align_params(lv_ndt_align_params* p) { default_ndt_align_params(p); }
+
+#define LV_NDT_BUILT(c) LV_REQUIRE((c)->ndt.built, LV_ESTATE, "no NDT target: call lv_ndt_build first")
+
+// a build (p given) or an add (p NULL) once the arguments have been judged.  The map source is read as lv_elev_build reads it.
+static int ndt_build_or_add(lv_ctx* c, const lv_ndt_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (!pts) {
+        LV_SETTLE_MAP(c);
+        LV_RELIN_POLL(c);
+    }
+    const bool any = !pts && c->map.built && c->map.m > 0;
+    const uint64_t more = pts ? (uint64_t)n : any ? (uint64_t)c->map.n_ids : 0u;
+    if (!p && c->ndt.n_given + more > NDT_MAX_POINTS) { set_error("lv_ndt_add: the target would hold more than 2^31 - 1 points"); return LV_EINVAL; }
+    if (!pts) return c->ndt.build(c->stream, p, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, nullptr, 0, 0, stats);
+    return c->ndt.build(c->stream, p, nullptr, 0, pts, stride, n, stats);
+}
+
+int lv_ndt_build(lv_ctx* c, const lv_ndt_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (const char* why = ndt_check_params(p)) { set_error("lv_ndt_build: %s", why); return LV_EINVAL; }
+    if (const char* why = ndt_check_points(pts, stride, n)) { set_error("lv_ndt_build: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return ndt_build_or_add(c, p, pts, stride, n, stats);
+}
+
+int lv_ndt_add(lv_ctx* c, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
+    if (const char* why = ndt_check_points(pts, stride, n)) { set_error("lv_ndt_add: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_NDT_BUILT(c);
+    return ndt_build_or_add(c, nullptr, pts, stride, n, stats);
+}
+
+int lv_ndt_fetch(lv_ctx* c, int layer, void* out, size_t capacity) {
+    if (!ndt_layer_width(layer)) { set_error("lv_ndt_fetch: layer %d: LV_NDT_COUNT .. LV_NDT_ICOV", layer); return LV_EINVAL; }
+    if (!out) { set_error("lv_ndt_fetch: null output"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_NDT_BUILT(c);
+    if (capacity < c->ndt.n_cells) { set_error("lv_ndt_fetch: room for nx * ny * nz = %zu voxels needed", c->ndt.n_cells); return LV_EINVAL; }
+    return c->ndt.fetch(c->stream, layer, out);
+}
+
+int lv_ndt_align(lv_ctx* c, const lv_ndt_align_params* params, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K,
+                 lv_ndt_result* results, int32_t best[2]) {
+    lv_ndt_align_params prm;
+    default_ndt_align_params(&prm);
+    if (params) prm = *params;
+    if (const char* why = ndt_check_align_params(&prm)) { set_error("lv_ndt_align: %s", why); return LV_EINVAL; }
+    if (int rc = ndt_check_align_args(src, stride, n_src, guesses, K, results, best)) return rc;
+    LV_CHECK_CTX(c);
+    LV_NDT_BUILT(c);
+    return c->ndt.align(c->stream, prm, src, stride, n_src, guesses, K, results, best);
+}
+
+int lv_ndt_info(lv_ctx* c, lv_ndt_target_info* out) {
+    if (!out) { set_error("lv_ndt_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *out = lv_ndt_target_info{};
+    if (c->ndt.built) *out = c->ndt.info;
+    return LV_OK;
+}
+
+int lv_ndt_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->ndt.release();
     return LV_OK;
 }
 

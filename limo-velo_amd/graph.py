@@ -70,6 +70,11 @@ class PoseGraph:
         t, q = relative(x_i, x_refined_j)
         self._edge(int(i), int(j), t, q, info_from_sigmas(sigma_t, sigma_r) if info is None else info, huber, True)
 
+    def add_registration(self, i, j, t, q, info, huber=0.0):
+        """A loop edge i -> j from a cloud-to-cloud registration (ndt.loop_measurement of lv_ndt_align's result): the measurement
+        T_i^-1 T_j as (t, q) with its 6 x 6 information."""
+        self._edge(int(i), int(j), np.asarray(t, np.float64), np.asarray(q, np.float64), info, huber, True)
+
     def add_gps(self, k, position, sigma=(0.2, 0.2, 0.5), lever=(0.0, 0.0, 0.0), huber=0.0):
         """A position prior on keyframe k: the antenna (at `lever` in the body frame) at `position` in the map frame
         (aiding.to_map of an ENU fix)."""
