@@ -1104,6 +1104,75 @@ void lv_default_mcl_params(lv_mcl_params* p);
 int  lv_occ_mcl_weigh(lv_ctx* ctx, const lv_mcl_params* p, const float* poses, size_t K, const float* beams, size_t B,
                       const uint32_t* table, size_t n_table, uint64_t* score, uint32_t* n_in, int64_t* best);
 
+/* ---- Resident localisation filter ------------------------------------------------------------------
+ * The whole cycle of AMCL on the device: K particles that stay there from one cycle to the next, with the motion update
+ * (sample_motion_model_odometry, Probabilistic Robotics, table 5.6, with the filter's own reproducible noise), the measurement
+ * update of "Localisation", the weights, the effective sample size, the estimate's sums and the systematic resampling.  f32
+ * operations in a stated order up to a cell or a quantised coordinate, integers after it, no float atomics: every output is a
+ * pure function of the arguments and the calls before, bitwise reproducible.
+ *   draws    mix(x) is splitmix64's finaliser with its additive constant; word(i, j) = mix(mix(mix(seed) ^ epoch) ^ ((i << 8) | j))
+ *            for particle i and j = 0..8, all 64-bit.  Standard normal n (0..2) of particle i: the sum of the twelve 16-bit fields
+ *            of the words 3n, 3n + 1, 3n + 2; G = 2 * sum - 12 * 65535; z = (float)G * 2^-17.  The resampling draw of an epoch is
+ *            mix(mix(mix(seed) ^ epoch) ^ UINT64_MAX).  epoch is a uint32 the store keeps: 0 after _set, incremented at the end of
+ *            every _move and every _resample; both are refused (LV_ESTATE) once it is 2^32 - 1.
+ *   move     delta = (rot1, trans, rot2), sigma = their standard deviations (from the alphas, by the caller), all finite,
+ *            sigma >= 0.  In f32, nothing fused, in this order: r1 = rot1 - z0 * s_rot1; tr = trans - z1 * s_trans;
+ *            r2 = rot2 - z2 * s_rot2; a = th + r1; (sn, cs) = the fixed polynomial of a; x += tr * cs; y += tr * sn; th = a + r2;
+ *            if th >= 3.14159274f then th -= 6.28318548f; then if th < -3.14159274f then th += 6.28318548f.  z stays.  A particle
+ *            whose heading is not USABLE ("Localisation") is left untouched; if a is not usable the heading becomes a and x, y stay.
+ *   weigh    the rule, the inputs and the limits of lv_occ_mcl_weigh on the resident poses (K * B <= 2^30 is judged once there
+ *            are particles); n_in is kept; acc_i becomes UINT64_MAX if it or the new score is UINT64_MAX, otherwise acc_i +=
+ *            score_i.  best: the least (score, index) of THIS scan's scores, as lv_occ_mcl_weigh gives it; may be NULL, and then
+ *            the call does not wait for the device.  The 2^20-th weigh since the last resampling is refused (LV_ESTATE): acc < 2^60.
+ *   weights  s_min = the least acc that is not UINT64_MAX; w_i = wtable[min((acc_i - s_min) >> shift, n_w - 1)], 0 where acc_i is
+ *            UINT64_MAX.  n_w 1..4096, every entry <= 2^20, shift 0..63.  W = sum w, sum_w2 = sum w^2, n_eligible = the particles
+ *            whose acc is not UINT64_MAX; s_min is -1 when there is none.
+ *   sums     over all particles, before any resampling.  Per axis a: q_a = floorf(((p_a - origin_a) / resolution) * 256) with
+ *            the origin and resolution of the field last built (reported in the statistics), clamped to +-2^22, 0 where it is
+ *            not finite; n_clamped = the particles clamped or zeroed in an axis.  qs = (int)rintf(sn * 1048576.0f), qc likewise,
+ *            both 0 for a heading that is not usable.  S[0..2] = sum w * q_a, S[3] = sum w * qs, S[4] = sum w * qc, in int64
+ *            (below 2^62).  The estimate is origin_a + resolution * (S[a] / W + 0.5) / 256 and atan2(S[3], S[4]).
+ *   decision mode 0: never; mode 2: whenever W > 0; mode 1: iff W > 0 and W^2 * below_den < below_num * K * sum_w2, exactly
+ *            (n_eff < below_num / below_den * K).  1 <= below_num <= below_den <= 65536.
+ *   resample systematic with M = K: C = the inclusive prefix sums of w, r = draw mod W, t_j = (j * W + r) / K, ancestor_j = the
+ *            smallest i with C_i > t_j; new pose j = old pose ancestor_j, bit for bit; every acc and the weigh counter become 0;
+ *            n_in is not gathered.  With W = 0 nothing moves.
+ * The particles are world poses: lv_occ_configure, a field build and lv_volume_recentre leave them alone, and a weigh reads the
+ * field as it stands at the call (a stale one is used as it is).  Arguments and NULLs are judged before the context (LV_EINVAL,
+ * nothing written, "null context" last); then LV_ESTATE: before lv_occ_configure (every call but _info and _clear), before a field
+ * build (_weigh and _resample), before _set.  A refused call changes nothing, the epoch included.  Nothing is allocated before
+ * _set; _clear and lv_destroy free everything.  _move does not wait for the device. */
+typedef struct lv_mcl_resample_params { int shift; int mode; uint32_t below_num, below_den; } lv_mcl_resample_params;
+typedef struct lv_mcl_filter_stats {
+    uint64_t W, sum_w2;
+    int64_t  s_min;             /* -1: no particle is eligible */
+    int64_t  S[5];
+    uint32_t n_eligible, n_clamped;
+    int      resampled;
+    uint32_t epoch;             /* after the call */
+    uint32_t since_resample;    /* weigh calls since the last resampling, after the call */
+    float    origin[3];         /* of the field the sums were quantised with */
+    float    resolution;
+} lv_mcl_filter_stats;
+typedef struct lv_mcl_filter_info { uint64_t K, seed; int set; uint32_t epoch, since_resample; } lv_mcl_filter_info;
+/* shift 0, mode 1, below_num 1, below_den 2. */
+void lv_default_mcl_resample_params(lv_mcl_resample_params* p);
+/* poses: K x 4 floats, K 1..2^20.  acc = 0, n_in = 0, epoch = 0. */
+int  lv_occ_mcl_filter_set(lv_ctx* ctx, const float* poses, size_t K, uint64_t seed);
+/* delta, sigma: 3 floats each. */
+int  lv_occ_mcl_filter_move(lv_ctx* ctx, const float* delta, const float* sigma);
+/* beams: B x 3 floats; table: n_table values; best: 2 values or NULL. */
+int  lv_occ_mcl_filter_weigh(lv_ctx* ctx, const lv_mcl_params* p, const float* beams, size_t B, const uint32_t* table, size_t n_table,
+                             int64_t* best);
+/* wtable: n_w values; ancestors: K values or NULL, written only when the call resampled. */
+int  lv_occ_mcl_filter_resample(lv_ctx* ctx, const lv_mcl_resample_params* p, const uint32_t* wtable, size_t n_w,
+                                lv_mcl_filter_stats* stats, uint32_t* ancestors);
+/* poses: K x 4 floats; acc, n_in: K values; each may be NULL, not all; capacity (in particles) >= K. */
+int  lv_occ_mcl_filter_get(lv_ctx* ctx, float* poses, uint64_t* acc, uint32_t* n_in, size_t capacity);
+/* zeros before _set; never LV_ESTATE. */
+int  lv_occ_mcl_filter_info(lv_ctx* ctx, lv_mcl_filter_info* out);
+int  lv_occ_mcl_filter_clear(lv_ctx* ctx);
+
 /* ---- TSDF and mesh -------------------------------------------------------------------------------------
  * A truncated signed distance field fused from the sweeps, and a triangle mesh of its zero surface: the TSDF layer of Voxblox
  * and nvblox with its mesh integrator ("a mesh of what the robot saw"; the reference has no counterpart).  The sweeps are the

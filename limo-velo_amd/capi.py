@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "lv_occ_distance_build_cells",
     "lv_default_rollout_params", "lv_occ_rollout",
     "lv_default_mcl_params", "lv_occ_mcl_weigh",
+    "lv_default_mcl_resample_params", "lv_occ_mcl_filter_set", "lv_occ_mcl_filter_move", "lv_occ_mcl_filter_weigh", "lv_occ_mcl_filter_resample",
+    "lv_occ_mcl_filter_get", "lv_occ_mcl_filter_info", "lv_occ_mcl_filter_clear",
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
@@ -498,6 +500,35 @@ MCL_ARGTYPES = {
 }
 
 
+class MclResampleParams(C.Structure):  # lv_mcl_resample_params
+    _fields_ = [("shift", C.c_int), ("mode", C.c_int), ("below_num", C.c_uint32), ("below_den", C.c_uint32)]
+
+
+class MclFilterStats(C.Structure):  # lv_mcl_filter_stats
+    _fields_ = [("W", C.c_uint64), ("sum_w2", C.c_uint64), ("s_min", C.c_int64), ("S", C.c_int64 * 5), ("n_eligible", C.c_uint32),
+                ("n_clamped", C.c_uint32), ("resampled", C.c_int), ("epoch", C.c_uint32), ("since_resample", C.c_uint32),
+                ("origin", C.c_float * 3), ("resolution", C.c_float)]
+
+
+class MclFilterInfo(C.Structure):  # lv_mcl_filter_info
+    _fields_ = [("K", C.c_uint64), ("seed", C.c_uint64), ("set", C.c_int), ("epoch", C.c_uint32), ("since_resample", C.c_uint32)]
+
+
+# ctypes signatures of the resident localisation filter (include/limovelo_hip.h "Resident localisation filter";
+# tests/test_occ_mcl_filter_abi.py)
+MCL_FILTER_ARGTYPES = {
+    "lv_occ_mcl_filter_set": [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_uint64],
+    "lv_occ_mcl_filter_move": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    "lv_occ_mcl_filter_weigh": [C.c_void_p, C.POINTER(MclParams), C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                C.POINTER(C.c_int64)],
+    "lv_occ_mcl_filter_resample": [C.c_void_p, C.POINTER(MclResampleParams), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(MclFilterStats),
+                                   C.POINTER(C.c_uint32)],
+    "lv_occ_mcl_filter_get": [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_size_t],
+    "lv_occ_mcl_filter_info": [C.c_void_p, C.POINTER(MclFilterInfo)],
+    "lv_occ_mcl_filter_clear": [C.c_void_p],
+}
+
+
 OBS_POSITION, OBS_VELOCITY_WORLD, OBS_VELOCITY_BODY, OBS_ATTITUDE = 1, 2, 3, 4   # LV_OBS_*
 OBSERVE_BATCH = 8   # LV_OBSERVE_BATCH
 
@@ -818,6 +849,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_rollout_params.argtypes = [C.POINTER(RolloutParams)]
         lib.lv_default_mcl_params.restype = None
         lib.lv_default_mcl_params.argtypes = [C.POINTER(MclParams)]
+        lib.lv_default_mcl_resample_params.restype = None
+        lib.lv_default_mcl_resample_params.argtypes = [C.POINTER(MclResampleParams)]
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         lib.lv_default_occ_mark_params.restype = None
@@ -833,7 +866,7 @@ def load_library() -> C.CDLL:
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -1027,6 +1060,14 @@ def default_rollout_params(**kw) -> RolloutParams:
 def default_mcl_params(**kw) -> MclParams:
     p = MclParams()
     load_library().lv_default_mcl_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_mcl_resample_params(**kw) -> MclResampleParams:
+    p = MclResampleParams()
+    load_library().lv_default_mcl_resample_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -1704,6 +1745,77 @@ class Context:
                                               t.ctypes.data_as(C.POINTER(C.c_uint32)) if len(t) else None, C.c_size_t(len(t)),
                                               ptr("score", C.c_uint64), ptr("n_in", C.c_uint32), ptr("best", C.c_int64)))
         return out
+
+    # --- resident localisation filter (include/limovelo_hip.h "Resident localisation filter")
+    def occ_mcl_filter_set(self, poses, seed: int = 0) -> None:
+        """lv_occ_mcl_filter_set: the particles [K, 4] (x, y, z, th) go to the device; acc, n_in and the epoch are 0."""
+        x = np.ascontiguousarray(poses, np.float32)
+        if x.ndim != 2 or x.shape[1] != 4:
+            raise ValueError("occ_mcl_filter_set: poses [K, 4]")
+        self._check(self.lib.lv_occ_mcl_filter_set(self.h, x.ctypes.data_as(C.POINTER(C.c_float)) if len(x) else None, C.c_size_t(len(x)),
+                                                   C.c_uint64(int(seed))))
+
+    def occ_mcl_filter_move(self, delta, sigma) -> None:
+        """lv_occ_mcl_filter_move by delta = (rot1, trans, rot2) with the standard deviations sigma (mcl.motion_sigmas)."""
+        d = np.ascontiguousarray(delta, np.float32).reshape(3)
+        s = np.ascontiguousarray(sigma, np.float32).reshape(3)
+        fptr = C.POINTER(C.c_float)
+        self._check(self.lib.lv_occ_mcl_filter_move(self.h, d.ctypes.data_as(fptr), s.ctypes.data_as(fptr)))
+
+    def occ_mcl_filter_weigh(self, beams, table, params: MclParams | None = None, want_best: bool = True):
+        """lv_occ_mcl_filter_weigh of the resident particles under the beams [B, 3] and the cost table: best [2] int64 (index, score;
+        -1, -1 if none) of this scan, or None when it is not asked for (the call then does not wait for the device)."""
+        p = params if params is not None else default_mcl_params()
+        e = np.ascontiguousarray(beams, np.float32)
+        t = np.ascontiguousarray(table, np.uint32)
+        if e.ndim != 2 or e.shape[1] != 3:
+            raise ValueError("occ_mcl_filter_weigh: beams [B, 3]")
+        if t.ndim != 1:
+            raise ValueError("occ_mcl_filter_weigh: table [n_table]")
+        best = np.zeros(2, np.int64) if want_best else None
+        self._check(self.lib.lv_occ_mcl_filter_weigh(self.h, C.byref(p), e.ctypes.data_as(C.POINTER(C.c_float)) if len(e) else None, C.c_size_t(len(e)),
+                                                     t.ctypes.data_as(C.POINTER(C.c_uint32)) if len(t) else None, C.c_size_t(len(t)),
+                                                     best.ctypes.data_as(C.POINTER(C.c_int64)) if want_best else None))
+        return best
+
+    def occ_mcl_filter_resample(self, wtable, params: MclResampleParams | None = None, want_ancestors: bool = False):
+        """lv_occ_mcl_filter_resample with the weight table [n_w] uint32: (MclFilterStats, ancestors [K] uint32 or None: asked for
+        and resampled)."""
+        p = params if params is not None else default_mcl_resample_params()
+        t = np.ascontiguousarray(wtable, np.uint32)
+        if t.ndim != 1:
+            raise ValueError("occ_mcl_filter_resample: wtable [n_w]")
+        stats = MclFilterStats()
+        anc = np.zeros(int(self.occ_mcl_filter_info().K), np.uint32) if want_ancestors else None
+        self._check(self.lib.lv_occ_mcl_filter_resample(self.h, C.byref(p), t.ctypes.data_as(C.POINTER(C.c_uint32)) if len(t) else None,
+                                                        C.c_size_t(len(t)), C.byref(stats),
+                                                        anc.ctypes.data_as(C.POINTER(C.c_uint32)) if anc is not None and len(anc) else None))
+        return stats, (anc if anc is not None and stats.resampled else None)
+
+    def occ_mcl_filter_get(self, want=("poses", "acc", "n_in")) -> dict:
+        """lv_occ_mcl_filter_get: those of poses [K, 4] f32, acc [K] uint64 and n_in [K] uint32 that `want` names."""
+        K = int(self.occ_mcl_filter_info().K)
+        out = {}
+        if "poses" in want:
+            out["poses"] = np.zeros((K, 4), np.float32)
+        if "acc" in want:
+            out["acc"] = np.zeros(K, np.uint64)
+        if "n_in" in want:
+            out["n_in"] = np.zeros(K, np.uint32)
+
+        def ptr(name, ct):
+            return out[name].ctypes.data_as(C.POINTER(ct)) if name in out else None
+
+        self._check(self.lib.lv_occ_mcl_filter_get(self.h, ptr("poses", C.c_float), ptr("acc", C.c_uint64), ptr("n_in", C.c_uint32), C.c_size_t(max(K, 1))))
+        return out
+
+    def occ_mcl_filter_info(self) -> MclFilterInfo:
+        info = MclFilterInfo()
+        self._check(self.lib.lv_occ_mcl_filter_info(self.h, C.byref(info)))
+        return info
+
+    def occ_mcl_filter_clear(self) -> None:
+        self._check(self.lib.lv_occ_mcl_filter_clear(self.h))
 
     def occ_view_gain(self, views) -> np.ndarray:
         """lv_occ_view_gain over views = [(R [3, 3], t [3], pattern end points [n, 3] sensor frame)] (1..32 of them); returns

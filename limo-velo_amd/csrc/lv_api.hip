@@ -17,6 +17,7 @@
 #include "lv_place.hpp"
 #include "lv_graph.hpp"
 #include "lv_ndt.hpp"
+#include "lv_mcl_filter.hpp"
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
 
@@ -56,6 +57,7 @@ struct lv_ctx {
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     GraphStore graph;   // lv_graph_*: the pose graph and the solver's vectors (lv_graph.hip); nothing allocated before lv_graph_set
     NdtStore ndt;       // lv_ndt_*: the target's Gaussians and the buffers of an alignment (lv_ndt.hip); nothing allocated before the first build
+    MclFilterStore mclf;   // lv_occ_mcl_filter_*: the resident particles and their buffers (lv_mcl_filter.hip); nothing allocated before lv_occ_mcl_filter_set
     VolumeTools vol;    // lv_occ_*, lv_tsdf_*, lv_volume_*: the two volumes, what is built from them and what keeps those honest (lv_volumes.hpp)
     ElevStore elev;     // lv_elev_*: the elevation map and its classes (lv_elevation.hip); nothing allocated before the first build
     BatchStore batch;   // lv_iterate_batch / lv_update_batch: their own buffers (lv_batch.hip)
@@ -263,6 +265,7 @@ void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part o
     c->place.release();
     c->graph.release();
     c->ndt.release();
+    c->mclf.release();
     c->elev.release();
     c->vol.release();
     c->batch.release();
@@ -1791,6 +1794,90 @@ int lv_occ_mcl_weigh(lv_ctx* c, const lv_mcl_params* p, const float* poses, size
     }
     LV_CHECK_CTX(c);
     return c->vol.mcl_weigh(c->stream, *p, poses, K, beams, B, table, n_table, score, n_in, best);
+}
+
+// ---- Resident localisation filter (lv_mcl_filter.hip).  The particles are world poses: they belong to no grid and no field, so
+// the store stands beside the volume tools and the entry points ask for the grid and the field themselves.
+void lv_default_mcl_resample_params(lv_mcl_resample_params* p) { default_mcl_resample_params(p); }
+
+#define LV_MCLF_GRID(c) LV_REQUIRE((c)->vol.occ.configured, LV_ESTATE, "no occupancy grid: call lv_occ_configure first")
+#define LV_MCLF_FIELD(c) LV_REQUIRE((c)->vol.dist.built, LV_ESTATE, "no distance field: call lv_occ_distance_build first")
+#define LV_MCLF_SET(c) LV_REQUIRE((c)->mclf.set, LV_ESTATE, "no particles: call lv_occ_mcl_filter_set first")
+#define LV_MCLF_EINVAL(name, why) \
+    do {                          \
+        if (const char* _w = (why)) { set_error(name ": %s", _w); return LV_EINVAL; } \
+    } while (0)
+#define LV_MCLF_ESTATE(name, why) \
+    do {                          \
+        if (const char* _w = (why)) { set_error(name ": %s", _w); return LV_ESTATE; } \
+    } while (0)
+
+int lv_occ_mcl_filter_set(lv_ctx* c, const float* poses, size_t K, uint64_t seed) {
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_set", mclf_check_set(poses, K));
+    LV_CHECK_CTX(c);
+    LV_MCLF_GRID(c);
+    return c->mclf.set_poses(c->stream, poses, K, seed);
+}
+
+int lv_occ_mcl_filter_move(lv_ctx* c, const float* delta, const float* sigma) {
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_move", mclf_check_move(delta, sigma));
+    LV_CHECK_CTX(c);
+    LV_MCLF_GRID(c);
+    LV_MCLF_SET(c);
+    LV_MCLF_ESTATE("lv_occ_mcl_filter_move", mclf_state_epoch(c->mclf.epoch));
+    return c->mclf.move(c->stream, delta, sigma);
+}
+
+int lv_occ_mcl_filter_weigh(lv_ctx* c, const lv_mcl_params* p, const float* beams, size_t B, const uint32_t* table, size_t n_table, int64_t* best) {
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_weigh", mclf_check_weigh(p, beams, B, table, n_table));
+    LV_CHECK_CTX(c);
+    LV_MCLF_GRID(c);
+    LV_MCLF_FIELD(c);
+    LV_MCLF_SET(c);
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_weigh", mclf_check_pairs(c->mclf.K, B));
+    LV_MCLF_ESTATE("lv_occ_mcl_filter_weigh", mclf_state_since(c->mclf.since));
+    return c->mclf.weigh(c->stream, c->vol.dist, *p, beams, B, table, n_table, best);
+}
+
+int lv_occ_mcl_filter_resample(lv_ctx* c, const lv_mcl_resample_params* p, const uint32_t* wtable, size_t n_w, lv_mcl_filter_stats* stats,
+                               uint32_t* ancestors) {
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_resample", mclf_check_resample(p, wtable, n_w, stats));
+    LV_CHECK_CTX(c);
+    LV_MCLF_GRID(c);
+    LV_MCLF_FIELD(c);
+    LV_MCLF_SET(c);
+    LV_MCLF_ESTATE("lv_occ_mcl_filter_resample", mclf_state_epoch(c->mclf.epoch));
+    return c->mclf.resample(c->stream, c->vol.dist, *p, wtable, n_w, stats, ancestors);
+}
+
+int lv_occ_mcl_filter_get(lv_ctx* c, float* poses, uint64_t* acc, uint32_t* n_in, size_t capacity) {
+    LV_MCLF_EINVAL("lv_occ_mcl_filter_get", mclf_check_get(poses, acc, n_in));
+    LV_CHECK_CTX(c);
+    LV_MCLF_GRID(c);
+    LV_MCLF_SET(c);
+    if (capacity < c->mclf.K) { set_error("lv_occ_mcl_filter_get: room for K = %zu particles needed", c->mclf.K); return LV_EINVAL; }
+    return c->mclf.get(c->stream, poses, acc, n_in);
+}
+
+int lv_occ_mcl_filter_info(lv_ctx* c, lv_mcl_filter_info* out) {
+    if (!out) { set_error("lv_occ_mcl_filter_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *out = lv_mcl_filter_info{};
+    if (c->mclf.set) {
+        out->set = 1;
+        out->K = (uint64_t)c->mclf.K;
+        out->seed = c->mclf.seed;
+        out->epoch = c->mclf.epoch;
+        out->since_resample = c->mclf.since;
+    }
+    return LV_OK;
+}
+
+int lv_occ_mcl_filter_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_HIP(hipStreamSynchronize(c->stream));
+    c->mclf.release();
+    return LV_OK;
 }
 
 // ---- TSDF and mesh (lv_tsdf.hip)

@@ -17,29 +17,11 @@
 #include <cstring>
 
 #include "lv_common.hpp"
+#include "lv_mcl_lanes.hpp"
 
 namespace lv {
 
 namespace {
-
-template <int G>
-struct MclLanes {
-    int g;
-    __device__ int first() const { return g; }
-    __device__ int stride() const { return G; }
-    __device__ void beam(const float* beams, int b, float& ex, float& ey, float& ez) const {
-        ex = beams[3 * b];
-        ey = beams[3 * b + 1];
-        ez = beams[3 * b + 2];
-    }
-    __device__ uint32_t cost(const uint32_t* table, uint32_t idx) const { return table[idx]; }
-    __device__ uint64_t sum(uint64_t v) const {
-        return (uint64_t)group_fold<G>((unsigned long long)v, [](unsigned long long a, unsigned long long b) { return a + b; });
-    }
-    __device__ uint32_t count(uint32_t v) const {
-        return group_fold<G>(v, [](uint32_t a, uint32_t b) { return a + b; });
-    }
-};
 
 // in: the table (MCL_MAX_TABLE words), the beams [B][3], the poses [K][4] (16-byte aligned: MclStore::run pads the beams).
 // key: the call's least key.

@@ -13,6 +13,8 @@ the loop.
   weigh()               lv_occ_mcl_weigh
   resample(), n_eff(), estimate()
   step(), track()       one cycle, and the loop
+  DeviceFilter          the same loop with the particles resident on the device (lv_occ_mcl_filter_*), with the filter's own
+                        reproducible noise; motion_sigmas(), estimate_from_stats() serve it
 
 A pose is (x, y, z, th): the robot moves in the plane, z places the scan in a 3-D field.  `ctx` is a capi.Context whose grid holds
 the map (occupancy.load_grid) and whose distance field is built (ctx.occ_distance_build)."""
@@ -239,3 +241,77 @@ def track(ctx, poses, deltas, scans, table, wtable, rng, **kw) -> list:
         x, acc = s["poses"], s["acc"]
         history.append(s)
     return history
+
+
+# ---- the resident filter (include/limovelo_hip.h "Resident localisation filter"): the same loop with the particles on the device
+def motion_sigmas(delta, alphas) -> np.ndarray:
+    """[3] f32: the standard deviations of (rot1, trans, rot2) for the odometry step delta under the noise parameters alphas =
+    (a1, a2, a3, a4), as move() takes them (Probabilistic Robotics, table 5.6, lines 5-7)."""
+    rot1, trans, rot2 = (float(v) for v in delta)
+    a1, a2, a3, a4 = (float(v) for v in alphas)
+    return np.array([math.sqrt(a1 * rot1 ** 2 + a2 * trans ** 2), math.sqrt(a3 * trans ** 2 + a4 * rot1 ** 2 + a4 * rot2 ** 2),
+                     math.sqrt(a1 * rot2 ** 2 + a2 * trans ** 2)], np.float32)
+
+
+def estimate_from_stats(stats) -> np.ndarray:
+    """[4] f64: the pose of a resampling call's statistics (capi.MclFilterStats): per axis origin + resolution * (S / W + 0.5) / 256,
+    the middle of the mean sub-unit, and atan2(S[3], S[4]) (NaN with no weight)."""
+    W = int(stats.W)
+    if W <= 0:
+        return np.full(4, np.nan)
+    res = float(stats.resolution)
+    xyz = [float(stats.origin[a]) + res * (int(stats.S[a]) / W + 0.5) / 256.0 for a in range(3)]
+    return np.array(xyz + [math.atan2(float(int(stats.S[3])), float(int(stats.S[4])))])
+
+
+def below_fraction(resample_below: float):
+    """(below_num, below_den) of lv_mcl_resample_params for the threshold n_eff < resample_below * K: 65536ths, at least one."""
+    return min(max(int(round(float(resample_below) * 65536.0)), 1), 65536), 65536
+
+
+class DeviceFilter:
+    """The particle filter with its particles resident on the device.  ctx: a capi.Context whose grid holds the map and whose
+    distance field is built; poses [K, 4]; seed: of the filter's own noise (every draw is a function of seed, epoch and particle).
+    Only the seven occ_mcl_filter_* calls of the context are used."""
+
+    def __init__(self, ctx, poses, seed: int = 0):
+        self.ctx = ctx
+        ctx.occ_mcl_filter_set(np.asarray(poses, np.float32).reshape(-1, 4), int(seed))
+
+    def move(self, delta, alphas=(0.05, 0.05, 0.05, 0.05)) -> None:
+        self.ctx.occ_mcl_filter_move(np.asarray(delta, np.float32), motion_sigmas(delta, alphas))
+
+    def weigh(self, beams, table, out_cost: int | None = None, min_inside: int = 1, want_best: bool = True):
+        """The measurement update; best [2] int64 of this scan (None when not asked for: the call then does not wait)."""
+        t = np.ascontiguousarray(table, np.uint32)
+        p = capi.MclParams(int(t[-1]) if out_cost is None else int(out_cost), int(min_inside))
+        return self.ctx.occ_mcl_filter_weigh(beams, t, p, want_best)
+
+    def resample(self, wtable, shift: int = 0, mode: int = 1, resample_below: float = 0.5, want_ancestors: bool = False):
+        """(statistics, ancestors or None) of lv_occ_mcl_filter_resample."""
+        num, den = below_fraction(resample_below)
+        return self.ctx.occ_mcl_filter_resample(wtable, capi.MclResampleParams(int(shift), int(mode), num, den), want_ancestors)
+
+    def poses(self) -> np.ndarray:
+        return self.ctx.occ_mcl_filter_get(("poses",))["poses"]
+
+    def step(self, delta, beams, table, wtable, alphas=(0.05, 0.05, 0.05, 0.05), shift: int = 0, resample_below: float = 0.5,
+             out_cost: int | None = None, min_inside: int = 1, mode: int = 1, fetch: bool = True) -> dict:
+        """One cycle, as step(): move, weigh, the estimate, and the resampling when n_eff falls below resample_below * K.  Returns
+        dict(best, estimate, n_eff, resampled, stats) and with fetch also poses, acc and n_in as they stand after the cycle and
+        moved, the poses that were weighed (two downloads a cycle: without fetch nothing of size K leaves the device)."""
+        self.move(delta, alphas)
+        best = self.weigh(beams, table, out_cost, min_inside)
+        out = {}
+        if fetch:
+            out["moved"] = self.poses()
+        stats, _ = self.resample(wtable, shift, mode, resample_below)
+        out.update(best=best, estimate=estimate_from_stats(stats), n_eff=n_eff(int(stats.W), int(stats.sum_w2)), resampled=bool(stats.resampled),
+                   stats=stats)
+        if fetch:
+            out.update(self.ctx.occ_mcl_filter_get())
+        return out
+
+    def track(self, deltas, scans, table, wtable, **kw) -> list:
+        """The loop: step() for every (delta, beams) of zip(deltas, scans).  Returns the steps' dicts."""
+        return [self.step(delta, beams, table, wtable, **kw) for delta, beams in zip(deltas, scans)]
