@@ -9,11 +9,7 @@
 #include "lv_host.hpp"
 #include "lv_knobs.hpp"
 #include "lv_rebuild.hpp"
-#include "lv_visibility.hpp"
-#include "lv_surface.hpp"
-#include "lv_cluster.hpp"
-#include "lv_planes.hpp"
-#include "lv_paint.hpp"
+#include "lv_maptools.hpp"
 #include "lv_place.hpp"
 #include "lv_graph.hpp"
 #include "lv_ndt.hpp"
@@ -48,12 +44,7 @@ struct lv_ctx {
     hipStream_t stream = nullptr;
 
     MapStore map;
-    QueryStore query;   // lv_map_knn / lv_map_radius_search / lv_map_box_search: their own buffers (lv_query.hip)
-    VisStore vis;       // lv_map_remove_dynamic: its own buffers (lv_visibility.hip)
-    PaintStore paint;   // lv_map_paint: its own buffers (lv_paint.hip)
-    SurfaceStore surface;   // lv_map_normals / lv_map_remove_outliers: their own buffers (lv_surface.hip)
-    ClusterStore cluster;   // lv_map_cluster / lv_map_remove_clusters: their own buffers (lv_cluster.hip)
-    PlaneStore planes;      // lv_map_planes: its own buffers (lv_planes.hip); nothing allocated before the first call
+    MapTools<MapRebuild<MapStore>> tools;   // the tools on the point map, their buffers and their order against inserts and rebuilds (lv_maptools.hpp)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     GraphStore graph;   // lv_graph_*: the pose graph and the solver's vectors (lv_graph.hip); nothing allocated before lv_graph_set
     NdtStore ndt;       // lv_ndt_*: the target's Gaussians and the buffers of an alignment (lv_ndt.hip); nothing allocated before the first build
@@ -107,7 +98,8 @@ struct SlowCall {
         }                                        \
     } while (0)
 
-// an incremental insert leaves its outcome in flight (MapStore::settle): pick it up before the map's bookkeeping is used
+// an incremental insert leaves its outcome in flight (MapStore::settle): pick it up before the map's bookkeeping is used.  Only
+// for the calls that settle WITHOUT polling the background rebuild (lv_maptools.hpp lists them); every other call: map_side(c).ready()
 #define LV_SETTLE_MAP(c)                               \
     do {                                               \
         int _rs = (c)->map.settle((c)->stream);        \
@@ -248,6 +240,9 @@ int lv_create(const lv_params* params, int device, lv_ctx** out) {
 static CtxStreams ctx_streams(lv_ctx* c) {
     return {c->stream, c->side_stream, c->ev_staged, c->overlap_insert && c->side_stream && c->stream == c->own_stream};
 }
+// ... and what a call that reads or edits the map sees of the context (lv_maptools.hpp): ready() is "settle the insert in flight,
+// then adopt or drop a finished background rebuild"
+static MapSide<MapRebuild<MapStore>> map_side(lv_ctx* c) { return {c->map, c->rebuild, ctx_streams(c), c->stream}; }
 
 void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part of the way: everything here takes what is not there)
     if (!c) return;
@@ -256,12 +251,7 @@ void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part o
     c->ranks.release_comm(c->stream);
     c->rebuild.release(c->map, ctx_streams(c));   // (joins its worker and waits for the device before anything is freed)
     c->map.release();
-    c->query.release();
-    c->vis.release();
-    c->paint.release();
-    c->surface.release();
-    c->cluster.release();
-    c->planes.release();
+    c->tools.release();
     c->place.release();
     c->graph.release();
     c->ndt.release();
@@ -329,12 +319,6 @@ static hipStream_t insert_stream(lv_ctx* c) {
     return c->map.built && c->map.m > 0 ? ctx_streams(c).side_behind() : c->stream;
 }
 
-#define LV_RELIN_POLL(c)                                          \
-    do {                                                          \
-        int _rp = (c)->rebuild.poll((c)->map, ctx_streams(c));    \
-        if (_rp) return _rp;                                      \
-    } while (0)
-
 int lv_map_build(lv_ctx* c, const void* points, size_t stride, size_t n) {
     LV_CHECK_CTX(c);
     c->rebuild.cancel(c->map, ctx_streams(c));
@@ -358,8 +342,7 @@ int lv_map_build(lv_ctx* c, const void* points, size_t stride, size_t n) {
 
 int lv_map_add(lv_ctx* c, const void* points, size_t stride, size_t n, int downsample) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     if (n == 0) return LV_OK;
     int rc = check_map_points(points, stride, n);
     if (rc) return rc;
@@ -397,8 +380,7 @@ __global__ void scan_to_world_kernel(const double* __restrict__ x, const float4*
 
 int lv_map_add_scan(lv_ctx* c, int downsample) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     const uint32_t n = c->scan.n;
     if (n == 0) return LV_OK;   // Mapper::add returns on an empty cloud (Mapper.cpp:20)
     if (int rp = c->filter.flush(c->stream, c->upd.d_kf)) return rp;
@@ -413,7 +395,7 @@ int lv_map_add_scan(lv_ctx* c, int downsample) {
     // The insert depends on nothing but the world points just staged, and nothing depends on it until the next search: it runs
     // on the context's SIDE stream, beside whatever the caller enqueues next (in the reference's loop, src/main.cpp:52-128: the
     // next cycle's IMU propagation, LiDAR window, de-skew and voxel grid — ~100 us of small launches while the insert's chain
-    // of ~150 us occupies a handful of CUs).  Everything that touches the map settles the insert first (LV_SETTLE_MAP: the
+    // of ~150 us occupies a handful of CUs).  Everything that touches the map settles the insert first (MapSide::ready, LV_SETTLE_MAP: the
     // host waits for the note the chain's last kernel posts), so no other ordering is needed.  Only with the context's own
     // stream: a caller-provided stream keeps everything on that stream.
     rc = c->rebuild.journal_add(c->map, ctx_streams(c), n, downsample, 0.2f, true);
@@ -428,8 +410,7 @@ int lv_map_evict_box(lv_ctx* c, const float lo[3], const float hi[3], int keep_i
     LV_CHECK_CTX(c);
     if (!lo || !hi) { set_error("null argument"); return LV_EINVAL; }
     uint32_t ne = 0;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     int rc = c->rebuild.journal_evict(c->map, ctx_streams(c), 2, lo, hi, keep_inside, 0);
     if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
     if (!rc) rc = c->map.evict_box(c->stream, lo, hi, keep_inside, &ne);
@@ -440,8 +421,7 @@ int lv_map_evict_box(lv_ctx* c, const float lo[3], const float hi[3], int keep_i
 int lv_map_evict_oldest(lv_ctx* c, size_t n_oldest, size_t* n_evicted) {
     LV_CHECK_CTX(c);
     uint32_t ne = 0;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     int rc = c->rebuild.journal_evict(c->map, ctx_streams(c), 3, nullptr, nullptr, 0, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest));
     if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
     if (!rc) rc = c->map.evict_oldest(c->stream, (uint32_t)(n_oldest > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : n_oldest), &ne);
@@ -451,260 +431,52 @@ int lv_map_evict_oldest(lv_ctx* c, size_t n_oldest, size_t* n_evicted) {
 
 void lv_default_visibility_params(lv_visibility_params* p) { default_visibility_params(p); }
 
-// Free-space removal (lv_visibility.hip), ordered like lv_map_evict_box: settle the insert in flight, adopt / drop a finished
-// background rebuild, journal the operation (the window-min images and poses: the worker replays the same pure rule on its copy),
-// order behind a snapshot, act
+// ---- The tools on the point map (lv_maptools.hpp: what each call asks for and in which order, and what a removal does to the
+// background rebuild).  An entry point checks the context and makes one call into c->tools.
 int lv_map_remove_dynamic(lv_ctx* c, const lv_view* views, size_t n_views, const lv_visibility_params* p, uint8_t* hits, size_t* n_removed) {
     LV_CHECK_CTX(c);
-    if (n_removed) *n_removed = 0;
-    VisRule q{};
-    int rc = visibility_rule(views, n_views, p, &q);
-    if (rc) return rc;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    if (!c->map.built || c->map.m == 0) return LV_OK;
-    rc = c->vis.build(c->stream, views, n_views, q);
-    if (rc) return rc;
-    const bool remove = p->dry_run == 0;
-    if (remove) {
-        rc = c->rebuild.journal_replay(c->map, ctx_streams(c), c->vis.d_blob, vis_blob_bytes(q), [q](MapStore& S, hipStream_t s, const void* blob) {
-            return vis_classify(S, s, blob, q, nullptr, nullptr, true, nullptr);
-        });
-        if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
-        if (rc) return rc;
-    }
-    const size_t m = c->map.m;   // (the store that acts: a copy adopted by the journal included)
-    const uint32_t* rank = nullptr;
-    if (hits) {
-        rc = c->vis.ensure_hits(m);
-        if (!rc) rc = c->query.ensure_rank(c->map, c->stream, &rank);
-        if (rc) return rc;
-    }
-    uint32_t nr = 0;
-    rc = vis_classify(c->map, c->stream, c->vis.d_blob, q, rank, hits ? c->vis.d_hits.p : nullptr, remove, &nr);
-    if (rc) return rc;
-    if (hits) LV_HIP(hipMemcpy(hits, c->vis.d_hits, m, hipMemcpyDeviceToHost));
-    if (n_removed) *n_removed = nr;
-    return LV_OK;
+    return c->tools.remove_dynamic(map_side(c), views, n_views, p, hits, n_removed);
 }
 
-// ---- Surface normals and outlier removal (lv_surface.hip)
 void lv_default_surface_params(lv_surface_params* p) { default_surface_params(p); }
 void lv_default_outlier_params(lv_outlier_params* p) { default_outlier_params(p); }
 
-// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
 int lv_map_normals(lv_ctx* c, const lv_surface_params* p, float* normals, float* curvature, float* mean_dist, int32_t* n_used, size_t capacity) {
     LV_CHECK_CTX(c);
-    SurfRule q{};
-    int rc = surface_rule(p, &q);
-    if (rc) return rc;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    const size_t m = c->map.m;
-    if (capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
-    if (!c->map.built || m == 0) return LV_OK;
-    const uint32_t* rank = nullptr;
-    rc = c->query.ensure_rank(c->map, c->stream, &rank);
-    if (!rc) rc = c->surface.ensure(c->map.n_ids, m, 0);
-    if (!rc) rc = surface_search(c->map, c->stream, c->surface, q, rank);
-    if (!rc && (normals || curvature)) rc = surface_finish(c->map, c->stream, c->surface, q, rank);
-    if (rc) return rc;
-    if (normals) LV_HIP(hipMemcpyAsync(normals, c->surface.d_normals, 3 * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (curvature) LV_HIP(hipMemcpyAsync(curvature, c->surface.d_curv, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (mean_dist) LV_HIP(hipMemcpyAsync(mean_dist, c->surface.d_mean, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (n_used) LV_HIP(hipMemcpyAsync(n_used, c->surface.d_used, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    return LV_OK;
+    return c->tools.normals(map_side(c), p, normals, curvature, mean_dist, n_used, capacity);
 }
 
-// Ordered like lv_map_remove_dynamic: settle the insert in flight, adopt / drop a finished background rebuild, resolve the rule
-// on the active store (read-only), journal the resolved rule (the worker replays it on its copy with the threshold fixed), order
-// behind a snapshot, act (on the values of the dry pass where the store is still the same)
 int lv_map_remove_outliers(lv_ctx* c, const lv_outlier_params* p, uint8_t* flags, size_t* n_removed, double* stats) {
     LV_CHECK_CTX(c);
-    SurfRule q{};
-    int rc = outlier_rule(p, &q);
-    if (rc) return rc;
-    // (valid from here on: the outputs are written)
-    if (n_removed) *n_removed = 0;
-    if (stats) stats[0] = stats[1] = stats[2] = 0.0;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    if (!c->map.built || c->map.m == 0) return LV_OK;
-    const bool remove = p->dry_run == 0;
-    const uint32_t* rank = nullptr;
-    double st3[3] = {0.0, 0.0, 0.0};
-    bool dry_pass = false;
-    if (remove) {
-        // the rule as the active store resolves it: a dry pass (mode 1 is resolved as it stands)
-        if (q.job == 1) {
-            rc = surface_outliers(c->map, c->stream, c->surface, q, nullptr, false, false, nullptr, st3);
-            if (rc) return rc;
-            dry_pass = true;
-        }
-        rc = c->surface.ensure(c->map.n_ids, c->map.m, q.job);
-        if (rc) return rc;
-        static_assert(sizeof(SurfRule) <= 2 * 256 * sizeof(double), "the rule is journaled out of SurfaceStore::d_part");
-        LV_HIP(hipMemcpyAsync(c->surface.d_part, &q, sizeof(SurfRule), hipMemcpyHostToDevice, c->stream));
-        LV_HIP(hipStreamSynchronize(c->stream));   // (q lives on this frame)
-        rc = c->rebuild.journal_replay(c->map, ctx_streams(c), c->surface.d_part, sizeof(SurfRule), [](MapStore& S, hipStream_t s, const void* blob) {
-            // (the worker runs beside the caller: its own rule copy and buffers, nothing of the context's SurfaceStore)
-            SurfRule r{};
-            LV_HIP(hipMemcpyAsync(&r, blob, sizeof(SurfRule), hipMemcpyDeviceToHost, s));
-            LV_HIP(hipStreamSynchronize(s));
-            SurfaceStore own;
-            const int rr = surface_outliers(S, s, own, r, nullptr, false, true, nullptr, nullptr);
-            own.release();   // (on every path: surface_outliers returns its errors, it does not throw)
-            return rr;
-        });
-        if (!rc) rc = c->rebuild.order(ctx_streams(c), c->stream);
-        if (rc) return rc;
-    }
-    const size_t m = c->map.m;   // (the store that acts: a copy adopted by the journal included)
-    if (flags) {
-        rc = c->query.ensure_rank(c->map, c->stream, &rank);
-        if (rc) return rc;
-    }
-    uint32_t nr = 0;
-    double st_act[3];
-    // (the dry pass's values stand unless the journal call adopted a rebuilt copy: the map's stamp tells)
-    rc = surface_outliers(c->map, c->stream, c->surface, q, rank, flags != nullptr, remove, &nr, st_act, dry_pass);
-    if (rc) return rc;
-    if (flags) LV_HIP(hipMemcpy(flags, c->surface.d_flags, m, hipMemcpyDeviceToHost));
-    if (n_removed) *n_removed = nr;
-    if (stats && q.job == 1) { const double* src = remove ? st3 : st_act; stats[0] = src[0]; stats[1] = src[1]; stats[2] = src[2]; }
-    return LV_OK;
+    return c->tools.remove_outliers(map_side(c), p, flags, n_removed, stats);
 }
 
-// ---- Map clustering (lv_cluster.hip)
 void lv_default_cluster_params(lv_cluster_params* p) { default_cluster_params(p); }
 
-// m bytes of the caller's (pageable) memory at living ranks -> the device
-static int cluster_upload(lv_ctx* c, uint8_t* dst, const uint8_t* src, size_t m) {
-    LV_HIP(hipMemcpyAsync(dst, src, m, hipMemcpyHostToDevice, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    return LV_OK;
-}
-
-// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
 int lv_map_cluster(lv_ctx* c, const lv_cluster_params* p, const uint8_t* mask, int32_t* labels, size_t capacity, uint32_t* sizes,
                    size_t sizes_capacity, size_t* n_clusters) {
     LV_CHECK_CTX(c);
-    ClusterRule q{};
-    int rc = cluster_rule(p, &q);
-    if (rc) return rc;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    const size_t m = c->map.m;
-    if (labels && capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
-    if (n_clusters) *n_clusters = 0;
-    if (!c->map.built || m == 0) return LV_OK;
-    const uint32_t* rank = nullptr;
-    rc = c->query.ensure_rank(c->map, c->stream, &rank);
-    if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
-    if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
-    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask.p : nullptr);
-    size_t C = 0;
-    if (!rc) rc = cluster_labels(c->map, c->stream, c->cluster, q, rank, labels != nullptr, &C);
-    if (rc) return rc;
-    if (labels) LV_HIP(hipMemcpyAsync(labels, c->cluster.d_labels, m * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    const size_t ns = C < sizes_capacity ? C : sizes_capacity;
-    if (sizes && ns) LV_HIP(hipMemcpyAsync(sizes, c->cluster.d_sizes, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    if (n_clusters) *n_clusters = C;
-    return LV_OK;
+    return c->tools.cluster_map(map_side(c), p, mask, labels, capacity, sizes, sizes_capacity, n_clusters);
 }
 
-// Ordered like lv_map_remove_outliers up to the journal: mask and seeds are per-point arrays in the ACTIVE store's map order,
-// which a replay on the worker's copy could only honour by carrying both arrays and the copy's own ranks along.  A removal
-// therefore first waits until a background rebuild in flight has landed (MapRebuild::status, wait: the copy is adopted with
-// everything journaled so far replayed) and then acts on the one store there is: nothing is lost, and the wait is stated in the
-// header.  A dry run touches nothing and reads the active store like lv_map_cluster.
 int lv_map_remove_clusters(lv_ctx* c, const lv_cluster_params* p, const uint8_t* mask, const uint8_t* seeds, uint8_t* flags, size_t* n_removed) {
     LV_CHECK_CTX(c);
-    ClusterRule q{};
-    int rc = cluster_rule(p, &q);
-    if (rc) return rc;
-    q.seeded = seeds ? 1 : 0;
-    // (valid from here on: the outputs are written)
-    if (n_removed) *n_removed = 0;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    if (!c->map.built || c->map.m == 0) return LV_OK;
-    const bool remove = p->dry_run == 0;
-    if (remove) {
-        rc = c->rebuild.status(c->map, ctx_streams(c), 1, nullptr);
-        if (rc) return rc;
-    }
-    const size_t m = c->map.m;   // (the store that acts: an adopted copy included; adoption keeps the map order)
-    const uint32_t* rank = nullptr;
-    rc = c->query.ensure_rank(c->map, c->stream, &rank);
-    if (!rc) rc = c->cluster.ensure(c->map.n_ids, m);
-    if (!rc && mask) rc = cluster_upload(c, c->cluster.d_mask, mask, m);
-    if (!rc && seeds) rc = cluster_upload(c, c->cluster.d_seeds, seeds, m);
-    if (!rc) rc = cluster_components(c->map, c->stream, c->cluster, q, rank, mask ? c->cluster.d_mask.p : nullptr);
-    uint32_t nr = 0;
-    if (!rc) rc = cluster_remove(c->map, c->stream, c->cluster, q, rank, c->cluster.d_seeds, flags ? c->cluster.d_flags.p : nullptr, remove, &nr);
-    if (rc) return rc;
-    if (flags) LV_HIP(hipMemcpy(flags, c->cluster.d_flags, m, hipMemcpyDeviceToHost));
-    if (n_removed) *n_removed = nr;
-    return LV_OK;
+    return c->tools.remove_clusters(map_side(c), p, mask, seeds, flags, n_removed);
 }
 
-// ---- Plane segmentation (lv_planes.hip)
 void lv_default_plane_params(lv_plane_params* p) { default_plane_params(p); }
 
-// Read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the active store
 int lv_map_planes(lv_ctx* c, const lv_plane_params* p, const uint8_t* mask, int32_t* labels, size_t capacity, lv_plane* planes,
                   size_t planes_capacity, size_t* n_planes) {
     LV_CHECK_CTX(c);
-    PlaneRule q{};
-    int rc = plane_rule(p, &q);
-    if (rc) return rc;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    const size_t m = c->map.m;
-    if (labels && capacity < m) { set_error("capacity %zu < %zu living points", capacity, m); return LV_EINVAL; }
-    if (n_planes) *n_planes = 0;
-    if (!c->map.built || m == 0) return LV_OK;
-    const uint32_t* rank = nullptr;
-    rc = c->query.ensure_rank(c->map, c->stream, &rank);
-    if (!rc) rc = c->planes.ensure(c->map.n_ids, m, q.iterations);
-    if (!rc && mask) rc = cluster_upload(c, c->planes.d_mask, mask, m);
-    lv_plane found[PLANE_MAX_PLANES];
-    size_t P = 0;
-    if (!rc) rc = planes_extract(c->map, c->stream, c->planes, q, rank, mask ? c->planes.d_mask.p : nullptr, labels != nullptr, found, &P);
-    if (rc) return rc;
-    if (labels) LV_HIP(hipMemcpy(labels, c->planes.d_labels, m * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const size_t np = P < planes_capacity ? P : planes_capacity;
-    if (planes && np) std::memcpy(planes, found, np * sizeof(lv_plane));
-    if (n_planes) *n_planes = P;
-    return LV_OK;
+    return c->tools.extract_planes(map_side(c), p, mask, labels, capacity, planes, planes_capacity, n_planes);
 }
 
 void lv_default_paint_params(lv_paint_params* p) { default_paint_params(p); }
 
-// Map painting (lv_paint.hip), read-only and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished
-// background rebuild, read the active store
 int lv_map_paint(lv_ctx* c, const lv_camera_view* views, size_t n_views, const lv_paint_params* p, float* rgb, float* depth, uint8_t* n_seen) {
     LV_CHECK_CTX(c);
-    PaintRule q{};
-    PaintCam cams[PAINT_MAX_VIEWS];
-    int rc = paint_rule(views, n_views, p, &q, cams);
-    if (rc) return rc;
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    if (!c->map.built || c->map.m == 0 || !(rgb || depth || n_seen)) return LV_OK;
-    const size_t m = c->map.m;
-    const uint32_t* rank = nullptr;
-    rc = c->query.ensure_rank(c->map, c->stream, &rank);
-    if (!rc) rc = c->paint.run(c->map, c->stream, views, cams, q, rank, rgb != nullptr, depth != nullptr, n_seen != nullptr);
-    if (rc) return rc;
-    if (rgb) LV_HIP(hipMemcpyAsync(rgb, c->paint.d_rgb, 3 * m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (depth) LV_HIP(hipMemcpyAsync(depth, c->paint.d_depth, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (n_seen) LV_HIP(hipMemcpyAsync(n_seen, c->paint.d_seen, m, hipMemcpyDeviceToHost, c->stream));
-    LV_HIP(hipStreamSynchronize(c->stream));
-    return LV_OK;
+    return c->tools.paint_map(map_side(c), views, n_views, p, rgb, depth, n_seen);
 }
 
 // ---- Place recognition (lv_place.hip)
@@ -755,16 +527,14 @@ int lv_place_add_scan(lv_ctx* c, const lv_state* x, uint32_t* id) {
     return c->place.add_scan(c->scan, c->stream, f, centre, id);
 }
 
-// read-only on the map and ordered like lv_map_knn: settle the insert in flight, adopt / drop a finished background rebuild, read the
-// active store
+// read-only on the map and ordered like the map tools (lv_maptools.hpp "the map source")
 int lv_place_add_map(lv_ctx* c, const double* centres, size_t n, uint32_t* first_id) {
     LV_CHECK_CTX(c);
     if (!centres) { set_error("null argument"); return LV_EINVAL; }
     if (n < 1 || n > PLACE_MAX_MAP_CENTRES) { set_error("n = %zu: must be in 1..%zu", n, PLACE_MAX_MAP_CENTRES); return LV_EINVAL; }
     if (int rc = place_centres_ok(centres, n)) return rc;
     if (c->place.n + n > PLACE_MAX_COUNT) { set_error("the place database holds 2^20 places"); return LV_ERANGE; }
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     return c->place.add_map(c->map, c->stream, centres, n, first_id);
 }
 
@@ -885,8 +655,7 @@ int lv_map_relinearise(lv_ctx* c) {
 
 int lv_map_relinearise_async(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     if (!c->map.built || c->map.m == 0) return LV_OK;
     return c->rebuild.start(c->map);
 }
@@ -894,8 +663,7 @@ int lv_map_relinearise_async(lv_ctx* c) {
 // every allocation a background rebuild needs, made at set-up time (MapRebuild::reserve)
 int lv_map_reserve_rebuild(lv_ctx* c) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     return c->rebuild.reserve(c->map, ctx_streams(c));
 }
 
@@ -906,8 +674,7 @@ int lv_map_rebuild_status(lv_ctx* c, int wait, uint64_t out[4]) {
 
 int lv_map_get_stats(lv_ctx* c, lv_map_stats* out) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     if (!out) { set_error("null argument"); return LV_EINVAL; }
     static_assert(sizeof(lv_map_stats) == sizeof(MapStats), "lv_map_stats layout");
     MapStats st;
@@ -947,28 +714,21 @@ int lv_map_fetch(lv_ctx* c, float* xyz_out, size_t capacity) {
     return LV_OK;
 }
 
-// Map queries (lv_query.hip): ordered behind every earlier map mutation — the insert in flight on the side stream (settle) and a
-// finished background rebuild (adopted by MapRebuild::poll) — and read the active store
+// Map queries (lv_query.hip): ordered behind every earlier map mutation like the tools above, they read the active store
 int lv_map_knn(lv_ctx* c, const void* q, size_t stride, size_t n, int k, float max_dist, uint32_t* idx, float* d2, int32_t* found) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    return c->query.knn(c->map, c->stream, q, stride, n, k, max_dist, idx, d2, found);
+    return c->tools.knn(map_side(c), q, stride, n, k, max_dist, idx, d2, found);
 }
 
 int lv_map_radius_search(lv_ctx* c, const void* q, size_t stride, size_t n, float radius, size_t* offsets, uint32_t* idx, float* d2,
                          size_t capacity, size_t* total) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    return c->query.radius(c->map, c->stream, q, stride, n, radius, offsets, idx, d2, capacity, total);
+    return c->tools.radius_search(map_side(c), q, stride, n, radius, offsets, idx, d2, capacity, total);
 }
 
 int lv_map_box_search(lv_ctx* c, const float lo[3], const float hi[3], uint32_t* idx, float* xyz, size_t capacity, size_t* n_out) {
     LV_CHECK_CTX(c);
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
-    return c->query.box(c->map, c->stream, lo, hi, idx, xyz, capacity, n_out);
+    return c->tools.box_search(map_side(c), lo, hi, idx, xyz, capacity, n_out);
 }
 
 // Multi-hypothesis passes / updates (lv_batch.hip): ordered behind every earlier map mutation like the map queries, the
@@ -993,8 +753,7 @@ int lv_iterate_batch(lv_ctx* c, const lv_state* xs, size_t m, lv_sums* out) {
     LV_CHECK_CTX(c);
     if (m == 0) return LV_OK;
     if (!xs || !out) { set_error("null argument"); return LV_EINVAL; }
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     return batch_common(c, xs, m, nullptr, false, nullptr, nullptr, nullptr, out);
 }
 
@@ -1002,8 +761,7 @@ int lv_update_batch(lv_ctx* c, lv_state* xs, size_t m, const double* P, double* 
     LV_CHECK_CTX(c);
     if (m == 0) return LV_OK;
     if (!xs || !P) { set_error("null argument"); return LV_EINVAL; }
-    LV_SETTLE_MAP(c);
-    LV_RELIN_POLL(c);
+    if (int rr = map_side(c).ready()) return rr;
     return batch_common(c, xs, m, P, true, xs, P_out, passes, last);
 }
 
@@ -1615,7 +1373,7 @@ int lv_occ_get_params(lv_ctx* c, lv_occupancy_params* out) { LV_CHECK_CTX(c); re
 
 void lv_default_occ_mark_params(lv_occ_mark_params* p) { default_occ_mark_params(p); }
 
-// The map source is read as lv_elev_build reads it, and only once there is a box to mark.
+// The map source (lv_maptools.hpp) is read only once there is a box to mark.
 int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
     if (!p) { set_error("lv_occ_mark: null params"); return LV_EINVAL; }
     if (p->min_points < 1 || p->min_points > (1 << 20)) { set_error("lv_occ_mark: min_points = %d: must be in 1..2^20", p->min_points); return LV_EINVAL; }
@@ -1627,13 +1385,10 @@ int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t 
     bool any_box = false;
     if (int rc = c->vol.occ_mark_box(*p, lo, hi, stats, &any_box)) return rc;
     if (!any_box) return LV_OK;
-    bool any = false;
-    if (!pts) {
-        LV_SETTLE_MAP(c);
-        LV_RELIN_POLL(c);
-        any = c->map.built && c->map.m > 0;
-    }
-    return c->vol.occ_mark(c->stream, *p, lo, hi, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, pts, stride, n, stats);
+    const float4* d_orig;
+    uint32_t n_ids, m;
+    if (int rc = map_side(c).source(pts, &d_orig, &n_ids, &m)) return rc;
+    return c->vol.occ_mark(c->stream, *p, lo, hi, d_orig, n_ids, pts, stride, n, stats);
 }
 
 // ---- Distance field (lv_distance.hip)
@@ -1927,16 +1682,14 @@ void lv_default_ndt_align_params(lv_ndt_align_params* p) { default_ndt_align_par
 
 #define LV_NDT_BUILT(c) LV_REQUIRE((c)->ndt.built, LV_ESTATE, "no NDT target: call lv_ndt_build first")
 
-// a build (p given) or an add (p NULL) once the arguments have been judged.  The map source is read as lv_elev_build reads it.
+// a build (p given) or an add (p NULL) once the arguments have been judged, from the caller's points or the map source (lv_maptools.hpp)
 static int ndt_build_or_add(lv_ctx* c, const lv_ndt_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
-    if (!pts) {
-        LV_SETTLE_MAP(c);
-        LV_RELIN_POLL(c);
-    }
-    const bool any = !pts && c->map.built && c->map.m > 0;
-    const uint64_t more = pts ? (uint64_t)n : any ? (uint64_t)c->map.n_ids : 0u;
+    const float4* d_orig;
+    uint32_t n_ids, m;
+    if (int rc = map_side(c).source(pts, &d_orig, &n_ids, &m)) return rc;
+    const uint64_t more = pts ? (uint64_t)n : (uint64_t)n_ids;
     if (!p && c->ndt.n_given + more > NDT_MAX_POINTS) { set_error("lv_ndt_add: the target would hold more than 2^31 - 1 points"); return LV_EINVAL; }
-    if (!pts) return c->ndt.build(c->stream, p, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, nullptr, 0, 0, stats);
+    if (!pts) return c->ndt.build(c->stream, p, d_orig, n_ids, nullptr, 0, 0, stats);
     return c->ndt.build(c->stream, p, nullptr, 0, pts, stride, n, stats);
 }
 
@@ -1991,37 +1744,20 @@ int lv_ndt_clear(lv_ctx* c) {
 }
 
 // ---- Elevation map (lv_elevation.hip)
-void lv_default_elevation_params(lv_elevation_params* p) {
-    if (!p) return;
-    *p = lv_elevation_params{};
-    p->origin[0] = -51.2f;
-    p->origin[1] = -51.2f;
-    p->origin[2] = -3.2f;
-    p->resolution = 0.2f;
-    p->nx = 512;
-    p->ny = 512;
-    p->min_points = 3;
-    p->head = 1920;        // 1.5 m: floor(m / resolution * 256)
-    p->max_span = 153;     // 0.12 m
-    p->max_step = 128;     // 0.10 m
-    p->max_slope2 = 34727; // floor((512 tan 20 deg)^2)
-}
+void lv_default_elevation_params(lv_elevation_params* p) { default_elevation_params(p); }
 
 #define LV_ELEV_BUILT(c) LV_REQUIRE((c)->elev.built, LV_ESTATE, "no elevation map: call lv_elev_build first")
 
-// (the arguments are judged before the context, as lv_occ_raycast's are).  The map source is read as lv_map_paint reads it:
-// the insert in flight settled, a finished background rebuild adopted, then the active store.
+// (the arguments are judged before the context, as lv_occ_raycast's are).  The caller's points, or the map source (lv_maptools.hpp).
 int lv_elev_build(lv_ctx* c, const lv_elevation_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]) {
     if (const char* why = elev_check_params(p)) { set_error("lv_elev_build: %s", why); return LV_EINVAL; }
     if (pts && stride < 12) { set_error("lv_elev_build: bad point array (stride %zu)", stride); return LV_EINVAL; }
     if (pts && n >= ELEV_MAX_N) { set_error("lv_elev_build: too many points"); return LV_EINVAL; }
     LV_CHECK_CTX(c);
-    if (!pts) {
-        LV_SETTLE_MAP(c);
-        LV_RELIN_POLL(c);
-        const bool any = c->map.built && c->map.m > 0;
-        return c->elev.build(c->stream, *p, any ? c->map.d_orig : nullptr, any ? c->map.n_ids : 0u, any ? c->map.m : 0u, nullptr, 0, 0, stats);
-    }
+    const float4* d_orig;
+    uint32_t n_ids, m;
+    if (int rc = map_side(c).source(pts, &d_orig, &n_ids, &m)) return rc;
+    if (!pts) return c->elev.build(c->stream, *p, d_orig, n_ids, m, nullptr, 0, 0, stats);
     return c->elev.build(c->stream, *p, nullptr, 0, 0, pts, stride, n, stats);
 }
 

@@ -1,9 +1,10 @@
 // lv_cluster.hpp — Euclidean clustering of the device map and removal by cluster (lv_map_cluster / lv_map_remove_clusters,
 // include/limovelo_hip.h "Map clustering"; kernels and host side in lv_cluster.hip).
 //
-// The first part is plain inline code that also compiles for the host (LV_CLUSTER_HOST_ONLY, through tests/emu/hip/hip_runtime.h
+// The first part is plain inline code that also compiles for the host (any compiler but hipcc, through tests/emu/hip/hip_runtime.h
 // whose atomics are sequential: tests/test_cluster_host.py holds it to scipy's connected components): the lock-free union-find
 // by minimum id, the key that orders the clusters and the rules that decide what is reported and what is removed.
+// LV_CLUSTER_HOST_ONLY leaves it at that first part (no ClusterStore, no lv_host.hpp).
 //
 // Union-find over parent[n_ids]: an included living id starts as its own parent, everything else holds CL_NONE and is never
 // touched.  A link always hangs the HIGHER root under the LOWER one, so a parent is smaller than its child (no cycle can form)
@@ -16,14 +17,13 @@
 
 #include <stdint.h>
 
-#if defined(LV_CLUSTER_HOST_ONLY)
 #include <hip/hip_runtime.h>
-#define LV_CL_D inline
-#define LV_CL_HD inline
-#elif defined(__HIPCC__)
-#include <hip/hip_runtime.h>
+#if defined(__HIPCC__)
 #define LV_CL_D __device__ __forceinline__
 #define LV_CL_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define LV_CL_D inline
+#define LV_CL_HD inline
 #endif
 
 namespace lv {
@@ -33,14 +33,14 @@ constexpr uint32_t CL_NONE = 0xFFFFFFFFu;   // parent of an id that takes no par
 // parent[] is read and written by every wavefront of the link kernel: relaxed accesses at device scope, so a value is never
 // served from a cache another compute die does not see
 LV_CL_D uint32_t cl_load(const uint32_t* p) {
-#if defined(LV_CLUSTER_HOST_ONLY)
+#if !defined(__HIPCC__)
     return *p;
 #else
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
 }
 LV_CL_D void cl_store(uint32_t* p, uint32_t v) {
-#if defined(LV_CLUSTER_HOST_ONLY)
+#if !defined(__HIPCC__)
     *p = v;
 #else
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

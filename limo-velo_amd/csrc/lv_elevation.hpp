@@ -104,6 +104,22 @@ LV_OCC_HD bool elev_query_cell(const ElevGrid& g, const float p[3], uint32_t& ce
     return true;
 }
 
+inline void default_elevation_params(lv_elevation_params* p) {
+    if (!p) return;
+    *p = lv_elevation_params{};
+    p->origin[0] = -51.2f;
+    p->origin[1] = -51.2f;
+    p->origin[2] = -3.2f;
+    p->resolution = 0.2f;
+    p->nx = 512;
+    p->ny = 512;
+    p->min_points = 3;
+    p->head = 1920;        // 1.5 m: floor(m / resolution * 256)
+    p->max_span = 153;     // 0.12 m
+    p->max_step = 128;     // 0.10 m
+    p->max_slope2 = 34727; // floor((512 tan 20 deg)^2)
+}
+
 // The parameters against their limits: NULL when they hold, otherwise what is wrong (lv_elev_build: LV_EINVAL)
 inline const char* elev_check_params(const lv_elevation_params* p) {
     if (!p) return "null params";
