@@ -1761,6 +1761,114 @@ int lv_graph_get_info(lv_ctx* ctx, lv_graph_info* info);
 /* Forgets the graph (the buffers stay for the next one). */
 int lv_graph_clear(lv_ctx* ctx);
 
+/* ---- Trajectory --------------------------------------------------------------------------------------
+ * A trajectory on the device for offline mapping: stamped poses (knots) that answer "where was the sensor at time t" for every
+ * point of a recording, that can be smoothed, that take the pose graph's corrections spread over time, and against which a whole
+ * recording's raw, time-stamped points are registered again in one pass.  Independent of the map, the volumes and the filter;
+ * everything in f64; times are f64 seconds and nothing narrows them (only differences of times enter the arithmetic); bitwise
+ * reproducible from call to call (no float atomics, fixed summation orders).  The rule is the __host__ __device__ code of
+ * limo-velo_amd/csrc/lv_traj.hpp on the quaternion algebra of lv_graph.hpp; tests/traj_ref.py restates it in numpy.
+ *
+ *   knot      (time, t, q): position and unit quaternion x, y, z, w as in lv_graph_pose; times strictly ascending.
+ *   sample    for time_a <= t < time_b of neighbouring knots: u = (t - time_a) / (time_b - time_a), p = p_a + u (p_b - p_a),
+ *             q = q_a * Exp(u Log(q_a^-1 q_b)), renormalised (q / sqrt(((x^2 + y^2) + z^2) + w^2)).  Log takes the quaternion with
+ *             w >= 0, the short way round, so a knot stored as -q gives the same rotation.  A time equal to a knot's time gives that
+ *             knot's pose bit for bit, the last knot's included; one knot alone is a constant.  p_b - p_a and Log(q_a^-1 q_b) are
+ *             formed once per knot.  Status: LV_TRAJ_INSIDE, LV_TRAJ_BEFORE (t below the first knot), LV_TRAJ_AFTER (above the
+ *             last), LV_TRAJ_NONFINITE.  Outside, LV_TRAJ_CLAMP gives the first / last knot's pose and LV_TRAJ_REFUSE gives NaN;
+ *             the status says which side under both.  A non-finite time gives NaN under both.
+ *   smooth    a kernel smoother, Jacobi style (every knot reads the values of the iteration before).  The window of knot i is
+ *             j in [max(0, i - half_window), min(n - 1, i + half_window)], w_j = exp(-0.5 ((time_j - time_i) / sigma)^2), the sums
+ *             run in ascending j, W = sum w_j; p_i <- p_i + (sum w_j (p_j - p_i)) / W and q_i <- q_i * Exp((sum w_j Log(q_i^-1 q_j)) / W),
+ *             renormalised: one step towards the weighted Karcher mean.  A knot with fixed[i] != 0 keeps its bits, and so do the
+ *             two ends under pin_ends.  iterations = 0 changes nothing.  THIS IS A SIGNAL SMOOTHER, NOT A STATISTICAL ONE: the store
+ *             holds no covariances, and weighing measurements against one another across loops remains lv_graph_*'s job.
+ *   correct   corr is itself a small trajectory whose poses are corrections D_k = T_now T_0^-1 at keyframe times.  Every knot i
+ *             becomes D(time_i) o knot_i with D(t) = corr sampled by the sample rule, clamped outside: t' = D_R t + D_t (row sums
+ *             left to right, then + D_t), q' = D_q * q renormalised.  A sampled correction that is the identity bit for bit
+ *             (q = (0, 0, 0, 1), t = 0) leaves the knot bit for bit (as lv_graph_warp_points promises).  Times are untouched.
+ *   register  a point p (x, y, z f32, its own f64 time t): b = E_R p + E_t with the extrinsic E (LiDAR in body), w = R(q(t)) b + p(t)
+ *             with the sampled pose, and with frame = LV_TRAJ_FRAME_AT: w = F_R w + F_t, F = (T(frame_time) E)^-1 formed once per
+ *             call: the continuous-time de-skew into the LiDAR frame at frame_time.  All in f64, every row ((a x + b y) + c z) + d,
+ *             rounded once to f32.  A point with a non-finite coordinate or time gives NaN and LV_TRAJ_NONFINITE; a point outside
+ *             the trajectory follows `extrapolate`.
+ *   routes    a workgroup takes 256 consecutive points, finds the knot range that brackets their finite times, and when the range
+ *             holds at most 256 knots stages it in LDS (the tile route); otherwise every lane searches the whole time array (the
+ *             search route).  Both run the same function on the same knots and give the same bits; stats[2] / stats[3] count the
+ *             workgroups of either.  lv_set_option("traj_tile", 0) forces the search route (tests, timing); default 1.
+ *   limits    1 <= n <= 2^20 knots; sample and register calls take up to 2^28 items.  lv_traj_set and lv_traj_correct give
+ *             LV_EINVAL, naming the record and the field, for a non-finite number, a quaternion whose norm is off 1 by more than
+ *             1e-6 and times that are not strictly ascending.  lv_traj_smooth: sigma > 0, half_window 1..64, iterations 0..100.
+ *             lv_traj_register: time_offset >= 12, time_offset + 8 <= stride (offsets need not be aligned), the extrinsic finite
+ *             and of unit norm, frame_time finite and on the trajectory.  Arguments are judged before the context ("null context"
+ *             comes last; frame_time against the trajectory needs the store and comes after it), and a rejected call writes
+ *             nothing: the trajectory held before stays bit for bit.
+ * Before lv_traj_set and after lv_traj_clear every call below except the two defaults gives LV_ESTATE; lv_traj_get_info reports
+ * set = 0 instead.  The calls run on the context's stream and return when their outputs are written.  With host arrays a register
+ * call is bound by its transfers, not by the kernel (DESIGN.md "Trajectory"); lv_traj_register_cloud is the route without the
+ * upload.  lv_destroy releases the store. */
+#define LV_TRAJ_MAX_KNOTS (1u << 20)
+#define LV_TRAJ_INSIDE 0
+#define LV_TRAJ_BEFORE 1
+#define LV_TRAJ_AFTER 2
+#define LV_TRAJ_NONFINITE 3
+#define LV_TRAJ_CLAMP 0
+#define LV_TRAJ_REFUSE 1
+#define LV_TRAJ_WORLD 0
+#define LV_TRAJ_FRAME_AT 1
+typedef struct lv_traj_knot {    /* 64 bytes */
+    double time;                 /* seconds */
+    double t[3];
+    double q[4];                 /* x, y, z, w */
+} lv_traj_knot;
+typedef struct lv_traj_smooth_params {   /* 24 bytes */
+    double  sigma;               /* seconds, > 0 (0.1) */
+    int32_t half_window;         /* knots each side, 1..64 (8) */
+    int32_t iterations;          /* 0..100 (1) */
+    int32_t pin_ends;            /* the first and the last knot keep their bits (1) */
+} lv_traj_smooth_params;
+typedef struct lv_traj_register_params {   /* 72 bytes */
+    int32_t extrapolate;         /* LV_TRAJ_CLAMP (default) or LV_TRAJ_REFUSE */
+    int32_t frame;               /* LV_TRAJ_WORLD (default) or LV_TRAJ_FRAME_AT */
+    double  ext_t[3];            /* E: LiDAR in body (offset_T_L_I); default 0 */
+    double  ext_q[4];            /* (offset_R_L_I as a quaternion); default 0, 0, 0, 1 */
+    double  frame_time;          /* with LV_TRAJ_FRAME_AT */
+} lv_traj_register_params;
+typedef struct lv_traj_info {    /* 64 bytes */
+    int32_t  set;                /* a trajectory is held */
+    uint32_t n;
+    double   t_first, t_last;
+    uint32_t smooth_iterations;  /* smoothing iterations applied since lv_traj_set */
+    uint32_t corrections;        /* lv_traj_correct calls applied since lv_traj_set */
+    uint64_t last_register[4];   /* the stats of the last register call */
+} lv_traj_info;
+void lv_default_traj_smooth_params(lv_traj_smooth_params* p);
+void lv_default_traj_register_params(lv_traj_register_params* p);
+/* Copies n knots to the device and forms their interval records.  Replaces the trajectory held before. */
+int lv_traj_set(lv_ctx* ctx, const lv_traj_knot* knots, size_t n);
+/* The current knots; capacity < n: LV_EINVAL. */
+int lv_traj_fetch(lv_ctx* ctx, lv_traj_knot* knots, size_t capacity);
+int lv_traj_get_info(lv_ctx* ctx, lv_traj_info* info);
+/* Forgets the trajectory (the buffers stay for the next one). */
+int lv_traj_clear(lv_ctx* ctx);
+/* The sample rule for n times: out n poses, status n bytes; either may be NULL. */
+int lv_traj_sample(lv_ctx* ctx, const double* times, size_t n, int extrapolate, lv_graph_pose* out, uint8_t* status);
+/* The smoother above; fixed: one byte per knot or NULL. */
+int lv_traj_smooth(lv_ctx* ctx, const lv_traj_smooth_params* params, const uint8_t* fixed);
+/* Applies the corrections corr (m >= 1 records, judged as lv_traj_set judges its knots) to every knot. */
+int lv_traj_correct(lv_ctx* ctx, const lv_traj_knot* corr, size_t m);
+/* Registers n points: records of `stride` bytes with x, y, z f32 at 0 and an f64 time at time_offset (16 in the reference's 32-byte
+ * Point).  params NULL: the defaults.  out: 3 n floats, status: n bytes; either may be NULL (to count only).  stats (may be NULL):
+ * points inside, points outside (before + after + non-finite), workgroups of the tile route, workgroups of the search route.
+ * n = 0: LV_OK, nothing written but stats. */
+int lv_traj_register(lv_ctx* ctx, const lv_traj_register_params* params, const void* pts, size_t stride, size_t time_offset, size_t n,
+                     float* out, uint8_t* status, uint64_t stats[4]);
+/* The same kernel on the device LiDAR buffer: the points with t1 <= time <= t2, oldest first, exactly what lv_cloud_fetch(t1, t2)
+ * returns and in its order.  The raw points do not leave the device and nothing in the buffer changes.  *n: the points of the
+ * window.  out == NULL: only *n is set (to size out: 3 *n floats; status: *n bytes, may be NULL); capacity < *n points: LV_EINVAL. */
+int lv_traj_register_cloud(lv_ctx* ctx, const lv_traj_register_params* params, double t1, double t2, float* out, uint8_t* status,
+                           size_t capacity, size_t* n, uint64_t stats[4]);
+
 /* ---- NDT registration --------------------------------------------------------------------------------
  * Cloud-to-cloud registration by the normal-distributions transform: a TARGET cloud becomes a voxel grid of Gaussians built
  * once, and a SOURCE cloud is aligned to it from K initial guesses at a time (what PCL's NormalDistributionsTransform::align,

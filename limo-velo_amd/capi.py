@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "lv_default_observation", "lv_observe", "lv_observe_results",
     "lv_default_graph_params", "lv_graph_set", "lv_graph_optimise", "lv_graph_fetch", "lv_graph_chi2", "lv_graph_warp_points",
     "lv_graph_get_info", "lv_graph_clear",
+    "lv_default_traj_smooth_params", "lv_default_traj_register_params", "lv_traj_set", "lv_traj_fetch", "lv_traj_get_info", "lv_traj_clear",
+    "lv_traj_sample", "lv_traj_smooth", "lv_traj_correct", "lv_traj_register", "lv_traj_register_cloud",
     "lv_default_ndt_params", "lv_default_ndt_align_params", "lv_ndt_build", "lv_ndt_add", "lv_ndt_fetch", "lv_ndt_align", "lv_ndt_info",
     "lv_ndt_clear",
 ]
@@ -240,6 +242,52 @@ GRAPH_ARGTYPES = {
     "lv_graph_warp_points": [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_float)],
     "lv_graph_get_info": [C.c_void_p, C.POINTER(GraphInfo)],
     "lv_graph_clear": [C.c_void_p],
+}
+
+
+class TrajKnot(C.Structure):  # lv_traj_knot (64 bytes)
+    _fields_ = [("time", C.c_double), ("t", C.c_double * 3), ("q", C.c_double * 4)]
+
+
+class TrajSmoothParams(C.Structure):  # lv_traj_smooth_params (24 bytes)
+    _fields_ = [("sigma", C.c_double), ("half_window", C.c_int32), ("iterations", C.c_int32), ("pin_ends", C.c_int32)]
+
+
+class TrajRegisterParams(C.Structure):  # lv_traj_register_params (72 bytes)
+    _fields_ = [("extrapolate", C.c_int32), ("frame", C.c_int32), ("ext_t", C.c_double * 3), ("ext_q", C.c_double * 4),
+                ("frame_time", C.c_double)]
+
+
+class TrajInfo(C.Structure):  # lv_traj_info (64 bytes)
+    _fields_ = [("set", C.c_int32), ("n", C.c_uint32), ("t_first", C.c_double), ("t_last", C.c_double), ("smooth_iterations", C.c_uint32),
+                ("corrections", C.c_uint32), ("last_register", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_}
+        d["last_register"] = [int(v) for v in self.last_register]
+        return d
+
+
+TRAJ_MAX_KNOTS = 1 << 20
+TRAJ_INSIDE, TRAJ_BEFORE, TRAJ_AFTER, TRAJ_NONFINITE = 0, 1, 2, 3
+TRAJ_CLAMP, TRAJ_REFUSE = 0, 1
+TRAJ_WORLD, TRAJ_FRAME_AT = 0, 1
+TRAJ_TILE = 256   # knots a workgroup of the register kernel stages (TRAJ_TILE of lv_traj.hpp)
+TRAJ_KNOT_DTYPE = np.dtype([("time", "f8"), ("t", "f8", 3), ("q", "f8", 4)])   # the same bytes as TrajKnot
+
+# ctypes signatures of the trajectory (include/limovelo_hip.h "Trajectory"; tests/test_traj_abi.py)
+TRAJ_ARGTYPES = {
+    "lv_traj_set": [C.c_void_p, C.POINTER(TrajKnot), C.c_size_t],
+    "lv_traj_fetch": [C.c_void_p, C.POINTER(TrajKnot), C.c_size_t],
+    "lv_traj_get_info": [C.c_void_p, C.POINTER(TrajInfo)],
+    "lv_traj_clear": [C.c_void_p],
+    "lv_traj_sample": [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_int, C.POINTER(GraphPose), C.POINTER(C.c_uint8)],
+    "lv_traj_smooth": [C.c_void_p, C.POINTER(TrajSmoothParams), C.POINTER(C.c_uint8)],
+    "lv_traj_correct": [C.c_void_p, C.POINTER(TrajKnot), C.c_size_t],
+    "lv_traj_register": [C.c_void_p, C.POINTER(TrajRegisterParams), C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_float),
+                         C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)],
+    "lv_traj_register_cloud": [C.c_void_p, C.POINTER(TrajRegisterParams), C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                               C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)],
 }
 
 
@@ -859,6 +907,10 @@ def load_library() -> C.CDLL:
         lib.lv_default_observation.argtypes = [C.POINTER(Observation), C.c_int]
         lib.lv_default_graph_params.restype = None
         lib.lv_default_graph_params.argtypes = [C.POINTER(GraphParams)]
+        lib.lv_default_traj_smooth_params.restype = None
+        lib.lv_default_traj_smooth_params.argtypes = [C.POINTER(TrajSmoothParams)]
+        lib.lv_default_traj_register_params.restype = None
+        lib.lv_default_traj_register_params.argtypes = [C.POINTER(TrajRegisterParams)]
         lib.lv_default_ndt_params.restype = None
         lib.lv_default_ndt_params.argtypes = [C.POINTER(NdtParams)]
         lib.lv_default_ndt_align_params.restype = None
@@ -867,7 +919,7 @@ def load_library() -> C.CDLL:
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
-                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **NDT_ARGTYPES}.items():
+                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -946,6 +998,38 @@ def default_place_params(**kw) -> PlaceParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_traj_smooth_params(**kw) -> TrajSmoothParams:
+    p = TrajSmoothParams()
+    load_library().lv_default_traj_smooth_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_traj_register_params(extrapolate=None, frame=None, ext_t=None, ext_q=None, frame_time=None) -> TrajRegisterParams:
+    p = TrajRegisterParams()
+    load_library().lv_default_traj_register_params(C.byref(p))
+    if extrapolate is not None:
+        p.extrapolate = int(extrapolate)
+    if frame is not None:
+        p.frame = int(frame)
+    if ext_t is not None:
+        p.ext_t[:] = [float(v) for v in ext_t]
+    if ext_q is not None:
+        p.ext_q[:] = [float(v) for v in ext_q]
+    if frame_time is not None:
+        p.frame_time = float(frame_time)
+    return p
+
+
+def traj_knots(times, poses) -> np.ndarray:
+    """TRAJ_KNOT_DTYPE records from times [n] and poses [n, 7] (t, q = x y z w)."""
+    x = np.asarray(poses, np.float64).reshape(-1, 7)
+    k = np.zeros(len(x), TRAJ_KNOT_DTYPE)
+    k["time"], k["t"], k["q"] = np.asarray(times, np.float64).reshape(-1), x[:, :3], x[:, 3:]
+    return k
 
 
 def default_graph_params(**kw) -> GraphParams:
@@ -2074,6 +2158,86 @@ class Context:
 
     def graph_clear(self):
         self._check(self.lib.lv_graph_clear(self.h))
+
+    # --- trajectory (include/limovelo_hip.h "Trajectory"; limo_velo_amd.offline has the helpers)
+    @staticmethod
+    def _traj_knots(knots):
+        k = np.ascontiguousarray(np.asarray(knots, TRAJ_KNOT_DTYPE).reshape(-1))
+        return k, k.ctypes.data_as(C.POINTER(TrajKnot))
+
+    def traj_set(self, knots):
+        """lv_traj_set: knots as TRAJ_KNOT_DTYPE records (capi.traj_knots builds them from times and poses)."""
+        k, p = self._traj_knots(knots)
+        self._check(self.lib.lv_traj_set(self.h, p, C.c_size_t(len(k))))
+
+    def traj_info(self) -> dict:
+        info = TrajInfo()
+        self._check(self.lib.lv_traj_get_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def traj_fetch(self) -> np.ndarray:
+        """The current knots (TRAJ_KNOT_DTYPE)."""
+        out = np.zeros(max(self.traj_info()["n"], 1), TRAJ_KNOT_DTYPE)
+        self._check(self.lib.lv_traj_fetch(self.h, out.ctypes.data_as(C.POINTER(TrajKnot)), C.c_size_t(len(out))))
+        return out[:self.traj_info()["n"]]
+
+    def traj_clear(self):
+        self._check(self.lib.lv_traj_clear(self.h))
+
+    def traj_sample(self, times, extrapolate=TRAJ_CLAMP):
+        """(poses [n, 7] f64, status [n] u8) of the trajectory at times [n] f64."""
+        t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
+        out, st = np.zeros((len(t), 7)), np.zeros(len(t), np.uint8)
+        self._check(self.lib.lv_traj_sample(self.h, t.ctypes.data_as(C.POINTER(C.c_double)), C.c_size_t(len(t)), int(extrapolate),
+                                            out.ctypes.data_as(C.POINTER(GraphPose)), st.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out, st
+
+    def traj_smooth(self, params: TrajSmoothParams | None = None, fixed=None, **kw):
+        """lv_traj_smooth with the given parameters (default: lv_default_traj_smooth_params changed by kw); fixed [n] bool or None."""
+        p = params if params is not None else default_traj_smooth_params(**kw)
+        f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, bool).astype(np.uint8))
+        if f is not None and len(f) != self.traj_info()["n"]:
+            raise ValueError("one flag per knot")
+        self._check(self.lib.lv_traj_smooth(self.h, C.byref(p), None if f is None else f.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def traj_correct(self, corrections):
+        """lv_traj_correct: corrections D_k at keyframe times as TRAJ_KNOT_DTYPE records (offline.corrections builds them)."""
+        k, p = self._traj_knots(corrections)
+        self._check(self.lib.lv_traj_correct(self.h, p, C.c_size_t(len(k))))
+
+    def traj_register(self, points, params: TrajRegisterParams | None = None, time_offset=None, want_points=True, want_status=True):
+        """lv_traj_register.  points: a structured array with x, y, z f32 at offset 0 and an f64 field "time" (POINT_DTYPE, what
+        cloud_fetch returns), or (bytes-like, stride, time_offset, n).  Returns (out [n, 3] f32 or None, status [n] u8 or None,
+        stats [4])."""
+        if isinstance(points, tuple):
+            raw, stride, toff, n = points
+            buf = np.frombuffer(raw, np.uint8)
+        else:
+            a = np.ascontiguousarray(points)
+            stride, n = a.dtype.itemsize, len(a)
+            toff = a.dtype.fields["time"][1] if time_offset is None else int(time_offset)
+            buf = a.view(np.uint8).reshape(-1)
+        p = params if params is not None else default_traj_register_params()
+        out = np.zeros((n, 3), np.float32) if want_points else None
+        st = np.zeros(n, np.uint8) if want_status else None
+        stats = (C.c_uint64 * 4)()
+        self._check(self.lib.lv_traj_register(self.h, C.byref(p), buf.ctypes.data_as(C.c_void_p) if n else None, C.c_size_t(stride),
+                                              C.c_size_t(toff), C.c_size_t(n),
+                                              out.ctypes.data_as(C.POINTER(C.c_float)) if want_points else None,
+                                              st.ctypes.data_as(C.POINTER(C.c_uint8)) if want_status else None, stats))
+        return out, st, [int(v) for v in stats]
+
+    def traj_register_cloud(self, t1: float, t2: float, params: TrajRegisterParams | None = None):
+        """lv_traj_register_cloud over the device LiDAR buffer's window [t1, t2]: (out [n, 3] f32, status [n] u8, stats [4])."""
+        p = params if params is not None else default_traj_register_params()
+        n = C.c_size_t(0)
+        stats = (C.c_uint64 * 4)()
+        self._check(self.lib.lv_traj_register_cloud(self.h, C.byref(p), C.c_double(t1), C.c_double(t2), None, None, C.c_size_t(0), C.byref(n), stats))
+        cnt = int(n.value)
+        out, st = np.zeros((max(cnt, 1), 3), np.float32), np.zeros(max(cnt, 1), np.uint8)
+        self._check(self.lib.lv_traj_register_cloud(self.h, C.byref(p), C.c_double(t1), C.c_double(t2), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    st.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(len(st)), C.byref(n), stats))
+        return out[:n.value], st[:n.value], [int(v) for v in stats]
 
     # --- NDT registration (include/limovelo_hip.h "NDT registration"; limo_velo_amd.ndt has the helpers)
     def _ndt_points(self, points):

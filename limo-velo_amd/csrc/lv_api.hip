@@ -12,6 +12,7 @@
 #include "lv_maptools.hpp"
 #include "lv_place.hpp"
 #include "lv_graph.hpp"
+#include "lv_traj.hpp"
 #include "lv_ndt.hpp"
 #include "lv_mcl_filter.hpp"
 #include "lv_elevation.hpp"
@@ -47,6 +48,7 @@ struct lv_ctx {
     MapTools<MapRebuild<MapStore>> tools;   // the tools on the point map, their buffers and their order against inserts and rebuilds (lv_maptools.hpp)
     PlaceStore place;   // lv_place_*: the place database and its buffers (lv_place.hip)
     GraphStore graph;   // lv_graph_*: the pose graph and the solver's vectors (lv_graph.hip); nothing allocated before lv_graph_set
+    TrajStore traj;     // lv_traj_*: the trajectory's knots, their interval records and the staging of a register call (lv_traj.hip); nothing allocated before lv_traj_set
     NdtStore ndt;       // lv_ndt_*: the target's Gaussians and the buffers of an alignment (lv_ndt.hip); nothing allocated before the first build
     MclFilterStore mclf;   // lv_occ_mcl_filter_*: the resident particles and their buffers (lv_mcl_filter.hip); nothing allocated before lv_occ_mcl_filter_set
     VolumeTools vol;    // lv_occ_*, lv_tsdf_*, lv_volume_*: the two volumes, what is built from them and what keeps those honest (lv_volumes.hpp)
@@ -254,6 +256,7 @@ void lv_destroy(lv_ctx* c) {   // (also of a context lv_create gave up on part o
     c->tools.release();
     c->place.release();
     c->graph.release();
+    c->traj.release();
     c->ndt.release();
     c->mclf.release();
     c->elev.release();
@@ -643,6 +646,100 @@ int lv_graph_clear(lv_ctx* c) {
     LV_GRAPH_SET(c);
     c->graph.clear();
     return LV_OK;
+}
+
+// ---- Trajectory (lv_traj.hip)
+void lv_default_traj_smooth_params(lv_traj_smooth_params* p) { default_traj_smooth_params(p); }
+void lv_default_traj_register_params(lv_traj_register_params* p) { default_traj_register_params(p); }
+
+#define LV_TRAJ_SET(c) LV_REQUIRE((c)->traj.set, LV_ESTATE, "no trajectory: call lv_traj_set first")
+
+int lv_traj_set(lv_ctx* c, const lv_traj_knot* knots, size_t n) {
+    if (int rc = traj_check(knots, n, "trajectory")) return rc;   // (before the context: "null context" comes last)
+    LV_CHECK_CTX(c);
+    return c->traj.assign(c->stream, knots, n);
+}
+
+int lv_traj_fetch(lv_ctx* c, lv_traj_knot* knots, size_t capacity) {
+    if (!knots) { set_error("null knots"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    if (capacity < c->traj.n) { set_error("capacity %zu < %zu knots", capacity, c->traj.n); return LV_EINVAL; }
+    return c->traj.fetch(c->stream, knots);
+}
+
+int lv_traj_get_info(lv_ctx* c, lv_traj_info* info) {
+    if (!info) { set_error("null info"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *info = c->traj.info;
+    return LV_OK;
+}
+
+int lv_traj_clear(lv_ctx* c) {
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    c->traj.clear();
+    return LV_OK;
+}
+
+int lv_traj_sample(lv_ctx* c, const double* times, size_t n, int extrapolate, lv_graph_pose* out, uint8_t* status) {
+    if (n > TRAJ_MAX_ITEMS) { set_error("trajectory sample: n = %zu above 2^28", n); return LV_EINVAL; }
+    if (n && !times) { set_error("trajectory sample: null times"); return LV_EINVAL; }
+    if (int rc = traj_extrapolate_ok(extrapolate)) return rc;
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    return c->traj.sample(c->stream, times, n, extrapolate, out, status);
+}
+
+int lv_traj_smooth(lv_ctx* c, const lv_traj_smooth_params* params, const uint8_t* fixed) {
+    if (int rc = traj_smooth_params_ok(params)) return rc;
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    return c->traj.smooth(c->stream, *params, fixed);
+}
+
+int lv_traj_correct(lv_ctx* c, const lv_traj_knot* corr, size_t m) {
+    if (int rc = traj_check(corr, m, "correction")) return rc;
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    return c->traj.correct(c->stream, corr, m);
+}
+
+int lv_traj_register(lv_ctx* c, const lv_traj_register_params* params, const void* pts, size_t stride, size_t time_offset, size_t n, float* out,
+                     uint8_t* status, uint64_t stats[4]) {
+    lv_traj_register_params prm;
+    default_traj_register_params(&prm);
+    if (params) prm = *params;
+    if (int rc = traj_register_params_ok(&prm)) return rc;
+    if (int rc = traj_register_layout_ok(pts, stride, time_offset, n)) return rc;
+    LV_CHECK_CTX(c);
+    LV_TRAJ_SET(c);
+    if (prm.frame == LV_TRAJ_FRAME_AT)
+        if (int rc = traj_frame_time_ok(prm.frame_time, c->traj.info.t_first, c->traj.info.t_last)) return rc;
+    return c->traj.register_host(c->stream, prm, pts, stride, time_offset, n, out, status, stats);
+}
+
+int lv_traj_register_cloud(lv_ctx* c, const lv_traj_register_params* params, double t1, double t2, float* out, uint8_t* status, size_t capacity,
+                           size_t* n, uint64_t stats[4]) {
+    lv_traj_register_params prm;
+    default_traj_register_params(&prm);
+    if (params) prm = *params;
+    if (int rc = traj_register_params_ok(&prm)) return rc;
+    if (!n) { set_error("trajectory register: null n"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    *n = 0;
+    LV_TRAJ_SET(c);
+    if (prm.frame == LV_TRAJ_FRAME_AT)
+        if (int rc = traj_frame_time_ok(prm.frame_time, c->traj.info.t_first, c->traj.info.t_last)) return rc;
+    uint32_t lo = 0, hi = 0;
+    if (int rc = c->cloud.window(c->stream, t1, t2, &lo, &hi)) return rc;   // (what lv_cloud_fetch cuts)
+    const size_t cnt = hi - lo;
+    *n = cnt;
+    if (!out) return LV_OK;
+    if (capacity < cnt) { set_error("capacity %zu too small for %zu points", capacity, cnt); return LV_EINVAL; }
+    const CloudPoint* first = c->cloud.d_buf + lo;
+    const TrajPoints in{&first->x, &first->time, (uint32_t)(sizeof(CloudPoint) / sizeof(float)), (uint32_t)(sizeof(CloudPoint) / sizeof(double))};
+    return c->traj.register_device(c->stream, prm, in, cnt, out, status, stats);
 }
 
 int lv_map_relinearise(lv_ctx* c) {
@@ -1040,6 +1137,7 @@ int lv_set_option(lv_ctx* c, const char* name, int value) {
     LV_CHECK_CTX(c);
     if (!name) { set_error("null argument"); return LV_EINVAL; }
     if (int rb = c->upd.busy("lv_set_option")) return rb;
+    if (!std::strcmp(name, "traj_tile")) { c->traj.tile = value != 0; return LV_OK; }   // (the trajectory stands beside the update's table)
     return Knobs<lv_ctx>::set_option(*c, name, value);   // (the table: lv_knobs.hpp)
 }
 

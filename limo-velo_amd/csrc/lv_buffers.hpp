@@ -1,7 +1,7 @@
 // lv_buffers.hpp — the host-side buffers of the map, scan and cloud stores (MapStore, ScanStore, CloudStore: lv_stores.hpp), of the
 // context (d_obs, h_states_ring) and of the map tools (QueryStore, BatchStore, VisStore, PaintStore, PlaceStore, SurfaceStore,
 // ClusterStore, PlaneStore, OccStore, DistStore, PlanStore, FrontierStore, RayStore, ElevStore, RolloutStore, MclStore, TsdfStore,
-// LatticeStore, GraphStore, NdtStore, MclFilterStore): a device buffer and its pinned twin that know their capacity, a stage for packed
+// LatticeStore, GraphStore, TrajStore, NdtStore, MclFilterStore): a device buffer and its pinned twin that know their capacity, a stage for packed
 // points, a record of four counters, and the grid size of a one-lane-per-item launch.  Host code only; tests/emu/buffers_emu.cpp
 // compiles it with g++ against tests/emu/hip/hip_runtime.h and tests/test_buffers_host.py holds it to the rules of DESIGN.md
 // "Host-side buffers".
