@@ -1232,6 +1232,7 @@ typedef struct lv_tsdf_params {
     int max_weight;                          /* 1..2^18 */
     int carve;                               /* 0 or 1 */
 } lv_tsdf_params;
+/* reserved: 1 when the built mesh carries vertex colours ("Colour layer": the layer was present at the build), otherwise 0 */
 typedef struct lv_mesh_info { int built, stale, min_weight, reserved; uint64_t vertices, triangles, active_cells, refused_edges; } lv_mesh_info;
 /* Defaults: the occupancy grid's footprint (0.2 m voxels, 512 x 512 x 64, origin -51.2, -51.2, -3.2, ranges 1..80 m),
  * trunc_cells 3, max_weight 10000, carve 0. */
@@ -1261,6 +1262,63 @@ int  lv_tsdf_mesh_fetch(lv_ctx* ctx, float* xyz, int32_t* sub, uint32_t* tri, si
 int  lv_tsdf_mesh_info(lv_ctx* ctx, lv_mesh_info* out);
 /* Frees the mesh. */
 int  lv_tsdf_mesh_clear(lv_ctx* ctx);
+
+/* ---- Colour layer ------------------------------------------------------------------------------------------
+ * A colour layer beside the TSDF, as Voxblox and nvblox carry one, and vertex colours for the mesh: the voxels near the surface
+ * take the colour of the camera images that see them (the reference's TODO "Add vision buffer and ability to paint the map's
+ * points", for the surface product).  The views and their parameters are lv_camera_view and lv_paint_params of "Map painting".
+ * Integer arithmetic after one float step (the projection and the sample): bitwise reproducible, independent of scheduling.
+ *   layer      per voxel four uint32: C[0..2], the sums of R, G, B, and the colour weight Wc.  Wc = 0: never coloured.  Always
+ *              C[c] <= 255 * Wc and Wc <= 65535.  16 bytes per voxel, allocated by the first lv_colour_integrate or
+ *              lv_colour_load, never before: a context that calls neither allocates nothing for it (lv_colour_info: present = 0).
+ *   candidates a voxel is a candidate iff W >= min_weight and |S| <= (int64)band * W; band in sub-units, 1..T; min_weight >= 1.
+ *              Judged once per call, against the volume as the call finds it.
+ *   centre     per axis p_a = origin_a + resolution * ((float)(256 * i_a + 128) / 256.0f), f32 and unfused, origin the volume's
+ *              present origin (after its shifts): the mesh's vertex in metres at v = 256 i + 128.
+ *   views      the candidates' centres are the point set of "Map painting" steps 1 to 6, unchanged: the depth gate, the
+ *              normalised radius, plumb_bob, the image bounds, the occlusion buffer filled by the candidates themselves with its
+ *              window-min, SEEN iff z - zbuf <= fmaxf(margin_abs, margin_rel * z), the bilinear sample s in f32.  blend must be 0
+ *              (LV_EINVAL otherwise); the limits on views and images are lv_map_paint's.
+ *   quantise   per seeing view and channel q = (uint32_t)(s + 0.5f), in 0..255.
+ *   accumulate per candidate n = the number of seeing views and dC[c] = the sum of their q: integer sums, so neither the order
+ *              of the views nor their split inside one call matters.
+ *   fold       every candidate with n > 0: Wn = Wc + n, Cn[c] = C[c] + dC[c]; if Wn > max_weight (1..65535) then
+ *              C[c] = (uint32)(((uint64)Cn[c] * max_weight) / Wn) and Wc = max_weight, otherwise C = Cn and Wc = Wn.
+ *   voxel      colour of a voxel: Wc > 0: c = (2 * C[c] + Wc) / (2 * Wc) by integer division, alpha 255; Wc = 0: 0, 0, 0, 0.
+ *   vertex     colour of a mesh vertex: of the 8 corner voxels of its active cell those with Wc > 0, k their number and sum[c] the
+ *              sum of their voxel colours; k > 0: (2 * sum[c] + k) / (2 * k), alpha 255; k = 0: 0, 0, 0, 0.  Computed inside
+ *              lv_tsdf_mesh_build when the layer is present: a snapshot with the mesh, in vertex order.
+ *   stats      candidates, (voxel, view) pairs that pass steps 1 to 3, pairs seen, voxels with n > 0.
+ * Order of judgement as for the TSDF calls: the arguments before the context (LV_EINVAL, nothing written; the null context last),
+ * then LV_ESTATE before lv_tsdf_configure, then what is the call's own (band > T: LV_EINVAL).  Without a layer lv_colour_fetch and
+ * lv_colour_query give LV_ESTATE and lv_colour_clear is LV_OK and does nothing; lv_mesh_colours gives LV_ESTATE without a mesh
+ * or with a mesh built while no layer was present.  lv_colour_integrate (whatever it returns once its arguments hold),
+ * lv_colour_load and lv_colour_clear set a built mesh's stale = 1.  lv_tsdf_load and lv_tsdf_clear zero the layer (colours of
+ * another volume mean nothing), lv_tsdf_integrate leaves it alone, lv_tsdf_configure and lv_destroy free it, and
+ * lv_volume_recentre(LV_VOLUME_SURFACE) moves it with S and W: new voxel (i, j, k) holds what (i + d) held or four zeros, no
+ * surviving bit changes, a zero shift touches nothing.
+ * Known limits: a voxel behind a wall thinner than the band takes the colour of a camera that looks at the wall's back, and only
+ * the candidates occlude: what the TSDF has not observed hides nothing. */
+typedef struct lv_colour_params { lv_paint_params view; int band; int min_weight; int max_weight; int reserved; } lv_colour_params;
+/* coloured: the voxels with Wc > 0, counted at the call.  (A struct tag without a typedef: the call below has the name.) */
+struct lv_colour_info { int present, reserved; uint64_t voxels, coloured; };
+/* Defaults: lv_default_paint_params but zbuf_scale 8, window 1, margin_abs 0.5; band 256, min_weight 1, max_weight 64. */
+void lv_default_colour_params(lv_colour_params* p);
+/* n_views 1..32.  stats (may be NULL) as above. */
+int  lv_colour_integrate(lv_ctx* ctx, const lv_camera_view* views, size_t n_views, const lv_colour_params* p, uint64_t stats[4]);
+/* sums: 4 uint32 per voxel (C[0], C[1], C[2], Wc); rgba: the voxel colours, 4 bytes per voxel.  Either may be NULL, not both;
+ * capacity (voxels) below nx * ny * nz: LV_EINVAL. */
+int  lv_colour_fetch(lv_ctx* ctx, uint32_t* sums, uint8_t* rgba, size_t capacity);
+/* Replaces the layer.  n (voxels) must equal nx * ny * nz and every voxel keep the invariants above (LV_EINVAL otherwise, layer
+ * unchanged). */
+int  lv_colour_load(lv_ctx* ctx, const uint32_t* sums, size_t n);
+/* The voxel colour of the voxel each world point falls in (quantised as lv_tsdf_query does); 0, 0, 0, 0 outside the grid. */
+int  lv_colour_query(lv_ctx* ctx, const void* pts, size_t stride, size_t n, uint8_t* rgba);
+/* Every voxel back to never coloured; keeps the allocation. */
+int  lv_colour_clear(lv_ctx* ctx);
+int  lv_colour_info(lv_ctx* ctx, struct lv_colour_info* out);
+/* rgba: 4 bytes per vertex of the mesh last built, in vertex order; cap_vertices below the vertex count: LV_EINVAL. */
+int  lv_mesh_colours(lv_ctx* ctx, uint8_t* rgba, size_t cap_vertices);
 
 /* ---- Rolling volumes -------------------------------------------------------------------------------------
  * The occupancy grid and the TSDF volume follow the robot (costmap_2d's rolling_window, the local maps of Voxblox / nvblox, the

@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "lv_occ_mcl_filter_get", "lv_occ_mcl_filter_info", "lv_occ_mcl_filter_clear",
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
+    "lv_default_colour_params", "lv_colour_integrate", "lv_colour_fetch", "lv_colour_load", "lv_colour_query", "lv_colour_clear",
+    "lv_colour_info", "lv_mesh_colours",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
     "lv_default_observation", "lv_observe", "lv_observe_results",
     "lv_default_graph_params", "lv_graph_set", "lv_graph_optimise", "lv_graph_fetch", "lv_graph_chi2", "lv_graph_warp_points",
@@ -638,6 +640,26 @@ TSDF_ARGTYPES = {
 }
 
 
+class ColourParams(C.Structure):  # lv_colour_params
+    _fields_ = [("view", LvPaintParams), ("band", C.c_int), ("min_weight", C.c_int), ("max_weight", C.c_int), ("reserved", C.c_int)]
+
+
+class ColourInfo(C.Structure):  # struct lv_colour_info
+    _fields_ = [("present", C.c_int), ("reserved", C.c_int), ("voxels", C.c_uint64), ("coloured", C.c_uint64)]
+
+
+# ctypes signatures of the colour layer (include/limovelo_hip.h "Colour layer"; tests/test_colour_abi.py)
+COLOUR_ARGTYPES = {
+    "lv_colour_integrate": [C.c_void_p, C.POINTER(LvCameraView), C.c_size_t, C.POINTER(ColourParams), C.POINTER(C.c_uint64)],
+    "lv_colour_fetch": [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_size_t],
+    "lv_colour_load": [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t],
+    "lv_colour_query": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8)],
+    "lv_colour_clear": [C.c_void_p],
+    "lv_colour_info": [C.c_void_p, C.POINTER(ColourInfo)],
+    "lv_mesh_colours": [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t],
+}
+
+
 LV_VOLUME_OCC, LV_VOLUME_SURFACE = 0, 1
 VOLUME_SHIFT_LIMIT = 1 << 20
 
@@ -901,6 +923,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_mcl_resample_params.argtypes = [C.POINTER(MclResampleParams)]
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
+        lib.lv_default_colour_params.restype = None
+        lib.lv_default_colour_params.argtypes = [C.POINTER(ColourParams)]
         lib.lv_default_occ_mark_params.restype = None
         lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
         lib.lv_default_observation.restype = None
@@ -918,7 +942,7 @@ def load_library() -> C.CDLL:
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **VOLUME_ARGTYPES,
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **COLOUR_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -1165,6 +1189,17 @@ def default_tsdf_params(**kw) -> TsdfParams:
             p.origin[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_colour_params(**kw) -> ColourParams:
+    """lv_default_colour_params; a keyword that names a field of lv_paint_params (zbuf_scale, window, margin_abs, ...) sets it in
+    the embedded `view`."""
+    p = ColourParams()
+    load_library().lv_default_colour_params(C.byref(p))
+    own = {f for f, _ in ColourParams._fields_}
+    for k, v in kw.items():
+        setattr(p if k in own else p.view, k, v)
     return p
 
 
@@ -2000,6 +2035,62 @@ class Context:
 
     def tsdf_mesh_clear(self):
         self._check(self.lib.lv_tsdf_mesh_clear(self.h))
+
+    # --- colour layer (include/limovelo_hip.h "Colour layer")
+    def colour_integrate(self, views, params: ColourParams | None = None) -> np.ndarray:
+        """lv_colour_integrate over views = [frame dict (camera_view)] (1..32, one call); returns stats [4] uint64: candidates,
+        (voxel, view) pairs projected, pairs seen, voxels coloured by the call."""
+        p = params if params is not None else default_colour_params()
+        arr = (LvCameraView * max(len(views), 1))()
+        keep = []
+        for i, f in enumerate(views):
+            arr[i], img = camera_view(f)
+            keep.append(img)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_colour_integrate(self.h, arr, C.c_size_t(len(views)), C.byref(p), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def colour_fetch(self, sums=True, rgba=False) -> dict:
+        """dict of the wanted arrays: sums [nz, ny, nx, 4] uint32 (C[0..2], Wc), rgba [nz, ny, nx, 4] uint8 (the voxel colours)."""
+        p = self.tsdf_params()
+        out = {}
+        if sums:
+            out["sums"] = np.zeros((p.nz, p.ny, p.nx, 4), np.uint32)
+        if rgba:
+            out["rgba"] = np.zeros((p.nz, p.ny, p.nx, 4), np.uint8)
+        self._check(self.lib.lv_colour_fetch(self.h, out["sums"].ctypes.data_as(C.POINTER(C.c_uint32)) if sums else None,
+                                             out["rgba"].ctypes.data_as(C.POINTER(C.c_uint8)) if rgba else None, C.c_size_t(p.nx * p.ny * p.nz)))
+        return out
+
+    def colour_load(self, sums):
+        a = np.ascontiguousarray(sums, np.uint32)
+        if a.size % 4:
+            raise ValueError("colour_load: four values per voxel")
+        self._check(self.lib.lv_colour_load(self.h, a.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(a.size // 4)))
+
+    def colour_query(self, pts) -> np.ndarray:
+        """rgba [n, 4] uint8 of the voxel each world point falls in; 0, 0, 0, 0 outside the grid and where never coloured."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        out = np.zeros((n, 4), np.uint8)
+        self._check(self.lib.lv_colour_query(self.h, a.ctypes.data_as(C.c_void_p), C.c_size_t(stride), C.c_size_t(n),
+                                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def colour_clear(self):
+        self._check(self.lib.lv_colour_clear(self.h))
+
+    def colour_info(self) -> ColourInfo:
+        out = ColourInfo()
+        self._check(self.lib.lv_colour_info(self.h, C.byref(out)))
+        return out
+
+    def mesh_colours(self) -> np.ndarray:
+        """rgba [V, 4] uint8 of the mesh last built, in vertex order (LvError where it carries none)."""
+        i = self.tsdf_mesh_info()
+        nv = int(i.vertices) if i.built else 0
+        out = np.zeros((max(nv, 1), 4), np.uint8)
+        self._check(self.lib.lv_mesh_colours(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(nv)))
+        return out[:nv]
 
     # --- rolling volumes (include/limovelo_hip.h "Rolling volumes")
     def volume_recentre(self, volume: int, shift) -> np.ndarray:

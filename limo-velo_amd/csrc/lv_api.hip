@@ -1757,6 +1757,50 @@ int lv_tsdf_mesh_fetch(lv_ctx* c, float* xyz, int32_t* sub, uint32_t* tri, size_
 int lv_tsdf_mesh_info(lv_ctx* c, lv_mesh_info* out) { LV_CHECK_CTX(c); return c->vol.mesh_info(out); }
 int lv_tsdf_mesh_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.mesh_clear(c->stream); }
 
+// ---- Colour layer (lv_colour.hip): what needs no context is judged before it, the rest in VolumeTools
+void lv_default_colour_params(lv_colour_params* p) { default_colour_params(p); }
+
+int lv_colour_integrate(lv_ctx* c, const lv_camera_view* views, size_t n_views, const lv_colour_params* p, uint64_t stats[4]) {
+    PaintRule q;
+    PaintCam cams[PAINT_MAX_VIEWS];
+    if (int rc = colour_rule(views, n_views, p, &q, cams)) return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.colour_integrate(c->stream, views, cams, q, *p, stats);
+}
+
+int lv_colour_fetch(lv_ctx* c, uint32_t* sums, uint8_t* rgba, size_t capacity) {
+    if (!sums && !rgba) { set_error("lv_colour_fetch: sums and rgba are both null"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.colour_fetch(c->stream, sums, rgba, capacity);
+}
+
+int lv_colour_load(lv_ctx* c, const uint32_t* sums, size_t n) {
+    if (!sums) { set_error("lv_colour_load: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.colour_load(c->stream, sums, n);
+}
+
+int lv_colour_query(lv_ctx* c, const void* pts, size_t stride, size_t n, uint8_t* rgba) {
+    if (n && (!pts || !rgba || stride < 12)) { set_error("lv_colour_query: bad point array (stride %zu) or null output", stride); return LV_EINVAL; }
+    if (n > 0xFFFFFFF0ull / 4) { set_error("lv_colour_query: too many points"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.colour_query(c->stream, pts, stride, n, rgba);
+}
+
+int lv_colour_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.colour_clear(c->stream); }
+
+int lv_colour_info(lv_ctx* c, struct lv_colour_info* out) {
+    if (!out) { set_error("lv_colour_info: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.colour_info(c->stream, out);
+}
+
+int lv_mesh_colours(lv_ctx* c, uint8_t* rgba, size_t cap_vertices) {
+    if (!rgba) { set_error("lv_mesh_colours: null argument"); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.mesh_colours(c->stream, rgba, cap_vertices);
+}
+
 // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)
 int lv_volume_recentre(lv_ctx* c, int volume, const int32_t shift[3], uint64_t stats[4]) {
     if (volume != LV_VOLUME_OCC && volume != LV_VOLUME_SURFACE) { set_error("lv_volume_recentre: volume %d: LV_VOLUME_OCC or LV_VOLUME_SURFACE", volume); return LV_EINVAL; }

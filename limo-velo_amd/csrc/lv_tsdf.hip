@@ -15,6 +15,10 @@
 // calls and holds 8 bytes per voxel, so nothing is allocated: tsdf_shift_gather_kernel writes (S, W) of every voxel's source
 // cell into its scratch word, two voxels and one 16-byte store per lane (an exposed voxel's word is 0, which is S = 0, W = 0),
 // and tsdf_shift_unpack_kernel moves the words into S and W, four voxels per lane, and zeroes them again.
+// The colour layer (lv_colour.hip) is a member of the store: clear() and load() zero it, recentre() moves it through a second buffer
+// of its own, mesh_build() takes the vertex colours from it, release() frees it.  A store without one does none of that.
+#include <utility>
+
 #include "lv_tsdf.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -256,7 +260,7 @@ __global__ __launch_bounds__(256) void tsdf_face_emit_kernel(const int32_t* __re
 }  // namespace
 
 void TsdfStore::mesh_release() {
-    mesh.d_xyz.release(); mesh.d_sub.release(); mesh.d_tri.release();
+    mesh.d_xyz.release(); mesh.d_sub.release(); mesh.d_tri.release(); mesh.d_rgba.release();
     mesh = TsdfMesh();
 }
 
@@ -264,6 +268,7 @@ void TsdfStore::release() {
     mesh_release();
     d_S.release(); d_W.release(); d_scratch.release(); stats.release(); pts.release(); d_out.release(); d_wout.release();
     d_flag.release(); d_vid.release(); d_fcnt.release(); d_foff.release(); d_tmp.release();
+    colour.release();
     *this = TsdfStore();
 }
 
@@ -291,6 +296,7 @@ int TsdfStore::configure(hipStream_t stream, const lv_tsdf_params& p) {
 int TsdfStore::clear(hipStream_t stream) {
     LV_HIP(hipMemsetAsync(d_S, 0, n_vox * sizeof(int32_t), stream));
     LV_HIP(hipMemsetAsync(d_W, 0, n_vox * sizeof(int32_t), stream));
+    if (colour.present) return colour_clear(stream);   // (waits for the stream)
     LV_HIP(hipStreamSynchronize(stream));
     return LV_OK;
 }
@@ -362,21 +368,29 @@ int TsdfStore::fetch(hipStream_t stream, int32_t* S, int32_t* W, float* metres) 
 int TsdfStore::load(hipStream_t stream, const int32_t* S, const int32_t* W) {
     LV_HIP(hipMemcpyAsync(d_S, S, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemcpyAsync(d_W, W, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (colour.present) return colour_clear(stream);   // (colours of another volume mean nothing; waits for the stream)
     LV_HIP(hipStreamSynchronize(stream));
     return LV_OK;
 }
 
 int TsdfStore::recentre(hipStream_t stream, const int32_t d[3], const int32_t s_new[3], const float origin_new[3], uint64_t out[4]) {
     int rc = stats.zero(stream);
+    if (!rc && colour.present) rc = colour.d_next.need(4 * n_vox);   // (before anything moves: a call that fails has changed nothing)
     if (rc) return rc;
     const GridDims g{grid.occ.nx, grid.occ.ny, grid.occ.nz};
     hipLaunchKernelGGL(tsdf_shift_gather_kernel, dim3(grid_stride_blocks((n_vox + 1) / 2)), dim3(256), 0, stream, d_S.p, d_W.p, d_scratch.p, g, d[0], d[1], d[2],
                        (uint32_t)n_vox, stats.d.p);
     hipLaunchKernelGGL(tsdf_shift_unpack_kernel, dim3(blocks_of((n_vox + 3) / 4)), dim3(256), 0, stream, d_S.p, d_W.p, d_scratch.p, (uint32_t)n_vox);
     LV_HIP(hipGetLastError());
+    if (colour.present) rc = colour_shift(stream, d);
+    if (rc) return rc;
     uint64_t st[4];
     rc = stats.read(stream, st);   // (waits for the stream)
     if (rc) return rc;
+    if (colour.present) {   // the moved layer takes the old one's place
+        std::swap(colour.d_sums, colour.d_next);
+        colour.d_next.release();
+    }
     if (out) {
         out[0] = (uint64_t)n_vox - st[1];   // a voxel is kept or exposed
         out[1] = st[1];
@@ -392,7 +406,7 @@ int TsdfStore::recentre(hipStream_t stream, const int32_t d[3], const int32_t s_
 }
 
 // exclusive sum of in[0 .. n] into out[0 .. n] (n + 1 items: out[n] is the total), then the total to the host
-static int tsdf_scan(hipStream_t stream, DevBuf<void>& tmp, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total) {
+int tsdf_scan(hipStream_t stream, DevBuf<void>& tmp, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total) {
     size_t bytes = 0;
     LV_HIP((hipError_t)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)(n + 1), stream));
     const int rc = tmp.need(bytes);
@@ -434,6 +448,10 @@ int TsdfStore::mesh_build(hipStream_t stream, int min_weight, uint64_t counts[4]
             hipLaunchKernelGGL(tsdf_vertex_kernel, dim3(blocks_of(n_vox)), dim3(256), 0, stream, d_S.p, d_W.p, g, nv, min_weight, d_flag.p, d_vid.p,
                                grid.occ.origin[0], grid.occ.origin[1], grid.occ.origin[2], grid.occ.resolution, mesh.d_sub.p, mesh.d_xyz.p);
             LV_HIP(hipGetLastError());
+            if (colour.present) {
+                rc = colour_vertices(stream, d_flag.p, d_vid.p, n_vert);
+                if (rc) return rc;
+            }
         }
         if (n_quad) {
             rc = mesh.d_tri.need(6 * (size_t)n_quad);
@@ -451,6 +469,7 @@ int TsdfStore::mesh_build(hipStream_t stream, int min_weight, uint64_t counts[4]
         return built;
     }
     mesh.built = true;
+    mesh.coloured = colour.present;
     mesh.stale = 0;
     mesh.min_weight = min_weight;
     mesh.counts[0] = n_vert;

@@ -10,6 +10,7 @@
 #pragma once
 
 #include "lv_occupancy.hpp"
+#include "lv_rules.hpp"   // PaintCam, PaintRule: what the colour layer's integrate takes
 
 namespace lv {
 
@@ -256,6 +257,28 @@ struct TsdfMesh {
     DevBuf<float> d_xyz;                 // 3 per vertex
     DevBuf<int32_t> d_sub;               // 3 per vertex
     DevBuf<uint32_t> d_tri;              // 3 per triangle
+    bool coloured = false;               // built while the colour layer was present: d_rgba holds the vertex colours
+    DevBuf<uint32_t> d_rgba;             // one packed r, g, b, a per vertex (bytes in that order)
+};
+
+// The colour layer of the volume ("Colour layer"; rule in lv_colour.hpp, kernels in lv_colour.hip) and the buffers of
+// lv_colour_integrate.  Nothing is allocated before the first lv_colour_integrate or lv_colour_load.
+struct ColourLayer {
+    bool present = false;
+    DevBuf<uint32_t> d_sums;             // 4 per voxel by grid_at: the sums of R, G, B and the colour weight Wc
+    DevBuf<uint32_t> d_next;             // recentre's second buffer, freed when the move is through
+    DevBuf<uint32_t> d_bcnt, d_boff;     // candidates per workgroup of the compaction and their exclusive sum
+    DevBuf<uint32_t> d_list;             // the candidates' voxel indices in linear order
+    DevBuf<uint32_t> d_rgba;             // lv_colour_fetch's and lv_colour_query's packed colours
+    PinBuf<uint8_t> h_raw;               // the staged images, the views, the texels, the occlusion cells: as PaintStore's
+    PinBuf<PaintCam> h_cams;             // PAINT_MAX_VIEWS entries
+    DevBuf<uint8_t> d_raw;
+    DevBuf<PaintCam> d_cams;
+    DevBuf<uint32_t> d_tex, d_cell, d_tmp;
+    void release() {
+        release_all(d_sums, d_next, d_bcnt, d_boff, d_list, d_rgba, h_raw, h_cams, d_raw, d_cams, d_tex, d_cell, d_tmp);
+        present = false;
+    }
 };
 
 // The volume of a context and the buffers of its calls.  Nothing is allocated before configure().
@@ -275,6 +298,7 @@ struct TsdfStore {
     TsdfMesh mesh;
     DevBuf<uint32_t> d_flag, d_vid, d_fcnt, d_foff;   // the build's per-voxel arrays (n_vox + 1 each), freed when it ends
     DevBuf<void> d_tmp;                       // hipcub scratch
+    ColourLayer colour;                       // the colour layer: zeroed by clear() and load(), moved by recentre(), read by mesh_build(), freed by release()
 
     int configure(hipStream_t stream, const lv_tsdf_params& p);
     int clear(hipStream_t stream);
@@ -288,6 +312,22 @@ struct TsdfStore {
     int mesh_fetch(hipStream_t stream, float* xyz, int32_t* sub, uint32_t* tri);
     void mesh_release();
     void release();
+
+    // ---- the colour layer (lv_colour.hip).  cams, q: paint_rule's.  All of them wait for the stream.
+    int colour_ensure(hipStream_t stream);   // allocates the layer, all zero, where it is not present
+    int colour_integrate(hipStream_t stream, const lv_camera_view* views, const PaintCam* cams, const PaintRule& q, int band, int min_weight,
+                         int max_weight, uint64_t out[4]);
+    int colour_fetch(hipStream_t stream, uint32_t* sums, uint8_t* rgba);
+    int colour_load(hipStream_t stream, const uint32_t* sums);
+    int colour_query(hipStream_t stream, const void* pts, size_t stride, size_t n, uint8_t* rgba);
+    int colour_clear(hipStream_t stream);
+    int colour_count(hipStream_t stream, uint64_t* coloured);
+    int colour_shift(hipStream_t stream, const int32_t d[3]);   // recentre's part: gathers into colour.d_next (the caller swaps)
+    int colour_vertices(hipStream_t stream, const uint32_t* flag, const uint32_t* vid, uint32_t n_vert);   // mesh_build's part
+    int mesh_colours(hipStream_t stream, uint8_t* rgba);
 };
+
+// exclusive sum of in[0 .. n] into out[0 .. n] (n + 1 items: out[n] is the total), then the total to the host (lv_tsdf.hip)
+int tsdf_scan(hipStream_t stream, DevBuf<void>& tmp, const uint32_t* in, uint32_t* out, size_t n, uint32_t* total);
 
 }  // namespace lv

@@ -1,6 +1,6 @@
 // lv_volumes.hpp — the volume tools of a context: the occupancy grid, what is built from it (distance field, plan, frontier, the
 // rays' packed states), what runs on those (rollouts, localisation), the TSDF volume with its mesh, and the rolling of both
-// volumes.  lv_ctx holds one VolumeTools; every lv_occ_*, lv_tsdf_* and lv_volume_* entry point of lv_api.hip judges what it
+// volumes.  lv_ctx holds one VolumeTools; every lv_occ_*, lv_tsdf_*, lv_colour_* and lv_volume_* entry point of lv_api.hip judges what it
 // judges before the context, checks the context, and makes one call here.  Host code only: tests/emu/volumes_emu.cpp compiles
 // it with g++ against tests/emu/hip/hip_runtime.h and its own stand-ins for the stores' member functions, and
 // tests/test_volumes_host.py holds it to the rules below.
@@ -39,6 +39,16 @@
 //   lv_tsdf_integrate, lv_tsdf_load (after    | before the store call                       | SURFACE EDIT: mesh.stale = 1
 //     tsdf_check_volume), lv_tsdf_clear       |                                             |   where built
 //   lv_volume_recentre (SURFACE)              | after success, non-zero shift               |
+//   ------------------------------------------+---------------------------------------------+---------------------------------
+//   lv_colour_integrate (after its argument   | before the store call, whatever it returns  | COLOUR EDIT: mesh.stale = 1
+//     checks), lv_colour_load (after its      |                                             |   where built
+//     value check), lv_colour_clear (with a   |                                             |
+//     layer)                                  |                                             |
+//
+// The colour layer lives inside TsdfStore, which looks after it in its own calls: load() and clear() zero it (colours of another
+// volume mean nothing), integrate() leaves it alone, configure() and release() free it, recentre() moves it with S and W (new
+// voxel (i, j, k) holds what (i + d) held, or four zeros; no surviving bit changes; a zero shift touches nothing), mesh_build()
+// reads it for the vertex colours.  No call of the tables above gains a store call for it.
 //
 // A grid edit does not touch the plan: the plan shows the FIELD, and the field says of itself that it is stale.  In the same way
 // a field edit or a grid edit does not touch the lattice: it shows the PLAN.
@@ -56,12 +66,16 @@
 //   rollout   GRID, PLAN, a planar plan; with a footprint FIELD, then a planar field of the plan's nx, ny (all LV_ESTATE).
 //   mcl       GRID, FIELD.
 //   surface   every lv_tsdf_* call but lv_tsdf_configure: SURFACE, then its arguments.  lv_tsdf_mesh_fetch: SURFACE, MESH.
+//   colour    every lv_colour_* call and lv_mesh_colours: SURFACE, then what is its own.  _integrate: band <= T (LV_EINVAL).
+//             _fetch, _query: LAYER (LV_ESTATE), then the capacity.  _load: n and the values (LV_EINVAL).  _clear without a layer:
+//             LV_OK, nothing done.  lv_mesh_colours: MESH, a mesh built with the layer present (both LV_ESTATE), the capacity.
 //   rolling   lv_volume_recentre: the volume it names, then grid_shift_check (LV_EINVAL).  lv_volume_shift_info: nothing; a volume
 //             that is not configured and a product that is not built (or whose grid is not configured) report zeros.
 //   mark      GRID, then the box clipped to the grid (an empty one: LV_OK, zero stats, before the point map is looked at).
 #pragma once
 #include <cstring>
 
+#include "lv_colour.hpp"
 #include "lv_distance.hpp"
 #include "lv_frontier.hpp"
 #include "lv_lattice.hpp"
@@ -82,6 +96,7 @@ namespace lv {
 #define LV_FRONTIER_BUILT LV_REQUIRE(frontier.built, LV_ESTATE, "no frontier: call lv_occ_frontier_build first")
 #define LV_LATTICE_BUILT LV_REQUIRE(lattice.built, LV_ESTATE, "no lattice: call lv_occ_lattice_build first")
 #define LV_SURFACE_CONFIGURED LV_REQUIRE(tsdf.configured, LV_ESTATE, "no TSDF volume: call lv_tsdf_configure first")
+#define LV_COLOUR_PRESENT LV_REQUIRE(tsdf.colour.present, LV_ESTATE, "no colour layer: call lv_colour_integrate or lv_colour_load first")
 
 // What lv_distance_info, lv_plan_info and lv_frontier_info share; true: s is built (the caller adds what is its own)
 template <class Info, class Store>
@@ -107,7 +122,8 @@ struct VolumeTools {
     RolloutStore rollout;     // lv_occ_rollout: its own buffers (lv_rollout.hip); nothing allocated before the first call
     MclStore mcl;             // lv_occ_mcl_weigh: its own buffers (lv_mcl.hip); nothing allocated before the first call
     LatticeStore lattice;     // lv_occ_lattice_*: the cost-to-go over (cell, heading) of the planar plan (lv_lattice.hip); nothing allocated before the first build
-    TsdfStore tsdf;           // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure
+    TsdfStore tsdf;           // lv_tsdf_*: the TSDF volume, its mesh and its buffers (lv_tsdf.hip); nothing allocated before lv_tsdf_configure.
+                              // lv_colour_*: its colour layer (lv_colour.hip); nothing allocated before the first lv_colour_integrate / _load
 
     // ---- the table's four edits and its stamps
     void grid_edited() {
@@ -122,6 +138,9 @@ struct VolumeTools {
         if (lattice.built) lattice.stale = 1;
     }
     void surface_edited() {
+        if (tsdf.mesh.built) tsdf.mesh.stale = 1;
+    }
+    void colour_edited() {
         if (tsdf.mesh.built) tsdf.mesh.stale = 1;
     }
     // a product remembers the accumulated shift of what it was built from ("Rolling volumes"); hands rc on
@@ -544,6 +563,7 @@ struct VolumeTools {
         out->triangles = m.counts[1];
         out->active_cells = m.counts[2];
         out->refused_edges = m.counts[3];
+        out->reserved = m.coloured ? 1 : 0;
         return LV_OK;
     }
 
@@ -552,6 +572,66 @@ struct VolumeTools {
         LV_HIP(hipStreamSynchronize(stream));
         tsdf.mesh_release();
         return LV_OK;
+    }
+
+    // ---- Colour layer (lv_colour.hip).  Only these methods reach the store's colour members.  Their entry points have judged
+    // what needs no context: null arguments, the views and parameters (colour_rule), the point array.
+    int colour_integrate(hipStream_t stream, const lv_camera_view* views, const PaintCam* cams, const PaintRule& q, const lv_colour_params& p,
+                         uint64_t stats[4]) {
+        LV_SURFACE_CONFIGURED;
+        if (p.band > tsdf.grid.T) { set_error("lv_colour_integrate: band = %d: must be in 1..T = %d", p.band, tsdf.grid.T); return LV_EINVAL; }
+        colour_edited();
+        return tsdf.colour_integrate(stream, views, cams, q, p.band, p.min_weight, p.max_weight, stats);
+    }
+
+    int colour_fetch(hipStream_t stream, uint32_t* sums, uint8_t* rgba, size_t capacity) {
+        LV_SURFACE_CONFIGURED;
+        LV_COLOUR_PRESENT;
+        if (capacity < tsdf.n_vox) { set_error("lv_colour_fetch: room for nx * ny * nz = %zu voxels needed", tsdf.n_vox); return LV_EINVAL; }
+        return tsdf.colour_fetch(stream, sums, rgba);
+    }
+
+    int colour_load(hipStream_t stream, const uint32_t* sums, size_t n) {
+        LV_SURFACE_CONFIGURED;
+        if (n != tsdf.n_vox) { set_error("lv_colour_load: %zu voxels for a volume of %zu", n, tsdf.n_vox); return LV_EINVAL; }
+        const size_t bad = colour_check_layer(sums, n);
+        if (bad != n) {
+            set_error("lv_colour_load: voxel %zu: C = %u, %u, %u, Wc = %u: Wc <= 65535 and C <= 255 * Wc", bad, sums[4 * bad], sums[4 * bad + 1],
+                      sums[4 * bad + 2], sums[4 * bad + 3]);
+            return LV_EINVAL;
+        }
+        colour_edited();
+        return tsdf.colour_load(stream, sums);
+    }
+
+    int colour_query(hipStream_t stream, const void* pts, size_t stride, size_t n, uint8_t* rgba) {
+        LV_SURFACE_CONFIGURED;
+        LV_COLOUR_PRESENT;
+        return tsdf.colour_query(stream, pts, stride, n, rgba);
+    }
+
+    int colour_clear(hipStream_t stream) {
+        LV_SURFACE_CONFIGURED;
+        if (!tsdf.colour.present) return LV_OK;
+        colour_edited();
+        return tsdf.colour_clear(stream);
+    }
+
+    int colour_info(hipStream_t stream, struct lv_colour_info* out) {
+        LV_SURFACE_CONFIGURED;
+        *out = {};
+        out->voxels = tsdf.n_vox;
+        if (!tsdf.colour.present) return LV_OK;
+        out->present = 1;
+        return tsdf.colour_count(stream, &out->coloured);
+    }
+
+    int mesh_colours(hipStream_t stream, uint8_t* rgba, size_t cap_vertices) {
+        LV_SURFACE_CONFIGURED;
+        LV_REQUIRE(tsdf.mesh.built, LV_ESTATE, "no mesh: call lv_tsdf_mesh_build first");
+        LV_REQUIRE(tsdf.mesh.coloured, LV_ESTATE, "the mesh was built without a colour layer: call lv_tsdf_mesh_build after lv_colour_integrate");
+        if (cap_vertices < tsdf.mesh.counts[0]) { set_error("lv_mesh_colours: room for %llu vertices needed", (unsigned long long)tsdf.mesh.counts[0]); return LV_EINVAL; }
+        return tsdf.mesh_colours(stream, rgba);
     }
 
     // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip).  volume: LV_VOLUME_OCC or LV_VOLUME_SURFACE
@@ -607,5 +687,6 @@ struct VolumeTools {
 #undef LV_FRONTIER_BUILT
 #undef LV_LATTICE_BUILT
 #undef LV_SURFACE_CONFIGURED
+#undef LV_COLOUR_PRESENT
 
 }  // namespace lv

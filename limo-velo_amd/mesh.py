@@ -2,7 +2,8 @@
 gives a volume the footprint of an occupancy grid, integrate() fuses sweeps of any number, distance() reads the field in metres,
 build() returns the triangle mesh of the zero surface, save_ply() writes it (ASCII or binary little-endian), save() / load()
 keep the volume as an .npz next to occupancy.save_grid's grid, and recentre() / follow() move the volume's box with the robot
-(lv_volume_recentre, "Rolling volumes")."""
+(lv_volume_recentre, "Rolling volumes").  paint() colours the volume from camera frames ("Colour layer"), colour_params_for()
+picks its occlusion parameters for a camera, build(colours=True) and save_ply(colours=...) carry the vertex colours."""
 from __future__ import annotations
 
 import numpy as np
@@ -37,36 +38,78 @@ def distance(ctx, pts):
     return ctx.tsdf_query(pts)
 
 
-def build(ctx, min_weight: int = 1):
+def paint(ctx, frames, params=None) -> np.ndarray:
+    """lv_colour_integrate over frames (frame dicts as capi.camera_view takes them) of any number, 32 views per call in order; the
+    stats [4] uint64 summed: candidates (of every call), pairs projected, pairs seen, voxels coloured (once per call that did)."""
+    p = params if params is not None else capi.default_colour_params()
+    stats = np.zeros(4, np.uint64)
+    frames = list(frames)
+    for c0 in range(0, len(frames), MAX_VIEWS):
+        stats += ctx.colour_integrate(frames[c0:c0 + MAX_VIEWS], p)
+    return stats
+
+
+def colour_params_for(ctx, frame, nearest: float):
+    """lv_colour_params for frames like `frame` whose nearest surface is `nearest` metres away: the occlusion cells' window,
+    zbuf_scale * (2 * window + 1) pixels, covers the voxel pitch fx * resolution / nearest there, so that the voxels of a wall
+    leave no holes for those behind it to be seen through; margin_abs = 2.5 voxels; band = one voxel."""
+    res = float(ctx.tsdf_params().resolution)
+    pitch = float(frame["fx"]) * res / float(nearest)
+    window, scale = 1, 1
+    while scale * (2 * window + 1) < pitch:
+        if scale < 16:
+            scale += 1
+        elif window < 8:
+            window, scale = window + 1, 1
+        else:
+            break
+    return capi.default_colour_params(zbuf_scale=scale, window=window, margin_abs=2.5 * res, band=256)
+
+
+def build(ctx, min_weight: int = 1, colours: bool = False):
     """(vertices [V, 3] f32 metres, triangles [F, 3] uint32, counts [4] uint64) of the volume's zero surface over the voxels with
     weight >= min_weight; counts: vertices, triangles, active cells, edges refused for a missing cell.  Normals (the triangles'
-    winding) point towards where the sensor was."""
+    winding) point towards where the sensor was.  colours: a fourth item, the vertex colours [V, 4] uint8 r, g, b, a (alpha 0: no
+    coloured voxel round the vertex), which needs the colour layer (paint())."""
     counts = ctx.tsdf_mesh_build(min_weight)
     m = ctx.tsdf_mesh_fetch(xyz=True, sub=False, tri=True)
+    if colours:
+        return m["xyz"], m["tri"], counts, ctx.mesh_colours()
     return m["xyz"], m["tri"], counts
 
 
-def save_ply(path, vertices, triangles, binary: bool = True):
+def save_ply(path, vertices, triangles, binary: bool = True, colours=None):
     """A PLY of the mesh: vertices [V, 3] (float x y z) and triangles [F, 3] (list uchar int vertex_indices), binary little-endian
-    or ASCII."""
+    or ASCII.  colours ([V, 3] or [V, 4] uint8): uchar red green blue per vertex behind x y z."""
     v = np.asarray(vertices, np.float32).reshape(-1, 3)
     t = np.asarray(triangles).reshape(-1, 3)
     if len(t) and (t.min() < 0 or t.max() >= len(v)):
         raise ValueError("a triangle refers to a vertex that does not exist")
+    c = None
+    if colours is not None:
+        c = np.asarray(colours, np.uint8).reshape(len(v), -1)[:, :3]
     head = ("ply\nformat " + ("binary_little_endian" if binary else "ascii") + f" 1.0\nelement vertex {len(v)}\n"
-            "property float x\nproperty float y\nproperty float z\n" + f"element face {len(t)}\n"
+            "property float x\nproperty float y\nproperty float z\n" +
+            ("property uchar red\nproperty uchar green\nproperty uchar blue\n" if c is not None else "") + f"element face {len(t)}\n"
             "property list uchar int vertex_indices\nend_header\n")
     with open(path, "wb") as f:
         f.write(head.encode("ascii"))
-        if binary:
+        if binary and c is not None:
+            rec = np.empty(len(v), dtype=[("p", "<f4", 3), ("c", "u1", 3)])
+            rec["p"] = v
+            rec["c"] = c
+            f.write(rec.tobytes())
+        elif binary:
             f.write(v.astype("<f4").tobytes())
+        if binary:
             rec = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", 3)])
             rec["n"] = 3
             rec["i"] = t
             f.write(rec.tobytes())
         else:
-            for p in v:
-                f.write(("%.9g %.9g %.9g\n" % (p[0], p[1], p[2])).encode("ascii"))
+            for i, p in enumerate(v):
+                tail = "" if c is None else " %d %d %d" % (c[i, 0], c[i, 1], c[i, 2])
+                f.write(("%.9g %.9g %.9g%s\n" % (p[0], p[1], p[2], tail)).encode("ascii"))
             for q in t:
                 f.write(("3 %d %d %d\n" % (q[0], q[1], q[2])).encode("ascii"))
 
@@ -85,7 +128,8 @@ def save(ctx, path: str):
     """The parameters and the volume (S and W, [nz, ny, nx] int32 each) as an .npz (the extension is added to a path without it;
     load() does the same, so the same path names the file in both)."""
     vol = ctx.tsdf_fetch(S=True, W=True)
-    np.savez_compressed(_npz(path), S=vol["S"], W=vol["W"], **{"p_" + k: np.asarray(v) for k, v in params_dict(ctx.tsdf_params()).items()})
+    extra = {"colour": ctx.colour_fetch(sums=True)["sums"]} if ctx.colour_info().present else {}   # ([nz, ny, nx, 4] uint32)
+    np.savez_compressed(_npz(path), S=vol["S"], W=vol["W"], **extra, **{"p_" + k: np.asarray(v) for k, v in params_dict(ctx.tsdf_params()).items()})
 
 
 def load(ctx, path: str):
@@ -96,9 +140,12 @@ def load(ctx, path: str):
             v = z["p_" + f]
             kw[f] = [float(x) for x in v] if f == "origin" else (int(v) if t is capi.C.c_int else float(v))
         S, W = z["S"], z["W"]
+        colour = z["colour"] if "colour" in z.files else None   # (files written before the colour layer have none)
     p = capi.default_tsdf_params(**kw)
     ctx.tsdf_configure(p)
     ctx.tsdf_load(S, W)
+    if colour is not None:
+        ctx.colour_load(colour)
     return p
 
 
