@@ -1320,6 +1320,74 @@ int  lv_colour_info(lv_ctx* ctx, struct lv_colour_info* out);
 /* rgba: 4 bytes per vertex of the mesh last built, in vertex order; cap_vertices below the vertex count: LV_EINVAL. */
 int  lv_mesh_colours(lv_ctx* ctx, uint8_t* rgba, size_t cap_vertices);
 
+/* ---- Surface ray casting ---------------------------------------------------------------------------------
+ * What a sensor would see of the TSDF surface from a pose: sub-voxel depth, the surface normal and the surface colour per ray,
+ * as the ray casters of Voxblox and nvblox give them, for rendered depth and colour views of the reconstruction and for
+ * synthetic scans in model-based localisation (the reference has no counterpart).  The walk of "Occupancy grid", unchanged, as
+ * "Ray casting" runs it, READING S, W and the colour layer.  Every step after the quantisation of a ray's ends is integer
+ * arithmetic (the normal: a fixed sequence of unfused f32 operations), so every output is a pure function of the volume and the
+ * arguments, the same bits whatever the schedule.
+ *   grid     the TSDF volume's, at its present origin (after its shifts).
+ *   ends     lv_surf_raycast: exactly lv_occ_raycast's ("Ray casting", ends): `from` as a view's sensor origin, `to` as a return's
+ *            world point; a ray one of whose ends fails (non-finite included) is IGNORED.  So |d_a| < 2^25 per axis for
+ *            d = qe - qs, and l2 = d . d < 2^52: every product below fits in int64.
+ *   cells    c_0 .. c_S, a_s and num_s / den_s as in "Ray casting".  A cell inside the grid is KNOWN iff W >= min_weight (the
+ *            call's parameter, >= 1); a KNOWN cell is IN iff S < 0, otherwise OUT; an in-grid cell that is not KNOWN is UNKNOWN.
+ *            Cells outside the grid have no state: they neither stop a ray nor count.
+ *   stop     s* is the least s whose c_s is IN; c_0 is examined like every other cell.  The ray is a HIT iff s* >= 1 and
+ *            c_(s* - 1) is inside the grid and OUT; then B = c_s* and A = c_(s* - 1).  Otherwise it is BLOCKED: it starts inside
+ *            the surface, or enters it from unobserved space or from outside the grid.  A ray with no such s is CLEAR.  UNKNOWN
+ *            cells are passed: a LiDAR volume fused without carve is unobserved in front of its truncation band, and a caster that
+ *            stopped there would see nothing.
+ *   depth    in sub-units along the ray, with len = floor(sqrt(l2)) exactly.  HIT: t = the mesh's crossing of the edge A -> B
+ *            (num = S_A W_B, den = num - S_B W_A, t = (256 num) / den, in 0..256); u_A = (256 A + 128 - qs) . d;
+ *            u = u_A + |d_a| t with a = a_s*, clamped to [0, l2]; depth = floor(u / len).  (B = A +- e_a, so the centres'
+ *            projections on the ray are 256 |d_a| apart: u is the zero of the TSDF interpolated linearly between them; a step
+ *            happened, so len >= 1.)  BLOCKED: depth = floor(num_s* len / den_s*), 0 for s* = 0; t = -1.  CLEAR: depth = len, t = -1.
+ *            Metres: resolution * ((float)depth / 256.0f), f32 and unfused; the caller's business.
+ *   record   HIT / BLOCKED: cell = the linear index of c_s*; steps = s*; axis = a_s* (-1 when s* = 0); n_known and n_unknown count
+ *            the in-grid OUT and UNKNOWN cells among c_0 .. c_(s* - 1).  CLEAR: cell = the linear index of ve, -1 outside the
+ *            grid; steps = S; axis = -1; the counts run over c_0 .. c_S.  IGNORED: status 0, cell -1, every other field 0.
+ *   normal   (optional, 3 f32 per ray; zeros for everything but a HIT) with phi(v) = (float)S_v / (float)W_v the gradient at B:
+ *            per axis a, both neighbours B +- e_a KNOWN: g_a = phi(+) - phi(-); only one KNOWN: g_a = 2.0f * (phi(+) - phi(B)) or
+ *            2.0f * (phi(B) - phi(-)); a neighbour outside the grid is not KNOWN.  If on any axis neither neighbour is KNOWN the
+ *            normal is zeros.  n = g / sqrtf((g_x g_x + g_y g_y) + g_z g_z), f32 and unfused in exactly that order, zeros when the
+ *            norm is not > 0.  It points from inside to outside, towards where the sensor was, as the mesh's faces do.
+ *   colour   (optional, 4 bytes per ray; 0, 0, 0, 0 for everything but a HIT) the voxel colour ("Colour layer", voxel) of B if its
+ *            Wc > 0, otherwise of A if its Wc > 0, otherwise 0, 0, 0, 0.  Without a layer: 0, 0, 0, 0 everywhere, LV_OK, and
+ *            nothing is allocated for the layer.
+ *   views    lv_surf_raycast_views: 1..32 lv_view whose returns are the end points of a scan pattern in the sensor frame, at most
+ *            2^24 returns together.  qs, qe and which returns are ignored or cut are exactly those of lv_tsdf_integrate /
+ *            lv_occ_view_gain for the same view; cut and hit returns alike are rays qs -> qe.  Results are written for every
+ *            return of every view, in order; ignored returns, and every return of a view that gives no evidence, are IGNORED.
+ *            stats: rays used, HIT, BLOCKED, CLEAR.
+ * Both calls read the LIVE volume and layer and change no bit of them, of the mesh or of any stale flag.  The walk reads a packed
+ * copy of the states (2 bits per voxel), rebuilt by the first call after the volume changed or when min_weight differs from the
+ * packed one; nothing is allocated before the first call, and lv_tsdf_configure and lv_destroy free everything.  Order of
+ * judgement as for the colour calls: parameters and NULL or short arguments before the context (min_weight < 1, strides below 12,
+ * NULL out, capacity below the returns: LV_EINVAL, nothing written; the null context last), then LV_ESTATE before
+ * lv_tsdf_configure.  The calls run on the context's stream and return when their host outputs are written. */
+/* Names: the calls and the states are lv_surf_* / LV_SURF_* ("surface"), the two structs lv_tsdf_ray_*: the set of lv_tsdf_*
+ * FUNCTIONS is closed (the volume and its mesh, "TSDF and mesh"), as lv_mesh_colours stands outside lv_colour_*. */
+#define LV_SURF_IGNORED 0
+#define LV_SURF_CLEAR   1
+#define LV_SURF_HIT     2
+#define LV_SURF_BLOCKED 3
+typedef struct lv_tsdf_ray_params { int min_weight; int reserved; } lv_tsdf_ray_params;
+typedef struct lv_tsdf_ray_result {           /* 32 bytes */
+    int32_t status, cell, steps, axis, depth, t, n_known, n_unknown;
+} lv_tsdf_ray_result;
+/* min_weight 1. */
+void lv_default_surf_ray_params(lv_tsdf_ray_params* p);
+/* from, to: n world points each, the first three floats of every stride bytes (strides >= 12); out: n results; normals (3 floats
+ * per ray) and rgba (4 bytes per ray) may be NULL.  n = 0 succeeds and writes nothing; n < 2^31 - 1. */
+int  lv_surf_raycast(lv_ctx* ctx, const lv_tsdf_ray_params* p, const void* from, size_t from_stride, const void* to, size_t to_stride,
+                     size_t n, lv_tsdf_ray_result* out, float* normals, uint8_t* rgba);
+/* n_views 1..32; out, normals, rgba: one entry per return of every view, in order; capacity (entries) below the returns:
+ * LV_EINVAL.  normals, rgba and stats may be NULL. */
+int  lv_surf_raycast_views(lv_ctx* ctx, const lv_tsdf_ray_params* p, const lv_view* views, size_t n_views, lv_tsdf_ray_result* out,
+                           float* normals, uint8_t* rgba, size_t capacity, uint64_t stats[4]);
+
 /* ---- Rolling volumes -------------------------------------------------------------------------------------
  * The occupancy grid and the TSDF volume follow the robot (costmap_2d's rolling_window, the local maps of Voxblox / nvblox, the
  * ring buffers of FIESTA / ego-planner; the reference has no counterpart).  lv_volume_recentre moves a volume by whole voxels:

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
     "lv_default_colour_params", "lv_colour_integrate", "lv_colour_fetch", "lv_colour_load", "lv_colour_query", "lv_colour_clear",
     "lv_colour_info", "lv_mesh_colours",
+    "lv_default_surf_ray_params", "lv_surf_raycast", "lv_surf_raycast_views",
     "lv_volume_recentre", "lv_volume_shift_info", "lv_default_occ_mark_params", "lv_occ_mark",
     "lv_default_observation", "lv_observe", "lv_observe_results",
     "lv_default_graph_params", "lv_graph_set", "lv_graph_optimise", "lv_graph_fetch", "lv_graph_chi2", "lv_graph_warp_points",
@@ -659,6 +660,29 @@ COLOUR_ARGTYPES = {
     "lv_mesh_colours": [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t],
 }
 
+LV_SURF_IGNORED, LV_SURF_CLEAR, LV_SURF_HIT, LV_SURF_BLOCKED = 0, 1, 2, 3
+
+
+class TsdfRayParams(C.Structure):  # lv_tsdf_ray_params
+    _fields_ = [("min_weight", C.c_int), ("reserved", C.c_int)]
+
+
+class TsdfRayResult(C.Structure):  # lv_tsdf_ray_result (32 bytes)
+    _fields_ = [("status", C.c_int32), ("cell", C.c_int32), ("steps", C.c_int32), ("axis", C.c_int32), ("depth", C.c_int32),
+                ("t", C.c_int32), ("n_known", C.c_int32), ("n_unknown", C.c_int32)]
+
+
+# the same record as a numpy dtype (Context.tsdf_raycast)
+TSDF_RAY_RESULT_DTYPE = np.dtype([(f, np.int32) for f, _ in TsdfRayResult._fields_])
+
+# ctypes signatures of the surface ray casting (include/limovelo_hip.h "Surface ray casting"; tests/test_tsdf_ray_abi.py)
+TSDF_RAY_ARGTYPES = {
+    "lv_surf_raycast": [C.c_void_p, C.POINTER(TsdfRayParams), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t,
+                        C.POINTER(TsdfRayResult), C.POINTER(C.c_float), C.POINTER(C.c_uint8)],
+    "lv_surf_raycast_views": [C.c_void_p, C.POINTER(TsdfRayParams), C.POINTER(View), C.c_size_t, C.POINTER(TsdfRayResult), C.POINTER(C.c_float),
+                              C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint64)],
+}
+
 
 LV_VOLUME_OCC, LV_VOLUME_SURFACE = 0, 1
 VOLUME_SHIFT_LIMIT = 1 << 20
@@ -925,6 +949,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
         lib.lv_default_colour_params.restype = None
         lib.lv_default_colour_params.argtypes = [C.POINTER(ColourParams)]
+        lib.lv_default_surf_ray_params.restype = None
+        lib.lv_default_surf_ray_params.argtypes = [C.POINTER(TsdfRayParams)]
         lib.lv_default_occ_mark_params.restype = None
         lib.lv_default_occ_mark_params.argtypes = [C.POINTER(OccMarkParams)]
         lib.lv_default_observation.restype = None
@@ -942,7 +968,7 @@ def load_library() -> C.CDLL:
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **COLOUR_ARGTYPES, **VOLUME_ARGTYPES,
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -1200,6 +1226,14 @@ def default_colour_params(**kw) -> ColourParams:
     own = {f for f, _ in ColourParams._fields_}
     for k, v in kw.items():
         setattr(p if k in own else p.view, k, v)
+    return p
+
+
+def default_tsdf_ray_params(**kw) -> TsdfRayParams:
+    p = TsdfRayParams()
+    load_library().lv_default_surf_ray_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -2091,6 +2125,40 @@ class Context:
         out = np.zeros((max(nv, 1), 4), np.uint8)
         self._check(self.lib.lv_mesh_colours(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_size_t(nv)))
         return out[:nv]
+
+    # --- surface ray casting (include/limovelo_hip.h "Surface ray casting")
+    def tsdf_raycast(self, frm, to, params: TsdfRayParams | None = None, normals=False, colours=False):
+        """lv_surf_raycast of the rays frm[i] -> to[i] ([n, 3] world points each; default min_weight 1); returns (results [n] of
+        TSDF_RAY_RESULT_DTYPE, normals [n, 3] f32 or None, rgba [n, 4] uint8 or None)."""
+        p = params if params is not None else default_tsdf_ray_params()
+        a, sa, n = _points(np.asarray(frm, np.float32).reshape(-1, 3))
+        b, sb, nb = _points(np.asarray(to, np.float32).reshape(-1, 3))
+        if n != nb:
+            raise ValueError("tsdf_raycast: as many `to` points as `from` points")
+        out = np.zeros(n, TSDF_RAY_RESULT_DTYPE)
+        nrm = np.zeros((n, 3), np.float32) if normals else None
+        col = np.zeros((n, 4), np.uint8) if colours else None
+        self._check(self.lib.lv_surf_raycast(self.h, C.byref(p), a.ctypes.data_as(C.c_void_p), C.c_size_t(sa), b.ctypes.data_as(C.c_void_p),
+                                             C.c_size_t(sb), C.c_size_t(n), out.ctypes.data_as(C.POINTER(TsdfRayResult)),
+                                             nrm.ctypes.data_as(C.POINTER(C.c_float)) if normals else None,
+                                             col.ctypes.data_as(C.POINTER(C.c_uint8)) if colours else None))
+        return out, nrm, col
+
+    def tsdf_raycast_views(self, views, params: TsdfRayParams | None = None, normals=False, colours=False):
+        """lv_surf_raycast_views over views = [(R [3, 3], t [3], pattern end points [n, 3] sensor frame)] (1..32); returns (results,
+        normals or None, rgba or None over every return of every view in order, stats [4] uint64: rays used, HIT, BLOCKED, CLEAR)."""
+        p = params if params is not None else default_tsdf_ray_params()
+        arr, keep = view_array(views)
+        n = sum(int(arr[i].n) for i in range(len(views)))
+        out = np.zeros(max(n, 1), TSDF_RAY_RESULT_DTYPE)
+        nrm = np.zeros((max(n, 1), 3), np.float32) if normals else None
+        col = np.zeros((max(n, 1), 4), np.uint8) if colours else None
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_surf_raycast_views(self.h, C.byref(p), arr, C.c_size_t(len(views)), out.ctypes.data_as(C.POINTER(TsdfRayResult)),
+                                                   nrm.ctypes.data_as(C.POINTER(C.c_float)) if normals else None,
+                                                   col.ctypes.data_as(C.POINTER(C.c_uint8)) if colours else None, C.c_size_t(n),
+                                                   stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[:n], (nrm[:n] if normals else None), (col[:n] if colours else None), stats
 
     # --- rolling volumes (include/limovelo_hip.h "Rolling volumes")
     def volume_recentre(self, volume: int, shift) -> np.ndarray:

@@ -17,6 +17,7 @@
 #include "lv_mcl_filter.hpp"
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
+#include "lv_tsdf_ray.hpp"
 
 #include <chrono>
 
@@ -1799,6 +1800,34 @@ int lv_mesh_colours(lv_ctx* c, uint8_t* rgba, size_t cap_vertices) {
     if (!rgba) { set_error("lv_mesh_colours: null argument"); return LV_EINVAL; }
     LV_CHECK_CTX(c);
     return c->vol.mesh_colours(c->stream, rgba, cap_vertices);
+}
+
+// ---- Surface ray casting (lv_tsdf_ray.hip): the arguments are judged before the context, as lv_occ_raycast's are
+void lv_default_surf_ray_params(lv_tsdf_ray_params* p) { default_tsdf_ray_params(p); }
+
+int lv_surf_raycast(lv_ctx* c, const lv_tsdf_ray_params* p, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
+                    lv_tsdf_ray_result* out, float* normals, uint8_t* rgba) {
+    if (const char* why = surf_check_params(p)) { set_error("lv_surf_raycast: %s", why); return LV_EINVAL; }
+    if (n >= SURF_MAX_N) { set_error("lv_surf_raycast: too many rays"); return LV_EINVAL; }
+    if (n && (!from || !to || !out || from_stride < 12 || to_stride < 12)) {
+        set_error("lv_surf_raycast: bad point arrays (strides %zu, %zu) or null output", from_stride, to_stride);
+        return LV_EINVAL;
+    }
+    LV_CHECK_CTX(c);
+    return c->vol.tsdf_raycast(c->stream, *p, from, from_stride, to, to_stride, n, out, normals, rgba);
+}
+
+int lv_surf_raycast_views(lv_ctx* c, const lv_tsdf_ray_params* p, const lv_view* views, size_t n_views, lv_tsdf_ray_result* out, float* normals,
+                          uint8_t* rgba, size_t capacity, uint64_t stats[4]) {
+    if (const char* why = surf_check_params(p)) { set_error("lv_surf_raycast_views: %s", why); return LV_EINVAL; }
+    if (!views || !out) { set_error("lv_surf_raycast_views: null argument"); return LV_EINVAL; }
+    if (n_views < 1 || n_views > (size_t)OCC_MAX_VIEWS) { set_error("lv_surf_raycast_views: n_views = %zu: must be in 1..%d", n_views, OCC_MAX_VIEWS); return LV_EINVAL; }
+    if (int rc = views_ok(views, n_views, "lv_surf_raycast_views: ", false, TSDF_MAX_RETURNS)) return rc;   // (t is not judged: lv_rules.hpp)
+    size_t total = 0;
+    for (size_t v = 0; v < n_views; ++v) total += views[v].n;
+    if (capacity < total) { set_error("lv_surf_raycast_views: room for %zu results needed", total); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.tsdf_raycast_views(c->stream, *p, views, n_views, out, normals, rgba, stats);
 }
 
 // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)

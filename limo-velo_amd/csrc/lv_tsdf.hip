@@ -15,6 +15,8 @@
 // calls and holds 8 bytes per voxel, so nothing is allocated: tsdf_shift_gather_kernel writes (S, W) of every voxel's source
 // cell into its scratch word, two voxels and one 16-byte store per lane (an exposed voxel's word is 0, which is S = 0, W = 0),
 // and tsdf_shift_unpack_kernel moves the words into S and W, four voxels per lane, and zeroes them again.
+// The rays' packed states (lv_tsdf_ray.hip) are a member of the store too: integrate(), load(), clear() and recentre() mark them
+// not packed, release() frees them.
 // The colour layer (lv_colour.hip) is a member of the store: clear() and load() zero it, recentre() moves it through a second buffer
 // of its own, mesh_build() takes the vertex colours from it, release() frees it.  A store without one does none of that.
 #include <utility>
@@ -269,6 +271,7 @@ void TsdfStore::release() {
     d_S.release(); d_W.release(); d_scratch.release(); stats.release(); pts.release(); d_out.release(); d_wout.release();
     d_flag.release(); d_vid.release(); d_fcnt.release(); d_foff.release(); d_tmp.release();
     colour.release();
+    rays.release();
     *this = TsdfStore();
 }
 
@@ -294,6 +297,7 @@ int TsdfStore::configure(hipStream_t stream, const lv_tsdf_params& p) {
 }
 
 int TsdfStore::clear(hipStream_t stream) {
+    rays.packed = false;
     LV_HIP(hipMemsetAsync(d_S, 0, n_vox * sizeof(int32_t), stream));
     LV_HIP(hipMemsetAsync(d_W, 0, n_vox * sizeof(int32_t), stream));
     if (colour.present) return colour_clear(stream);   // (waits for the stream)
@@ -304,6 +308,7 @@ int TsdfStore::clear(hipStream_t stream) {
 int TsdfStore::integrate(hipStream_t stream, const lv_view* views, size_t n_views, uint64_t out[4]) {
     size_t total = 0;
     for (size_t v = 0; v < n_views; ++v) total += views[v].n;
+    rays.packed = false;
     int rc = LV_OK;
     if (total) {   // every view's returns in one upload
         rc = pts.reserve(stream, total);
@@ -366,6 +371,7 @@ int TsdfStore::fetch(hipStream_t stream, int32_t* S, int32_t* W, float* metres) 
 }
 
 int TsdfStore::load(hipStream_t stream, const int32_t* S, const int32_t* W) {
+    rays.packed = false;
     LV_HIP(hipMemcpyAsync(d_S, S, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     LV_HIP(hipMemcpyAsync(d_W, W, n_vox * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     if (colour.present) return colour_clear(stream);   // (colours of another volume mean nothing; waits for the stream)
@@ -374,6 +380,7 @@ int TsdfStore::load(hipStream_t stream, const int32_t* S, const int32_t* W) {
 }
 
 int TsdfStore::recentre(hipStream_t stream, const int32_t d[3], const int32_t s_new[3], const float origin_new[3], uint64_t out[4]) {
+    rays.packed = false;
     int rc = stats.zero(stream);
     if (!rc && colour.present) rc = colour.d_next.need(4 * n_vox);   // (before anything moves: a call that fails has changed nothing)
     if (rc) return rc;

@@ -281,6 +281,24 @@ struct ColourLayer {
     }
 };
 
+// The packed cell states of the volume ("Surface ray casting"; rule in lv_tsdf_ray.hpp, kernels in lv_tsdf_ray.hip) and the buffers
+// of lv_surf_raycast / lv_surf_raycast_views.  Nothing is allocated before the first of them; the states are built by the first
+// call after S or W changed (`packed` false) or with another min_weight.
+struct TsdfRays {
+    bool packed = false;
+    int min_weight = 0;                  // what d_states was packed with
+    DevBuf<uint32_t> d_states;           // 2 bits per voxel in lv_ray.hpp's layout
+    PointStage pts;                      // lv_surf_raycast: every `from`, then every `to`; _views: every view's returns
+    DevBuf<lv_tsdf_ray_result> d_res;
+    DevBuf<float> d_nrm;                 // 3 per ray
+    DevBuf<uint32_t> d_rgba;             // one packed r, g, b, a per ray
+    void release() {
+        d_states.release(); pts.release(); d_res.release(); d_nrm.release(); d_rgba.release();
+        packed = false;
+        min_weight = 0;
+    }
+};
+
 // The volume of a context and the buffers of its calls.  Nothing is allocated before configure().
 struct TsdfStore {
     bool configured = false;
@@ -299,6 +317,7 @@ struct TsdfStore {
     DevBuf<uint32_t> d_flag, d_vid, d_fcnt, d_foff;   // the build's per-voxel arrays (n_vox + 1 each), freed when it ends
     DevBuf<void> d_tmp;                       // hipcub scratch
     ColourLayer colour;                       // the colour layer: zeroed by clear() and load(), moved by recentre(), read by mesh_build(), freed by release()
+    TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), load(), clear() and recentre(), freed by release()
 
     int configure(hipStream_t stream, const lv_tsdf_params& p);
     int clear(hipStream_t stream);
@@ -312,6 +331,13 @@ struct TsdfStore {
     int mesh_fetch(hipStream_t stream, float* xyz, int32_t* sub, uint32_t* tri);
     void mesh_release();
     void release();
+
+    // ---- ray casting (lv_tsdf_ray.hip).  normals, rgba may be NULL.  Both wait for the stream.
+    int raycast(hipStream_t stream, int min_weight, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
+                lv_tsdf_ray_result* out, float* normals, uint8_t* rgba);
+    int raycast_views(hipStream_t stream, int min_weight, const lv_view* views, size_t n_views, lv_tsdf_ray_result* out, float* normals,
+                      uint8_t* rgba, uint64_t stats[4]);
+    int rays_pack(hipStream_t stream, int min_weight);   // builds the packed states where they are not those of S, W and min_weight
 
     // ---- the colour layer (lv_colour.hip).  cams, q: paint_rule's.  All of them wait for the stream.
     int colour_ensure(hipStream_t stream);   // allocates the layer, all zero, where it is not present

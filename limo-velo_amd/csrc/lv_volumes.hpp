@@ -69,6 +69,9 @@
 //   colour    every lv_colour_* call and lv_mesh_colours: SURFACE, then what is its own.  _integrate: band <= T (LV_EINVAL).
 //             _fetch, _query: LAYER (LV_ESTATE), then the capacity.  _load: n and the values (LV_EINVAL).  _clear without a layer:
 //             LV_OK, nothing done.  lv_mesh_colours: MESH, a mesh built with the layer present (both LV_ESTATE), the capacity.
+//   surface rays  lv_surf_raycast, lv_surf_raycast_views: SURFACE; everything else was judged before the context.  They read the
+//             volume, the layer and the store's packed states (which TsdfStore itself keeps: its integrate, load, clear and recentre
+//             mark them not packed) and touch no `stale`.
 //   rolling   lv_volume_recentre: the volume it names, then grid_shift_check (LV_EINVAL).  lv_volume_shift_info: nothing; a volume
 //             that is not configured and a product that is not built (or whose grid is not configured) report zeros.
 //   mark      GRID, then the box clipped to the grid (an empty one: LV_OK, zero stats, before the point map is looked at).
@@ -632,6 +635,20 @@ struct VolumeTools {
         LV_REQUIRE(tsdf.mesh.coloured, LV_ESTATE, "the mesh was built without a colour layer: call lv_tsdf_mesh_build after lv_colour_integrate");
         if (cap_vertices < tsdf.mesh.counts[0]) { set_error("lv_mesh_colours: room for %llu vertices needed", (unsigned long long)tsdf.mesh.counts[0]); return LV_EINVAL; }
         return tsdf.mesh_colours(stream, rgba);
+    }
+
+    // ---- Surface ray casting (lv_tsdf_ray.hip).  Only these methods reach the store's ray members.  Their entry points have judged
+    // what needs no context: the parameters, null and short arguments, the views, the capacity.
+    int tsdf_raycast(hipStream_t stream, const lv_tsdf_ray_params& p, const void* from, size_t from_stride, const void* to, size_t to_stride, size_t n,
+                     lv_tsdf_ray_result* out, float* normals, uint8_t* rgba) {
+        LV_SURFACE_CONFIGURED;
+        return tsdf.raycast(stream, p.min_weight, from, from_stride, to, to_stride, n, out, normals, rgba);
+    }
+
+    int tsdf_raycast_views(hipStream_t stream, const lv_tsdf_ray_params& p, const lv_view* views, size_t n_views, lv_tsdf_ray_result* out,
+                           float* normals, uint8_t* rgba, uint64_t stats[4]) {
+        LV_SURFACE_CONFIGURED;
+        return tsdf.raycast_views(stream, p.min_weight, views, n_views, out, normals, rgba, stats);
     }
 
     // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip).  volume: LV_VOLUME_OCC or LV_VOLUME_SURFACE

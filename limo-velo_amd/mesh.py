@@ -3,7 +3,9 @@ gives a volume the footprint of an occupancy grid, integrate() fuses sweeps of a
 build() returns the triangle mesh of the zero surface, save_ply() writes it (ASCII or binary little-endian), save() / load()
 keep the volume as an .npz next to occupancy.save_grid's grid, and recentre() / follow() move the volume's box with the robot
 (lv_volume_recentre, "Rolling volumes").  paint() colours the volume from camera frames ("Colour layer"), colour_params_for()
-picks its occlusion parameters for a camera, build(colours=True) and save_ply(colours=...) carry the vertex colours."""
+picks its occlusion parameters for a camera, build(colours=True) and save_ply(colours=...) carry the vertex colours.  raycast()
+casts rays at the surface ("Surface ray casting"), simulate_scan() a whole scan pattern from a pose, camera_pattern() and render()
+a pinhole camera's depth, normal and colour images."""
 from __future__ import annotations
 
 import numpy as np
@@ -161,3 +163,68 @@ def follow(ctx, position, keep=0.25, step=32, axes=(True, True, False)):
     if any(d):
         recentre(ctx, d)
     return d
+
+
+def range_metres(resolution, results) -> np.ndarray:
+    """[n] f32: resolution * ((float)depth / 256.0f) of HIT and BLOCKED rays, inf for CLEAR ones, NaN for IGNORED ones."""
+    m = (np.float32(resolution) * (results["depth"].astype(np.float32) / np.float32(256.0))).astype(np.float32)
+    m[results["status"] == capi.LV_SURF_CLEAR] = np.inf
+    m[results["status"] == capi.LV_SURF_IGNORED] = np.nan
+    return m
+
+
+def raycast(ctx, frm, to, min_weight: int = 1, normals: bool = False, colours: bool = False):
+    """lv_surf_raycast of the rays frm[i] -> to[i] ([n, 3] world points; frm may be one point for all): (results [n] of
+    capi.TSDF_RAY_RESULT_DTYPE, ranges [n] f32 metres) and, where asked for, the normals [n, 3] f32 and the colours [n, 4] uint8
+    behind them.  The range is that of the surface for a HIT (status LV_SURF_HIT), of the cell that stopped the ray for a BLOCKED
+    one, inf for CLEAR and NaN for IGNORED."""
+    to = np.asarray(to, np.float32).reshape(-1, 3)
+    frm = np.ascontiguousarray(np.broadcast_to(np.asarray(frm, np.float32).reshape(-1, 3), to.shape))
+    res, nrm, col = ctx.tsdf_raycast(frm, to, capi.default_tsdf_ray_params(min_weight=int(min_weight)), normals, colours)
+    out = (res, range_metres(ctx.tsdf_params().resolution, res))
+    return out + ((nrm,) if normals else ()) + ((col,) if colours else ())
+
+
+def _cast_view(ctx, R, t, pattern, min_weight, normals, colours):
+    pattern = np.asarray(pattern, np.float32).reshape(-1, 3)
+    res, nrm, col, _ = ctx.tsdf_raycast_views([(np.asarray(R, np.float32).reshape(3, 3), np.asarray(t, np.float32).reshape(3), pattern)],
+                                              capi.default_tsdf_ray_params(min_weight=int(min_weight)), normals, colours)
+    rng = range_metres(ctx.tsdf_params().resolution, res)
+    rng[res["status"] == capi.LV_SURF_BLOCKED] = np.inf   # (no surface seen: what stopped the ray is its back, or unobserved space)
+    with np.errstate(all="ignore"):
+        unit = pattern.astype(np.float64) / np.linalg.norm(pattern.astype(np.float64), axis=1)[:, None]
+    return res, rng, unit, nrm, col
+
+
+def simulate_scan(ctx, R, t, pattern, min_weight: int = 1):
+    """What a LiDAR at the pose (R, t) would measure of the surface: lv_surf_raycast_views of the beams of `pattern`
+    (occupancy.scan_pattern's end points, sensor frame), which are the rays lv_tsdf_integrate would walk for those returns.
+    Returns (ranges [n] f32 metres, points [n, 3] f64 in the sensor frame): the range of a beam that HITs the surface, inf where it
+    meets none (CLEAR, or BLOCKED: it met the surface from behind or out of unobserved space), NaN where the return is ignored; the
+    points are NaN where the range is not finite."""
+    _, rng, unit, _, _ = _cast_view(ctx, R, t, pattern, min_weight, False, False)
+    pts = unit * np.where(np.isfinite(rng), rng, np.nan).astype(np.float64)[:, None]
+    return rng, pts
+
+
+def camera_pattern(fx, fy, cx, cy, width, height, max_range) -> np.ndarray:
+    """[height * width, 3] f32: the end points, in the camera frame (z forward, x right, y down), of the rays of length max_range
+    through the pixel centres of a pinhole camera without distortion, row-major."""
+    v, u = np.meshgrid(np.arange(int(height), dtype=np.float64), np.arange(int(width), dtype=np.float64), indexing="ij")
+    d = np.stack([(u - float(cx)) / float(fx), (v - float(cy)) / float(fy), np.ones_like(u)], axis=-1).reshape(-1, 3)
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    return (float(max_range) * d).astype(np.float32)
+
+
+def render(ctx, R, t, fx, fy, cx, cy, width, height, max_range=None, min_weight: int = 1):
+    """The surface as a pinhole camera at the pose (R, t) (camera to world) sees it: (depth [height, width] f32, normals [height,
+    width, 3] f32 in the world frame, rgba [height, width, 4] uint8).  depth is the z-depth, the range times the z component of the
+    pixel's unit ray, NaN where the ray does not HIT the surface; normals and colours are zeros there.  max_range: the rays'
+    length (default: the volume's max_range).  No distortion."""
+    if max_range is None:
+        max_range = ctx.tsdf_params().max_range
+    pattern = camera_pattern(fx, fy, cx, cy, width, height, max_range)
+    res, rng, unit, nrm, col = _cast_view(ctx, R, t, pattern, min_weight, True, True)
+    depth = np.where(res["status"] == capi.LV_SURF_HIT, rng.astype(np.float64) * unit[:, 2], np.nan).astype(np.float32)
+    shape = (int(height), int(width))
+    return depth.reshape(shape), nrm.reshape(shape + (3,)), col.reshape(shape + (4,))
