@@ -1263,6 +1263,62 @@ int  lv_tsdf_mesh_info(lv_ctx* ctx, lv_mesh_info* out);
 /* Frees the mesh. */
 int  lv_tsdf_mesh_clear(lv_ctx* ctx);
 
+/* ---- Depth fusion ------------------------------------------------------------------------------------------
+ * Depth-camera images fused into the TSDF volume: the projective integrator of KinectFusion, Voxblox and nvblox
+ * (ProjectiveTsdfIntegrator; the reference has no counterpart).  Where lv_tsdf_integrate walks every return's ray through the
+ * volume, here every voxel projects itself into every image and reads one pixel: exactly one thread owns a voxel, so there are
+ * no atomics on the volume and no scratch pass, and the result is the same bits whatever the schedule.  A view is one depth
+ * image with its pinhole camera and its pose camera -> world; R, t, fx, fy, cx, cy and dist mean exactly what they mean in
+ * lv_camera_view ("Map painting").  Depth is z along the optical axis (the ROS convention), not range.
+ *   formats    LV_DEPTH_U16: ROS 16UC1, D = (float)raw * depth_scale metres, raw 0 is "no measurement"; depth_scale finite and
+ *              > 0 (0.001 for millimetres).  LV_DEPTH_F32: ROS 32FC1, metres; depth_scale is ignored.
+ *   limits     1..32 views; width and height 1..8192 each, width * height <= 2^24 per view and <= 2^26 pixels per call;
+ *              row_stride >= width * bytes per pixel.  `depth` needs no alignment: the rows are staged by memcpy.
+ * For every voxel and every view, in view order.  Every f32 operation is a single rounded operation in the order written;
+ * nothing is fused (-ffp-contract=off) and division is correctly rounded.
+ *   1. centre    p_a = origin_a + resolution * ((float)(256 * i_a + 128) / 256.0f) with the volume's present origin (after its
+ *                shifts): the centre of "Colour layer".
+ *   2. project   "Map painting" steps 1 to 3, unchanged, with this call's min_depth, max_depth and max_norm_radius: they yield
+ *                z, u, v, or the view does not judge the voxel.
+ *   3. pixel     px = (int)floorf(u + 0.5f), py = (int)floorf(v + 0.5f): the nearest pixel, never an interpolation (across a
+ *                depth edge that would invent a surface).
+ *   4. depth     U16: raw 0 is invalid, otherwise D = (float)raw * depth_scale.  F32: D is the value.  D is invalid unless it is
+ *                finite and min_depth <= D <= max_depth (NaN, +-inf, 0 and negatives fall out by that comparison).
+ *   5. distance  q = floorf(((D - z) / resolution) * 256.0f), compared in f32 against (float)T.  q < -T: no contribution.
+ *                q > T: s = T if carve != 0, otherwise no contribution.  Otherwise s = (int32)q.
+ *   6. add       (dS += s, dW += 1).
+ * After the last view every voxel with dW > 0 folds as in "TSDF and mesh" (one call), with the volume's max_weight.  Integer
+ * sums commute, so neither the order of the views nor, as long as W stays below max_weight, their split over calls matters
+ * (at max_weight the fold rescales, and a rescale after every call is not the rescale after all of them).
+ *   stats      (voxel, view) pairs that pass step 2; those of them with a valid D; the sum of dW; voxels with dW > 0.
+ * Order of judgement as for lv_colour_integrate: the arguments before the context (LV_EINVAL, nothing written; the null context
+ * last), then LV_ESTATE before lv_tsdf_configure.  Once its arguments hold, and whatever it then returns, the call sets a built
+ * mesh's stale = 1 and makes the next lv_surf_raycast pack the states anew, as lv_tsdf_integrate does; it leaves the colour
+ * layer alone.  It runs on the context's stream and returns when stats are written.
+ * Known limits: the distance is the difference in z, not the distance to the surface: on a surface seen at an angle it
+ * overestimates by 1 / cos, as Voxblox and nvblox accept.  One observation weighs 1 whatever its depth, as one LiDAR ray does. */
+/* Names: lv_depth_*, as the layer's calls are lv_colour_*: the set of lv_tsdf_* FUNCTIONS is closed ("Surface ray casting"). */
+enum { LV_DEPTH_U16 = 0, LV_DEPTH_F32 = 1 };   /* the ROS encodings 16UC1 / 32FC1 */
+typedef struct lv_depth_view {
+    float R[9]; float t[3];          /* as lv_camera_view */
+    float fx, fy, cx, cy;
+    float dist[5];
+    int   width, height;
+    int   format;                    /* LV_DEPTH_* */
+    float depth_scale;               /* metres per unit, U16 only */
+    const void* depth; size_t row_stride;   /* bytes between rows */
+} lv_depth_view;
+typedef struct lv_depth_params {
+    float min_depth, max_depth;      /* 0 < min_depth < max_depth: of the voxel's z and of the measured D alike */
+    float max_norm_radius;           /* > 0, as lv_paint_params */
+    int   carve;                     /* 0 or 1: whether free space in front of the band takes s = T */
+    int   reserved;
+} lv_depth_params;
+/* Defaults: depth 0.3..10 m, max_norm_radius 1.5, carve 0. */
+void lv_default_depth_params(lv_depth_params* p);
+/* n_views 1..32.  stats (may be NULL) as above. */
+int  lv_depth_integrate(lv_ctx* ctx, const lv_depth_view* views, size_t n_views, const lv_depth_params* p, uint64_t stats[4]);
+
 /* ---- Colour layer ------------------------------------------------------------------------------------------
  * A colour layer beside the TSDF, as Voxblox and nvblox carry one, and vertex colours for the mesh: the voxels near the surface
  * take the colour of the camera images that see them (the reference's TODO "Add vision buffer and ability to paint the map's

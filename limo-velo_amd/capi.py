@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "lv_occ_mcl_filter_get", "lv_occ_mcl_filter_info", "lv_occ_mcl_filter_clear",
     "lv_default_tsdf_params", "lv_tsdf_configure", "lv_tsdf_integrate", "lv_tsdf_query", "lv_tsdf_fetch", "lv_tsdf_load", "lv_tsdf_clear",
     "lv_tsdf_get_params", "lv_tsdf_mesh_build", "lv_tsdf_mesh_fetch", "lv_tsdf_mesh_info", "lv_tsdf_mesh_clear",
+    "lv_default_depth_params", "lv_depth_integrate",
     "lv_default_colour_params", "lv_colour_integrate", "lv_colour_fetch", "lv_colour_load", "lv_colour_query", "lv_colour_clear",
     "lv_colour_info", "lv_mesh_colours",
     "lv_default_surf_ray_params", "lv_surf_raycast", "lv_surf_raycast_views",
@@ -641,6 +642,49 @@ TSDF_ARGTYPES = {
 }
 
 
+LV_DEPTH_U16, LV_DEPTH_F32 = 0, 1
+DEPTH_DTYPES = {LV_DEPTH_U16: np.dtype(np.uint16), LV_DEPTH_F32: np.dtype(np.float32)}
+
+
+class DepthView(C.Structure):  # lv_depth_view
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("dist", C.c_float * 5), ("width", C.c_int), ("height", C.c_int), ("format", C.c_int), ("depth_scale", C.c_float),
+                ("depth", C.c_void_p), ("row_stride", C.c_size_t)]
+
+
+class DepthParams(C.Structure):  # lv_depth_params
+    _fields_ = [("min_depth", C.c_float), ("max_depth", C.c_float), ("max_norm_radius", C.c_float), ("carve", C.c_int), ("reserved", C.c_int)]
+
+
+# ctypes signatures of the depth fusion (include/limovelo_hip.h "Depth fusion"; tests/test_depth_abi.py)
+DEPTH_ARGTYPES = {
+    "lv_depth_integrate": [C.c_void_p, C.POINTER(DepthView), C.c_size_t, C.POINTER(DepthParams), C.POINTER(C.c_uint64)],
+}
+
+
+def depth_view(frame):
+    """(DepthView, depth array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, depth ([h, w]
+    uint16: LV_DEPTH_U16, or float32: LV_DEPTH_F32, metres; rows may be strided), optional depth_scale (metres per unit of a
+    uint16 image, default 0.001) and dist (k1, k2, p1, p2, k3)."""
+    img = np.asarray(frame["depth"])
+    if img.ndim != 2 or img.dtype not in (np.uint16, np.float32):
+        raise ValueError("depth must be a 2-D uint16 or float32 array")
+    if img.strides[1] != img.itemsize or img.strides[0] < img.shape[1] * img.itemsize:
+        img = np.ascontiguousarray(img)
+    v = DepthView()
+    v.R[:] = [float(x) for x in np.asarray(frame["R"], np.float32).ravel()]
+    v.t[:] = [float(x) for x in np.asarray(frame["t"], np.float32).ravel()]
+    v.fx, v.fy, v.cx, v.cy = (float(frame[k]) for k in ("fx", "fy", "cx", "cy"))
+    dist = frame.get("dist")
+    v.dist[:] = [float(x) for x in np.asarray(np.zeros(5) if dist is None else dist, np.float32).ravel()]
+    v.height, v.width = int(img.shape[0]), int(img.shape[1])
+    v.format = LV_DEPTH_U16 if img.dtype == np.uint16 else LV_DEPTH_F32
+    v.depth_scale = float(frame.get("depth_scale", 0.001))
+    v.depth = img.ctypes.data
+    v.row_stride = int(img.strides[0])
+    return v, img
+
+
 class ColourParams(C.Structure):  # lv_colour_params
     _fields_ = [("view", LvPaintParams), ("band", C.c_int), ("min_weight", C.c_int), ("max_weight", C.c_int), ("reserved", C.c_int)]
 
@@ -947,6 +991,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_mcl_resample_params.argtypes = [C.POINTER(MclResampleParams)]
         lib.lv_default_tsdf_params.restype = None
         lib.lv_default_tsdf_params.argtypes = [C.POINTER(TsdfParams)]
+        lib.lv_default_depth_params.restype = None
+        lib.lv_default_depth_params.argtypes = [C.POINTER(DepthParams)]
         lib.lv_default_colour_params.restype = None
         lib.lv_default_colour_params.argtypes = [C.POINTER(ColourParams)]
         lib.lv_default_surf_ray_params.restype = None
@@ -968,7 +1014,7 @@ def load_library() -> C.CDLL:
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
-                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
+                               **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **DEPTH_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
@@ -1215,6 +1261,14 @@ def default_tsdf_params(**kw) -> TsdfParams:
             p.origin[:] = [float(x) for x in v]
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_depth_params(**kw) -> DepthParams:
+    p = DepthParams()
+    load_library().lv_default_depth_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p
 
 
@@ -2069,6 +2123,20 @@ class Context:
 
     def tsdf_mesh_clear(self):
         self._check(self.lib.lv_tsdf_mesh_clear(self.h))
+
+    # --- depth fusion (include/limovelo_hip.h "Depth fusion")
+    def tsdf_integrate_depth(self, frames, params: DepthParams | None = None) -> np.ndarray:
+        """lv_depth_integrate over frames = [frame dict (depth_view)] (1..32, one call); returns stats [4] uint64: (voxel, view) pairs
+        projected, those with a valid depth, contributions, voxels touched."""
+        p = params if params is not None else default_depth_params()
+        arr = (DepthView * max(len(frames), 1))()
+        keep = []
+        for i, f in enumerate(frames):
+            arr[i], img = depth_view(f)
+            keep.append(img)
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_depth_integrate(self.h, arr, C.c_size_t(len(frames)), C.byref(p), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
 
     # --- colour layer (include/limovelo_hip.h "Colour layer")
     def colour_integrate(self, views, params: ColourParams | None = None) -> np.ndarray:

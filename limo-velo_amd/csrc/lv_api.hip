@@ -18,6 +18,7 @@
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
 #include "lv_tsdf_ray.hpp"
+#include "lv_depth.hpp"
 
 #include <chrono>
 
@@ -1757,6 +1758,17 @@ int lv_tsdf_mesh_fetch(lv_ctx* c, float* xyz, int32_t* sub, uint32_t* tri, size_
 }
 int lv_tsdf_mesh_info(lv_ctx* c, lv_mesh_info* out) { LV_CHECK_CTX(c); return c->vol.mesh_info(out); }
 int lv_tsdf_mesh_clear(lv_ctx* c) { LV_CHECK_CTX(c); return c->vol.mesh_clear(c->stream); }
+
+// ---- Depth fusion (lv_depth.hip): the arguments are judged before the context, as lv_colour_integrate's are
+void lv_default_depth_params(lv_depth_params* p) { default_depth_params(p); }
+
+int lv_depth_integrate(lv_ctx* c, const lv_depth_view* views, size_t n_views, const lv_depth_params* p, uint64_t stats[4]) {
+    DepthRule q;
+    DepthCam cams[DEPTH_MAX_VIEWS];
+    if (int rc = depth_rule(views, n_views, p, &q, cams)) return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.depth_integrate(c->stream, views, cams, q, stats);
+}
 
 // ---- Colour layer (lv_colour.hip): what needs no context is judged before it, the rest in VolumeTools
 void lv_default_colour_params(lv_colour_params* p) { default_colour_params(p); }

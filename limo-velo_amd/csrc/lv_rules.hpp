@@ -228,6 +228,28 @@ struct PaintCam {
 };
 static_assert(sizeof(PaintCam) == 128, "PaintCam is 128 B");
 
+// What paint_project reads of a view, from its pose and intrinsics (dist: k1, k2, p1, p2, k3); every other field zero
+inline PaintCam paint_cam_of(const float R[9], const float t[3], float fx, float fy, float cx, float cy, const float dist[5], int width, int height) {
+    PaintCam c;
+    std::memset(&c, 0, sizeof(c));
+    std::memcpy(c.R, R, sizeof(c.R));
+    std::memcpy(c.t, t, sizeof(c.t));
+    c.fx = fx;
+    c.fy = fy;
+    c.cx = cx;
+    c.cy = cy;
+    c.k1 = dist[0];
+    c.k2 = dist[1];
+    c.p1 = dist[2];
+    c.p2 = dist[3];
+    c.k3 = dist[4];
+    c.wm1 = (float)(width - 1);
+    c.hm1 = (float)(height - 1);
+    c.width = width;
+    c.height = height;
+    return c;
+}
+
 // The call's parameters (r2_max = max_norm_radius^2 in f32, s = zbuf_scale as f32)
 struct PaintRule {
     int n_views, window, blend;
@@ -284,22 +306,7 @@ inline int paint_rule(const lv_camera_view* views, size_t n_views, const lv_pain
         const size_t np = (size_t)w.width * (size_t)w.height;
         const int cw = (w.width + s - 1) / s, ch = (w.height + s - 1) / s;
         PaintCam& c = cams[v];
-        std::memset(&c, 0, sizeof(c));
-        std::memcpy(c.R, w.R, sizeof(c.R));
-        std::memcpy(c.t, w.t, sizeof(c.t));
-        c.fx = w.fx;
-        c.fy = w.fy;
-        c.cx = w.cx;
-        c.cy = w.cy;
-        c.k1 = w.dist[0];
-        c.k2 = w.dist[1];
-        c.p1 = w.dist[2];
-        c.p2 = w.dist[3];
-        c.k3 = w.dist[4];
-        c.wm1 = (float)(w.width - 1);
-        c.hm1 = (float)(w.height - 1);
-        c.width = w.width;
-        c.height = w.height;
+        c = paint_cam_of(w.R, w.t, w.fx, w.fy, w.cx, w.cy, w.dist, w.width, w.height);
         c.cw = cw;
         c.ch = ch;
         c.format = w.format;
@@ -329,6 +336,25 @@ inline int paint_rule(const lv_camera_view* views, size_t n_views, const lv_pain
     q->raw_bytes = raw;
     return LV_OK;
 }
+
+// ---- Depth fusion (lv_depth.hip; its argument rule, depth_rule, is lv_depth.hpp's)
+// One depth view as the kernel takes it (144 B): cam.format is LV_DEPTH_*, cam.raw_off the first staged byte of the view (rows of
+// width * 2 or width * 4 bytes, back to back; a multiple of 256); cam.tex_off, cell_off, cw and ch are not used.
+struct DepthCam {
+    PaintCam cam;
+    float scale;               // depth_scale (U16)
+    uint32_t pad[3];
+};
+static_assert(sizeof(DepthCam) == 144, "DepthCam is 144 B");
+
+// The call's parameters: view holds what paint_project reads (n_views, min_depth, max_depth, r2_max), the rest of it is zero;
+// rho = max_norm_radius
+struct DepthRule {
+    PaintRule view;
+    float rho;
+    int carve;
+    size_t raw_bytes;
+};
 
 // ---- Place recognition (lv_place.hip)
 constexpr int PLACE_MAX_RINGS = 32;

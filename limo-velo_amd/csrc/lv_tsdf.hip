@@ -19,6 +19,8 @@
 // not packed, release() frees them.
 // The colour layer (lv_colour.hip) is a member of the store: clear() and load() zero it, recentre() moves it through a second buffer
 // of its own, mesh_build() takes the vertex colours from it, release() frees it.  A store without one does none of that.
+// Depth fusion (lv_depth.hip) is a member as well: integrate_depth() folds into S and W directly, one owner per voxel, without
+// the scratch words; release() frees its staging.
 #include <utility>
 
 #include "lv_tsdf.hpp"
@@ -272,6 +274,7 @@ void TsdfStore::release() {
     d_flag.release(); d_vid.release(); d_fcnt.release(); d_foff.release(); d_tmp.release();
     colour.release();
     rays.release();
+    depth.release();
     *this = TsdfStore();
 }
 

@@ -299,6 +299,16 @@ struct TsdfRays {
     }
 };
 
+// The buffers of lv_depth_integrate ("Depth fusion"; rule in lv_depth.hpp, kernel in lv_depth.hip): the staged images and the
+// views, pinned and on the device.  Nothing is allocated before the first call that some voxel is judged in.
+struct DepthStage {
+    PinBuf<uint8_t> h_raw;
+    PinBuf<DepthCam> h_cams;             // PAINT_MAX_VIEWS entries
+    DevBuf<uint8_t> d_raw;
+    DevBuf<DepthCam> d_cams;
+    void release() { release_all(h_raw, h_cams, d_raw, d_cams); }
+};
+
 // The volume of a context and the buffers of its calls.  Nothing is allocated before configure().
 struct TsdfStore {
     bool configured = false;
@@ -317,7 +327,8 @@ struct TsdfStore {
     DevBuf<uint32_t> d_flag, d_vid, d_fcnt, d_foff;   // the build's per-voxel arrays (n_vox + 1 each), freed when it ends
     DevBuf<void> d_tmp;                       // hipcub scratch
     ColourLayer colour;                       // the colour layer: zeroed by clear() and load(), moved by recentre(), read by mesh_build(), freed by release()
-    TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), load(), clear() and recentre(), freed by release()
+    TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), integrate_depth(), load(), clear() and recentre(), freed by release()
+    DepthStage depth;                         // integrate_depth()'s staging, freed by release()
 
     int configure(hipStream_t stream, const lv_tsdf_params& p);
     int clear(hipStream_t stream);
@@ -338,6 +349,10 @@ struct TsdfStore {
     int raycast_views(hipStream_t stream, int min_weight, const lv_view* views, size_t n_views, lv_tsdf_ray_result* out, float* normals,
                       uint8_t* rgba, uint64_t stats[4]);
     int rays_pack(hipStream_t stream, int min_weight);   // builds the packed states where they are not those of S, W and min_weight
+
+    // ---- depth fusion (lv_depth.hip).  cams, q: depth_rule's.  Marks the rays' states not packed, leaves the colour layer alone,
+    // waits for the stream.
+    int integrate_depth(hipStream_t stream, const lv_depth_view* views, const DepthCam* cams, const DepthRule& q, uint64_t out[4]);
 
     // ---- the colour layer (lv_colour.hip).  cams, q: paint_rule's.  All of them wait for the stream.
     int colour_ensure(hipStream_t stream);   // allocates the layer, all zero, where it is not present

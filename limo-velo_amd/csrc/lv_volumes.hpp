@@ -1,6 +1,6 @@
 // lv_volumes.hpp — the volume tools of a context: the occupancy grid, what is built from it (distance field, plan, frontier, the
 // rays' packed states), what runs on those (rollouts, localisation), the TSDF volume with its mesh, and the rolling of both
-// volumes.  lv_ctx holds one VolumeTools; every lv_occ_*, lv_tsdf_*, lv_colour_* and lv_volume_* entry point of lv_api.hip judges what it
+// volumes.  lv_ctx holds one VolumeTools; every lv_occ_*, lv_tsdf_*, lv_depth_*, lv_colour_* and lv_volume_* entry point of lv_api.hip judges what it
 // judges before the context, checks the context, and makes one call here.  Host code only: tests/emu/volumes_emu.cpp compiles
 // it with g++ against tests/emu/hip/hip_runtime.h and its own stand-ins for the stores' member functions, and
 // tests/test_volumes_host.py holds it to the rules below.
@@ -39,6 +39,8 @@
 //   lv_tsdf_integrate, lv_tsdf_load (after    | before the store call                       | SURFACE EDIT: mesh.stale = 1
 //     tsdf_check_volume), lv_tsdf_clear       |                                             |   where built
 //   lv_volume_recentre (SURFACE)              | after success, non-zero shift               |
+//   lv_depth_integrate (after its argument    | before the store call, whatever it returns  |
+//     checks)                                 |                                             |
 //   ------------------------------------------+---------------------------------------------+---------------------------------
 //   lv_colour_integrate (after its argument   | before the store call, whatever it returns  | COLOUR EDIT: mesh.stale = 1
 //     checks), lv_colour_load (after its      |                                             |   where built
@@ -72,6 +74,8 @@
 //   surface rays  lv_surf_raycast, lv_surf_raycast_views: SURFACE; everything else was judged before the context.  They read the
 //             volume, the layer and the store's packed states (which TsdfStore itself keeps: its integrate, load, clear and recentre
 //             mark them not packed) and touch no `stale`.
+//   depth     lv_depth_integrate: SURFACE; everything else was judged before the context.  TsdfStore's integrate_depth marks the rays'
+//             packed states not packed, as its integrate does, and leaves the colour layer alone.
 //   rolling   lv_volume_recentre: the volume it names, then grid_shift_check (LV_EINVAL).  lv_volume_shift_info: nothing; a volume
 //             that is not configured and a product that is not built (or whose grid is not configured) report zeros.
 //   mark      GRID, then the box clipped to the grid (an empty one: LV_OK, zero stats, before the point map is looked at).
@@ -575,6 +579,14 @@ struct VolumeTools {
         LV_HIP(hipStreamSynchronize(stream));
         tsdf.mesh_release();
         return LV_OK;
+    }
+
+    // ---- Depth fusion (lv_depth.hip).  Only this method reaches the store's integrate_depth.  Its entry point has judged what
+    // needs no context: null arguments, the views and parameters (depth_rule).
+    int depth_integrate(hipStream_t stream, const lv_depth_view* views, const DepthCam* cams, const DepthRule& q, uint64_t stats[4]) {
+        LV_SURFACE_CONFIGURED;
+        surface_edited();
+        return tsdf.integrate_depth(stream, views, cams, q, stats);
     }
 
     // ---- Colour layer (lv_colour.hip).  Only these methods reach the store's colour members.  Their entry points have judged

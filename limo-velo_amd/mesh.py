@@ -5,7 +5,8 @@ keep the volume as an .npz next to occupancy.save_grid's grid, and recentre() / 
 (lv_volume_recentre, "Rolling volumes").  paint() colours the volume from camera frames ("Colour layer"), colour_params_for()
 picks its occlusion parameters for a camera, build(colours=True) and save_ply(colours=...) carry the vertex colours.  raycast()
 casts rays at the surface ("Surface ray casting"), simulate_scan() a whole scan pattern from a pose, camera_pattern() and render()
-a pinhole camera's depth, normal and colour images."""
+a pinhole camera's depth, normal and colour images.  integrate_depth() fuses depth-camera frames ("Depth fusion"), depth_frame()
+makes one, render_frame() renders one from the surface."""
 from __future__ import annotations
 
 import numpy as np
@@ -31,6 +32,28 @@ def integrate(ctx, sweeps) -> np.ndarray:
     sweeps = list(sweeps)
     for c0 in range(0, len(sweeps), MAX_VIEWS):
         stats += ctx.tsdf_integrate(sweeps[c0:c0 + MAX_VIEWS])
+    return stats
+
+
+def depth_frame(depth, R, t, fx, fy, cx, cy, depth_scale: float = 0.001, dist=None) -> dict:
+    """A frame dict as integrate_depth() takes it: depth ([h, w] uint16 in units of depth_scale metres, 0 = no measurement, or
+    float32 metres, NaN = none; z along the optical axis), the pose camera -> world (R, t), the pinhole, optional plumb_bob dist."""
+    f = dict(depth=np.asarray(depth), R=np.asarray(R, np.float32).reshape(3, 3), t=np.asarray(t, np.float32).reshape(3), fx=float(fx), fy=float(fy),
+             cx=float(cx), cy=float(cy), depth_scale=float(depth_scale))
+    if dist is not None:
+        f["dist"] = np.asarray(dist, np.float32).reshape(5)
+    return f
+
+
+def integrate_depth(ctx, frames, params=None) -> np.ndarray:
+    """lv_depth_integrate over depth frames (depth_frame()) of any number, 32 views per call in order; the stats [4] uint64 summed:
+    (voxel, view) pairs projected, those with a valid depth, contributions, voxels touched (once per call that touched them).
+    Below the volume's max_weight the split over calls does not change the volume."""
+    p = params if params is not None else capi.default_depth_params()
+    stats = np.zeros(4, np.uint64)
+    frames = list(frames)
+    for c0 in range(0, len(frames), MAX_VIEWS):
+        stats += ctx.tsdf_integrate_depth(frames[c0:c0 + MAX_VIEWS], p)
     return stats
 
 
@@ -228,3 +251,10 @@ def render(ctx, R, t, fx, fy, cx, cy, width, height, max_range=None, min_weight:
     depth = np.where(res["status"] == capi.LV_SURF_HIT, rng.astype(np.float64) * unit[:, 2], np.nan).astype(np.float32)
     shape = (int(height), int(width))
     return depth.reshape(shape), nrm.reshape(shape + (3,)), col.reshape(shape + (4,))
+
+
+def render_frame(ctx, R, t, fx, fy, cx, cy, width, height, max_range=None, min_weight: int = 1) -> dict:
+    """render()'s depth as a depth frame (float32 metres, NaN where no ray HITs): what a depth camera at the pose would hand to
+    integrate_depth() of another context."""
+    depth, _, _ = render(ctx, R, t, fx, fy, cx, cy, width, height, max_range, min_weight)
+    return depth_frame(depth, R, t, fx, fy, cx, cy)
