@@ -5,7 +5,10 @@ for branch — the three-term Taylor pair of cos_sinc_sqrt below 2^-13, the clam
 nv / w, the pole branch of the S2 basis, the 3.1415926 exit of the S2 difference.  Inputs are doubles (exact in mpmath), every
 branch is decided on the 50-digit values, results are rounded to double only by the caller.  So `oracle - this` is the oracle's
 own rounding error, and `device - this` the device's, as long as no input sits within rounding of a branch bound (the case
-table keeps its cases a per cent away from them)."""
+table keeps its cases a per cent away from them).
+
+kf_step is one whole pass of the iterated update built from those rules, with upstream's gain in its textbook form and mpmath's
+own 23 x 23 inverse: what tests/solve_regimes.py adjudicates the oracle, the device's block form and the device with."""
 import mpmath as mp
 import numpy as np
 
@@ -19,6 +22,8 @@ PI_EXIT = mp.mpf(3.1415926)            # the literal of the S2 difference's exit
 
 
 def _v(a):
+    if isinstance(a, (list, tuple)) and len(a) and isinstance(a[0], mp.mpf):
+        return list(a)   # already 50-digit values (kf_step hands its own increment to boxplus unrounded)
     return [mp.mpf(float(t)) for t in np.asarray(a, np.float64).ravel()]
 
 
@@ -151,6 +156,116 @@ def predict_state(x, dt, acc, gyro):
         o[14 + i] = x[14 + i] + (a_in[i] + x[23 + i]) * dt
     o[3:7] = quat_mul(x[3:7], so3_exp(omega, dt))
     return o
+
+
+def s2_Nx_yy(vec):
+    """2 x 3:  Bx^T hat(vec) / len^2."""
+    Bx, H = s2_Bx(vec), hat(vec)
+    return [[sum(Bx[k][i] * H[k][j] for k in range(3)) / S2_LEN / S2_LEN for j in range(3)] for i in range(2)]
+
+
+def s2_Mx(vec, delta):
+    """3 x 2:  -hat(vec) A(Bx delta)^T Bx, and -hat(vec) Bx below the tolerance (the rule's exp_delta is the identity: the
+    oracle's note on the integer 1 / 2)."""
+    Bx, H = s2_Bx(vec), hat(vec)
+    if mp.sqrt(delta[0] ** 2 + delta[1] ** 2) < TOL:
+        T = [[-H[i][j] for j in range(3)] for i in range(3)]
+    else:
+        A = A_matrix(mat_vec(Bx, delta))
+        T = [[-sum(H[i][k] * A[j][k] for k in range(3)) for j in range(3)] for i in range(3)]
+    return [[sum(T[i][k] * Bx[k][j] for k in range(3)) for j in range(2)] for i in range(3)]
+
+
+def s2_projection(grav, grav_prop, delta):
+    """2 x 2:  Nx(grav) Mx(grav_prop, delta), the S2 block of the update's projections."""
+    Nx, Mx = s2_Nx_yy(grav), s2_Mx(grav_prop, delta)
+    return [[sum(Nx[i][k] * Mx[k][j] for k in range(3)) for j in range(2)] for i in range(2)]
+
+
+def projection(seg, grav, grav_prop):
+    """The 23 x 23 projection J of one pass: A(seg_rot)^T and A(seg_ext)^T on the two SO3 blocks, the S2 block, identity
+    elsewhere.  seg is the tangent the blocks are evaluated at (x [-] x_prop before the solve, dx_ on the terminal pass)."""
+    J = mp.eye(23)
+    for idx in (3, 6):
+        A = A_matrix(seg[idx:idx + 3])
+        for i in range(3):
+            for j in range(3):
+                J[idx + i, idx + j] = A[j][i]
+    T = s2_projection(grav, grav_prop, seg[21:23])
+    for i in range(2):
+        for j in range(2):
+            J[21 + i, 21 + j] = T[i][j]
+    return J
+
+
+def _kf_step(x, x_prop, P_prop, rec, R, limits, finalize, keep):
+    xd, xp = _v(x), _v(x_prop)
+    R = mp.mpf(float(R))
+    P = mp.matrix([[mp.mpf(float(t)) for t in row] for row in np.asarray(P_prop, np.float64).reshape(23, 23)])
+    HTH = mp.zeros(23, 23)
+    HTh = mp.zeros(23, 1)
+    for i in range(12):
+        HTh[i] = mp.mpf(float(rec["HTh"][i]))
+        for j in range(12):
+            HTH[i, j] = mp.mpf(float(rec["HTH"][i][j]))
+    dx = boxminus(xd, xp)
+    J = projection(dx, xd[23:26], xp[23:26])
+    dx_new = J * mp.matrix(dx)
+    P_ = J * P * J.T
+    # P_inv = ((P_ / R)^-1 + E H^T H E^T)^-1, on the kept dofs; rows and columns of the others are zero (their variance is)
+    keep = list(range(23)) if keep is None else list(keep)
+    n = len(keep)
+    sub = lambda M: mp.matrix([[M[a, b] for b in keep] for a in keep])
+    if n < 23:
+        out = [i for i in range(23) if i not in keep]
+        assert all(P[i, j] == 0 for i in out for j in range(23)) and all(HTH[i, j] == 0 for i in out for j in range(23))
+    inner = mp.inverse(sub(P_) / R) + sub(HTH)
+    small = mp.inverse(inner)
+    P_inv = mp.zeros(23, 23)
+    for a in range(n):
+        for b in range(n):
+            P_inv[keep[a], keep[b]] = small[a, b]
+    K_h = P_inv * HTh
+    K_x = P_inv * HTH          # columns >= 12 are zero
+    dxo = K_h + (K_x - mp.eye(23)) * dx_new
+    dxo = [dxo[i] for i in range(23)]
+    x_new = boxplus(xd, dxo)
+    lim = _v(limits)
+    conv = all(abs(dxo[i]) <= lim[i] for i in range(23))
+    P_out = None
+    if finalize:
+        J2 = projection(dxo, x_new[23:26], xp[23:26])
+        L = J2 * P_ * J2.T
+        P_out = L - (J2 * K_x) * (P_ * J2.T)
+    return x_new, dxo, conv, P_out
+
+
+def _result(x_new, dxo, conv, P_out):
+    P = None if P_out is None else np.array([[float(P_out[i, j]) for j in range(23)] for i in range(23)])
+    return dict(x=_f(x_new), dx=_f(dxo), conv=conv, P=P, x_mp=x_new, dx_mp=dxo, P_mp=P_out)
+
+
+def kf_step(x, x_prop, P_prop, rec, R, limits, finalize):
+    """One pass of the iterated update, the textbook statement of oracle/lv_oracle.cpp::kf_step in 50 digits:
+        dx = x [-] x_prop,  dx_new = J dx,  P_ = J P J^T,  P_inv = ((P_ / R)^-1 + E H^T H E^T)^-1  (mpmath's own inverse),
+        dx_ = P_inv[:, :12] H^T h + (P_inv[:, :12] H^T H - I) dx_new,  x [+] dx_,  converge = all(|dx_i| <= limits_i),
+    and on `finalize` the posterior  J2 P_ J2^T - (J2 K_x) (P_ J2^T)  with J2 the projections at dx_ and the new gravity.
+    x, x_prop, P_prop, rec (dict HTH [12, 12], HTh [12]), R and limits are doubles; returns dict(x, dx, conv, P) as doubles
+    / bool and x_mp, dx_mp, P_mp, the unrounded values."""
+    return _result(*_kf_step(x, x_prop, P_prop, rec, R, limits, finalize, None))
+
+
+def kf_step_reduced(x, x_prop, P_prop, rec, R, limits, finalize, keep):
+    """kf_step solved on the dofs `keep` alone: for a P whose other rows and columns are exactly zero (a dof without variance
+    is not estimated), where (P / R)^-1 does not exist.  The limit of kf_step as those variances go to zero: P_inv is zero
+    outside keep x keep, so those dofs return -dx_new (zero while they sit at their prediction) and P keeps its zeros."""
+    return _result(*_kf_step(x, x_prop, P_prop, rec, R, limits, finalize, keep))
+
+
+def err_mat(a, b_mp):
+    """max |a - b| of a double [23, 23] against an mp matrix, as a float."""
+    a = np.asarray(a, np.float64)
+    return float(max(abs(mp.mpf(float(a[i, j])) - b_mp[i, j]) for i in range(23) for j in range(23)))
 
 
 def err(a, b_mp):

@@ -134,7 +134,9 @@ def test_results_do_not_depend_on_the_batch(capi, scene_small):
 
 
 @pytest.mark.parametrize("kw,ext", [(dict(NUM_MATCH_POINTS=3), None), (dict(NUM_MATCH_POINTS=8), None), (dict(estimate_extrinsics=1), "xaloc"),
-                                    (dict(degeneracy_mode=2), None), (dict(MAX_NUM_ITERS=0), None), (dict(MAX_NUM_ITERS=5), None)])
+                                    (dict(degeneracy_mode=2), None), (dict(MAX_NUM_ITERS=0), None), (dict(MAX_NUM_ITERS=5), None),
+                                    (dict(LiDAR_noise=1.0), None), (dict(LiDAR_noise=1e-6), None), (dict(LIMITS=[1.0] * 22 + [1e-12]), None),
+                                    (dict(LIMITS=[1.0] * 23), None)])
 def test_parameters(capi, scene_small, kw, ext):
     from limo_velo_amd import synth
 
