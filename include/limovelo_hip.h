@@ -2172,6 +2172,95 @@ int lv_ndt_info(lv_ctx* ctx, lv_ndt_target_info* out);
 /* Forgets the target and frees its memory. */
 int lv_ndt_clear(lv_ctx* ctx);
 
+/* ---- Surface registration ------------------------------------------------------------------------------
+ * The pose of a sensor against the TSDF surface: the other half of KinectFusion, of SDF-Tracker (Bylow et al. 2013), of voxblox's
+ * ICP refinement and of voxgraph's submap registration (the reference has no counterpart).  A depth frame is tracked against the
+ * volume it fills, a scan is re-localised in a saved volume, the synthetic scans of "Surface ray casting" find their consumer.
+ * lv_surf_sample gives the interpolated distance and its gradient at world points; lv_surf_align minimises the distances of a
+ * source cloud from K initial guesses at a time, shaped as lv_ndt_align is.  (The section stands here, not behind "Surface ray
+ * casting", because its records hold an lv_graph_pose.)  The rule is the __host__ __device__ code of
+ * limo-velo_amd/csrc/lv_surf_align.hpp; tests/surf_align_ref.py restates it in numpy.  f64 throughout, every sum in one order:
+ * a call repeats its own bits, and a hypothesis gives the same bits alone as in a batch.
+ *
+ *   sample    of a world point x (f64), with o_a = (double)origin_a at the volume's present origin (after its shifts),
+ *             r = (double)resolution and n_a the grid size: u_a = (x_a - o_a) / r - 0.5; a u_a that is not finite or has
+ *             |u_a| >= 2^24 makes the point OUTSIDE.  i_a = floor(u_a), f_a = u_a - i_a; the point is OUTSIDE unless 0 <= i_a and
+ *             i_a + 1 <= n_a - 1 on every axis.  The corners are the voxels (i_x + a, i_y + b, i_z + c), a, b, c in {0, 1}; the
+ *             point is UNKNOWN unless every corner has W >= min_weight, otherwise KNOWN with phi_abc = (double)S / (double)W.
+ *               along x:  c_bc = phi_0bc + f_x * (phi_1bc - phi_0bc),   e_bc = phi_1bc - phi_0bc
+ *               along y:  c_c = c_0c + f_y * (c_1c - c_0c),   ex_c = e_0c + f_y * (e_1c - e_0c),   ey_c = c_1c - c_0c
+ *               along z:  v = c_0 + f_z * (c_1 - c_0),   gx = ex_0 + f_z * (ex_1 - ex_0),   gy = ey_0 + f_z * (ey_1 - ey_0),
+ *                         gz = c_1 - c_0
+ *             d = (r / 256) * v in metres; n = (gx, gy, gz) / 256, dimensionless: the exact gradient of the interpolant, not
+ *             normalised, zero where the field is clamped flat.  Only + - * / and floor occur.
+ *   term      for source point p (f32) at the pose (t, q), R = R(q): x = R p + t in f64, the rows summed as in "NDT
+ *             registration".  The point is IN iff sample(x) is KNOWN and |d| <= max_dist.  With a = |d| and the Huber width h:
+ *             h = 0 or a <= h gives w = 1, rho = 0.5 * d * d; otherwise w = h / a, rho = h * (a - 0.5 * h).  A = -R [p]x,
+ *             J = [ n^T , n^T A ] (1 x 6, (n^T A)_c = (n_0 A_0c + n_1 A_1c) + n_2 A_2c).  An IN point adds
+ *               H_ab <- H_ab + (w J_a) J_b  (the 21 entries of the upper triangle, a <= b, in the order of lv_ndt_result.info),
+ *               g_a <- g_a + (w d) J_a,   E <- E + rho,   and 1 to n_in.
+ *   cost      E + (double)(n_src - n_in) * rho(max_dist): every source point that is not IN pays what a point at the gate pays, so
+ *             the costs of different poses are comparable and a step cannot win by pushing points out of the band.
+ *   sums      exactly those of "NDT registration": workgroups of 256 lanes take LV_SURF_ALIGN_CHUNK consecutive source points, lane l
+ *             the points l and l + 256 of its chunk in ascending order; an xor-butterfly per wavefront, the four wavefronts added
+ *             in order, the chunk partials added in chunk order; 28 accumulators and the count.  No float atomics.
+ *   loop      each hypothesis on its own: (H + lambda diag H) delta = -g by the pose graph's 6 x 6 Cholesky (a pivot that is not
+ *             positive freezes that component: a scan on one plane does not diverge), trial pose t + dt, q * exp(dth / 2)
+ *             renormalised.  ACCEPTED iff delta is finite, the trial's n_in >= min_points and
+ *             cost_new <= cost_old + 64 eps |cost_old| (eps = 2^-52); then lambda <- max(lambda / 3, lambda_min) and the trial's
+ *             sums become the current ones (one evaluation per iteration); otherwise lambda <- min(4 lambda, lambda_max).
+ *   status    LV_SURF_ALIGN_NO_OVERLAP when n_in < min_points at the guess: the guess is returned bit for bit, cost and info
+ *             zero.  LV_SURF_ALIGN_CONVERGED when an accepted step has max-norm <= step_tol; LV_SURF_ALIGN_MAX_ITERATIONS after
+ *             max_iterations turns (accepted + rejected; 0 only scores the guesses).
+ *   best      best[0] is the hypothesis of least cost among those that are not NO_OVERLAP, the smaller index winning a tie;
+ *             best[1] its n_in.  -1, -1 with none.
+ *   limits    as lv_ndt_align's: K <= 4096, n_src <= 2^20, K * n_src <= 2^30; a guess finite with a quaternion whose norm is
+ *             within 1e-6 of 1.  min_weight >= 1, max_iterations 0..1000, min_points >= 1, max_dist finite and > 0, huber and
+ *             step_tol finite and >= 0, 0 < lambda_min <= lambda_init <= lambda_max < inf.  lv_surf_sample: n < 2^31 - 1.
+ *             K = 0 writes best only; n_src = 0 gives NO_OVERLAP everywhere with the poses untouched.
+ * Order of judgement as for the surface rays: parameters and NULL or short arguments before the context (LV_EINVAL, nothing
+ * written, "null context" last), then LV_ESTATE before lv_tsdf_configure.  Both calls READ the live volume: they change no bit of
+ * S, W, the colour layer, the mesh, the packed ray states or any stale flag.  They run on the context's stream and return when
+ * their outputs are written.  Nothing is allocated before the first call; lv_tsdf_configure and lv_destroy free the scratch. */
+/* Names: lv_surf_*, as the rays' calls are: the set of lv_tsdf_* FUNCTIONS is closed ("Surface ray casting"). */
+#define LV_SURF_SAMPLE_OUTSIDE 0
+#define LV_SURF_SAMPLE_UNKNOWN 1
+#define LV_SURF_SAMPLE_KNOWN   2
+#define LV_SURF_ALIGN_CONVERGED 0
+#define LV_SURF_ALIGN_MAX_ITERATIONS 1
+#define LV_SURF_ALIGN_NO_OVERLAP 2
+#define LV_SURF_ALIGN_CHUNK 512   /* source points per workgroup of the evaluation */
+typedef struct lv_surf_align_params {   /* 64 bytes */
+    int32_t  min_weight;         /* 1 */
+    int32_t  max_iterations;     /* 50; 0..1000 */
+    uint32_t min_points;         /* 6; >= 1 */
+    int32_t  reserved;
+    double   max_dist;           /* 0.4 m; finite, > 0 */
+    double   huber;              /* 0.1 m; finite, >= 0; 0: quadratic */
+    double   step_tol;           /* 1e-6 */
+    double   lambda_init;        /* 1e-4 */
+    double   lambda_min;         /* 1e-10 */
+    double   lambda_max;         /* 1e8 */
+} lv_surf_align_params;
+typedef struct lv_surf_align_result {   /* 264 bytes, laid out as lv_ndt_result with cost for score */
+    lv_graph_pose pose;
+    double   cost;               /* E plus the gate charge at the pose */
+    double   info[21];           /* the upper triangle of H at the pose, laid out as lv_graph_edge.info */
+    double   last_step;          /* max-norm of the last accepted step (0 when none was) */
+    double   lambda;             /* after the last iteration */
+    uint32_t n_in;               /* source points IN at the pose */
+    int32_t  status;             /* LV_SURF_ALIGN_CONVERGED, LV_SURF_ALIGN_MAX_ITERATIONS or LV_SURF_ALIGN_NO_OVERLAP */
+    uint32_t accepted, rejected;
+} lv_surf_align_result;
+void lv_default_surf_align_params(lv_surf_align_params* p);
+/* pts: n world points (x, y, z as f32 at the start of every `stride` bytes, stride >= 12).  out: 4 doubles per point (d, n_x, n_y,
+ * n_z), zeros unless KNOWN; status: one byte per point (LV_SURF_SAMPLE_*); either may be NULL, not both.  n = 0 succeeds. */
+int lv_surf_sample(lv_ctx* ctx, int min_weight, const void* pts, size_t stride, size_t n, double* out, uint8_t* status);
+/* src: n_src points in the sensor frame; guesses: K poses sensor -> world.  params NULL: the defaults.  results: K records (may be
+ * NULL when K = 0); best: 2 values. */
+int lv_surf_align(lv_ctx* ctx, const lv_surf_align_params* params, const void* src, size_t stride, size_t n_src,
+                  const lv_graph_pose* guesses, size_t K, lv_surf_align_result* results, int32_t best[2]);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 typedef struct lv_timing {
     float last_update_ms;      /* device time of the last lv_update (HIP events on the ctx stream) */

@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "lv_traj_sample", "lv_traj_smooth", "lv_traj_correct", "lv_traj_register", "lv_traj_register_cloud",
     "lv_default_ndt_params", "lv_default_ndt_align_params", "lv_ndt_build", "lv_ndt_add", "lv_ndt_fetch", "lv_ndt_align", "lv_ndt_info",
     "lv_ndt_clear",
+    "lv_default_surf_align_params", "lv_surf_sample", "lv_surf_align",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -334,6 +335,32 @@ NDT_ARGTYPES = {
                      C.POINTER(NdtResult), C.POINTER(C.c_int32)],
     "lv_ndt_info": [C.c_void_p, C.POINTER(NdtTargetInfo)],
     "lv_ndt_clear": [C.c_void_p],
+}
+
+
+class SurfAlignParams(C.Structure):  # lv_surf_align_params (64 bytes)
+    _fields_ = [("min_weight", C.c_int32), ("max_iterations", C.c_int32), ("min_points", C.c_uint32), ("reserved", C.c_int32),
+                ("max_dist", C.c_double), ("huber", C.c_double), ("step_tol", C.c_double), ("lambda_init", C.c_double),
+                ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
+class SurfAlignResult(C.Structure):  # lv_surf_align_result (264 bytes): lv_ndt_result with cost for score
+    _fields_ = [("pose", GraphPose), ("cost", C.c_double), ("info", C.c_double * 21), ("last_step", C.c_double), ("lambda_", C.c_double),
+                ("n_in", C.c_uint32), ("status", C.c_int32), ("accepted", C.c_uint32), ("rejected", C.c_uint32)]
+
+
+SURF_SAMPLE_OUTSIDE, SURF_SAMPLE_UNKNOWN, SURF_SAMPLE_KNOWN = 0, 1, 2
+SURF_ALIGN_CONVERGED, SURF_ALIGN_MAX_ITERATIONS, SURF_ALIGN_NO_OVERLAP = 0, 1, 2
+SURF_ALIGN_CHUNK = 512   # LV_SURF_ALIGN_CHUNK: source points per workgroup of the evaluation
+# the same bytes as SurfAlignResult
+SURF_ALIGN_RESULT_DTYPE = np.dtype([("t", "f8", 3), ("q", "f8", 4), ("cost", "f8"), ("info", "f8", 21), ("last_step", "f8"), ("lambda", "f8"),
+                                    ("n_in", "u4"), ("status", "i4"), ("accepted", "u4"), ("rejected", "u4")])
+
+# ctypes signatures of the surface registration (include/limovelo_hip.h "Surface registration"; tests/test_surf_align_abi.py)
+SURF_ALIGN_ARGTYPES = {
+    "lv_surf_sample": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint8)],
+    "lv_surf_align": [C.c_void_p, C.POINTER(SurfAlignParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(GraphPose), C.c_size_t,
+                      C.POINTER(SurfAlignResult), C.POINTER(C.c_int32)],
 }
 
 
@@ -1011,11 +1038,13 @@ def load_library() -> C.CDLL:
         lib.lv_default_ndt_params.argtypes = [C.POINTER(NdtParams)]
         lib.lv_default_ndt_align_params.restype = None
         lib.lv_default_ndt_align_params.argtypes = [C.POINTER(NdtAlignParams)]
+        lib.lv_default_surf_align_params.restype = None
+        lib.lv_default_surf_align_params.argtypes = [C.POINTER(SurfAlignParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **DEPTH_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
-                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES}.items():
+                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES, **SURF_ALIGN_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -1150,6 +1179,14 @@ def default_ndt_params(**kw) -> NdtParams:
 def default_ndt_align_params(**kw) -> NdtAlignParams:
     p = NdtAlignParams()
     load_library().lv_default_ndt_align_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_surf_align_params(**kw) -> SurfAlignParams:
+    p = SurfAlignParams()
+    load_library().lv_default_surf_align_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -2522,6 +2559,31 @@ class Context:
 
     def ndt_clear(self):
         self._check(self.lib.lv_ndt_clear(self.h))
+
+    # --- Surface registration (include/limovelo_hip.h "Surface registration"; limo_velo_amd.mesh has the helpers)
+    def surf_sample(self, pts, min_weight: int = 1):
+        """lv_surf_sample at world points [n, 3]: (d [n] f64 metres, n [n, 3] f64 the gradient, status [n] uint8 of SURF_SAMPLE_*);
+        d and n are zeros where the point is not KNOWN."""
+        a, stride, n = _points(np.asarray(pts, np.float32).reshape(-1, 3))
+        out = np.zeros((n, 4), np.float64)
+        status = np.zeros(n, np.uint8)
+        self._check(self.lib.lv_surf_sample(self.h, int(min_weight), a.ctypes.data_as(C.c_void_p) if n else None, C.c_size_t(stride), C.c_size_t(n),
+                                            out.ctypes.data_as(C.POINTER(C.c_double)), status.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out[:, 0].copy(), out[:, 1:].copy(), status
+
+    def surf_align(self, source, guesses, params: SurfAlignParams | None = None, **kw):
+        """lv_surf_align of source [n, 3] (sensor frame) from guesses [K, 7] f64 (t, q = x y z w, sensor -> world): (results, best)
+        with results an array of SURF_ALIGN_RESULT_DTYPE [K] and best = (index, n_in) or (-1, -1)."""
+        p = params if params is not None else default_surf_align_params(**kw)
+        a, stride, n = _points(np.asarray(source, np.float32).reshape(-1, 3))
+        g = np.ascontiguousarray(np.asarray(guesses, np.float64).reshape(-1, 7))
+        res = np.zeros(len(g), SURF_ALIGN_RESULT_DTYPE)
+        best = np.zeros(2, np.int32)
+        self._check(self.lib.lv_surf_align(self.h, C.byref(p), a.ctypes.data_as(C.c_void_p) if n else None, C.c_size_t(stride), C.c_size_t(n),
+                                           g.ctypes.data_as(C.POINTER(GraphPose)) if len(g) else None, C.c_size_t(len(g)),
+                                           res.ctypes.data_as(C.POINTER(SurfAlignResult)) if len(g) else None,
+                                           best.ctypes.data_as(C.POINTER(C.c_int32))))
+        return res, (int(best[0]), int(best[1]))
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

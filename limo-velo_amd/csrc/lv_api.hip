@@ -18,6 +18,7 @@
 #include "lv_elevation.hpp"
 #include "lv_volumes.hpp"
 #include "lv_tsdf_ray.hpp"
+#include "lv_surf_align.hpp"
 #include "lv_depth.hpp"
 
 #include <chrono>
@@ -1840,6 +1841,26 @@ int lv_surf_raycast_views(lv_ctx* c, const lv_tsdf_ray_params* p, const lv_view*
     if (capacity < total) { set_error("lv_surf_raycast_views: room for %zu results needed", total); return LV_EINVAL; }
     LV_CHECK_CTX(c);
     return c->vol.tsdf_raycast_views(c->stream, *p, views, n_views, out, normals, rgba, stats);
+}
+
+// ---- Surface registration (lv_surf_align.hip): the arguments are judged before the context, as the surface rays' are
+void lv_default_surf_align_params(lv_surf_align_params* p) { default_surf_align_params(p); }
+
+int lv_surf_sample(lv_ctx* c, int min_weight, const void* pts, size_t stride, size_t n, double* out, uint8_t* status) {
+    if (int rc = surf_check_sample_args(min_weight, pts, stride, n, out, status)) return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.surf_sample(c->stream, min_weight, pts, stride, n, out, status);
+}
+
+int lv_surf_align(lv_ctx* c, const lv_surf_align_params* params, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K,
+                  lv_surf_align_result* results, int32_t best[2]) {
+    lv_surf_align_params prm;
+    default_surf_align_params(&prm);
+    if (params) prm = *params;
+    if (const char* why = surf_check_align_params(&prm)) { set_error("lv_surf_align: %s", why); return LV_EINVAL; }
+    if (int rc = surf_check_align_args(src, stride, n_src, guesses, K, results, best)) return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.surf_align(c->stream, prm, src, stride, n_src, guesses, K, results, best);
 }
 
 // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)

@@ -275,6 +275,7 @@ void TsdfStore::release() {
     colour.release();
     rays.release();
     depth.release();
+    align.release();
     *this = TsdfStore();
 }
 

@@ -309,6 +309,23 @@ struct DepthStage {
     void release() { release_all(h_raw, h_cams, d_raw, d_cams); }
 };
 
+// The scratch of lv_surf_sample and lv_surf_align ("Surface registration"; rule in lv_surf_align.hpp, kernels in
+// lv_surf_align.hip).  Nothing is allocated before the first of them.
+struct NdtHyp;   // lv_ndt.hpp: what the loop keeps per hypothesis
+struct SurfAlignStage {
+    PointStage pts;                      // lv_surf_sample's points, lv_surf_align's source
+    DevBuf<double> d_out;                // lv_surf_sample: 4 per point
+    DevBuf<uint8_t> d_status;            // lv_surf_sample: one per point
+    DevBuf<lv_surf_align_result> d_res;
+    PinBuf<lv_surf_align_result> h_res;
+    DevBuf<NdtHyp> d_hyp;
+    PinBuf<NdtHyp> h_hyp;
+    DevBuf<double> d_part;               // SURF_PART per (hypothesis, chunk)
+    DevBuf<uint32_t> d_running;
+    PinBuf<uint32_t> h_running;
+    void release() { release_all(pts, d_out, d_status, d_res, h_res, d_hyp, h_hyp, d_part, d_running, h_running); }
+};
+
 // The volume of a context and the buffers of its calls.  Nothing is allocated before configure().
 struct TsdfStore {
     bool configured = false;
@@ -329,6 +346,7 @@ struct TsdfStore {
     ColourLayer colour;                       // the colour layer: zeroed by clear() and load(), moved by recentre(), read by mesh_build(), freed by release()
     TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), integrate_depth(), load(), clear() and recentre(), freed by release()
     DepthStage depth;                         // integrate_depth()'s staging, freed by release()
+    SurfAlignStage align;                     // surf_sample()'s and surf_align()'s scratch, freed by release()
 
     int configure(hipStream_t stream, const lv_tsdf_params& p);
     int clear(hipStream_t stream);
@@ -353,6 +371,11 @@ struct TsdfStore {
     // ---- depth fusion (lv_depth.hip).  cams, q: depth_rule's.  Marks the rays' states not packed, leaves the colour layer alone,
     // waits for the stream.
     int integrate_depth(hipStream_t stream, const lv_depth_view* views, const DepthCam* cams, const DepthRule& q, uint64_t out[4]);
+
+    // ---- registration (lv_surf_align.hip).  Both read S and W, write nothing of the store but `align`, and wait for the stream.
+    int surf_sample(hipStream_t stream, int min_weight, const void* pts, size_t stride, size_t n, double* out, uint8_t* status);
+    int surf_align(hipStream_t stream, const lv_surf_align_params& prm, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses,
+                   size_t K, lv_surf_align_result* results, int32_t best[2]);
 
     // ---- the colour layer (lv_colour.hip).  cams, q: paint_rule's.  All of them wait for the stream.
     int colour_ensure(hipStream_t stream);   // allocates the layer, all zero, where it is not present

@@ -74,6 +74,8 @@
 //   surface rays  lv_surf_raycast, lv_surf_raycast_views: SURFACE; everything else was judged before the context.  They read the
 //             volume, the layer and the store's packed states (which TsdfStore itself keeps: its integrate, load, clear and recentre
 //             mark them not packed) and touch no `stale`.
+//   surface registration  lv_surf_sample, lv_surf_align: SURFACE; everything else was judged before the context; reads the live
+//             volume, marks nothing.
 //   depth     lv_depth_integrate: SURFACE; everything else was judged before the context.  TsdfStore's integrate_depth marks the rays'
 //             packed states not packed, as its integrate does, and leaves the colour layer alone.
 //   rolling   lv_volume_recentre: the volume it names, then grid_shift_check (LV_EINVAL).  lv_volume_shift_info: nothing; a volume
@@ -661,6 +663,19 @@ struct VolumeTools {
                            float* normals, uint8_t* rgba, uint64_t stats[4]) {
         LV_SURFACE_CONFIGURED;
         return tsdf.raycast_views(stream, p.min_weight, views, n_views, out, normals, rgba, stats);
+    }
+
+    // ---- Surface registration (lv_surf_align.hip).  Only these methods reach the store's registration members.  Their entry points
+    // have judged what needs no context: the parameters, null and short arguments, the guesses.
+    int surf_sample(hipStream_t stream, int min_weight, const void* pts, size_t stride, size_t n, double* out, uint8_t* status) {
+        LV_SURFACE_CONFIGURED;
+        return tsdf.surf_sample(stream, min_weight, pts, stride, n, out, status);
+    }
+
+    int surf_align(hipStream_t stream, const lv_surf_align_params& p, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses,
+                   size_t K, lv_surf_align_result* results, int32_t best[2]) {
+        LV_SURFACE_CONFIGURED;
+        return tsdf.surf_align(stream, p, src, stride, n_src, guesses, K, results, best);
     }
 
     // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip).  volume: LV_VOLUME_OCC or LV_VOLUME_SURFACE

@@ -6,12 +6,16 @@ keep the volume as an .npz next to occupancy.save_grid's grid, and recentre() / 
 picks its occlusion parameters for a camera, build(colours=True) and save_ply(colours=...) carry the vertex colours.  raycast()
 casts rays at the surface ("Surface ray casting"), simulate_scan() a whole scan pattern from a pose, camera_pattern() and render()
 a pinhole camera's depth, normal and colour images.  integrate_depth() fuses depth-camera frames ("Depth fusion"), depth_frame()
-makes one, render_frame() renders one from the surface."""
+makes one, render_frame() renders one from the surface.  sample() reads the interpolated distance and its gradient ("Surface
+registration"), align() registers a cloud against the surface from any number of guesses, align_params_for() picks the gate and
+the Huber width from the volume, frame_points() back-projects a depth frame, track_depth() refines a camera pose against the
+volume, loop_measurement() turns a result into a pose-graph edge."""
 from __future__ import annotations
 
 import numpy as np
 
-from . import capi
+from . import capi, ndt
+from .synth import quat_to_rot
 from .occupancy import follow_shift
 
 MAX_VIEWS = 32   # views per lv_tsdf_integrate
@@ -258,3 +262,75 @@ def render_frame(ctx, R, t, fx, fy, cx, cy, width, height, max_range=None, min_w
     integrate_depth() of another context."""
     depth, _, _ = render(ctx, R, t, fx, fy, cx, cy, width, height, max_range, min_weight)
     return depth_frame(depth, R, t, fx, fy, cx, cy)
+
+
+def sample(ctx, pts, min_weight: int = 1):
+    """lv_surf_sample at world points [n, 3]: (d [n] f64 metres, n [n, 3] f64, status [n] uint8): the trilinear distance to the
+    surface, positive on the sensor's side, and the exact gradient of that interpolant (about unit length inside the band, zero
+    where the field is clamped); zeros where status is not capi.SURF_SAMPLE_KNOWN (outside the volume, or next to a voxel below
+    min_weight)."""
+    return ctx.surf_sample(pts, min_weight)
+
+
+def align_params_for(ctx, **kw):
+    """lv_surf_align_params for ctx's volume: max_dist = (trunc_cells - 1) * resolution, inside which the fused distances are not
+    clamped, and huber = resolution / 2; kw overrides any field (a volume with trunc_cells = 1 needs its own max_dist)."""
+    p = ctx.tsdf_params()
+    res = float(p.resolution)
+    return capi.default_surf_align_params(**dict(dict(max_dist=(p.trunc_cells - 1) * res, huber=res / 2), **kw))
+
+
+def align(ctx, points, guesses, **kw):
+    """lv_surf_align of points [n, 3] (sensor frame) against the surface from guesses [K, 7] (t, q = x y z w, sensor -> world) with
+    align_params_for(ctx, **kw): (results [K] of capi.SURF_ALIGN_RESULT_DTYPE, best = (index, n_in) or (-1, -1))."""
+    return ctx.surf_align(points, guesses, align_params_for(ctx, **kw))
+
+
+def frame_points(frame, stride: int = 1) -> np.ndarray:
+    """[n, 3] f32: the pixels of a depth_frame() with a valid depth (finite and > 0), every stride-th row and column, as points in
+    the camera frame (z forward, x right, y down; pixel centres at whole u, v as in camera_pattern()).  Pinhole only."""
+    if "dist" in frame and np.any(np.asarray(frame["dist"]) != 0):
+        raise ValueError("frame_points: a distorted frame is not supported (dist must be zero)")
+    d = np.asarray(frame["depth"])
+    z = d.astype(np.float64) * (float(frame.get("depth_scale", 0.001)) if d.dtype.kind in "ui" else 1.0)
+    s = int(stride)
+    if s < 1:
+        raise ValueError("frame_points: stride >= 1")
+    v, u = np.meshgrid(np.arange(0, d.shape[0], s, dtype=np.float64), np.arange(0, d.shape[1], s, dtype=np.float64), indexing="ij")
+    z = z[::s, ::s]
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(z) & (z > 0)
+    z, u, v = z[ok], u[ok], v[ok]
+    return np.stack([(u - float(frame["cx"])) / float(frame["fx"]) * z, (v - float(frame["cy"])) / float(frame["fy"]) * z, z], axis=1).astype(np.float32)
+
+
+def _quat_of(R) -> np.ndarray:
+    """x, y, z, w of a rotation matrix (Shepperd's branches)"""
+    R = np.asarray(R, np.float64).reshape(3, 3)
+    k = int(np.argmax([R[0, 0], R[1, 1], R[2, 2], np.trace(R)]))
+    if k == 3:
+        q = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], 1.0 + np.trace(R)])
+    else:
+        i, j, l = k, (k + 1) % 3, (k + 2) % 3
+        q = np.zeros(4)
+        q[i] = 1.0 + R[i, i] - R[j, j] - R[l, l]
+        q[j] = R[j, i] + R[i, j]
+        q[l] = R[l, i] + R[i, l]
+        q[3] = R[l, j] - R[j, l]
+    return q / np.linalg.norm(q)
+
+
+def track_depth(ctx, frame, guess=None, stride: int = 4, **kw):
+    """The pose of a depth camera against the volume: frame_points(frame, stride) aligned from guess = (R, t) camera -> world (None:
+    the frame's own pose).  Returns (R [3, 3] f64, t [3] f64, result): the refined pose and its capi.SURF_ALIGN_RESULT_DTYPE record
+    (status capi.SURF_ALIGN_NO_OVERLAP: the guess, untouched)."""
+    R0, t0 = (frame["R"], frame["t"]) if guess is None else guess
+    g = np.concatenate([np.asarray(t0, np.float64).reshape(3), _quat_of(R0)])
+    res, _ = align(ctx, frame_points(frame, stride), g[None], **kw)
+    return quat_to_rot(res[0]["q"]), res[0]["t"].copy(), res[0]
+
+
+def loop_measurement(x_i, result):
+    """ndt.loop_measurement for a surface registration: (t, q, info) of T_i^-1 T_j for PoseGraph.add_registration, where the volume
+    is in the frame keyframe i's pose x_i is given in."""
+    return ndt.loop_measurement(x_i, result)
