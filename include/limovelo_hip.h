@@ -1492,6 +1492,58 @@ void lv_default_occ_mark_params(lv_occ_mark_params* p);
 /* stats (may be NULL): points used, voxels holding >= min_points, voxels marked, voxels left alone because they were observed. */
 int  lv_occ_mark(lv_ctx* ctx, const lv_occ_mark_params* p, const void* pts, size_t stride, size_t n, uint64_t stats[4]);
 
+/* ---- Occupancy from the surface --------------------------------------------------------------------------
+ * The way from the TSDF volume to the occupancy grid (the TSDF -> ESDF / costmap step of Voxblox and nvblox; the reference has no
+ * counterpart).  lv_occ_from_surface classifies the volume's voxels into solid, open and unknown, optionally grows the solid ones
+ * by whole voxels, and writes the result into the occupancy grid on the device, in the grid's own terms: everything built from
+ * the grid (distance field, plans, frontiers, rays, localisation, lv_occ_project) then works for a robot that fuses depth images,
+ * and the distance field of such a grid is the ESDF of the surface.  One f32 step, integers after it: a pure function of the
+ * volume, the grid and the parameters, bitwise reproducible.
+ *   voxels   with S, W as in "TSDF and mesh", a TSDF voxel is KNOWN iff W >= min_weight (1..2^18), SOLID iff KNOWN and
+ *            (int64)S <= (int64)band * W (its fused distance is at most band / 256 voxel; band in -4096..4096: 0 gives the
+ *            voxels on or behind the surface, a positive band thickens walls towards the sensor, a band beyond +-T makes
+ *            everything known, or nothing, solid), OPEN iff KNOWN and not SOLID.
+ *   class    of voxel v = (i, j, k) of the inclusive box lo..hi clipped to the grid as lv_occ_mark's.  Its centre is
+ *            c_a = origin_g[a] + (((float)v_a + 0.5f) * resolution_g), f32, unfused, in that order; c is quantised in the volume
+ *            as lv_tsdf_query quantises a point (occ_quant of "Occupancy grid" against the volume's origin and resolution, then
+ *            q >> 8), which gives the TSDF voxel u.  An axis that does not quantise, or u outside the volume: v is OUTSIDE, its
+ *            class NONE.  Otherwise OCCUPIED iff any TSDF voxel u + d, d in [-reach, reach]^3 (reach 0..4), inside the volume, is
+ *            SOLID; else FREE iff u itself is OPEN; else NONE.  Free space is never grown: unknown space is never declared free
+ *            by a neighbour.  Both volumes stand at their current origins, origin0 + (float)shift * resolution ("Rolling
+ *            volumes"), and may differ in origin, resolution, shape and shift.
+ *   write    with a = fminf(fmaxf(l_solid, l_min), l_max) and b = fminf(fmaxf(l_open, l_min), l_max) from the grid's clamps
+ *            (l_solid, l_open finite, l_open < 0 < l_solid):
+ *              LV_OCC_SURFACE_FILL        only where L is NaN: OCCUPIED -> a, FREE -> b.  Observed voxels and NONE are left alone:
+ *                                         ray evidence is never overridden (lv_occ_mark's only_unknown).
+ *              LV_OCC_SURFACE_OVERWRITE   the same whatever L held; NONE is left alone.
+ *              LV_OCC_SURFACE_REPLACE     as OVERWRITE, and NONE -> never observed (bits 0x7FC00000): inside the box the grid
+ *                                         becomes a pure function of the volume.
+ *              LV_OCC_SURFACE_ACCUMULATE  OCCUPIED -> fminf(fmaxf((isnan(L) ? 0 : L) + l_solid, l_min), l_max), FREE the same with
+ *                                         l_open, once per call; NONE is left alone.  Surface evidence adds to LiDAR evidence.
+ *            Every value written is NaN or lies in [l_min, l_max].  The field and the frontier go stale iff a voxel's 32 bits
+ *            changed; nothing of the volume, its colour layer, its mesh or its packed ray states is touched.
+ * The parameters are judged before the context (LV_EINVAL, messages prefixed "lv_occ_from_surface: ", the null context last), then
+ * LV_ESTATE without an occupancy grid, then LV_ESTATE without a TSDF volume; a box that is empty after clipping gives LV_OK and
+ * zero stats before anything else is touched.  Three bitmaps of the volume (one bit per voxel each) are allocated by the first
+ * call and kept until lv_occ_configure. */
+#define LV_OCC_SURFACE_FILL        0
+#define LV_OCC_SURFACE_OVERWRITE   1
+#define LV_OCC_SURFACE_REPLACE     2
+#define LV_OCC_SURFACE_ACCUMULATE  3
+typedef struct lv_occ_surface_params {
+    int lo[3], hi[3];        /* inclusive voxel box of the occupancy grid, clipped to it as lv_occ_mark's */
+    int min_weight;          /* 1..2^18 */
+    int band;                /* -4096..4096, in 1/256 voxel of the TSDF */
+    int reach;               /* 0..4 TSDF voxels */
+    int mode;                /* one of the four above */
+    float l_solid, l_open;   /* finite, l_open < 0 < l_solid */
+} lv_occ_surface_params;
+/* Defaults: the whole grid (lo 0, hi 2^30), min_weight 1, band 0, reach 0, mode LV_OCC_SURFACE_FILL, l_solid 3.5, l_open -2.0. */
+void lv_default_occ_surface_params(lv_occ_surface_params* p);
+/* stats (may be NULL): voxels of the box classed OCCUPIED, classed FREE, voxels whose 32 bits changed, voxels of the box that are
+ * OUTSIDE. */
+int  lv_occ_from_surface(lv_ctx* ctx, const lv_occ_surface_params* p, uint64_t stats[4]);
+
 /* ---- Localizator side ----------------------------------------------------------------------- */
 /* `this->points2match = points`                   — src/Modules/Localizator.cpp:131.
  * Uploads the scan (LiDAR frame) once per correct(); it is invariant across IKFoM passes. */

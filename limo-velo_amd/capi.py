@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "lv_default_ndt_params", "lv_default_ndt_align_params", "lv_ndt_build", "lv_ndt_add", "lv_ndt_fetch", "lv_ndt_align", "lv_ndt_info",
     "lv_ndt_clear",
     "lv_default_surf_align_params", "lv_surf_sample", "lv_surf_align",
+    "lv_default_occ_surface_params", "lv_occ_from_surface",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -776,6 +777,20 @@ VOLUME_ARGTYPES = {
 }
 
 
+LV_OCC_SURFACE_FILL, LV_OCC_SURFACE_OVERWRITE, LV_OCC_SURFACE_REPLACE, LV_OCC_SURFACE_ACCUMULATE = 0, 1, 2, 3
+
+
+class OccSurfaceParams(C.Structure):  # lv_occ_surface_params
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("min_weight", C.c_int), ("band", C.c_int), ("reach", C.c_int), ("mode", C.c_int),
+                ("l_solid", C.c_float), ("l_open", C.c_float)]
+
+
+# ctypes signatures of the way from the surface to the grid (include/limovelo_hip.h "Occupancy from the surface"; tests/test_surf_occ_abi.py)
+OCC_SURFACE_ARGTYPES = {
+    "lv_occ_from_surface": [C.c_void_p, C.POINTER(OccSurfaceParams), C.POINTER(C.c_uint64)],
+}
+
+
 def camera_view(frame):
     """(LvCameraView, image array it points into) from a frame dict: R [3, 3] and t [3] camera -> world, fx, fy, cx, cy, image
     ([h, w, 3] or [h, w] uint8; rows may be strided), optional format (LV_IMAGE_*; default RGB8, MONO8 for a 2-D image) and dist
@@ -1040,11 +1055,14 @@ def load_library() -> C.CDLL:
         lib.lv_default_ndt_align_params.argtypes = [C.POINTER(NdtAlignParams)]
         lib.lv_default_surf_align_params.restype = None
         lib.lv_default_surf_align_params.argtypes = [C.POINTER(SurfAlignParams)]
+        lib.lv_default_occ_surface_params.restype = None
+        lib.lv_default_occ_surface_params.argtypes = [C.POINTER(OccSurfaceParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
                                **CLUSTER_ARGTYPES, **PLANE_ARGTYPES, **OCCUPANCY_ARGTYPES, **DISTANCE_ARGTYPES, **PLAN_ARGTYPES, **LATTICE_ARGTYPES,
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **DEPTH_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
-                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES, **SURF_ALIGN_ARGTYPES}.items():
+                               **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES, **SURF_ALIGN_ARGTYPES,
+                               **OCC_SURFACE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -1331,6 +1349,17 @@ def default_tsdf_ray_params(**kw) -> TsdfRayParams:
 def default_occ_mark_params(**kw) -> OccMarkParams:
     p = OccMarkParams()
     load_library().lv_default_occ_mark_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("lo", "hi"):
+            getattr(p, k)[:] = [int(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def default_occ_surface_params(**kw) -> OccSurfaceParams:
+    p = OccSurfaceParams()
+    load_library().lv_default_occ_surface_params(C.byref(p))
     for k, v in kw.items():
         if k in ("lo", "hi"):
             getattr(p, k)[:] = [int(x) for x in v]
@@ -2292,6 +2321,14 @@ class Context:
                 a, stride = np.zeros((1, 3), np.float32), 12
         self._check(self.lib.lv_occ_mark(self.h, C.byref(p), None if a is None else C.c_void_p(a.ctypes.data), C.c_size_t(stride), C.c_size_t(n),
                                          stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
+
+    def occ_from_surface(self, params: OccSurfaceParams | None = None) -> np.ndarray:
+        """lv_occ_from_surface ("Occupancy from the surface"): the occupancy grid's box filled from the TSDF volume; returns stats
+        [4] uint64: voxels classed OCCUPIED, classed FREE, voxels whose bits changed, voxels outside the volume."""
+        p = params if params is not None else default_occ_surface_params()
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_occ_from_surface(self.h, C.byref(p), stats.ctypes.data_as(C.POINTER(C.c_uint64))))
         return stats
 
     # --- place recognition (include/limovelo_hip.h "Place recognition")

@@ -20,6 +20,7 @@
 #include "lv_tsdf_ray.hpp"
 #include "lv_surf_align.hpp"
 #include "lv_depth.hpp"
+#include "lv_surf_occ.hpp"
 
 #include <chrono>
 
@@ -1490,6 +1491,16 @@ int lv_occ_mark(lv_ctx* c, const lv_occ_mark_params* p, const void* pts, size_t 
     uint32_t n_ids, m;
     if (int rc = map_side(c).source(pts, &d_orig, &n_ids, &m)) return rc;
     return c->vol.occ_mark(c->stream, *p, lo, hi, d_orig, n_ids, pts, stride, n, stats);
+}
+
+// ---- Occupancy from the surface (lv_surf_occ.hip)
+void lv_default_occ_surface_params(lv_occ_surface_params* p) { default_occ_surface_params(p); }
+
+int lv_occ_from_surface(lv_ctx* c, const lv_occ_surface_params* p, uint64_t stats[4]) {
+    char why[96];
+    if (!surf_occ_check_params(p, why, sizeof(why))) { set_error("lv_occ_from_surface: %s", why); return LV_EINVAL; }
+    LV_CHECK_CTX(c);
+    return c->vol.occ_from_surface(c->stream, *p, stats);
 }
 
 // ---- Distance field (lv_distance.hip)

@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void occ_mark_apply_kernel(float* __restrict__
 }  // namespace
 
 void OccStore::release() {
-    d_L.release(); d_L2.release(); d_bits.release(); stats.release(); pts.release(); d_out.release(); d_proj.release();
+    d_L.release(); d_L2.release(); d_bits.release(); stats.release(); pts.release(); d_out.release(); d_proj.release(); d_sbits.release();
     *this = OccStore();
 }
 

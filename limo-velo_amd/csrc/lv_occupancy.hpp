@@ -14,6 +14,8 @@
 
 namespace lv {
 
+struct TsdfStore;   // lv_tsdf.hpp: what from_surface() reads
+
 constexpr int OCC_MAX_VIEWS = 32;
 constexpr int OCC_MAX_DIM = 1024;
 constexpr uint64_t OCC_MAX_VOXELS = (uint64_t)1 << 28;
@@ -198,6 +200,7 @@ struct OccStore {
     PointStage pts;                // every view's returns, or the query points
     DevBuf<float> d_out;           // lv_occ_query's results
     DevBuf<int8_t> d_proj;         // lv_occ_project's result (nx * ny)
+    DevBuf<uint32_t> d_sbits;      // lv_occ_from_surface's three bitmaps of the TSDF volume (SOLID, OPEN, a spare), in d_bits' layout.  Not allocated before the first call
 
     int configure(hipStream_t stream, const lv_occupancy_params& p);
     int clear(hipStream_t stream);
@@ -211,6 +214,9 @@ struct OccStore {
     // lo..hi: already clipped to the grid, not empty.  The points: map_orig (the map's float4 per id, n_ids of them; the living ones count) or the caller's
     int mark(hipStream_t stream, const lv_occ_mark_params& p, const int lo[3], const int hi[3], const void* map_orig, uint32_t n_ids,
              const void* points, size_t stride, size_t n, uint64_t out[4]);
+    // lv_surf_occ.hip ("Occupancy from the surface").  lo..hi: already clipped to the grid, not empty.  out: voxels classed OCCUPIED,
+    // classed FREE, voxels whose bits changed, voxels OUTSIDE the volume
+    int from_surface(hipStream_t stream, const TsdfStore& tsdf, const lv_occ_surface_params& p, const int lo[3], const int hi[3], uint64_t out[4]);
     void release();
 };
 

@@ -18,6 +18,9 @@
 //                                             |   zeroes stats)                             |
 //   lv_occ_mark                               | after success, and only if it wrote a voxel |
 //                                             |   (st[2] != 0)                              |
+//   lv_occ_from_surface                       | after success, and only if it changed a     |
+//                                             |   voxel's bits (st[2] != 0); it marks       |
+//                                             |   nothing on the surface side               |
 //   ------------------------------------------+---------------------------------------------+---------------------------------
 //   lv_occ_distance_build, _build_cells       | before the build, whatever it returns        | FIELD EDIT: plan.stale = 1
 //     (after its plane-size check)            |                                             |   where built
@@ -81,6 +84,8 @@
 //   rolling   lv_volume_recentre: the volume it names, then grid_shift_check (LV_EINVAL).  lv_volume_shift_info: nothing; a volume
 //             that is not configured and a product that is not built (or whose grid is not configured) report zeros.
 //   mark      GRID, then the box clipped to the grid (an empty one: LV_OK, zero stats, before the point map is looked at).
+//   from surface  lv_occ_from_surface: GRID, SURFACE, then the box clipped to the grid (an empty one: LV_OK, zero stats, no store
+//             call); the parameters were judged before the context.  It reads the live volume and writes nothing of it.
 #pragma once
 #include <cstring>
 
@@ -242,6 +247,22 @@ struct VolumeTools {
         const int rc = pts ? occ.mark(stream, p, lo, hi, nullptr, 0, pts, stride, n, st) : occ.mark(stream, p, lo, hi, map_orig, n_ids, nullptr, 0, 0, st);
         if (rc) return rc;
         if (st[2]) grid_edited();
+        if (stats)
+            for (int i = 0; i < 4; ++i) stats[i] = st[i];
+        return LV_OK;
+    }
+
+    // ---- Occupancy from the surface (lv_surf_occ.hip).  Only this method reaches the store's from_surface.  Its entry point has
+    // judged the parameters (surf_occ_check_params).
+    int occ_from_surface(hipStream_t stream, const lv_occ_surface_params& p, uint64_t stats[4]) {
+        LV_GRID_CONFIGURED;
+        LV_SURFACE_CONFIGURED;
+        uint64_t st[4] = {0, 0, 0, 0};
+        int lo[3], hi[3];
+        if (grid_clip_box(occ.grid, p.lo, p.hi, lo, hi)) {
+            if (int rc = occ.from_surface(stream, tsdf, p, lo, hi, st)) return rc;
+            if (st[2]) grid_edited();
+        }
         if (stats)
             for (int i = 0; i < 4; ++i) stats[i] = st[i];
         return LV_OK;

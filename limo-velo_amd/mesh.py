@@ -9,7 +9,8 @@ a pinhole camera's depth, normal and colour images.  integrate_depth() fuses dep
 makes one, render_frame() renders one from the surface.  sample() reads the interpolated distance and its gradient ("Surface
 registration"), align() registers a cloud against the surface from any number of guesses, align_params_for() picks the gate and
 the Huber width from the volume, frame_points() back-projects a depth frame, track_depth() refines a camera pose against the
-volume, loop_measurement() turns a result into a pose-graph edge."""
+volume, loop_measurement() turns a result into a pose-graph edge.  to_occupancy() fills the occupancy grid from the volume
+("Occupancy from the surface"), configuring one like the volume where there is none."""
 from __future__ import annotations
 
 import numpy as np
@@ -334,3 +335,25 @@ def loop_measurement(x_i, result):
     """ndt.loop_measurement for a surface registration: (t, q, info) of T_i^-1 T_j for PoseGraph.add_registration, where the volume
     is in the frame keyframe i's pose x_i is given in."""
     return ndt.loop_measurement(x_i, result)
+
+
+def to_occupancy(ctx, **kw) -> np.ndarray:
+    """The occupancy grid filled from the volume (occupancy.from_surface; kw as there, mode included).  Where no grid is configured
+    one is configured like the volume first: its origin, resolution, shape and ranges, the log-odds constants at their defaults
+    (the inverse of like_occupancy()).  Returns from_surface's stats."""
+    from . import occupancy
+
+    try:
+        ctx.occ_params()
+    except capi.LvError as e:
+        if "no occupancy grid" not in str(e):
+            raise
+        t = ctx.tsdf_params()
+        p = capi.default_occupancy_params()
+        for f in _SHARED:
+            if f == "origin":
+                p.origin[:] = [float(v) for v in t.origin]
+            else:
+                setattr(p, f, getattr(t, f))
+        ctx.occ_configure(p)
+    return occupancy.from_surface(ctx, **kw)

@@ -11,7 +11,8 @@ the robot and hands back targets with their routes.  raycast() / line_of_sight()
 from a place and view_gain() how much unknown space a pose would uncover (lv_occ_raycast, lv_occ_view_gain, "Ray casting"); with a
 gain_pattern explore() reports that gain at every target.  recentre() / follow() move the grid's box with the robot by whole
 voxels (lv_volume_recentre, "Rolling volumes"), exposed_boxes() names the strips a shift uncovered and mark_from_map() fills them
-from the device map's points (lv_occ_mark)."""
+from the device map's points (lv_occ_mark).  from_surface() fills the grid from the TSDF volume (lv_occ_from_surface, "Occupancy
+from the surface") and surface_costmap() projects the result: the costmap of a robot that fuses depth images."""
 from __future__ import annotations
 
 import math
@@ -370,7 +371,8 @@ def follow_shift(params, position, keep=0.25, step=32, axes=(True, True, False))
 def follow(ctx, position, keep=0.25, step=32, axes=(True, True, False)):
     """Keeps the grid round the robot: when the voxel of `position` is more than keep * n voxels from the grid's centre on a
     followed axis (default x and y), the grid is recentred along that axis by the multiple of `step` voxels that brings the
-    position nearest the centre.  Returns the shift applied, (0, 0, 0) when the grid stayed."""
+    position nearest the centre.  Returns the shift applied, (0, 0, 0) when the grid stayed.  The strip it exposed
+    (exposed_boxes()) can be filled from the point map (mark_from_map()) or from the TSDF surface (from_surface())."""
     d = follow_shift(ctx.occ_params(), position, keep, step, axes)
     if any(d):
         recentre(ctx, d)
@@ -380,7 +382,8 @@ def follow(ctx, position, keep=0.25, step=32, axes=(True, True, False)):
 def exposed_boxes(params, shift):
     """The voxels a recentre by `shift` left never observed, as up to three disjoint inclusive voxel boxes [(lo, hi)] of the
     SHIFTED grid, in the form lv_occ_mark takes: the strip across x, the strip across y of what x kept, the strip across z of
-    what x and y kept.  (A shift of a whole grid or more gives the whole grid as one box.)"""
+    what x and y kept.  (A shift of a whole grid or more gives the whole grid as one box.)  from_surface() takes the same boxes:
+    the exposed voxels can be filled from the TSDF surface as well as by mark_from_map()."""
     n = (int(params.nx), int(params.ny), int(params.nz))
     kept, gone = [], []
     for a in range(3):
@@ -407,3 +410,23 @@ def mark_from_map(ctx, box=None, min_points=1, only_unknown=True, l_mark=None) -
     if l_mark is not None:
         kw["l_mark"] = float(l_mark)
     return ctx.occ_mark(capi.default_occ_mark_params(**kw))
+
+
+def from_surface(ctx, mode=capi.LV_OCC_SURFACE_FILL, box=None, **kw) -> np.ndarray:
+    """lv_occ_from_surface ("Occupancy from the surface"): the voxels of `box` = (lo, hi) (inclusive voxel indices, default the
+    whole grid) take what the TSDF volume says of their centres: OCCUPIED where a solid TSDF voxel lies within `reach` voxels,
+    FREE where their own TSDF voxel is known and open, nothing otherwise.  mode: capi.LV_OCC_SURFACE_FILL writes only never
+    observed voxels (ray evidence stays), _OVERWRITE every classed voxel, _REPLACE also forgets the voxels the volume knows nothing
+    of, _ACCUMULATE adds l_solid / l_open to what the voxel holds.  kw: min_weight, band, reach, l_solid, l_open.  Returns stats
+    [4] uint64: voxels classed OCCUPIED, classed FREE, voxels changed, voxels outside the volume."""
+    kw = dict(kw, mode=int(mode))
+    if box is not None:
+        kw.update(lo=box[0], hi=box[1])
+    return ctx.occ_from_surface(capi.default_occ_surface_params(**kw))
+
+
+def surface_costmap(ctx, k_lo: int, k_hi: int, **kw) -> np.ndarray:
+    """The costmap of a robot that fuses depth images: the whole grid becomes a pure function of the TSDF volume (from_surface in
+    mode REPLACE; kw as there), then lv_occ_project over the layers k_lo..k_hi: [ny, nx] int8, 100 occupied, 0 free, -1 unknown."""
+    from_surface(ctx, capi.LV_OCC_SURFACE_REPLACE, None, **kw)
+    return ctx.occ_project(k_lo, k_hi)
