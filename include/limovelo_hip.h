@@ -2313,6 +2313,71 @@ int lv_surf_sample(lv_ctx* ctx, int min_weight, const void* pts, size_t stride, 
 int lv_surf_align(lv_ctx* ctx, const lv_surf_align_params* params, const void* src, size_t stride, size_t n_src,
                   const lv_graph_pose* guesses, size_t K, lv_surf_align_result* results, int32_t best[2]);
 
+/* ---- Submap merging ------------------------------------------------------------------------------------
+ * One TSDF volume resampled into the context's volume under a rigid pose and folded in as evidence: mergeLayerAintoLayerB of
+ * Voxblox and voxgraph, the other half of the submap workflow whose registration is lv_surf_align (the reference has no
+ * counterpart).  A long run is kept as small submaps (saved volumes, each with a pose-graph node) and the global surface is
+ * rebuilt from them after every optimisation; two robots' volumes, or volumes of another resolution, are fused.  A submap is a
+ * volume as lv_tsdf_fetch gives it, with the grid it was fetched from; `pose` carries the submap's frame into the world.  (The
+ * section stands here because the call takes an lv_graph_pose.)  The rule is the __host__ __device__ code of
+ * limo-velo_amd/csrc/lv_surf_merge.hpp; tests/surf_merge_ref.py restates it in numpy.  It is shaped like "Depth fusion": one
+ * thread owns a destination voxel, there are no atomics on the volume, and after one f64 step everything is integers, so the
+ * result is the same bits whatever the schedule.
+ * For every destination voxel.  Every f64 operation is a single rounded operation in the order written; nothing is fused.
+ * Everything after step 3 is integers.  FR = 32.
+ *   1. centre    p_a: the f32 centre of "Depth fusion" step 1, with the volume's present origin (after its shifts), widened to
+ *                f64.
+ *   2. into the submap   d = p - t; x_b = (R_0b d_0 + R_1b d_1) + R_2b d_2, that is R^T d, with R = R(q) as "NDT registration"
+ *                builds it.
+ *   3. lattice   u_b = (x_b - (double)sub.origin_b) / (double)sub.resolution - 0.5.  A u_b that is not finite or has
+ *                |u_b| >= 2^24 makes the voxel OUTSIDE.  LV_MERGE_TRILINEAR: e_b = (int64)floor(u_b * 32.0 + 0.5), the position
+ *                rounded to 1/32 of a source voxel.  LV_MERGE_NEAREST: e_b = 32 * (int64)floor(u_b + 0.5).  i_b = e_b >> 5 (floor)
+ *                and f_b = e_b & 31.
+ *   4. corners   corner (a, b, c) in {0, 1}^3 is the source voxel (i_x + a, i_y + b, i_z + c) with the weight w = wx wy wz,
+ *                w_axis = f for offset 1 and 32 - f for offset 0; the weights sum to 2^15.  Corners of weight 0 are not read and
+ *                need not exist: a voxel on the submap's last layer with f = 0 is still inside.  The voxel is OUTSIDE if a corner of
+ *                non-zero weight lies outside [0, n - 1] on an axis; otherwise UNKNOWN if such a corner has W_c < min_weight;
+ *                otherwise KNOWN.
+ *   5. distances a_c = floor(S_c * 256 / W_c) in int64 (|a_c| <= 2^20, since |S| <= Ts * W and Ts <= 2^12); m = sum w a_c
+ *                (|m| <= 2^35); Wn = sum w W_c (<= 2^33).  The distances are interpolated unweighted by W: a W-weighted mean does
+ *                not reproduce a linear field (0.6 voxel off where W varies 1..40: tests/test_surf_merge_ref.py shows it).
+ *   6. units     kq = (int64)floorf((sub.resolution / resolution) * 4096.0f + 0.5f), once per call in f32; LV_EINVAL unless
+ *                512 <= kq <= 32768, a resolution ratio of 1/8 to 8.  sbar = floor(m * kq / 2^27), the distance in 1/256
+ *                destination sub-unit (|m * kq| <= 2^50).  With Td the volume's T: sbar < -256 Td gives no contribution, the voxel is
+ *                DROPPED; sbar > 256 Td gives sbar = 256 Td.
+ *   7. weight    dW = max(1, Wn >> 15), dS = floor(sbar * dW / 256) (|sbar * dW| <= 2^38, |dS| <= Td * dW <= 2^30).  Then the
+ *                voxel folds exactly as "TSDF and mesh" (one call) folds (dS, dW) with the volume's max_weight: |S + dS| <= 2^31
+ *                (|S| <= Td * max_weight <= 2^30; the sum is held in int64) and the product (S + dS) * max_weight stays below 2^55.
+ * Integer sums commute: merging A then B equals B then A bit for bit while W stays below max_weight (at max_weight the fold
+ * rescales, as in "Depth fusion").  At the identity, and at whole-voxel shifts on one lattice with equal resolution, dW = W and
+ * |dS - S| <= 1 + W / 256 (the floor of step 5).
+ *   stats      voxels not OUTSIDE; voxels that contribute (dW > 0: KNOWN and not DROPPED); the sum of dW; voxels DROPPED.
+ *   limits     the submap's grid as lv_tsdf_configure's (origin finite, resolution finite and > 0, nx, ny, nz each 1..1024,
+ *              nx * ny * nz <= 2^28), trunc_cells 1..16 (Ts = 256 * trunc_cells); every source voxel 0 <= W <= 2^18 and
+ *              |S| <= Ts * W, judged as lv_tsdf_load judges a load; the pose finite with a quaternion whose norm is within 1e-6
+ *              of 1; min_weight >= 1; interp LV_MERGE_TRILINEAR or LV_MERGE_NEAREST.
+ * Order of judgement as for lv_depth_integrate: the arguments before the context (LV_EINVAL, nothing written; the null context
+ * last), then LV_ESTATE before lv_tsdf_configure, then kq against the volume's resolution (LV_EINVAL).  Once its arguments hold,
+ * and whatever it then returns, the call sets a built mesh's stale = 1 and makes the next lv_surf_raycast pack the states anew,
+ * as lv_tsdf_integrate does; it leaves the colour layer alone and never touches the occupancy side.  A submap whose box cannot
+ * meet the volume gives LV_OK, zero stats and no launch.  The submap is staged once per call; the call runs on the context's
+ * stream and returns when stats are written.
+ * Known limits: colours are not merged: the submap carries no colour layer and the volume's layer is left as it is.  The
+ * distance is resampled, not re-measured: under a rotation the truncation band keeps its width along the old rays, as in Voxblox.
+ * A voxel takes evidence only where all its corners of non-zero weight are known, so a merged surface ends half a source voxel
+ * inside the submap's known region. */
+/* Names: lv_surf_*, as the registration's calls are: the set of lv_tsdf_* FUNCTIONS is closed ("Surface ray casting"). */
+enum { LV_MERGE_TRILINEAR = 0, LV_MERGE_NEAREST = 1 };
+typedef struct lv_surf_submap {          /* 48 bytes: a volume as lv_tsdf_fetch gives it, with the grid it was fetched from */
+    float origin[3]; float resolution; int nx, ny, nz; int trunc_cells;
+    const int32_t* S; const int32_t* W;  /* nx * ny * nz each, x fastest */
+} lv_surf_submap;
+typedef struct lv_surf_merge_params { int32_t min_weight; int32_t interp; int32_t reserved[2]; } lv_surf_merge_params;   /* 16 bytes */
+/* Defaults: min_weight 1, LV_MERGE_TRILINEAR. */
+void lv_default_surf_merge_params(lv_surf_merge_params* p);
+/* pose: submap -> world.  p NULL: the defaults.  stats (may be NULL) as above. */
+int  lv_surf_merge(lv_ctx* ctx, const lv_surf_submap* sub, const lv_graph_pose* pose, const lv_surf_merge_params* p, uint64_t stats[4]);
+
 /* ---- instrumentation ------------------------------------------------------------------------- */
 typedef struct lv_timing {
     float last_update_ms;      /* device time of the last lv_update (HIP events on the ctx stream) */

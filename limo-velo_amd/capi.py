@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     "lv_ndt_clear",
     "lv_default_surf_align_params", "lv_surf_sample", "lv_surf_align",
     "lv_default_occ_surface_params", "lv_occ_from_surface",
+    "lv_default_surf_merge_params", "lv_surf_merge",
 ]
 
 # ctypes signatures of the map queries (include/limovelo_hip.h "Map queries"; tests/test_map_query_abi.py holds them to the header)
@@ -362,6 +363,24 @@ SURF_ALIGN_ARGTYPES = {
     "lv_surf_sample": [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_uint8)],
     "lv_surf_align": [C.c_void_p, C.POINTER(SurfAlignParams), C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(GraphPose), C.c_size_t,
                       C.POINTER(SurfAlignResult), C.POINTER(C.c_int32)],
+}
+
+
+LV_MERGE_TRILINEAR, LV_MERGE_NEAREST = 0, 1
+
+
+class SurfSubmap(C.Structure):  # lv_surf_submap (48 bytes)
+    _fields_ = [("origin", C.c_float * 3), ("resolution", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("trunc_cells", C.c_int),
+                ("S", C.POINTER(C.c_int32)), ("W", C.POINTER(C.c_int32))]
+
+
+class SurfMergeParams(C.Structure):  # lv_surf_merge_params (16 bytes)
+    _fields_ = [("min_weight", C.c_int32), ("interp", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# ctypes signatures of the submap merge (include/limovelo_hip.h "Submap merging"; tests/test_surf_merge_abi.py)
+SURF_MERGE_ARGTYPES = {
+    "lv_surf_merge": [C.c_void_p, C.POINTER(SurfSubmap), C.POINTER(GraphPose), C.POINTER(SurfMergeParams), C.POINTER(C.c_uint64)],
 }
 
 
@@ -1055,6 +1074,8 @@ def load_library() -> C.CDLL:
         lib.lv_default_ndt_align_params.argtypes = [C.POINTER(NdtAlignParams)]
         lib.lv_default_surf_align_params.restype = None
         lib.lv_default_surf_align_params.argtypes = [C.POINTER(SurfAlignParams)]
+        lib.lv_default_surf_merge_params.restype = None
+        lib.lv_default_surf_merge_params.argtypes = [C.POINTER(SurfMergeParams)]
         lib.lv_default_occ_surface_params.restype = None
         lib.lv_default_occ_surface_params.argtypes = [C.POINTER(OccSurfaceParams)]
         for name, argtypes in {**QUERY_ARGTYPES, **BATCH_ARGTYPES, **VISIBILITY_ARGTYPES, **PAINT_ARGTYPES, **PLACE_ARGTYPES, **SURFACE_ARGTYPES,
@@ -1062,7 +1083,7 @@ def load_library() -> C.CDLL:
                                **FRONTIER_ARGTYPES,
                                **RAY_ARGTYPES, **ELEVATION_ARGTYPES, **ROLLOUT_ARGTYPES, **MCL_ARGTYPES, **MCL_FILTER_ARGTYPES, **TSDF_ARGTYPES, **DEPTH_ARGTYPES, **COLOUR_ARGTYPES, **TSDF_RAY_ARGTYPES, **VOLUME_ARGTYPES,
                                **OBSERVE_ARGTYPES, **GRAPH_ARGTYPES, **TRAJ_ARGTYPES, **NDT_ARGTYPES, **SURF_ALIGN_ARGTYPES,
-                               **OCC_SURFACE_ARGTYPES}.items():
+                               **OCC_SURFACE_ARGTYPES, **SURF_MERGE_ARGTYPES}.items():
             getattr(lib, name).argtypes = argtypes
             getattr(lib, name).restype = C.c_int
         _lib = lib
@@ -1200,6 +1221,30 @@ def default_ndt_align_params(**kw) -> NdtAlignParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_surf_merge_params(**kw) -> SurfMergeParams:
+    p = SurfMergeParams()
+    load_library().lv_default_surf_merge_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def surf_submap(origin, resolution, trunc_cells, S, W):
+    """(SurfSubmap, the int32 arrays it points into) from a volume as Context.tsdf_fetch gives it: S and W [nz, ny, nx]."""
+    a = np.ascontiguousarray(S, np.int32)
+    b = np.ascontiguousarray(W, np.int32)
+    if a.ndim != 3 or a.shape != b.shape:
+        raise ValueError("surf_submap: S and W of one [nz, ny, nx] shape")
+    m = SurfSubmap()
+    m.origin[:] = [float(v) for v in origin]
+    m.resolution = float(resolution)
+    m.nz, m.ny, m.nx = (int(v) for v in a.shape)
+    m.trunc_cells = int(trunc_cells)
+    m.S = a.ctypes.data_as(C.POINTER(C.c_int32))
+    m.W = b.ctypes.data_as(C.POINTER(C.c_int32))
+    return m, (a, b)
 
 
 def default_surf_align_params(**kw) -> SurfAlignParams:
@@ -2621,6 +2666,16 @@ class Context:
                                            res.ctypes.data_as(C.POINTER(SurfAlignResult)) if len(g) else None,
                                            best.ctypes.data_as(C.POINTER(C.c_int32))))
         return res, (int(best[0]), int(best[1]))
+
+    # --- Submap merging (include/limovelo_hip.h "Submap merging"; limo_velo_amd.mesh has the helpers)
+    def surf_merge(self, submap: SurfSubmap, pose, params: SurfMergeParams | None = None) -> np.ndarray:
+        """lv_surf_merge of a SurfSubmap (surf_submap()) at pose [7] f64 (t, q = x y z w, submap -> world); params None: the
+        defaults.  Returns stats [4] uint64: voxels not OUTSIDE, voxels that contribute, the sum of dW, voxels DROPPED."""
+        g = np.ascontiguousarray(np.asarray(pose, np.float64).reshape(7))
+        stats = np.zeros(4, np.uint64)
+        self._check(self.lib.lv_surf_merge(self.h, C.byref(submap), g.ctypes.data_as(C.POINTER(GraphPose)),
+                                           C.byref(params) if params is not None else None, stats.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return stats
 
     def scan_set(self, pts):
         a, stride, n = _points(pts)

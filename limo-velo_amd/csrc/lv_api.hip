@@ -21,6 +21,7 @@
 #include "lv_surf_align.hpp"
 #include "lv_depth.hpp"
 #include "lv_surf_occ.hpp"
+#include "lv_surf_merge.hpp"
 
 #include <chrono>
 
@@ -1872,6 +1873,16 @@ int lv_surf_align(lv_ctx* c, const lv_surf_align_params* params, const void* src
     if (int rc = surf_check_align_args(src, stride, n_src, guesses, K, results, best)) return rc;
     LV_CHECK_CTX(c);
     return c->vol.surf_align(c->stream, prm, src, stride, n_src, guesses, K, results, best);
+}
+
+// ---- Submap merging (lv_surf_merge.hip)
+void lv_default_surf_merge_params(lv_surf_merge_params* p) { default_surf_merge_params(p); }
+
+int lv_surf_merge(lv_ctx* c, const lv_surf_submap* sub, const lv_graph_pose* pose, const lv_surf_merge_params* p, uint64_t stats[4]) {
+    SurfMergeRule q;
+    if (int rc = surf_merge_rule(sub, pose, p, &q)) return rc;
+    LV_CHECK_CTX(c);
+    return c->vol.surf_merge(c->stream, *sub, q, stats);
 }
 
 // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip)

@@ -276,6 +276,7 @@ void TsdfStore::release() {
     rays.release();
     depth.release();
     align.release();
+    merged.release();
     *this = TsdfStore();
 }
 

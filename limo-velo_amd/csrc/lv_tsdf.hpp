@@ -326,6 +326,15 @@ struct SurfAlignStage {
     void release() { release_all(pts, d_out, d_status, d_res, h_res, d_hyp, h_hyp, d_part, d_running, h_running); }
 };
 
+// The staging of lv_surf_merge ("Submap merging"; rule in lv_surf_merge.hpp, kernel in lv_surf_merge.hip): the submap as
+// interleaved (S, W) pairs, pinned and on the device, grown on demand.  Nothing is allocated before the first call that launches.
+struct SurfMergeRule;   // lv_surf_merge.hpp: one call as the kernel takes it
+struct MergeStage {
+    PinBuf<int32_t> h_sw;                // 2 per source voxel
+    DevBuf<int32_t> d_sw;
+    void release() { release_all(h_sw, d_sw); }
+};
+
 // The volume of a context and the buffers of its calls.  Nothing is allocated before configure().
 struct TsdfStore {
     bool configured = false;
@@ -344,9 +353,10 @@ struct TsdfStore {
     DevBuf<uint32_t> d_flag, d_vid, d_fcnt, d_foff;   // the build's per-voxel arrays (n_vox + 1 each), freed when it ends
     DevBuf<void> d_tmp;                       // hipcub scratch
     ColourLayer colour;                       // the colour layer: zeroed by clear() and load(), moved by recentre(), read by mesh_build(), freed by release()
-    TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), integrate_depth(), load(), clear() and recentre(), freed by release()
+    TsdfRays rays;                            // the rays' packed states: invalidated by integrate(), integrate_depth(), load(), clear() and recentre() (and for merge() by VolumeTools::surf_merge), freed by release()
     DepthStage depth;                         // integrate_depth()'s staging, freed by release()
     SurfAlignStage align;                     // surf_sample()'s and surf_align()'s scratch, freed by release()
+    MergeStage merged;                        // merge()'s staging, freed by release()
 
     int configure(hipStream_t stream, const lv_tsdf_params& p);
     int clear(hipStream_t stream);
@@ -376,6 +386,10 @@ struct TsdfStore {
     int surf_sample(hipStream_t stream, int min_weight, const void* pts, size_t stride, size_t n, double* out, uint8_t* status);
     int surf_align(hipStream_t stream, const lv_surf_align_params& prm, const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses,
                    size_t K, lv_surf_align_result* results, int32_t best[2]);
+
+    // ---- submap merging (lv_surf_merge.hip).  q: surf_merge_rule's with kq filled; lo..hi: surf_merge_box's voxels [lo, hi), not
+    // empty.  Writes S and W only, waits for the stream.
+    int merge(hipStream_t stream, const lv_surf_submap& sub, const SurfMergeRule& q, const int lo[3], const int hi[3], uint64_t out[4]);
 
     // ---- the colour layer (lv_colour.hip).  cams, q: paint_rule's.  All of them wait for the stream.
     int colour_ensure(hipStream_t stream);   // allocates the layer, all zero, where it is not present

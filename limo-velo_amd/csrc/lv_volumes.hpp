@@ -44,6 +44,9 @@
 //   lv_volume_recentre (SURFACE)              | after success, non-zero shift               |
 //   lv_depth_integrate (after its argument    | before the store call, whatever it returns  |
 //     checks)                                 |                                             |
+//   lv_surf_merge (after its argument checks, | before the box is looked at and before the  |   and, for lv_surf_merge, which
+//     the volume and the resolution ratio)    |   store call, whatever it returns           |   TsdfStore::merge leaves to this
+//                                             |                                             |   file: tsdf.rays.packed = false
 //   ------------------------------------------+---------------------------------------------+---------------------------------
 //   lv_colour_integrate (after its argument   | before the store call, whatever it returns  | COLOUR EDIT: mesh.stale = 1
 //     checks), lv_colour_load (after its      |                                             |   where built
@@ -86,6 +89,9 @@
 //   mark      GRID, then the box clipped to the grid (an empty one: LV_OK, zero stats, before the point map is looked at).
 //   from surface  lv_occ_from_surface: GRID, SURFACE, then the box clipped to the grid (an empty one: LV_OK, zero stats, no store
 //             call); the parameters were judged before the context.  It reads the live volume and writes nothing of it.
+//   merge     lv_surf_merge: SURFACE, then the resolution ratio against the volume (surf_merge_scale, LV_EINVAL), then the marks of
+//             the table, then the voxels the submap's box can reach (none: LV_OK, zero stats, no store call); everything else was
+//             judged before the context.  It leaves the colour layer alone and touches nothing of the occupancy side.
 #pragma once
 #include <cstring>
 
@@ -99,6 +105,7 @@
 #include "lv_ray.hpp"
 #include "lv_rollout.hpp"
 #include "lv_rules.hpp"
+#include "lv_surf_merge.hpp"
 #include "lv_tsdf.hpp"
 
 namespace lv {
@@ -697,6 +704,22 @@ struct VolumeTools {
                    size_t K, lv_surf_align_result* results, int32_t best[2]) {
         LV_SURFACE_CONFIGURED;
         return tsdf.surf_align(stream, p, src, stride, n_src, guesses, K, results, best);
+    }
+
+    // ---- Submap merging (lv_surf_merge.hip).  Only this method reaches the store's merge.  Its entry point has judged what needs
+    // no context (surf_merge_rule): q is that rule, kq still open.
+    int surf_merge(hipStream_t stream, const lv_surf_submap& sub, const SurfMergeRule& q, uint64_t stats[4]) {
+        LV_SURFACE_CONFIGURED;
+        SurfMergeRule r = q;
+        if (int rc = surf_merge_scale(sub.resolution, tsdf.grid.occ.resolution, &r.kq)) return rc;
+        surface_edited();
+        tsdf.rays.packed = false;
+        int lo[3], hi[3];
+        if (!surf_merge_box(tsdf.grid, r, lo, hi)) {   // the submap cannot meet the volume: nothing is staged, nothing runs
+            if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+            return LV_OK;
+        }
+        return tsdf.merge(stream, sub, r, lo, hi, stats);
     }
 
     // ---- Rolling volumes (lv_grid.hpp's rule; lv_occupancy.hip, lv_tsdf.hip).  volume: LV_VOLUME_OCC or LV_VOLUME_SURFACE

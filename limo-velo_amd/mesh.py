@@ -10,7 +10,9 @@ makes one, render_frame() renders one from the surface.  sample() reads the inte
 registration"), align() registers a cloud against the surface from any number of guesses, align_params_for() picks the gate and
 the Huber width from the volume, frame_points() back-projects a depth frame, track_depth() refines a camera pose against the
 volume, loop_measurement() turns a result into a pose-graph edge.  to_occupancy() fills the occupancy grid from the volume
-("Occupancy from the surface"), configuring one like the volume where there is none."""
+("Occupancy from the surface"), configuring one like the volume where there is none.  submap() takes the live volume as a submap,
+merge() resamples a submap into the volume under a rigid pose ("Submap merging"), and Submaps keeps a run's submaps with their
+poses, saves and loads them, and rebuilds the volume from them at the poses a pose graph has optimised."""
 from __future__ import annotations
 
 import numpy as np
@@ -357,3 +359,80 @@ def to_occupancy(ctx, **kw) -> np.ndarray:
                 setattr(p, f, getattr(t, f))
         ctx.occ_configure(p)
     return occupancy.from_surface(ctx, **kw)
+
+
+def submap(ctx) -> dict:
+    """The live volume as a submap: dict(origin [3], resolution, trunc_cells, S, W [nz, ny, nx] int32), what merge() takes."""
+    p = ctx.tsdf_params()
+    vol = ctx.tsdf_fetch(S=True, W=True)
+    return dict(origin=np.array([float(v) for v in p.origin], np.float32), resolution=np.float32(p.resolution), trunc_cells=int(p.trunc_cells),
+                S=vol["S"], W=vol["W"])
+
+
+def pose7(pose) -> np.ndarray:
+    """[7] f64 (t, q = x y z w) of a pose given as that, as (t [3], q [4]) or as a 4 x 4 matrix."""
+    a = pose if isinstance(pose, np.ndarray) else None
+    if a is None and len(pose) == 2:
+        return np.concatenate([np.asarray(pose[0], np.float64).reshape(3), np.asarray(pose[1], np.float64).reshape(4)])
+    a = np.asarray(pose, np.float64)
+    if a.shape == (4, 4):
+        return np.concatenate([a[:3, 3], _quat_of(a[:3, :3])])
+    return a.reshape(7).copy()
+
+
+def merge(ctx, submap, pose, min_weight: int = 1, nearest: bool = False) -> np.ndarray:
+    """lv_surf_merge: the submap (submap()'s dict) resampled into ctx's volume at pose (submap -> world: (t, q), [7] or 4 x 4) and
+    folded in as evidence; a built mesh goes stale.  Returns stats [4] uint64: destination voxels not OUTSIDE the submap, voxels
+    that took evidence, the sum of their dW, voxels DROPPED behind the volume's band."""
+    m, keep = capi.surf_submap(submap["origin"], submap["resolution"], submap["trunc_cells"], submap["S"], submap["W"])
+    prm = capi.default_surf_merge_params(min_weight=int(min_weight), interp=capi.LV_MERGE_NEAREST if nearest else capi.LV_MERGE_TRILINEAR)
+    stats = ctx.surf_merge(m, pose7(pose), prm)
+    del keep
+    return stats
+
+
+class Submaps:
+    """A run kept as submaps: volumes as submap() gives them, each with the pose (submap -> world) of its pose-graph node.  fuse()
+    rebuilds ctx's volume from all of them, e.g. at the poses graph.PoseGraph has optimised."""
+
+    def __init__(self):
+        self.submaps = []
+        self.poses = []
+
+    def __len__(self):
+        return len(self.submaps)
+
+    def add(self, submap, pose) -> int:
+        """Keeps a submap with its pose; returns its index."""
+        self.submaps.append(dict(submap))
+        self.poses.append(pose7(pose))
+        return len(self.submaps) - 1
+
+    def save(self, path: str):
+        """All submaps and poses as one .npz (the extension is added to a path without it)."""
+        z = {"n": np.asarray(len(self)), "poses": np.asarray(self.poses, np.float64).reshape(-1, 7)}
+        for k, m in enumerate(self.submaps):
+            z[f"S{k}"], z[f"W{k}"] = np.asarray(m["S"], np.int32), np.asarray(m["W"], np.int32)
+            z[f"g{k}"] = np.array([*(float(v) for v in m["origin"]), float(m["resolution"]), float(m["trunc_cells"])], np.float32)
+        np.savez_compressed(_npz(path), **z)
+
+    @classmethod
+    def load(cls, path: str):
+        out = cls()
+        with np.load(_npz(path)) as z:
+            for k in range(int(z["n"])):
+                g = z[f"g{k}"]
+                out.add(dict(origin=g[:3].copy(), resolution=np.float32(g[3]), trunc_cells=int(g[4]), S=z[f"S{k}"], W=z[f"W{k}"]), z["poses"][k])
+        return out
+
+    def fuse(self, ctx, poses=None, min_weight: int = 1, nearest: bool = False) -> np.ndarray:
+        """lv_tsdf_clear, then one merge per submap in order, at `poses` (one per submap; default: the poses kept).  Returns the summed
+        stats."""
+        use = self.poses if poses is None else [pose7(p) for p in poses]
+        if len(use) != len(self.submaps):
+            raise ValueError("Submaps.fuse: one pose per submap")
+        ctx.tsdf_clear()
+        stats = np.zeros(4, np.uint64)
+        for m, p in zip(self.submaps, use):
+            stats += merge(ctx, m, p, min_weight=min_weight, nearest=nearest)
+        return stats
