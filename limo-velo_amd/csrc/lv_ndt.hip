@@ -5,30 +5,15 @@
 //                        point): ndt_point, then integer atomics into n, S1 and S2 of its voxel.  Integer sums commute: the
 //                        moments do not depend on the order of the points or of the lanes.
 //   ndt_gauss_kernel     one lane per voxel: ndt_gaussian into MEAN, COV and ICOV; the voxel counts are folded per wavefront.
-//   ndt_eval_kernel      one workgroup of 256 lanes per (chunk of NDT_CHUNK source points, hypothesis): lane l takes the points
-//                        l, l + 256, ... of the chunk in ascending order into 28 f64 accumulators and a count; the wavefronts fold
-//                        by an xor-butterfly (a + b == b + a: every lane holds the same bits), the four of them add in order, and
-//                        the workgroup writes one partial of NDT_PART doubles.  The chunk is a constant of the header: the sums
-//                        do not depend on the chip.
-//   ndt_turn_kernel      one workgroup per hypothesis: its four wavefronts stage the partials in LDS, 64 chunks at a time; the first
-//                        wavefront adds them, lane a < 29 its entry in chunk order, then lane 0 runs ndt_turn (acceptance,
-//                        lambda, the damped 6 x 6 solve, the trial pose).  A hypothesis that finishes
-//                        lowers the count of running ones (an integer atomic); the host enqueues NDT_ITER_CHUNK iterations
-//                        between two looks at that count, and the workgroups of a finished hypothesis return at once.
+//   ndt_eval_kernel, ndt_turn_kernel   the evaluation and the turn of lv_ndt_align: the bodies are lv_align.hpp's (align_eval,
+//                        align_turn_body) over NdtRule, the host driver is its align_run.
 #include "lv_ndt.hpp"
-
-#include <algorithm>
-#include <cstring>
 
 #include "lv_host.hpp"
 
 namespace lv {
 
 namespace {
-
-constexpr int NB = 256;   // lanes per workgroup of the evaluation
-constexpr int NT = 256;   // lanes per workgroup of the turn
-constexpr int NT_TILE = 64;   // partials staged in LDS at a time
 
 template <bool MAP>
 __device__ __forceinline__ bool ndt_source(const void* __restrict__ src, uint32_t i, float p[3]) {
@@ -107,78 +92,23 @@ __global__ __launch_bounds__(256) void ndt_gauss_kernel(NdtGrid g, uint32_t n_ce
     wave_add_to(stats + 3, sparse);
 }
 
-// grid (chunks, K).  part: NDT_PART doubles per (hypothesis, chunk)
-__global__ __launch_bounds__(NB) void ndt_eval_kernel(NdtView v, const float* __restrict__ src, uint32_t n_src, uint32_t n_chunks,
-                                                      const lv_ndt_result* __restrict__ res, const NdtHyp* __restrict__ hyp, int search, double hd,
-                                                      double* __restrict__ part) {
-    __shared__ double sh[NB / 64][NDT_ACC + 1];
-    const uint32_t h = blockIdx.y, chunk = blockIdx.x;
-    if (res[h].status != NDT_RUNNING) return;   // (uniform over the workgroup)
-    const lv_graph_pose x = hyp[h].trial;
-    double R[9];
-    gr_rot(x.q, R);
-    double acc[NDT_ACC];
-#pragma unroll
-    for (int a = 0; a < NDT_ACC; ++a) acc[a] = 0.0;
-    uint32_t cnt = 0;
-    const uint32_t end = min(n_src, (chunk + 1) * NDT_CHUNK);
-    for (uint32_t i = chunk * NDT_CHUNK + threadIdx.x; i < end; i += NB) {
-        const float p[3] = {src[3 * (size_t)i], src[3 * (size_t)i + 1], src[3 * (size_t)i + 2]};
-        cnt += ndt_point_terms(v, R, x.t, p, search, hd, acc) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int a = 0; a < NDT_ACC; ++a) acc[a] = wave_sum(acc[a]);
-    cnt = wave_sum(cnt);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < NDT_ACC; ++a) sh[threadIdx.x >> 6][a] = acc[a];
-        sh[threadIdx.x >> 6][NDT_ACC] = (double)cnt;   // (at most NDT_CHUNK: exact)
-    }
-    __syncthreads();
-    if (threadIdx.x <= NDT_ACC) {
-        double t = sh[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < NB / 64; ++w) t = t + sh[w][threadIdx.x];
-        part[((size_t)h * n_chunks + chunk) * NDT_PART + threadIdx.x] = t;
-    }
+// grid (chunks, K).  part: ALIGN_PART doubles per (hypothesis, chunk)
+__global__ __launch_bounds__(ALIGN_NB) void ndt_eval_kernel(NdtRule q, const float* __restrict__ src, uint32_t n_src, uint32_t n_chunks,
+                                                            const lv_ndt_result* __restrict__ res, const AlignHyp* __restrict__ hyp,
+                                                            double* __restrict__ part) {
+    align_eval(q, src, n_src, n_chunks, res, hyp, part);
 }
 
-// One workgroup per hypothesis.  All four wavefronts stage the partials in LDS, NT_TILE chunks at a time (coalesced, the loads of a
-// tile in flight together: one lane adding straight from global memory waits for every load in turn); the first wavefront then
-// adds each entry in chunk order and its lane 0 runs the turn.
-__global__ __launch_bounds__(NT) void ndt_turn_kernel(lv_ndt_align_params prm, int first, const double* __restrict__ part, uint32_t n_chunks,
-                                                      lv_ndt_result* __restrict__ res, NdtHyp* __restrict__ hyp, uint32_t* running) {
-    __shared__ double tile[NT_TILE][NDT_PART];
-    __shared__ double tot[NDT_PART];
-    const uint32_t h = blockIdx.x;
-    if (res[h].status != NDT_RUNNING) return;   // (uniform over the workgroup)
-    const double* p = part + (size_t)h * n_chunks * NDT_PART;
-    const uint32_t a = threadIdx.x % NDT_PART, row = threadIdx.x / NDT_PART;
-    double t = 0.0;
-    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NT_TILE) {
-        const uint32_t m = min((uint32_t)NT_TILE, n_chunks - c0);
-        for (uint32_t c = row; c < m; c += NT / NDT_PART) tile[c][a] = p[(size_t)(c0 + c) * NDT_PART + a];
-        __syncthreads();
-        if (threadIdx.x <= NDT_ACC)
-            for (uint32_t c = 0; c < m; ++c) t = t + tile[c][threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x <= NDT_ACC) tot[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lv_ndt_result r = res[h];
-        NdtHyp y = hyp[h];
-        const bool done = ndt_turn(prm, first != 0, tot, (uint32_t)tot[NDT_ACC], r, y);
-        res[h] = r;
-        hyp[h] = y;
-        if (done) atomicSub(running, 1u);
-    }
+// one workgroup per hypothesis
+__global__ __launch_bounds__(ALIGN_NT) void ndt_turn_kernel(NdtRule q, int first, const double* __restrict__ part, uint32_t n_chunks,
+                                                            lv_ndt_result* __restrict__ res, AlignHyp* __restrict__ hyp, uint32_t* running) {
+    align_turn_body(q, first, part, n_chunks, res, hyp, running);
 }
 
 }  // namespace
 
 void NdtStore::release() {
-    release_all(d_n, d_S1, d_S2, d_mean, d_cov, d_icov, stats, pts, src, d_res, h_res, d_hyp, h_hyp, d_part, d_running, h_running);
+    release_all(d_n, d_S1, d_S2, d_mean, d_cov, d_icov, stats, pts, loop);
     *this = NdtStore();
 }
 
@@ -259,66 +189,8 @@ int NdtStore::fetch(hipStream_t stream, int layer, void* out) {
 
 int NdtStore::align(hipStream_t stream, const lv_ndt_align_params& prm, const void* points, size_t stride, size_t n_src, const lv_graph_pose* guesses,
                     size_t K, lv_ndt_result* results, int32_t best[2]) {
-    if (K == 0) {
-        best[0] = best[1] = -1;
-        return LV_OK;
-    }
-    const uint32_t n_chunks = blocks_of(n_src, NDT_CHUNK);
-    int rc = src.reserve(stream, n_src, 3 * 4096);   // (synchronises the stream: the pinned records below are free)
-    if (!rc) rc = d_res.need_pow2(K, 64);
-    if (!rc) rc = h_res.need_pow2(K, 64);
-    if (!rc) rc = d_hyp.need_pow2(K, 64);
-    if (!rc) rc = h_hyp.need_pow2(K, 64);
-    if (!rc) rc = d_part.need_pow2(std::max<size_t>((size_t)K * n_chunks * NDT_PART, 1), 64 * NDT_PART);
-    if (!rc) rc = d_running.need(1);
-    if (!rc) rc = h_running.need(2);
-    if (rc) return rc;
-    // the records as the loop starts them
-    for (size_t k = 0; k < K; ++k) {
-        lv_ndt_result r{};
-        r.pose = guesses[k];
-        r.lambda = prm.lambda_init;
-        r.status = n_src ? NDT_RUNNING : LV_NDT_NO_OVERLAP;
-        h_res.p[k] = r;
-        NdtHyp y{};
-        y.trial = guesses[k];   // the first evaluation stands at the guess
-        h_hyp.p[k] = y;
-    }
-    if (n_src == 0) {   // nothing to evaluate: every guess comes back as it is
-        std::memcpy(results, h_res.p, K * sizeof(lv_ndt_result));
-        ndt_best(results, K, best);
-        return LV_OK;
-    }
-    src.append(points, stride, n_src);
-    rc = src.upload(stream);
-    if (rc) return rc;
-    h_running.p[1] = (uint32_t)K;
-    LV_HIP(hipMemcpyAsync(d_res.p, h_res.p, K * sizeof(lv_ndt_result), hipMemcpyHostToDevice, stream));
-    LV_HIP(hipMemcpyAsync(d_running.p, h_running.p + 1, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    LV_HIP(hipMemcpyAsync(d_hyp.p, h_hyp.p, K * sizeof(NdtHyp), hipMemcpyHostToDevice, stream));
-    const NdtView view{grid, d_mean.p, d_icov.p};
-    const double hd = -0.5 * prm.d2;
-    const dim3 eg(n_chunks, (uint32_t)K);
-    for (int it = 0; it <= prm.max_iterations;) {
-        const int end = std::min(prm.max_iterations + 1, it + NDT_ITER_CHUNK);
-        for (; it < end; ++it) {
-            hipLaunchKernelGGL(ndt_eval_kernel, eg, dim3(NB), 0, stream, view, src.d.p, (uint32_t)n_src, n_chunks, d_res.p, d_hyp.p, prm.search, hd,
-                               d_part.p);
-            LV_HIP(hipGetLastError());
-            hipLaunchKernelGGL(ndt_turn_kernel, dim3((uint32_t)K), dim3(NT), 0, stream, prm, it == 0 ? 1 : 0, d_part.p, n_chunks, d_res.p, d_hyp.p,
-                               d_running.p);
-            LV_HIP(hipGetLastError());
-        }
-        LV_HIP(hipMemcpyAsync(h_running.p, d_running.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        LV_HIP(hipStreamSynchronize(stream));
-        if (h_running.p[0] == 0) break;
-    }
-    LV_HIP(hipMemcpyAsync(h_res.p, d_res.p, K * sizeof(lv_ndt_result), hipMemcpyDeviceToHost, stream));
-    LV_HIP(hipStreamSynchronize(stream));
-    if (h_running.p[0] != 0) { set_error("lv_ndt_align: %u hypotheses did not finish", h_running.p[0]); return LV_EHIP; }
-    std::memcpy(results, h_res.p, K * sizeof(lv_ndt_result));
-    ndt_best(results, K, best);
-    return LV_OK;
+    const NdtRule q = ndt_rule_of(prm, NdtView{grid, d_mean.p, d_icov.p});
+    return align_run(stream, loop, q, ndt_eval_kernel, ndt_turn_kernel, points, stride, n_src, guesses, K, results, best, "lv_ndt_align");
 }
 
 }  // namespace lv

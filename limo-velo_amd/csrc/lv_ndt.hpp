@@ -2,18 +2,16 @@
 //
 // The first part is the rule as plain __host__ __device__ code in f64: the voxel and local coordinate of a point (lv_grid.hpp's
 // occ_quant, as it is), the Gaussian of a voxel from its integer moments, what one source point adds to S, g and H at a pose, the
-// damped solve and the Levenberg-Marquardt bookkeeping of one hypothesis, and the argument rules.  The kernels of lv_ndt.hip run
+// method's rule for the Levenberg-Marquardt loop of lv_align.hpp (NdtRule), and the argument rules.  The kernels of lv_ndt.hip run
 // exactly these functions; tests/emu/ndt_emu.cpp compiles them with g++ through tests/emu/hip/hip_runtime.h and
 // tests/test_ndt_host.py holds them to tests/ndt_ref.py (moments by equality, f64 algebra at 1e-12: libm differs between host and
 // device).  Every sum is written out in one order and the library is built with -ffp-contract=off.
 //
-// The quaternion algebra, the retraction and the 6 x 6 Cholesky are lv_graph.hpp's.
+// The order of the 21 entries, the damped solve, the turn of one hypothesis, `best`, the shared argument rules, the kernel bodies
+// and the host driver of lv_ndt_align are lv_align.hpp's; the quaternion algebra is lv_graph.hpp's.
 #pragma once
 
-#include "../../include/limovelo_hip.h"
-#include "lv_buffers.hpp"
-#include "lv_graph.hpp"
-#include "lv_grid.hpp"
+#include "lv_align.hpp"
 
 namespace lv {
 
@@ -22,13 +20,8 @@ static_assert(sizeof(lv_ndt_align_params) == 48, "lv_ndt_align_params is 48 byte
 static_assert(sizeof(lv_ndt_result) == 264, "lv_ndt_result is 264 bytes");
 static_assert(sizeof(lv_ndt_target_info) == 80, "lv_ndt_target_info is 80 bytes");
 
-constexpr uint32_t NDT_CHUNK = LV_NDT_CHUNK;       // source points per workgroup of the evaluation
-constexpr int NDT_ACC = 28;                        // 21 of H, 6 of g, S
-constexpr int NDT_PART = 32;                       // doubles per workgroup partial: NDT_ACC, n_in, padding
-constexpr int NDT_ITER_CHUNK = 8;                  // iterations enqueued between two looks at the count of running hypotheses
 constexpr uint64_t NDT_MAX_POINTS = 0x7FFFFFFFull; // the points of a target: build plus adds
 constexpr double NDT_D2_DEFAULT = 0.43312300470355464;
-constexpr int32_t NDT_RUNNING = -1;                // a status of the loop, never returned
 
 // The grid as the kernels take it
 struct NdtGrid {
@@ -103,9 +96,6 @@ LV_OCC_HD bool ndt_gaussian(const NdtGrid& g, const int32_t c[3], uint32_t n, co
 }
 
 // ---- the evaluation
-// the index of (a, b), a <= b, in the 21 entries of a 6 x 6 upper triangle
-LV_OCC_HD constexpr int ndt_tri(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }
-
 // What source point p adds to acc (21 of H, 6 of g, S) at the pose (R, t); hd = -0.5 d2.  true: the point counts in n_in.
 LV_OCC_HD bool ndt_point_terms(const NdtView& v, const double* R, const double* t, const float* p, int search, double hd, double* acc) {
     const double pd[3] = {(double)p[0], (double)p[1], (double)p[2]};
@@ -152,13 +142,13 @@ LV_OCC_HD bool ndt_point_terms(const NdtView& v, const double* R, const double* 
     Mf[6] = M[2]; Mf[7] = M[4]; Mf[8] = M[5];
     gr_mm(Mf, A, MA);
     for (int a = 0; a < 3; ++a)
-        for (int c = a; c < 3; ++c) acc[ndt_tri(a, c)] = acc[ndt_tri(a, c)] + Mf[a * 3 + c];
+        for (int c = a; c < 3; ++c) acc[align_tri(a, c)] = acc[align_tri(a, c)] + Mf[a * 3 + c];
     for (int a = 0; a < 3; ++a)
-        for (int c = 0; c < 3; ++c) acc[ndt_tri(a, 3 + c)] = acc[ndt_tri(a, 3 + c)] + MA[a * 3 + c];
+        for (int c = 0; c < 3; ++c) acc[align_tri(a, 3 + c)] = acc[align_tri(a, 3 + c)] + MA[a * 3 + c];
     for (int a = 0; a < 3; ++a)
         for (int c = a; c < 3; ++c) {
             const double h = (A[a] * MA[c] + A[3 + a] * MA[3 + c]) + A[6 + a] * MA[6 + c];
-            acc[ndt_tri(3 + a, 3 + c)] = acc[ndt_tri(3 + a, 3 + c)] + h;
+            acc[align_tri(3 + a, 3 + c)] = acc[align_tri(3 + a, 3 + c)] + h;
         }
     for (int a = 0; a < 3; ++a) {
         acc[21 + a] = acc[21 + a] + b[a];
@@ -169,77 +159,37 @@ LV_OCC_HD bool ndt_point_terms(const NdtView& v, const double* R, const double* 
     return true;
 }
 
-// d of (H + lambda diag H) d = -g (H: 21 entries, g: 6); returns the max-norm of d
-LV_OCC_HD double ndt_solve(const double* H21, const double* g, double lambda, double* d) {
-    double M[36], Mi[36];
-    gr_info(H21, M);
-    for (int a = 0; a < 6; ++a) M[a * 7] = M[a * 7] + lambda * M[a * 7];
-    graph_block_inverse(M, Mi);
-    double m = 0.0;
-    for (int a = 0; a < 6; ++a) {
-        double s = 0.0;
-        for (int k = 0; k < 6; ++k) s = s + Mi[a * 6 + k] * g[k];
-        d[a] = -s;
-        const double v = fabs(d[a]);
-        m = v > m ? v : m;                       // (a NaN is caught by the finiteness test of the step, below)
-        if (!(v - v == 0.0)) m = INFINITY;
-    }
-    return m;
-}
-
 LV_OCC_HD bool ndt_accept(double s_new, double s_old) { return s_new >= s_old - 64.0 * 2.220446049250313e-16 * fabs(s_old); }
 
-// What the loop keeps per hypothesis beside its lv_ndt_result (whose pose, score, info and n_in are the CURRENT ones)
-struct NdtHyp {
-    lv_graph_pose trial;   // where the next evaluation stands
-    double g[6];           // the gradient at the current pose
-    double step;           // max-norm of the increment that gave `trial`
-    uint32_t iterations;   // accepted + rejected
-    uint32_t pad;
+// The method as the loop of lv_align.hpp takes it: S is maximised, a guess needs one point, a trial none
+struct NdtRule {
+    using Result = lv_ndt_result;
+    AlignLoop loop;
+    NdtView v;
+    int search;
+    double hd;   // -0.5 d2
+    LV_OCC_HD bool point_terms(const double* R, const double* t, const float* p, double* acc) const { return ndt_point_terms(v, R, t, p, search, hd, acc); }
+    LV_OCC_HD double objective(const double* tot, uint32_t) const { return tot[27]; }
+    LV_OCC_HD static double& objective_of(Result& r) { return r.score; }
+    LV_OCC_HD static bool accept(double s_new, double s_old) { return ndt_accept(s_new, s_old); }
+    static bool better(const Result& a, const Result& b) { return a.score > b.score; }
 };
+inline NdtRule ndt_rule_of(const lv_ndt_align_params& p, const NdtView& v) {
+    return NdtRule{AlignLoop{p.max_iterations, 1, 0, 0, p.step_tol, p.lambda_init, p.lambda_min, p.lambda_max}, v, p.search, -0.5 * p.d2};
+}
 
-// One turn of the loop for one hypothesis, after an evaluation at h.trial gave tot (NDT_ACC sums) and n_in.  first: the
-// evaluation stood at the guess.  Returns true when the hypothesis has just finished (res.status left NDT_RUNNING).
-LV_OCC_HD bool ndt_turn(const lv_ndt_align_params& prm, bool first, const double* tot, uint32_t n_in, lv_ndt_result& res, NdtHyp& h) {
-    bool take = first;
-    if (first) {
-        if (n_in == 0) {
-            res.status = LV_NDT_NO_OVERLAP;
-            return true;
-        }
-    } else {
-        const double step = h.step;
-        if (step - step == 0.0 && ndt_accept(tot[27], res.score)) {
-            take = true;
-            res.accepted = res.accepted + 1;
-            res.last_step = step;
-            res.lambda = res.lambda / 3.0 > prm.lambda_min ? res.lambda / 3.0 : prm.lambda_min;
-        } else {
-            res.rejected = res.rejected + 1;
-            res.lambda = 4.0 * res.lambda < prm.lambda_max ? 4.0 * res.lambda : prm.lambda_max;
-        }
-        h.iterations = h.iterations + 1;
-    }
-    if (take) {
-        if (!first) res.pose = h.trial;
-        for (int k = 0; k < 21; ++k) res.info[k] = tot[k];
-        for (int k = 0; k < 6; ++k) h.g[k] = tot[21 + k];
-        res.score = tot[27];
-        res.n_in = n_in;
-        if (!first && h.step <= prm.step_tol) {
-            res.status = LV_NDT_CONVERGED;
-            return true;
-        }
-    }
-    if (h.iterations >= (uint32_t)prm.max_iterations) {
-        res.status = LV_NDT_MAX_ITERATIONS;
-        return true;
-    }
-    double d[6];
-    h.step = ndt_solve(res.info, h.g, res.lambda, d);
-    if (h.step - h.step == 0.0) graph_retract(res.pose, d, &h.trial);
-    else h.trial = res.pose;   // (rejected at the next turn)
-    return false;
+// The shared loop under the method's own names, for a caller written against NDT registration alone (lv_api.hip's argument check;
+// a host program that steps the loop itself, as tests/emu/ndt_emu.cpp did before align_one).  Each is one line into lv_align.hpp.
+constexpr int NDT_ACC = ALIGN_ACC;
+constexpr int32_t NDT_RUNNING = ALIGN_RUNNING;
+using NdtHyp = AlignHyp;
+inline bool ndt_turn(const lv_ndt_align_params& prm, bool first, const double* tot, uint32_t n_in, lv_ndt_result& res, NdtHyp& h) {
+    return align_turn(ndt_rule_of(prm, NdtView{}), first, tot, n_in, res, h);
+}
+inline void ndt_best(const lv_ndt_result* res, size_t K, int32_t best[2]) { align_best<NdtRule>(res, K, best); }
+inline int ndt_check_align_args(const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K, const lv_ndt_result* results,
+                                const int32_t* best) {
+    return align_check_args("lv_ndt_align", src, stride, n_src, guesses, K, results, best);
 }
 
 // ---- the argument rules
@@ -287,30 +237,9 @@ inline const char* ndt_check_points(const void* pts, size_t stride, size_t n) {
 inline const char* ndt_check_align_params(const lv_ndt_align_params* p) {
     const auto fin = [](double v) { return v - v == 0.0; };
     if (p->search != 1 && p->search != 7) return "search: 1 or 7";
-    if (p->max_iterations < 0 || p->max_iterations > 1000) return "max_iterations: 0..1000";
+    if (const char* why = align_check_iterations(p->max_iterations)) return why;
     if (!(p->d2 > 0.0 && fin(p->d2))) return "d2: finite and > 0";
-    if (!(p->step_tol >= 0.0 && fin(p->step_tol))) return "step_tol: finite and >= 0";
-    if (!(p->lambda_min > 0.0 && p->lambda_min <= p->lambda_init && p->lambda_init <= p->lambda_max && fin(p->lambda_max)))
-        return "0 < lambda_min <= lambda_init <= lambda_max < inf";
-    return nullptr;
-}
-// everything of lv_ndt_align but its parameters; the message is set
-inline int ndt_check_align_args(const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K, const lv_ndt_result* results,
-                                const int32_t* best) {
-    using namespace graph_detail;
-    if (!best) { set_error("lv_ndt_align: null best"); return LV_EINVAL; }
-    if (K > LV_NDT_MAX_GUESSES) { set_error("lv_ndt_align: K = %zu above 4096", K); return LV_EINVAL; }
-    if (n_src > LV_NDT_MAX_SOURCE) { set_error("lv_ndt_align: n_src = %zu above 2^20", n_src); return LV_EINVAL; }
-    if ((uint64_t)K * (uint64_t)n_src > ((uint64_t)1 << 30)) { set_error("lv_ndt_align: K * n_src above 2^30"); return LV_EINVAL; }
-    if (n_src && (!src || stride < 12)) { set_error("lv_ndt_align: bad source array (stride %zu)", stride); return LV_EINVAL; }
-    if (K && !guesses) { set_error("lv_ndt_align: null guesses"); return LV_EINVAL; }
-    if (K && !results) { set_error("lv_ndt_align: null results"); return LV_EINVAL; }
-    for (size_t k = 0; k < K; ++k) {
-        if (!finite_all(guesses[k].t, 3)) { set_error("lv_ndt_align: guess %zu: t: a non-finite number", k); return LV_EINVAL; }
-        if (!finite_all(guesses[k].q, 4)) { set_error("lv_ndt_align: guess %zu: q: a non-finite number", k); return LV_EINVAL; }
-        if (!unit_quat(guesses[k].q)) { set_error("lv_ndt_align: guess %zu: q: norm off 1 by more than 1e-6", k); return LV_EINVAL; }
-    }
-    return LV_OK;
+    return align_check_loop(p->step_tol, p->lambda_init, p->lambda_min, p->lambda_max);
 }
 
 inline NdtGrid ndt_grid_of(const lv_ndt_params& p) {
@@ -336,18 +265,6 @@ inline size_t ndt_layer_width(int layer) {
 }
 inline size_t ndt_layer_elem(int layer) { return layer == LV_NDT_COUNT ? 4 : 8; }
 
-// best[2] of K results
-inline void ndt_best(const lv_ndt_result* res, size_t K, int32_t best[2]) {
-    best[0] = best[1] = -1;
-    for (size_t k = 0; k < K; ++k) {
-        if (res[k].status == LV_NDT_NO_OVERLAP) continue;
-        if (best[0] < 0 || res[k].score > res[best[0]].score) {
-            best[0] = (int32_t)k;
-            best[1] = (int32_t)res[k].n_in;
-        }
-    }
-}
-
 // ---- the store (host side in lv_ndt.hip).  Nothing is allocated before the first build().
 struct NdtStore {
     bool built = false;
@@ -360,15 +277,7 @@ struct NdtStore {
     DevBuf<double> d_mean, d_cov, d_icov;
     Counters4 stats;
     PointStage pts;                       // the caller's points of a build or add
-    // lv_ndt_align
-    PointStage src;
-    DevBuf<lv_ndt_result> d_res;
-    PinBuf<lv_ndt_result> h_res;
-    DevBuf<NdtHyp> d_hyp;
-    PinBuf<NdtHyp> h_hyp;
-    DevBuf<double> d_part;
-    DevBuf<uint32_t> d_running;
-    PinBuf<uint32_t> h_running;
+    AlignStage<lv_ndt_result> loop;       // lv_ndt_align's scratch
 
     int build(hipStream_t stream, const lv_ndt_params* p, const float4* map_orig, uint32_t n_ids, const void* points, size_t stride, size_t n,
               uint64_t out[4]);

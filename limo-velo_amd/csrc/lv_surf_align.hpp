@@ -2,17 +2,17 @@
 // registration"; kernels and host side in lv_surf_align.hip, the scratch a member of TsdfStore).
 //
 // The rule as plain __host__ __device__ code in f64: the trilinear sample of phi = S / W with the exact gradient of the
-// interpolant, what one source point adds to H, g and E at a pose, the cost with its gate charge, the Levenberg-Marquardt turn of
-// one hypothesis, and the argument rules.  The kernels of lv_surf_align.hip run exactly these functions;
+// interpolant, what one source point adds to H, g and E at a pose, the cost with its gate charge, the method's rule for the
+// Levenberg-Marquardt loop of lv_align.hpp (SurfAlignRule), and the argument rules.  The kernels of lv_surf_align.hip run exactly these functions;
 // tests/emu/surf_align_emu.cpp compiles them with g++ through tests/emu/hip/hip_runtime.h and tests/test_surf_align_host.py holds
 // them to tests/surf_align_ref.py (the sample by equality: only + - * / and floor occur).  Every sum is written out in one order
 // and the library is built with -ffp-contract=off.
 //
-// The quaternion algebra, the retraction and the 6 x 6 Cholesky are lv_graph.hpp's; the order of the 21 entries (ndt_tri), the
-// damped solve (ndt_solve) and the loop's record per hypothesis (NdtHyp) are lv_ndt.hpp's, used as they stand.
+// The order of the 21 entries, the damped solve, the turn of one hypothesis, `best`, the shared argument rules, the kernel bodies
+// and the host driver of lv_surf_align are lv_align.hpp's, as they are NDT registration's; the quaternion algebra is lv_graph.hpp's.
 #pragma once
 
-#include "lv_ndt.hpp"
+#include "lv_align.hpp"
 #include "lv_tsdf.hpp"
 
 namespace lv {
@@ -21,11 +21,6 @@ static_assert(sizeof(lv_surf_align_params) == 64, "lv_surf_align_params is 64 by
 static_assert(sizeof(lv_surf_align_result) == 264, "lv_surf_align_result is 264 bytes");
 static_assert(sizeof(lv_surf_align_result) == sizeof(lv_ndt_result), "laid out as lv_ndt_result");
 
-constexpr uint32_t SURF_ALIGN_CHUNK = LV_SURF_ALIGN_CHUNK;   // source points per workgroup of the evaluation
-constexpr int SURF_ACC = 28;                                 // 21 of H, 6 of g, E
-constexpr int SURF_PART = 32;                                // doubles per workgroup partial: SURF_ACC, n_in, padding
-constexpr int SURF_ITER_CHUNK = 8;                           // turns enqueued between two looks at the count of running hypotheses
-constexpr int32_t SURF_RUNNING = -1;                         // a status of the loop, never returned
 constexpr double SURF_U_LIMIT = 16777216.0;                  // 2^24: a point this many voxels from the origin is OUTSIDE
 constexpr uint64_t SURF_SAMPLE_MAX_N = 0x7FFFFFFFull;        // lv_surf_sample: n below this
 
@@ -150,7 +145,7 @@ LV_OCC_HD bool surf_point_terms(const SurfView& v, const double* R, const double
     }
     for (int a = 0; a < 6; ++a) wJ[a] = w * J[a];
     for (int a = 0; a < 6; ++a)
-        for (int b = a; b < 6; ++b) acc[ndt_tri(a, b)] = acc[ndt_tri(a, b)] + wJ[a] * J[b];
+        for (int b = a; b < 6; ++b) acc[align_tri(a, b)] = acc[align_tri(a, b)] + wJ[a] * J[b];
     const double wd = w * d;
     for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + wd * J[a];
     acc[27] = acc[27] + rho;
@@ -159,51 +154,39 @@ LV_OCC_HD bool surf_point_terms(const SurfView& v, const double* R, const double
 
 LV_OCC_HD bool surf_accept(double c_new, double c_old) { return c_new <= c_old + 64.0 * 2.220446049250313e-16 * fabs(c_old); }
 
-// One turn of the loop for one hypothesis, after an evaluation at h.trial gave tot (SURF_ACC sums) and n_in.  first: the
-// evaluation stood at the guess.  res holds the CURRENT pose, cost, info and n_in.  Returns true when the hypothesis has just
-// finished (res.status left SURF_RUNNING).
-LV_OCC_HD bool surf_turn(const lv_surf_align_params& prm, uint32_t n_src, bool first, const double* tot, uint32_t n_in, lv_surf_align_result& res,
-                         NdtHyp& h) {
-    const double cost = surf_cost(tot[27], n_src, n_in, prm.max_dist, prm.huber);
-    bool take = first;
-    if (first) {
-        if (n_in < prm.min_points) {
-            res.status = LV_SURF_ALIGN_NO_OVERLAP;
-            return true;
-        }
-    } else {
-        const double step = h.step;
-        if (step - step == 0.0 && n_in >= prm.min_points && surf_accept(cost, res.cost)) {
-            take = true;
-            res.accepted = res.accepted + 1;
-            res.last_step = step;
-            res.lambda = res.lambda / 3.0 > prm.lambda_min ? res.lambda / 3.0 : prm.lambda_min;
-        } else {
-            res.rejected = res.rejected + 1;
-            res.lambda = 4.0 * res.lambda < prm.lambda_max ? 4.0 * res.lambda : prm.lambda_max;
-        }
-        h.iterations = h.iterations + 1;
-    }
-    if (take) {
-        if (!first) res.pose = h.trial;
-        for (int k = 0; k < 21; ++k) res.info[k] = tot[k];
-        for (int k = 0; k < 6; ++k) h.g[k] = tot[21 + k];
-        res.cost = cost;
-        res.n_in = n_in;
-        if (!first && h.step <= prm.step_tol) {
-            res.status = LV_SURF_ALIGN_CONVERGED;
-            return true;
-        }
-    }
-    if (h.iterations >= (uint32_t)prm.max_iterations) {
-        res.status = LV_SURF_ALIGN_MAX_ITERATIONS;
-        return true;
-    }
-    double d[6];
-    h.step = ndt_solve(res.info, h.g, res.lambda, d);
-    if (h.step - h.step == 0.0) graph_retract(res.pose, d, &h.trial);
-    else h.trial = res.pose;   // (rejected at the next turn)
-    return false;
+// The method as the loop of lv_align.hpp takes it: the cost (E plus the gate charge of the n_src - n_in points that are not IN) is
+// minimised, a guess and a trial both need min_points
+struct SurfAlignRule {
+    using Result = lv_surf_align_result;
+    AlignLoop loop;
+    SurfView v;
+    double max_dist, huber;
+    uint32_t n_src;
+    LV_OCC_HD bool point_terms(const double* R, const double* t, const float* p, double* acc) const { return surf_point_terms(v, R, t, p, max_dist, huber, acc); }
+    LV_OCC_HD double objective(const double* tot, uint32_t n_in) const { return surf_cost(tot[27], n_src, n_in, max_dist, huber); }
+    LV_OCC_HD static double& objective_of(Result& r) { return r.cost; }
+    LV_OCC_HD static bool accept(double c_new, double c_old) { return surf_accept(c_new, c_old); }
+    static bool better(const Result& a, const Result& b) { return a.cost < b.cost; }
+};
+inline SurfAlignRule surf_align_rule_of(const lv_surf_align_params& p, const SurfView& v, uint32_t n_src) {
+    return SurfAlignRule{AlignLoop{p.max_iterations, p.min_points, p.min_points, 0, p.step_tol, p.lambda_init, p.lambda_min, p.lambda_max}, v, p.max_dist,
+                    p.huber, n_src};
+}
+
+// The shared loop under the method's own names, for a caller written against surface registration alone (lv_api.hip's argument
+// check; a host program that steps the loop itself, as tests/emu/surf_align_emu.cpp did before align_one).  One line each into
+// lv_align.hpp.
+constexpr int SURF_ACC = ALIGN_ACC;
+constexpr int32_t SURF_RUNNING = ALIGN_RUNNING;
+using NdtHyp = AlignHyp;   // (the record's first name)
+inline bool surf_turn(const lv_surf_align_params& prm, uint32_t n_src, bool first, const double* tot, uint32_t n_in, lv_surf_align_result& res,
+                      AlignHyp& h) {
+    return align_turn(surf_align_rule_of(prm, SurfView{}, n_src), first, tot, n_in, res, h);
+}
+inline void surf_align_best(const lv_surf_align_result* res, size_t K, int32_t best[2]) { align_best<SurfAlignRule>(res, K, best); }
+inline int surf_check_align_args(const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K,
+                                 const lv_surf_align_result* results, const int32_t* best) {
+    return align_check_args("lv_surf_align", src, stride, n_src, guesses, K, results, best);
 }
 
 // ---- the argument rules
@@ -224,32 +207,11 @@ inline void default_surf_align_params(lv_surf_align_params* p) {
 inline const char* surf_check_align_params(const lv_surf_align_params* p) {
     const auto fin = [](double v) { return v - v == 0.0; };
     if (p->min_weight < 1) return "min_weight: at least 1";
-    if (p->max_iterations < 0 || p->max_iterations > 1000) return "max_iterations: 0..1000";
+    if (const char* why = align_check_iterations(p->max_iterations)) return why;
     if (p->min_points < 1) return "min_points: at least 1";
     if (!(p->max_dist > 0.0 && fin(p->max_dist))) return "max_dist: finite and > 0";
     if (!(p->huber >= 0.0 && fin(p->huber))) return "huber: finite and >= 0";
-    if (!(p->step_tol >= 0.0 && fin(p->step_tol))) return "step_tol: finite and >= 0";
-    if (!(p->lambda_min > 0.0 && p->lambda_min <= p->lambda_init && p->lambda_init <= p->lambda_max && fin(p->lambda_max)))
-        return "0 < lambda_min <= lambda_init <= lambda_max < inf";
-    return nullptr;
-}
-// everything of lv_surf_align but its parameters; the message is set
-inline int surf_check_align_args(const void* src, size_t stride, size_t n_src, const lv_graph_pose* guesses, size_t K, const lv_surf_align_result* results,
-                                 const int32_t* best) {
-    using namespace graph_detail;
-    if (!best) { set_error("lv_surf_align: null best"); return LV_EINVAL; }
-    if (K > LV_NDT_MAX_GUESSES) { set_error("lv_surf_align: K = %zu above 4096", K); return LV_EINVAL; }
-    if (n_src > LV_NDT_MAX_SOURCE) { set_error("lv_surf_align: n_src = %zu above 2^20", n_src); return LV_EINVAL; }
-    if ((uint64_t)K * (uint64_t)n_src > ((uint64_t)1 << 30)) { set_error("lv_surf_align: K * n_src above 2^30"); return LV_EINVAL; }
-    if (n_src && (!src || stride < 12)) { set_error("lv_surf_align: bad source array (stride %zu)", stride); return LV_EINVAL; }
-    if (K && !guesses) { set_error("lv_surf_align: null guesses"); return LV_EINVAL; }
-    if (K && !results) { set_error("lv_surf_align: null results"); return LV_EINVAL; }
-    for (size_t k = 0; k < K; ++k) {
-        if (!finite_all(guesses[k].t, 3)) { set_error("lv_surf_align: guess %zu: t: a non-finite number", k); return LV_EINVAL; }
-        if (!finite_all(guesses[k].q, 4)) { set_error("lv_surf_align: guess %zu: q: a non-finite number", k); return LV_EINVAL; }
-        if (!unit_quat(guesses[k].q)) { set_error("lv_surf_align: guess %zu: q: norm off 1 by more than 1e-6", k); return LV_EINVAL; }
-    }
-    return LV_OK;
+    return align_check_loop(p->step_tol, p->lambda_init, p->lambda_min, p->lambda_max);
 }
 // lv_surf_sample's arguments; the message is set
 inline int surf_check_sample_args(int min_weight, const void* pts, size_t stride, size_t n, const double* out, const uint8_t* status) {
@@ -258,18 +220,6 @@ inline int surf_check_sample_args(int min_weight, const void* pts, size_t stride
     if (n >= SURF_SAMPLE_MAX_N) { set_error("lv_surf_sample: too many points"); return LV_EINVAL; }
     if (n && (!pts || stride < 12)) { set_error("lv_surf_sample: bad point array (stride %zu)", stride); return LV_EINVAL; }
     return LV_OK;
-}
-
-// best[2] of K results: the least cost among those that are not NO_OVERLAP, the smaller index winning a tie
-inline void surf_align_best(const lv_surf_align_result* res, size_t K, int32_t best[2]) {
-    best[0] = best[1] = -1;
-    for (size_t k = 0; k < K; ++k) {
-        if (res[k].status == LV_SURF_ALIGN_NO_OVERLAP) continue;
-        if (best[0] < 0 || res[k].cost < res[best[0]].cost) {
-            best[0] = (int32_t)k;
-            best[1] = (int32_t)res[k].n_in;
-        }
-    }
 }
 
 }  // namespace lv

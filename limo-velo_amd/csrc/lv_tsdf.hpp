@@ -9,6 +9,7 @@
 // occ_quant every step is integer arithmetic, so the three agree on every voxel, vertex and index.
 #pragma once
 
+#include "lv_align.hpp"   // AlignStage: the scratch of lv_surf_align
 #include "lv_occupancy.hpp"
 #include "lv_rules.hpp"   // PaintCam, PaintRule: what the colour layer's integrate takes
 
@@ -311,19 +312,11 @@ struct DepthStage {
 
 // The scratch of lv_surf_sample and lv_surf_align ("Surface registration"; rule in lv_surf_align.hpp, kernels in
 // lv_surf_align.hip).  Nothing is allocated before the first of them.
-struct NdtHyp;   // lv_ndt.hpp: what the loop keeps per hypothesis
 struct SurfAlignStage {
-    PointStage pts;                      // lv_surf_sample's points, lv_surf_align's source
+    AlignStage<lv_surf_align_result> loop;   // lv_surf_align's scratch (lv_align.hpp); loop.src holds lv_surf_sample's points too
     DevBuf<double> d_out;                // lv_surf_sample: 4 per point
     DevBuf<uint8_t> d_status;            // lv_surf_sample: one per point
-    DevBuf<lv_surf_align_result> d_res;
-    PinBuf<lv_surf_align_result> h_res;
-    DevBuf<NdtHyp> d_hyp;
-    PinBuf<NdtHyp> h_hyp;
-    DevBuf<double> d_part;               // SURF_PART per (hypothesis, chunk)
-    DevBuf<uint32_t> d_running;
-    PinBuf<uint32_t> h_running;
-    void release() { release_all(pts, d_out, d_status, d_res, h_res, d_hyp, h_hyp, d_part, d_running, h_running); }
+    void release() { release_all(loop, d_out, d_status); }
 };
 
 // The staging of lv_surf_merge ("Submap merging"; rule in lv_surf_merge.hpp, kernel in lv_surf_merge.hip): the submap as

@@ -86,32 +86,24 @@ int main(int argc, char** argv) {
     fwrite(S2.data(), 8, nc * 6, f);
     fclose(f);
 
-    const NdtView v{g, mean.data(), icov.data()};
+    const NdtRule q = ndt_rule_of(prm, NdtView{g, mean.data(), icov.data()});
     double eval_ms = 0.0;
     long evals = 0;
+    const auto evaluate = [&](const lv_graph_pose& x, double* tot) {
+        t0 = Clock::now();
+        const uint32_t n_in = align_evaluate(q, src.data(), src.size() / 3, x, tot);
+        eval_ms += ms_since(t0);
+        ++evals;
+        return n_in;
+    };
     std::vector<lv_ndt_result> res((size_t)K);
     for (int k = 0; k < K; ++k) {
-        lv_ndt_result r{};
-        NdtHyp h{};
+        lv_graph_pose x;
         for (int a = 0; a < 3; ++a)
-            if (scanf("%lf", &r.pose.t[a]) != 1) return 2;
+            if (scanf("%lf", &x.t[a]) != 1) return 2;
         for (int a = 0; a < 4; ++a)
-            if (scanf("%lf", &r.pose.q[a]) != 1) return 2;
-        r.lambda = prm.lambda_init;
-        r.status = NDT_RUNNING;
-        h.trial = r.pose;
-        for (int it = 0; r.status == NDT_RUNNING; ++it) {
-            double tot[NDT_ACC], R[9];
-            for (int a = 0; a < NDT_ACC; ++a) tot[a] = 0.0;
-            gr_rot(h.trial.q, R);
-            uint32_t n_in = 0;
-            t0 = Clock::now();
-            for (size_t i = 0; i < src.size() / 3; ++i) n_in += ndt_point_terms(v, R, h.trial.t, &src[3 * i], prm.search, -0.5 * prm.d2, tot) ? 1u : 0u;
-            eval_ms += ms_since(t0);
-            ++evals;
-            ndt_turn(prm, it == 0, tot, n_in, r, h);
-        }
-        res[(size_t)k] = r;
+            if (scanf("%lf", &x.q[a]) != 1) return 2;
+        res[(size_t)k] = align_one(q, evaluate, x);
     }
     printf("eval_ms %.4f\n", evals ? eval_ms / (double)evals : 0.0);
     for (const auto& r : res)

@@ -53,26 +53,32 @@ int main(int argc, char** argv) {
     const int min_weight = atoi(argv[5]);
     const double max_dist = atof(argv[6]), huber = atof(argv[7]);
     const int K = atoi(argv[8]);
-    const SurfView v = surf_view_of(g, min_weight, S.data(), W.data());
     const uint32_t n_src = (uint32_t)(src.size() / 3);
+    // the loop with no iteration and no least n_in: the guess is scored whatever it holds
+    lv_surf_align_params prm;
+    default_surf_align_params(&prm);
+    prm.max_iterations = 0;
+    prm.min_points = 0;
+    prm.max_dist = max_dist;
+    prm.huber = huber;
+    const SurfAlignRule q = surf_align_rule_of(prm, surf_view_of(g, min_weight, S.data(), W.data()), n_src);
     double eval_ms = 0.0;
-    std::vector<double> cost((size_t)K);
-    std::vector<uint32_t> n_in((size_t)K, 0);
+    const auto evaluate = [&](const lv_graph_pose& x, double* tot) {
+        const auto t0 = Clock::now();
+        const uint32_t n_in = align_evaluate(q, src.data(), n_src, x, tot);
+        eval_ms += std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
+        return n_in;
+    };
+    std::vector<lv_surf_align_result> res((size_t)K);
     for (int k = 0; k < K; ++k) {
         lv_graph_pose x;
         for (int a = 0; a < 3; ++a)
             if (scanf("%lf", &x.t[a]) != 1) return 2;
         for (int a = 0; a < 4; ++a)
             if (scanf("%lf", &x.q[a]) != 1) return 2;
-        double acc[SURF_ACC], R[9];
-        for (int a = 0; a < SURF_ACC; ++a) acc[a] = 0.0;
-        gr_rot(x.q, R);
-        const auto t0 = Clock::now();
-        for (uint32_t i = 0; i < n_src; ++i) n_in[(size_t)k] += surf_point_terms(v, R, x.t, &src[3 * (size_t)i], max_dist, huber, acc) ? 1u : 0u;
-        eval_ms += std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
-        cost[(size_t)k] = surf_cost(acc[27], n_src, n_in[(size_t)k], max_dist, huber);
+        res[(size_t)k] = align_one(q, evaluate, x);
     }
     printf("eval_ms %.4f\n", K ? eval_ms / (double)K : 0.0);
-    for (int k = 0; k < K; ++k) printf("%u %.17g\n", n_in[(size_t)k], cost[(size_t)k]);
+    for (const auto& r : res) printf("%u %.17g\n", r.n_in, r.cost);
     return 0;
 }

@@ -124,16 +124,6 @@ static Target build(const lv_ndt_params& p, const std::vector<float>& pts) {
     return T;
 }
 
-// one evaluation: the points in ascending order into one accumulator
-static uint32_t evaluate(const Target& T, const std::vector<float>& src, const lv_graph_pose& x, int search, double d2, double* acc) {
-    const NdtView v{T.g, T.mean.data(), T.icov.data()};
-    double R[9];
-    gr_rot(x.q, R);
-    for (int a = 0; a < NDT_ACC; ++a) acc[a] = 0.0;
-    uint32_t n_in = 0;
-    for (size_t i = 0; i < src.size() / 3; ++i) n_in += ndt_point_terms(v, R, x.t, &src[3 * i], search, -0.5 * d2, acc) ? 1u : 0u;
-    return n_in;
-}
 
 int main() {
     const int mode = (int)ri();
@@ -157,32 +147,24 @@ int main() {
         const lv_ndt_params p = read_params();
         const Target T = build(p, read_points());
         const std::vector<float> src = read_points();
+        const NdtView v{T.g, T.mean.data(), T.icov.data()};
         if (mode == 1) {
             const lv_graph_pose x = read_pose();
-            const int search = (int)ri();
-            const double d2 = rd();
-            double acc[NDT_ACC];
-            const uint32_t n_in = evaluate(T, src, x, search, d2, acc);
-            pv(acc, NDT_ACC);
+            lv_ndt_align_params a{};
+            a.search = (int32_t)ri();
+            a.d2 = rd();
+            double acc[ALIGN_ACC];
+            const uint32_t n_in = align_evaluate(ndt_rule_of(a, v), src.data(), src.size() / 3, x, acc);
+            pv(acc, ALIGN_ACC);
             printf("%u\n", n_in);
             return 0;
         }
-        const lv_ndt_align_params prm = read_align_params();
+        const NdtRule q = ndt_rule_of(read_align_params(), v);
         const size_t K = (size_t)ri();
         std::vector<lv_ndt_result> res(K);
         for (size_t k = 0; k < K; ++k) {
-            lv_ndt_result r{};
-            NdtHyp h{};
-            r.pose = read_pose();
-            r.lambda = prm.lambda_init;
-            r.status = NDT_RUNNING;
-            h.trial = r.pose;
-            for (int it = 0; r.status == NDT_RUNNING; ++it) {
-                if (it > prm.max_iterations) return 3;   // the loop must have ended by now
-                double tot[NDT_ACC];
-                const uint32_t n_in = evaluate(T, src, h.trial, prm.search, prm.d2, tot);
-                ndt_turn(prm, it == 0, tot, n_in, r, h);
-            }
+            const lv_ndt_result r = align_one(q, [&](const lv_graph_pose& x, double* tot) { return align_evaluate(q, src.data(), src.size() / 3, x, tot); }, read_pose());
+            if (r.status == ALIGN_RUNNING) return 3;   // the loop must have ended by now
             res[k] = r;
             const double head[10] = {r.pose.t[0], r.pose.t[1], r.pose.t[2], r.pose.q[0], r.pose.q[1], r.pose.q[2], r.pose.q[3], r.score, r.last_step, r.lambda};
             pv(head, 10);
@@ -190,7 +172,7 @@ int main() {
             pv(r.info, 21);
         }
         int32_t best[2];
-        ndt_best(res.data(), K, best);
+        align_best<NdtRule>(res.data(), K, best);
         printf("%d %d\n", best[0], best[1]);
     } else if (mode == 2) {
         for (long long c = ri(); c > 0; --c) {
@@ -218,8 +200,8 @@ int main() {
             std::vector<lv_ndt_result> res(1);
             float pt[3] = {0, 0, 0};
             int32_t best[2];
-            const int rc = ndt_check_align_args(has_src ? pt : nullptr, stride, n_src, has_guesses ? g.data() : nullptr, K,
-                                                has_results ? res.data() : nullptr, has_best ? best : nullptr);
+            const int rc = align_check_args("lv_ndt_align", has_src ? pt : nullptr, stride, n_src, has_guesses ? g.data() : nullptr, K,
+                                            has_results ? res.data() : nullptr, has_best ? best : nullptr);
             if (rc) printf("bad: %s\n", g_err);
             else printf("ok\n");
         }

@@ -95,15 +95,6 @@ static lv_graph_pose read_pose() {
     return x;
 }
 
-// one evaluation: the points in ascending order into one accumulator
-static uint32_t evaluate(const SurfView& v, const std::vector<float>& src, const lv_graph_pose& x, double max_dist, double huber, double* acc) {
-    double R[9];
-    gr_rot(x.q, R);
-    for (int a = 0; a < SURF_ACC; ++a) acc[a] = 0.0;
-    uint32_t n_in = 0;
-    for (size_t i = 0; i < src.size() / 3; ++i) n_in += surf_point_terms(v, R, x.t, &src[3 * i], max_dist, huber, acc) ? 1u : 0u;
-    return n_in;
-}
 
 int main() {
     const int mode = (int)ri();
@@ -123,34 +114,27 @@ int main() {
         const uint32_t n_src = (uint32_t)(src.size() / 3);
         if (mode == 1) {
             const lv_graph_pose x = read_pose();
-            const double max_dist = rd(), huber = rd();
-            double acc[SURF_ACC];
-            const uint32_t n_in = evaluate(vol.view(), src, x, max_dist, huber, acc);
-            pv(acc, SURF_ACC);
+            lv_surf_align_params a{};
+            a.max_dist = rd();
+            a.huber = rd();
+            const SurfAlignRule q = surf_align_rule_of(a, vol.view(), n_src);
+            double acc[ALIGN_ACC];
+            const uint32_t n_in = align_evaluate(q, src.data(), n_src, x, acc);
+            pv(acc, ALIGN_ACC);
             printf("%u\n", n_in);
-            const double cost = surf_cost(acc[27], n_src, n_in, max_dist, huber);
+            const double cost = q.objective(acc, n_in);
             pv(&cost, 1);
             return 0;
         }
         const lv_surf_align_params prm = read_params();
         Volume with = vol;
         with.min_weight = prm.min_weight;
-        const SurfView v = with.view();
+        const SurfAlignRule q = surf_align_rule_of(prm, with.view(), n_src);
         const size_t K = (size_t)ri();
         std::vector<lv_surf_align_result> res(K);
         for (size_t k = 0; k < K; ++k) {
-            lv_surf_align_result r{};
-            NdtHyp h{};
-            r.pose = read_pose();
-            r.lambda = prm.lambda_init;
-            r.status = SURF_RUNNING;
-            h.trial = r.pose;
-            for (int it = 0; r.status == SURF_RUNNING; ++it) {
-                if (it > prm.max_iterations) return 3;   // the loop must have ended by now
-                double tot[SURF_ACC];
-                const uint32_t n_in = evaluate(v, src, h.trial, prm.max_dist, prm.huber, tot);
-                surf_turn(prm, n_src, it == 0, tot, n_in, r, h);
-            }
+            const lv_surf_align_result r = align_one(q, [&](const lv_graph_pose& x, double* tot) { return align_evaluate(q, src.data(), n_src, x, tot); }, read_pose());
+            if (r.status == ALIGN_RUNNING) return 3;   // the loop must have ended by now
             res[k] = r;
             const double head[10] = {r.pose.t[0], r.pose.t[1], r.pose.t[2], r.pose.q[0], r.pose.q[1], r.pose.q[2], r.pose.q[3], r.cost, r.last_step, r.lambda};
             pv(head, 10);
@@ -158,7 +142,7 @@ int main() {
             pv(r.info, 21);
         }
         int32_t best[2];
-        surf_align_best(res.data(), K, best);
+        align_best<SurfAlignRule>(res.data(), K, best);
         printf("%d %d\n", best[0], best[1]);
     } else if (mode == 2) {
         for (long long c = ri(); c > 0; --c) {
@@ -180,8 +164,8 @@ int main() {
             std::vector<lv_surf_align_result> res(1);
             float pt[3] = {0, 0, 0};
             int32_t best[2];
-            const int rc = surf_check_align_args(has_src ? pt : nullptr, stride, n_src, has_guesses ? g.data() : nullptr, K,
-                                                 has_results ? res.data() : nullptr, has_best ? best : nullptr);
+            const int rc = align_check_args("lv_surf_align", has_src ? pt : nullptr, stride, n_src, has_guesses ? g.data() : nullptr, K,
+                                            has_results ? res.data() : nullptr, has_best ? best : nullptr);
             if (rc) printf("bad: %s\n", g_err);
             else printf("ok\n");
         }

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import graph_ref as gr
 import ndt_cases as cases
 import ndt_ref as nr
 
@@ -101,7 +102,7 @@ def test_no_overlap_evaluation(emu):
 
 @pytest.mark.parametrize("name", list(cases.ALIGN_CASES))
 def test_loop(emu, name):
-    """ndt_turn on the host against the reference's loop, by the bounds the device is held to"""
+    """align_turn over NdtRule on the host against the reference's loop, by the bounds the device is held to"""
     c = cases.ALIGN_CASES[name]()
     ref, best = cases.reference(name)
     g = c["guesses"]
@@ -127,6 +128,35 @@ def test_loop_edges(emu):
     assert np.array_equal(np.array(out[3].split(), float)[:7], far) and out[4] == f"0 {nr.NO_OVERLAP} 0 0" and out[-1] == f"0 {n_in}"
     out = emu(5, "\n".join([_prm(c["prm"]), _pts(c["target"]), _pts(c["source"]), _align_prm(**c["solve"]), "1", _f(far)]))
     assert out[1] == f"0 {nr.NO_OVERLAP} 0 0" and out[-1] == "-1 -1"
+
+
+def test_loop_takes_a_trial_without_overlap(emu):
+    """NDT asks one point of the guess and NOTHING of a trial: with the score underflowed to 0 a trial that lost every point is
+    taken (S = 0 >= 0).  One used voxel; one source point 2 km out on the sensor's x axis, half a metre off the voxel's mean and
+    1 mm inside its face: exp(-0.5 d2 e' Omega e) is 0 at d2 = 10, so S, g and H are 0 and the step is 0.  The guess' quaternion is a
+    quarter turn about z of norm 1 + 5e-7: R(q) stretches by |q|^2, the retraction renormalises, and the point moves 2 mm across
+    the face into an empty voxel.  (A loop that asked one point of a trial too would reject it five times: MAX_ITERATIONS,
+    accepted = 0, n_in = 1.)"""
+    prm = nr.params(origin=(0.0, 0.0, 0.0), resolution=1.0, nx=4, ny=4, nz=4)
+    target = (np.array([1.5, 1.5, 1.5]) + np.random.default_rng(3).uniform(-0.01, 0.01, (8, 3))).astype(np.float32)
+    src = np.array([[2048.0, 0.0, 0.0]], np.float32)
+    q = (1.0 + 5e-7) * np.array([0.0, 0.0, math.sqrt(0.5), math.sqrt(0.5)])
+    guess = np.concatenate([np.array([1.999, 1.5, 1.5]) - gr.rot(q) @ src[0].astype(float), q])
+    solve = dict(search=1, d2=10.0, max_iterations=5)
+    T = nr.build(prm, target)
+    acc, n_in = nr.evaluate(prm, T, src, guess, 1, 10.0)
+    assert n_in == 1 and not acc.any()
+    r = nr.align_one(prm, T, src, guess, **solve)
+    assert (r["status"], r["accepted"], r["rejected"], r["n_in"], r["score"]) == (nr.CONVERGED, 1, 0, 0, 0.0)
+    assert nr.evaluate(prm, T, src, r["pose"], 1, 10.0)[1] == 0 and not np.array_equal(r["pose"], guess)
+    out = emu(1, "\n".join([_prm(prm), _pts(target), _pts(src), _f(guess), "1 10.0"]))
+    assert not np.array(out[0].split(), float).any() and int(out[1]) == 1
+    out = emu(5, "\n".join([_prm(prm), _pts(target), _pts(src), _align_prm(**solve), "1", _f(guess)]))
+    head = np.array(out[0].split(), float)
+    assert [int(v) for v in out[1].split()] == [0, nr.CONVERGED, 1, 0]
+    assert nr.pose_distance(head[:7], r["pose"]) <= 1e-8 and not np.array_equal(head[:7], guess)
+    assert head[7] == 0.0 and head[8] == 0.0 and head[9] == pytest.approx(r["lambda"], rel=1e-12)
+    assert not np.array(out[2].split(), float).any() and out[-1] == "0 0"
 
 
 def test_params_rule(emu):

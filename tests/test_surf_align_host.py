@@ -102,7 +102,7 @@ def test_no_overlap_evaluation(emu):
 
 @pytest.mark.parametrize("name", list(cases.CASES))
 def test_loop(emu, name):
-    """surf_turn on the host against the reference's loop, by the bounds the device is held to"""
+    """align_turn over SurfAlignRule on the host against the reference's loop, by the bounds the device is held to"""
     c = cases.CASES[name]()
     ref, best = cases.reference(name)
     g = c["guesses"]
